@@ -15,8 +15,13 @@ interface-only form (every rank solves its own rows, two RCCL all-to-alls of 10 
 --exchange a2a: the transposed solve, --exchange gather: the reference's protocol - halo rank -> rank+1, all-gather of owned
 rows, redundant patch solve).
 
-Prints ONE JSON line on rank 0 with the driver's contract plus "roofline" (dominant kernel, live hipEvent timing) and
-"cpu_baseline" (the C oracle "port" on a bounded radial sample of the same workload, rank 0, N = 1 only).
+Prints ONE JSON line on rank 0 with the driver's contract. A plain run does only what `value` needs: set-up, warm-up, the K
+timed steps.  --full adds everything else the benchmark measures or checks: "roofline" and "kernels_roofline" (hipEvent timing
+of every kernel, a serial pass of its own), "native_equivalent", "deferred_diagnostic", "other_configs", "cpu_baseline" (the C
+oracle "port" on the same workload, rank 0, N = 1 only) and, for N > 1, the self-check of the two exchange implementations.
+--dump-outputs DIR writes what the timed model computed in its last timed step as DIR/<name>.npy (float64; a fixed, seeded
+sample of rows where an array is large, 64 MB in all): the inputs are the same from run to run, so that two builds can be
+compared output for output.
 """
 import argparse
 import json
@@ -62,6 +67,14 @@ PAR = dict(g=9.81, Kh=5000.0, Cd=2.4e-3, Hfree=2000.0, f=5.0e-5, Um=0.0, Vm=0.0)
 # 64-level Chebyshev column whose end spacing is 1.2 m. ts = 0.2 s ran 6000 steps without a NaN (0.25 s: 2000+; 0.5 s
 # blows up after 1600). Throughput does not depend on ts.
 TS = 0.2
+# Steps of the timed model right after it is built, before its W warm-up steps (every mode, so that the state after step
+# K + W is the same with or without --full): first-use costs of its streams, and the device out of idle - from an idle GPU the
+# first ~25 steps of any run are up to 18 % slow (profiles/r03/step_times_from_idle.txt), and with the driver's
+# `--warmup 5` the timed steps would otherwise sample that ramp.  Half a second of device time on the headline grid, about as
+# long as the native-ring run and the serial pass that --full runs before the timed steps.
+SETTLE_STEPS = 500
+DUMP_BYTES = 64 << 20         # --dump-outputs: all arrays together (every rank's)
+DUMP_SEED = 20240917          # the row sample of an array above its share of DUMP_BYTES
 
 
 def initial_condition(pts):
@@ -80,6 +93,34 @@ def grid_kwargs(workload):
     nc, L, nz = WORKLOADS[workload]
     return dict(geometry="RLZ", xmin=0.0, xmax=3.0e5, num_cells=nc, vars=VARS6, BCL=BCL6, BCR=BCR6, BCT=BCT6, zmin=0.0,
                 zmax=2000.0, zDim=nz), L
+
+
+def sample_rows(a, max_values):
+    """`a` itself if it holds at most max_values numbers, else the same fixed, seeded sample of its rows (in row order) on every run."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.size <= max_values:
+        return a
+    keep = max(1, max_values // max(1, a.size // a.shape[0]))
+    return a[np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], keep, replace=False))]
+
+
+def dump_outputs(run, out_dir, world, rank=0):
+    """What the caller of ModelRun.step() receives after the last timed step: the patch's A coefficients (the model state,
+    [s_patch, V]; with more than one rank written by rank 0) and each local tile's new values var_np1 [N, V]."""
+    arrays = {}
+    a = run.patch_spectral()          # with > 1 rank a collective: every rank calls it
+    if a is not None and rank == 0:
+        arrays["spectral_a"] = a
+    for t, g in zip(run.tile_ids, run.tiles):
+        arrays["var_np1" if world == 1 and len(run.tiles) == 1 else "var_np1_tile%d" % t] = g.var_np1
+    share = DUMP_BYTES // 8 // (max(world, len(run.tiles)) + 1)       # numbers per array: the patch plus one array per tile
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, arr in arrays.items():
+        arr = np.ascontiguousarray(sample_rows(arr, share))
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return shapes
 
 
 def cpu_baseline(workload, sample_cells, steps):
@@ -240,9 +281,11 @@ def load_pmc(S, workload):
     return pmc
 
 
-def time_other_config(S, torch, dev, name, steps, warmup, graph_replay=True):
-    """BASELINE.json config 2 / 3 on this GPU: `warmup` steps with an event pair around every kernel (the per-kernel table), then
-    `steps` timed steps with no event on the stream (ms_per_step).  Returns the dictionary reported under other_configs."""
+def time_other_config(S, torch, dev, name, steps, warmup, graph_replay=True, full=True, dump_dir=None):
+    """BASELINE.json config 2 / 3 on this GPU: `warmup` steps (full: with an event pair around every kernel, the per-kernel table),
+    then `steps` timed steps with no event on the stream (ms_per_step); full: then the same steps replayed from hipGraphs.
+    dump_dir: the timed model's outputs after its last timed step (dump_outputs).  Returns the dictionary reported under
+    other_configs (the roofline entries with full only)."""
     import bench_configs as BC
     case = getattr(BC, OTHER_WORKLOADS[name])()
     mp = BC.model_parameters(S, case)
@@ -253,12 +296,12 @@ def time_other_config(S, torch, dev, name, steps, warmup, graph_replay=True):
     for _ in range(20):                               # clocks, caches, first-launch costs
         run.step()
     torch.cuda.synchronize()
-    tile.enable_timers(True)
+    tile.enable_timers(full)
     tile.reset_timers()
     for _ in range(warmup):
         run.step()
     torch.cuda.synchronize()
-    tm = tile.timers()
+    tm = tile.timers() if full else {}
     tile.enable_timers(False)
     per_step = {k: v[0] / max(warmup, 1) for k, v in tm.items() if v[1] > 0}
     launches = {k: v[1] / max(warmup, 1) for k, v in tm.items() if v[1] > 0}
@@ -267,6 +310,23 @@ def time_other_config(S, torch, dev, name, steps, warmup, graph_replay=True):
         run.step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
+    nan = bool(tile.check_nan())
+    dumped = dump_outputs(run, dump_dir, 1) if dump_dir else None
+    d = tile.dims
+    # SURVEY.md 8(d)'s fixed byte model of a step: B_step = 8 V [N (2 D + 5) + 4 S]
+    b_step = 8.0 * d.n_vars * (d.n_points * (2 * d.n_derivs + 5) + 4 * d.s_patch)
+    out = {"workload": {"r_linear_advection_1d": "R grid, models/LinearAdvection1D.jl verbatim: 100 cells, PERIODIC, %d points, 1 var, 3 derivative slots, fp64" % d.n_points,
+                        "rl_cha_bell2024": "RL two-layer shallow-water slab, models/cha_bell2024/Oneway_ShallowWater_Slab.jl verbatim: 100 cells -> 300 native "
+                                           "ragged rings (4 + 4 ri points, kmax = ri), %d points x 6 vars, 5 derivative slots, fp64" % d.n_points,
+                        "rz_513x128_semi": "RZ %d x %d (radius x Chebyshev levels, b_zDim = zDim), 5 vars, LinearAcousticRZ + semi-implicit adjustment "
+                                           "(src/semiimplicit.jl:521-597), fp64" % (d.rDim, d.zDim)}[name],
+           "steps_per_s": 1.0 / dt, "ms_per_step": 1e3 * dt, "steps": steps, "nan": nan,
+           "survey_bytes_per_step": b_step, "survey_model_frac_of_hbm_peak": b_step / dt / 1e9 / HBM_PEAK_GBS}
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if not full:
+        run.close()
+        return out
     # the same steps replayed from hipGraphs (sx_step with SX_GRAPH=1: one graph launch per step; bit-identical fields)
     graph = None
     try:
@@ -292,21 +352,11 @@ def time_other_config(S, torch, dev, name, steps, warmup, graph_replay=True):
         graph = {"steps_per_s": None, "error": repr(e)[:200]}
     rows = kernel_table(tile, per_step, launches, load_pmc(S, name))
     dom = max(per_step.items(), key=lambda kv: kv[1])[0] if per_step else None
-    d = tile.dims
-    # SURVEY.md 8(d)'s fixed byte model of a step: B_step = 8 V [N (2 D + 5) + 4 S]
-    b_step = 8.0 * d.n_vars * (d.n_points * (2 * d.n_derivs + 5) + 4 * d.s_patch)
-    out = {"workload": {"r_linear_advection_1d": "R grid, models/LinearAdvection1D.jl verbatim: 100 cells, PERIODIC, %d points, 1 var, 3 derivative slots, fp64" % d.n_points,
-                        "rl_cha_bell2024": "RL two-layer shallow-water slab, models/cha_bell2024/Oneway_ShallowWater_Slab.jl verbatim: 100 cells -> 300 native "
-                                           "ragged rings (4 + 4 ri points, kmax = ri), %d points x 6 vars, 5 derivative slots, fp64" % d.n_points,
-                        "rz_513x128_semi": "RZ %d x %d (radius x Chebyshev levels, b_zDim = zDim), 5 vars, LinearAcousticRZ + semi-implicit adjustment "
-                                           "(src/semiimplicit.jl:521-597), fp64" % (d.rDim, d.zDim)}[name],
-           "steps_per_s": 1.0 / dt, "ms_per_step": 1e3 * dt, "steps": steps, "nan": bool(tile.check_nan()), "graph_replay": graph,
-           "survey_bytes_per_step": b_step, "survey_model_frac_of_hbm_peak": b_step / dt / 1e9 / HBM_PEAK_GBS,
-           "kernel_ms_per_step_sum": sum(per_step.values()),
-           "roofline": ({"bound": "hbm", "kernel": dom, "achieved": rows[dom]["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": rows[dom]["frac"], "traffic": rows[dom].get("pmc_bytes"), "avg_launch_ms": rows[dom]["ms_per_launch"],
-                         "algorithmic_bytes_per_launch": rows[dom]["algorithmic_bytes"]} if dom else None),
-           "kernels_roofline": rows}
+    out.update({"graph_replay": graph, "kernel_ms_per_step_sum": sum(per_step.values()),
+                "roofline": ({"bound": "hbm", "kernel": dom, "achieved": rows[dom]["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": rows[dom]["frac"], "traffic": rows[dom].get("pmc_bytes"), "avg_launch_ms": rows[dom]["ms_per_launch"],
+                              "algorithmic_bytes_per_launch": rows[dom]["algorithmic_bytes"]} if dom else None),
+                "kernels_roofline": rows})
     run.close()
     return out
 
@@ -344,7 +394,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-cells", type=int, default=0, help="0 = time the C port on the full grid (default); n > 0 = extrapolate from n cells")
     ap.add_argument("--cpu-steps", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: roofline and per-kernel tables, native_equivalent, "
+                         "deferred_diagnostic, other_configs, cpu_baseline, the N > 1 exchange self-check (the --no-* options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed model computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    full = args.full
 
     # dmabuf IPC for RCCL / cross-process device buffers; must be in the environment before the HIP runtime starts
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -369,13 +425,17 @@ def main():
         # configs 2 / 3 as the line's own workload (one GPU): value = that configuration's steps/s, labelled as not the headline
         if world != 1:
             raise SystemExit("bench.py: --workload %s is a one-GPU configuration" % args.workload)
-        r = time_other_config(S, torch, dev, args.workload, args.steps, max(args.warmup, 1), graph_replay=not args.no_graph_replay)
+        r = time_other_config(S, torch, dev, args.workload, args.steps, max(args.warmup, 1), graph_replay=not args.no_graph_replay,
+                              full=full, dump_dir=args.dump_outputs)
         out = {"metric": "model steps/sec, %s (BASELINE.json config, not the headline configuration)" % args.workload,
                "value": None if r["nan"] else r["steps_per_s"], "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
                "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64",
                "data": "synthetic", "config": {"workload": r["workload"], "nan": r["nan"], "survey_bytes_per_step": r["survey_bytes_per_step"],
-                                                 "survey_model_frac_of_hbm_peak": r["survey_model_frac_of_hbm_peak"]},
-               "roofline": r["roofline"], "kernels_roofline": r["kernels_roofline"]}
+                                                 "survey_model_frac_of_hbm_peak": r["survey_model_frac_of_hbm_peak"]}}
+        if full:
+            out.update({"roofline": r["roofline"], "kernels_roofline": r["kernels_roofline"]})
+        if "dumped_outputs" in r:
+            out["dumped_outputs"] = r["dumped_outputs"]
         print(json.dumps(out), flush=True)
         raise SystemExit(3 if r["nan"] else 0)
 
@@ -420,6 +480,8 @@ def main():
                 os.environ.pop("SX_OVERLAP", None)
         return r
 
+    two_streams = world == 1 and args.schedule == "overlap" and args.storage == "f64"
+    run = None
     if world > 1 and impl == "lib":
         # LibExchange itself makes the ranks agree before its first collective (probe on every rank -> all_gather of the
         # outcome -> unique-id broadcast -> ncclCommInitRank), so it raises on EVERY rank or on none and all ranks take the same
@@ -433,7 +495,7 @@ def main():
             print("bench.py: in-library exchange unavailable (%s), using torch.distributed" % err, file=sys.stderr)
             impl = "torch (lib failed: %s)" % err
             run = make_run("torch")
-        if impl == "lib" and not args.no_selfcheck:
+        if impl == "lib" and full and not args.no_selfcheck:
             # both implementations of the exchange, two steps each from the same initial condition: same fields.  One after
             # the other with a device-wide wait in between: the library's communicator and torch's are never in flight at
             # the same time (two communicators whose kernels meet in different orders on different ranks can deadlock)
@@ -458,22 +520,25 @@ def main():
             torch.cuda.synchronize()
             dist.barrier()
             preheat = other
-    else:
+    elif full or not two_streams:
         run = make_run(impl if world > 1 else "torch")
-    tile = run.tiles[0]
+    tile = run.tiles[0] if run is not None else None
     headline = (world == 1 and args.workload == "rlz_513x256x64")
     # N = 1 headline: the SAME work on two streams (SX_OVERLAP=1: inner-ring chain k_rl_inverse -> k_phys_hrbl_inner beside
     # k_node_fft -> k_phys_hrbl; bit-identical fields, tests/test_gpu_configs.py::test_config4_full_size_two_stream_modes_are_bit_identical) is the faster schedule and
     # what `value` is timed with; the dominant kernel then shares the chip, so its event-timed duration (the roofline measurement) comes
-    # from a serial pass of the same K steps on `run`, after the timed region.  --schedule serial times `value` on `run` itself.
-    run_ov = None
-    if world == 1 and args.schedule == "overlap" and args.storage == "f64":
-        run_ov = make_run("torch", overlap=True)
-        # first-use costs of the second stream (its creation, the fork / join events, the first launches behind them: 200 us of host
-        # time per step over the first steps, profiles/r04/overlap_steps.txt) are set-up, not throughput: 10 steps here, before anything is timed
-        for _ in range(10):
-            run_ov.step()
-        torch.cuda.synchronize()
+    # from a serial pass of the same K steps on `run` (--full only, before the timed region; a plain run does not build `run`).
+    # --schedule serial times `value` on `run` itself.
+    run_ov = make_run("torch", overlap=True) if two_streams else None
+    timed = run_ov if run_ov is not None else run
+    # first-use costs of the second stream (its creation, the fork / join events, the first launches behind them: 200 us of host
+    # time per step over the first steps, profiles/r04/overlap_steps.txt) are set-up, not throughput, and so is the device's way out
+    # of idle: SETTLE_STEPS steps of the timed model, before anything is timed
+    for _ in range(SETTLE_STEPS):
+        timed.step()
+    torch.cuda.synchronize()
+    if dist is not None:
+        dist.barrier()
 
     # The same model on Springsteel's NATIVE ragged rings (SURVEY.md 8(d) "native-equivalent shape": 85 cells -> 255 rings of
     # 4 + 4 ri points, 131,580 horizontal points x 64 levels): the layout a drop-in must run; its azimuthal transforms are dense
@@ -486,7 +551,7 @@ def main():
     # After this run the GPU is in its working state
     # when the W warm-up steps begin.  `--no-native` skips it.
     native, runn = None, None
-    if headline and rank == 0 and not args.no_native:
+    if headline and rank == 0 and full and not args.no_native:
         try:
             kwn, _ = grid_kwargs(args.workload)
             kwn["num_cells"] = 85
@@ -518,29 +583,37 @@ def main():
     # Warm-up of `run` (serial schedule), with every kernel timed (rank 0): finds the dominant kernel and gives the per-kernel table.
     # An event pair costs ~4 us on the stream, 16 pairs per step were 6 % of the step - so a TIMED region carries the pair of the
     # dominant kernel only (the roofline object needs that one, measured live over K steps), or none at all (the overlapped schedule).
-    use_timers = (rank == 0 and not args.no_kernel_timers)
-    tile.enable_timers(use_timers)
-    tile.reset_timers()
-    for _ in range(args.warmup):
-        run.step()
-    barrier()
-    warm = tile.timers() if use_timers else {}
-    all_kernels = {k: v[0] / max(args.warmup, 1) for k, v in warm.items() if v[1] > 0}
-    launches = {k: v[1] / max(args.warmup, 1) for k, v in warm.items() if v[1] > 0}
-    dominant = max(all_kernels.items(), key=lambda kv: kv[1])[0] if all_kernels and args.warmup > 0 else None
-    tile.timer_only(dominant)
-    tile.reset_timers()
+    # A plain run: the W warm-up steps on the timed model, no event anywhere.
+    all_kernels, launches = {}, {}
+    if full:
+        use_timers = (rank == 0 and not args.no_kernel_timers)
+        tile.enable_timers(use_timers)
+        tile.reset_timers()
+        for _ in range(args.warmup):
+            run.step()
+        barrier()
+        warm = tile.timers() if use_timers else {}
+        all_kernels = {k: v[0] / max(args.warmup, 1) for k, v in warm.items() if v[1] > 0}
+        launches = {k: v[1] / max(args.warmup, 1) for k, v in warm.items() if v[1] > 0}
+        dominant = max(all_kernels.items(), key=lambda kv: kv[1])[0] if all_kernels and args.warmup > 0 else None
+        tile.timer_only(dominant)
+        tile.reset_timers()
+    elif run_ov is None:
+        for _ in range(args.warmup):
+            run.step()
+        barrier()
 
     serial = None
     if run_ov is not None:
-        # ---- the serial pass FIRST: K steps on one stream with the dominant kernel's event pair -> roofline (and the device stays busy)
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            run.step()
-        barrier()
-        el_serial = time.perf_counter() - t0
-        serial = {"steps_per_s": args.steps / el_serial, "ms_per_step": 1e3 * el_serial / args.steps, "steps": args.steps,
-                  "note": "one stream, the dominant kernel's hipEvent pair on it: the pass `roofline` is measured in (it runs before the timed region)"}
+        if full:
+            # ---- the serial pass FIRST: K steps on one stream with the dominant kernel's event pair -> roofline (and the device stays busy)
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                run.step()
+            barrier()
+            el_serial = time.perf_counter() - t0
+            serial = {"steps_per_s": args.steps / el_serial, "ms_per_step": 1e3 * el_serial / args.steps, "steps": args.steps,
+                      "note": "one stream, the dominant kernel's hipEvent pair on it: the pass `roofline` is measured in (it runs before the timed region)"}
         # ---- THE timed region: W warm-up steps, then exactly K steps of the two-stream schedule, no event on any stream
         for _ in range(args.warmup):
             run_ov.step()
@@ -550,7 +623,7 @@ def main():
             run_ov.step()
         barrier()
         elapsed = time.perf_counter() - t0
-        nan = bool(run_ov.tiles[0].check_nan()) or bool(tile.check_nan())
+        nan = bool(run_ov.tiles[0].check_nan()) or (run is not None and bool(tile.check_nan()))
     else:
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -558,15 +631,17 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         nan = tile.check_nan()
-    timers = {k: v for k, v in tile.timers().items() if v[1] > 0}
+    dumped = dump_outputs(timed, args.dump_outputs, world, rank) if args.dump_outputs else None
+    timers = {k: v for k, v in tile.timers().items() if v[1] > 0} if full else {}
     if runn is not None:
         runn.close()
     if preheat is not None:
         preheat.close()
     if run_ov is not None:
         run_ov.close()
-    tile.enable_timers(False)
-    tile.timer_only(None)
+    if full:
+        tile.enable_timers(False)
+        tile.timer_only(None)
 
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.backend == "nccl" else "cpu")
@@ -575,21 +650,11 @@ def main():
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        # dominant kernel by accumulated device time
-        if not timers:                      # --no-kernel-timers (diagnostic)
-            timers = {"none": (0.0, 0)}
-        name, (ms, calls) = max(timers.items(), key=lambda kv: kv[1][0])
-        avg_ms = ms / max(calls, 1)
-        bytes_per_launch = tile.kernel_bytes(name) if calls else 0.0
-        achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
         nc, _, nz = WORKLOADS[args.workload]
-        pmc = load_pmc(S, args.workload) if (world == 1 and args.storage == "f64") else None
-        traffic = pmc.get(name, {}).get("hbm_bytes") if pmc else None
-        step_traffic = sum(pmc[k]["hbm_bytes"] * launches.get(k, 0.0) for k in all_kernels if k in pmc) if pmc else None
-        rows = kernel_table(tile, all_kernels, launches, pmc) if all_kernels else {}
-        if name in rows:                    # the dominant kernel's row from the timed pass (K steps), not from the warm-up
-            rows[name].update({"ms_per_launch": avg_ms, "achieved_GBs": achieved, "frac": achieved / HBM_PEAK_GBS,
-                               "pmc_GBs": (traffic / (avg_ms * 1e-3) / 1e9) if traffic and avg_ms > 0 else None, "timed_over": "%d steps" % args.steps})
+        # what ran on the device right before the W warm-up steps (from an idle GPU the first ~25 steps of any run are
+        # up to 18 % slow)
+        busy = (["self-check's torch.distributed run, 100 steps"] if preheat is not None else []) + ["%d steps of the timed model" % SETTLE_STEPS]
+        busy += (["native_equivalent run"] if native is not None else []) + (["the serial roofline pass"] if serial is not None else [])
         out = {
             "metric": ("model steps/sec, RLZ 512x256x64 shallow-water" if args.workload == "rlz_513x256x64"
                        else "model steps/sec, %s shallow-water (not the headline configuration)" % args.workload),
@@ -607,37 +672,53 @@ def main():
             "data": "synthetic",
             "config": {"workload": "RLZ %dx%dx%d (rings x azimuth x levels), 6 vars, 7 derivative slots, "
                                    "Oneway_ShallowWater_HeightResolvedBL, uniform ring table kmax<=%d, b_zDim %d"
-                                   % (3 * nc, L, nz, L // 2 - 1, int(tile.dims.b_zDim)),
-                       "num_cells": nc, "tiles": world, "tile_cells": list(run.layout.ncells), "exchange": run.exchange_kind,
+                                   % (3 * nc, L, nz, L // 2 - 1, int(timed.tiles[0].dims.b_zDim)),
+                       "num_cells": nc, "tiles": world, "tile_cells": list(timed.layout.ncells), "exchange": timed.exchange_kind,
                        "exchange_impl": (impl if world > 1 else "none"), "exchange_selfcheck_max_rel_diff": selfcheck,
                        "schedule": ("two streams (SX_OVERLAP=1): the inner-ring chain beside the node-space chain; the same kernels, "
                                     "bit-identical fields" if run_ov is not None else "one stream"),
-                       # what ran on the device right before the W warm-up steps (from an idle GPU the first ~25 steps of
-                       # any run are up to 18 % slow)
-                       "device_busy_before_warmup": ("native_equivalent run, then the serial roofline pass" if (native is not None and serial is not None) else "native_equivalent run" if native is not None else
-                                                     "self-check's torch.distributed run, 100 steps" if preheat is not None else "nothing (cold start)"),
+                       "device_busy_before_warmup": ", then ".join(busy),
                        "ts": TS_OF.get(args.workload, TS), "nan": bool(nan),
                        "parity": PARITY_CLAIM if args.storage == "f64" else "declared tolerance of the fp32-storage mode: values 1e-6, derivative slots 5e-5 (DESIGN.md 3)"},
-            "roofline": {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                         "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "measured_in": ("the serial pass (serial_schedule), %d steps, run right before the timed region" % args.steps if serial is not None else "the timed region"),
-                         "achievable_peak": HBM_ACHIEVABLE_GBS, "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
-                         # whole step: PMC bytes of every kernel of a step / step time (null without matching PMC passes)
-                         "step_traffic": step_traffic,
-                         "step_achieved": (step_traffic / (ms_per_step * 1e-3) / 1e9) if step_traffic else None,
-                         "step_frac": (step_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS) if step_traffic else None},
-            # every kernel of a step: algorithmic bytes, PMC bytes (matching build only), launch time, fraction of the HBM peak - from the
-            # warm-up steps of the serial schedule (all event pairs on); the dominant kernel's row from its K timed steps
-            "kernels_roofline": rows,
-            "kernels_ms_per_step": {k: v for k, v in sorted(all_kernels.items())},
-            "dominant_kernel_ms_timed_region": {k: v[0] / args.steps for k, v in sorted(timers.items())},
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if full:
+            # dominant kernel by accumulated device time
+            if not timers:                      # --no-kernel-timers (diagnostic)
+                timers = {"none": (0.0, 0)}
+            name, (ms, calls) = max(timers.items(), key=lambda kv: kv[1][0])
+            avg_ms = ms / max(calls, 1)
+            bytes_per_launch = tile.kernel_bytes(name) if calls else 0.0
+            achieved = bytes_per_launch / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            pmc = load_pmc(S, args.workload) if (world == 1 and args.storage == "f64") else None
+            traffic = pmc.get(name, {}).get("hbm_bytes") if pmc else None
+            step_traffic = sum(pmc[k]["hbm_bytes"] * launches.get(k, 0.0) for k in all_kernels if k in pmc) if pmc else None
+            rows = kernel_table(tile, all_kernels, launches, pmc) if all_kernels else {}
+            if name in rows:                    # the dominant kernel's row from the timed pass (K steps), not from the warm-up
+                rows[name].update({"ms_per_launch": avg_ms, "achieved_GBs": achieved, "frac": achieved / HBM_PEAK_GBS,
+                                   "pmc_GBs": (traffic / (avg_ms * 1e-3) / 1e9) if traffic and avg_ms > 0 else None, "timed_over": "%d steps" % args.steps})
+            out.update({
+                "roofline": {"bound": "hbm", "kernel": name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                             "avg_launch_ms": avg_ms, "algorithmic_bytes_per_launch": bytes_per_launch,
+                             "measured_in": ("the serial pass (serial_schedule), %d steps, run right before the timed region" % args.steps if serial is not None else "the timed region"),
+                             "achievable_peak": HBM_ACHIEVABLE_GBS, "frac_of_achievable": achieved / HBM_ACHIEVABLE_GBS,
+                             # whole step: PMC bytes of every kernel of a step / step time (null without matching PMC passes)
+                             "step_traffic": step_traffic,
+                             "step_achieved": (step_traffic / (ms_per_step * 1e-3) / 1e9) if step_traffic else None,
+                             "step_frac": (step_traffic / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS) if step_traffic else None},
+                # every kernel of a step: algorithmic bytes, PMC bytes (matching build only), launch time, fraction of the HBM peak - from the
+                # warm-up steps of the serial schedule (all event pairs on); the dominant kernel's row from its K timed steps
+                "kernels_roofline": rows,
+                "kernels_ms_per_step": {k: v for k, v in sorted(all_kernels.items())},
+                "dominant_kernel_ms_timed_region": {k: v[0] / args.steps for k, v in sorted(timers.items())},
+            })
         if serial is not None:
             out["serial_schedule"] = serial
         if native is not None:
             out["native_equivalent"] = native
-        if headline and not args.no_native and not nan:
+        if headline and full and not args.no_native and not nan:
             # NOT the headline: the same model with SX_DEFER_DIAG=1 - the diagnostic variable w (written by the equation set
             # before it is read, so its spline coefficients are consumed by output only) skips the forward transform and the
             # solve inside the step and is brought up to date when something reads A or B; every observable is bit-identical
@@ -663,7 +744,7 @@ def main():
             except Exception as e:
                 os.environ.pop("SX_DEFER_DIAG", None)
                 out["deferred_diagnostic"] = {"steps_per_s": None, "error": repr(e)[:200]}
-        if headline and not args.no_other_configs:
+        if headline and full and not args.no_other_configs:
             # BASELINE.json configs 2 and 3 ("1 MI355X" configurations; parity: tests/test_gpu_configs.py) - reported, never `value`
             out["other_configs"] = {}
             for oname in sorted(OTHER_WORKLOADS):
@@ -671,7 +752,7 @@ def main():
                     out["other_configs"][oname] = time_other_config(S, torch, dev, oname, 200 if args.steps >= 20 else max(5, args.steps), 20)
                 except Exception as e:
                     out["other_configs"][oname] = {"steps_per_s": None, "error": repr(e)[:200]}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_sample_cells, args.cpu_steps)
             except Exception as e:   # the baseline is a reported side figure; never lose the GPU line over it
@@ -686,7 +767,8 @@ def main():
                 "; " + out["error"] if "error" in out else "")
             nan = True
         print(json.dumps(out), flush=True)
-    run.close()
+    if run is not None:
+        run.close()
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

@@ -5,7 +5,7 @@ set -e
 ROUND=${1:-r02}
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof/$ROUND; mkdir -p $OUT
 export TMPDIR=/tmp
-BENCH="python3 $ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-native --no-kernel-timers"
+BENCH="python3 $ROOT/bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-native --no-kernel-timers"
 NAT="python3 $ROOT/profiles/native_timers.py 5"
 cd /tmp
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d $OUT/sq1 -o sq1 -- $BENCH > /dev/null 2> $OUT/sq1.log

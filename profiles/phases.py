@@ -1,6 +1,6 @@
 """Summarise the in-kernel phase stamps of the diagnostic build (make -C scythe.jl_amd/csrc phases):
-   SCYTHE_HIP_LIB=profiles/libscythe_hip_phases.so SX_PHASES_OUT=gpurun_out/phases.bin python bench.py --steps 5 --warmup 2 --no-cpu-baseline
-   python profiles/phases.py gpurun_out/phases.bin
+   SCYTHE_HIP_LIB=profiles/libscythe_hip_phases.so SX_PHASES_OUT=phases.bin python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
+   python profiles/phases.py phases.bin
 Stamps per workgroup of k_phys_hrbl_cell (s_memtime, shader cycles): 0 entry, 1 first-phase values in LDS (first 20 node loads
 arrived), 2 before the MFMA phase, 3 after it, 4 results visible, 5/6/7 ring 0/1/2 finished (stores issued)."""
 import sys

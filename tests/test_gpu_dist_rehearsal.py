@@ -111,7 +111,7 @@ def test_bench_cli_two_ranks_on_one_device():
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--workload", "rlz_small", "--backend", "gloo", "--one-device"]
+           "--workload", "rlz_small", "--backend", "gloo", "--one-device", "--full"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -186,7 +186,7 @@ def test_bench_cli_two_ranks_rccl():
     for exchange in ("iface", "a2a", "gather"):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-               "--workload", "rlz_small", "--exchange", exchange]
+               "--workload", "rlz_small", "--exchange", exchange, "--full"]
         out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
         assert out.returncode == 0, out.stderr[-2000:]
         d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -282,7 +282,7 @@ def test_bench_cli_two_ranks_in_library_exchange_through_the_stand_in_transport(
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SX_RCCL_LIB"] = lib
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "rlz_small",
-           "--backend", "gloo", "--one-device", "--exchange-impl", "lib"]
+           "--backend", "gloo", "--one-device", "--exchange-impl", "lib", "--full"]
     out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
