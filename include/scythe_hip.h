@@ -209,7 +209,9 @@ int sx_advance(sx_handle *h, int32_t t);
  * step's kernel launches are captured into a hipGraph - once per rotation of the tendency-history buffers, from the third step
  * this handle executes (Adams-Bashforth-3: the launch arguments then repeat with period 3) - and replayed: ONE graph launch per
  * step instead of 5-9 kernel launches, for grids whose step is shorter than the host takes to enqueue it (R, RZ and small RL
- * grids).  Bit-identical to the plain launches; timers on, or a failed capture, fall back to them. */
+ * grids).  Bit-identical to the plain launches; timers on, or a failed capture, fall back to them.  The captured graphs hold the
+ * stream and the B buffers' pointers: sx_set_stream (to another stream), sx_bind_tile_b (to another buffer) and sx_bind_patch_b drop
+ * them, and the next sx_step captures again. */
 int sx_step(sx_handle *h, int32_t t);
 /* physical_model only (src/semiimplicit.jl:357-363) on the current tile.physical */
 int sx_physics(sx_handle *h, int32_t t);

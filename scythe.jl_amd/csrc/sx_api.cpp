@@ -1010,6 +1010,10 @@ int sx_advance(sx_handle *h, int32_t t) {
 
 namespace sx {
 void graphs_release(sx_handle *h) {
+    bool any = false;
+    for (auto g : h->graph_exec) any = any || g;
+    if (!any) return;
+    hipStreamSynchronize(h->stream ? h->stream : h->graph_stream);      // a replay may still be in flight
     for (auto &g : h->graph_exec) {
         if (g) hipGraphExecDestroy(g);
         g = nullptr;
@@ -1117,7 +1121,9 @@ int sx_tile_b_device(sx_handle *h, void **p, int64_t *rows, int64_t *cols) {
 int sx_bind_tile_b(sx_handle *h, void *p) {
     clear_error();
     if (!h) { set_error("null handle"); return 1; }
-    h->d_Btile = p ? (double *)p : (h->d_Btile_own ? h->d_Btile_own : h->d_Bfull);
+    double *nb = p ? (double *)p : (h->d_Btile_own ? h->d_Btile_own : h->d_Bfull);
+    if (nb != h->d_Btile) graphs_release(h);      // the captured launches write the old buffer
+    h->d_Btile = nb;
     return 0;
 }
 
@@ -1131,6 +1137,7 @@ int sx_halo_add(sx_handle *h, const void *recv) {
 int sx_bind_patch_b(sx_handle *h, const void *base, const int64_t *rowoff) {
     clear_error();
     if (!h) { set_error("null handle"); return 1; }
+    graphs_release(h);          // the captured solve reads the old source (and its contiguity decides the kernel)
     std::vector<int64_t> ro(h->b_rDim);
     if (base && rowoff) {
         for (int m = 0; m < h->b_rDim; m++) ro[m] = rowoff[m];

@@ -14,7 +14,8 @@
 //   4. a = Gamma^T x          written to the A rows (and, transposed solve, to the second tile that shares the row)
 // Same interface as k_solve: row m of the right-hand side is Bsrc[boffA[m] + col] (+ Bsrc[boffB[m] + col]), row m of the solution
 // goes to A[aoffA[m] + col] (and A[aoffB[m] + col]); LINEAR: m * stride + col on both sides.
-// Results agree with the Cholesky solve to rounding (tests/test_pcr_tables.py on the host, tests/test_gpu_parity.py on the device).
+// Results agree with the Cholesky solve to rounding (tests/test_pcr_tables.py on the host, tests/test_gpu_solve.py on the device at
+// every launch geometry).
 #include "sx_internal.hpp"
 #include <cstdlib>
 #include <map>
@@ -143,8 +144,8 @@ k_solve_pcr(const double *__restrict__ Bsrc, const int64_t *__restrict__ boffA, 
     double *x = nxt;
     if (cd.periodic) {
         // corner blocks of the cyclic matrix: x -= G (E^T x) over the edge unknowns 0, 1, 2, n-3, n-2, n-1
-        if (tid < 6 * R) {
-            const int c = tid & (R - 1), q = tid >> logR;
+        for (int e = tid; e < 6 * R; e += nt) {          // 6R can exceed blockDim (R = 16, classes of 7-12 unknowns: 64 threads)
+            const int c = e & (R - 1), q = e >> logR;
             ye[q * R + c] = x[(q < 3 ? q : cd.n - 6 + q) * R + c];
         }
         __syncthreads();

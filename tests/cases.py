@@ -276,6 +276,64 @@ def rel_err_per_var(a, b):
     return worst
 
 
+# ----------------------------------------------------------------------------- splineTransform! (B -> A) references
+def spline_columns(x, b_rDim):
+    """[s_patch, V] patch array (reference layout: s = (z-mode * n_blocks + block) * b_rDim + node) -> [columns, b_rDim]:
+    one row per (variable, z-mode, wavenumber block) right-hand side of the radial solve."""
+    x = np.asarray(x)
+    return np.transpose(x.reshape(b_rDim, -1, x.shape[1], order="F"), (2, 1, 0)).reshape(-1, b_rDim)
+
+
+def rel_err_per_column(a, b, b_rDim):
+    """Per spectral column of a [s_patch, V] patch array: max|a - b| over the column / max|b| over the same column.
+    A column of b that is exactly zero demands an exactly zero column of a."""
+    ca, cb = spline_columns(a, b_rDim), spline_columns(b, b_rDim)
+    diff, sc = np.abs(ca - cb).max(axis=1), np.abs(cb).max(axis=1)
+    return np.where(sc > 0, diff / np.where(sc > 0, sc, 1.0), np.where(diff > 0, np.inf, 0.0))
+
+
+def dense_spline_transform(case, shared):
+    """oracle_np.Grid.spline_transform (Spline1D.SA: the dense Cholesky factor of Gamma (P + eps_q Q) Gamma^T) with each
+    boundary-condition class factored once and all its columns solved in one call - for grids with 10^4 - 10^5 columns."""
+    g = oracle_grid(case)
+    shared = np.asarray(shared)
+    A = np.zeros_like(shared)
+    nb = g.b_rDim
+    for vi, v in enumerate(g.names):
+        X = shared[:, vi].reshape(g.b_zDim, g.K2, nb)            # [z-mode, block, node]
+        Y = np.zeros_like(X)
+        for blocks in (slice(0, 1), slice(1, g.K2)):
+            if blocks.start >= g.K2:
+                continue
+            spl = g.var_spline(v, blocks.start)
+            rhs = X[:, blocks, :].reshape(-1, nb).T                  # [node, columns]
+            y = np.linalg.solve(spl.cho, spl.G @ rhs)
+            Y[:, blocks, :] = (spl.G.T @ np.linalg.solve(spl.cho.T, y)).T.reshape(g.b_zDim, -1, nb)
+        A[:, vi] = Y.reshape(-1)
+    return A
+
+
+def pcr_launch_geometry(case, ngroups=None, r_force=0):
+    """What launch_solve_pcr (scythe.jl_amd/csrc/sx_pcr.hip) picks for one launch over `ngroups` (variable, z-mode) groups
+    (default: the whole patch): R columns per workgroup, threads per workgroup, the column count of the last workgroup of the
+    k = 0 run of a variable and of a group's k >= 1 run (== R: no partial segment), and whether the tables exist at all
+    (nblk_max <= 1024; else the launch falls back to k_solve).  r_force: SX_PCR_R."""
+    g = oracle_grid(case)
+    nfree = {O.gamma_matrix(g.nc, bl, g.BCR[v]).shape[0] for v in g.names for bl in (g.BCL_k0[v], g.BCL[v])}
+    nblk = max((n + 2) // 3 for n in nfree)
+    K2 = 2 * (g.kDim + 1) if g.has_l else 1          # the handle's block count (block 1 unused)
+    ng = g.V * g.b_zDim if ngroups is None else ngroups
+    total = ng * (K2 - 1 if K2 > 1 else 1)
+    R = r_force if r_force > 0 else 4 if total <= 4096 else 8 if total <= 16384 else 16
+    while R > 1 and nblk * R > 1024:
+        R //= 2
+    R = 1 << (R.bit_length() - 1)
+    threads = min(1024, -(-max(nblk * R, -(-g.b_rDim * R // 4)) // 64) * 64)
+    last = lambda n: n - (n - 1) // R * R
+    return dict(R=R, threads=threads, columns=total, nblk=nblk, tail_k0=last(g.b_zDim),
+                tail_k=last(K2 - 2) if K2 > 2 else None, tables=nblk <= 1024)
+
+
 # ----------------------------------------------------------------------------- BASELINE.json configs at full size
 from bench_configs import config2_literal     # noqa: E402,F401  (one definition for bench.py and the tests)
 

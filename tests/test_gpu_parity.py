@@ -405,6 +405,57 @@ def test_step_replayed_from_a_hip_graph_is_bit_identical(monkeypatch, maker, kw,
     assert np.array_equal(plain.run.tiles[0].var_np1, graph.run.tiles[0].var_np1)
 
 
+@pytest.mark.parametrize("maker,kw", [(cases.r_bcs, {"bcl": "R1T0", "bcr": "R1T1"}), (cases.rz_semiimplicit, {"num_cells": 9, "zDim": 16}),
+                                      (cases.rlz_hrbl, {"num_cells": 8, "zDim": 32, "ring_L": 32})])
+def test_step_graph_after_rebinding_the_b_buffers_is_bit_identical(monkeypatch, maker, kw):
+    """sx_bind_tile_b / sx_bind_patch_b between graph replays (what a host that owns its B buffers does): the captured launches
+    hold the old pointers, so the binds must drop the graphs.  Plain and SX_GRAPH=1 handles step through the same sequence -
+    6 steps (three captures, one replay), B rows bound to a caller buffer X, then the patch source bound to X as well, then both
+    back to the handle's own buffers, 4 steps each - and after every phase var_np1, patchSpectral and X are bit-identical.
+    Every buffer ever bound stays alive until both handles are gone."""
+    import torch
+    case = maker(**kw)
+    plain = cases.HipModel(case)
+    monkeypatch.setenv("SX_GRAPH", "1")
+    graph = cases.HipModel(case)
+    monkeypatch.delenv("SX_GRAPH")
+    runs = (plain, graph)
+    tiles = [r.run.tiles[0] for r in runs]
+    _, rows, ncols = tiles[0].tile_b_device()
+    assert rows == int(tiles[0].dims.b_rDim)
+    bufs = [torch.zeros((rows, ncols), dtype=torch.float64, device="cuda") for _ in runs]
+    rowoff = np.arange(rows, dtype=np.int64) * ncols
+
+    def phase(name, nsteps):
+        for _ in range(nsteps):
+            for r in runs:
+                r.step()
+        for g in tiles:
+            g.synchronize()
+        torch.cuda.synchronize()
+        fa, fb = tiles[0].var_np1, tiles[1].var_np1
+        assert np.isfinite(fa).all(), name
+        assert np.array_equal(fa, fb), name + ": var_np1"
+        assert np.array_equal(tiles[0].patchSpectral, tiles[1].patchSpectral), name + ": patchSpectral"
+        assert torch.equal(bufs[0], bufs[1]), name + ": bound B buffer"
+
+    phase("before any bind", 6)
+    for g, x in zip(tiles, bufs):
+        g.bind_tile_b(x.data_ptr())
+    phase("tile B bound", 4)
+    assert bufs[0].abs().max().item() > 0
+    for g, x in zip(tiles, bufs):
+        g.bind_patch_b(x.data_ptr(), rowoff)
+    phase("tile and patch B bound", 4)
+    for g in tiles:
+        g.bind_tile_b(0)
+        g.bind_patch_b(0, rowoff)
+    phase("own buffers again", 4)
+    for r in runs:
+        r.run.close()
+    del bufs
+
+
 def test_step_graph_on_a_user_stream_and_restart(monkeypatch, tmp_path):
     """The capture on a non-default stream (the caller's torch stream), and a run restarted from a checkpoint at t >= 3: its first two
     steps are plain launches (lazily created state must exist before a capture), then it captures - bit-identical to the plain run."""
