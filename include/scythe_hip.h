@@ -50,12 +50,16 @@ enum {
                                         with a linearised pressure-gradient force */
     SX_EQ_EULER_TEST = 8,            /* src/testModels.jl:100-215: moist Euler RZ (s, xi, mu, u, w) about a reference state,
                                         semi-implicit in the vertical acoustic terms; needs sx_model_desc.ref_state */
+    SX_EQ_LINEAR_SW_1D = 9,          /* src/shallowWaterModels.jl:235-259: LinearShallowWater1D (h, u) on an R grid */
+    SX_EQ_LINEAR_SW_RL = 10,         /* src/shallowWaterModels.jl:261-298: LinearShallowWaterRL (h, u, v) on an RL grid */
     SX_EQ_NONE = 99                  /* transforms only: sx_advance copies physical[:, :, 1] into var_np1 */
 };
 
-/* physical_params, fixed positions (model.physical_params Dict, models/ *.jl) */
+/* physical_params, fixed positions (model.physical_params Dict, models/ *.jl).  SX_P_H (:H, the mean depth of the linear
+ * shallow-water sets, src/shallowWaterModels.jl:244, 272) came after the first 12 without an ABI version change: see
+ * sx_model_desc.params. */
 enum { SX_P_G = 0, SX_P_K, SX_P_CD, SX_P_HFREE, SX_P_HB, SX_P_F, SX_P_S1, SX_P_C0, SX_P_KH, SX_P_UM, SX_P_VM,
-       SX_P_PXI_BAR, SX_NPARAMS };
+       SX_P_PXI_BAR, SX_P_H, SX_NPARAMS };
 
 /* GridParameters flattened (src/spectralGrid.jl:20-45; tile construction src/semiimplicit.jl:155-169).
  * The patch fields describe the whole domain; the tile fields select this handle's radial range. */
@@ -96,7 +100,9 @@ typedef struct sx_model_desc {
     double ts;
     int32_t equation_set;     /* SX_EQ_* */
     int32_t semiimplicit;     /* options[:semiimplicit] */
-    const double *params;     /* [SX_NPARAMS] */
+    const double *params;     /* [SX_NPARAMS]; only the first 12 (up to SX_P_PXI_BAR) are read unless equation_set is
+                                 SX_EQ_LINEAR_SW_1D or SX_EQ_LINEAR_SW_RL, which also read params[SX_P_H]: a caller built
+                                 against the 12-entry table (before SX_P_H) never has a 13th double read */
     int32_t w_index, xi_index;/* 1-based variable indices of "w" and "xi" (semi-implicit only), 0 = absent */
     int32_t col_var;          /* 1-based variable whose vertical BCs the column operators of HRBL use ("h",
                                  src/shallowWaterModels.jl:423), 0 = variable 1 */

@@ -36,7 +36,7 @@ struct SxModelDesc                          # mirrors sx_model_desc
 end
 
 const SX_GEOM = Dict("R" => 0, "RZ" => 1, "RL" => 2, "RLZ" => 3)
-const SX_PARAMS = (:g, :K, :Cd, :Hfree, :Hb, :f, :S1, :c_0, :Kh, :Um, :Vm, :Pxi_bar)
+const SX_PARAMS = (:g, :K, :Cd, :Hfree, :Hb, :f, :S1, :c_0, :Kh, :Um, :Vm, :Pxi_bar, :H)
 
 function sx_bc(d::Dict)                     # CubicBSpline.* / Chebyshev.* Dict tag -> SX_BC_* code
     d == CubicBSpline.R0 && return Int32(0);  d == CubicBSpline.R1T0 && return Int32(1)

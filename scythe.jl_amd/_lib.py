@@ -10,7 +10,7 @@ LIB_PATH = os.environ.get("SCYTHE_HIP_LIB") or os.path.join(_HERE, "libscythe_hi
 SX_ABI_VERSION = 2
 GEOM = {"R": 0, "RZ": 1, "RL": 2, "RLZ": 3}
 BC = {"R0": 0, "R1T0": 1, "R1T1": 2, "R1T2": 3, "R2T10": 4, "R2T20": 5, "R3": 6, "PERIODIC": 7}
-PARAM_ORDER = ["g", "K", "Cd", "Hfree", "Hb", "f", "S1", "c_0", "Kh", "Um", "Vm", "Pxi_bar"]
+PARAM_ORDER = ["g", "K", "Cd", "Hfree", "Hb", "f", "S1", "c_0", "Kh", "Um", "Vm", "Pxi_bar", "H"]
 
 P_I32 = C.POINTER(C.c_int32)
 P_I64 = C.POINTER(C.c_int64)

@@ -164,6 +164,8 @@ int sx_equation_set_id(const char *name) {
         {"Oneway_ShallowWater_HeightResolvedBL", SX_EQ_ONEWAY_SW_HRBL},
         {"LinearAcousticRZ", SX_EQ_LINEAR_ACOUSTIC_RZ},
         {"Euler_test", SX_EQ_EULER_TEST},
+        {"LinearShallowWater1D", SX_EQ_LINEAR_SW_1D},
+        {"LinearShallowWaterRL", SX_EQ_LINEAR_SW_RL},
         {"None", SX_EQ_NONE},
     };
     if (!name) return -1;
@@ -304,16 +306,24 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     // model
     h->ts = m->ts; h->eq = m->equation_set; h->semi = m->semiimplicit;
     h->w_index = m->w_index; h->xi_index = m->xi_index; h->col_var = m->col_var > 0 ? m->col_var : 1;
-    if (m->params) std::memcpy(h->par, m->params, sizeof(double) * SX_NPARAMS);
+    if (m->params) {
+        // the 12 entries up to SX_P_PXI_BAR always; SX_P_H only for the sets that read it, so that a caller built against the
+        // 12-entry table never has a 13th double read (include/scythe_hip.h, sx_model_desc.params)
+        std::memcpy(h->par, m->params, sizeof(double) * (SX_P_PXI_BAR + 1));
+        if (h->eq == SX_EQ_LINEAR_SW_1D || h->eq == SX_EQ_LINEAR_SW_RL) h->par[SX_P_H] = m->params[SX_P_H];
+    }
     {
         const int eq = h->eq;
-        const int need_geom = (eq == SX_EQ_LINEAR_ADVECTION_1D) ? SX_GEOM_R
+        const int need_geom = (eq == SX_EQ_LINEAR_ADVECTION_1D || eq == SX_EQ_LINEAR_SW_1D) ? SX_GEOM_R
                             : (eq == SX_EQ_LINEAR_ADVECTION_RZ || eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST) ? SX_GEOM_RZ
-                            : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB) ? SX_GEOM_RL
+                            : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB ||
+                               eq == SX_EQ_LINEAR_SW_RL) ? SX_GEOM_RL
                             : (eq == SX_EQ_LINEAR_ADVECTION_RLZ || eq == SX_EQ_ONEWAY_SW_HRBL) ? SX_GEOM_RLZ : -1;
-        const int need_vars = (eq == SX_EQ_LINEAR_ADVECTION_RZ) ? 4 : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_LINEAR_ADVECTION_RLZ) ? 3
+        const int need_vars = (eq == SX_EQ_LINEAR_ADVECTION_RZ) ? 4
+                            : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_LINEAR_ADVECTION_RLZ || eq == SX_EQ_LINEAR_SW_RL) ? 3
                             : (eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB || eq == SX_EQ_ONEWAY_SW_HRBL) ? 6
-                            : (eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST) ? 5 : 1;
+                            : (eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST) ? 5
+                            : (eq == SX_EQ_LINEAR_SW_1D) ? 2 : 1;
         if (eq != SX_EQ_NONE && need_geom < 0) { set_error("equation set not in scope"); delete h; return 1; }
         if (eq != SX_EQ_NONE && (need_geom != h->geom || h->V < need_vars)) {
             set_error("equation set does not match the grid geometry / variable count");
@@ -532,6 +542,15 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
             case SX_EQ_LINEAR_ACOUSTIC_RZ: case SX_EQ_EULER_TEST:
                 eq[0] = eq[2] = eq[3] = eq[4] = u | r | rr | z | zz;
                 eq[1] = u | r | z;
+                break;
+            case SX_EQ_LINEAR_SW_1D:          // src/shallowWaterModels.jl:253-254
+                eq[0] = u | r;
+                eq[1] = u | r | rr;
+                break;
+            case SX_EQ_LINEAR_SW_RL:          // src/shallowWaterModels.jl:291-293
+                eq[0] = u | r | l;
+                eq[1] = u | r | rr | ll;
+                eq[2] = u | r | rr | l | ll;
                 break;
             default: break;
         }

@@ -1078,6 +1078,26 @@ __global__ void k_phys_pointwise(PhysArgsT<ST> a) {
             }
             for (int v = 5; v < a.V; v++) ab_step(a, v, p, PSV(v), 0.0);
         } break;
+        case SX_EQ_LINEAR_SW_1D: {             // src/shallowWaterModels.jl:235-259
+            const double g = par[SX_P_G], K = par[SX_P_K], H = par[SX_P_H];
+            const double e0 = -H * PS(1, a.s_r);
+            const double e1 = (-g * PS(0, a.s_r)) + (K * PS(1, a.s_rr));
+            ab_step(a, 0, p, PSV(0), e0);
+            ab_step(a, 1, p, PSV(1), e1);
+            for (int v = 2; v < a.V; v++) ab_step(a, v, p, PSV(v), 0.0);
+        } break;
+        case SX_EQ_LINEAR_SW_RL: {             // src/shallowWaterModels.jl:261-298 (no -u / r^2 term, unlike the slab sets)
+            const double g = par[SX_P_G], K = par[SX_P_K], H = par[SX_P_H];
+            const double u = PSV(1), ur = PS(1, a.s_r), urr = PS(1, a.s_rr), ull = PS(1, a.s_ll);
+            const double vr = PS(2, a.s_r), vrr = PS(2, a.s_rr), vl = PS(2, a.s_l), vll = PS(2, a.s_ll);
+            const double e0 = -H * ((u / r) + ur + (vl / r));
+            const double e1 = (-g * PS(0, a.s_r)) + (K * ((ur / r) + urr + (ull / (r * r))));
+            const double e2 = (-g * (PS(0, a.s_l) / r)) + (K * ((vr / r) + vrr + (vll / (r * r))));
+            ab_step(a, 0, p, PSV(0), e0);
+            ab_step(a, 1, p, u, e1);
+            ab_step(a, 2, p, PSV(2), e2);
+            for (int v = 3; v < a.V; v++) ab_step(a, v, p, PSV(v), 0.0);
+        } break;
         default: break;
     }
 }
