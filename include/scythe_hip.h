@@ -52,6 +52,14 @@ enum {
                                         semi-implicit in the vertical acoustic terms; needs sx_model_desc.ref_state */
     SX_EQ_LINEAR_SW_1D = 9,          /* src/shallowWaterModels.jl:235-259: LinearShallowWater1D (h, u) on an R grid */
     SX_EQ_LINEAR_SW_RL = 10,         /* src/shallowWaterModels.jl:261-298: LinearShallowWaterRL (h, u, v) on an RL grid */
+    SX_EQ_RAINFALL_TEST = 11,        /* src/testModels.jl:387-585 + src/microphysics.jl:139-195: rainfall_test, Euler_test with
+                                        Ooyama (2001) warm rain on an RZ grid (s, xi, mu, u, w, mu_c, mu_r, qss = variables
+                                        1-8); needs sx_model_desc.ref_state, and xi_index 2 / w_index 5 when semi-implicit.
+                                        After the explicit (and semi-implicit) step, condensation_adjustment runs per column.
+                                        Kept for parity, a quirk of the reference: its two clamps min(q_v, q_cond) and
+                                        max(-q_c, q_cond) take whole columns (Julia's lexicographic isless on vectors, not a
+                                        broadcast), so each keeps ONE of its two arguments for the entire column, decided at
+                                        the first level where the two differ (isequal: -0.0 != 0.0, NaN == NaN) */
     SX_EQ_NONE = 99                  /* transforms only: sx_advance copies physical[:, :, 1] into var_np1 */
 };
 
@@ -106,7 +114,7 @@ typedef struct sx_model_desc {
     int32_t w_index, xi_index;/* 1-based variable indices of "w" and "xi" (semi-implicit only), 0 = absent */
     int32_t col_var;          /* 1-based variable whose vertical BCs the column operators of HRBL use ("h",
                                  src/shallowWaterModels.jl:423), 0 = variable 1 */
-    const double *ref_state;  /* ReferenceState (src/reference_state.jl:4-10) for Euler_test, or NULL:
+    const double *ref_state;  /* ReferenceState (src/reference_state.jl:4-10) for Euler_test or rainfall_test, or NULL:
                                  [3][3][zDim] = (sbar, xibar, mubar) x (value, d/dz, d2/dz2) x level (0 = bottom);
                                  Pxi_bar travels in params[SX_P_PXI_BAR] */
 } sx_model_desc;

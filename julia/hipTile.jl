@@ -32,7 +32,7 @@ struct SxModelDesc                          # mirrors sx_model_desc
     equation_set::Int32; semiimplicit::Int32
     params::Ptr{Float64}
     w_index::Int32; xi_index::Int32; col_var::Int32
-    ref_state::Ptr{Float64}                 # Euler_test: [3][3][zDim] (sbar, xibar, mubar) x (value, z, zz), else C_NULL
+    ref_state::Ptr{Float64}                 # Euler_test or rainfall_test: [3][3][zDim] (sbar, xibar, mubar) x (value, z, zz), else C_NULL
 end
 
 const SX_GEOM = Dict("R" => 0, "RZ" => 1, "RL" => 2, "RLZ" => 3)
@@ -83,7 +83,7 @@ function createHipModelTile(patch::AbstractGrid, tile_params::Matrix, model::Mod
                        Int32(tile_params[4, w] - 1), Int32(tile_params[3, w]), Int32(myid()), 0)
         eq = ccall((:sx_equation_set_id, libsx), Cint, (Cstring,), model.equation_set)
         eq < 0 && error("equation set $(model.equation_set) is not available on the HIP path")
-        # Euler_test: ref = permutedims(cat(rs.sbar, rs.xibar, rs.mubar; dims = 3), (1, 2, 3)) flattened level-fastest,
+        # Euler_test / rainfall_test: ref = permutedims(cat(rs.sbar, rs.xibar, rs.mubar; dims = 3), (1, 2, 3)) flattened level-fastest,
         # kept alive in the GC.@preserve list; par[12] = rs.Pxi_bar (src/testModels.jl:171)
         m = SxModelDesc(model.ts, eq, model.options[:semiimplicit] ? 1 : 0, pointer(par),
                         get(gp.vars, "w", 0), get(gp.vars, "xi", 0), get(gp.vars, "h", 0), C_NULL)

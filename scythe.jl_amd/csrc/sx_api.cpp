@@ -166,6 +166,7 @@ int sx_equation_set_id(const char *name) {
         {"Euler_test", SX_EQ_EULER_TEST},
         {"LinearShallowWater1D", SX_EQ_LINEAR_SW_1D},
         {"LinearShallowWaterRL", SX_EQ_LINEAR_SW_RL},
+        {"rainfall_test", SX_EQ_RAINFALL_TEST},
         {"None", SX_EQ_NONE},
     };
     if (!name) return -1;
@@ -315,7 +316,8 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     {
         const int eq = h->eq;
         const int need_geom = (eq == SX_EQ_LINEAR_ADVECTION_1D || eq == SX_EQ_LINEAR_SW_1D) ? SX_GEOM_R
-                            : (eq == SX_EQ_LINEAR_ADVECTION_RZ || eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST) ? SX_GEOM_RZ
+                            : (eq == SX_EQ_LINEAR_ADVECTION_RZ || eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST ||
+                               eq == SX_EQ_RAINFALL_TEST) ? SX_GEOM_RZ
                             : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB ||
                                eq == SX_EQ_LINEAR_SW_RL) ? SX_GEOM_RL
                             : (eq == SX_EQ_LINEAR_ADVECTION_RLZ || eq == SX_EQ_ONEWAY_SW_HRBL) ? SX_GEOM_RLZ : -1;
@@ -323,7 +325,8 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
                             : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_LINEAR_ADVECTION_RLZ || eq == SX_EQ_LINEAR_SW_RL) ? 3
                             : (eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB || eq == SX_EQ_ONEWAY_SW_HRBL) ? 6
                             : (eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST) ? 5
-                            : (eq == SX_EQ_LINEAR_SW_1D) ? 2 : 1;
+                            : (eq == SX_EQ_LINEAR_SW_1D) ? 2
+                            : (eq == SX_EQ_RAINFALL_TEST) ? 8 : 1;
         if (eq != SX_EQ_NONE && need_geom < 0) { set_error("equation set not in scope"); delete h; return 1; }
         if (eq != SX_EQ_NONE && (need_geom != h->geom || h->V < need_vars)) {
             set_error("equation set does not match the grid geometry / variable count");
@@ -332,6 +335,12 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         }
         if (h->semi && (!h->has_z || h->w_index < 1 || h->xi_index < 1 || h->w_index > h->V || h->xi_index > h->V || h->Zb != h->nz)) {
             set_error("semi-implicit adjustment needs an RZ/RLZ grid, w and xi variables and b_zDim == zDim");
+            delete h;
+            return 1;
+        }
+        if (eq == SX_EQ_RAINFALL_TEST && h->semi && (h->xi_index != 2 || h->w_index != 5)) {
+            // the tendency writes the implicit terms by position (src/testModels.jl:545-566), the adjustment finds xi and w by name
+            set_error("rainfall_test with semiimplicit needs xi = variable 2 and w = variable 5");
             delete h;
             return 1;
         }
@@ -494,8 +503,11 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         if (!upload(h, &h->d_z, one)) FAIL();
     }
 
-    if (h->eq == SX_EQ_EULER_TEST) {
-        if (!m->ref_state) { set_error("Euler_test needs sx_model_desc.ref_state (ReferenceState)"); FAIL(); }
+    if (h->eq == SX_EQ_EULER_TEST || h->eq == SX_EQ_RAINFALL_TEST) {
+        if (!m->ref_state) {
+            set_error(std::string(h->eq == SX_EQ_EULER_TEST ? "Euler_test" : "rainfall_test") + " needs sx_model_desc.ref_state (ReferenceState)");
+            FAIL();
+        }
         std::vector<double> ref(m->ref_state, m->ref_state + (size_t)9 * h->nz);
         if (!upload(h, &h->d_ref, ref)) FAIL();
     }
@@ -542,6 +554,10 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
             case SX_EQ_LINEAR_ACOUSTIC_RZ: case SX_EQ_EULER_TEST:
                 eq[0] = eq[2] = eq[3] = eq[4] = u | r | rr | z | zz;
                 eq[1] = u | r | z;
+                break;
+            case SX_EQ_RAINFALL_TEST:         // src/testModels.jl:404-455: xi and qss have no K diffusion
+                for (int v = 0; v < 8; v++) eq[v] = u | r | rr | z | zz;
+                eq[1] = eq[7] = u | r | z;
                 break;
             case SX_EQ_LINEAR_SW_1D:          // src/shallowWaterModels.jl:253-254
                 eq[0] = u | r;
@@ -1352,6 +1368,8 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_sbz") b = wi * fl + w * S_tile;
     else if (k == "k_solve") b = w * 4.0 * S_patch;                 // read B, write y, read y, write A
     else if (k == "k_semiimplicit") b = w * N * 2.0 * 5.0;
+    else if (k == "k_phys_rain") b = N * (eq_planes + w * (4.0 * V + (h->semi ? V : 0.0)));   // as k_phys_pointwise, + impdot
+    else if (k == "k_condensation") b = w * N * (6.0 + 3.0);       // read s, xi, mu, mu_c, mu_r, qss of var_np1; write s, mu, mu_c
     else if (k == "k_rz_inverse") b = w * S_tile + N * out_planes;       // read the tile's A rows, write the requested physical planes
     else if (k == "k_rz_forward") b = w * N * V + w * S_tile;            // read var_np1, write the tile's B rows
     *bytes = b;

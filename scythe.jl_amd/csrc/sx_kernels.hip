@@ -928,7 +928,7 @@ __device__ __forceinline__ double ab_step(const A &a, int v, int64_t p, double u
 
 // value of variable v / derivative slot s (>= 1) of variable v at point p
 #define PSV(v) a.P.val[(int64_t)(v) * a.N + p]
-// Moist thermodynamics of Euler_test (src/thermodynamics.jl; constants :2-17, :31-32)
+// Moist thermodynamics of Euler_test and rainfall_test (src/thermodynamics.jl; constants :2-17, :31-32)
 namespace thermo {
 constexpr double Rd = 287.04, Rv = 461.50, Cvd = 716.96, Cvv = 1410.0, gravity = 9.81, L_v0 = 2.501e6, T_0 = 273.16, p_0 = 1000.0,
                  q0 = 1.0e-7;
@@ -961,6 +961,124 @@ __device__ __forceinline__ double P_qv(double Tk, double rho_d, double q_v) {   
 }
 __device__ __forceinline__ double pressure_gradient(double Tk, double rho_d, double q_v, double s_x, double xi_x, double qv_x) {   // :250-258
     return (P_s(Tk, rho_d, q_v) * s_x) + (P_xi(Tk, rho_d, q_v) * xi_x) + (P_qv(Tk, rho_d, q_v) * qv_x);
+}
+// rainfall_test's additions: the constants Cl, Cpd, Cpv, Eps (:2-17), the saturation functions (:82-186) and Ooyama's (2001) warm
+// rain (src/microphysics.jl:84-137, 197-261), each written expression by expression as in the reference (Julia's x^2 is x * x)
+constexpr double Cl = 4186.0, Cpd = Cvd + Rd, Cpv = Cvv + Rv, Eps = Rd / Rv;
+__device__ __forceinline__ double L_v(double Tk) { return L_v0 + ((Cpv - Cl) * (Tk - T_0)); }                             // :41-44
+// p of thermodynamic_tuple (:260-269), total pressure in hPa
+__device__ __forceinline__ double pressure(double Tk, double rho_d, double q_v) {
+    return (0.01 * Rd * Tk * rho_d) + (0.01 * Rv * Tk * rho_d * q_v);
+}
+__device__ __forceinline__ double vapor_pressure(double p, double q_v) { return (p * q_v) / (Eps + q_v); }                  // :89-94
+__device__ __forceinline__ double sat_pressure_liquid_buck(double Tk, double phPa) {                                        // :101-118
+    const double Tc = Tk - 273.15;
+    const double A = 7.2e-4, B = 3.20e-6, C = 5.9e-10;
+    const double fw4 = 1.0 + A + (phPa * (B + (C * (Tc * Tc))));
+    const double a = 6.1121, b = 18.729, c = 257.87, d = 227.3;
+    const double ew4 = a * exp((b - (Tc / d)) * Tc / (Tc + c));
+    return fw4 * ew4;
+}
+__device__ __forceinline__ double sat_pressure_liquid_buck_dT(double Tk, double phPa) {                                     // :120-142
+    const double Tc = Tk - 273.15;
+    const double A = 7.2e-4, B = 3.20e-6, C = 5.9e-10;
+    const double fw4 = 1.0 + A + (phPa * (B + (C * (Tc * Tc))));
+    const double d_fw4 = 2.0 * phPa * C * Tc;
+    const double a = 6.1121, b = 18.729, c = 257.87, d = 227.3;
+    const double ew4 = a * exp((b - (Tc / d)) * Tc / (Tc + c));
+    const double T1 = (d * b - (2.0 * Tc)) * (d * (Tc + c)) - d * ((d * b * Tc) - (Tc * Tc));
+    const double dTc = d * (Tc + c);
+    const double T2 = dTc * dTc;
+    const double d_ew4 = ew4 * T1 / T2;
+    return ew4 * d_fw4 + fw4 * d_ew4;
+}
+__device__ __forceinline__ double q_sat_liquid(double Tk, double phPa) {                                                    // :163-170
+    const double ew = sat_pressure_liquid_buck(Tk, phPa);
+    return Eps * ew / (phPa - ew);
+}
+__device__ __forceinline__ double cp_moist(double q_v, double q_l) { return Cpd + (q_v * Cpv) + (q_l * Cl); }
+// dq_sat/dT of Q_s_factor and dqsdp (src/microphysics.jl:107-124)
+__device__ __forceinline__ double dqsdT(double Tk, double p, double e_s) {
+    const double pe = p - e_s;
+    return sat_pressure_liquid_buck_dT(Tk, p) * Eps * p / (pe * pe);
+}
+__device__ __forceinline__ double Q_s_factor(double Tk, double p, double q_v, double q_l) {                                 // microphysics.jl:107-114
+    const double e_s = sat_pressure_liquid_buck(Tk, p);
+    return L_v(Tk) * dqsdT(Tk, p, e_s) / cp_moist(q_v, q_l);
+}
+__device__ __forceinline__ double dqsdp(double Tk, double p, double rho_d, double q_v, double q_l) {                        // :116-124
+    const double q_sat = q_sat_liquid(Tk, p);
+    const double e_s = sat_pressure_liquid_buck(Tk, p);
+    return (q_sat / (100.0 * (p - e_s)) - (dqsdT(Tk, p, e_s) / (rho_d * cp_moist(q_v, q_l))));
+}
+__device__ __forceinline__ double vapor_diffusity(double Tk, double p) { return 0.211 * pow(Tk / 273.15, 1.94) * (1013.25 / p); }   // :134-140
+__device__ __forceinline__ double invtau_condensation(double Tk, double p, double N_c, double r_c) {                         // :126-132
+    return 4.0 * M_PI * vapor_diffusity(Tk, p) * N_c * (r_c * 1.0e-4);
+}
+// Julia's scalar min / max on Float64: NaN propagates and -0.0 < 0.0
+__device__ __forceinline__ double jl_min(double x, double y) {
+    return ((y < x) || (signbit(y) > signbit(x))) ? (isnan(x) ? x : y) : (isnan(y) ? y : x);
+}
+__device__ __forceinline__ double jl_max(double x, double y) {
+    return ((y > x) || (signbit(y) < signbit(x))) ? (isnan(x) ? x : y) : (isnan(y) ? y : x);
+}
+// Julia's isequal / isless on Float64 (the element comparisons of cmp on vectors): NaN equals NaN and is above every number,
+// -0.0 is below 0.0
+__device__ __forceinline__ bool jl_isequal(double x, double y) {
+    return (isnan(x) && isnan(y)) || ((signbit(x) == signbit(y)) && (x == y));
+}
+__device__ __forceinline__ bool jl_isless(double x, double y) {
+    return (!isnan(x) && (isnan(y) || (signbit(x) && !signbit(y)))) || (x < y);
+}
+__device__ __forceinline__ double q_condensation(double qss, double Tk, double p, double q_v, double q_l, double N_c,       // :84-93
+                                                 double r_c) {
+    const double Q_s = Q_s_factor(Tk, p, q_v, q_l);
+    double q_cond = qss / (1.0 + Q_s);
+    q_cond = jl_min(q_v, q_cond);              // broadcast in the reference: elementwise
+    q_cond = jl_max(-q_l, q_cond);
+    return q_cond * invtau_condensation(Tk, p, N_c, r_c);
+}
+__device__ __forceinline__ double s_condensation(double q_cond, double Tk, double rho_d, double q_v, double q_l, double p) {   // :96-105
+    const double Cm = (q_l * Cl) / (Cvd + (q_v * Cvv) + (q_l * Cl));
+    const double e = vapor_pressure(p, q_v);
+    const double sat_e = sat_pressure_liquid_buck(Tk, p);
+    return q_cond * (((-L_v(Tk) * Cm) / Tk) - (Cl * log(Tk / T_0)) + (Rv * log(e / sat_e)));
+}
+__device__ __forceinline__ double autoconversion(double q_c, double rho_d) {                                                              // :197-206
+    double q_auto = 0.001 * (q_c - 0.001);
+    if (q_auto < 0.0) q_auto = 0.0;
+    return q_auto;
+}
+__device__ __forceinline__ double f_ice(double Tk) {                                                                         // :219-227
+    if (Tk < 273.15) return 0.2 + 0.8 * (1.0 / cosh((273.15 - Tk) / 5.0));
+    return 1.0;
+}
+__device__ __forceinline__ double collection(double q_c, double q_r, double rho_d, double Tk) {                                           // :208-217
+    double q_coll = 2.20 * q_c * pow(q_r, 0.875) * f_ice(Tk);
+    if (q_coll < 0.0) q_coll = 0.0;
+    return q_coll;
+}
+__device__ __forceinline__ double f_ventilation(double q_r, double rho_d, double Tk) {                                      // :243-250
+    const double rho_r = q_r * rho_d;
+    double f_vent = 1.6 + 30.39 * pow(rho_r, 0.2046) * pow(f_ice(Tk), 1.5);
+    if (f_vent < 0.0) f_vent = 0.0;
+    return f_vent;
+}
+__device__ __forceinline__ double rain_evaporation(double q_r, double rho_d, double Tk, double p) {                         // :229-241
+    const double e_s = sat_pressure_liquid_buck(Tk, p);
+    const double rho_vs = e_s / (Rv * Tk);
+    const double rho_r = q_r * rho_d;
+    double q_evap = (f_ventilation(q_r, rho_d, Tk) * pow(rho_r, 0.525)) / (1.0e4 * ((2.03 * rho_vs) + (3.337 / Tk)));
+    if (q_evap < 0.0) q_evap = 0.0;
+    return q_evap;
+}
+// :252-261.  Vt is -14.164 times a non-negative number and then clamped at 0 from below, so it is 0.0 or -0.0 for every finite
+// state: k_phys_rain drops the flux divergence it feeds (src/testModels.jl:524-528) and never calls this
+__device__ __forceinline__ double sedimentation(double q_r, double rho_d, double Tk) {
+    const double rho_r = q_r * rho_d;
+    double Vt = -14.164 * pow(rho_r, 0.1364) * pow(rho_d0 / rho_d, 0.5) * f_ice(Tk);
+    if (Vt < 0.0) Vt = 0.0;
+    return Vt;
 }
 }  // namespace thermo
 
@@ -1099,6 +1217,77 @@ __global__ void k_phys_pointwise(PhysArgsT<ST> a) {
             for (int v = 3; v < a.V; v++) ab_step(a, v, p, PSV(v), 0.0);
         } break;
         default: break;
+    }
+}
+
+// rainfall_test (src/testModels.jl:387-585): Euler_test with Ooyama (2001) warm rain; variables s, xi, mu, u, w, mu_c, mu_r, qss by
+// position.  A kernel of its own so that this exp / log / pow chain leaves the register allocation of k_phys_pointwise alone.
+// condensation_adjustment follows in k_condensation, after the semi-implicit step.
+template <class ST>
+__global__ void __launch_bounds__(256) k_phys_rain(PhysArgsT<ST> a) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= a.N) return;
+    const double *par = a.par;
+    const double K = par[SX_P_K], Pxi_bar = par[SX_P_PXI_BAR];
+    const double N_c = 100.0, r_c = 10.0;                  // :500-501
+    const int k = (int)(p % a.nz), nz = a.nz;
+    // ReferenceState rows: sbar, sbar_z, sbar_zz, xibar, xibar_z, xibar_zz, mubar, mubar_z, mubar_zz
+    const double sbar = a.ref[k], sbar_z = a.ref[nz + k], xibar = a.ref[3 * nz + k], xibar_z = a.ref[4 * nz + k];
+    const double mubar = a.ref[6 * nz + k], mubar_z = a.ref[7 * nz + k];
+    const double s = PSV(0), s_x = PS(0, a.s_r), s_z = PS(0, a.s_z);
+    const double xi = PSV(1), xi_x = PS(1, a.s_r), xi_z = PS(1, a.s_z);
+    const double mu = PSV(2), mu_x = PS(2, a.s_r), mu_z = PS(2, a.s_z);
+    const double u = PSV(3), u_x = PS(3, a.s_r), u_z = PS(3, a.s_z);
+    const double w = PSV(4), w_x = PS(4, a.s_r), w_z = PS(4, a.s_z);
+    const double mu_c = PSV(5), mu_r = PSV(6), qss = PSV(7);
+
+    const double mu_total = mu + mubar;
+    const double q_v = thermo::ahyp(mu_total);
+    const double rho_d = thermo::dry_density(xi + xibar);
+    const double Tk = thermo::temperature(s + sbar, rho_d, q_v);
+    const double pr = thermo::pressure(Tk, rho_d, q_v);
+    const double q_c = thermo::ahyp(mu_c), q_r = thermo::ahyp(mu_r);
+    const double q_l = q_c + q_r, q_t = q_v + q_l;
+    const double rho_t = rho_d * (1.0 + q_t);
+    const double mu_factor = thermo::dmudq(mu_total, q_v);
+    const double qvp_x = mu_x / mu_factor, qvp_z = mu_z / mu_factor;
+    const double rhobar = thermo::dry_density(xibar) * (1.0 + thermo::ahyp(mubar));
+    const double rho_p = rho_t - rhobar;
+    const double dpdx = thermo::pressure_gradient(Tk, rho_d, q_v, s_x, xi_x, qvp_x);
+    const double dpdz = thermo::pressure_gradient(Tk, rho_d, q_v, s_z, xi_z, qvp_z);
+
+    const double Cm = (q_l * thermo::Cl) / (thermo::Cvd + (q_v * thermo::Cvv) + (q_l * thermo::Cl));
+    const double s_div = Cm * (thermo::Rd + q_v * thermo::Rv) * (u_x + w_z);
+    const double q_cond = thermo::q_condensation(qss, Tk, pr, q_v, q_l, N_c, r_c);
+    const double s_cond = thermo::s_condensation(q_cond, Tk, rho_d, q_v, q_l, pr);
+    const double cloudtau = thermo::invtau_condensation(Tk, pr, N_c, r_c);
+    const double raintau = thermo::rain_evaporation(q_r, rho_d, Tk, pr);
+    const double q_evap = -qss * raintau;
+    const double qss_cond = thermo::dqsdp(Tk, pr, rho_d, q_v, q_l) * ((u * dpdx) + (w * (dpdz - rhobar * thermo::gravity))) -
+                            qss * (cloudtau + raintau);
+    const double q_auto = thermo::autoconversion(q_c, rho_d);
+    const double q_coll = thermo::collection(q_c, q_r, rho_d, Tk);
+    // No sedimentation term: Vt_flux = CIx(q_r .* Vt) ./ rho_d (:524-528) is identically zero because sedimentation clamps its
+    // Vt = -14.164 rho_r^0.1364 (rho_d0 / rho_d)^0.5 f_ice(Tk) <= 0 at 0 from below (src/microphysics.jl:252-261), so no column
+    // operator is built for it
+
+    double e[8];
+    e[0] = (((-u * s_x) + (-w * (s_z + sbar_z))) + (s_cond + s_div)) + (K * (PS(0, a.s_rr) + PS(0, a.s_zz)));
+    e[1] = ((-u * xi_x) + (-w * (xi_z + xibar_z))) + (-u_x - w_z);
+    e[2] = (((-u * mu_x) + (-w * (mu_z + mubar_z))) + (mu_factor * (q_evap - q_cond))) + (K * (PS(2, a.s_rr) + PS(2, a.s_zz)));
+    e[3] = (((-u * u_x) + (-w * u_z)) + (-dpdx / rho_t)) + (K * (PS(3, a.s_rr) + PS(3, a.s_zz)));
+    e[4] = (((-u * w_x) + (-w * w_z)) + (((-thermo::gravity * rho_p) - dpdz) / rho_t)) + (K * (PS(4, a.s_rr) + PS(4, a.s_zz)));
+    e[5] = (((-u * PS(5, a.s_r)) + (-w * PS(5, a.s_z))) + (thermo::dmudq(mu_c, q_c) * (q_cond - q_auto - q_coll))) +
+           (K * (PS(5, a.s_rr) + PS(5, a.s_zz)));
+    e[6] = (((-u * PS(6, a.s_r)) + (-w * PS(6, a.s_z))) + (thermo::dmudq(mu_r, q_r) * (q_auto + q_coll - q_evap))) +
+           (K * (PS(6, a.s_rr) + PS(6, a.s_zz)));
+    e[7] = ((-u * PS(7, a.s_r)) + (-w * PS(7, a.s_z))) + qss_cond;
+    const double vals[8] = {s, xi, mu, u, w, mu_c, mu_r, qss};
+    for (int v = 0; v < 8; v++) ab_step(a, v, p, vals[v], e[v]);
+    for (int v = 8; v < a.V; v++) ab_step(a, v, p, PSV(v), 0.0);
+    if (a.In) {            // impdot: only kept when semi-implicit; mu and qss hold q_v and qss for the reference's (unused) history
+        for (int v = 0; v < a.V; v++)
+            a.In[(int64_t)v * a.N + p] = (v == 1) ? -w_z : (v == 2) ? q_v : (v == 4) ? -(Pxi_bar * xi_z) : (v == 7) ? qss : 0.0;
     }
 }
 
@@ -1719,6 +1908,67 @@ __global__ void __launch_bounds__(256) k_semiimplicit(SemiArgs a, int cpb) {
     a.np1[(int64_t)a.xi * a.N + p] = xrec - (a.tau * wz);
 }
 
+// condensation_adjustment (src/microphysics.jl:139-195) of rainfall_test on var_np1, one workgroup per group of columns: thread (c, k)
+// owns level k of column c.  The reference hands it one RZ column at a time (src/semiimplicit.jl:334-349) and clamps with
+//     q_cond = min(q_v, q_cond);  q_cond = max(-q_c, q_cond)          (:185-187, vectors, not broadcast)
+// Julia's min / max of two vectors compare them with isless, which is lexicographic (cmp walks to the first level where
+// !isequal(a, b) and compares with isless there), so each clamp keeps ONE of its two arguments for the whole column.  Kept for
+// parity: an LDS minimum finds that first level, and every thread of the column reads the isless result stored at it.  No level
+// differs: the first argument stays.
+__global__ void __launch_bounds__(256) k_condensation(double *__restrict__ np1, const double *__restrict__ ref, int64_t N, int nz,
+                                                       int cpb) {
+    extern __shared__ int smi[];
+    int *first = smi;                        // [2][cpb]: first differing level of the min step, of the max step
+    int *lt = smi + 2 * cpb;                 // [2][cpb][nz]: isless at each level, for the min step and the max step
+    const int k = threadIdx.x % nz, cl = threadIdx.x / nz;
+    const int64_t col = (int64_t)blockIdx.x * cpb + cl;
+    const bool live = (cl < cpb) && (col < N / nz);
+    const int64_t p = live ? col * nz + k : 0;
+    if (cl < cpb && k == 0) { first[cl] = nz; first[cpb + cl] = nz; }
+    double s = 0.0, mu = 0.0, mu_c = 0.0, mu_total = 0.0, q_v = 0.0, rho_d = 0.0, Tk = 0.0, pr = 0.0, q_c = 0.0, q_l = 0.0;
+    double q_cond = 0.0;
+    __syncthreads();
+    if (live) {
+        s = np1[p];
+        const double xi = np1[N + p];
+        mu = np1[2 * N + p];
+        mu_c = np1[5 * N + p];
+        const double mu_r = np1[6 * N + p], qss = np1[7 * N + p];
+        // ReferenceState rows 0, 3, 6: sbar, xibar, mubar
+        mu_total = mu + ref[6 * nz + k];
+        q_v = thermo::ahyp(mu_total);
+        rho_d = thermo::dry_density(xi + ref[3 * nz + k]);
+        Tk = thermo::temperature(s + ref[k], rho_d, q_v);
+        pr = thermo::pressure(Tk, rho_d, q_v);
+        q_c = thermo::ahyp(mu_c);
+        const double q_r = thermo::ahyp(mu_r);
+        q_l = q_c + q_r;
+        const double q_sat = thermo::q_sat_liquid(Tk, pr);
+        const double Q_s = thermo::Q_s_factor(Tk, pr, q_v, q_l);
+        q_cond = (q_v - q_sat - qss) / (1.0 + Q_s);
+        // min(q_v, q_cond) = isless(q_cond, q_v) ? q_cond : q_v
+        if (!thermo::jl_isequal(q_cond, q_v)) atomicMin(&first[cl], k);
+        lt[cl * nz + k] = thermo::jl_isless(q_cond, q_v) ? 1 : 0;
+    }
+    __syncthreads();
+    if (live) {
+        const int f = first[cl];
+        if (!(f < nz && lt[cl * nz + f])) q_cond = q_v;
+        // max(-q_c, q_cond) = isless(q_cond, -q_c) ? -q_c : q_cond
+        if (!thermo::jl_isequal(q_cond, -q_c)) atomicMin(&first[cpb + cl], k);
+        lt[(cpb + cl) * nz + k] = thermo::jl_isless(q_cond, -q_c) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!live) return;
+    const int f = first[cpb + cl];
+    if (f < nz && lt[(cpb + cl) * nz + f]) q_cond = -q_c;
+    // explicit Euler increment with tau_r = 0.25, elementwise (:188-190); q_l is the liquid before the increment
+    const double tau_r = 0.25;
+    np1[2 * N + p] = mu - tau_r * thermo::dmudq(mu_total, q_v) * q_cond;
+    np1[5 * N + p] = mu_c + tau_r * thermo::dmudq(mu_c, q_c) * q_cond;
+    np1[p] = s + tau_r * thermo::s_condensation(q_cond, Tk, rho_d, q_v, q_l, pr);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 static inline dim3 grid1(int64_t n, int bs) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
@@ -1916,6 +2166,12 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
         hipLaunchKernelGGL(k_phys_hrbl<ST>, grid1(h->Nh, cpb), dim3(bs), lds, h->stream, a, cpb);
         HIPCHK(hipGetLastError());
         timer_end(h);
+    } else if (h->eq == SX_EQ_RAINFALL_TEST) {
+        const int id = timer_id(h, "k_phys_rain");
+        timer_begin(h, id);
+        hipLaunchKernelGGL(k_phys_rain<ST>, grid1(h->N, 256), dim3(256), 0, h->stream, a);
+        HIPCHK(hipGetLastError());
+        timer_end(h);
     } else {
         const int id = timer_id(h, "k_phys_pointwise");
         timer_begin(h, id);
@@ -1939,6 +2195,15 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
             const size_t lds = sizeof(double) * 3 * cpb * h->nz;
             hipLaunchKernelGGL(k_semiimplicit, grid1(h->Nh, cpb), dim3(cpb * h->nz), lds, h->stream, s, cpb);
         }
+        HIPCHK(hipGetLastError());
+        timer_end(h);
+    }
+    if (h->eq == SX_EQ_RAINFALL_TEST) {        // after the explicit and the semi-implicit step (src/testModels.jl:572-580)
+        const int id = timer_id(h, "k_condensation");
+        timer_begin(h, id);
+        const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
+        const size_t lds = sizeof(int) * 2 * cpb * (1 + h->nz);
+        hipLaunchKernelGGL(k_condensation, grid1(h->Nh, cpb), dim3(cpb * h->nz), lds, h->stream, h->d_np1, h->d_ref, h->N, h->nz, cpb);
         HIPCHK(hipGetLastError());
         timer_end(h);
     }

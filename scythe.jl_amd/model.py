@@ -162,6 +162,9 @@ def grid_desc(patch: GridParameters, tile_cell0=0, tile_num_cells=None, tile_num
     return d, keep
 
 
+RAINFALL_VARS = {"s": 1, "xi": 2, "mu": 3, "u": 4, "w": 5, "mu_c": 6, "mu_r": 7, "qss": 8}
+
+
 def model_desc(model: Optional[ModelParameters], patch: GridParameters):
     m = L.ModelDesc()
     keep = {}
@@ -176,7 +179,11 @@ def model_desc(model: Optional[ModelParameters], patch: GridParameters):
             raise ValueError("equation set %r is not defined on the HIP path" % model.equation_set)
         pp = {(k if isinstance(k, str) else str(k)).lstrip(":"): v for k, v in model.physical_params.items()}
         opts = {str(k).lstrip(":"): v for k, v in (model.options or {}).items()}
-        if model.equation_set == "Euler_test":
+        if model.equation_set == "rainfall_test" and patch.vars != RAINFALL_VARS:
+            # its tendency reads the variables by position (src/testModels.jl:404-450), condensation_adjustment by name
+            # (src/microphysics.jl:142-165): any other mapping would mix the two
+            raise ValueError("rainfall_test needs grid_params.vars = %r" % (RAINFALL_VARS,))
+        if model.equation_set in ("Euler_test", "rainfall_test"):
             # createModelTile builds mtile.ref_state from model.ref_state_file (src/semiimplicit.jl:44-124)
             if model.ref_state is None:
                 from . import reference_state as RS
