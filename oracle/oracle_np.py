@@ -14,7 +14,8 @@ package Springsteel.jl (Project.toml:20, unpinned) at these call sites:
   Chebyshev column ops CB/CA/CI/CIx/CIxx/CIInt                src/semiimplicit.jl:569-596,
                                                               src/shallowWaterModels.jl:423-504
 and the in-tree step structure (src/semiimplicit.jl:301-332, 672-698, 521-597, 768-781) plus
-equation sets (src/testModels.jl:1-98, src/shallowWaterModels.jl:1-233, 346-511).
+every equation set the library accepts (src/testModels.jl:1-215, 387-585, src/shallowWaterModels.jl:1-298, 346-511,
+with src/thermodynamics.jl and src/microphysics.jl) and the synthetic LinearAcousticRZ.
 
 Parity status:
   * R-grid cubic-B-spline + AB3 pipeline: PINNED by the reference's notebook known-answer
@@ -586,10 +587,13 @@ def semi_matrices(ch, pxi_bar, tau):
     return np.asarray(ch._x["T"] @ Hinv, dtype=np.float64), np.asarray(ch._x["TD"] @ Hinv, dtype=np.float64)
 
 
-# ----------------------------------------------------------------------------- moist thermodynamics (Euler_test)
-# Restated from src/thermodynamics.jl (constants :2-17, :31-32): only what Euler_test (src/testModels.jl:100-215) calls.
+# ----------------------------------------------------------------------------- moist thermodynamics (Euler_test, rainfall_test)
+# Restated from src/thermodynamics.jl (constants :2-17, :31-32) and src/microphysics.jl: only what Euler_test
+# (src/testModels.jl:100-215) and rainfall_test (src/testModels.jl:387-585) call.
 TH = dict(Rd=287.04, Rv=461.50, Cvd=716.96, Cvv=1410.0, Cl=4186.0, gravity=9.81, L_v0=2.501e6, T_0=273.16, p_0=1000.0, q0=1.0e-7)
 TH["Cpv"] = TH["Cvv"] + TH["Rv"]
+TH["Cpd"] = TH["Cvd"] + TH["Rd"]
+TH["Eps"] = TH["Rd"] / TH["Rv"]
 TH["rho_d0"] = 100.0 * TH["p_0"] / (TH["T_0"] * TH["Rd"])
 TH["rho_v0"] = 100.0 * (6.112 * np.exp(17.67 * (TH["T_0"] - 273.15) / ((TH["T_0"] - 273.15) + 243.5))) / (TH["T_0"] * TH["Rv"])
 
@@ -634,9 +638,217 @@ def th_pressure_gradient(Tk, rho_d, q_v, s_x, xi_x, qv_x):     # :250-258
     return (th_P_s(Tk, rho_d, q_v) * s_x) + (th_P_xi(Tk, rho_d, q_v) * xi_x) + (th_P_qv(Tk, rho_d, q_v) * qv_x)
 
 
-def tendency(grid, eq, par, phys, pts, col_ops=None):
+def th_L_v(Tk):                                        # :41-44
+    return TH["L_v0"] + ((TH["Cpv"] - TH["Cl"]) * (Tk - TH["T_0"]))
+
+
+def th_pressure(Tk, rho_d, q_v):                       # p of thermodynamic_tuple, :260-269
+    return (0.01 * TH["Rd"] * Tk * rho_d) + (0.01 * TH["Rv"] * Tk * rho_d * q_v)
+
+
+def th_vapor_pressure(p, q_v):                         # :89-94
+    return (p * q_v) / (TH["Eps"] + q_v)
+
+
+def th_sat_pressure_liquid_buck(Tk, phPa):             # :101-118
+    Tc = Tk - 273.15
+    A, B, C = 7.2e-4, 3.20e-6, 5.9e-10
+    fw4 = 1.0 + A + (phPa * (B + (C * (Tc * Tc))))
+    a, b, c, d = 6.1121, 18.729, 257.87, 227.3
+    return fw4 * (a * np.exp((b - (Tc / d)) * Tc / (Tc + c)))
+
+
+def th_sat_pressure_liquid_buck_dT(Tk, phPa):          # :120-142
+    Tc = Tk - 273.15
+    A, B, C = 7.2e-4, 3.20e-6, 5.9e-10
+    fw4 = 1.0 + A + (phPa * (B + (C * (Tc * Tc))))
+    d_fw4 = 2.0 * phPa * C * Tc
+    a, b, c, d = 6.1121, 18.729, 257.87, 227.3
+    ew4 = a * np.exp((b - (Tc / d)) * Tc / (Tc + c))
+    T1 = (d * b - (2.0 * Tc)) * (d * (Tc + c)) - d * ((d * b * Tc) - (Tc * Tc))
+    T2 = (d * (Tc + c)) * (d * (Tc + c))
+    return ew4 * d_fw4 + fw4 * (ew4 * T1 / T2)
+
+
+def th_q_sat_liquid(Tk, phPa):                         # :163-170
+    ew = th_sat_pressure_liquid_buck(Tk, phPa)
+    return TH["Eps"] * ew / (phPa - ew)
+
+
+def _th_cp(q_v, q_l):
+    return TH["Cpd"] + (q_v * TH["Cpv"]) + (q_l * TH["Cl"])
+
+
+def _th_dqsdT(Tk, p, e_s):
+    return th_sat_pressure_liquid_buck_dT(Tk, p) * TH["Eps"] * p / ((p - e_s) * (p - e_s))
+
+
+def th_Q_s_factor(Tk, p, q_v, q_l):                    # src/microphysics.jl:107-114
+    e_s = th_sat_pressure_liquid_buck(Tk, p)
+    return th_L_v(Tk) * _th_dqsdT(Tk, p, e_s) / _th_cp(q_v, q_l)
+
+
+def th_dqsdp(Tk, p, rho_d, q_v, q_l):                  # src/microphysics.jl:116-124
+    e_s = th_sat_pressure_liquid_buck(Tk, p)
+    return th_q_sat_liquid(Tk, p) / (100.0 * (p - e_s)) - (_th_dqsdT(Tk, p, e_s) / (rho_d * _th_cp(q_v, q_l)))
+
+
+def th_vapor_diffusity(Tk, p):                         # src/microphysics.jl:134-140
+    return 0.211 * (Tk / 273.15) ** 1.94 * (1013.25 / p)
+
+
+def th_invtau_condensation(Tk, p, N_c, r_c):           # src/microphysics.jl:126-132
+    return 4.0 * np.pi * th_vapor_diffusity(Tk, p) * N_c * (r_c * 1.0e-4)
+
+
+def jl_min(x, y):
+    """Julia's scalar min on Float64, elementwise: NaN propagates, -0.0 < 0.0."""
+    x, y = np.broadcast_arrays(np.asarray(x, float), np.asarray(y, float))
+    pick_y = (y < x) | (np.signbit(y) & ~np.signbit(x))
+    return np.where(pick_y, np.where(np.isnan(x), x, y), np.where(np.isnan(y), y, x))
+
+
+def jl_max(x, y):
+    x, y = np.broadcast_arrays(np.asarray(x, float), np.asarray(y, float))
+    pick_y = (y > x) | (~np.signbit(y) & np.signbit(x))
+    return np.where(pick_y, np.where(np.isnan(x), x, y), np.where(np.isnan(y), y, x))
+
+
+def th_q_condensation(qss, Tk, p, q_v, q_l, N_c, r_c):    # src/microphysics.jl:84-93 (broadcast: scalar min / max)
+    q_cond = qss / (1.0 + th_Q_s_factor(Tk, p, q_v, q_l))
+    q_cond = jl_min(q_v, q_cond)
+    q_cond = jl_max(-q_l, q_cond)
+    return q_cond * th_invtau_condensation(Tk, p, N_c, r_c)
+
+
+def th_s_condensation(q_cond, Tk, rho_d, q_v, q_l, p):    # src/microphysics.jl:96-105
+    Cm = (q_l * TH["Cl"]) / (TH["Cvd"] + (q_v * TH["Cvv"]) + (q_l * TH["Cl"]))
+    e = th_vapor_pressure(p, q_v)
+    sat_e = th_sat_pressure_liquid_buck(Tk, p)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return q_cond * (((-th_L_v(Tk) * Cm) / Tk) - (TH["Cl"] * np.log(Tk / TH["T_0"])) + (TH["Rv"] * np.log(e / sat_e)))
+
+
+def th_autoconversion(q_c, rho_d):                     # src/microphysics.jl:197-206
+    q = 0.001 * (q_c - 0.001)
+    return np.where(q < 0.0, 0.0, q)
+
+
+def th_f_ice(Tk):                                      # src/microphysics.jl:219-227
+    return np.where(Tk < 273.15, 0.2 + 0.8 * (1.0 / np.cosh((273.15 - Tk) / 5.0)), 1.0)
+
+
+def th_collection(q_c, q_r, rho_d, Tk):                # src/microphysics.jl:208-217
+    q = 2.20 * q_c * q_r ** 0.875 * th_f_ice(Tk)
+    return np.where(q < 0.0, 0.0, q)
+
+
+def th_f_ventilation(q_r, rho_d, Tk):                  # src/microphysics.jl:243-250
+    f = 1.6 + 30.39 * (q_r * rho_d) ** 0.2046 * th_f_ice(Tk) ** 1.5
+    return np.where(f < 0.0, 0.0, f)
+
+
+def th_rain_evaporation(q_r, rho_d, Tk, p):            # src/microphysics.jl:229-241
+    rho_vs = th_sat_pressure_liquid_buck(Tk, p) / (TH["Rv"] * Tk)
+    q = (th_f_ventilation(q_r, rho_d, Tk) * (q_r * rho_d) ** 0.525) / (1.0e4 * ((2.03 * rho_vs) + (3.337 / Tk)))
+    return np.where(q < 0.0, 0.0, q)
+
+
+def th_sedimentation(q_r, rho_d, Tk):                  # src/microphysics.jl:252-261
+    Vt = -14.164 * (q_r * rho_d) ** 0.1364 * (TH["rho_d0"] / rho_d) ** 0.5 * th_f_ice(Tk)
+    return np.where(Vt < 0.0, 0.0, Vt)
+
+
+def sedimentation_flux(grid, q_r, rho_d, Tk):
+    """Vt_flux = CIx(q_r .* Vt) ./ rho_d through the mu_r column's filtered Chebyshev derivative (src/testModels.jl:521-528);
+    zero for every finite state (the library drops it)."""
+    nz = grid.zDim
+    Vt = th_sedimentation(q_r, rho_d, Tk)
+    col = (q_r * Vt).reshape(-1, nz)
+    return (col @ grid.cheb("mu_r").Vdz.T).reshape(-1) / rho_d
+
+
+def thermo_state(s, xi, mu, mu_c, mu_r, sbar, xibar, mubar):
+    """thermodynamic_tuple of the totals plus q_c, q_r, q_l (src/testModels.jl:474-484, src/microphysics.jl:166-178)."""
+    mu_total = mu + mubar
+    q_v = th_ahyp(mu_total)
+    rho_d = th_dry_density(xi + xibar)
+    Tk = th_temperature(s + sbar, rho_d, q_v)
+    q_c, q_r = th_ahyp(mu_c), th_ahyp(mu_r)
+    return dict(mu_total=mu_total, q_v=q_v, rho_d=rho_d, Tk=Tk, p=th_pressure(Tk, rho_d, q_v), q_c=q_c, q_r=q_r, q_l=q_c + q_r)
+
+
+def ref_levels(par, N, nz):
+    """The reference state's profiles and their d/dz, d2/dz2 at each of N points (z fastest): sbar, sbar_z, sbar_zz, xibar, ..."""
+    rs, lev = par["ref_state"], np.arange(N) % nz
+    return {k + suf: rs[k][lev, j] for k in ("sbar", "xibar", "mubar") for j, suf in enumerate(("", "_z", "_zz"))}
+
+
+# rainfall_test's cloud droplets (src/testModels.jl:500-501) and condensation_adjustment's time scale (src/microphysics.jl:182)
+RAIN_N_C, RAIN_R_C, RAIN_TAU_R = 100.0, 10.0, 0.25
+
+
+def _isequal(a, b):
+    return (np.isnan(a) & np.isnan(b)) | ((np.signbit(a) == np.signbit(b)) & (a == b))
+
+
+def _isless(a, b):
+    return (~np.isnan(a) & (np.isnan(b) | (np.signbit(a) & ~np.signbit(b)))) | (a < b)
+
+
+def column_isless(a, b):
+    """Julia's isless(a, b) of two vectors, per row of [ncol, nz]: cmp walks to the first index where !isequal and compares
+    with isless there; equal vectors are not less."""
+    diff = ~_isequal(a, b)
+    first = np.argmax(diff, axis=1)
+    rows = np.arange(a.shape[0])
+    return diff.any(axis=1) & _isless(a[rows, first], b[rows, first])
+
+
+def column_min(x, y):
+    """Julia's min(x, y) = ifelse(isless(y, x), y, x) on vectors, per row: one of the two rows whole."""
+    return np.where(column_isless(y, x)[:, None], y, x)
+
+
+def column_max(x, y):
+    """max(x, y) = ifelse(isless(y, x), x, y)"""
+    return np.where(column_isless(y, x)[:, None], x, y)
+
+
+def condensation_adjustment(np1, par, nz, elementwise=False):
+    """src/microphysics.jl:139-195 on var_np1 [N, V] of one tile (whole columns, z fastest); returns the adjusted copy.
+    elementwise=True clamps point by point instead - not the reference; only to show that a case tells the two apart."""
+    out = np1.copy()
+    R = ref_levels(par, np1.shape[0], nz)
+    s, xi, mu, mu_c, mu_r, qss = (np1[:, v] for v in (0, 1, 2, 5, 6, 7))
+    T = thermo_state(s, xi, mu, mu_c, mu_r, R["sbar"], R["xibar"], R["mubar"])
+    q_v, Tk, p, q_c, q_l = T["q_v"], T["Tk"], T["p"], T["q_c"], T["q_l"]
+    q_sat = th_q_sat_liquid(Tk, p)
+    Q_s = th_Q_s_factor(Tk, p, q_v, q_l)
+    q_cond = (q_v - q_sat - qss) / (1.0 + Q_s)
+    if elementwise:
+        q_cond = jl_max(-q_c, jl_min(q_v, q_cond))
+    else:
+        col = lambda a: a.reshape(-1, nz)
+        q_cond = column_min(col(q_v), col(q_cond))
+        q_cond = column_max(col(-q_c), q_cond).reshape(-1)
+    out[:, 2] = mu - RAIN_TAU_R * th_dmudq(T["mu_total"], q_v) * q_cond
+    out[:, 5] = mu_c + RAIN_TAU_R * th_dmudq(mu_c, q_c) * q_cond
+    out[:, 0] = s + RAIN_TAU_R * th_s_condensation(q_cond, Tk, T["rho_d"], q_v, q_l, p)
+    return out
+
+
+def rain_rates(grid, par, phys):
+    """Every microphysical rate of rainfall_test's tendency, [N] each: q_cond, s_cond, q_evap, qss_cond, q_auto, q_coll, Vt_flux."""
+    rates = {}
+    tendency(grid, "rainfall_test", par, phys, None, rates=rates)
+    return rates
+
+
+def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
     """Pointwise tendencies of the in-scope equation sets. phys [N,V,D]; returns (expdot [N,V], impdot [N,V] or None, phys)
-    (phys is returned because the shallow-water sets overwrite the diagnostic w in slot 1)."""
+    (phys is returned because the shallow-water sets overwrite the diagnostic w in slot 1).  rainfall_test puts its
+    microphysical rates into `rates` if given (rain_rates)."""
     N = phys.shape[0]
     E = np.zeros((N, grid.V))
     I = None
@@ -758,14 +970,73 @@ def tendency(grid, eq, par, phys, pts, col_ops=None):
         E[:, 4] = ((-u * P(5, "r")) + (-w * P(5, "z"))) + \
                   (-(TH["gravity"] * rho_p / rho_t) - (th_pressure_gradient(Tk, rho_d, q_v, P(1, "z"), P(2, "z"), qvp_z) / rho_t)) + dif(5)
         I[:, 4] = -(pxi * P(2, "z"))
+    elif eq == "LinearShallowWater1D":                  # src/shallowWaterModels.jl:253-254
+        g, K, H = par["g"], par["K"], par["H"]
+        E[:, 0] = -H * P(2, "r")
+        E[:, 1] = (-g * P(1, "r")) + (K * P(2, "rr"))
+    elif eq == "LinearShallowWaterRL":                  # src/shallowWaterModels.jl:291-293 (no -u / r^2 term)
+        g, K, H = par["g"], par["K"], par["H"]
+        r = pts[:, 0]
+        u, ur, urr, ull = P(2, "u"), P(2, "r"), P(2, "rr"), P(2, "ll")
+        vr, vrr, vl, vll = P(3, "r"), P(3, "rr"), P(3, "l"), P(3, "ll")
+        E[:, 0] = -H * ((u / r) + ur + (vl / r))
+        E[:, 1] = (-g * P(1, "r")) + (K * ((ur / r) + urr + (ull / (r * r))))
+        E[:, 2] = (-g * (P(1, "l") / r)) + (K * ((vr / r) + vrr + (vll / (r * r))))
+    elif eq == "rainfall_test":                         # src/testModels.jl:387-570, with the sedimentation flux the library drops
+        K, Pxi_bar = par["K"], par["Pxi_bar"]
+        R = ref_levels(par, N, grid.zDim)
+        u, w = P(4, "u"), P(5, "u")
+        T = thermo_state(P(1, "u"), P(2, "u"), P(3, "u"), P(6, "u"), P(7, "u"), R["sbar"], R["xibar"], R["mubar"])
+        q_v, rho_d, Tk, p, q_c, q_r, q_l = (T[k] for k in ("q_v", "rho_d", "Tk", "p", "q_c", "q_r", "q_l"))
+        rho_t = rho_d * (1.0 + (q_v + q_l))
+        mu_factor = th_dmudq(T["mu_total"], q_v)
+        qvp_x, qvp_z = P(3, "r") / mu_factor, P(3, "z") / mu_factor
+        rhobar = th_dry_density(R["xibar"]) * (1.0 + th_ahyp(R["mubar"]))
+        rho_p = rho_t - rhobar
+        dpdx = th_pressure_gradient(Tk, rho_d, q_v, P(1, "r"), P(2, "r"), qvp_x)
+        dpdz = th_pressure_gradient(Tk, rho_d, q_v, P(1, "z"), P(2, "z"), qvp_z)
+        Cm = (q_l * TH["Cl"]) / (TH["Cvd"] + (q_v * TH["Cvv"]) + (q_l * TH["Cl"]))
+        s_div = Cm * (TH["Rd"] + q_v * TH["Rv"]) * (P(4, "r") + P(5, "z"))
+        qss = P(8, "u")
+        q_cond = th_q_condensation(qss, Tk, p, q_v, q_l, RAIN_N_C, RAIN_R_C)
+        s_cond = th_s_condensation(q_cond, Tk, rho_d, q_v, q_l, p)
+        cloudtau = th_invtau_condensation(Tk, p, RAIN_N_C, RAIN_R_C)
+        raintau = th_rain_evaporation(q_r, rho_d, Tk, p)
+        q_evap = -qss * raintau
+        qss_cond = th_dqsdp(Tk, p, rho_d, q_v, q_l) * ((u * dpdx) + (w * (dpdz - rhobar * TH["gravity"]))) - qss * (cloudtau + raintau)
+        q_auto = th_autoconversion(q_c, rho_d)
+        q_coll = th_collection(q_c, q_r, rho_d, Tk)
+        Vt_flux = sedimentation_flux(grid, q_r, rho_d, Tk)
+        adv = lambda v, bar_z=0.0: (-u * P(v, "r")) + (-w * (P(v, "z") + bar_z))
+        dif = lambda v: K * (P(v, "rr") + P(v, "zz"))
+        I = np.zeros((N, grid.V))
+        E[:, 0] = adv(1, R["sbar_z"]) + (s_cond + s_div) + dif(1)
+        E[:, 1] = adv(2, R["xibar_z"]) + (-P(4, "r") - P(5, "z"))
+        I[:, 1] = -P(5, "z")
+        E[:, 2] = adv(3, R["mubar_z"]) + (mu_factor * (q_evap - q_cond)) + dif(3)
+        I[:, 2] = q_v
+        E[:, 3] = adv(4) + (-dpdx / rho_t) + dif(4)
+        E[:, 4] = adv(5) + (((-TH["gravity"] * rho_p) - dpdz) / rho_t) + dif(5)
+        I[:, 4] = -(Pxi_bar * P(2, "z"))
+        E[:, 5] = adv(6) + (th_dmudq(P(6, "u"), q_c) * (q_cond - q_auto - q_coll)) + dif(6)
+        E[:, 6] = adv(7) + (th_dmudq(P(7, "u"), q_r) * (q_auto + q_coll - q_evap - Vt_flux)) + dif(7)
+        E[:, 7] = adv(8) + qss_cond
+        I[:, 7] = qss
+        if rates is not None:
+            rates.update(q_cond=q_cond, s_cond=s_cond, q_evap=q_evap, qss_cond=qss_cond, q_auto=q_auto, q_coll=q_coll,
+                         Vt_flux=Vt_flux)
     else:
         raise ValueError("equation set not in scope: " + eq)
     return E, I, phys
 
 
+
 class Model:
     """One patch split into radial tiles, stepped with the reference's per-step protocol
-    (src/semiimplicit.jl:258-332). Pure numpy; small cases only."""
+    (src/semiimplicit.jl:258-332). Pure numpy; small cases only.  rainfall_test runs condensation_adjustment after the
+    explicit and the semi-implicit step (src/testModels.jl:572-580); `elementwise = True` selects its point-by-point
+    clamp instead (not the reference)."""
+    elementwise = False
 
     def __init__(self, grid, equation_set, ts, params, tiles=None, semiimplicit=False, pxi_bar=0.0, helmholtz="extended"):
         """helmholtz = "extended": the Helmholtz operator inverted once in extended precision ("truth" arbiter: what the
@@ -815,6 +1086,8 @@ class Model:
             unp1, hs["e1"], hs["e2"] = explicit_timestep(t, self.ts, phys[:, :, 0], E, hs["e1"], hs["e2"])
             if self.semi:
                 unp1 = self._semiimplicit(i, t, unp1, I)
+            if self.eq == "rainfall_test":
+                unp1 = condensation_adjustment(unp1, self.par, g.zDim, self.elementwise)
             b = g.forward(unp1, c0, n)                                       # calcTendency
             g.add_tile_to_shared(shared, b, c0, n, i == len(self.tiles) - 1)
         self.A = g.spline_transform(shared)                                  # splineTransform!

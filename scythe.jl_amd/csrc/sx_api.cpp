@@ -134,6 +134,51 @@ static const int DERIV_SLOTS[4][7] = {
     {0, 1, 2, 3, 4, 5, 6},       // RLZ
 };
 
+// derivative kinds, in the column order of DERIV_SLOTS; h->slot[] maps them to the geometry's slots
+enum { KU = 1, KR = 2, KRR = 4, KL = 8, KLL = 16, KZ = 32, KZZ = 64 };
+enum { KRZ = KU | KR | KRR | KZ | KZZ, KRL = KU | KR | KRR | KL | KLL };     // every kind of an RZ / an RL grid
+enum { KURZ = KU | KR | KZ, KURL = KU | KR | KL };                            // value and first derivatives
+
+// What sx_create and sx_kernel_bytes need to know about an equation set: one row per SX_EQ_* id.
+struct EqSet {
+    int id;
+    const char *name;       // the reference's name (src/semiimplicit.jl:359-361)
+    int geom, min_vars;     // required geometry (-1: any) and the least number of variables
+    bool reads_H;           // reads params[SX_P_H] (include/scythe_hip.h, sx_model_desc.params)
+    bool needs_ref;         // needs sx_model_desc.ref_state
+    int semi_xi, semi_w;    // 1-based xi / w positions it requires when semi-implicit, 0 = any
+    bool diag_w;            // variable 6 is a diagnostic w: no tendency history (DESIGN.md "Slot masks")
+    int kinds[8];           // derivative kinds read by each of the first min_vars variables; the others read the value only
+};
+
+static const EqSet EQ_SETS[] = {
+    // id, name, geom, min_vars, reads_H, needs_ref, semi_xi, semi_w, diag_w, kinds per variable
+    {SX_EQ_LINEAR_ADVECTION_1D,  "LinearAdvection1D",                    SX_GEOM_R,   1, 0, 0, 0, 0, 0, {KU | KR | KRR}},
+    {SX_EQ_LINEAR_ADVECTION_RZ,  "LinearAdvectionRZ",                    SX_GEOM_RZ,  4, 0, 0, 0, 0, 0, {KRZ, KU, KU, KU}},
+    {SX_EQ_LINEAR_ADVECTION_RL,  "LinearAdvectionRL",                    SX_GEOM_RL,  3, 0, 0, 0, 0, 0, {KRL, KU, KU}},
+    {SX_EQ_LINEAR_ADVECTION_RLZ, "LinearAdvectionRLZ",                   SX_GEOM_RLZ, 3, 0, 0, 0, 0, 0, {KRL, KU, KU}},
+    {SX_EQ_ONEWAY_SW_SLAB,       "Oneway_ShallowWater_Slab",             SX_GEOM_RL,  6, 0, 0, 0, 0, 1, {KURL, KURL, KURL, KRL, KRL, 0}},
+    {SX_EQ_TWOWAY_SW_SLAB,       "Twoway_ShallowWater_Slab",             SX_GEOM_RL,  6, 0, 0, 0, 0, 1, {KURL, KURL, KURL, KRL, KRL, 0}},
+    {SX_EQ_ONEWAY_SW_HRBL,       "Oneway_ShallowWater_HeightResolvedBL", SX_GEOM_RLZ, 6, 0, 0, 0, 0, 1,
+     {KURL, KURL, KURL, KRL | KZ, KRL | KZ, 0}},
+    {SX_EQ_LINEAR_ACOUSTIC_RZ,   "LinearAcousticRZ",                     SX_GEOM_RZ,  5, 0, 0, 0, 0, 0, {KRZ, KURZ, KRZ, KRZ, KRZ}},
+    {SX_EQ_EULER_TEST,           "Euler_test",                           SX_GEOM_RZ,  5, 0, 1, 0, 0, 0, {KRZ, KURZ, KRZ, KRZ, KRZ}},
+    // src/shallowWaterModels.jl:253-254 and 291-293
+    {SX_EQ_LINEAR_SW_1D,         "LinearShallowWater1D",                 SX_GEOM_R,   2, 1, 0, 0, 0, 0, {KU | KR, KU | KR | KRR}},
+    {SX_EQ_LINEAR_SW_RL,         "LinearShallowWaterRL",                 SX_GEOM_RL,  3, 1, 0, 0, 0, 0, {KURL, KU | KR | KRR | KLL, KRL}},
+    // src/testModels.jl:404-455: xi and qss have no K diffusion.  Semi-implicit, the tendency writes the implicit terms by
+    // position (src/testModels.jl:545-566) while the adjustment finds xi and w by name: hence the fixed xi / w
+    {SX_EQ_RAINFALL_TEST,        "rainfall_test",                        SX_GEOM_RZ,  8, 0, 1, 2, 5, 0,
+     {KRZ, KURZ, KRZ, KRZ, KRZ, KRZ, KRZ, KURZ}},
+    {SX_EQ_NONE,                 "None",                                 -1,          1, 0, 0, 0, 0, 0, {KU}},
+};
+
+static const EqSet *eq_set(int id) {
+    for (const EqSet &e : EQ_SETS)
+        if (e.id == id) return &e;
+    return nullptr;
+}
+
 static int default_bzdim(int zDim) {
     int b = (int)std::floor((2.0 * zDim - 1.0) / 3.0) + 1;
     return std::min(zDim, b);
@@ -154,24 +199,10 @@ const char *sx_last_error(void) { return g_err.c_str(); }
 int sx_abi_version(void) { return SX_ABI_VERSION; }
 
 int sx_equation_set_id(const char *name) {
-    static const std::map<std::string, int> ids = {
-        {"LinearAdvection1D", SX_EQ_LINEAR_ADVECTION_1D},
-        {"LinearAdvectionRZ", SX_EQ_LINEAR_ADVECTION_RZ},
-        {"LinearAdvectionRL", SX_EQ_LINEAR_ADVECTION_RL},
-        {"LinearAdvectionRLZ", SX_EQ_LINEAR_ADVECTION_RLZ},
-        {"Oneway_ShallowWater_Slab", SX_EQ_ONEWAY_SW_SLAB},
-        {"Twoway_ShallowWater_Slab", SX_EQ_TWOWAY_SW_SLAB},
-        {"Oneway_ShallowWater_HeightResolvedBL", SX_EQ_ONEWAY_SW_HRBL},
-        {"LinearAcousticRZ", SX_EQ_LINEAR_ACOUSTIC_RZ},
-        {"Euler_test", SX_EQ_EULER_TEST},
-        {"LinearShallowWater1D", SX_EQ_LINEAR_SW_1D},
-        {"LinearShallowWaterRL", SX_EQ_LINEAR_SW_RL},
-        {"rainfall_test", SX_EQ_RAINFALL_TEST},
-        {"None", SX_EQ_NONE},
-    };
-    if (!name) return -1;
-    auto it = ids.find(name);
-    return it == ids.end() ? -1 : it->second;
+    if (name)
+        for (const EqSet &e : EQ_SETS)
+            if (!std::strcmp(e.name, name)) return e.id;
+    return -1;
 }
 
 static int tile_sizes(const sx_grid_desc *g, int n, std::vector<int> &cells) {
@@ -307,43 +338,34 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     // model
     h->ts = m->ts; h->eq = m->equation_set; h->semi = m->semiimplicit;
     h->w_index = m->w_index; h->xi_index = m->xi_index; h->col_var = m->col_var > 0 ? m->col_var : 1;
+    const EqSet *es = eq_set(h->eq);
+    if (!es) { set_error("equation set not in scope"); delete h; return 1; }
     if (m->params) {
         // the 12 entries up to SX_P_PXI_BAR always; SX_P_H only for the sets that read it, so that a caller built against the
         // 12-entry table never has a 13th double read (include/scythe_hip.h, sx_model_desc.params)
         std::memcpy(h->par, m->params, sizeof(double) * (SX_P_PXI_BAR + 1));
-        if (h->eq == SX_EQ_LINEAR_SW_1D || h->eq == SX_EQ_LINEAR_SW_RL) h->par[SX_P_H] = m->params[SX_P_H];
+        if (es->reads_H) h->par[SX_P_H] = m->params[SX_P_H];
     }
-    {
-        const int eq = h->eq;
-        const int need_geom = (eq == SX_EQ_LINEAR_ADVECTION_1D || eq == SX_EQ_LINEAR_SW_1D) ? SX_GEOM_R
-                            : (eq == SX_EQ_LINEAR_ADVECTION_RZ || eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST ||
-                               eq == SX_EQ_RAINFALL_TEST) ? SX_GEOM_RZ
-                            : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB ||
-                               eq == SX_EQ_LINEAR_SW_RL) ? SX_GEOM_RL
-                            : (eq == SX_EQ_LINEAR_ADVECTION_RLZ || eq == SX_EQ_ONEWAY_SW_HRBL) ? SX_GEOM_RLZ : -1;
-        const int need_vars = (eq == SX_EQ_LINEAR_ADVECTION_RZ) ? 4
-                            : (eq == SX_EQ_LINEAR_ADVECTION_RL || eq == SX_EQ_LINEAR_ADVECTION_RLZ || eq == SX_EQ_LINEAR_SW_RL) ? 3
-                            : (eq == SX_EQ_ONEWAY_SW_SLAB || eq == SX_EQ_TWOWAY_SW_SLAB || eq == SX_EQ_ONEWAY_SW_HRBL) ? 6
-                            : (eq == SX_EQ_LINEAR_ACOUSTIC_RZ || eq == SX_EQ_EULER_TEST) ? 5
-                            : (eq == SX_EQ_LINEAR_SW_1D) ? 2
-                            : (eq == SX_EQ_RAINFALL_TEST) ? 8 : 1;
-        if (eq != SX_EQ_NONE && need_geom < 0) { set_error("equation set not in scope"); delete h; return 1; }
-        if (eq != SX_EQ_NONE && (need_geom != h->geom || h->V < need_vars)) {
-            set_error("equation set does not match the grid geometry / variable count");
-            delete h;
-            return 1;
-        }
-        if (h->semi && (!h->has_z || h->w_index < 1 || h->xi_index < 1 || h->w_index > h->V || h->xi_index > h->V || h->Zb != h->nz)) {
-            set_error("semi-implicit adjustment needs an RZ/RLZ grid, w and xi variables and b_zDim == zDim");
-            delete h;
-            return 1;
-        }
-        if (eq == SX_EQ_RAINFALL_TEST && h->semi && (h->xi_index != 2 || h->w_index != 5)) {
-            // the tendency writes the implicit terms by position (src/testModels.jl:545-566), the adjustment finds xi and w by name
-            set_error("rainfall_test with semiimplicit needs xi = variable 2 and w = variable 5");
-            delete h;
-            return 1;
-        }
+    if (es->geom >= 0 && (es->geom != h->geom || h->V < es->min_vars)) {
+        set_error("equation set does not match the grid geometry / variable count");
+        delete h;
+        return 1;
+    }
+    if (h->semi && (!h->has_z || h->w_index < 1 || h->xi_index < 1 || h->w_index > h->V || h->xi_index > h->V || h->Zb != h->nz)) {
+        set_error("semi-implicit adjustment needs an RZ/RLZ grid, w and xi variables and b_zDim == zDim");
+        delete h;
+        return 1;
+    }
+    if (h->semi && es->semi_xi && (h->xi_index != es->semi_xi || h->w_index != es->semi_w)) {
+        set_error(std::string(es->name) + " with semiimplicit needs xi = variable " + std::to_string(es->semi_xi) +
+                  " and w = variable " + std::to_string(es->semi_w));
+        delete h;
+        return 1;
+    }
+    if (es->needs_ref && !m->ref_state) {
+        set_error(std::string(es->name) + " needs sx_model_desc.ref_state (ReferenceState)");
+        delete h;
+        return 1;
     }
 #define FAIL()            \
     do {                  \
@@ -503,11 +525,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         if (!upload(h, &h->d_z, one)) FAIL();
     }
 
-    if (h->eq == SX_EQ_EULER_TEST || h->eq == SX_EQ_RAINFALL_TEST) {
-        if (!m->ref_state) {
-            set_error(std::string(h->eq == SX_EQ_EULER_TEST ? "Euler_test" : "rainfall_test") + " needs sx_model_desc.ref_state (ReferenceState)");
-            FAIL();
-        }
+    if (es->needs_ref) {
         std::vector<double> ref(m->ref_state, m->ref_state + (size_t)9 * h->nz);
         if (!upload(h, &h->d_ref, ref)) FAIL();
     }
@@ -541,34 +559,11 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         const int u = 1 << h->slot[0], r = 1 << h->slot[1], rr = 1 << h->slot[2];
         const int l = h->has_l ? 1 << h->slot[3] : 0, ll = h->has_l ? 1 << h->slot[4] : 0;
         const int z = h->has_z ? 1 << h->slot[5] : 0, zz = h->has_z ? 1 << h->slot[6] : 0;
-        std::vector<int> full(h->V, (1 << h->D) - 1), eq(h->V, u);
-        switch (h->eq) {
-            case SX_EQ_LINEAR_ADVECTION_1D: eq[0] = u | r | rr; break;
-            case SX_EQ_LINEAR_ADVECTION_RZ: eq[0] = u | r | rr | z | zz; break;
-            case SX_EQ_LINEAR_ADVECTION_RL: case SX_EQ_LINEAR_ADVECTION_RLZ: eq[0] = u | r | rr | l | ll; break;
-            case SX_EQ_ONEWAY_SW_SLAB: case SX_EQ_TWOWAY_SW_SLAB: case SX_EQ_ONEWAY_SW_HRBL:
-                eq[0] = eq[1] = eq[2] = u | r | l;
-                eq[3] = eq[4] = u | r | rr | l | ll | (h->eq == SX_EQ_ONEWAY_SW_HRBL ? z : 0);
-                eq[5] = 0;        // w is diagnostic: written by the equation set before it is read
-                break;
-            case SX_EQ_LINEAR_ACOUSTIC_RZ: case SX_EQ_EULER_TEST:
-                eq[0] = eq[2] = eq[3] = eq[4] = u | r | rr | z | zz;
-                eq[1] = u | r | z;
-                break;
-            case SX_EQ_RAINFALL_TEST:         // src/testModels.jl:404-455: xi and qss have no K diffusion
-                for (int v = 0; v < 8; v++) eq[v] = u | r | rr | z | zz;
-                eq[1] = eq[7] = u | r | z;
-                break;
-            case SX_EQ_LINEAR_SW_1D:          // src/shallowWaterModels.jl:253-254
-                eq[0] = u | r;
-                eq[1] = u | r | rr;
-                break;
-            case SX_EQ_LINEAR_SW_RL:          // src/shallowWaterModels.jl:291-293
-                eq[0] = u | r | l;
-                eq[1] = u | r | rr | ll;
-                eq[2] = u | r | rr | l | ll;
-                break;
-            default: break;
+        std::vector<int> full(h->V, (1 << h->D) - 1), eq(h->V);
+        for (int v = 0; v < h->V; v++) {
+            const int kinds = v < es->min_vars ? es->kinds[v] : KU;
+            for (int k = 0; k < 7; k++)
+                if ((kinds >> k & 1) && h->slot[k] >= 0) eq[v] |= 1 << h->slot[k];
         }
         for (int v = 0; v < h->V; v++) {
             h->mask_full_bits += __builtin_popcount(full[v]);
@@ -1360,7 +1355,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_phys_pointwise" || k == "k_phys_hrbl") {
         // read the requested slots, E_nm1, E_nm2; write E_n, var_np1; the SW sets also write the diagnostic w plane and
         // keep no tendency history for it
-        const bool sw = (h->eq == SX_EQ_ONEWAY_SW_SLAB || h->eq == SX_EQ_TWOWAY_SW_SLAB || h->eq == SX_EQ_ONEWAY_SW_HRBL);
+        const bool sw = eq_set(h->eq)->diag_w;
         b = N * (eq_planes + w * (4.0 * V + (sw ? -3.0 : 0.0)));        // inside sx_advance the diagnostic w plane is not stored
     }
     else if (k == "k_fl_forward") b = w * N * V + wi * fl;

@@ -1,47 +1,10 @@
-"""LinearShallowWater1D and LinearShallowWaterRL (src/shallowWaterModels.jl:235-298) for the tests: the tendency restated in numpy
-for the oracle twin, the cases, and the closed-form solutions the sets admit.
-
-oracle/oracle_np.py knows only the sets it was written for and stays as it is.  `patch_oracle(monkeypatch)` wraps its module-level
-`tendency`, which `Model.step` looks up as a global, so that the twin runs the two new sets and delegates every other name."""
+"""LinearShallowWater1D and LinearShallowWaterRL (src/shallowWaterModels.jl:235-298) for the tests: the variable maps, the cases
+and the closed-form solutions the sets admit.  The tendency lives in oracle/oracle_np.py with the other equation sets."""
 import numpy as np
-
-from oracle import oracle_np as O
 
 SETS = ("LinearShallowWater1D", "LinearShallowWaterRL")
 VARS_1D = {"h": 1, "u": 2}
 VARS_RL = {"h": 1, "u": 2, "v": 3}
-
-
-def tendency(grid, eq, par, phys, pts):
-    """The reference's expressions term by term, in the reference's order of operations (the library's k_phys_pointwise
-    evaluates the same ones)."""
-    E = np.zeros((phys.shape[0], grid.V))
-    P = lambda v, s: phys[:, v - 1, grid.slots.index(s)]
-    g, K, H = par["g"], par["K"], par["H"]
-    if eq == "LinearShallowWater1D":                # src/shallowWaterModels.jl:253-254
-        E[:, 0] = -H * P(2, "r")
-        E[:, 1] = (-g * P(1, "r")) + (K * P(2, "rr"))
-    elif eq == "LinearShallowWaterRL":              # src/shallowWaterModels.jl:291-293 (no -u / r^2 term)
-        r = pts[:, 0]
-        u, ur, urr, ull = P(2, "u"), P(2, "r"), P(2, "rr"), P(2, "ll")
-        vr, vrr, vl, vll = P(3, "r"), P(3, "rr"), P(3, "l"), P(3, "ll")
-        E[:, 0] = -H * ((u / r) + ur + (vl / r))
-        E[:, 1] = (-g * P(1, "r")) + (K * ((ur / r) + urr + (ull / (r * r))))
-        E[:, 2] = (-g * (P(1, "l") / r)) + (K * ((vr / r) + vrr + (vll / (r * r))))
-    else:
-        raise ValueError(eq)
-    return E, None, phys
-
-
-def patch_oracle(monkeypatch):
-    """Route the two new names of oracle_np.tendency to `tendency` above for the duration of one test."""
-    original = O.tendency
-
-    def wrapped(grid, eq, par, phys, pts, col_ops=None):
-        if eq in SETS:
-            return tendency(grid, eq, par, phys, pts)
-        return original(grid, eq, par, phys, pts, col_ops)
-    monkeypatch.setattr(O, "tendency", wrapped)
 
 
 # ----------------------------------------------------------------------------- cases (tests/cases.py dictionaries)

@@ -1,5 +1,5 @@
 """-m gpu: LinearShallowWater1D and LinearShallowWaterRL (src/shallowWaterModels.jl:235-298) on the HIP path - against the numpy
-oracle twin running the restated tendency (tests/linear_sw.py), against closed-form gravity waves, through restart and
+oracle twin running the restated tendency (oracle/oracle_np.py), against closed-form gravity waves, through restart and
 integrate_model, and the refusals of sx_create.
 
 The linear gravity wave is the suite's one exact, oscillating, multi-variable solution on an RL grid: h drives v through its
@@ -22,10 +22,9 @@ def _advance(model, steps):
     return model.physical()
 
 
-def _parity(monkeypatch, case, steps, num_tiles=1, exchange="a2a", impl="torch", oracle=None):
+def _parity(case, steps, num_tiles=1, exchange="a2a", impl="torch", oracle=None):
     """rel_err_per_var of the HIP run against the one-patch oracle twin after `steps` steps; `oracle` = that twin's result if
     already computed for this case.  Also checks that the run changed every variable (the comparison is not of two idle states)."""
-    LS.patch_oracle(monkeypatch)
     hip = cases.HipModel(case, num_tiles=num_tiles, exchange=exchange, impl=impl)
     p0 = hip.physical().copy()
     a = _advance(hip, steps)
@@ -39,18 +38,18 @@ def _parity(monkeypatch, case, steps, num_tiles=1, exchange="a2a", impl="torch",
 
 
 @pytest.mark.parametrize("bc", ["PERIODIC", "walls"])
-def test_linear_shallow_water_1d_matches_the_oracle_twin(monkeypatch, bc):
+def test_linear_shallow_water_1d_matches_the_oracle_twin(bc):
     """R grid, 40 steps: PERIODIC, and walls (u R1T0, h R1T1 at both ends)."""
-    err, _ = _parity(monkeypatch, LS.r_case(num_cells=24, bc=bc), 40)
+    err, _ = _parity(LS.r_case(num_cells=24, bc=bc), 40)
     print("\nLinearShallowWater1D %s: %.2e" % (bc, err))
     assert err < TOL
 
 
 @pytest.mark.parametrize("ring_L", [None, 16, 32, 24, 12])
-def test_linear_shallow_water_rl_matches_the_oracle_twin(monkeypatch, ring_L):
+def test_linear_shallow_water_rl_matches_the_oracle_twin(ring_L):
     """RL grid, 40 steps: native ragged rings (DFT kernels), uniform power-of-two tables (FFT kernels), uniform tables of a
     multiple of 4 that is not a power of two (DFT kernels on a uniform table); wavenumbers 1-3 in every variable."""
-    err, _ = _parity(monkeypatch, LS.rl_case(num_cells=10, ring_L=ring_L), 40)
+    err, _ = _parity(LS.rl_case(num_cells=10, ring_L=ring_L), 40)
     print("\nLinearShallowWaterRL ring_L=%s: %.2e" % (ring_L, err))
     assert err < TOL
 
@@ -61,11 +60,11 @@ _ORACLE = {}
 @pytest.mark.parametrize("num_cells,ntiles", [(20, 2), (30, 3)])
 @pytest.mark.parametrize("exchange", ["a2a", "iface", "gather"])
 @pytest.mark.parametrize("impl", ["lib", "torch"])
-def test_linear_shallow_water_rl_on_tiles_matches_the_one_patch_oracle_twin(monkeypatch, num_cells, ntiles, exchange, impl):
+def test_linear_shallow_water_rl_on_tiles_matches_the_one_patch_oracle_twin(num_cells, ntiles, exchange, impl):
     """Native rings split into 2 and 3 tiles (gridpoint-balanced), every exchange protocol through the library's own buffers
     (loopback) and through the Python-side stand-in, 20 steps against the one-patch twin (computed once per patch)."""
     case = LS.rl_case(num_cells=num_cells)
-    err, _ORACLE[num_cells] = _parity(monkeypatch, case, 20, num_tiles=ntiles, exchange=exchange, impl=impl,
+    err, _ORACLE[num_cells] = _parity(case, 20, num_tiles=ntiles, exchange=exchange, impl=impl,
                                       oracle=_ORACLE.get(num_cells))
     print("\n%d cells, %d tiles, %s / %s: %.2e" % (num_cells, ntiles, exchange, impl, err))
     assert err < TOL
@@ -243,10 +242,9 @@ def draw(rng):
     return case, tiles, exchange, impl
 
 
-def test_seeded_random_linear_shallow_water_configurations(monkeypatch):
+def test_seeded_random_linear_shallow_water_configurations():
     """12 seeded draws, 10 steps each, against the one-patch oracle twin at 1e-10 in every variable and slot."""
     import scythe_jl_amd as S
-    LS.patch_oracle(monkeypatch)
     rng = np.random.default_rng(20261016)
     bad, compared = [], 0
     for i in range(12):

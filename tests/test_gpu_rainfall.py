@@ -1,5 +1,5 @@
 """-m gpu: rainfall_test (src/testModels.jl:387-585 + condensation_adjustment, src/microphysics.jl:139-195) on the HIP path -
-against the numpy oracle twin (tests/rainfall.py) on one patch and on tiles, the whole-column clamp against a pointwise one, graph
+against the numpy oracle twin (oracle/oracle_np.py) on one patch and on tiles, the whole-column clamp against a pointwise one, graph
 replay, a sounding file, integrate_model and restart, fp32 derivative planes, the refusals of sx_create and a seeded sweep."""
 import os
 
@@ -26,10 +26,9 @@ def _twin(case, steps, elementwise=False):
     return _advance(m, steps)
 
 
-def _parity(monkeypatch, case, steps, num_tiles=1, exchange="a2a", impl="torch", oracle=None):
+def _parity(case, steps, num_tiles=1, exchange="a2a", impl="torch", oracle=None):
     """rel_err_per_var of the HIP run against the one-patch oracle twin after `steps` steps, and that twin's result; also checks
     that the run changed every variable."""
-    RF.patch_oracle(monkeypatch)
     hip = cases.HipModel(case, num_tiles=num_tiles, exchange=exchange, impl=impl)
     p0 = hip.physical().copy()
     a = _advance(hip, steps)
@@ -43,10 +42,10 @@ def _parity(monkeypatch, case, steps, num_tiles=1, exchange="a2a", impl="torch",
 
 
 @pytest.mark.parametrize("semi,zDim", [(True, 12), (False, 12), (True, 14), (False, 16)])
-def test_rainfall_matches_the_oracle_twin(monkeypatch, semi, zDim):
+def test_rainfall_matches_the_oracle_twin(semi, zDim):
     """12 steps (Euler, AB2, then AB3) with and without the semi-implicit adjustment, at 12, 14 and 16 levels (two groups of
     columns per workgroup of k_condensation that are not a power of two)."""
-    err, _ = _parity(monkeypatch, RF.rz_rain(semiimplicit=semi, zDim=zDim), 12)
+    err, _ = _parity(RF.rz_rain(semiimplicit=semi, zDim=zDim), 12)
     print("\nrainfall_test semi=%s zDim=%d: %.2e" % (semi, zDim, err))
     assert err < TOL
 
@@ -57,21 +56,20 @@ _ORACLE = {}
 @pytest.mark.parametrize("num_cells,ntiles", [(20, 2), (30, 3)])
 @pytest.mark.parametrize("exchange", ["a2a", "iface", "gather"])
 @pytest.mark.parametrize("impl", ["lib", "torch"])
-def test_rainfall_on_tiles_matches_the_one_patch_oracle_twin(monkeypatch, num_cells, ntiles, exchange, impl):
+def test_rainfall_on_tiles_matches_the_one_patch_oracle_twin(num_cells, ntiles, exchange, impl):
     """2 and 3 tiles, every exchange protocol through the library's own buffers and through the Python-side stand-in, 12 steps
     against the one-patch twin (computed once per patch)."""
     case = RF.rz_rain(num_cells=num_cells)
-    err, _ORACLE[num_cells] = _parity(monkeypatch, case, 12, num_tiles=ntiles, exchange=exchange, impl=impl,
+    err, _ORACLE[num_cells] = _parity(case, 12, num_tiles=ntiles, exchange=exchange, impl=impl,
                                       oracle=_ORACLE.get(num_cells))
     print("\n%d cells, %d tiles, %s / %s: %.2e" % (num_cells, ntiles, exchange, impl, err))
     assert err < TOL
 
 
 @pytest.mark.parametrize("semi", [True, False])
-def test_condensation_adjustment_clamps_whole_columns(monkeypatch, semi):
+def test_condensation_adjustment_clamps_whole_columns(semi):
     """rz_rain_mixed, 3 steps: the twin's whole-column clamp and a pointwise one differ by more than 1e-6, and the GPU follows the
     whole-column one to 1e-10."""
-    RF.patch_oracle(monkeypatch)
     case = RF.rz_rain_mixed(semiimplicit=semi)
     col, pw = _twin(case, 3), _twin(case, 3, elementwise=True)
     apart = cases.rel_err_per_var(pw, col)
@@ -106,11 +104,10 @@ def test_step_replayed_from_a_hip_graph_is_bit_identical(monkeypatch):
     graph.run.close()
 
 
-def test_rainfall_with_reference_state_built_from_a_sounding_file(monkeypatch, tmp_path):
+def test_rainfall_with_reference_state_built_from_a_sounding_file(tmp_path):
     """ModelParameters.ref_state_file -> interpolate_reference_file -> ReferenceState on the device (Pxi_bar from the reference
     state), then the same run in the twin fed with the same profiles."""
     import scythe_jl_amd as S
-    RF.patch_oracle(monkeypatch)
     case = RF.rz_rain(num_cells=6, zDim=16)
     f = tmp_path / "sounding.txt"
     f.write_text("1000.0 300.0 16.0\n" + "".join("%g %g %g\n" % (a, 300.0 + 4.0e-3 * a, 16.0 * np.exp(-a / 2.5e3))
@@ -177,10 +174,9 @@ def test_integrate_model_output_and_restart(tmp_path):
     assert np.array_equal(whole, halves)
 
 
-def test_fp32_derivative_planes_follow_the_twin(monkeypatch):
+def test_fp32_derivative_planes_follow_the_twin():
     """storage="f32": k_phys_rain<float> reads fp32 derivative slots (values, state and arithmetic stay fp64); after 12 steps the
     values are within the suite's fp32 bound of the fp64 twin, and not bit-equal to it (the fp32 path ran)."""
-    RF.patch_oracle(monkeypatch)
     case = RF.rz_rain(num_cells=8, zDim=16)
     hip = cases.HipModel(case, storage="f32")
     a = _advance(hip, 12)
@@ -245,11 +241,10 @@ def draw(rng):
     return case, tiles, exchange, impl
 
 
-def test_seeded_random_rainfall_configurations(monkeypatch):
+def test_seeded_random_rainfall_configurations():
     """10 seeded draws (cells, 6 - 20 levels, tiles, exchange, K, time step, semi-implicit or not), 6 steps each, against the
     one-patch oracle twin at 1e-10 in every variable and slot (the d2/dz2 slot at 20 levels: 1e-10 (zDim / 16)^4)."""
     import scythe_jl_amd as S
-    RF.patch_oracle(monkeypatch)
     rng = np.random.default_rng(20261016)
     bad, compared = [], 0
     for i in range(10):

@@ -1,6 +1,6 @@
 """CPU-only: LinearShallowWater1D and LinearShallowWaterRL (src/shallowWaterModels.jl:235-298) through the host side of the library -
 the equation-set names, the parameter table's three mirrors (C header, Python, Julia), and the numpy restatement of the two sets
-(tests/linear_sw.py) on the oracle twin against the closed-form periodic 1D mode, with the parameters the Python mirror packs for
+(oracle/oracle_np.py) on the oracle twin against the closed-form periodic 1D mode, with the parameters the Python mirror packs for
 sx_create."""
 import os
 import re
@@ -73,10 +73,9 @@ def _packed_params(case):
     return dict(zip(_lib.PARAM_ORDER, list(keep["par"])))
 
 
-def periodic_mode_error(monkeypatch, num_cells, ts, steps, K, m=2, g=2.0, H=0.5):
+def periodic_mode_error(num_cells, ts, steps, K, m=2, g=2.0, H=0.5):
     """Oracle twin (numpy restatement of LinearShallowWater1D) on the PERIODIC line [-6, 6], started from the right-moving
     gravity wave h = cos(kap x), u = sqrt(g / H) cos(kap x); error of h and of u / sqrt(g / H) against tests/linear_sw.py::mode_1d."""
-    LS.patch_oracle(monkeypatch)
     kap = 2.0 * np.pi * m / 12.0
     u0 = np.sqrt(g / H) + 0.0j
     keep = {}
@@ -98,10 +97,10 @@ def periodic_mode_error(monkeypatch, num_cells, ts, steps, K, m=2, g=2.0, H=0.5)
 
 
 @pytest.mark.parametrize("K", [0.0, 0.05])
-def test_numpy_restatement_follows_the_exact_periodic_mode(monkeypatch, K):
+def test_numpy_restatement_follows_the_exact_periodic_mode(K):
     """24 cells, 150 steps of 0.02: the wave (c = sqrt(g H) = 1, wavelength 6) travels half a wavelength, h changes by ~2;
     the twin stays within 3.3e-3 of the 2 x 2 matrix-exponential solution (the spline's truncation error at kap DX = 0.52) -
     a wrong sign, a swapped g / H or a missing term is an O(1) difference."""
-    err, change = periodic_mode_error(monkeypatch, 24, 0.02, 150, K)
+    err, change = periodic_mode_error(24, 0.02, 150, K)
     print("\nLinearShallowWater1D twin, K = %g: h changed by %.2f, error %.2e" % (K, change, err))
     assert change > 1.8 and err < 1e-2

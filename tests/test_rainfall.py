@@ -1,9 +1,10 @@
 """rainfall_test (src/testModels.jl:387-585) without a GPU: the name, the numpy restatement of the warm-rain thermodynamics
-(tests/rainfall.py), the reference's zero sedimentation flux, Julia's whole-column min / max of condensation_adjustment, a twin
+(oracle/oracle_np.py), the reference's zero sedimentation flux, Julia's whole-column min / max of condensation_adjustment, a twin
 run that exercises every process, and the host descriptor."""
 import numpy as np
 import pytest
 
+from oracle import oracle_np as O
 from tests import cases
 from tests import rainfall as RF
 
@@ -21,10 +22,10 @@ def test_buck_derivative_and_latent_heat():
     Tk = np.linspace(230.0, 310.0, 41)
     for p in (300.0, 700.0, 1013.0):
         h = 1e-3
-        fd = (RF.sat_pressure_liquid_buck(Tk + h, p) - RF.sat_pressure_liquid_buck(Tk - h, p)) / (2.0 * h)
-        an = RF.sat_pressure_liquid_buck_dT(Tk, p)
+        fd = (O.th_sat_pressure_liquid_buck(Tk + h, p) - O.th_sat_pressure_liquid_buck(Tk - h, p)) / (2.0 * h)
+        an = O.th_sat_pressure_liquid_buck_dT(Tk, p)
         assert np.abs(fd / an - 1.0).max() < 1e-7
-    assert RF.L_v(RF.TH["T_0"]) == RF.TH["L_v0"]
+    assert O.th_L_v(O.TH["T_0"]) == O.TH["L_v0"]
 
 
 def test_sedimentation_flux_is_exactly_zero():
@@ -38,8 +39,8 @@ def test_sedimentation_flux_is_exactly_zero():
         q_r = scale * rng.random(n)
         rho_d = rng.uniform(0.3, 1.3, n)
         Tk = rng.uniform(200.0, 310.0, n)
-        assert np.all(RF.sedimentation(q_r, rho_d, Tk) == 0.0)
-        assert np.all(RF.sedimentation_flux(g, q_r, rho_d, Tk) == 0.0)
+        assert np.all(O.th_sedimentation(q_r, rho_d, Tk) == 0.0)
+        assert np.all(O.sedimentation_flux(g, q_r, rho_d, Tk) == 0.0)
 
 
 def test_column_min_max_are_lexicographic():
@@ -50,7 +51,7 @@ def test_column_min_max_are_lexicographic():
         nz = int(rng.integers(1, 9))
         x = rng.integers(-2, 3, size=(6, nz)).astype(float) * 0.5 + 1.0   # many ties, no zeros
         y = rng.integers(-2, 3, size=(6, nz)).astype(float) * 0.5 + 1.0
-        mn, mx = RF.column_min(x, y), RF.column_max(x, y)
+        mn, mx = O.column_min(x, y), O.column_max(x, y)
         for r in range(6):
             assert list(mn[r]) == min(list(x[r]), list(y[r]))
             assert list(mx[r]) == max(list(x[r]), list(y[r]))
@@ -62,20 +63,20 @@ def test_column_min_max_use_julias_isequal_and_isless():
     x = np.array([[-0.0, 5.0, 1.0]])
     y = np.array([[0.0, 1.0, 1.0]])
     assert min([-0.0, 5.0, 1.0], [0.0, 1.0, 1.0]) == [0.0, 1.0, 1.0]          # Python: ties at level 0, decides at level 1
-    assert np.array_equal(RF.column_min(x, y), x) and np.signbit(RF.column_min(x, y)[0, 0])
-    assert np.array_equal(RF.column_max(x, y), y) and not np.signbit(RF.column_max(x, y)[0, 0])
+    assert np.array_equal(O.column_min(x, y), x) and np.signbit(O.column_min(x, y)[0, 0])
+    assert np.array_equal(O.column_max(x, y), y) and not np.signbit(O.column_max(x, y)[0, 0])
     a = np.array([[np.nan, 1.0]])
     b = np.array([[np.nan, 2.0]])
-    assert np.array_equal(RF.column_min(a, b), a, equal_nan=True)             # NaN level is equal: level 1 decides
+    assert np.array_equal(O.column_min(a, b), a, equal_nan=True)             # NaN level is equal: level 1 decides
     c = np.array([[1e300, 0.0]])
-    assert np.array_equal(RF.column_max(a, c), a, equal_nan=True)             # NaN above every number
-    assert np.array_equal(RF.column_min(a, c), c)
+    assert np.array_equal(O.column_max(a, c), a, equal_nan=True)             # NaN above every number
+    assert np.array_equal(O.column_min(a, c), c)
     same = np.array([[1.0, 2.0]])
-    assert not RF.column_isless(same, same.copy())[0]                        # equal columns: the first argument stays
+    assert not O.column_isless(same, same.copy())[0]                        # equal columns: the first argument stays
     # the scalar min / max of q_condensation stay elementwise, with -0.0 < 0.0 and NaN propagating
-    assert np.signbit(RF.jl_min(0.0, -0.0)) and not np.signbit(RF.jl_max(-0.0, 0.0))
-    assert np.isnan(RF.jl_min(np.nan, 1.0)) and np.isnan(RF.jl_max(1.0, np.nan))
-    assert np.array_equal(RF.jl_min([1.0, 3.0], [2.0, 2.0]), [1.0, 2.0])
+    assert np.signbit(O.jl_min(0.0, -0.0)) and not np.signbit(O.jl_max(-0.0, 0.0))
+    assert np.isnan(O.jl_min(np.nan, 1.0)) and np.isnan(O.jl_max(1.0, np.nan))
+    assert np.array_equal(O.jl_min([1.0, 3.0], [2.0, 2.0]), [1.0, 2.0])
 
 
 @pytest.mark.parametrize("semi", [True, False])
@@ -83,22 +84,21 @@ def test_twin_run_exercises_every_process(monkeypatch, semi):
     """10 steps of the oracle twin stay finite and every microphysical rate of the tendency - condensation, its entropy
     source, rain evaporation, the qss source, autoconversion, collection - is non-zero somewhere, as is the adjustment's
     q_cond; mu + mubar stays positive (q_v = 0 gives NaN in the reference, and no guard is added)."""
-    RF.patch_oracle(monkeypatch)
     case = RF.rz_rain(semiimplicit=semi)
     m = cases.OracleModel(case, numpy_twin=True)
     seen = {}
     adj = []
-    orig = RF.condensation_adjustment
+    orig = O.condensation_adjustment
 
     def spy(np1, par, nz, elementwise=False):
         out = orig(np1, par, nz, elementwise)
         adj.append(np.abs(out[:, 5] - np1[:, 5]).max())
         return out
-    monkeypatch.setattr(RF, "condensation_adjustment", spy)
+    monkeypatch.setattr("oracle.oracle_np.condensation_adjustment", spy)
     nz = case["grid"]["zDim"]
     for _ in range(10):
         ph = m.physical()
-        for k, v in RF.rates(m.g, case["par"], ph).items():
+        for k, v in O.rain_rates(m.g, case["par"], ph).items():
             seen[k] = max(seen.get(k, 0.0), np.abs(v).max())
         mubar = case["par"]["ref_state"]["mubar"][np.arange(len(ph)) % nz, 0]
         assert (ph[:, 2, 0] + mubar).min() > 0.0
@@ -109,20 +109,19 @@ def test_twin_run_exercises_every_process(monkeypatch, semi):
     assert len(adj) == 10 and min(adj) > 0.0
 
 
-def test_mixed_case_tells_the_column_rule_from_a_pointwise_one(monkeypatch):
+def test_mixed_case_tells_the_column_rule_from_a_pointwise_one():
     """rz_rain_mixed: some columns keep the raw q_cond, some take -q_c, and the run after 3 steps differs by O(1) from one that
     clamps point by point."""
-    RF.patch_oracle(monkeypatch)
     case = RF.rz_rain_mixed()
     a = cases.OracleModel(case, numpy_twin=True)
     b = cases.OracleModel(case, numpy_twin=True)
     b.m.elementwise = True
     ph = a.physical()
-    R = RF._levels(case["par"], len(ph), 12)
-    T = RF.thermo_state(*(ph[:, v, 0] for v in (0, 1, 2, 5, 6)), R["sbar"], R["xibar"], R["mubar"])
-    q_cond = ((T["q_v"] - RF.q_sat_liquid(T["Tk"], T["p"]) - ph[:, 7, 0]) /
-              (1.0 + RF.Q_s_factor(T["Tk"], T["p"], T["q_v"], T["q_l"]))).reshape(-1, 12)
-    takes = RF.column_isless(q_cond, (-T["q_c"]).reshape(-1, 12))
+    R = O.ref_levels(case["par"], len(ph), 12)
+    T = O.thermo_state(*(ph[:, v, 0] for v in (0, 1, 2, 5, 6)), R["sbar"], R["xibar"], R["mubar"])
+    q_cond = ((T["q_v"] - O.th_q_sat_liquid(T["Tk"], T["p"]) - ph[:, 7, 0]) /
+              (1.0 + O.th_Q_s_factor(T["Tk"], T["p"], T["q_v"], T["q_l"]))).reshape(-1, 12)
+    takes = O.column_isless(q_cond, (-T["q_c"]).reshape(-1, 12))
     assert 0 < takes.sum() < len(takes)
     for _ in range(3):
         a.step()
