@@ -498,6 +498,57 @@ def inverse_xp(grid, A, rings, cell0=0):
     return out
 
 
+def forward_xp(grid, values, cell0=0, ncells=None):
+    """Grid.forward (spectralTransform!: vertical CB, ring FB, radial quadrature ph0^T (W F)) in EXTENDED precision from the
+    Float64 values of the tile (cell0, ncells): the operators are formed in longdouble from their exact definitions (the
+    Chebyshev CB of Cheb._x, ring angles rounded once as in Ring, the B-spline basis at the Gauss offsets, the quadrature
+    weights) and every sum is taken in longdouble.
+    Returns (B, scale), both longdouble in forward's layout [(zm * K2_t + blk) * (ncells + 3) + node, V]: scale is the same
+    chain of sums over absolute values (|ph0| W |FB| |CB| |u|), the per-entry condition scale an fp64 evaluation of B is
+    rounded against (any fp64 summation order is within a few n * 2^-53 * scale of B)."""
+    g = grid
+    ncells = g.nc if ncells is None else ncells
+    rr = list(g.tile_rings(cell0, ncells))
+    K2t = g.tile_K2(cell0, ncells)
+    nbt = ncells + 3
+    # basis of the tile's nodes at its mish points: ring i sits in tile cell i // 3 at offset GAUSS_OFF[i % 3], and node n of the
+    # tile is centred at cell n - 1, so delta = (i // 3 + 1/2 + off) - (n - 1) exactly
+    goff = np.array([-np.sqrt(XP(3) / XP(5)) / 2, XP(0), np.sqrt(XP(3) / XP(5)) / 2], dtype=XP)
+    ii = np.arange(len(rr))
+    pos = (ii // MUBAR).astype(XP) + XP(0.5) + goff[ii % MUBAR]
+    ph0 = bspline(pos[:, None] - (np.arange(nbt, dtype=XP) - 1)[None, :], 0)          # [rings, nbt]
+    W = XP(g.DX) * (np.array([8, 5, 8], dtype=XP) / XP(21))[ii % MUBAR]
+    R = ph0 * W[:, None]
+    B = np.zeros((g.b_zDim * K2t * nbt, g.V), dtype=XP)
+    S = np.zeros_like(B)
+    base = g.ringstart[rr[0]]
+    FB = {}
+    for i, ring in enumerate(rr):
+        L, km, off = int(g.L[ring]), int(g.kmax[ring]), g.off[ring]
+        if (L, km, off) not in FB:
+            lam = XP(off) + 2 * PI_X * np.arange(L, dtype=XP) / XP(L)
+            f = np.zeros((1 + 2 * km, L), dtype=XP)
+            f[0] = 1
+            for k in range(1, km + 1):
+                f[2 * k - 1], f[2 * k] = np.cos(k * lam), -np.sin(k * lam)
+            FB[(L, km, off)] = f / XP(L)
+    for vi, v in enumerate(g.names):
+        CB = g.cheb(v)._x["CB"] if g.has_z else None
+        F = np.zeros((len(rr), g.b_zDim, K2t), dtype=XP)
+        Fa = np.zeros_like(F)
+        for i, ring in enumerate(rr):
+            L = int(g.L[ring])
+            p0 = (g.ringstart[ring] - base) * g.zDim
+            u = values[p0:p0 + L * g.zDim, vi].reshape(L, g.zDim).astype(XP)               # [lambda, z]
+            bz, bza = ((CB @ u.T), (np.abs(CB) @ np.abs(u).T)) if g.has_z else (u.T, np.abs(u).T)
+            fb = FB[(L, int(g.kmax[ring]), g.off[ring])]
+            F[i, :, :fb.shape[0]] = bz @ fb.T
+            Fa[i, :, :fb.shape[0]] = bza @ np.abs(fb).T
+        B[:, vi] = np.einsum("in,izk->zkn", R, F).reshape(-1)
+        S[:, vi] = np.einsum("in,izk->zkn", np.abs(R), Fa).reshape(-1)
+    return B, S
+
+
 class _LazyRings:
     """Dense ring operators are built on first use (the C oracle never needs them)."""
 

@@ -440,3 +440,99 @@ def check_full(hip, orc, rings, title, orc_alt=None):
     return e_hip, e_orc, d
 
 
+
+
+# ----------------------------------------------------------------------------- forward-path launch geometry (host mirrors)
+def _handle_dims(case, tile=None):
+    """(K2 of the handle, tile cells, nz, Zb) as sx_create sets them: K2 = 2 (kDim + 1) with kDim the PATCH's largest kmax."""
+    g = oracle_grid(case)
+    ncells = g.nc if tile is None else tile[1]
+    K2 = 2 * (g.kDim + 1) if g.has_l else 1
+    return g, K2, ncells
+
+
+def _env_int(env, name, default):
+    v = (env or {}).get(name)
+    return default if v is None else int(v)
+
+
+def sb_launch_geometry(case, env=None, storage="f64", tile=None, v_cnt=None):
+    """What launch_sb (scythe.jl_amd/csrc/sx_kernels.hip) launches for spectralTransform! on the tile (cell0, ncells) (default:
+    the whole patch) with the switches in `env` (SX_SBW_MFMA, SX_SBW_PF, SX_SBW_T256, SX_SBW_SEG, SX_RZ_FUSED) and v_cnt
+    variables in the window (default: all).  Restates the launcher's arithmetic:
+      kernel (with its template arguments), threads, bw (wavenumber blocks per workgroup), groups = ceil(K2 / bw) v_cnt,
+      nseg, cps = max(ncells <= 64 ? 2 : 6, ceil(ncells / nseg)) cells per segment, segs = ceil(ncells / cps), last = the last
+      segment's cells, tail = K2 % bw, and for the matrix-core kernels MT = ceil(Zb / 16), mhalf = ceil(MT / 2) and nmt, the
+      row tiles of each wave of a workgroup (k_sbw_mfma's mt0 / mt1 / nmt)."""
+    g, K2, ncells = _handle_dims(case, tile)
+    V = g.V if v_cnt is None else v_cnt
+    if not g.has_z:
+        return dict(kernel="k_sb", threads=256, ncells=ncells, K2=K2)
+    nz, Zb = g.zDim, g.b_zDim
+    sp32 = storage == "f32x"
+    if g.geometry == "RZ" and _env_int(env, "SX_RZ_FUSED", 1) != 0 and not sp32:
+        return dict(kernel="k_rz_forward", ncells=ncells, K2=K2)
+    if nz not in (32, 64, 128):
+        return dict(kernel="k_sbz", threads=256, ncells=ncells, K2=K2, bw=64, tail=K2 % 64)
+    mf = _env_int(env, "SX_SBW_MFMA", 1) != 0 and (Zb <= 64 if nz <= 64 else Zb <= 96)
+    if sp32 and not mf:
+        return dict(kernel=None, refused="storage_f32 = 2", ncells=ncells, K2=K2)       # sx_create refuses the handle
+    t256 = _env_int(env, "SX_SBW_T256", 1) != 0 and mf and nz == 64
+    bw = 32 if (mf and nz == 128) or t256 else 64
+    groups = -(-K2 // bw) * V
+    pf = (_env_int(env, "SX_SBW_PF", 0) != 0 and nz <= 64) or mf
+    seg_env = _env_int(env, "SX_SBW_SEG", 0)
+    nseg = seg_env if seg_env > 0 else max(1, (512 if (mf and nz == 128) or t256 else 256 if pf or nz == 128 else 384) // groups)
+    cps = max(2 if ncells <= 64 else 6, -(-ncells // nseg))
+    segs = -(-ncells // cps)
+    threads = 256 if t256 else 512
+    if sp32:
+        kernel = "k_sbw_mfma<%s, float>" % ("64, 32, 256" if t256 else "64, 64, 512" if nz == 64 else "32, 64, 512" if nz == 32
+                                             else "128, 32, 512")
+    elif t256:
+        kernel = "k_sbw_mfma<64, 32, 256>"
+    elif mf:
+        kernel = "k_sbw_mfma<%s>" % ("128, 32" if nz == 128 else nz)
+    else:
+        kernel = "k_sbw<%d, %s>" % (nz, "true" if pf and nz <= 64 else "false")
+    out = dict(kernel=kernel, threads=threads, bw=bw, groups=groups, nseg=nseg, cps=cps, segs=segs,
+               last=ncells - (segs - 1) * cps, tail=K2 % bw, ncells=ncells, K2=K2)
+    if mf:
+        MT = -(-Zb // 16)
+        mhalf = (MT + 1) // 2
+        nmt = []
+        for wv in range(threads // 64):
+            if bw == 64:
+                nmt.append(mhalf if wv < 4 else MT - mhalf)
+            else:
+                mt0 = wv >> 1
+                mt1 = mt0 + threads // 128
+                nmt.append(0 if mt0 >= MT else 2 if mt1 < MT else 1)
+        out.update(MT=MT, mhalf=mhalf, nmt=tuple(nmt))
+    return out
+
+
+def zinv_launch_geometry(case, env=None, storage="f64"):
+    """What launch_zinv (sx_kernels.hip) launches for the vertical inverse into Az: k_colmat_mfma<MT = zDim / 16, OT, CT> at zDim
+    32 / 64 / 128 (CT from SX_ZINV_CT: 1, 2 or 4 at 128 levels, default 2; 2 at 64 levels on request, else 1), k_colmat
+    otherwise; grid.x = ceil(K2 / (64 CT)) and the tail K2 % (64 CT) of the last workgroup.  None where no k_zinv runs (R / RL
+    grids, fused RZ)."""
+    g, K2, _ = _handle_dims(case)
+    if not g.has_z or (g.geometry == "RZ" and _env_int(env, "SX_RZ_FUSED", 1) != 0 and storage != "f32x"):
+        return None
+    nz = g.zDim
+    ct_env = _env_int(env, "SX_ZINV_CT", 0)
+    ct = ((ct_env if ct_env in (1, 4) else 2) if nz == 128 else 2 if nz == 64 and ct_env == 2 else 1)
+    OT = "float" if storage == "f32x" else "double"
+    kernel = "k_colmat_mfma<%d, %s, %d>" % (nz // 16, OT, ct) if nz in (32, 64, 128) else "k_colmat"
+    return dict(kernel=kernel, MT=nz // 16 if nz in (32, 64, 128) else None, CT=ct, OT=OT, grid_x=-(-K2 // (64 * ct)),
+                tail=K2 % (64 * ct), K2=K2)
+
+
+# every instantiation the two launchers can pick
+SB_KERNELS = {"k_sb", "k_sbz", "k_rz_forward", "k_sbw<32, false>", "k_sbw<32, true>", "k_sbw<64, false>", "k_sbw<64, true>",
+              "k_sbw<128, false>", "k_sbw_mfma<32>", "k_sbw_mfma<64>", "k_sbw_mfma<64, 32, 256>", "k_sbw_mfma<128, 32>",
+              "k_sbw_mfma<32, 64, 512, float>", "k_sbw_mfma<64, 64, 512, float>", "k_sbw_mfma<64, 32, 256, float>",
+              "k_sbw_mfma<128, 32, 512, float>"}
+ZINV_KERNELS = {"k_colmat"} | {"k_colmat_mfma<%d, %s, %d>" % (mt, ot, ct) for ot in ("double", "float")
+                               for mt, ct in ((2, 1), (4, 1), (4, 2), (8, 1), (8, 2), (8, 4))}

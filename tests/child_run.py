@@ -7,8 +7,8 @@ run_in_child(tmp_path, job, overrides): the child is `python -m tests.child_run 
 to the .npz; the parent compares them with run_job(job) in its own process and with the oracle.  A child that dies on a signal or
 hangs ends the whole session (pytest.exit): after a crashed or hung GPU process nothing more may start on the GPU.
 
-A job is JSON: {"kind": "spline" | "rz_transforms" | "model", "cases": [[maker, kwargs, grid overrides], ...], "steps": n}
-with `maker` a function of tests/cases.py."""
+A job is JSON: {"kind": "spline" | "rz_transforms" | "model" | "forward", "cases": [[maker, kwargs, grid overrides(, storage)],
+...], "steps": n} with `maker` a function of tests/cases.py and `storage` a GridParameters.storage (default "f64")."""
 import json
 import os
 import subprocess
@@ -21,10 +21,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def make_case(spec):
     from tests import cases
-    maker, kw, grid = spec
+    maker, kw, grid = spec[:3]
     case = getattr(cases, maker)(**kw)
     case["grid"].update(grid)
     return case
+
+
+def forward_inputs(N, V, s_patch, seed=11):
+    """The random inputs of a "forward" job: physical values [N, V] and A coefficients [s_patch, V]."""
+    rng = np.random.default_rng(seed)
+    return rng.standard_normal((N, V)), rng.standard_normal((s_patch, V))
 
 
 def run_job(job):
@@ -53,6 +59,19 @@ def run_job(job):
             g.set_physical_values(vals)
             g.spectralTransform_()
             out["spec%d" % i] = g.spectral
+            g.close()
+        elif job["kind"] == "forward":           # spectralTransform! + splineTransform!, tileTransform! (test_gpu_forward.py)
+            gp, mp = cases.hip_params(case, spec[3] if len(spec) > 3 else "f64")
+            g = S.Grid(gp, mp)
+            vals, a = forward_inputs(g.N, g.V, int(g.dims.s_patch))
+            g.set_physical_values(vals)
+            g.spectralTransform_()
+            out["b%d" % i] = g.spectral
+            g.splineTransform_()
+            out["a%d" % i] = g.patchSpectral
+            g.set_patch_spectral_a(a)
+            g.tileTransform_()
+            out["phys%d" % i] = g.physical
             g.close()
         elif job["kind"] == "model":             # job["steps"] model steps from the case's initial condition
             hip = cases.HipModel(case)
