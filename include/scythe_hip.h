@@ -170,6 +170,19 @@ int sx_cheb_column_ops(double zmin, double zmax, int32_t zDim, int32_t b_zDim, i
 int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_q, int32_t bcl, int32_t bcr, const double *b,
                           double *a_pcr, double *a_chol, int32_t *levels);
 
+/* The launch shape the library takes for given dimensions, with the SX_* switches as the environment has them now (read by the
+ * function sx_create uses): which kernel instantiation - its text, such as "k_sbw_mfma<64, 32, 256>", into kernel[kernel_cap];
+ * empty where none runs or the handle would be refused - and its grid arithmetic.  in / out by kind:
+ *   SX_PLAN_FORWARD  spectralTransform!'s radial inner products:  in = geometry, zDim, b_zDim, K2 (device blocks per row: 2 (kDim + 1),
+ *                    or 1 without azimuth), variables in the window, tile cells, storage_f32 == 2;
+ *                    out = threads, bw, groups, nseg, cps, segs (sliding-window kernels; 0 where a kernel has no such figure)
+ *   SX_PLAN_ZINV     vertical inverse:  in = geometry, zDim, K2, storage_f32 == 2;  out = CT, grid_x
+ *   SX_PLAN_PCR      parallel-cyclic-reduction solve:  in = largest block-row count of the spline classes, num_cells + 3, K2,
+ *                    (variable, z-mode) groups of the launch;  out = R, log2 R, threads;  kernel: empty
+ * Pure host helper (no handle, no device): the tests name the launch shapes they cover from it; never on the step path. */
+enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2 };
+int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap);
+
 /* --- state in / out (host pointers, reference layouts) ------------------------------------------------------------- */
 /* read_physical_grid -> physical[:, v, 1]  (src/semiimplicit.jl:134): values[n_points, n_vars] */
 int sx_set_physical_values(sx_handle *h, const double *values);

@@ -189,6 +189,61 @@ static inline int64_t ref_index(int zm, int blk, int node, int K2, int nb) { ret
 // device block index of reference block b (0: k = 0, 2k-1: Re k, 2k: Im k)
 static inline int dev_blk(int b) { return b == 0 ? 0 : b + 1; }
 
+// ---- the SX_* kernel-selection switches: one row per variable, read once per handle --------------------------------------
+// An unset variable leaves the member's initialiser (sx_internal.hpp).  SX_RCCL_LIB (a path, sx_comm.cpp) and the *_PHASES_OUT
+// paths of the -DSX_PHASES build are not switches and are not here.
+enum SwitchKind {
+    FLAG,        // atoi(value) != 0.  Default-off members: off unless non-zero; default-on members: on unless zero
+    FLAG_AS_2,   // the same, with "on" stored as 2 (SX_DFT_EIGHTH: the number of planes of an eighth-wave unit)
+    INTEGER      // atoi / atoll(value)
+};
+struct SwitchRow {
+    const char *env;
+    int Switches::*i;
+    int64_t Switches::*l;
+    SwitchKind kind;
+    SwitchRow(const char *e, int Switches::*m, SwitchKind k) : env(e), i(m), l(nullptr), kind(k) {}
+    SwitchRow(const char *e, int64_t Switches::*m) : env(e), i(nullptr), l(m), kind(INTEGER) {}
+};
+static const SwitchRow SWITCHES[] = {
+    {"SX_OVERLAP", &Switches::overlap, INTEGER},
+    {"SX_GRAPH", &Switches::use_graph, FLAG},
+    {"SX_NODE_MODE", &Switches::node_mode, FLAG},
+    {"SX_DEFER_DIAG", &Switches::defer_diag, FLAG},
+    {"SX_FFT_REG", &Switches::fft_reg, FLAG},
+    {"SX_DFT_MFMA", &Switches::dft_mfma, FLAG},
+    {"SX_DFT_HALFWG", &Switches::dft_half_wg, FLAG},
+    {"SX_DFT_EIGHTH", &Switches::dft_eighth, FLAG_AS_2},
+    {"SX_DFT_MERGE", &Switches::dft_merge, FLAG},
+    {"SX_DFT_RLQ", &Switches::rl_quarter, FLAG},
+    {"SX_DFT_HALF", &Switches::dft_half, FLAG},
+    {"SX_DFT_CLASSES", &Switches::dft_classes, INTEGER},
+    {"SX_FUSE_ZINV", &Switches::fuse_zinv, FLAG},
+    {"SX_ZINV_CT", &Switches::zinv_ct, INTEGER},
+    {"SX_SBW_MFMA", &Switches::sbw_mfma, FLAG},
+    {"SX_SBW_PF", &Switches::sbw_prefetch, FLAG},
+    {"SX_SBW_T256", &Switches::sbw_t256, FLAG},
+    {"SX_SBW_SEG", &Switches::sbw_seg, INTEGER},
+    {"SX_WIDE", &Switches::wide, FLAG},
+    {"SX_SOLVE_PCR", &Switches::solve_pcr, INTEGER},
+    {"SX_PCR_MAXCOLS", &Switches::pcr_maxcols},
+    {"SX_PCR_R", &Switches::pcr_r, INTEGER},
+    {"SX_RZ_FUSED", &Switches::rz_fused, FLAG},
+    {"SX_RZ_INV", &Switches::rz_inv, FLAG},
+    {"SX_SEMI_MFMA", &Switches::semi_mfma, FLAG},
+};
+
+Switches read_switches() {
+    Switches sw;
+    for (const SwitchRow &r : SWITCHES) {
+        const char *v = getenv(r.env);
+        if (!v) continue;
+        if (r.l) sw.*r.l = atoll(v);
+        else sw.*r.i = r.kind == INTEGER ? atoi(v) : atoi(v) == 0 ? 0 : r.kind == FLAG_AS_2 ? 2 : 1;
+    }
+    return sw;
+}
+
 }  // namespace sx
 
 using namespace sx;
@@ -298,21 +353,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     h->f32 = g->storage_f32 ? 1 : 0;
     h->sp32 = g->storage_f32 == 2 ? 1 : 0;
     if (g->storage_f32 < 0 || g->storage_f32 > 2) { set_error("storage_f32 must be 0, 1 or 2"); delete h; return 1; }
-    h->overlap = getenv("SX_OVERLAP") ? atoi(getenv("SX_OVERLAP")) : 0;
-    h->wide = !(getenv("SX_WIDE") && atoi(getenv("SX_WIDE")) == 0);
-    h->fuse_zinv = getenv("SX_FUSE_ZINV") && atoi(getenv("SX_FUSE_ZINV")) != 0;
-    h->sbw_prefetch = getenv("SX_SBW_PF") && atoi(getenv("SX_SBW_PF")) != 0;
-    h->sbw_mfma = !(getenv("SX_SBW_MFMA") && atoi(getenv("SX_SBW_MFMA")) == 0);
-    h->rz_fused = !(getenv("SX_RZ_FUSED") && atoi(getenv("SX_RZ_FUSED")) == 0);
-    h->semi_mfma = !(getenv("SX_SEMI_MFMA") && atoi(getenv("SX_SEMI_MFMA")) == 0);
-    h->use_graph = getenv("SX_GRAPH") && atoi(getenv("SX_GRAPH")) != 0;
-    h->fft_reg = !(getenv("SX_FFT_REG") && atoi(getenv("SX_FFT_REG")) == 0);
-    h->dft_merge = !(getenv("SX_DFT_MERGE") && atoi(getenv("SX_DFT_MERGE")) == 0);
-    if (getenv("SX_DFT_HALFWG")) h->dft_half_wg = atoi(getenv("SX_DFT_HALFWG")) != 0;
-    if (getenv("SX_DFT_EIGHTH")) h->dft_eighth = atoi(getenv("SX_DFT_EIGHTH")) != 0 ? 2 : 0;
-    h->rl_quarter = !(getenv("SX_DFT_RLQ") && atoi(getenv("SX_DFT_RLQ")) == 0);
-    h->solve_pcr = getenv("SX_SOLVE_PCR") ? atoi(getenv("SX_SOLVE_PCR")) : -1;
-    if (getenv("SX_PCR_MAXCOLS")) h->pcr_maxcols = atoll(getenv("SX_PCR_MAXCOLS"));
+    h->sw = read_switches();
     h->cell0 = g->tile_cell0; h->ncells = g->tile_num_cells; h->tile_num = g->tile_num;
     h->nrings = MUBAR * h->ncells; h->nbt = h->ncells + 3;
     for (int i = 0; i < 7; i++) h->slot[i] = DERIV_SLOTS[h->geom][i];
@@ -540,7 +581,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         if (!dalloc(h, &h->d_E[i], (size_t)h->V * N)) FAIL();
         if (h->semi && !dalloc(h, &h->d_I[i], (size_t)h->V * N)) FAIL();
     }
-    if (h->sp32 && !(fft_path_ok(h) && h->has_z && (h->nz == 32 || h->nz == 64 || h->nz == 128) && h->sbw_mfma &&
+    if (h->sp32 && !(fft_path_ok(h) && h->has_z && (h->nz == 32 || h->nz == 64 || h->nz == 128) && h->sw.sbw_mfma &&
                      (h->nz <= 64 ? h->Zb <= 64 : h->Zb <= 96))) {
         set_error("storage_f32 = 2 (fp32 spectral intermediates) needs an RLZ / RZ grid on a uniform power-of-two ring table with zDim 32, 64 or 128");
         FAIL();
@@ -603,7 +644,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         }
         // node-space ("radial last") inverse: uniform power-of-two rings + the MFMA HRBL kernel
         if (h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 && fft_path_ok(h) && h->has_z && (h->nz == 64 || h->nz == 32 || h->nz == 128) &&
-            !(getenv("SX_NODE_MODE") && atoi(getenv("SX_NODE_MODE")) == 0)) {
+            h->sw.node_mode) {
             h->node_mode = 1;
             h->R_in = 0;
             while (h->R_in < h->nrings && h->hkmax[h->R_in] < h->kDim) h->R_in++;
@@ -665,8 +706,8 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     }
     h->v_lo = 0; h->v_cnt = h->V;
     // deferred diagnostic variable (sx_internal.hpp): one-tile HRBL runs whose forward path is the FFT + matrix-core kernels
-    h->defer_diag = getenv("SX_DEFER_DIAG") && atoi(getenv("SX_DEFER_DIAG")) != 0 && h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 &&
-                    h->ncells == h->nc && fft_path_ok(h) && h->has_z && (h->nz == 32 || h->nz == 64 || h->nz == 128) && h->sbw_mfma &&
+    h->defer_diag = h->sw.defer_diag && h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 &&
+                    h->ncells == h->nc && fft_path_ok(h) && h->has_z && (h->nz == 32 || h->nz == 64 || h->nz == 128) && h->sw.sbw_mfma &&
                     (h->nz <= 64 ? h->Zb <= 64 : h->Zb <= 96);
     if (sx_bind_patch_b(h, nullptr, nullptr)) FAIL();
     *out = h;
@@ -730,6 +771,33 @@ int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_
     if (a_pcr) pcr_apply_host(t, nb, b, a_pcr);
     if (a_chol) cholesky_apply_host(sc, nb, b, a_chol);
     if (levels) *levels = t.levels;
+    return 0;
+}
+
+int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap) {
+    clear_error();
+    if (!in || !out) { set_error("sx_launch_plan: null argument"); return 1; }
+    if (kind != SX_PLAN_FORWARD && kind != SX_PLAN_ZINV && kind != SX_PLAN_PCR) { set_error("sx_launch_plan: unknown kind " + std::to_string(kind)); return 1; }
+    // the dimensions among the inputs (not the geometry in front, not the fp32 flag at the end) divide: positive
+    const int first = kind == SX_PLAN_PCR ? 0 : 1, last = kind == SX_PLAN_FORWARD ? 6 : kind == SX_PLAN_ZINV ? 3 : 4;
+    for (int i = first; i < last; i++)
+        if (in[i] < 1) { set_error("sx_launch_plan: dimensions must be positive"); return 1; }
+    const Switches sw = read_switches();
+    std::string name;
+    if (kind == SX_PLAN_FORWARD) {
+        const SbPlan p = plan_sb(in[0], in[1], in[2], in[3], in[4], in[5], in[6], sw);
+        name = kernel_name(p.kernel);
+        const int32_t o[6] = {p.threads, p.bw, p.groups, p.nseg, p.cps, p.segs};
+        std::copy(o, o + 6, out);
+    } else if (kind == SX_PLAN_ZINV) {
+        const ZinvPlan p = plan_zinv(in[0], in[1], in[2], in[3], sw);
+        name = kernel_name(p);
+        out[0] = p.CT; out[1] = p.grid_x;
+    } else {
+        const PcrPlan p = plan_pcr(in[0], in[1], in[2], in[3], sw);
+        out[0] = p.R; out[1] = p.logR; out[2] = p.threads;
+    }
+    if (kernel && kernel_cap > 0) snprintf(kernel, (size_t)kernel_cap, "%s", name.c_str());
     return 0;
 }
 
@@ -1070,7 +1138,7 @@ int sx_step(sx_handle *h, int32_t t) {
     if (h->ncells != h->nc) { set_error("sx_step: one-tile patches only (tiles exchange between sx_advance and the solve)"); return 1; }
     // the first two steps a handle executes are always plain launches: Euler / AB2 arguments, and everything created lazily on a
     // first launch (work lists, elimination tables, function attributes) must exist before a capture, which may not allocate
-    const bool graph = h->use_graph && !h->timers_on && t >= 3 && h->plain_steps >= 2 && h->eq != SX_EQ_NONE && !h->comm_state;
+    const bool graph = h->sw.use_graph && !h->timers_on && t >= 3 && h->plain_steps >= 2 && h->eq != SX_EQ_NONE && !h->comm_state;
     if (!graph) {
         step_launches(h, t);
         h->plain_steps++;
@@ -1081,7 +1149,7 @@ int sx_step(sx_handle *h, int32_t t) {
         // capture this rotation's launches.  The null stream cannot be captured: a handle that runs on it captures and replays on
         // a private BLOCKING stream, which the null stream's legacy semantics order against everything else the handle does
         hipStream_t user = h->stream;
-        if (!user && !h->graph_stream && hipStreamCreate(&h->graph_stream) != hipSuccess) { h->use_graph = 0; step_launches(h, t); return status(); }
+        if (!user && !h->graph_stream && hipStreamCreate(&h->graph_stream) != hipSuccess) { h->sw.use_graph = 0; step_launches(h, t); return status(); }
         hipStream_t cs = user ? user : h->graph_stream;
         hipGraph_t g = nullptr;
         hipGraphExec_t ex = nullptr;
@@ -1098,7 +1166,7 @@ int sx_step(sx_handle *h, int32_t t) {
         if (!ok) {          // no graphs on this handle from here on; redo the step with plain launches (nothing ran during the capture)
             (void)hipGetLastError();
             clear_error();
-            h->use_graph = 0;
+            h->sw.use_graph = 0;
             h->rot = rot0;
             step_launches(h, t);
             return status();

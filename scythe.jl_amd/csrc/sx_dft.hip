@@ -1418,8 +1418,7 @@ bool dft_mfma_ok(const sx_handle *h) {
     // fewer than 8 levels leave most of the MFMA N dimension empty: the scalar kernels then, as far as THEY reach (511 points,
     // kmax 255); beyond that the matrix-core kernels run with a partial level chunk rather than refusing the grid
     if (!dft_planes(h) && h->nz < 8 && h->L_max <= 511 && h->kmax_max <= 255) return false;
-    static const bool off = getenv("SX_DFT_MFMA") && atoi(getenv("SX_DFT_MFMA")) == 0;       // scalar kernels instead (debugging)
-    if (off) return false;
+    if (!h->sw.dft_mfma) return false;       // scalar kernels instead (debugging)
     return h->L_all_mult4;
 }
 
@@ -1427,8 +1426,7 @@ bool dft_mfma_ok(const sx_handle *h) {
 // occupancy) of the largest: class c covers rings [c n/4, (c+1) n/4), sized for its last ring.
 template <class F>
 static void for_ring_classes(sx_handle *h, int n_rings, F f, int max_classes = 4) {
-    static const int cls_env = getenv("SX_DFT_CLASSES") ? atoi(getenv("SX_DFT_CLASSES")) : 0;        // experiments
-    const int ncls = n_rings >= 16 ? (cls_env > 0 ? cls_env : max_classes) : 1;
+    const int ncls = n_rings >= 16 ? (h->sw.dft_classes > 0 ? h->sw.dft_classes : max_classes) : 1;
     for (int c = 0; c < ncls; c++) {
         const int r0 = (int)((int64_t)n_rings * c / ncls), r1 = (int)((int64_t)n_rings * (c + 1) / ncls);
         if (r1 <= r0) continue;
@@ -1485,7 +1483,7 @@ static void launch_rl_inverse_dft_planes(sx_handle *h, bool full) {
     }
     if (pc.n > 0) push();                       // V <= 8 variables x 5 planes = 40 columns at most: 3 groups
     if (pgs.ng == 0) return;
-    if (h->rl_quarter && pgs.ng <= 3) {
+    if (h->sw.rl_quarter && pgs.ng <= 3) {
         // one launch over (ring, part) items, most expensive first; a part = 8 row tiles of the quarter ring (one per wave)
         if (!rlq_lists(h)) return;
         const double *a = h->d_A + (int64_t)h->cell0 * h->C;
@@ -1585,8 +1583,8 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
         const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * kcap4 * CST);
         dim3 g((h->nz + DZC - 1) / DZC, h->n_dft_items[which] - nbig, 1);
         if (g.y == 0) { timer_end(h); return; }
-        if (h->dft_merge) {
-            const bool e8 = h->dft_eighth != 0;
+        if (h->sw.dft_merge) {
+            const bool e8 = h->sw.dft_eighth != 0;
             const int kz = e8 ? 32 * ((h->dft_kcap_small + 1 + 31) / 32) : 8 * ((h->dft_kcap_small / 2 + 1 + 3) / 4);          // rows a K step can touch (see the kernel)
             const size_t pad = e8 ? sizeof(double) * 32 * CST : 0;     // the pipelined loops request one K step beyond the staged rows
             const size_t lds2 = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * kz * CST) + pad;
@@ -1594,7 +1592,7 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
             const size_t ldsm = two ? lds2 : sizeof(double) * (2 * (size_t)lcap + (size_t)2 * kz * CST) + pad;
             // two 256-thread workgroups per CU (HT) where one set + half the twiddle table fit 80 KB
             const size_t ldsh = sizeof(double) * ((size_t)2 * kz * CST + (size_t)lcap);
-            if (e8 && h->dft_half_wg && ldsh <= 80 * 1024) {
+            if (e8 && h->sw.dft_half_wg && ldsh <= 80 * 1024) {
 #define DFT_INVH(ST)                                                                                                                 \
                 {                                                                                                                    \
                     auto kern = k_rl_inverse_dft_merged<ST, 2, true>;                                                                \
@@ -1645,8 +1643,8 @@ void launch_fl_forward_dft(sx_handle *h) {
     const int id = timer_id(h, "k_fl_forward");
     timer_begin(h, id);
     const int planes = dft_planes(h) ? 1 : 0;
-    static const bool half = getenv("SX_DFT_HALF") && atoi(getenv("SX_DFT_HALF")) != 0;      // A/B: the half-ring kernel
-    if (planes && h->rl_quarter && rlq_lists(h)) {      // RL grids: quarter-wave fold, one launch over (ring, part) items
+    const bool half = h->sw.dft_half != 0;      // A/B: the half-ring kernel
+    if (planes && h->sw.rl_quarter && rlq_lists(h)) {      // RL grids: quarter-wave fold, one launch over (ring, part) items
         const int lcap = h->L_max;
         const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * LCQ * CST);
         HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_qp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));

@@ -692,7 +692,7 @@ bool fft_path_ok(const sx_handle *h) {
 // matrix-core prologue (per coefficient group four rounds of 16 L2 loads -> 8 MFMAs at the 128 registers the kernel has, an
 // LDS round trip and two workgroup barriers) is serial time in a kernel whose limit is its serial time.
 bool fft_fused_zinv(const sx_handle *h) {
-    return h->fuse_zinv && h->node_mode && h->has_z && h->uniform_L <= 256 && h->Zb <= 64 && h->nz % 16 == 0 && !h->sp32;
+    return h->sw.fuse_zinv && h->node_mode && h->has_z && h->uniform_L <= 256 && h->Zb <= 64 && h->nz % 16 == 0 && !h->sp32;
 }
 
 static int fft_fzc(int) { return 16; }
@@ -739,7 +739,7 @@ static void launch_inv(sx_handle *h, const int *d_mask, const InvTarget &tg, con
     } while (0)
 #define INV_LAUNCH(NODE, ST, AT)                                                                                                     \
     do {                                                                                                                             \
-        if constexpr (LOGL == 8 || LOGL == 9) { if (h->fft_reg) { INV_LAUNCH_REG(NODE, ST, AT); break; } }                                        \
+        if constexpr (LOGL == 8 || LOGL == 9) { if (h->sw.fft_reg) { INV_LAUNCH_REG(NODE, ST, AT); break; } }                                        \
         INV_LAUNCH_V(NODE, ST, AT, 0, 2);                                                                                            \
     } while (0)
 #define INV_LAUNCH_FUSED(ST)                                                                                                         \

@@ -99,6 +99,67 @@ struct SemiArgs {
     double ts, tau, pxi;
 };
 
+// ---- kernel-selection switches (environment, read once per handle by read_switches: sx_api.cpp) ---------------------
+// The member initialiser is the value of an unset variable.  DESIGN.md has the table with what each one was measured for.
+struct Switches {
+    // second stream for the inner-ring chain of sx_advance (launch_inverse_and_physics); off unless SX_OVERLAP=1: measured
+    // +2.6 % (669 vs 653 steps/s) - the two chains compete for the same HBM bandwidth - and it blurs the per-kernel timers
+    int overlap = 0;
+    int use_graph = 0;      // SX_GRAPH=1: hipGraph replay of a one-tile step (sx_step), one instantiated graph per history rotation
+    int node_mode = 1;      // SX_NODE_MODE=0: ring-wise inverse everywhere (sx_create decides where the node-space form applies at all)
+    int defer_diag = 0;     // SX_DEFER_DIAG=1: asks for sx_handle::defer_diag (sx_create decides whether the handle qualifies)
+    int fft_reg = 1;        // 256-point inverse transforms: register-resident passes with lane swaps (SX_FFT_REG=0: every pass through LDS)
+    int dft_mfma = 1;       // native rings: the matrix-core DFT kernels (SX_DFT_MFMA=0: scalar kernels instead, debugging)
+    int dft_half_wg = 1;    // eighth-wave kernel as two 256-thread workgroups per CU where one set + half a twiddle table fit 80 KB (SX_DFT_HALFWG=0: one 512-thread workgroup)
+    int dft_eighth = 2;     // merged kernel: eighth-wave units of two planes (round 4; SX_DFT_EIGHTH=0: quarter-wave units of up to four)
+    int dft_merge = 1;      // RLZ native rings: merged-pass inverse DFT kernel (SX_DFT_MERGE=0: one set per pass, whole tiles per wave)
+    int rl_quarter = 1;     // RL grids: quarter-wave DFT kernels over one work list (SX_DFT_RLQ=0: the half-ring kernels in two ring classes)
+    int dft_half = 0;       // SX_DFT_HALF=1: the half-ring forward DFT kernel on native rings (A/B)
+    int dft_classes = 0;    // SX_DFT_CLASSES=n: launch classes of the older DFT kernels (experiments; <= 0: the launcher's own count)
+    int fuse_zinv = 0;      // SX_FUSE_ZINV=1: vertical inverse inside the node FFT kernel (measured slower: sx_fft.hip)
+    int zinv_ct = 0;        // SX_ZINV_CT=n: column tiles per wave of k_zinv (A/B; values without a kernel take the default: plan_zinv)
+    int sbw_mfma = 1;       // k_sbw_mfma (matrix-core vertical contraction, operator in registers) for zDim 64 / 32 (SX_SBW_MFMA=0: k_sbw)
+    int sbw_prefetch = 0;   // k_sbw requests the next cell's ring spectra before contracting the current node (SX_SBW_PF=0: off)
+    // zDim 64: 256-thread workgroups of 32 blocks, two per CU - one loads while the other contracts (0.127 -> 0.118 ms;
+    // SX_SBW_T256=0 restores the 512-thread form)
+    int sbw_t256 = 1;
+    int sbw_seg = 0;        // SX_SBW_SEG=n: segments per (block group, variable) of the sliding-window kernels (experiments; <= 0: by size)
+    int wide = 1;           // 16-byte-per-lane loads / stores in the equation-set kernels (SX_WIDE=0: the 8-byte forms, A/B timing)
+    int solve_pcr = -1;     // SX_SOLVE_PCR: 0 never, 1 wherever the tables exist, -1 by column count
+    int64_t pcr_maxcols = 16384;   // SX_PCR_MAXCOLS
+    int pcr_r = 0;          // SX_PCR_R=n: columns per workgroup of k_solve_pcr (<= 0: by column count)
+    int rz_fused = 1;       // RZ grids: the fused radius-on-the-matrix-cores kernels of sx_rz.hip (SX_RZ_FUSED=0: the general kernels)
+    int rz_inv = 1;         // fused RZ inverse by node tiles (SX_RZ_INV=0: the ring-tile form, A/B)
+    int semi_mfma = 1;      // semi-implicit column operators on the matrix cores (SX_SEMI_MFMA=0: k_semiimplicit)
+};
+Switches read_switches();   // from the environment (sx_api.cpp)
+
+// ---- launch plans (sx_plan.cpp): which kernel and which grid, from plain integers - no handle, no device ---------------
+// The launchers dispatch on them; sx_launch_plan hands them to the tests, which therefore name the shapes the library launches.
+enum class SbKernel {
+    refused,   // fp32 ring spectra (storage_f32 = 2) where the matrix-core kernel does not apply: sx_create refuses the handle
+    sb, sbz, rz_forward, sbw_32, sbw_32_pf, sbw_64, sbw_64_pf, sbw_128, mfma_32, mfma_64, mfma_64_t256, mfma_128,
+    mfma_32_f32, mfma_64_f32, mfma_64_t256_f32, mfma_128_f32
+};
+struct SbPlan {      // the sliding-window kernels' grid is (ceil(K2 / bw), v_cnt, segs); the other fields are 0 for k_sb / k_sbz / k_rz_forward
+    SbKernel kernel = SbKernel::refused;
+    int threads = 0, bw = 0;              // threads and wavenumber blocks per workgroup
+    int groups = 0, nseg = 0, cps = 0, segs = 0;   // ceil(K2 / bw) v_cnt; segments aimed at; cells per segment; segments
+};
+enum class ZinvKernel { none /* R / RL grids, fused RZ */, colmat, mfma_2_1, mfma_4_1, mfma_4_2, mfma_8_1, mfma_8_2, mfma_8_4 };   // mfma_<MT>_<CT>
+struct ZinvPlan {
+    ZinvKernel kernel = ZinvKernel::none;
+    bool f32 = false;                     // OT of k_colmat_mfma: float (fp32 spectra) or double
+    int CT = 1, grid_x = 0;               // column tiles per wave, ceil(K2 / (64 CT))
+};
+struct PcrPlan { int R = 1, logR = 0, threads = 64; };
+constexpr int PCR_IPT = 4;     // row items (patch row, column) per thread while k_solve_pcr loads B and stores A: nb * R <= 4 * blockDim (plan_pcr)
+SbPlan plan_sb(int geometry, int nz, int Zb, int K2, int v_cnt, int ncells, int sp32, const Switches &sw);
+ZinvPlan plan_zinv(int geometry, int nz, int K2, int sp32, const Switches &sw);
+PcrPlan plan_pcr(int nblk_max, int b_rDim, int K2, int ngroups, const Switches &sw);
+std::string kernel_name(SbKernel k);      // "k_sbw_mfma<64, 32, 256>", ...; empty for `refused`
+std::string kernel_name(const ZinvPlan &p);   // "k_colmat_mfma<8, double, 4>", ...; empty for `none`
+
 struct Timer {
     const char *name;
     double ms = 0.0;
@@ -113,6 +174,7 @@ struct PendingEvent {
 }  // namespace sx
 
 struct sx_handle {
+    sx::Switches sw;   // every SX_* kernel-selection switch, as the environment had it at sx_create
     // geometry
     int geom = 0, has_l = 0, has_z = 0;
     double xmin = 0, xmax = 0, DX = 0, l_q = 2.0, zmin = 0, zmax = 0;
@@ -142,26 +204,18 @@ struct sx_handle {
     std::vector<int> a2a_cell0, a2a_ncells;
     int *d_a2a_owner = nullptr;
     int64_t *d_a2a_soff = nullptr, *d_a2a_cw = nullptr, *d_a2a_cs = nullptr, *d_a2a_offA = nullptr, *d_a2a_offB = nullptr;
-    // second stream for the inner-ring chain of sx_advance (launch_inverse_and_physics); off unless SX_OVERLAP=1: measured
-    // +2.6 % (669 vs 653 steps/s) - the two chains compete for the same HBM bandwidth - and it blurs the per-kernel timers
-    hipStream_t stream2 = nullptr;
+    hipStream_t stream2 = nullptr;      // second stream for the inner-ring chain of sx_advance (Switches::overlap)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int overlap = 0;
     // native-ring DFT launches (sx_dft.hip): (ring, variable) work items, most expensive first; [0] inverse with the
     // equation-set slot mask, [1] inverse with every slot, [2] forward
     int *d_dft_items[3] = {nullptr, nullptr, nullptr};
     int n_dft_items[3] = {0, 0, 0};
     int n_dft_big[3] = {0, 0, 0};            // of which (listed first) rings with kmax > DFT_KMAX_SINGLE: chunked kernels
     int dft_lcap_small = 0, dft_kcap_small = 0;   // largest ring length / kmax among the other rings
-    // hipGraph replay of a one-tile step (sx_step; SX_GRAPH=1): one instantiated graph per history rotation
-    int use_graph = 0, plain_steps = 0;
+    // hipGraph replay of a one-tile step (sx_step; Switches::use_graph): one instantiated graph per history rotation
+    int plain_steps = 0;
     hipGraphExec_t graph_exec[3] = {nullptr, nullptr, nullptr};
     hipStream_t graph_stream = nullptr;      // capture / replay stream when the handle runs on the (uncapturable) null stream
-    int fft_reg = 1;                         // 256-point inverse transforms: register-resident passes with lane swaps (SX_FFT_REG=0: every pass through LDS)
-    int dft_half_wg = 1;                     // eighth-wave kernel as two 256-thread workgroups per CU where one set + half a twiddle table fit 80 KB (SX_DFT_HALFWG=0: one 512-thread workgroup)
-    int dft_eighth = 2;                      // merged kernel: eighth-wave units of two planes (round 4; SX_DFT_EIGHTH=0: quarter-wave units of up to four)
-    int dft_merge = 1;                       // RLZ native rings: merged-pass inverse DFT kernel (SX_DFT_MERGE=0: one set per pass, whole tiles per wave)
-    int rl_quarter = 1;                      // RL grids: quarter-wave DFT kernels over one work list (SX_DFT_RLQ=0: the half-ring kernels in two ring classes)
     int *d_rlq_items[2] = {nullptr, nullptr};    // (ring, part) items of the RL inverse / forward launch, most expensive first
     int n_rlq_items[2] = {0, 0};
     // SX_DEFER_DIAG=1 (one-tile HRBL runs on the FFT path): the diagnostic variable w is written by the equation set before it is
@@ -170,10 +224,6 @@ struct sx_handle {
     // something reads A or B.  v_lo / v_cnt: the variable window the forward-path launchers cover.
     int defer_diag = 0, v_lo = 0, v_cnt = 0;
     bool diag_dirty = false;
-    int fuse_zinv = 0;      // SX_FUSE_ZINV=1: vertical inverse inside the node FFT kernel (measured slower: sx_fft.hip)
-    int sbw_mfma = 1;       // k_sbw_mfma (matrix-core vertical contraction, operator in registers) for zDim 64 / 32 (SX_SBW_MFMA=0: k_sbw)
-    int sbw_prefetch = 0;   // k_sbw requests the next cell's ring spectra before contracting the current node (SX_SBW_PF=0: off)
-    int wide = 1;    // 16-byte-per-lane loads / stores in the equation-set kernels (SX_WIDE=0: the 8-byte forms, A/B timing)
     std::vector<int> hmask_full, hmask_eq;       // host copies of d_mask_full / d_mask_eq
     bool in_advance = false;    // set while sx_advance launches the equation set (the diagnostic w plane is then not stored)
     bool L_all_mult4 = false;   // every ring length is a multiple of 4 (native rings are): the MFMA DFT kernels apply
@@ -198,11 +248,7 @@ struct sx_handle {
     void *comm_state = nullptr;               // RCCL exchange state (sx_comm.cpp)
     void *iface_state = nullptr;              // interface-only patch solve (sx_iface.hip)
     void *pcr_state = nullptr;                // parallel-cyclic-reduction tables and launch lists (sx_pcr.hip)
-    int solve_pcr = -1;                       // SX_SOLVE_PCR read at sx_create: 0 never, 1 wherever the tables exist, -1 by column count
-    int64_t pcr_maxcols = 16384;              // SX_PCR_MAXCOLS
-    int rz_fused = 1;                         // RZ grids: the fused radius-on-the-matrix-cores kernels of sx_rz.hip (SX_RZ_FUSED=0: the general kernels)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
-    int semi_mfma = 1;                        // semi-implicit column operators on the matrix cores (SX_SEMI_MFMA=0: k_semiimplicit)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
     std::vector<int> hcls;                    // host copy of d_cls: [v][2] -> class of (k = 0, k >= 1)
     int *d_mask_full = nullptr, *d_mask_eq = nullptr;   // per-variable bit masks of derivative slots to produce

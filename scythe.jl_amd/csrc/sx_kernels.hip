@@ -2018,23 +2018,27 @@ void launch_zinv(sx_handle *h, bool full) {
         const int rows = (!full && h->node_mode && fft_fused_zinv(h)) ? (h->R_in > 0 ? std::min(h->nbt, h->R_in / MUBAR + 3) : 0) : h->nbt;
         h->last_zinv_rows = rows;
         if (rows == 0) { timer_end(h); return; }
-        static const int ct_env = getenv("SX_ZINV_CT") ? atoi(getenv("SX_ZINV_CT")) : 0;      // A/B: column tiles per wave at 128 levels
-        // only CT = 1, 2, 4 are instantiated at 128 levels (1, 2 at 64): any other request takes the default, never a grid sized for a kernel that is not launched
-        const int ct = h->nz == 128 ? ((ct_env == 1 || ct_env == 4) ? ct_env : 2) : (h->nz == 64 && ct_env == 2 ? 2 : 1);
-        dim3 g((h->K2 + 64 * ct - 1) / (64 * ct), njobs, rows);
+        const ZinvPlan p = plan_zinv(h->geom, h->nz, h->K2, h->sp32, h->sw);
+        dim3 g(p.grid_x, njobs, rows);
         const ColJob *jobs = full ? h->d_jobs_zinv_full : h->d_jobs_zinv_eq;
         const int64_t azrow = (int64_t)h->V * 3 * h->nz * h->K2;
-#define ZINV(MT, OT, CT) hipLaunchKernelGGL((k_colmat_mfma<MT, OT, CT>), g, dim3(256), 0, h->stream, h->d_A, reinterpret_cast<OT *>(h->d_Az), h->d_MzT, jobs, h->Zb, h->K2, h->C, azrow, h->cell0)
-        if (h->nz == 64 && ct == 2) { if (h->sp32) ZINV(4, float, 2); else ZINV(4, double, 2); }
-        else if (h->nz == 64) { if (h->sp32) ZINV(4, float, 1); else ZINV(4, double, 1); }
-        else if (h->nz == 32) { if (h->sp32) ZINV(2, float, 1); else ZINV(2, double, 1); }
-        else if (h->nz == 128 && ct == 1) { if (h->sp32) ZINV(8, float, 1); else ZINV(8, double, 1); }
-        else if (h->nz == 128 && ct == 4) { if (h->sp32) ZINV(8, float, 4); else ZINV(8, double, 4); }
-        else if (h->nz == 128) { if (h->sp32) ZINV(8, float, 2); else ZINV(8, double, 2); }
-#undef ZINV
-        else
+#define ZINV_T(MT, OT, CT) hipLaunchKernelGGL((k_colmat_mfma<MT, OT, CT>), g, dim3(256), 0, h->stream, h->d_A, reinterpret_cast<OT *>(h->d_Az), h->d_MzT, jobs, h->Zb, h->K2, h->C, azrow, h->cell0)
+#define ZINV(MT, CT) if (p.f32) ZINV_T(MT, float, CT); else ZINV_T(MT, double, CT); break
+        switch (p.kernel) {
+        case ZinvKernel::mfma_2_1: ZINV(2, 1);
+        case ZinvKernel::mfma_4_1: ZINV(4, 1);
+        case ZinvKernel::mfma_4_2: ZINV(4, 2);
+        case ZinvKernel::mfma_8_1: ZINV(8, 1);
+        case ZinvKernel::mfma_8_2: ZINV(8, 2);
+        case ZinvKernel::mfma_8_4: ZINV(8, 4);
+        case ZinvKernel::colmat:
             hipLaunchKernelGGL(k_colmat, g, dim3(64, 4), sizeof(double) * 64 * h->Zb, h->stream, h->d_A, h->d_Az, h->d_Mz, jobs,
                                h->Zb, h->nz, h->K2, h->C, azrow, h->cell0);
+            break;
+        case ZinvKernel::none: break;      // not reached: has_z and not the fused RZ form (above)
+        }
+#undef ZINV
+#undef ZINV_T
         HIPCHK(hipGetLastError());
     }
     timer_end(h);
@@ -2127,7 +2131,7 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
             a.col0 = 0; a.col1 = split;
 #define RING_LAUNCH(NZ_, CPB_)                                                                                                     \
             do {                                                                                                                      \
-                if (h->wide) hipLaunchKernelGGL((k_phys_hrbl_mfma<NZ_, CPB_, ST, true>), grid1(split, CPB_), dim3(CPB_ * NZ_), 0, h->stream, a);   \
+                if (h->sw.wide) hipLaunchKernelGGL((k_phys_hrbl_mfma<NZ_, CPB_, ST, true>), grid1(split, CPB_), dim3(CPB_ * NZ_), 0, h->stream, a);   \
                 else hipLaunchKernelGGL((k_phys_hrbl_mfma<NZ_, CPB_, ST, false>), grid1(split, CPB_), dim3(CPB_ * NZ_), 0, h->stream, a);          \
             } while (0)
             if (h->nz == 64) RING_LAUNCH(64, PCPB);
@@ -2147,7 +2151,7 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
 #endif
 #define CELL_LAUNCH(NZ_, LAM_)                                                                                                     \
             do {                                                                                                                      \
-                if (h->wide) hipLaunchKernelGGL((k_phys_hrbl_cell<NZ_, LAM_, ST, true>), dim3(ncell * (h->uniform_L / LAM_)), dim3(LAM_ * NZ_), 0, h->stream, a, h->R_in / MUBAR);   \
+                if (h->sw.wide) hipLaunchKernelGGL((k_phys_hrbl_cell<NZ_, LAM_, ST, true>), dim3(ncell * (h->uniform_L / LAM_)), dim3(LAM_ * NZ_), 0, h->stream, a, h->R_in / MUBAR);   \
                 else hipLaunchKernelGGL((k_phys_hrbl_cell<NZ_, LAM_, ST, false>), dim3(ncell * (h->uniform_L / LAM_)), dim3(LAM_ * NZ_), 0, h->stream, a, h->R_in / MUBAR);          \
             } while (0)
             if (h->nz == 64) CELL_LAUNCH(64, 4);      // LAM 2: 0.55 ms (6 of 16 MFMA columns, 1 KB chunks); 4: 0.41 ms
@@ -2189,7 +2193,7 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
         s.MrecT = h->d_MrecT; s.MdzT = h->d_MdzT; s.WT = h->d_WT[which]; s.XT = h->d_XT[which];
         s.N = h->N; s.nz = h->nz; s.t = t; s.wi = h->w_index - 1; s.xi = h->xi_index - 1;
         s.ts = h->ts; s.tau = h->tau[which]; s.pxi = h->par[SX_P_PXI_BAR];
-        if (h->semi_mfma) launch_semi_mfma(h, s);       // the four column operators on the matrix cores (sx_rz.hip)
+        if (h->sw.semi_mfma) launch_semi_mfma(h, s);       // the four column operators on the matrix cores (sx_rz.hip)
         else {
             const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
             const size_t lds = sizeof(double) * 3 * cpb * h->nz;
@@ -2223,7 +2227,7 @@ void launch_physics(sx_handle *h, int t) { launch_physics_part(h, t, 0); }
 // inverse and joined before the forward transform (measured gain 2.6 %: off by default, see sx_internal.hpp).
 void launch_inverse_and_physics(sx_handle *h, int t) {
     struct Scope { sx_handle *h; Scope(sx_handle *x) : h(x) { h->in_advance = true; } ~Scope() { h->in_advance = false; } } scope(h);
-    const bool two = h->node_mode && h->R_in > 0 && h->overlap && h->eq == SX_EQ_ONEWAY_SW_HRBL && !h->semi;
+    const bool two = h->node_mode && h->R_in > 0 && h->sw.overlap && h->eq == SX_EQ_ONEWAY_SW_HRBL && !h->semi;
     if (!two) {
         launch_rl_inverse(h, false);
         launch_physics(h, t);
@@ -2247,9 +2251,9 @@ void launch_inverse_and_physics(sx_handle *h, int t) {
     launch_node_fft(h);
     // overlap = 2: only the node FFT shares the chip with the inner chain; the cell-wise equation-set kernel (the dominant
     // one, whose event-timed duration is the roofline measurement) starts after the join and runs alone
-    if (h->overlap == 2) HIPCHK(hipStreamWaitEvent(s0, h->ev_join, 0));
+    if (h->sw.overlap == 2) HIPCHK(hipStreamWaitEvent(s0, h->ev_join, 0));
     launch_physics_part(h, t, 2);
-    if (h->overlap != 2) HIPCHK(hipStreamWaitEvent(s0, h->ev_join, 0));
+    if (h->sw.overlap != 2) HIPCHK(hipStreamWaitEvent(s0, h->ev_join, 0));
 }
 
 void launch_fl_forward(sx_handle *h) {
@@ -2272,65 +2276,51 @@ void launch_fl_forward(sx_handle *h) {
 }
 
 void launch_sb(sx_handle *h) {
-    if (rz_fused(h)) { launch_rz_forward(h); return; }
-    if (h->has_z) {        // fused with the vertical forward transform
-        const int id = timer_id(h, "k_sbz");
-        timer_begin(h, id);
-        if (h->nz == 64 || h->nz == 32 || h->nz == 128) {
-            // cells per workgroup (+3 warm-up cells).  With the prefetch (zDim <= 64: 177 VGPRs, one 512-thread workgroup per
-            // CU) the grid is ONE round of at most 256 workgroups; without it (zDim 128: 16 values per thread and ring leave no
-            // registers for a second set; or SX_SBW_PF=0) about 1.5 workgroups per CU as before.  On large tiles never fewer
-            // than 6 cells so that the warm-up stays below half of the reads
-            const bool mf = h->sbw_mfma && (h->nz <= 64 ? h->Zb <= 64 : h->Zb <= 96);      // matrix-core contraction + prefetch (k_sbw_mfma)
-            // zDim 64: 256-thread workgroups of 32 blocks, two per CU - one loads while the other contracts (0.127 -> 0.118 ms;
-            // SX_SBW_T256=0 restores the 512-thread form)
-            static const bool t256_env = !(getenv("SX_SBW_T256") && atoi(getenv("SX_SBW_T256")) == 0);
-            const bool t256 = t256_env && mf && h->nz == 64;
-            const int bw = ((mf && h->nz == 128) || t256) ? 32 : 64;         // wavenumber blocks per workgroup
-            const int groups = ((h->K2 + bw - 1) / bw) * h->v_cnt;
-            const bool pf = (h->sbw_prefetch && h->nz <= 64) || mf;
-            static const int seg_env = getenv("SX_SBW_SEG") ? atoi(getenv("SX_SBW_SEG")) : 0;      // experiments: segments per (block group, variable)
-            const int nseg = seg_env > 0 ? seg_env : std::max(1, ((mf && h->nz == 128) || t256 ? 512 : pf || h->nz == 128 ? 256 : 384) / groups);
-            // small tiles (multi-GPU strong scaling): the kernel is then one workgroup's latency chain, which is proportional
-            // to the cells it walks, so short segments (down to 2 cells + 3 warm-up) beat the saved re-reads
-            const int cps = std::max(h->ncells <= 64 ? 2 : 6, (h->ncells + nseg - 1) / nseg);
-            dim3 gw((h->K2 + bw - 1) / bw, h->v_cnt, (h->ncells + cps - 1) / cps);      // variable window: see sx_internal.hpp
-            const int64_t flo = (int64_t)h->v_lo * h->nz * h->K2, blo = (int64_t)h->v_lo * h->Zb * h->K2;
-#ifdef SX_PHASES
-            if (!g_sbw_buf) {
-                g_sbw_n = (int64_t)gw.x * gw.y * gw.z;
-                hipMalloc(&g_sbw_buf, sizeof(long long) * g_sbw_n * 8);
-                hipMemset(g_sbw_buf, 0, sizeof(long long) * g_sbw_n * 8);
-                hipMemcpyToSymbol(HIP_SYMBOL(g_sbw_dbg), &g_sbw_buf, sizeof(g_sbw_buf));
-            }
-#endif
-            auto kern = h->nz == 64 ? (pf ? k_sbw<64, true> : k_sbw<64, false>) : h->nz == 32 ? (pf ? k_sbw<32, true> : k_sbw<32, false>) : k_sbw<128, false>;
-            if (mf) kern = h->nz == 64 ? k_sbw_mfma<64> : h->nz == 32 ? k_sbw_mfma<32> : k_sbw_mfma<128, 32>;
-            if (t256) kern = k_sbw_mfma<64, 32, 256>;
-            if (h->sp32) {             // fp32-stored ring spectra (storage_f32 = 2; sx_create guarantees the matrix-core kernel applies)
-                auto kf = t256 ? k_sbw_mfma<64, 32, 256, float> : h->nz == 64 ? k_sbw_mfma<64, 64, 512, float>
-                          : h->nz == 32 ? k_sbw_mfma<32, 64, 512, float> : k_sbw_mfma<128, 32, 512, float>;
-                hipLaunchKernelGGL(kf, gw, dim3(t256 ? 256 : 512), 0, h->stream, reinterpret_cast<const float *>(h->d_Fl) + flo, h->d_Btile + blo, h->d_phi,
-                                   h->d_wq, h->d_CB, h->ncells, h->V, h->Zb, h->K2, h->C, cps);
-            } else
-            hipLaunchKernelGGL(kern, gw, dim3(t256 ? 256 : 512), 0, h->stream, h->d_Fl + flo, h->d_Btile + blo, h->d_phi, h->d_wq, h->d_CB, h->ncells,
-                               h->V, h->Zb, h->K2, h->C, cps);
-            HIPCHK(hipGetLastError());
-            timer_end(h);
-            return;
-        }
-        dim3 g((h->K2 + 63) / 64, h->V, h->nbt);
+    const SbPlan p = plan_sb(h->geom, h->nz, h->Zb, h->K2, h->v_cnt, h->ncells, h->sp32, h->sw);
+    if (p.kernel == SbKernel::rz_forward) { launch_rz_forward(h); return; }
+    if (p.kernel == SbKernel::refused) { set_error("launch_sb: fp32 ring spectra (storage_f32 = 2) need the matrix-core sliding-window kernel"); return; }
+    const int id = timer_id(h, h->has_z ? "k_sbz" : "k_sb");       // k_sbz: fused with the vertical forward transform
+    timer_begin(h, id);
+    if (p.kernel == SbKernel::sb) {
+        const int64_t plane = (int64_t)h->V * h->nz * h->K2;
+        dim3 g((unsigned)((plane + 255) / 256), h->nbt);
+        hipLaunchKernelGGL(k_sb, g, dim3(p.threads), 0, h->stream, h->d_Fl, h->d_Btile, h->d_phi, h->d_wq, h->ncells, plane);
+    } else if (p.kernel == SbKernel::sbz) {
+        dim3 g((h->K2 + p.bw - 1) / p.bw, h->V, h->nbt);
         hipLaunchKernelGGL(k_sbz, g, dim3(64, 4), sizeof(double) * 64 * h->nz, h->stream, h->d_Fl, h->d_Btile, h->d_phi, h->d_wq,
                            h->d_CB, h->ncells, h->V, h->nz, h->Zb, h->K2, h->C);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
-        return;
+    } else {       // the sliding-window kernels
+        dim3 gw((h->K2 + p.bw - 1) / p.bw, h->v_cnt, p.segs);      // variable window: see sx_internal.hpp
+        const int64_t flo = (int64_t)h->v_lo * h->nz * h->K2, blo = (int64_t)h->v_lo * h->Zb * h->K2;
+#ifdef SX_PHASES
+        if (!g_sbw_buf) {
+            g_sbw_n = (int64_t)gw.x * gw.y * gw.z;
+            hipMalloc(&g_sbw_buf, sizeof(long long) * g_sbw_n * 8);
+            hipMemset(g_sbw_buf, 0, sizeof(long long) * g_sbw_n * 8);
+            hipMemcpyToSymbol(HIP_SYMBOL(g_sbw_dbg), &g_sbw_buf, sizeof(g_sbw_buf));
+        }
+#endif
+        // FT: how the ring spectra d_Fl are stored (float: storage_f32 = 2)
+#define SBW(FT, ...) hipLaunchKernelGGL((__VA_ARGS__), gw, dim3(p.threads), 0, h->stream, reinterpret_cast<const FT *>(h->d_Fl) + flo, h->d_Btile + blo, \
+                                        h->d_phi, h->d_wq, h->d_CB, h->ncells, h->V, h->Zb, h->K2, h->C, p.cps); break
+        switch (p.kernel) {
+        case SbKernel::sbw_32: SBW(double, k_sbw<32, false>);
+        case SbKernel::sbw_32_pf: SBW(double, k_sbw<32, true>);
+        case SbKernel::sbw_64: SBW(double, k_sbw<64, false>);
+        case SbKernel::sbw_64_pf: SBW(double, k_sbw<64, true>);
+        case SbKernel::sbw_128: SBW(double, k_sbw<128, false>);
+        case SbKernel::mfma_32: SBW(double, k_sbw_mfma<32>);
+        case SbKernel::mfma_64: SBW(double, k_sbw_mfma<64>);
+        case SbKernel::mfma_64_t256: SBW(double, k_sbw_mfma<64, 32, 256>);
+        case SbKernel::mfma_128: SBW(double, k_sbw_mfma<128, 32>);
+        case SbKernel::mfma_32_f32: SBW(float, k_sbw_mfma<32, 64, 512, float>);
+        case SbKernel::mfma_64_f32: SBW(float, k_sbw_mfma<64, 64, 512, float>);
+        case SbKernel::mfma_64_t256_f32: SBW(float, k_sbw_mfma<64, 32, 256, float>);
+        case SbKernel::mfma_128_f32: SBW(float, k_sbw_mfma<128, 32, 512, float>);
+        default: break;      // the other kernels: above
+        }
+#undef SBW
     }
-    const int id = timer_id(h, "k_sb");
-    timer_begin(h, id);
-    const int64_t plane = (int64_t)h->V * h->nz * h->K2;
-    dim3 g((unsigned)((plane + 255) / 256), h->nbt);
-    hipLaunchKernelGGL(k_sb, g, dim3(256), 0, h->stream, h->d_Fl, h->d_Btile, h->d_phi, h->d_wq, h->ncells, plane);
     HIPCHK(hipGetLastError());
     timer_end(h);
 }

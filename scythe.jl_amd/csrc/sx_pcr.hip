@@ -39,8 +39,6 @@ struct PcrSeg {          // columns col0 + c * cstride, c < ncols (<= R), all of
     int ncols, cstride, cls, pad;
 };
 
-constexpr int PCR_IPT = 4;     // row items (patch row, column) per thread while loading B and storing A: nb * R <= 4 * blockDim (launcher)
-
 template <bool LINEAR>
 __global__ void __launch_bounds__(1024)
 k_solve_pcr(const double *__restrict__ Bsrc, const int64_t *__restrict__ boffA, const int64_t *__restrict__ boffB,
@@ -238,8 +236,8 @@ void pcr_release(sx_handle *h) {
 // forces the answer (1: wherever the tables exist); by default launches of up to SX_PCR_MAXCOLS (16384) columns do - above that the
 // lane-per-column kernel fills the chip and streams its rows at the HBM rate.
 bool pcr_wanted(sx_handle *h, int64_t ncols) {
-    if (h->solve_pcr == 0) return false;
-    if (h->solve_pcr != 1 && ncols > h->pcr_maxcols) return false;
+    if (h->sw.solve_pcr == 0) return false;
+    if (h->sw.solve_pcr != 1 && ncols > h->sw.pcr_maxcols) return false;
     return pcr_state(h)->ok;
 }
 
@@ -253,13 +251,8 @@ void launch_solve_pcr(sx_handle *h, bool linear, const double *Bsrc, const int64
     auto it = st->launches.find(key);
     if (it == st->launches.end()) {
         PcrLaunch pl;
-        const int64_t total = (int64_t)ng * (h->K2 > 1 ? h->K2 - 1 : 1);
-        static const int r_env = getenv("SX_PCR_R") ? atoi(getenv("SX_PCR_R")) : 0;
-        int R = r_env > 0 ? r_env : total <= 4096 ? 4 : total <= 16384 ? 8 : 16;
-        while (R > 1 && (int64_t)st->nblk_max * R > 1024) R >>= 1;
-        int logR = 0;
-        while ((1 << (logR + 1)) <= R) logR++;
-        R = 1 << logR;
+        const PcrPlan p = plan_pcr(st->nblk_max, h->b_rDim, h->K2, ng, h->sw);
+        const int R = p.R;
         std::vector<PcrSeg> segs;
         auto add = [&](int64_t col0, int64_t count, int cstride, int cls) {
             for (int64_t c = 0; c < count; c += R)
@@ -278,8 +271,8 @@ void launch_solve_pcr(sx_handle *h, bool linear, const double *Bsrc, const int64
         if (h->K2 > 2)
             for (int g = 0; g < ng; g++) add((int64_t)g * h->K2 + 2, h->K2 - 2, 1, h->hcls[(size_t)((vz0 + g) / h->Zb) * 2 + 1]);
         pl.nsegs = (int)segs.size();
-        pl.logR = logR;
-        pl.threads = std::min(1024, ((std::max(st->nblk_max * R, (h->b_rDim * R + PCR_IPT - 1) / PCR_IPT) + 63) / 64) * 64);
+        pl.logR = p.logR;
+        pl.threads = p.threads;
         pl.lds = sizeof(double) * ((size_t)2 * std::max(st->np_max, h->b_rDim) * R + 6 * R);
         void *d = nullptr;
         if (hipMalloc(&d, sizeof(PcrSeg) * segs.size()) != hipSuccess ||

@@ -1,0 +1,87 @@
+// Launch plans: which kernel instantiation and which grid a launcher takes, as pure functions of plain integers and the
+// switches.  No handle, no device: the launchers (sx_kernels.hip, sx_pcr.hip) dispatch on these, and sx_launch_plan returns
+// them to a caller without a GPU, so the tests name the launch shapes from the same arithmetic that launches them.
+#include "sx_internal.hpp"
+#include <algorithm>
+
+namespace sx {
+
+static bool fused_rz(int geometry, int sp32, const Switches &sw) { return sw.rz_fused && geometry == SX_GEOM_RZ && !sp32; }   // = rz_fused(h)
+
+// spectralTransform!'s radial inner products B = sum over cells (fused with the vertical forward transform where there is one)
+SbPlan plan_sb(int geometry, int nz, int Zb, int K2, int v_cnt, int ncells, int sp32, const Switches &sw) {
+    SbPlan p;
+    if (fused_rz(geometry, sp32, sw)) { p.kernel = SbKernel::rz_forward; return p; }
+    if (geometry != SX_GEOM_RZ && geometry != SX_GEOM_RLZ) { p.kernel = SbKernel::sb; p.threads = 256; return p; }
+    if (nz != 32 && nz != 64 && nz != 128) { p.kernel = SbKernel::sbz; p.threads = 256; p.bw = 64; return p; }
+    const bool mf = sw.sbw_mfma && (nz <= 64 ? Zb <= 64 : Zb <= 96);      // matrix-core contraction + prefetch (k_sbw_mfma)
+    if (sp32 && !mf) return p;                                            // refused
+    const bool t256 = sw.sbw_t256 && mf && nz == 64;
+    const bool narrow = (mf && nz == 128) || t256;
+    const bool pf = (sw.sbw_prefetch && nz <= 64) || mf;
+    // cells per workgroup (+3 warm-up cells).  With the prefetch (zDim <= 64: 177 VGPRs, one 512-thread workgroup per
+    // CU) the grid is ONE round of at most 256 workgroups; without it (zDim 128: 16 values per thread and ring leave no
+    // registers for a second set; or SX_SBW_PF=0) about 1.5 workgroups per CU as before.  On large tiles never fewer
+    // than 6 cells so that the warm-up stays below half of the reads
+    p.threads = t256 ? 256 : 512;
+    p.bw = narrow ? 32 : 64;
+    p.groups = ((K2 + p.bw - 1) / p.bw) * v_cnt;
+    p.nseg = sw.sbw_seg > 0 ? sw.sbw_seg : std::max(1, (narrow ? 512 : pf || nz == 128 ? 256 : 384) / p.groups);
+    // small tiles (multi-GPU strong scaling): the kernel is then one workgroup's latency chain, which is proportional
+    // to the cells it walks, so short segments (down to 2 cells + 3 warm-up) beat the saved re-reads
+    p.cps = std::max(ncells <= 64 ? 2 : 6, (ncells + p.nseg - 1) / p.nseg);
+    p.segs = (ncells + p.cps - 1) / p.cps;
+    using K = SbKernel;
+    if (sp32) p.kernel = t256 ? K::mfma_64_t256_f32 : nz == 64 ? K::mfma_64_f32 : nz == 32 ? K::mfma_32_f32 : K::mfma_128_f32;
+    else if (t256) p.kernel = K::mfma_64_t256;
+    else if (mf) p.kernel = nz == 64 ? K::mfma_64 : nz == 32 ? K::mfma_32 : K::mfma_128;
+    else p.kernel = nz == 64 ? (pf ? K::sbw_64_pf : K::sbw_64) : nz == 32 ? (pf ? K::sbw_32_pf : K::sbw_32) : K::sbw_128;
+    return p;
+}
+
+// the vertical inverse into Az (k_zinv)
+ZinvPlan plan_zinv(int geometry, int nz, int K2, int sp32, const Switches &sw) {
+    ZinvPlan p;
+    if ((geometry != SX_GEOM_RZ && geometry != SX_GEOM_RLZ) || fused_rz(geometry, sp32, sw)) return p;   // RZ: part of k_rz_inverse (sx_rz.hip)
+    // only CT = 1, 2, 4 are instantiated at 128 levels (1, 2 at 64): any other request takes the default, never a grid sized for a kernel that is not launched
+    const int ct = sw.zinv_ct;
+    p.CT = nz == 128 ? ((ct == 1 || ct == 4) ? ct : 2) : (nz == 64 && ct == 2 ? 2 : 1);
+    p.grid_x = (K2 + 64 * p.CT - 1) / (64 * p.CT);
+    p.f32 = sp32 != 0;
+    using K = ZinvKernel;
+    p.kernel = nz == 32 ? K::mfma_2_1 : nz == 64 ? (p.CT == 2 ? K::mfma_4_2 : K::mfma_4_1)
+               : nz == 128 ? (p.CT == 1 ? K::mfma_8_1 : p.CT == 4 ? K::mfma_8_4 : K::mfma_8_2) : K::colmat;
+    return p;
+}
+
+// k_solve_pcr over `ngroups` (variable, z-mode) groups: R columns per workgroup, by the launch's column count unless SX_PCR_R names
+// it; a power of two, and small enough that one thread per (block row, column) fits a workgroup (nblk_max R <= 1024)
+PcrPlan plan_pcr(int nblk_max, int b_rDim, int K2, int ngroups, const Switches &sw) {
+    PcrPlan p;
+    const int64_t total = (int64_t)ngroups * (K2 > 1 ? K2 - 1 : 1);
+    int R = sw.pcr_r > 0 ? sw.pcr_r : total <= 4096 ? 4 : total <= 16384 ? 8 : 16;
+    while (R > 1 && (int64_t)nblk_max * R > 1024) R >>= 1;
+    while ((1 << (p.logR + 1)) <= R) p.logR++;
+    p.R = 1 << p.logR;
+    p.threads = std::min(1024, ((std::max(nblk_max * p.R, (b_rDim * p.R + PCR_IPT - 1) / PCR_IPT) + 63) / 64) * 64);
+    return p;
+}
+
+std::string kernel_name(SbKernel k) {
+    static const char *const NAMES[] = {
+        "", "k_sb", "k_sbz", "k_rz_forward", "k_sbw<32, false>", "k_sbw<32, true>", "k_sbw<64, false>", "k_sbw<64, true>", "k_sbw<128, false>",
+        "k_sbw_mfma<32>", "k_sbw_mfma<64>", "k_sbw_mfma<64, 32, 256>", "k_sbw_mfma<128, 32>", "k_sbw_mfma<32, 64, 512, float>",
+        "k_sbw_mfma<64, 64, 512, float>", "k_sbw_mfma<64, 32, 256, float>", "k_sbw_mfma<128, 32, 512, float>"};
+    static_assert(sizeof(NAMES) / sizeof(NAMES[0]) == (size_t)SbKernel::mfma_128_f32 + 1, "one name per SbKernel");
+    return NAMES[(int)k];
+}
+
+std::string kernel_name(const ZinvPlan &p) {
+    if (p.kernel == ZinvKernel::none) return "";
+    if (p.kernel == ZinvKernel::colmat) return "k_colmat";
+    static const int MT[] = {2, 4, 4, 8, 8, 8};      // mfma_<MT>_<CT> in enum order; CT is the plan's
+    return "k_colmat_mfma<" + std::to_string(MT[(int)p.kernel - (int)ZinvKernel::mfma_2_1]) + ", " + (p.f32 ? "float" : "double") + ", " +
+           std::to_string(p.CT) + ">";
+}
+
+}  // namespace sx

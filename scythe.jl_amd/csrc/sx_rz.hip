@@ -418,13 +418,12 @@ void launch_semi_mfma(sx_handle *h, const SemiArgs &a) {
     hipLaunchKernelGGL(k_semi_mfma, dim3((unsigned)((h->Nh + RZ_T - 1) / RZ_T)), dim3(threads), lds, h->stream, a, h->Nh);
 }
 
-bool rz_fused(const sx_handle *h) { return h->rz_fused && h->geom == SX_GEOM_RZ && !h->sp32; }
+bool rz_fused(const sx_handle *h) { return h->sw.rz_fused && h->geom == SX_GEOM_RZ && !h->sp32; }
 
 void launch_rz_inverse(sx_handle *h, const int *d_mask) {
     const int id = timer_id(h, "k_rz_inverse");
     timer_begin(h, id);
-    static const bool by_nodes = !(getenv("SX_RZ_INV") && atoi(getenv("SX_RZ_INV")) == 0);      // A/B: 0 = the ring-tile form
-    if (by_nodes) {
+    if (h->sw.rz_inv) {      // A/B: 0 = the ring-tile form
         const int Zpn = (h->Zb + 31) / 32 * 32;
         dim3 gn((h->ncells + RZ_CT - 1) / RZ_CT, h->V, ((h->nz + 15) / 16 + 3) / 4);
         const size_t ldsn = sizeof(double) * ((size_t)Zpn * RZ_T + 3 * RZ_T * 65 + 3 * RZ_CT * MUBAR * 4);

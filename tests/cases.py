@@ -1,4 +1,7 @@
 """Shared test cases: one description drives the CPU oracle (oracle/) and the HIP path (scythe.jl_amd)."""
+import os
+from unittest import mock
+
 import numpy as np
 
 from oracle import oracle_np as O
@@ -7,6 +10,7 @@ from oracle import oracle_c as OC
 VARS6 = {"h": 1, "u": 2, "v": 3, "ub": 4, "vb": 5, "wb": 6}
 BCL6 = {"h": "R1T1", "u": "R1T0", "v": "R1T0", "ub": "R1T0", "vb": "R1T0", "wb": "R1T1"}   # models/cha_bell2024
 BCR6 = {"h": "R0", "u": "R1T1", "v": "R0", "ub": "R1T1", "vb": "R0", "wb": "R0"}
+GEOM = {"R": 0, "RZ": 1, "RL": 2, "RLZ": 3}      # SX_GEOM_* (include/scythe_hip.h)
 SW_PAR = dict(g=9.81, K=5000.0, Cd=2.4e-3, Hfree=2000.0, Hb=1000.0, f=5.0e-5, S1=1.0e-4, Kh=5000.0, Um=2.0, Vm=-1.0)
 
 
@@ -315,22 +319,16 @@ def dense_spline_transform(case, shared):
 
 def pcr_launch_geometry(case, ngroups=None, r_force=0):
     """What launch_solve_pcr (scythe.jl_amd/csrc/sx_pcr.hip) picks for one launch over `ngroups` (variable, z-mode) groups
-    (default: the whole patch): R columns per workgroup, threads per workgroup, the column count of the last workgroup of the
-    k = 0 run of a variable and of a group's k >= 1 run (== R: no partial segment), and whether the tables exist at all
-    (nblk_max <= 1024; else the launch falls back to k_solve).  r_force: SX_PCR_R."""
-    g = oracle_grid(case)
+    (default: the whole patch), from the library's own plan: R columns per workgroup, threads per workgroup; and the column
+    count of the last workgroup of the k = 0 run of a variable and of a group's k >= 1 run (== R: no partial segment), and
+    whether the tables exist at all (nblk_max <= 1024; else the launch falls back to k_solve).  r_force: SX_PCR_R."""
+    g, K2, _ = _handle_dims(case)
     nfree = {O.gamma_matrix(g.nc, bl, g.BCR[v]).shape[0] for v in g.names for bl in (g.BCL_k0[v], g.BCL[v])}
     nblk = max((n + 2) // 3 for n in nfree)
-    K2 = 2 * (g.kDim + 1) if g.has_l else 1          # the handle's block count (block 1 unused)
     ng = g.V * g.b_zDim if ngroups is None else ngroups
-    total = ng * (K2 - 1 if K2 > 1 else 1)
-    R = r_force if r_force > 0 else 4 if total <= 4096 else 8 if total <= 16384 else 16
-    while R > 1 and nblk * R > 1024:
-        R //= 2
-    R = 1 << (R.bit_length() - 1)
-    threads = min(1024, -(-max(nblk * R, -(-g.b_rDim * R // 4)) // 64) * 64)
+    _, (R, _, threads, *_) = launch_plan(PLAN_PCR, nblk, g.b_rDim, K2, ng, env={"SX_PCR_R": r_force} if r_force > 0 else None)
     last = lambda n: n - (n - 1) // R * R
-    return dict(R=R, threads=threads, columns=total, nblk=nblk, tail_k0=last(g.b_zDim),
+    return dict(R=R, threads=threads, columns=ng * (K2 - 1 if K2 > 1 else 1), nblk=nblk, tail_k0=last(g.b_zDim),
                 tail_k=last(K2 - 2) if K2 > 2 else None, tables=nblk <= 1024)
 
 
@@ -442,7 +440,27 @@ def check_full(hip, orc, rings, title, orc_alt=None):
 
 
 
-# ----------------------------------------------------------------------------- forward-path launch geometry (host mirrors)
+# ----------------------------------------------------------------------------- launch geometry, asked of the library
+PLAN_FORWARD, PLAN_ZINV, PLAN_PCR = 0, 1, 2      # include/scythe_hip.h
+_UNSET = object()
+
+
+def launch_plan(kind, *dims, env=_UNSET):
+    """sx_launch_plan (host only): (kernel text, [out integers]) under the SX_* switches of os.environ as it is now, or, with
+    `env`, under exactly the SX_* variables of that dict (None: no switch set) whatever the caller's environment holds."""
+    import ctypes as C
+    import scythe_jl_amd as S
+    from scythe_jl_amd import _lib as L
+    if env is not _UNSET:
+        scoped = {k: v for k, v in os.environ.items() if not k.startswith("SX_")}
+        scoped.update((k, str(v)) for k, v in (env or {}).items())
+        with mock.patch.dict(os.environ, scoped, clear=True):
+            return launch_plan(kind, *dims)
+    out, name = (C.c_int32 * 6)(), C.create_string_buffer(64)
+    L.check(S.load().sx_launch_plan(kind, (C.c_int32 * len(dims))(*dims), out, name, len(name)))
+    return name.value.decode(), list(out)
+
+
 def _handle_dims(case, tile=None):
     """(K2 of the handle, tile cells, nz, Zb) as sx_create sets them: K2 = 2 (kDim + 1) with kDim the PATCH's largest kmax."""
     g = oracle_grid(case)
@@ -451,53 +469,30 @@ def _handle_dims(case, tile=None):
     return g, K2, ncells
 
 
-def _env_int(env, name, default):
-    v = (env or {}).get(name)
-    return default if v is None else int(v)
-
-
 def sb_launch_geometry(case, env=None, storage="f64", tile=None, v_cnt=None):
     """What launch_sb (scythe.jl_amd/csrc/sx_kernels.hip) launches for spectralTransform! on the tile (cell0, ncells) (default:
     the whole patch) with the switches in `env` (SX_SBW_MFMA, SX_SBW_PF, SX_SBW_T256, SX_SBW_SEG, SX_RZ_FUSED) and v_cnt
-    variables in the window (default: all).  Restates the launcher's arithmetic:
+    variables in the window (default: all), from the library's own plan:
       kernel (with its template arguments), threads, bw (wavenumber blocks per workgroup), groups = ceil(K2 / bw) v_cnt,
-      nseg, cps = max(ncells <= 64 ? 2 : 6, ceil(ncells / nseg)) cells per segment, segs = ceil(ncells / cps), last = the last
-      segment's cells, tail = K2 % bw, and for the matrix-core kernels MT = ceil(Zb / 16), mhalf = ceil(MT / 2) and nmt, the
-      row tiles of each wave of a workgroup (k_sbw_mfma's mt0 / mt1 / nmt)."""
+      nseg, cps = max(ncells <= 64 ? 2 : 6, ceil(ncells / nseg)) cells per segment, segs = ceil(ncells / cps);
+    and what follows from those inside the kernels: last = the last segment's cells, tail = K2 % bw, and for the matrix-core
+    kernels MT = ceil(Zb / 16), mhalf = ceil(MT / 2) and nmt, the row tiles of each wave of a workgroup (k_sbw_mfma's mt0 /
+    mt1 / nmt)."""
     g, K2, ncells = _handle_dims(case, tile)
-    V = g.V if v_cnt is None else v_cnt
-    if not g.has_z:
-        return dict(kernel="k_sb", threads=256, ncells=ncells, K2=K2)
-    nz, Zb = g.zDim, g.b_zDim
-    sp32 = storage == "f32x"
-    if g.geometry == "RZ" and _env_int(env, "SX_RZ_FUSED", 1) != 0 and not sp32:
-        return dict(kernel="k_rz_forward", ncells=ncells, K2=K2)
-    if nz not in (32, 64, 128):
-        return dict(kernel="k_sbz", threads=256, ncells=ncells, K2=K2, bw=64, tail=K2 % 64)
-    mf = _env_int(env, "SX_SBW_MFMA", 1) != 0 and (Zb <= 64 if nz <= 64 else Zb <= 96)
-    if sp32 and not mf:
+    Zb = g.b_zDim if g.has_z else 1
+    kernel, (threads, bw, groups, nseg, cps, segs) = launch_plan(PLAN_FORWARD, GEOM[g.geometry], g.zDim if g.has_z else 1, Zb, K2,
+                                                                 g.V if v_cnt is None else v_cnt, ncells, storage == "f32x", env=env)
+    if not kernel:
         return dict(kernel=None, refused="storage_f32 = 2", ncells=ncells, K2=K2)       # sx_create refuses the handle
-    t256 = _env_int(env, "SX_SBW_T256", 1) != 0 and mf and nz == 64
-    bw = 32 if (mf and nz == 128) or t256 else 64
-    groups = -(-K2 // bw) * V
-    pf = (_env_int(env, "SX_SBW_PF", 0) != 0 and nz <= 64) or mf
-    seg_env = _env_int(env, "SX_SBW_SEG", 0)
-    nseg = seg_env if seg_env > 0 else max(1, (512 if (mf and nz == 128) or t256 else 256 if pf or nz == 128 else 384) // groups)
-    cps = max(2 if ncells <= 64 else 6, -(-ncells // nseg))
-    segs = -(-ncells // cps)
-    threads = 256 if t256 else 512
-    if sp32:
-        kernel = "k_sbw_mfma<%s, float>" % ("64, 32, 256" if t256 else "64, 64, 512" if nz == 64 else "32, 64, 512" if nz == 32
-                                             else "128, 32, 512")
-    elif t256:
-        kernel = "k_sbw_mfma<64, 32, 256>"
-    elif mf:
-        kernel = "k_sbw_mfma<%s>" % ("128, 32" if nz == 128 else nz)
-    else:
-        kernel = "k_sbw<%d, %s>" % (nz, "true" if pf and nz <= 64 else "false")
+    if kernel == "k_rz_forward":
+        return dict(kernel=kernel, ncells=ncells, K2=K2)
+    if kernel == "k_sb":
+        return dict(kernel=kernel, threads=threads, ncells=ncells, K2=K2)
+    if kernel == "k_sbz":
+        return dict(kernel=kernel, threads=threads, ncells=ncells, K2=K2, bw=bw, tail=K2 % bw)
     out = dict(kernel=kernel, threads=threads, bw=bw, groups=groups, nseg=nseg, cps=cps, segs=segs,
                last=ncells - (segs - 1) * cps, tail=K2 % bw, ncells=ncells, K2=K2)
-    if mf:
+    if kernel.startswith("k_sbw_mfma"):
         MT = -(-Zb // 16)
         mhalf = (MT + 1) // 2
         nmt = []
@@ -513,20 +508,17 @@ def sb_launch_geometry(case, env=None, storage="f64", tile=None, v_cnt=None):
 
 
 def zinv_launch_geometry(case, env=None, storage="f64"):
-    """What launch_zinv (sx_kernels.hip) launches for the vertical inverse into Az: k_colmat_mfma<MT = zDim / 16, OT, CT> at zDim
-    32 / 64 / 128 (CT from SX_ZINV_CT: 1, 2 or 4 at 128 levels, default 2; 2 at 64 levels on request, else 1), k_colmat
-    otherwise; grid.x = ceil(K2 / (64 CT)) and the tail K2 % (64 CT) of the last workgroup.  None where no k_zinv runs (R / RL
-    grids, fused RZ)."""
+    """What launch_zinv (sx_kernels.hip) launches for the vertical inverse into Az, from the library's own plan:
+    k_colmat_mfma<MT = zDim / 16, OT, CT> at zDim 32 / 64 / 128 (CT from SX_ZINV_CT: 1, 2 or 4 at 128 levels, default 2; 2 at 64
+    levels on request, else 1), k_colmat otherwise; grid.x = ceil(K2 / (64 CT)) and the tail K2 % (64 CT) of the last workgroup.
+    None where no k_zinv runs (R / RL grids, fused RZ)."""
     g, K2, _ = _handle_dims(case)
-    if not g.has_z or (g.geometry == "RZ" and _env_int(env, "SX_RZ_FUSED", 1) != 0 and storage != "f32x"):
+    kernel, (ct, grid_x, *_) = launch_plan(PLAN_ZINV, GEOM[g.geometry], g.zDim if g.has_z else 1, K2, storage == "f32x", env=env)
+    if not kernel:
         return None
-    nz = g.zDim
-    ct_env = _env_int(env, "SX_ZINV_CT", 0)
-    ct = ((ct_env if ct_env in (1, 4) else 2) if nz == 128 else 2 if nz == 64 and ct_env == 2 else 1)
-    OT = "float" if storage == "f32x" else "double"
-    kernel = "k_colmat_mfma<%d, %s, %d>" % (nz // 16, OT, ct) if nz in (32, 64, 128) else "k_colmat"
-    return dict(kernel=kernel, MT=nz // 16 if nz in (32, 64, 128) else None, CT=ct, OT=OT, grid_x=-(-K2 // (64 * ct)),
-                tail=K2 % (64 * ct), K2=K2)
+    mfma = kernel != "k_colmat"
+    return dict(kernel=kernel, MT=g.zDim // 16 if mfma else None, CT=ct, OT="float" if storage == "f32x" else "double",
+                grid_x=grid_x, tail=K2 % (64 * ct), K2=K2)
 
 
 # every instantiation the two launchers can pick

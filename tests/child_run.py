@@ -1,6 +1,6 @@
-"""One GPU job in a fresh child process, for the switches the library reads ONCE per process (into `static const` locals on the
-first launch that needs them: SX_PCR_R, SX_RZ_INV, SX_SBW_T256, SX_DFT_HALF).  A monkeypatch.setenv after the pytest process
-launched that kernel changes nothing, so the variant behind such a switch runs in a child started with the variable set.
+"""One GPU job in a fresh child process started with SX_* switches set, as a user sets them: before the process starts.  (The
+library reads every switch once per handle, at sx_create, so a monkeypatch.setenv before a handle is created reaches that handle
+too; tests/test_gpu_static_switches.py holds that with two handles in one process.)
 
 run_in_child(tmp_path, job, overrides): the child is `python -m tests.child_run <job json> <out.npz>` with os.environ | overrides
 (every queue and device variable inherited as it is), one child at a time, under a time limit.  The child writes the job's arrays

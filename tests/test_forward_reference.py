@@ -1,6 +1,6 @@
 """The references of tests/test_gpu_forward.py, checked without a GPU: oracle_np.forward_xp (spectralTransform! in extended
-precision with its condition scale) and the host mirrors of launch_sb / launch_zinv (cases.sb_launch_geometry /
-zinv_launch_geometry), pinned on shapes worked out by hand from the launcher code."""
+precision with its condition scale) and the library's launch plans for launch_sb / launch_zinv (sx_launch_plan through
+cases.sb_launch_geometry / zinv_launch_geometry), pinned on shapes worked out by hand from the launcher code."""
 import numpy as np
 import pytest
 

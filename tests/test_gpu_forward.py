@@ -4,7 +4,7 @@ launch_sb (csrc/sx_kernels.hip) picks k_sb (no z), k_sbz (zDim not 32 / 64 / 128
 k_sbw_mfma instantiations (fp64 or fp32-stored ring spectra), then cuts the patch into segments of cps cells with a 3-cell warm-up,
 the last segment owning the 3 trailing nodes; inside k_sbw_mfma the rows are split into row tiles per wave.  launch_zinv picks
 k_colmat_mfma<MT, OT, CT> or k_colmat.  Every case id names that launch as cases.sb_launch_geometry / zinv_launch_geometry
-compute it (the launchers' arithmetic restated on the host, pinned by tests/test_forward_reference.py), and
+report it (the library's own launch plans, sx_launch_plan, pinned by tests/test_forward_reference.py), and
 test_the_cases_reach_every_launcher_branch checks on the host that the list covers every instantiation.
 
 B is compared entry by entry with oracle_np.forward_xp, the same operation in extended precision, which also returns each entry's

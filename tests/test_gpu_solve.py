@@ -72,7 +72,7 @@ def _geometry_of_id(name):
 
 
 def test_the_ids_name_the_launch_geometry():
-    """The geometry in every id is what launch_solve_pcr computes (restated in cases.pcr_launch_geometry)."""
+    """The geometry in every id is what launch_solve_pcr computes (its plan, through cases.pcr_launch_geometry)."""
     for name, make in SOLVE_CASES + [(FULL_ID, FULL_CASE)]:
         geo = cases.pcr_launch_geometry(make())
         R, threads, tails = _geometry_of_id(name)

@@ -1,8 +1,10 @@
-"""-m gpu: the kernel variants behind process-wide switches, each run in a fresh child process (tests/child_run.py).
+"""-m gpu: the kernel variants behind SX_PCR_R, SX_RZ_INV, SX_SBW_T256 and SX_DFT_HALF.
 
-SX_PCR_R, SX_RZ_INV, SX_SBW_T256 and SX_DFT_HALF are read into `static const` locals on the first launch that needs them, so
-within one pytest process only the first value ever counts.  Every case here runs in its own child with the variable set, on a
-shape where the switch changes the launch, and is compared with the default in this process and with the oracle."""
+The library reads every switch once per handle, at sx_create (csrc/sx_api.cpp: read_switches), so a handle created after a
+monkeypatch.setenv runs the variant: test_two_handles_of_one_process_take_their_own_columns_per_workgroup holds that.  The older
+cases start a child process (tests/child_run.py) with the variable set from its first instruction on, which is how a user sets
+one; each runs on a shape where the switch changes the launch and is compared with the default in this process and with the
+oracle."""
 import numpy as np
 import pytest
 
@@ -92,3 +94,37 @@ def test_half_ring_forward_dft_on_native_rings(tmp_path):
     half-ring kernel (k_fl_forward_dft over ring classes) instead of the quarter-wave work list (k_fl_forward_dft_q).
     rlz_hrbl 9 cells x native x 10, 4 steps: every variable within 1e-13 of the default, fields within 1e-10 of the oracle."""
     _model_variant(tmp_path, ["rlz_hrbl", {"num_cells": 9, "zDim": 10}, {}], 4, {"SX_DFT_HALF": "1"})
+
+
+def test_two_handles_of_one_process_take_their_own_columns_per_workgroup(monkeypatch):
+    """One process, two handles of the PERIODIC KAT at 12 cells with SX_SOLVE_PCR=1: the first created under SX_PCR_R=1, the
+    second under SX_PCR_R=4.  The library's plan reports R = 1 and R = 4 under the two environments (the solution does not show
+    which R ran: a second handle that kept the first one's R would pass the comparison, not the plan), and each handle's
+    solution is within 1e-13 per column of the lane-per-column solve."""
+    import scythe_jl_amd as S
+    spec = PCR_SHAPES[1]
+    case = make_case(spec)
+    og = cases.oracle_grid(case)
+    geo = cases.pcr_launch_geometry(case)
+    job = {"kind": "spline", "cases": [spec]}
+    monkeypatch.setenv("SX_SOLVE_PCR", "1")
+    grids, sols = [], []
+    for r in (1, 4):
+        monkeypatch.setenv("SX_PCR_R", str(r))
+        _, (R, logR, _, *_) = cases.launch_plan(cases.PLAN_PCR, geo["nblk"], og.b_rDim, cases._handle_dims(case)[1], og.V * og.b_zDim)
+        assert (R, 1 << logR) == (r, r)
+        g = S.Grid(*cases.hip_params(case))          # both handles alive at once: nothing of the first is shared with the second
+        grids.append(g)
+    for g in grids:
+        g.set_patch_spectral_b(np.random.default_rng(5).standard_normal((int(g.dims.s_patch), g.V)))
+        g.splineTransform_()
+        sols.append(g.patchSpectral)
+        g.close()
+    monkeypatch.delenv("SX_PCR_R")
+    monkeypatch.setenv("SX_SOLVE_PCR", "0")
+    lane = run_job(job)["a0"]
+    for r, a in zip((1, 4), sols):
+        assert np.isfinite(a).all() and np.abs(a).max() > 0
+        e = cases.rel_err_per_column(a, lane, og.b_rDim).max()
+        print("SX_PCR_R=%d vs the lane-per-column solve: %.2e" % (r, e))
+        assert e <= 1e-13, (r, e)

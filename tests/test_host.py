@@ -238,3 +238,39 @@ def test_exchange_auto_picks_the_interface_only_solve_where_tiles_allow_it():
     # native rings balance gridpoints: the outer tiles are the short ones
     lay = S.PatchLayout(S.GridParameters(geometry="RL", xmin=0.0, xmax=1.0, num_cells=171, vars={"u": 1}), 8)
     assert sum(lay.ncells) == 171 and min(lay.ncells) >= 9
+
+
+def test_switches_are_read_in_one_place_and_documented():
+    """csrc/: getenv( occurs only in the switch reader (read_switches, sx_api.cpp), for SX_RCCL_LIB (a path, sx_comm.cpp) and
+    inside #ifdef SX_PHASES blocks (the *_PHASES_OUT paths of the diagnostic build); and DESIGN.md names every SX_* variable of
+    the switch table."""
+    import os
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "scythe.jl_amd", "csrc")
+    found = []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".cpp", ".hip", ".hpp")):
+            continue
+        depth, phases = 0, None          # preprocessor nesting; the depth at which an #ifdef SX_PHASES block opened
+        for ln, line in enumerate(open(os.path.join(csrc, name)), 1):
+            t = line.strip()
+            if t.startswith("#if"):
+                depth += 1
+                if phases is None and re.match(r"#ifdef\s+SX_PHASES\b", t):
+                    phases = depth
+            elif t.startswith("#endif"):
+                if phases == depth:
+                    phases = None
+                depth -= 1
+            if "getenv(" in line and phases is None:
+                found.append((name, t))
+    assert len(found) == 2, found
+    assert ("sx_api.cpp", "const char *v = getenv(r.env);") in found
+    assert [t for n, t in found if n == "sx_comm.cpp" and 'getenv("SX_RCCL_LIB")' in t], found
+    api = open(os.path.join(csrc, "sx_api.cpp")).read()
+    table = api[api.index("static const SwitchRow SWITCHES[] = {"):api.index("Switches read_switches() {")]
+    names = re.findall(r'\{"(SX_[A-Z0-9_]+)", &Switches::', table)
+    assert len(names) == 25 and len(set(names)) == 25 and table.count("{\"") == 25, names
+    design = open(os.path.join(root, "DESIGN.md")).read()
+    assert not [n for n in names if not re.search(r"`%s[`=]" % n, design)]
