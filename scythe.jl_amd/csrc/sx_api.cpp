@@ -465,13 +465,17 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     basis_tables(h->DX, phi);
     quad_weights(h->DX, wq);
     std::vector<double> hphi((size_t)3 * h->nrings * 4), hwq(h->nrings), hr(h->Nh), hcos(h->Nh), hsin(h->Nh);
-    const double off3[MUBAR] = {-std::sqrt(3.0 / 5.0) / 2.0, 0.0, std::sqrt(3.0 / 5.0) / 2.0};
+    for (int d = 0; d < 3; d++)
+        for (int mu = 0; mu < MUBAR; mu++)
+            for (int j = 0; j < 4; j++) h->cell_consts.phiw[d][mu][j] = phi[d][mu][j];
+    for (int mu = 0; mu < MUBAR; mu++) h->cell_consts.goff[mu] = gauss_offset(mu);
+    h->cell_consts.xmin = h->xmin; h->cell_consts.DX = h->DX; h->cell_consts.gcell0 = h->cell0;
     for (int i = 0; i < h->nrings; i++) {
         const int mu = i % MUBAR, c = h->cell0 + i / MUBAR;
         for (int d = 0; d < 3; d++)
             for (int j = 0; j < 4; j++) hphi[((size_t)d * h->nrings + i) * 4 + j] = phi[d][mu][j];
         hwq[i] = wq[mu];
-        const double r = h->xmin + h->DX * (c + 0.5 + off3[mu]);
+        const double r = h->xmin + h->DX * (c + 0.5 + gauss_offset(mu));
         for (int l = 0; l < h->hL[i]; l++) {
             const double lam = h->hoff[i] + 2.0 * M_PI * l / h->hL[i];
             hr[h->hpstart[i] + l] = r;
@@ -581,8 +585,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         if (!dalloc(h, &h->d_E[i], (size_t)h->V * N)) FAIL();
         if (h->semi && !dalloc(h, &h->d_I[i], (size_t)h->V * N)) FAIL();
     }
-    if (h->sp32 && !(fft_path_ok(h) && h->has_z && (h->nz == 32 || h->nz == 64 || h->nz == 128) && h->sw.sbw_mfma &&
-                     (h->nz <= 64 ? h->Zb <= 64 : h->Zb <= 96))) {
+    if (h->sp32 && !(mfma_shape(h, true) && h->sw.sbw_mfma)) {
         set_error("storage_f32 = 2 (fp32 spectral intermediates) needs an RLZ / RZ grid on a uniform power-of-two ring table with zDim 32, 64 or 128");
         FAIL();
     }
@@ -643,8 +646,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
             }
         }
         // node-space ("radial last") inverse: uniform power-of-two rings + the MFMA HRBL kernel
-        if (h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 && fft_path_ok(h) && h->has_z && (h->nz == 64 || h->nz == 32 || h->nz == 128) &&
-            h->sw.node_mode) {
+        if (h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 && mfma_shape(h) && h->sw.node_mode) {
             h->node_mode = 1;
             h->R_in = 0;
             while (h->R_in < h->nrings && h->hkmax[h->R_in] < h->kDim) h->R_in++;
@@ -706,9 +708,8 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     }
     h->v_lo = 0; h->v_cnt = h->V;
     // deferred diagnostic variable (sx_internal.hpp): one-tile HRBL runs whose forward path is the FFT + matrix-core kernels
-    h->defer_diag = h->sw.defer_diag && h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 &&
-                    h->ncells == h->nc && fft_path_ok(h) && h->has_z && (h->nz == 32 || h->nz == 64 || h->nz == 128) && h->sw.sbw_mfma &&
-                    (h->nz <= 64 ? h->Zb <= 64 : h->Zb <= 96);
+    h->defer_diag = h->sw.defer_diag && h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 && h->ncells == h->nc && mfma_shape(h, true) &&
+                    h->sw.sbw_mfma;
     if (sx_bind_patch_b(h, nullptr, nullptr)) FAIL();
     *out = h;
     return status();
@@ -830,7 +831,6 @@ int sx_synchronize(sx_handle *h) {
 int sx_get_gridpoints(const sx_handle *h, double *out) {
     clear_error();
     if (!h || !out) { set_error("null argument"); return 1; }
-    const double off3[MUBAR] = {-std::sqrt(3.0 / 5.0) / 2.0, 0.0, std::sqrt(3.0 / 5.0) / 2.0};
     std::vector<double> z(h->nz, 0.0);
     if (h->has_z)
         for (int n = 0; n < h->nz; n++)
@@ -838,7 +838,7 @@ int sx_get_gridpoints(const sx_handle *h, double *out) {
     int64_t p = 0;
     for (int i = 0; i < h->nrings; i++) {
         const int mu = i % MUBAR, c = h->cell0 + i / MUBAR;
-        const double r = h->xmin + h->DX * (c + 0.5 + off3[mu]);
+        const double r = h->xmin + h->DX * (c + 0.5 + gauss_offset(mu));
         for (int l = 0; l < h->hL[i]; l++) {
             const double lam = h->hoff[i] + 2.0 * M_PI * l / h->hL[i];
             for (int k = 0; k < h->nz; k++, p++) {
@@ -1052,6 +1052,17 @@ void flush_diag(sx_handle *h) {
     launch_solve(h);
     h->v_lo = 0; h->v_cnt = h->V;
 }
+
+// the launches of one time step: sx_advance stops before the banded solve (tiles exchange there), sx_step runs it (one-tile patches)
+static void step_launches(sx_handle *h, int t, bool solve) {
+    launch_zinv(h, false);
+    launch_inverse_and_physics(h, t);
+    if (h->defer_diag) { h->v_cnt = h->V - 1; h->diag_dirty = true; }      // w's coefficients follow on demand (flush_diag)
+    launch_fl_forward(h);
+    launch_sb(h);
+    if (solve) launch_solve(h);
+    h->v_cnt = h->V;
+}
 }  // namespace sx
 
 extern "C" {
@@ -1095,12 +1106,7 @@ int sx_advance(sx_handle *h, int32_t t) {
     clear_error();
     if (!h) { set_error("null handle"); return 1; }
     if (t < 1) { set_error("t is 1-based"); return 1; }
-    launch_zinv(h, false);
-    launch_inverse_and_physics(h, t);
-    if (h->defer_diag) { h->v_cnt = h->V - 1; h->diag_dirty = true; }      // w's coefficients follow on demand (flush_diag)
-    launch_fl_forward(h);
-    launch_sb(h);
-    h->v_cnt = h->V;
+    step_launches(h, t, false);
     return status();
 }
 
@@ -1118,15 +1124,6 @@ void graphs_release(sx_handle *h) {
     }
 }
 
-static void step_launches(sx_handle *h, int t) {          // = sx_advance + sx_spline_transform
-    launch_zinv(h, false);
-    launch_inverse_and_physics(h, t);
-    if (h->defer_diag) { h->v_cnt = h->V - 1; h->diag_dirty = true; }
-    launch_fl_forward(h);
-    launch_sb(h);
-    launch_solve(h);
-    h->v_cnt = h->V;
-}
 }  // namespace sx
 
 extern "C" {
@@ -1140,7 +1137,7 @@ int sx_step(sx_handle *h, int32_t t) {
     // first launch (work lists, elimination tables, function attributes) must exist before a capture, which may not allocate
     const bool graph = h->sw.use_graph && !h->timers_on && t >= 3 && h->plain_steps >= 2 && h->eq != SX_EQ_NONE && !h->comm_state;
     if (!graph) {
-        step_launches(h, t);
+        step_launches(h, t, true);
         h->plain_steps++;
         return status();
     }
@@ -1149,7 +1146,7 @@ int sx_step(sx_handle *h, int32_t t) {
         // capture this rotation's launches.  The null stream cannot be captured: a handle that runs on it captures and replays on
         // a private BLOCKING stream, which the null stream's legacy semantics order against everything else the handle does
         hipStream_t user = h->stream;
-        if (!user && !h->graph_stream && hipStreamCreate(&h->graph_stream) != hipSuccess) { h->sw.use_graph = 0; step_launches(h, t); return status(); }
+        if (!user && !h->graph_stream && hipStreamCreate(&h->graph_stream) != hipSuccess) { h->sw.use_graph = 0; step_launches(h, t, true); return status(); }
         hipStream_t cs = user ? user : h->graph_stream;
         hipGraph_t g = nullptr;
         hipGraphExec_t ex = nullptr;
@@ -1157,7 +1154,7 @@ int sx_step(sx_handle *h, int32_t t) {
         bool ok = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) == hipSuccess;
         if (ok) {
             h->stream = cs;
-            step_launches(h, t);
+            step_launches(h, t, true);
             h->stream = user;
             ok = hipStreamEndCapture(cs, &g) == hipSuccess && g && !error_status();
             if (ok) ok = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess;
@@ -1168,7 +1165,7 @@ int sx_step(sx_handle *h, int32_t t) {
             clear_error();
             h->sw.use_graph = 0;
             h->rot = rot0;
-            step_launches(h, t);
+            step_launches(h, t, true);
             return status();
         }
         h->graph_exec[key] = ex;

@@ -26,12 +26,6 @@
 
 namespace sx {
 
-#define HIPCHK3(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) set_error(std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
 typedef double dft_d4 __attribute__((ext_vector_type(4)));
 
 // phase stamps of the diagnostic build (-DSX_PHASES): per workgroup of k_rl_inverse_dft, as seen by wave 0:
@@ -1492,7 +1486,7 @@ static void launch_rl_inverse_dft_planes(sx_handle *h, bool full) {
         {                                                                                                                            \
             const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * KCHQ * NG * CSTP);                                   \
             auto kern = k_rl_inverse_dft_planes_q<ST, NG>;                                                                           \
-            HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             hipLaunchKernelGGL(kern, dim3(h->n_rlq_items[0]), dim3(512), lds, h->stream, a, planes_of<ST>(h->d_phys, h->V, h->N),    \
                                h->d_phi, h->d_L, h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->K2,      \
                                h->nrings, h->N, h->C, pgs, h->d_rlq_items[0], lcap);                                                 \
@@ -1500,7 +1494,7 @@ static void launch_rl_inverse_dft_planes(sx_handle *h, bool full) {
         if (h->f32) { if (pgs.ng == 1) DFT_INVQ(float, 1) else if (pgs.ng == 2) DFT_INVQ(float, 2) else DFT_INVQ(float, 3) }
         else { if (pgs.ng == 1) DFT_INVQ(double, 1) else if (pgs.ng == 2) DFT_INVQ(double, 2) else DFT_INVQ(double, 3) }
 #undef DFT_INVQ
-        HIPCHK3(hipGetLastError());
+        HIPCHK(hipGetLastError());
         return;
     }
     const double *a = h->d_A + (int64_t)h->cell0 * h->C;
@@ -1512,14 +1506,14 @@ static void launch_rl_inverse_dft_planes(sx_handle *h, bool full) {
 #define DFT_INVP(ST)                                                                                                                 \
         {                                                                                                                            \
             auto kern = k_rl_inverse_dft_planes<ST>;                                                                                 \
-            HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             hipLaunchKernelGGL(kern, dim3(nr, nsplit, pgs.ng), dim3(512), lds, h->stream, a, planes_of<ST>(h->d_phys, h->V, h->N),   \
                                h->d_phi, h->d_L, h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->K2,      \
                                h->nrings, h->N, h->C, pgs, r0, lcap, kcap4);                                                                \
         }
         if (h->f32) DFT_INVP(float) else DFT_INVP(double)
 #undef DFT_INVP
-        HIPCHK3(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }, 2);
 }
 
@@ -1569,7 +1563,7 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
 #define DFT_INVB(ST)                                                                                                                 \
             {                                                                                                                        \
                 auto kern = k_rl_inverse_dft_big<ST>;                                                                                \
-                HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); \
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); \
                 hipLaunchKernelGGL(kern, gb, dim3(512), ldsb, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L, \
                                    h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2,     \
                                    h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],   \
@@ -1577,7 +1571,7 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
             }
             if (h->f32) DFT_INVB(float) else DFT_INVB(double)
 #undef DFT_INVB
-            HIPCHK3(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
         const int lcap = h->dft_lcap_small, kcap4 = (h->dft_kcap_small + 1 + 3) & ~3;
         const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * kcap4 * CST);
@@ -1596,7 +1590,7 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
 #define DFT_INVH(ST)                                                                                                                 \
                 {                                                                                                                    \
                     auto kern = k_rl_inverse_dft_merged<ST, 2, true>;                                                                \
-                    HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsh)); \
+                    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsh)); \
                     hipLaunchKernelGGL(kern, g, dim3(256), ldsh, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L, \
                                        h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2, \
                                        h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5], \
@@ -1604,14 +1598,14 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
                 }
                 if (h->f32) DFT_INVH(float) else DFT_INVH(double)
 #undef DFT_INVH
-                HIPCHK3(hipGetLastError());
+                HIPCHK(hipGetLastError());
                 timer_end(h);
                 return;
             }
 #define DFT_INVM(ST)                                                                                                                 \
             {                                                                                                                        \
                 auto kern = e8 ? k_rl_inverse_dft_merged<ST, 2> : k_rl_inverse_dft_merged<ST, 0>;                                    \
-                HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm)); \
+                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm)); \
                 hipLaunchKernelGGL(kern, g, dim3(512), ldsm, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L,  \
                                    h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2,     \
                                    h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],   \
@@ -1619,14 +1613,14 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
             }
             if (h->f32) DFT_INVM(float) else DFT_INVM(double)
 #undef DFT_INVM
-            HIPCHK3(hipGetLastError());
+            HIPCHK(hipGetLastError());
             timer_end(h);
             return;
         }
 #define DFT_INV(ST)                                                                                                                  \
         {                                                                                                                            \
             auto kern = k_rl_inverse_dft<ST>;                                                                                        \
-            HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
             hipLaunchKernelGGL(kern, g, dim3(512), lds, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L,       \
                                h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2,         \
                                h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],       \
@@ -1634,7 +1628,7 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
         }
         if (h->f32) DFT_INV(float) else DFT_INV(double)
 #undef DFT_INV
-        HIPCHK3(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }
     timer_end(h);
 }
@@ -1647,10 +1641,10 @@ void launch_fl_forward_dft(sx_handle *h) {
     if (planes && h->sw.rl_quarter && rlq_lists(h)) {      // RL grids: quarter-wave fold, one launch over (ring, part) items
         const int lcap = h->L_max;
         const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * LCQ * CST);
-        HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_qp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_qp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_fl_forward_dft_qp, dim3(h->n_rlq_items[1]), dim3(512), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
                            h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->K2, h->N, h->d_rlq_items[1], lcap);
-        HIPCHK3(hipGetLastError());
+        HIPCHK(hipGetLastError());
         timer_end(h);
         return;
     }
@@ -1666,10 +1660,10 @@ void launch_fl_forward_dft(sx_handle *h) {
             const int kparts = part == 0 ? ((h->kmax_max / 2 + 1 + 15) / 16 + 4 * NTW - 1) / (4 * NTW) : 1;
             const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * LCZ * CST);
             dim3 g((h->nz + DZC - 1) / DZC, n, kparts);
-            HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_q), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_q), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(k_fl_forward_dft_q, g, dim3(512), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
                                h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N, h->d_dft_items[2] + (part == 0 ? 0 : 2 * nbig), lcap);
-            HIPCHK3(hipGetLastError());
+            HIPCHK(hipGetLastError());
         }
         timer_end(h);
         return;
@@ -1681,10 +1675,10 @@ void launch_fl_forward_dft(sx_handle *h) {
         int kcap = 0;
         for (int i = r0; i < r0 + nr; i++) kcap = std::max(kcap, h->hkmax[i]);
         dim3 g(planes ? 1 : (h->nz + DZC - 1) / DZC, planes ? ((kcap + 1 + 15) / 16 + 7) / 8 : h->V, nr);
-        HIPCHK3(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(k_fl_forward_dft, g, dim3(512), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
                            h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N, r0, lcap, planes, ntw);
-        HIPCHK3(hipGetLastError());
+        HIPCHK(hipGetLastError());
     }, planes ? 2 : 4);
     timer_end(h);
 }

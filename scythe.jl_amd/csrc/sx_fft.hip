@@ -16,12 +16,6 @@
 
 namespace sx {
 
-#define HIPCHK2(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) set_error(std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
 // z levels per workgroup (FZC) and complex transforms per slot and workgroup (FNP = FZC / 2).  A transform of length L is
 // owned by LPT = min(L / 4, 64) lanes of ONE wave, so every pass is wave-local; for L = 512 a lane carries NB = 2 radix-4
 // butterflies per pass (and NK = 4 wavenumbers while staging) instead of spreading the transform over two waves that had to
@@ -717,7 +711,7 @@ static void launch_inv(sx_handle *h, const int *d_mask, const InvTarget &tg, con
 #define INV_LAUNCH_V(NODE, ST, AT, HL, SETS)                                                                                         \
     do {                                                                                                                             \
         if (fft_lds(L, SETS) > 65536)                                                                                                \
-            HIPCHK2(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, HL, SETS>),           \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, HL, SETS>),           \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds(L, SETS)));                        \
         hipLaunchKernelGGL((k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, HL, SETS>), g, dim3(fft_threads(L, HL)), fft_lds(L, SETS), h->stream, \
                            reinterpret_cast<const AT *>(az), planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart,          \
@@ -729,7 +723,7 @@ static void launch_inv(sx_handle *h, const int *d_mask, const InvTarget &tg, con
     do {                                                                                                                             \
         constexpr int RS = 2;                                                                                                        \
         if (fft_lds(L, RS, true) > 65536)                                                                                            \
-            HIPCHK2(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, 0, RS, false, true>), \
+            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, 0, RS, false, true>), \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds(L, RS, true)));                    \
         hipLaunchKernelGGL((k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, 0, RS, false, true>), g, dim3(fft_threads(L, 0)), fft_lds(L, RS, true), h->stream, \
                            reinterpret_cast<const AT *>(az), planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart,          \
@@ -769,7 +763,7 @@ static void launch_inv_any(sx_handle *h, const int *d_mask, const InvTarget &tg)
         case 8: launch_inv<8>(h, d_mask, tg, az, azrow); break;
         default: launch_inv<9>(h, d_mask, tg, az, azrow); break;
     }
-    HIPCHK2(hipGetLastError());
+    HIPCHK(hipGetLastError());
 }
 
 template <int LOGL>
@@ -841,7 +835,7 @@ void launch_fl_forward_fft(sx_handle *h) {
         case 8: launch_fwd<8>(h, g); break;
         default: launch_fwd<9>(h, g); break;
     }
-    HIPCHK2(hipGetLastError());
+    HIPCHK(hipGetLastError());
     timer_end(h);
 }
 

@@ -29,12 +29,6 @@
 
 namespace sx {
 
-#define HIPCHK(x)                                                                                   \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) set_error(std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
 constexpr int IF_E = 6, IF_X = 4, IF_R = IF_E + IF_X;      // edge values + foreign rows = rows per tile that travel
 constexpr int IF_META = 8;                                  // per class: nt, rowbase, nlead, ntrail, xrow[4]
 

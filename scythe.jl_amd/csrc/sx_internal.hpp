@@ -1,13 +1,23 @@
 // Internal declarations of libscythe_hip.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <utility>
 #include <vector>
 #include "scythe_hip.h"
 
+// a failed HIP call becomes the library's error text, naming the call and the place of the use
+#define HIPCHK(x)                                                                                   \
+    do {                                                                                            \
+        hipError_t e_ = (x);                                                                        \
+        if (e_ != hipSuccess) ::sx::set_error(std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
+    } while (0)
+
 namespace sx {
+
+void set_error(const std::string &msg);
 
 constexpr int DFT_KMAX_SINGLE = 319;   // largest kmax whose coefficient sets fit the LDS beside the twiddle table (sx_dft.hip)
 constexpr int MUBAR = 3;   // CubicBSpline.mubar: mish points per cell (src/spectralGrid.jl:24)
@@ -61,6 +71,11 @@ void pcr_apply_host(const PcrTables &t, int nb, const double *b, double *a);
 // the serial statement of the same solve (banded Cholesky factors of build_spline_class), on the host
 void cholesky_apply_host(const SplineClass &sc, int nb, const double *b, double *a);
 void basis_tables(double DX, double phi[4][MUBAR][4]);
+// offset of Gauss point mu from its cell's centre, in cells: ring mu of cell c lies at r = xmin + DX (c + 0.5 + gauss_offset(mu))
+inline double gauss_offset(int mu) {
+    const double o = std::sqrt(3.0 / 5.0) / 2.0;
+    return mu == 0 ? -o : mu == 1 ? 0.0 : o;
+}
 void quad_weights(double DX, double w[MUBAR]);
 int bc_rank(int bc);
 bool build_spline_class(int nc, double DX, double l_q, int bcl, int bcr, SplineClass &out, std::string &err);
@@ -84,6 +99,15 @@ template <class ST>
 __host__ __device__ inline Planes<ST> planes_of(double *base, int V, int64_t n) {
     return Planes<ST>{base, reinterpret_cast<ST *>(base + (int64_t)V * n)};
 }
+
+// Cell-independent constants of the cell-wise equation-set kernel (sx_physics.hip), filled by sx_create; kernel arguments, so
+// scalar registers and no loads: basis weights phi / phi' / phi'' of a cell's 3 Gauss points at its 4 nodes, and what it takes to
+// recompute r exactly as sx_create tabulates it
+struct CellConsts {
+    double phiw[3][MUBAR][4];
+    double xmin, DX, goff[MUBAR];
+    int gcell0;           // patch index of the tile's first cell
+};
 
 struct ColJob {
     int64_t in_off, out_off, mat_off;
@@ -227,6 +251,7 @@ struct sx_handle {
     std::vector<int> hmask_full, hmask_eq;       // host copies of d_mask_full / d_mask_eq
     bool in_advance = false;    // set while sx_advance launches the equation set (the diagnostic w plane is then not stored)
     bool L_all_mult4 = false;   // every ring length is a multiple of 4 (native rings are): the MFMA DFT kernels apply
+    sx::CellConsts cell_consts = {};
     double *d_ref = nullptr;    // ReferenceState [3][3][nz] (Euler_test)
     int f32 = 0;   // fp32 storage of the derivative slots of d_phys / d_G (typed by the launchers)
     int sp32 = 0;  // storage_f32 = 2: the spectral transform intermediates d_Az and d_Fl are fp32 as well (fp64 accumulation)
@@ -277,10 +302,17 @@ struct sx_handle {
 };
 
 namespace sx {
-// kernel launchers (sx_kernels.hip); each returns hipError_t from the launch
+// kernel launchers (transforms, solve, pack: sx_kernels.hip; equation sets: sx_physics.hip); a failed launch goes to set_error
+inline dim3 grid1(int64_t n, int bs) { return dim3((unsigned)((n + bs - 1) / bs)); }
 void launch_zinv(sx_handle *h, bool full);
 void launch_rl_inverse(sx_handle *h, bool full);
 bool fft_path_ok(const sx_handle *h);
+// zDim with matrix-core column kernels (the HRBL equation set, the sliding-window forward transform)
+inline bool mfma_levels(int nz) { return nz == 32 || nz == 64 || nz == 128; }
+// the matrix-core shape: uniform power-of-two rings with such a zDim; zb_bound: b_zDim also fits k_sbw_mfma's row tiles
+inline bool mfma_shape(const sx_handle *h, bool zb_bound = false) {
+    return fft_path_ok(h) && h->has_z && mfma_levels(h->nz) && (!zb_bound || (h->nz <= 64 ? h->Zb <= 64 : h->Zb <= 96));
+}
 bool fft_fused_zinv(const sx_handle *h);
 bool dft_mfma_ok(const sx_handle *h);
 void launch_rl_inverse_dft(sx_handle *h, const int *d_mask);
@@ -303,7 +335,6 @@ int timer_id(sx_handle *h, const char *name);
 void timer_begin(sx_handle *h, int id);
 void timer_end(sx_handle *h);
 void timers_flush(sx_handle *h);
-void set_error(const std::string &msg);
 void clear_error();
 int error_status();   // 1 if set_error has been called since the last clear_error
 void comm_release(sx_handle *h);

@@ -22,12 +22,6 @@
 
 namespace sx {
 
-#define HIPCHK3(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) set_error(std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
 struct PcrClassDev {
     int n, nblk, levels, periodic;
     const double *coef, *dinv, *gin_w, *gout_w, *G;
@@ -291,7 +285,7 @@ void launch_solve_pcr(sx_handle *h, bool linear, const double *Bsrc, const int64
     else
         hipLaunchKernelGGL(k_solve_pcr<false>, dim3(pl.nsegs), dim3(pl.threads), pl.lds, h->stream, Bsrc, boffA, boffB, A, aoffA, aoffB,
                            st->d_classes, pl.d_segs, h->b_rDim, pl.logR, stride);
-    HIPCHK3(hipGetLastError());
+    HIPCHK(hipGetLastError());
 }
 
 }  // namespace sx

@@ -19,12 +19,6 @@
 
 namespace sx {
 
-#define HIPCHK4(x)                                                                                  \
-    do {                                                                                            \
-        hipError_t e_ = (x);                                                                        \
-        if (e_ != hipSuccess) set_error(std::string(#x) + ": " + hipGetErrorString(e_) + " (" __FILE__ ":" + std::to_string(__LINE__) + ")"); \
-    } while (0)
-
 typedef double rz_d4 __attribute__((ext_vector_type(4)));
 constexpr int RZ_T = 16;          // rings (inverse) / nodes (forward) per workgroup: one MFMA row tile
 constexpr int RZ_KC = 16;         // K steps whose operator fragments are in registers at once (32 VGPRs)
@@ -412,7 +406,7 @@ k_semi_mfma(SemiArgs a, int64_t ncol) {
 void launch_semi_mfma(sx_handle *h, const SemiArgs &a) {
     const int Kp = (h->nz + 4 * RZ_KC - 1) / (4 * RZ_KC) * (4 * RZ_KC);
     const size_t lds = sizeof(double) * 4 * Kp * RZ_T;
-    if (lds > 65536) HIPCHK4(hipFuncSetAttribute(reinterpret_cast<const void *>(k_semi_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_semi_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     const int nzt = (h->nz + 15) / 16;
     const int threads = 64 * std::min(8, nzt);
     hipLaunchKernelGGL(k_semi_mfma, dim3((unsigned)((h->Nh + RZ_T - 1) / RZ_T)), dim3(threads), lds, h->stream, a, h->Nh);
@@ -432,7 +426,7 @@ void launch_rz_inverse(sx_handle *h, const int *d_mask) {
                                        d_mask, h->V, h->nz, h->Zb, h->ncells, h->nbt, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
         if (ldsn <= 65536) {
             if (h->f32) RZ_INVN(float); else RZ_INVN(double);
-            HIPCHK4(hipGetLastError());
+            HIPCHK(hipGetLastError());
             timer_end(h);
             return;
         }
@@ -442,15 +436,15 @@ void launch_rz_inverse(sx_handle *h, const int *d_mask) {
     dim3 g((h->nrings + RZ_T - 1) / RZ_T, h->V, ((h->nz + 15) / 16 + 3) / 4);
     const size_t lds = sizeof(double) * 3 * Zp * RZ_T;
     if (lds > 65536) {
-        HIPCHK4(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK4(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
     const double *arows = h->d_A + (int64_t)h->cell0 * h->C;
 #define RZ_INV(ST) hipLaunchKernelGGL(k_rz_inverse<ST>, g, dim3(256), lds, h->stream, arows, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_MzT, \
                                       d_mask, h->V, h->nz, h->Zb, h->nrings, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
     if (h->f32) RZ_INV(float); else RZ_INV(double);
 #undef RZ_INV
-    HIPCHK4(hipGetLastError());
+    HIPCHK(hipGetLastError());
     timer_end(h);
 }
 
@@ -463,7 +457,7 @@ void launch_rz_forward(sx_handle *h) {
     const size_t lds = sizeof(double) * (Np * RZ_T + 19 * MUBAR * 4);
     hipLaunchKernelGGL(k_rz_forward, g, dim3(256), lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N, h->d_Btile + (int64_t)h->v_lo * h->Zb,
                        h->d_phi, h->d_wq, h->d_CBT, h->ncells, h->nbt, h->V, h->nz, h->Zb, h->N, h->C, mt_per_wg);
-    HIPCHK4(hipGetLastError());
+    HIPCHK(hipGetLastError());
     timer_end(h);
 }
 

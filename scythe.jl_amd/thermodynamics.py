@@ -1,5 +1,5 @@
 """Host mirror of src/thermodynamics.jl (vectorised numpy): what the reference-state construction and output
-diagnostics need.  The per-step thermodynamics of the equation sets runs on the device (csrc/sx_kernels.hip, namespace
+diagnostics need.  The per-step thermodynamics of the equation sets runs on the device (csrc/sx_physics.hip, namespace
 thermo); these functions are set-up / post-processing helpers with the reference's names and argument order."""
 import numpy as np
 
