@@ -250,6 +250,30 @@ int sx_check_nan(sx_handle *h, int32_t *flag);
  * maximum NaN (like maximum(abs, x) in Julia).  No allocation per call: the scratch lives with the handle. */
 int sx_max_abs(sx_handle *h, double *out);
 
+/* --- evaluation at arbitrary points --------------------------------------------------------------------------------
+ * The state is the continuous function u(r, lambda, z) = sum A[zm, blk, node] phi_node(r) F_blk(lambda) C_zm(z); tileTransform!
+ * (src/semiimplicit.jl:241, 305) samples it at the tile's own gridpoints only.  sx_evaluate samples the A coefficients the handle
+ * holds now (the patch rows sx_tile_transform reads) anywhere in the tile:
+ *   points[n_points, n_coord] column-major, columns r[, lambda][, z] as sx_get_gridpoints returns them;
+ *   out[n_points, n_vars, n_derivs] column-major, slots as in `physical` (u, r, rr[, l, ll][, z, zz]).
+ * r within the tile's extent and z within [zmin, zmax], both ends included; lambda any finite real.  A NaN / Inf coordinate, an r or z
+ * out of range or a null pointer with n_points > 0 fail the call before anything is written to out.
+ * Azimuthal truncation: the inverse transform at ring ri sums the wavenumbers k <= kmax[ri] only.  SX_EVAL_RING_K: at radius r the
+ * kmax of the last patch ring whose radius is <= r (ring 1 below the first ring; piecewise constant in r, and the tile's own
+ * gridpoints give what sx_tile_transform + sx_get_physical give).  SX_EVAL_ALL_K: every wavenumber of the patch (smooth in r).
+ * Vertical: with a = CA b, CA the boundary-condition projection of the variable's (bcb, bct), the DCT-I series
+ * a0 + 2 sum a_k T_k(x) + a_{N-1} T_{N-1}(x) at x = (z - mid) / (-Lz / 2); z, zz from the coefficient-space derivative.
+ * Runs on the handle's stream and returns after the copy-out; reads A only: `physical`, var_np1, the tendency history, the B arrays
+ * and captured graphs stay as they are (a deferred diagnostic variable is brought up to date first, as for every reader of A). */
+enum { SX_EVAL_RING_K = 0, SX_EVAL_ALL_K = 1 };
+int sx_evaluate(sx_handle *h, const double *points, int64_t n_points, int32_t flags, double *out);
+/* The weights sx_evaluate applies at ONE point of the tile the descriptor selects, for variable var: node0 = 0-based patch row of the
+ * first of the 4 spline nodes, w_r = phi, phi', phi'' at them, kcap as above, w_z[s][zm] = row s (value, d/dz, d2/dz2) of the
+ * vertical operator at the point's z (RZ / RLZ grids; untouched otherwise).  Refuses what sx_evaluate refuses; any output pointer
+ * may be NULL.  Pure host helper (no handle, no device): the basis arithmetic is testable where there is no GPU. */
+int sx_eval_basis(const sx_grid_desc *grid, int32_t var /*1-based*/, const double *point /*[n_coord]*/, int32_t flags,
+                  int32_t *node0, double *w_r /*[3][4]*/, int32_t *kcap, double *w_z /*[3][b_zDim]*/);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

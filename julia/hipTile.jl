@@ -151,6 +151,19 @@ function splineTransform!(mtile::HipModelTile, sharedSpectral::SharedArray{Float
 end
 
 # master output path: patch.spectral .= get_val_from(w, :(mtile.patchSpectral)); tileTransform!(...)  (:289-290)
+# the state at arbitrary points of the tile (sx_evaluate): points[n, n_coord] with columns r[, lambda][, z] as getGridpoints returns
+# them -> values[n, n_vars, n_derivs], slots as in tile.physical; all_k = false cuts the azimuthal series as tileTransform! does on
+# the rings (kmax of the last ring at or below r), true sums every wavenumber of the patch
+function evaluateDevice(mtile::HipModelTile, points::Matrix{Float64}; all_k::Bool = false)
+    n = size(points, 1)
+    d = Ref{SxDims}()
+    sxcheck(ccall((:sx_get_dims, libsx), Cint, (Ptr{Cvoid}, Ref{SxDims}), mtile.handle, d))
+    out = zeros(Float64, n, d[].n_vars, d[].n_derivs)
+    sxcheck(ccall((:sx_evaluate, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Ptr{Float64}),
+                  mtile.handle, points, n, all_k ? 1 : 0, out))
+    return out
+end
+
 function patchSpectral(mtile::HipModelTile)
     sxcheck(ccall((:sx_get_patch_spectral_a, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}),
                   mtile.handle, mtile.patchSpectral))

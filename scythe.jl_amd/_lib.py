@@ -10,6 +10,7 @@ LIB_PATH = os.environ.get("SCYTHE_HIP_LIB") or os.path.join(_HERE, "libscythe_hi
 SX_ABI_VERSION = 2
 GEOM = {"R": 0, "RZ": 1, "RL": 2, "RLZ": 3}
 BC = {"R0": 0, "R1T0": 1, "R1T1": 2, "R1T2": 3, "R2T10": 4, "R2T20": 5, "R3": 6, "PERIODIC": 7}
+EVAL_RING_K, EVAL_ALL_K = 0, 1      # SX_EVAL_*
 PARAM_ORDER = ["g", "K", "Cd", "Hfree", "Hb", "f", "S1", "c_0", "Kh", "Um", "Vm", "Pxi_bar", "H"]
 
 P_I32 = C.POINTER(C.c_int32)
@@ -103,6 +104,8 @@ SYMBOLS = {
     "sx_timer_only": (C.c_int, [_H, C.c_char_p]),
     "sx_get_timers": (C.c_int, [_H, C.c_int32, C.POINTER(C.c_char_p), P_D, P_I64, P_I32]),
     "sx_kernel_bytes": (C.c_int, [_H, C.c_char_p, P_D]),
+    "sx_evaluate": (C.c_int, [_H, P_D, C.c_int64, C.c_int32, P_D]),
+    "sx_eval_basis": (C.c_int, [C.POINTER(GridDesc), C.c_int32, P_D, C.c_int32, P_I32, P_D, P_I32, P_D]),
 }
 
 _lib = None

@@ -86,6 +86,22 @@ bool build_helmholtz(const ChebOps &w, double pxi_bar, double tau, std::vector<d
                      std::string &err);
 void ring_table(int has_l, int uniform_L, int ri /*1-based patch ring*/, int &L, int &kmax, double &off);
 
+// ---- evaluation at arbitrary points (sx_setup.cpp: the weights; sx_eval.hip: sx_eval_basis, sx_evaluate and its kernel) ------
+struct EvalGeom {       // what the weights of one point depend on: from a descriptor (sx_eval_basis) or a handle (sx_evaluate)
+    int has_l = 0, has_z = 0, nc = 0, cell0 = 0, ncells = 0, uniform_L = 0, kDim = 0, nz = 1, Zb = 1;
+    double xmin = 0, xmax = 0, DX = 0, zmin = 0, zmax = 0;
+    double tile_lo() const { return cell0 == 0 ? xmin : xmin + cell0 * DX; }
+    double tile_hi() const { return cell0 + ncells == nc ? xmax : xmin + (cell0 + ncells) * DX; }
+};
+struct EvalVert {       // one vertical boundary-condition class
+    int bcb = 0, bct = 0;
+    std::vector<long double> W[3];   // [nz][Zb]  CA, Dc CA, Dc Dc CA
+};
+void eval_radial(const EvalGeom &g, double r, int &node0, double w[3][4]);
+int eval_kcap(const EvalGeom &g, double r, int flags);
+bool build_eval_vert(double zmin, double zmax, int nz, int Zb, int bcb, int bct, EvalVert &out, std::string &err);
+void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int Zb, double z, double *w /*[3][Zb]*/);
+
 // ---- device-side tables handed to the kernels -----------------------------------------------------------------------
 // `physical` [slot][v][N] and the node-space transforms G [slot][v][NG] as the kernels see them: the VALUE slot (slot 0)
 // is always fp64 - it is time-stepping state - while the derivative slots 1..D-1 are ST = double, or float in the
@@ -273,6 +289,7 @@ struct sx_handle {
     void *comm_state = nullptr;               // RCCL exchange state (sx_comm.cpp)
     void *iface_state = nullptr;              // interface-only patch solve (sx_iface.hip)
     void *pcr_state = nullptr;                // parallel-cyclic-reduction tables and launch lists (sx_pcr.hip)
+    void *eval_state = nullptr;               // sx_evaluate's vertical classes and device scratch, made on first use (sx_eval.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
     std::vector<int> hcls;                    // host copy of d_cls: [v][2] -> class of (k = 0, k >= 1)
@@ -342,6 +359,8 @@ void flush_diag(sx_handle *h);
 void graphs_release(sx_handle *h);
 void iface_release(sx_handle *h);
 void pcr_release(sx_handle *h);
+void eval_release(sx_handle *h);
+double eval_last_bytes(const sx_handle *h);   // A bytes the last sx_evaluate read
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);
 void launch_rz_forward(sx_handle *h);

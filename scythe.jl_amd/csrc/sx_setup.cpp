@@ -16,16 +16,17 @@ static const double GAUSS_OFF[MUBAR] = {-SQRT35 / 2.0, 0.0, SQRT35 / 2.0};
 static const double QUAD_W[MUBAR] = {8.0 / 21.0, 5.0 / 21.0, 8.0 / 21.0};
 
 // d-th derivative of the cardinal cubic B-spline with respect to its argument
-static double bspl(double delta, int d) {
-    double z = std::fabs(delta);
-    if (z >= 2.0) return 0.0;
-    double s = delta > 0 ? 1.0 : -1.0;
-    double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
+template <class T>
+static T bspl(T delta, int d) {
+    T z = std::fabs(delta);
+    if (z >= T(2.0)) return T(0.0);
+    T s = delta > 0 ? T(1.0) : T(-1.0);
+    T p = T(2.0) - z, q = z < T(1.0) ? T(1.0) - z : T(0.0);
     switch (d) {
-        case 0: return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
-        case 1: return -s * (p * p / 2.0 - 2.0 * q * q);
-        case 2: return p - 4.0 * q;
-        default: return s * (z < 1.0 ? 3.0 : -1.0);
+        case 0: return p * p * p / T(6.0) - T(4.0) * q * q * q / T(6.0);
+        case 1: return -s * (p * p / T(2.0) - T(2.0) * q * q);
+        case 2: return p - T(4.0) * q;
+        default: return s * (z < T(1.0) ? T(3.0) : T(-1.0));
     }
 }
 
@@ -34,7 +35,7 @@ void basis_tables(double DX, double phi[4][MUBAR][4]) {
     for (int d = 0; d < 4; d++) {
         double sc = 1.0 / std::pow(DX, d);
         for (int mu = 0; mu < MUBAR; mu++)
-            for (int j = 0; j < 4; j++) phi[d][mu][j] = bspl(1.5 + GAUSS_OFF[mu] - j, d) * sc;
+            for (int j = 0; j < 4; j++) phi[d][mu][j] = bspl<double>(1.5 + GAUSS_OFF[mu] - j, d) * sc;
     }
 }
 
@@ -436,40 +437,8 @@ static void cheb_factors(double zmin, double zmax, int N, ChebX &x) {
     matmul(x.TD, x.Dc, x.TDD, N, N, N);
 }
 
-bool build_cheb_ops(double zmin, double zmax, int nz, int Zb, int bcb, int bct, ChebOps &o, std::string &err) {
-    if (nz < 4) { err = "zDim must be >= 4"; return false; }
-    o.bcb = bcb;
-    o.bct = bct;
-    const int N = nz;
-    const xreal PI = 4.0L * atanl(1.0L);
-    const xreal Lz = (xreal)zmax - (xreal)zmin;
-    o.z.resize(N);
-    for (int n = 0; n < N; n++) o.z[n] = std::cos(n * M_PI / (N - 1)) * (-0.5 * (zmax - zmin)) + 0.5 * (zmin + zmax);
-    (void)PI;
-    ChebX x;
-    cheb_factors(zmin, zmax, N, x);
-    xmat CB((size_t)Zb * N);
-    for (int k = 0; k < Zb; k++)
-        for (int n = 0; n < N; n++) CB[(size_t)k * N + n] = x.T[(size_t)k * N + n] / (2.0L * (N - 1));
-    // coefficient-space integral, zero at the bottom (x = +1 where every T_k = 1)
-    xmat Ic((size_t)N * N, 0.0L);
-    std::vector<xreal> ai(N);
-    for (int j = 0; j < N; j++) {
-        std::fill(ai.begin(), ai.end(), 0.0L);
-        auto a = [&](int k) { return k == j ? 1.0L : 0.0L; };
-        for (int k = 1; k < N - 1; k++) {
-            xreal up = (k + 1 < N - 1) ? a(k + 1) : 0.5L * a(k + 1);
-            ai[k] = (a(k - 1) - up) / (2.0L * k);
-        }
-        ai[N - 1] = a(N - 2) / (xreal)(N - 1);
-        xreal s = 0.0L;
-        for (int k = 1; k < N; k++) {
-            ai[k] *= (-0.5L * Lz);
-            s += (k == N - 1 ? 1.0L : 2.0L) * ai[k];
-        }
-        ai[0] = -s;
-        for (int i = 0; i < N; i++) Ic[(size_t)i * N + j] = ai[i];
-    }
+// b -> a: padding to N coefficients and the projection onto the boundary conditions (bcb, bct), [N][Zb]
+static bool cheb_ca(const ChebX &x, int N, int Zb, int bcb, int bct, xmat &CA, std::string &err) {
     // BC projection (orthogonal projection onto the null space of the constraint rows)
     std::vector<std::vector<xreal>> rows;
     const int bcs[2] = {bcb, bct}, rix[2] = {0, N - 1};
@@ -506,9 +475,48 @@ bool build_cheb_ops(double zmin, double zmax, int nz, int Zb, int bcb, int bct, 
                 proj[(size_t)i * N + j] -= s;
             }
     }
-    xmat CA((size_t)N * Zb, 0.0L);
+    CA.assign((size_t)N * Zb, 0.0L);
     for (int i = 0; i < N; i++)
         for (int k = 0; k < Zb; k++) CA[(size_t)i * Zb + k] = proj[(size_t)i * N + k];
+    return true;
+}
+
+bool build_cheb_ops(double zmin, double zmax, int nz, int Zb, int bcb, int bct, ChebOps &o, std::string &err) {
+    if (nz < 4) { err = "zDim must be >= 4"; return false; }
+    o.bcb = bcb;
+    o.bct = bct;
+    const int N = nz;
+    const xreal PI = 4.0L * atanl(1.0L);
+    const xreal Lz = (xreal)zmax - (xreal)zmin;
+    o.z.resize(N);
+    for (int n = 0; n < N; n++) o.z[n] = std::cos(n * M_PI / (N - 1)) * (-0.5 * (zmax - zmin)) + 0.5 * (zmin + zmax);
+    (void)PI;
+    ChebX x;
+    cheb_factors(zmin, zmax, N, x);
+    xmat CB((size_t)Zb * N);
+    for (int k = 0; k < Zb; k++)
+        for (int n = 0; n < N; n++) CB[(size_t)k * N + n] = x.T[(size_t)k * N + n] / (2.0L * (N - 1));
+    // coefficient-space integral, zero at the bottom (x = +1 where every T_k = 1)
+    xmat Ic((size_t)N * N, 0.0L);
+    std::vector<xreal> ai(N);
+    for (int j = 0; j < N; j++) {
+        std::fill(ai.begin(), ai.end(), 0.0L);
+        auto a = [&](int k) { return k == j ? 1.0L : 0.0L; };
+        for (int k = 1; k < N - 1; k++) {
+            xreal up = (k + 1 < N - 1) ? a(k + 1) : 0.5L * a(k + 1);
+            ai[k] = (a(k - 1) - up) / (2.0L * k);
+        }
+        ai[N - 1] = a(N - 2) / (xreal)(N - 1);
+        xreal s = 0.0L;
+        for (int k = 1; k < N; k++) {
+            ai[k] *= (-0.5L * Lz);
+            s += (k == N - 1 ? 1.0L : 2.0L) * ai[k];
+        }
+        ai[0] = -s;
+        for (int i = 0; i < N; i++) Ic[(size_t)i * N + j] = ai[i];
+    }
+    xmat CA;
+    if (!cheb_ca(x, N, Zb, bcb, bct, CA, err)) return false;
     xmat M0, M1, M2, TI, TICA, Mint, Mdz, Mrec, Mdzz;
     matmul(x.T, CA, M0, N, N, Zb);
     matmul(x.TD, CA, M1, N, N, Zb);
@@ -569,6 +577,73 @@ bool build_helmholtz(const ChebOps &w, double pxi_bar, double tau, std::vector<d
     Wmat = to_double(W);
     Xmat = to_double(X);
     return true;
+}
+
+// ---------------------------------------------------------------------------------------------- evaluation at arbitrary points
+// The weights sx_evaluate's kernel applies and sx_eval_basis returns (sx_eval.hip), formed in extended precision from the Float64
+// coordinate and rounded once.
+
+// phi, phi', phi'' of the 4 nodes that overlap the cell of r (tile cells only: the tile's A rows are the ones the handle holds);
+// node0 = that cell = the patch row of the first node
+void eval_radial(const EvalGeom &g, double r, int &node0, double w[3][4]) {
+    int c = (int)std::floor((r - g.xmin) / g.DX);
+    c = std::min(std::max(c, g.cell0), g.cell0 + g.ncells - 1);
+    node0 = c;
+    const xreal DX = (xreal)g.DX;
+    for (int j = 0; j < 4; j++) {
+        const xreal delta = ((xreal)r - ((xreal)g.xmin + (xreal)(c - 1 + j) * DX)) / DX;
+        xreal sc = 1.0L;
+        for (int d = 0; d < 3; d++, sc *= DX) w[d][j] = (double)(bspl<xreal>(delta, d) / sc);
+    }
+}
+
+// SX_EVAL_RING_K: kmax of the last patch ring at or below r (ring 1 below the first); SX_EVAL_ALL_K: the patch's kDim
+int eval_kcap(const EvalGeom &g, double r, int flags) {
+    if (!g.has_l) return 0;
+    if (flags == SX_EVAL_ALL_K) return g.kDim;
+    const double t = (r - g.xmin) / g.DX;
+    const int c = std::min(std::max((int)std::floor(t), 0), g.nc - 1);
+    // a ring radius is printed as xmin + DX (c + 0.5 + offset): a few ulp of what went into t absorb its rounding on the way back
+    const double tol = 4.0 * 2.220446049250313e-16 * (std::fabs(t) + 1.0 + std::max(std::fabs(g.xmin), std::fabs(g.xmax)) / g.DX);
+    int cnt = 0;
+    for (int mu = 0; mu < MUBAR; mu++)
+        if (0.5 + gauss_offset(mu) <= t - c + tol) cnt++;
+    const int ring = std::max(MUBAR * c + cnt - 1, 0);
+    int L, kmax;
+    double off;
+    ring_table(1, g.uniform_L, ring + 1, L, kmax, off);
+    return kmax;
+}
+
+// CA, Dc CA, Dc Dc CA of a vertical boundary-condition class, [nz][Zb] each, kept in extended precision
+bool build_eval_vert(double zmin, double zmax, int nz, int Zb, int bcb, int bct, EvalVert &o, std::string &err) {
+    if (nz < 4) { err = "zDim must be >= 4"; return false; }
+    ChebX x;
+    cheb_factors(zmin, zmax, nz, x);
+    xmat CA, DCA, DDCA;
+    if (!cheb_ca(x, nz, Zb, bcb, bct, CA, err)) return false;
+    matmul(x.Dc, CA, DCA, nz, nz, Zb);
+    matmul(x.Dc, DCA, DDCA, nz, nz, Zb);
+    o.bcb = bcb; o.bct = bct;
+    o.W[0] = CA; o.W[1] = DCA; o.W[2] = DDCA;
+    return true;
+}
+
+// rows of the b -> (value, d/dz, d2/dz2) operator at z: the DCT-I series a0 + 2 sum a_k T_k(x) + a_{N-1} T_{N-1}(x) at
+// x = (z - mid) / (-Lz / 2) applied to a = CA b and to its coefficient-space derivatives; w [3][Zb]
+void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int Zb, double z, double *w) {
+    const xreal mid = ((xreal)zmin + (xreal)zmax) / 2.0L, half = ((xreal)zmax - (xreal)zmin) / 2.0L;
+    xreal x = ((xreal)z - mid) / (-half);
+    x = std::min(std::max(x, (xreal)-1.0L), (xreal)1.0L);
+    const xreal th = acosl(x);
+    std::vector<xreal> t(nz);
+    for (int n = 0; n < nz; n++) t[n] = ((n == 0 || n == nz - 1) ? 1.0L : 2.0L) * cosl((xreal)n * th);
+    for (int s = 0; s < 3; s++)
+        for (int k = 0; k < Zb; k++) {
+            xreal acc = 0.0L;
+            for (int n = 0; n < nz; n++) acc += t[n] * ev.W[s][(size_t)n * Zb + k];
+            w[(size_t)s * Zb + k] = (double)acc;
+        }
 }
 
 void ring_table(int has_l, int uniform_L, int ri, int &L, int &kmax, double &off) {

@@ -427,6 +427,28 @@ class ModelRun:
             out.append(g.physical)
         return np.concatenate(out, axis=0)
 
+    def evaluate(self, points, all_k=False):
+        """Grid.evaluate over the local tiles: every point goes to the local tile that contains its radius (a shared edge to the
+        lower tile).  Returns (values [n, V, D], held [n] bool): held marks the points this process holds; the rows of the others
+        are zero (write_output's convention: each process deals with its local tiles)."""
+        patch = self.patch
+        nco = len(patch.geometry)
+        p = np.asarray(points, dtype=np.float64)
+        p = p.reshape(-1, nco) if p.ndim != 2 else p
+        g0 = self.tiles[0]
+        out = np.zeros((p.shape[0], g0.V, g0.D), order="F")
+        held = np.zeros(p.shape[0], dtype=bool)
+        DX = (patch.xmax - patch.xmin) / patch.num_cells
+        for t, g in sorted(zip(self.tile_ids, self.tiles)):
+            c0, n = self.layout.cell0[t], self.layout.ncells[t]
+            lo = patch.xmin if c0 == 0 else patch.xmin + c0 * DX                      # the extent sx_evaluate accepts
+            hi = patch.xmax if c0 + n == patch.num_cells else patch.xmin + (c0 + n) * DX
+            sel = np.nonzero((p[:, 0] >= lo) & (p[:, 0] <= hi) & ~held)[0]
+            if len(sel):
+                out[sel] = g.evaluate(p[sel], all_k)
+                held[sel] = True
+        return out, held
+
     def patch_spectral(self):
         """mtile.patchSpectral as the master pulls it from a worker for output (src/semiimplicit.jl:288-293): the patch's A
         coefficients [s_patch, V].  With the reference's protocol every tile holds the whole patch; with the transposed solve a

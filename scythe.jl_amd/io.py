@@ -99,3 +99,22 @@ def write_output(run, model, time, derivatives=True, spectral=True):
         np.savetxt(os.path.join(model.output_dir, "spectral_out_%s.csv" % tag), np.concatenate([idx, a], axis=1), delimiter=",",
                    header=",".join(["i"] + names), comments="", fmt="%.17g")
     return path
+
+
+def write_gridded_output(run, model, time, points, names=None):
+    """The state at arbitrary points (ModelRun.evaluate), written as gridded_out_<tag>.csv beside physical_out_<tag>.csv: one row
+    per point this process holds, the coordinate columns r[, l][, z] and then <var>, <var>_r, ... as in physical_out.  names
+    restricts the variables (default: all)."""
+    gp = model.grid_params
+    allnames = gp.var_names()
+    names = allnames if names is None else list(names)
+    vi = [allnames.index(n) for n in names]
+    slots = _SLOTS[gp.geometry]
+    p = np.asarray(points, dtype=np.float64)
+    p = p.reshape(-1, len(_COORD[gp.geometry])) if p.ndim != 2 else p
+    vals, held = run.evaluate(p)
+    path = os.path.join(model.output_dir, "gridded_out_%s.csv" % output_time_tag(time))
+    arr = np.concatenate([p[held]] + [vals[held][:, vi, d] for d in range(len(slots))], axis=1)
+    header = _COORD[gp.geometry] + [n + _SUFFIX[s] for s in slots for n in names]
+    np.savetxt(path, arr, delimiter=",", header=",".join(header), comments="", fmt="%.17g")
+    return path

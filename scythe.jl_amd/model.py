@@ -321,6 +321,21 @@ class Grid:
         L.check(self._lib.sx_get_patch_spectral_a(self._h, out.ctypes.data_as(L.P_D)))
         return out
 
+    def evaluate(self, points, all_k=False):
+        """The spectral state (the A coefficients the tile holds now) at arbitrary points of the tile: points [n, n_coord] with
+        columns r[, lambda][, z] as getGridpoints returns them -> ndarray [n, V, D], slots as in `physical` (sx_evaluate).
+        all_k=False cuts the azimuthal series at the kmax of the last ring at or below each radius, as tileTransform! does on the
+        rings; all_k=True sums every wavenumber of the patch."""
+        nc = int(self.dims.n_coord)
+        p = np.asarray(points, dtype=np.float64)
+        p = np.asfortranarray(p.reshape(-1, nc) if p.ndim != 2 else p)
+        if p.shape[1] != nc:
+            raise ValueError("points must have %d coordinate column(s)" % nc)
+        out = np.zeros((p.shape[0], self.V, self.D), order="F")
+        L.check(self._lib.sx_evaluate(self._h, p.ctypes.data_as(L.P_D), p.shape[0], L.EVAL_ALL_K if all_k else L.EVAL_RING_K,
+                                      out.ctypes.data_as(L.P_D)))
+        return out
+
     # -- operators
     def spectralTransform_(self):
         L.check(self._lib.sx_spectral_transform(self._h))
@@ -492,6 +507,59 @@ def getGridpoints(grid: Grid):
     out = np.zeros((n, nc), order="F")
     L.check(grid._lib.sx_get_gridpoints(grid._h, out.ctypes.data_as(L.P_D)))
     return out[:, 0].copy() if nc == 1 else out
+
+
+def eval_basis(patch: GridParameters, var, point, all_k=False, tile_cell0=0, tile_num_cells=None):
+    """The weights sx_evaluate applies at one point, for variable `var` (name or 1-based index), on the host (sx_eval_basis):
+    (node0, w_r [3, 4], kcap, w_z [3, b_zDim] or None).  node0 is the 0-based patch row of the first of the 4 spline nodes."""
+    d, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    v = patch.vars[var] if isinstance(var, str) else int(var)
+    pt = np.ascontiguousarray(np.atleast_1d(point), dtype=np.float64)
+    if len(pt) != len(patch.geometry):
+        raise ValueError("point must have %d coordinate(s)" % len(patch.geometry))
+    node0, kcap = C.c_int32(-1), C.c_int32(-1)
+    w_r = np.zeros((3, 4))
+    w_z = np.zeros((3, patch.b_zDim)) if "Z" in patch.geometry else None
+    L.check(L.load().sx_eval_basis(C.byref(d), v, pt.ctypes.data_as(L.P_D), L.EVAL_ALL_K if all_k else L.EVAL_RING_K, C.byref(node0),
+                                   w_r.ctypes.data_as(L.P_D), C.byref(kcap), w_z.ctypes.data_as(L.P_D) if w_z is not None else None))
+    return node0.value, w_r, kcap.value, w_z
+
+
+def regular_gridpoints(gp: GridParameters, nr, nl=None, nz=None):
+    """An evenly spaced tensor grid in r[, lambda][, z], edges included (lambda: [0, 2 pi], both ends), as rows r[, lambda][, z] in
+    getGridpoints' order: r slowest, z fastest."""
+    axes = [np.linspace(gp.xmin, gp.xmax, int(nr))]
+    if "L" in gp.geometry:
+        if nl is None:
+            raise ValueError("nl is needed on an %s grid" % gp.geometry)
+        axes.append(np.linspace(0.0, 2.0 * np.pi, int(nl)))
+    if "Z" in gp.geometry:
+        if nz is None:
+            raise ValueError("nz is needed on an %s grid" % gp.geometry)
+        axes.append(np.linspace(gp.zmin, gp.zmax, int(nz)))
+    mesh = np.meshgrid(*axes, indexing="ij")
+    return np.stack([m.reshape(-1) for m in mesh], axis=1)
+
+
+def cartesian_gridpoints(gp: GridParameters, nx, ny, nz=None):
+    """x, y evenly spaced on [-xmax, xmax]^2 (x slowest; with nz, z levels on [zmin, zmax] fastest) mapped to (r, lambda); keeps the
+    points with xmin <= r <= xmax.  Returns (points [n_kept, n_coord], index [n_kept] of every kept point in the full nx * ny
+    [* nz] grid)."""
+    if "L" not in gp.geometry:
+        raise ValueError("a Cartesian grid needs an RL or RLZ geometry")
+    x = np.linspace(-gp.xmax, gp.xmax, int(nx))
+    y = np.linspace(-gp.xmax, gp.xmax, int(ny))
+    axes = [x, y]
+    if "Z" in gp.geometry:
+        if nz is None:
+            raise ValueError("nz is needed on an %s grid" % gp.geometry)
+        axes.append(np.linspace(gp.zmin, gp.zmax, int(nz)))
+    mesh = [m.reshape(-1) for m in np.meshgrid(*axes, indexing="ij")]
+    r = np.hypot(mesh[0], mesh[1])
+    lam = np.mod(np.arctan2(mesh[1], mesh[0]), 2.0 * np.pi)
+    keep = np.nonzero((r >= gp.xmin) & (r <= gp.xmax))[0]
+    cols = [r[keep], lam[keep]] + ([mesh[2][keep]] if len(mesh) == 3 else [])
+    return np.stack(cols, axis=1), keep
 
 
 def num_columns(grid: Grid):
