@@ -274,6 +274,48 @@ int sx_evaluate(sx_handle *h, const double *points, int64_t n_points, int32_t fl
 int sx_eval_basis(const sx_grid_desc *grid, int32_t var /*1-based*/, const double *point /*[n_coord]*/, int32_t flags,
                   int32_t *node0, double *w_r /*[3][4]*/, int32_t *kcap, double *w_z /*[3][b_zDim]*/);
 
+/* --- integrals and azimuthal means of field products ------------------------------------------------------------------
+ * On-device diagnostics: budgets and azimuthal means / eddy covariances without pulling `physical` to the host.
+ * Integrand program: n_terms <= 64 monomial terms feed n_out <= 16 outputs.  Term t is
+ *     coef[t] * r^p * prod_{f < nf} field(var_f, slot_f)        added to output out_t,
+ * nf = 0 .. 4 (nf = 0: the measure itself, area or volume), p an integer in [-2, 2], r the point's first coordinate (the double
+ * sx_get_gridpoints returns), var 1-based, slot an index into `physical`'s derivative slots of the geometry (u, r, rr[, l, ll][, z, zz]).
+ * Factor entries at f >= nf are ignored.  A program names at most 16 distinct (var, slot) planes; a sum that is no monomial (vorticity
+ * squared) is written out as several terms.
+ * Source.  SX_REDUCE_PHYSICAL: `physical` as it stands - defined only after sx_tile_transform, exactly as for sx_get_physical; with
+ * storage_f32 the derivative slots are read in the type they are stored in.  SX_REDUCE_STATE: var_np1, slot 0 only; it is complete
+ * after every sx_advance / sx_set_physical_values (what sx_check_nan relies on), so this source costs no transform.
+ * Kind.  SX_REDUCE_AZIMUTH: out[tile ring, level, n_out] column-major, the ring fastest = (1 / L_ring) sum_lambda integrand, the
+ * azimuthal mean at every ring and level (R / RZ grids: L = 1, the pointwise value).  SX_REDUCE_DOMAIN: out[n_out] =
+ * sum_points w_r[ring] w_l[ring] w_z[level] integrand, this tile's share of the domain integral (tiles own disjoint cells: a patch
+ * integral is the sum of the tile results), with
+ *     w_r = DX (5, 8, 5) / 18 * J(r)   3-point Gauss-Legendre on each cell, whose nodes the radial gridpoints are (exact to degree 5
+ *                                      per cell; NOT the 8:5:8 projection weights of the transforms), J = r on RL / RLZ, 1 on R / RZ
+ *     w_l = 2 pi / L_ring              1 without an azimuth
+ *     w_z = Clenshaw-Curtis weights of the zDim Chebyshev-Gauss-Lobatto levels times (zmax - zmin) / 2 (exact to degree zDim - 1),
+ *                                      1 without a vertical
+ * formed on the host in extended precision and rounded once.
+ * Refused, with a message and before anything is written to out: a null pointer with a non-zero count; n_terms > 64, n_out > 16, more
+ * than 16 planes; var, slot, out, p or n_factors out of range; a slot other than 0 with SX_REDUCE_STATE; p < 0 on a tile with a
+ * gridpoint at r == 0.
+ * Sums are accumulated in double-double, each by a fixed lane in a fixed order that depends on the grid and the program alone (no
+ * floating-point atomics): two calls on the same data agree bitwise, and the rounding error does not grow with the point count.
+ * sx_reduce runs on the handle's stream and returns after the copy-out; it reads only: `physical`, var_np1, the tendency history, A, B
+ * and captured graphs stay as they are, and it does not run the tile transform itself. */
+enum { SX_REDUCE_DOMAIN = 0, SX_REDUCE_AZIMUTH = 1 };
+enum { SX_REDUCE_PHYSICAL = 0, SX_REDUCE_STATE = 1 };
+/* terms[n_terms][11] = out, r_power, n_factors, var[4], slot[4] */
+int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const double *coef,
+              const int32_t *terms, int32_t n_out, double *out);
+/* pure host helpers, no handle and no device (the pattern of sx_eval_basis) */
+/* the weights above for the tile the descriptor selects; any output pointer may be NULL, w_z is untouched without a vertical */
+int sx_reduce_weights(const sx_grid_desc *grid, double *w_r /*[3 tile_num_cells]*/,
+                      double *w_l /*[3 tile_num_cells]*/, double *w_z /*[zDim]*/);
+/* the validator sx_reduce itself calls: refuses what sx_reduce refuses of a program, and returns the distinct (var, slot) planes it
+ * names in first-use order (n_factors = 0 names none); planes / n_planes may be NULL and are written on success only */
+int sx_reduce_planes(const sx_grid_desc *grid, int32_t source, int32_t n_terms, const int32_t *terms,
+                     int32_t n_out, int32_t *planes /*[16][2]*/, int32_t *n_planes);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

@@ -101,6 +101,8 @@ void eval_radial(const EvalGeom &g, double r, int &node0, double w[3][4]);
 int eval_kcap(const EvalGeom &g, double r, int flags);
 bool build_eval_vert(double zmin, double zmax, int nz, int Zb, int bcb, int bct, EvalVert &out, std::string &err);
 void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int Zb, double z, double *w /*[3][Zb]*/);
+// quadrature weights of sx_reduce's domain integral (sx_setup.cpp); reads the geometry fields of g only (not kDim, Zb)
+void reduce_weights(const EvalGeom &g, double *w_r /*[3 ncells]*/, double *w_l /*[3 ncells]*/, double *w_z /*[nz]*/);
 
 // ---- device-side tables handed to the kernels -----------------------------------------------------------------------
 // `physical` [slot][v][N] and the node-space transforms G [slot][v][NG] as the kernels see them: the VALUE slot (slot 0)
@@ -290,6 +292,7 @@ struct sx_handle {
     void *iface_state = nullptr;              // interface-only patch solve (sx_iface.hip)
     void *pcr_state = nullptr;                // parallel-cyclic-reduction tables and launch lists (sx_pcr.hip)
     void *eval_state = nullptr;               // sx_evaluate's vertical classes and device scratch, made on first use (sx_eval.hip)
+    void *reduce_state = nullptr;             // sx_reduce's work list, weights and ring-sum scratch, made on first use (sx_reduce.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
     std::vector<int> hcls;                    // host copy of d_cls: [v][2] -> class of (k = 0, k >= 1)
@@ -361,6 +364,8 @@ void iface_release(sx_handle *h);
 void pcr_release(sx_handle *h);
 void eval_release(sx_handle *h);
 double eval_last_bytes(const sx_handle *h);   // A bytes the last sx_evaluate read
+void reduce_release(sx_handle *h);
+double reduce_last_bytes(const sx_handle *h);   // plane bytes the last sx_reduce read
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);
 void launch_rz_forward(sx_handle *h);

@@ -1,0 +1,414 @@
+// sx_reduce / sx_reduce_weights / sx_reduce_planes: integrals and azimuthal means of field products (include/scythe_hip.h).
+//
+// Two stages.  k_reduce forms the azimuthal sums S[ring][level][output] = sum_lambda integrand: a workgroup takes one piece of one ring
+// (a run of lambdas, all levels), its threads take consecutive points - z innermost, so a thread keeps ONE level and strides over the
+// lambdas - read every plane the program names once, evaluate all terms from registers and add them to one double-double accumulator
+// per output; the workgroup then adds, per level and in lambda order, the accumulators of the threads that share the level.  Grids
+// without an azimuth (L = 1) have nothing to sum: there a workgroup takes 256 consecutive points and writes their integrands.
+// k_reduce_final adds the pieces of a ring in order and divides by L (SX_REDUCE_AZIMUTH), or forms the weighted sum over rings and
+// levels (SX_REDUCE_DOMAIN: a fixed number of workgroups per output, fixed strides, a fixed tree, then the workgroups' sums in order).  Nothing is added atomically: which lane adds
+// what, and in which order, follows from the grid and the program alone, so two calls on the same data agree bitwise; and every sum is
+// double-double, so the rounding error is that of the terms and does not grow with the point count.
+//
+// The program is a kernel ARGUMENT (constant memory, scalar loads: its indices are uniform), terms sorted by output so that the
+// accumulators are indexed statically.
+#include "sx_internal.hpp"
+#include <algorithm>
+#include <cstring>
+
+namespace sx {
+
+constexpr int RED_T = 256;          // threads per workgroup of k_reduce
+constexpr int RED_TF = 1024;        // threads per workgroup of k_reduce_final's domain sum
+constexpr int RED_ITERS = 32;       // strides of a workgroup over its piece of a ring: pieces per ring = ceil(strides / RED_ITERS)
+constexpr int RED_TERMS = 64, RED_OUT = 16, RED_PLANES = 16, RED_FACTORS = 4, RED_TERM_W = 11;
+
+struct RedProg {
+    double coef[RED_TERMS];
+    int8_t p[RED_TERMS], nf[RED_TERMS];
+    uint8_t f[RED_TERMS][RED_FACTORS];      // plane of each factor
+    uint8_t start[RED_OUT + 1];             // terms of output o: [start[o], start[o + 1])
+    uint8_t pvar[RED_PLANES], pslot[RED_PLANES];   // 0-based variable, slot
+    int n_planes, n_out;
+};
+
+struct RedItem { int ring, lam0, nlam, pad; };
+
+struct ReduceState {
+    RedItem *d_items = nullptr;     // ring pieces (grids with an azimuth) or whole rings
+    int *d_first = nullptr;         // [nrings + 1] first piece of each ring
+    double *d_wrl = nullptr, *d_wz = nullptr;   // w_r w_l per ring, w_z per level
+    double2 *d_part = nullptr;      // [piece][output][level] (hi, lo)
+    double2 *d_part2 = nullptr;     // [RED_OUT][blocks2] sums of the domain kind's first level
+    int blocks2 = 1;                // workgroups per output of k_reduce_domain: 4 (piece, level) entries per thread, at most 64
+    double *d_out = nullptr;
+    size_t cap_part = 0, cap_out = 0;
+    int n_items = 0;
+    double last_bytes = 0;
+};
+
+// (hi, lo) += x, the rounding error of the sum kept in lo (Knuth's two-sum: no ordering of |hi|, |x| assumed)
+__device__ inline void dd_add(double &hi, double &lo, double x) {
+    const double s = hi + x, b = s - hi;
+    lo += (hi - (s - b)) + (x - b);
+    hi = s;
+}
+__device__ inline void dd_add(double &hi, double &lo, double xh, double xl) {
+    dd_add(hi, lo, xh);
+    lo += xl;
+}
+
+// One point: load the planes, evaluate the terms.  pt < N is the caller's business.
+template <class ST>
+__device__ inline void reduce_point(const Planes<ST> &P, int V, int64_t N, int64_t pt, double r, const RedProg &g, double (&hi)[RED_OUT],
+                                    double (&lo)[RED_OUT]) {
+    double val[RED_PLANES];
+#pragma unroll
+    for (int j = 0; j < RED_PLANES; j++) {
+        val[j] = 0.0;
+        if (j < g.n_planes) {
+            const int v = g.pvar[j], s = g.pslot[j];
+            val[j] = s == 0 ? P.val[(int64_t)v * N + pt] : (double)P.der[((int64_t)(s - 1) * V + v) * N + pt];
+        }
+    }
+    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
+#pragma unroll
+    for (int o = 0; o < RED_OUT; o++) {
+        for (int t = g.start[o]; t < g.start[o + 1]; t++) {       // empty at o >= n_out
+            const int p = g.p[t], nf = g.nf[t];
+            double x = g.coef[t];
+            if (p != 0) x *= p == 1 ? r : p == 2 ? rr : p == -1 ? ri : rri;
+#pragma unroll
+            for (int f = 0; f < RED_FACTORS; f++)
+                if (f < nf) x *= val[g.f[t][f]];
+            dd_add(hi[o], lo[o], x);
+        }
+    }
+}
+
+// RINGS: grid = pieces; a thread's level is tid % nz, its first lambda lam0 + tid / nz, its stride RED_T / nz lambdas.
+// !RINGS (every ring has one lambda): grid = ceil(N / RED_T); thread = point; piece = ring.   part [piece][output][level]
+template <class ST, bool RINGS>
+__global__ __launch_bounds__(RED_T) void k_reduce(Planes<ST> P, int V, int64_t N, int nz, const RedItem *__restrict__ items,
+                                                  const int64_t *__restrict__ pstart, const double *__restrict__ rh, RedProg g,
+                                                  double2 *__restrict__ part) {
+    __shared__ double s_hi[RED_T], s_lo[RED_T];
+    const int tid = threadIdx.x;
+    double hi[RED_OUT], lo[RED_OUT];
+#pragma unroll
+    for (int o = 0; o < RED_OUT; o++) hi[o] = lo[o] = 0.0;
+    if (RINGS) {
+        const RedItem it = items[blockIdx.x];
+        const int G = RED_T / nz, z = tid % nz, gl = tid / nz;
+        const int64_t h0 = pstart[it.ring];
+        const double r = rh[h0];
+        if (gl < G)
+            for (int l = it.lam0 + gl; l < it.lam0 + it.nlam; l += G) reduce_point<ST>(P, V, N, (h0 + l) * nz + z, r, g, hi, lo);
+#pragma unroll
+        for (int o = 0; o < RED_OUT; o++) {
+            if (o >= g.n_out) continue;
+            s_hi[tid] = hi[o]; s_lo[tid] = lo[o];
+            __syncthreads();
+            if (tid < nz) {
+                double a = s_hi[tid], b = s_lo[tid];
+                for (int k = 1; k < G; k++) dd_add(a, b, s_hi[k * nz + tid], s_lo[k * nz + tid]);
+                part[((int64_t)blockIdx.x * g.n_out + o) * nz + tid] = make_double2(a, b);
+            }
+            __syncthreads();
+        }
+    } else {
+        const int64_t pt = (int64_t)blockIdx.x * RED_T + tid;
+        if (pt >= N) return;
+        const int64_t ring = pt / nz;
+        const int z = (int)(pt - ring * nz);
+        reduce_point<ST>(P, V, N, pt, rh[ring], g, hi, lo);
+#pragma unroll
+        for (int o = 0; o < RED_OUT; o++) {
+            if (o < g.n_out) part[((int64_t)ring * g.n_out + o) * nz + z] = make_double2(hi[o], lo[o]);
+        }
+    }
+}
+
+// SX_REDUCE_AZIMUTH: thread = (ring, level, output), the ring fastest as in out; the ring's pieces in order, then / L
+__global__ void k_reduce_mean(const double2 *__restrict__ part, const int *__restrict__ first, const int *__restrict__ L, int nrings, int nz,
+                              int n_out, double *__restrict__ out) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)nrings * nz * n_out) return;
+    const int ring = (int)(e % nrings), z = (int)(e / nrings % nz), o = (int)(e / nrings / nz);
+    double a = 0.0, b = 0.0;
+    for (int i = first[ring]; i < first[ring + 1]; i++) {
+        const double2 x = part[((int64_t)i * n_out + o) * nz + z];
+        dd_add(a, b, x.x, x.y);
+    }
+    out[e] = (a + b) / (double)L[ring];
+}
+
+// SX_REDUCE_DOMAIN, two levels.  k_reduce_domain: grid (n_out, blocks); the (piece, level) entries are dealt to the blocks x RED_TF
+// threads of an output in order (thread g takes entries g, g + blocks RED_TF, ...), each ring sum is weighted without a rounding error
+// of the product (fma), and a workgroup adds its RED_TF double-double sums in a fixed tree -> part2[output][block].
+// k_reduce_domain_sum: thread = output, the blocks in order.  The block count follows from the grid alone (reduce_state).
+__global__ __launch_bounds__(RED_TF) void k_reduce_domain(const double2 *__restrict__ part, const RedItem *__restrict__ items,
+                                                          const double *__restrict__ wrl, const double *__restrict__ wz, int n_items, int nz,
+                                                          int n_out, double2 *__restrict__ part2) {
+    __shared__ double s_hi[RED_TF], s_lo[RED_TF];
+    const int tid = threadIdx.x, o = blockIdx.x;
+    double a = 0.0, b = 0.0;
+    for (int64_t e = (int64_t)blockIdx.y * RED_TF + tid; e < (int64_t)n_items * nz; e += (int64_t)gridDim.y * RED_TF) {
+        const int i = (int)(e / nz), z = (int)(e - (int64_t)i * nz);
+        const double2 x = part[((int64_t)i * n_out + o) * nz + z];
+        const double w = wrl[items[i].ring] * wz[z];
+        const double ph = w * x.x, pl = fma(w, x.x, -ph) + w * x.y;
+        dd_add(a, b, ph, pl);
+    }
+    s_hi[tid] = a; s_lo[tid] = b;
+    __syncthreads();
+    for (int s = RED_TF / 2; s >= 1; s >>= 1) {
+        if (tid < s) {
+            dd_add(a, b, s_hi[tid + s], s_lo[tid + s]);
+            s_hi[tid] = a; s_lo[tid] = b;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) part2[(int64_t)o * gridDim.y + blockIdx.y] = make_double2(a, b);
+}
+
+__global__ void k_reduce_domain_sum(const double2 *__restrict__ part2, int blocks, int n_out, double *__restrict__ out) {
+    const int o = blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= n_out) return;
+    double a = 0.0, b = 0.0;
+    for (int k = 0; k < blocks; k++) dd_add(a, b, part2[(int64_t)o * blocks + k].x, part2[(int64_t)o * blocks + k].y);
+    out[o] = a + b;
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------
+void reduce_release(sx_handle *h) {
+    ReduceState *st = (ReduceState *)h->reduce_state;
+    if (!st) return;
+    hipFree(st->d_items); hipFree(st->d_first); hipFree(st->d_wrl); hipFree(st->d_wz); hipFree(st->d_part); hipFree(st->d_part2); hipFree(st->d_out);
+    delete st;
+    h->reduce_state = nullptr;
+}
+
+double reduce_last_bytes(const sx_handle *h) { return h->reduce_state ? ((const ReduceState *)h->reduce_state)->last_bytes : 0.0; }
+
+template <class T>
+static bool to_device(T **p, const std::vector<T> &v) {
+    if (hipMalloc((void **)p, sizeof(T) * std::max<size_t>(v.size(), 1)) != hipSuccess ||
+        (!v.empty() && hipMemcpy(*p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("sx_reduce: hipMalloc / hipMemcpy of the work list failed");
+        return false;
+    }
+    return true;
+}
+
+template <class T>
+static bool grow(T **p, size_t &cap, size_t need) {
+    if (need <= cap) return true;
+    if (*p) hipFree(*p);
+    *p = nullptr; cap = 0;
+    const size_t n = need + need / 4;
+    if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) { set_error("sx_reduce: hipMalloc of the scratch failed"); return false; }
+    cap = n;
+    return true;
+}
+
+static EvalGeom reduce_geom(const sx_handle *h) {
+    EvalGeom g;
+    g.has_l = h->has_l; g.has_z = h->has_z; g.nc = h->nc; g.cell0 = h->cell0; g.ncells = h->ncells; g.uniform_L = h->uniform_L;
+    g.nz = h->nz; g.xmin = h->xmin; g.xmax = h->xmax; g.DX = h->DX; g.zmin = h->zmin; g.zmax = h->zmax;
+    return g;
+}
+
+// the work list and the weights: functions of the grid alone, made once per handle
+static ReduceState *reduce_state(sx_handle *h) {
+    if (h->reduce_state) return (ReduceState *)h->reduce_state;
+    ReduceState *st = new ReduceState();
+    std::vector<RedItem> items;
+    std::vector<int> first(h->nrings + 1, 0);
+    const int G = RED_T / h->nz;         // lambdas per stride (nz <= 256: sx_create)
+    for (int i = 0; i < h->nrings; i++) {
+        first[i] = (int)items.size();
+        const int L = h->hL[i];
+        const int strides = (L + G - 1) / G, pieces = h->has_l ? (strides + RED_ITERS - 1) / RED_ITERS : 1;
+        for (int c = 0; c < pieces; c++) {
+            const int l0 = (int)((int64_t)L * c / pieces), l1 = (int)((int64_t)L * (c + 1) / pieces);
+            items.push_back(RedItem{i, l0, l1 - l0, 0});
+        }
+    }
+    first[h->nrings] = (int)items.size();
+    std::vector<double> wr(h->nrings), wl(h->nrings), wz(h->nz, 1.0), wrl(h->nrings);
+    reduce_weights(reduce_geom(h), wr.data(), wl.data(), wz.data());
+    for (int i = 0; i < h->nrings; i++) wrl[i] = wr[i] * wl[i];
+    st->n_items = (int)items.size();
+    st->blocks2 = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)items.size() * h->nz + 4 * RED_TF - 1) / (4 * RED_TF)));
+    h->reduce_state = st;
+    if (!to_device(&st->d_items, items) || !to_device(&st->d_first, first) || !to_device(&st->d_wrl, wrl) || !to_device(&st->d_wz, wz) ||
+        !to_device(&st->d_part2, std::vector<double2>((size_t)RED_OUT * st->blocks2))) {
+        reduce_release(h);
+        return nullptr;
+    }
+    return st;
+}
+
+static bool desc_ok(const sx_grid_desc *gd, const char *who) {
+    if (!gd) { set_error(std::string(who) + ": null argument"); return false; }
+    if (gd->abi_version != SX_ABI_VERSION) { set_error("sx_grid_desc.abi_version mismatch"); return false; }
+    if (gd->geometry < SX_GEOM_R || gd->geometry > SX_GEOM_RLZ) { set_error("Unknown geometry"); return false; }
+    if (gd->num_cells < 3 || gd->nvars < 1 || !(gd->xmax > gd->xmin)) { set_error("invalid grid parameters"); return false; }
+    if (gd->tile_cell0 < 0 || gd->tile_num_cells < 1 || gd->tile_cell0 + gd->tile_num_cells > gd->num_cells) { set_error("tile range outside the patch"); return false; }
+    return true;
+}
+
+static EvalGeom desc_geom(const sx_grid_desc *gd) {
+    EvalGeom g;
+    g.has_l = gd->geometry == SX_GEOM_RL || gd->geometry == SX_GEOM_RLZ;
+    g.has_z = gd->geometry == SX_GEOM_RZ || gd->geometry == SX_GEOM_RLZ;
+    g.nc = gd->num_cells; g.cell0 = gd->tile_cell0; g.ncells = gd->tile_num_cells;
+    g.uniform_L = g.has_l ? gd->ring_uniform_L : 0;
+    g.xmin = gd->xmin; g.xmax = gd->xmax; g.DX = (gd->xmax - gd->xmin) / gd->num_cells;
+    g.nz = g.has_z ? gd->zDim : 1; g.zmin = gd->zmin; g.zmax = gd->zmax;
+    return g;
+}
+
+template <class ST, bool RINGS>
+static void launch_stage1(sx_handle *h, ReduceState *st, const double *base, unsigned blocks, const RedProg &prog) {
+    hipLaunchKernelGGL((k_reduce<ST, RINGS>), dim3(blocks), dim3(RED_T), 0, h->stream, planes_of<ST>(const_cast<double *>(base), h->V, h->N), h->V,
+                       h->N, h->nz, st->d_items, h->d_pstart, h->d_r, prog, st->d_part);
+}
+
+}  // namespace sx
+
+using namespace sx;
+
+extern "C" {
+
+int sx_reduce_weights(const sx_grid_desc *gd, double *w_r, double *w_l, double *w_z) {
+    clear_error();
+    if (!desc_ok(gd, "sx_reduce_weights")) return 1;
+    const EvalGeom g = desc_geom(gd);
+    if (g.has_z && (g.nz < 4 || !(g.zmax > g.zmin))) { set_error("invalid vertical grid (need zDim >= 4, zmax > zmin)"); return 1; }
+    reduce_weights(g, w_r, w_l, w_z);
+    return 0;
+}
+
+int sx_reduce_planes(const sx_grid_desc *gd, int32_t source, int32_t n_terms, const int32_t *terms, int32_t n_out, int32_t *planes,
+                     int32_t *n_planes) {
+    clear_error();
+    if (!desc_ok(gd, "sx_reduce_planes")) return 1;
+    if (source != SX_REDUCE_PHYSICAL && source != SX_REDUCE_STATE) { set_error("sx_reduce: source must be SX_REDUCE_PHYSICAL or SX_REDUCE_STATE"); return 1; }
+    if (n_terms < 0 || n_terms > RED_TERMS) { set_error("sx_reduce: n_terms must be 0 .. 64"); return 1; }
+    if (n_out < 0 || n_out > RED_OUT) { set_error("sx_reduce: n_out must be 0 .. 16"); return 1; }
+    if (n_terms > 0 && !terms) { set_error("sx_reduce: null terms with n_terms > 0"); return 1; }
+    const int D = gd->geometry == SX_GEOM_R ? 3 : gd->geometry == SX_GEOM_RLZ ? 7 : 5;
+    int32_t found[RED_PLANES][2];
+    int nfound = 0;
+    bool neg_p = false;
+    for (int t = 0; t < n_terms; t++) {
+        const int32_t *q = terms + (size_t)t * RED_TERM_W;
+        const std::string at = "sx_reduce: term " + std::to_string(t) + ": ";
+        if (q[0] < 0 || q[0] >= n_out) { set_error(at + "out = " + std::to_string(q[0]) + " is not in [0, n_out)"); return 1; }
+        if (q[1] < -2 || q[1] > 2) { set_error(at + "r_power = " + std::to_string(q[1]) + " is not in [-2, 2]"); return 1; }
+        if (q[2] < 0 || q[2] > RED_FACTORS) { set_error(at + "n_factors = " + std::to_string(q[2]) + " is not in [0, 4]"); return 1; }
+        neg_p = neg_p || q[1] < 0;
+        for (int f = 0; f < q[2]; f++) {
+            const int32_t var = q[3 + f], slot = q[3 + RED_FACTORS + f];
+            if (var < 1 || var > gd->nvars) { set_error(at + "var = " + std::to_string(var) + " is 1-based and at most nvars"); return 1; }
+            if (slot < 0 || slot >= D) { set_error(at + "slot = " + std::to_string(slot) + " is not a derivative slot of the geometry"); return 1; }
+            if (source == SX_REDUCE_STATE && slot != 0) { set_error(at + "SX_REDUCE_STATE holds the values only (slot 0)"); return 1; }
+            int j = 0;
+            while (j < nfound && (found[j][0] != var || found[j][1] != slot)) j++;
+            if (j == nfound) {
+                if (nfound == RED_PLANES) { set_error("sx_reduce: the program names more than 16 distinct (var, slot) planes"); return 1; }
+                found[nfound][0] = var; found[nfound][1] = slot;
+                nfound++;
+            }
+        }
+    }
+    if (neg_p) {
+        const double DX = (gd->xmax - gd->xmin) / gd->num_cells;
+        for (int i = 0; i < MUBAR * gd->tile_num_cells; i++)
+            if (gd->xmin + DX * (gd->tile_cell0 + i / MUBAR + 0.5 + gauss_offset(i % MUBAR)) == 0.0) {
+                set_error("sx_reduce: a negative r_power on a tile with a gridpoint at r == 0");
+                return 1;
+            }
+    }
+    if (planes) std::memcpy(planes, found, sizeof(int32_t) * 2 * nfound);
+    if (n_planes) *n_planes = nfound;
+    return 0;
+}
+
+int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out,
+              double *out) {
+    clear_error();
+    if (!h) { set_error("null handle"); return 1; }
+    if (kind != SX_REDUCE_DOMAIN && kind != SX_REDUCE_AZIMUTH) { set_error("sx_reduce: kind must be SX_REDUCE_DOMAIN or SX_REDUCE_AZIMUTH"); return 1; }
+    sx_grid_desc gd = {};
+    gd.abi_version = SX_ABI_VERSION; gd.geometry = h->geom; gd.xmin = h->xmin; gd.xmax = h->xmax; gd.num_cells = h->nc; gd.nvars = h->V;
+    gd.tile_cell0 = h->cell0; gd.tile_num_cells = h->ncells;
+    int32_t planes[RED_PLANES][2], n_planes = 0;
+    if (sx_reduce_planes(&gd, source, n_terms, terms, n_out, &planes[0][0], &n_planes)) return 1;
+    if (n_terms > 0 && !coef) { set_error("sx_reduce: null coef with n_terms > 0"); return 1; }
+    if (n_out > 0 && !out) { set_error("sx_reduce: null out with n_out > 0"); return 1; }
+    if (n_out == 0) return 0;
+    ReduceState *st = reduce_state(h);
+    if (!st) return 1;
+
+    // the program as the kernel reads it: terms by output (their order within an output kept), factors as plane numbers
+    RedProg prog;
+    std::memset(&prog, 0, sizeof(prog));
+    prog.n_planes = n_planes; prog.n_out = n_out;
+    for (int j = 0; j < n_planes; j++) { prog.pvar[j] = (uint8_t)(planes[j][0] - 1); prog.pslot[j] = (uint8_t)planes[j][1]; }
+    int k = 0;
+    for (int o = 0; o < n_out; o++) {
+        prog.start[o] = (uint8_t)k;
+        for (int t = 0; t < n_terms; t++) {
+            const int32_t *q = terms + (size_t)t * RED_TERM_W;
+            if (q[0] != o) continue;
+            prog.coef[k] = coef[t]; prog.p[k] = (int8_t)q[1]; prog.nf[k] = (int8_t)q[2];
+            for (int f = 0; f < q[2]; f++) {
+                int j = 0;
+                while (planes[j][0] != q[3 + f] || planes[j][1] != q[3 + RED_FACTORS + f]) j++;
+                prog.f[k][f] = (uint8_t)j;
+            }
+            k++;
+        }
+    }
+    for (int o = n_out; o <= RED_OUT; o++) prog.start[o] = (uint8_t)k;
+
+    const size_t n_res = kind == SX_REDUCE_AZIMUTH ? (size_t)h->nrings * h->nz * n_out : (size_t)n_out;
+    if (!grow(&st->d_part, st->cap_part, (size_t)st->n_items * n_out * h->nz) || !grow(&st->d_out, st->cap_out, n_res)) return 1;
+    st->last_bytes = 0;
+    for (int j = 0; j < n_planes; j++) st->last_bytes += (double)h->N * (source == SX_REDUCE_PHYSICAL && h->f32 && planes[j][1] > 0 ? 4.0 : 8.0);
+
+    timer_begin(h, timer_id(h, "k_reduce"));
+    const unsigned flat_blocks = (unsigned)((h->N + RED_T - 1) / RED_T);
+    if (source == SX_REDUCE_STATE || !h->f32) {
+        const double *base = source == SX_REDUCE_STATE ? h->d_np1 : h->d_phys;
+        if (h->has_l) launch_stage1<double, true>(h, st, base, (unsigned)st->n_items, prog);
+        else launch_stage1<double, false>(h, st, base, flat_blocks, prog);
+    } else {
+        if (h->has_l) launch_stage1<float, true>(h, st, h->d_phys, (unsigned)st->n_items, prog);
+        else launch_stage1<float, false>(h, st, h->d_phys, flat_blocks, prog);
+    }
+    HIPCHK(hipGetLastError());
+    timer_end(h);
+    timer_begin(h, timer_id(h, "k_reduce_final"));
+    if (kind == SX_REDUCE_AZIMUTH)
+        hipLaunchKernelGGL(k_reduce_mean, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_part, st->d_first, h->d_L, h->nrings, h->nz,
+                           n_out, st->d_out);
+    else {
+        hipLaunchKernelGGL(k_reduce_domain, dim3((unsigned)n_out, (unsigned)st->blocks2), dim3(RED_TF), 0, h->stream, st->d_part, st->d_items,
+                           st->d_wrl, st->d_wz, st->n_items, h->nz, n_out, st->d_part2);
+        hipLaunchKernelGGL(k_reduce_domain_sum, dim3(1), dim3(64), 0, h->stream, st->d_part2, st->blocks2, n_out, st->d_out);
+    }
+    HIPCHK(hipGetLastError());
+    timer_end(h);
+    std::vector<double> res(n_res);      // held back until the call has succeeded: a failed call writes nothing to out
+    HIPCHK(hipMemcpyAsync(res.data(), st->d_out, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (error_status()) return 1;
+    std::memcpy(out, res.data(), sizeof(double) * n_res);
+    return 0;
+}
+
+}  // extern "C"

@@ -646,6 +646,35 @@ void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int
         }
 }
 
+// ---------------------------------------------------------------------------------------------- quadrature weights of sx_reduce
+// The weights of the domain integral (include/scythe_hip.h, "integrals and azimuthal means"), formed in extended precision and
+// rounded once; any output pointer may be null.  w_r[ring] = DX (5, 8, 5) / 18 J(r): 3-point Gauss-Legendre on the cell, whose nodes
+// the tile's radial gridpoints are (NOT quad_weights' 8:5:8 projection weights, which do not integrate x^2), J = r - the double
+// sx_get_gridpoints returns - with an azimuth and 1 without.  w_l[ring] = 2 pi / L, 1 without an azimuth.  w_z[level] =
+// Clenshaw-Curtis weights of the nz Chebyshev-Gauss-Lobatto levels times (zmax - zmin) / 2 (symmetric: bottom-first and top-first agree).
+void reduce_weights(const EvalGeom &g, double *w_r, double *w_l, double *w_z) {
+    const xreal DX = ((xreal)g.xmax - (xreal)g.xmin) / (xreal)g.nc, PI = acosl(-1.0L);
+    for (int i = 0; i < MUBAR * g.ncells; i++) {
+        const int mu = i % MUBAR, c = g.cell0 + i / MUBAR;
+        const double r = g.xmin + g.DX * (c + 0.5 + gauss_offset(mu));
+        int L, km;
+        double off;
+        ring_table(g.has_l, g.uniform_L, MUBAR * g.cell0 + i + 1, L, km, off);
+        if (w_r) w_r[i] = (double)(DX * (xreal)(mu == 1 ? 8 : 5) / 18.0L * (g.has_l ? (xreal)r : 1.0L));
+        if (w_l) w_l[i] = g.has_l ? (double)(2.0L * PI / (xreal)L) : 1.0;
+    }
+    if (w_z && g.has_z) {
+        const int n = g.nz - 1;
+        const xreal half = ((xreal)g.zmax - (xreal)g.zmin) / 2.0L;
+        for (int j = 0; j <= n; j++) {
+            xreal s = 1.0L;
+            for (int k = 1; 2 * k <= n; k++)
+                s -= (2 * k == n ? 1.0L : 2.0L) / (xreal)(4 * k * k - 1) * cosl(2.0L * (xreal)k * (xreal)j * PI / (xreal)n);
+            w_z[j] = (double)(((j == 0 || j == n) ? 1.0L : 2.0L) / (xreal)n * s * half);
+        }
+    }
+}
+
 void ring_table(int has_l, int uniform_L, int ri, int &L, int &kmax, double &off) {
     if (!has_l) { L = 1; kmax = 0; off = 0.0; return; }
     if (uniform_L > 0) {

@@ -361,6 +361,7 @@ class ModelRun:
             else:
                 raise ValueError("exchange must be 'a2a', 'iface' or 'gather'")
         self.t = 0
+        self._ring_axes = None      # azimuthal_mean's (r, z) axes, formed on first use
 
     def _bind_streams(self, device):
         """Kernels of a tile run on ITS stream; torch's collectives order themselves against torch's CURRENT stream.  Hand
@@ -448,6 +449,43 @@ class ModelRun:
                 out[sel] = g.evaluate(p[sel], all_k)
                 held[sel] = True
         return out, held
+
+    def _tiles_in_order(self):
+        """the local tiles by tile number"""
+        return [g for _, g in sorted(zip(self.tile_ids, self.tiles), key=lambda tg: tg[0])]
+
+    def integrate(self, terms, source="physical"):
+        """Domain integrals of field products over the local tiles (Grid.reduce, kind="domain"): ndarray [n_out], the tile results
+        summed in tile order.  source="physical" runs tileTransform! on every local tile first; source="state" reads var_np1 and
+        costs no transform.  With one process per GPU every rank returns its own tiles' share (evaluate's convention: no
+        collective is added)."""
+        total = np.zeros(max((int(term[0]) for term in terms), default=-1) + 1)
+        for g in self._tiles_in_order():
+            if source == "physical":
+                g.tileTransform_()
+            total = total + g.reduce(terms, "domain", source)
+        return total
+
+    def azimuthal_mean(self, terms, source="physical"):
+        """Azimuthal means of field products over the local tiles (Grid.reduce, kind="azimuth"): (r [rings], z [zDim] or [0.0]
+        without a vertical, mean [rings, zDim, n_out]), the rings of the local tiles concatenated in tile order."""
+        if self._ring_axes is None:       # the rings' radii and the levels: functions of the grid, formed once
+            rs, z = [], np.zeros(1)
+            for g in self._tiles_in_order():
+                pts = getGridpoints(g)
+                pts = pts.reshape(len(pts), -1)
+                r = pts[:, 0]
+                rs.append(r[np.concatenate([[True], r[1:] != r[:-1]])])      # ring-major points: a ring's radius is one double
+                if "Z" in self.patch.geometry:
+                    z = pts[:self.patch.zDim, -1].copy()
+            self._ring_axes = (np.concatenate(rs), z)
+        means = []
+        for g in self._tiles_in_order():
+            if source == "physical":
+                g.tileTransform_()
+            means.append(g.reduce(terms, "azimuth", source))
+        rs, z = self._ring_axes
+        return rs.copy(), z.copy(), np.concatenate(means, axis=0)
 
     def patch_spectral(self):
         """mtile.patchSpectral as the master pulls it from a worker for output (src/semiimplicit.jl:288-293): the patch's A

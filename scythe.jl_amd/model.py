@@ -336,6 +336,23 @@ class Grid:
                                       out.ctypes.data_as(L.P_D)))
         return out
 
+    def reduce(self, terms, kind="domain", source="physical"):
+        """Integrals or azimuthal means of field products on the device (sx_reduce).  terms: a list of
+        (out, coef, r_power, [(var, slot), ...]): coef * r^r_power * the product of the named fields is added to output `out`; var a
+        name or a 1-based index, slot one of "" r rr l ll z zz or an index into `physical`'s slots; n_out = max(out) + 1.
+        kind="domain": ndarray [n_out], this tile's share of the domain integral (Gauss-Legendre in r with the polar area element on
+        RL / RLZ, 2 pi / L in lambda, Clenshaw-Curtis in z).  kind="azimuth": ndarray [tile rings, levels, n_out], the mean over
+        lambda at every ring and level.  source="physical" reads `physical` as it stands (call tileTransform_ first);
+        source="state" reads var_np1 (values only), complete after every step."""
+        coef, packed, n_out = pack_reduce_program(self.patch_params, terms)
+        if kind not in L.REDUCE_KIND or source not in L.REDUCE_SOURCE:
+            raise ValueError("kind must be 'domain' or 'azimuth', source 'physical' or 'state'")
+        nz = max(int(self.dims.zDim), 1)
+        out = np.zeros(n_out) if kind == "domain" else np.zeros((int(self.dims.tile_rDim), nz, n_out), order="F")
+        L.check(self._lib.sx_reduce(self._h, L.REDUCE_KIND[kind], L.REDUCE_SOURCE[source], len(coef), coef.ctypes.data_as(L.P_D),
+                                    packed.ctypes.data_as(L.P_I32), n_out, out.ctypes.data_as(L.P_D)))
+        return out
+
     # -- operators
     def spectralTransform_(self):
         L.check(self._lib.sx_spectral_transform(self._h))
@@ -523,6 +540,80 @@ def eval_basis(patch: GridParameters, var, point, all_k=False, tile_cell0=0, til
     L.check(L.load().sx_eval_basis(C.byref(d), v, pt.ctypes.data_as(L.P_D), L.EVAL_ALL_K if all_k else L.EVAL_RING_K, C.byref(node0),
                                    w_r.ctypes.data_as(L.P_D), C.byref(kcap), w_z.ctypes.data_as(L.P_D) if w_z is not None else None))
     return node0.value, w_r, kcap.value, w_z
+
+
+# ----------------------------------------------------------------------------- integrals and azimuthal means (sx_reduce)
+class Program(list):
+    """An integrand program for Grid.reduce / ModelRun.integrate: a list of (out, coef, r_power, [(var, slot), ...]) terms with a
+    name per output."""
+
+    def __init__(self, terms=(), names=()):
+        super().__init__(terms)
+        self.names = list(names)
+
+
+def pack_reduce_program(patch: GridParameters, terms):
+    """terms -> (coef float64 [n], terms int32 [n, 11] = out, r_power, n_factors, var[4], slot[4] as sx_reduce reads them, n_out);
+    variable and slot names are resolved against the patch, everything else is left to the library to refuse."""
+    slots = L.SLOTS[patch.geometry]
+    coef = np.zeros(len(terms))
+    packed = np.zeros((len(terms), 11), dtype=np.int32)
+    for i, (out, c, p, factors) in enumerate(terms):
+        if len(factors) > 4:
+            raise ValueError("term %d has %d factors; at most 4" % (i, len(factors)))
+        coef[i] = float(c)
+        packed[i, :3] = int(out), int(p), len(factors)
+        for f, (var, slot) in enumerate(factors):
+            if isinstance(var, str) and var not in patch.vars:
+                raise ValueError("term %d: unknown variable %r" % (i, var))
+            if isinstance(slot, str) and slot not in slots:
+                raise ValueError("term %d: an %s grid has no slot %r" % (i, patch.geometry, slot))
+            packed[i, 3 + f] = patch.vars[var] if isinstance(var, str) else int(var)
+            packed[i, 7 + f] = slots.index(slot) if isinstance(slot, str) else int(slot)
+    n_out = int(packed[:, 0].max()) + 1 if len(terms) else 0
+    return coef, packed, n_out
+
+
+def reduce_weights(patch: GridParameters, tile_cell0=0, tile_num_cells=None):
+    """The quadrature weights of Grid.reduce(kind="domain") for a tile, on the host (sx_reduce_weights): (w_r [3 cells],
+    w_l [3 cells], w_z [zDim] or None).  w_r = DX (5, 8, 5) / 18 (times r on RL / RLZ), w_l = 2 pi / L, w_z = Clenshaw-Curtis."""
+    d, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    n = 3 * d.tile_num_cells
+    w_r, w_l = np.zeros(n), np.zeros(n)
+    w_z = np.zeros(patch.zDim) if "Z" in patch.geometry else None
+    L.check(L.load().sx_reduce_weights(C.byref(d), w_r.ctypes.data_as(L.P_D), w_l.ctypes.data_as(L.P_D),
+                                       w_z.ctypes.data_as(L.P_D) if w_z is not None else None))
+    return w_r, w_l, w_z
+
+
+def reduce_planes(patch: GridParameters, terms, source="physical", tile_cell0=0, tile_num_cells=None):
+    """The distinct (var, slot) planes a program reads, in first-use order, as the validator of sx_reduce sees them
+    (sx_reduce_planes): ndarray [n_planes, 2] of (1-based variable, slot index).  Raises what Grid.reduce would refuse."""
+    d, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    coef, packed, n_out = pack_reduce_program(patch, terms)
+    planes = np.zeros((16, 2), dtype=np.int32)
+    n = C.c_int32(0)
+    L.check(L.load().sx_reduce_planes(C.byref(d), L.REDUCE_SOURCE[source], len(coef), packed.ctypes.data_as(L.P_I32), n_out,
+                                      planes.ctypes.data_as(L.P_I32), C.byref(n)))
+    return planes[:n.value].copy()
+
+
+def invariants(model: ModelParameters):
+    """The conserved (or budget) integrals of an equation set as a Program for ModelRun.integrate:
+    LinearShallowWater1D  mass = int h, energy = 1/2 int (g h^2 + H u^2);  LinearShallowWaterRL  the same with H (u^2 + v^2);
+    LinearAdvection*      the first moment int q and the second moment int q^2 of the advected variable (variable 1)."""
+    eq = model.equation_set
+    pp = {(k if isinstance(k, str) else str(k)).lstrip(":"): v for k, v in model.physical_params.items()}
+    if eq in ("LinearShallowWater1D", "LinearShallowWaterRL"):
+        g, H = float(pp["g"]), float(pp["H"])
+        terms = [(0, 1.0, 0, [("h", "")]), (1, 0.5 * g, 0, [("h", ""), ("h", "")]), (1, 0.5 * H, 0, [("u", ""), ("u", "")])]
+        if eq == "LinearShallowWaterRL":
+            terms.append((1, 0.5 * H, 0, [("v", ""), ("v", "")]))
+        return Program(terms, ["mass", "energy"])
+    if eq.startswith("LinearAdvection"):
+        q = model.grid_params.var_names()[0]
+        return Program([(0, 1.0, 0, [(q, "")]), (1, 1.0, 0, [(q, ""), (q, "")])], ["integral", "integral_of_square"])
+    raise ValueError("equation set %r has no invariants defined" % eq)
 
 
 def regular_gridpoints(gp: GridParameters, nr, nl=None, nz=None):
