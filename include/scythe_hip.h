@@ -267,12 +267,42 @@ int sx_max_abs(sx_handle *h, double *out);
  * and captured graphs stay as they are (a deferred diagnostic variable is brought up to date first, as for every reader of A). */
 enum { SX_EVAL_RING_K = 0, SX_EVAL_ALL_K = 1 };
 int sx_evaluate(sx_handle *h, const double *points, int64_t n_points, int32_t flags, double *out);
+/* sx_evaluate restricted to a wavenumber band: only the wavenumbers kmin <= k <= min(kmax, kcap) of the azimuthal series are summed
+ * (k = 0 is the azimuthal mean), everything else as sx_evaluate.  0 <= kmin <= kmax; a kmax above sx_dims.kDim is clamped; kmin > kmax or
+ * a negative bound is refused.  sx_evaluate is the band (0, kDim), bit for bit.  On a grid without an azimuth only k = 0 exists. */
+int sx_evaluate_band(sx_handle *h, const double *points, int64_t n_points, int32_t flags, int32_t kmin, int32_t kmax, double *out);
 /* The weights sx_evaluate applies at ONE point of the tile the descriptor selects, for variable var: node0 = 0-based patch row of the
  * first of the 4 spline nodes, w_r = phi, phi', phi'' at them, kcap as above, w_z[s][zm] = row s (value, d/dz, d2/dz2) of the
  * vertical operator at the point's z (RZ / RLZ grids; untouched otherwise).  Refuses what sx_evaluate refuses; any output pointer
  * may be NULL.  Pure host helper (no handle, no device): the basis arithmetic is testable where there is no GPU. */
 int sx_eval_basis(const sx_grid_desc *grid, int32_t var /*1-based*/, const double *point /*[n_coord]*/, int32_t flags,
                   int32_t *node0, double *w_r /*[3][4]*/, int32_t *kcap, double *w_z /*[3][b_zDim]*/);
+
+/* --- azimuthal harmonics of the state ---------------------------------------------------------------------------------
+ * With F_blk as above (block 0 -> 1, block 2k -> 2 cos k lambda, block 2k + 1 -> -2 sin k lambda) the state at (r, z) is
+ *     u(r, lambda, z) = Re sum_{k = 0}^{kcap(r)} eps_k c_k(r, z) e^{i k lambda},   eps_0 = 1, eps_k = 2 for k >= 1,
+ * and the coefficient blocks are the harmonics themselves:
+ *     c_k(r, z) = sum_node sum_zm (A[zm, 2k, node] + i A[zm, 2k + 1, node]) phi_node(r) Wz[zm](z)
+ * (Im c_0 = 0: block 1 is padding and is never read).  On a ring of the grid, for k <= kmax[ring] < L / 2, c_k is the discrete
+ * transform (1 / L) sum_j u_j e^{-i k lambda_j} of the ring's values.  No Fourier transform is taken and nothing but A is read.
+ * slot_mask picks any subset of five slots, bits 0..4 = u, r, rr, z, zz: radial weights phi, phi', phi'', phi, phi and vertical
+ * operator row 0, 0, 0, 1, 2 (value, d/dz, d2/dz2).  lambda derivatives are i k c_k and are left to the caller.
+ * The radial weights, the wavenumber cap kcap(r) (flags SX_EVAL_RING_K / SX_EVAL_ALL_K) and the vertical rows are those of sx_evaluate
+ * (sx_eval_basis returns them); entries with k > kcap(r) are exact zeros.
+ *   radii[n_r]: any order, duplicates allowed, within the tile's extent, both ends included;
+ *   heights[n_z]: within [zmin, zmax]; a grid without a vertical takes heights = NULL, n_z = 0 (one "height") and no z / zz bit;
+ *   out[2 (kDim + 1), n_z, n_r, n_vars, n_slots] column-major, n_slots = popcount(slot_mask) in the order u, r, rr, z, zz: the tensor
+ *   product of the radii and the heights.  The first axis is the device block axis (re, im interleaved): viewed as complex the array
+ *   is [kDim + 1, n_z, n_r, n_vars, n_slots].  kDim = sx_dims.kDim; a grid without an azimuth has kDim = 0 and c_0 = the value.
+ * Refused, with a message and before anything is written to out: a NaN / Inf or out-of-range radius or height; n_r < 0 or n_z < 0;
+ * slot_mask 0 or with a bit the geometry has no slot for; flags other than the two above; a null pointer with a non-zero count;
+ * a grid whose b_zDim exceeds 128 (the vertical modes of a column are held in registers).
+ * n_r == 0 succeeds and writes nothing.  A result does not depend on which other radii are in the call (bitwise).
+ * Runs on the handle's stream and returns after the copy-out; reads A only: `physical`, var_np1, the tendency history, the B arrays
+ * and captured graphs stay as they are (a deferred diagnostic variable is brought up to date first, as for every reader of A). */
+enum { SX_HARM_U = 1, SX_HARM_R = 2, SX_HARM_RR = 4, SX_HARM_Z = 8, SX_HARM_ZZ = 16 };
+int sx_harmonics(sx_handle *h, const double *radii, int32_t n_r, const double *heights, int32_t n_z,
+                 int32_t flags, int32_t slot_mask, double *out);
 
 /* --- integrals and azimuthal means of field products ------------------------------------------------------------------
  * On-device diagnostics: budgets and azimuthal means / eddy covariances without pulling `physical` to the host.

@@ -164,6 +164,31 @@ function evaluateDevice(mtile::HipModelTile, points::Matrix{Float64}; all_k::Boo
     return out
 end
 
+# the same restricted to the wavenumbers kmin <= k <= kmax (sx_evaluate_band): (2, 2) is the wave-2 part of every field
+function evaluateBandDevice(mtile::HipModelTile, points::Matrix{Float64}, kmin::Integer, kmax::Integer; all_k::Bool = false)
+    n = size(points, 1)
+    d = Ref{SxDims}()
+    sxcheck(ccall((:sx_get_dims, libsx), Cint, (Ptr{Cvoid}, Ref{SxDims}), mtile.handle, d))
+    out = zeros(Float64, n, d[].n_vars, d[].n_derivs)
+    sxcheck(ccall((:sx_evaluate_band, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int32, Int32, Int32, Ptr{Float64}),
+                  mtile.handle, points, n, all_k ? 1 : 0, kmin, kmax, out))
+    return out
+end
+
+# the azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: ComplexF64 [kDim + 1, n_z, n_r, n_vars,
+# n_slots], the state being real(sum_k eps_k c_k exp(im k lambda)), eps_0 = 1, eps_k = 2; slot_mask bits 0..4 = u, r, rr, z, zz.
+# A grid without a vertical takes heights = nothing (one "height") and no z / zz bit
+function harmonicsDevice(mtile::HipModelTile, radii::Vector{Float64}, heights::Union{Vector{Float64}, Nothing} = nothing;
+                         all_k::Bool = false, slot_mask::Integer = 1)
+    d = Ref{SxDims}()
+    sxcheck(ccall((:sx_get_dims, libsx), Cint, (Ptr{Cvoid}, Ref{SxDims}), mtile.handle, d))
+    n_z = heights === nothing ? 0 : length(heights)
+    out = zeros(ComplexF64, d[].kDim + 1, max(n_z, 1), length(radii), d[].n_vars, count_ones(slot_mask))
+    sxcheck(ccall((:sx_harmonics, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int32, Ptr{Float64}, Int32, Int32, Int32, Ptr{ComplexF64}),
+                  mtile.handle, radii, length(radii), heights === nothing ? C_NULL : heights, n_z, all_k ? 1 : 0, slot_mask, out))
+    return out
+end
+
 function patchSpectral(mtile::HipModelTile)
     sxcheck(ccall((:sx_get_patch_spectral_a, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}),
                   mtile.handle, mtile.patchSpectral))

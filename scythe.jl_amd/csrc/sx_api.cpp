@@ -731,6 +731,7 @@ int sx_destroy(sx_handle *h) {
     iface_release(h);
     pcr_release(h);
     eval_release(h);
+    harm_release(h);
     reduce_release(h);
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
@@ -1435,6 +1436,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_rz_inverse") b = w * S_tile + N * out_planes;       // read the tile's A rows, write the requested physical planes
     else if (k == "k_rz_forward") b = w * N * V + w * S_tile;            // read var_np1, write the tile's B rows
     else if (k == "k_evaluate") b = eval_last_bytes(h);                  // the last call's batches x 4 rows x live columns of A
+    else if (k == "k_harmonics") b = harm_last_bytes(h);                // the last call's radii x 4 rows x b_zDim x (2 kcap + 1) of A
     else if (k == "k_reduce") b = reduce_last_bytes(h);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
     *bytes = b;
     return 0;

@@ -62,7 +62,7 @@ __device__ inline double2 eval_cs(int k, double lh, double ll) {
 __global__ __launch_bounds__(EVAL_T) void k_evaluate(const double *__restrict__ A, int64_t C, const EvalPt *__restrict__ pts,
                                                      const int2 *__restrict__ batches, const double *__restrict__ wz,
                                                      const int *__restrict__ vcls, int ncls, int Zb, int K2, int has_l, int csw, int P,
-                                                     EvalSlots slots, double *__restrict__ res, int64_t nres, int V) {
+                                                     int kmin, int kband, EvalSlots slots, double *__restrict__ res, int64_t nres, int V) {
     extern __shared__ double lds[];
     double2 *cs = reinterpret_cast<double2 *>(lds);
     double *zw = lds + (size_t)2 * P * csw;
@@ -82,6 +82,7 @@ __global__ __launch_bounds__(EVAL_T) void k_evaluate(const double *__restrict__ 
     }
     int kmaxb = 0;
     for (int p = 0; p < np; p++) kmaxb = max(kmaxb, pts[start + p].kcap);
+    kmaxb = min(kmaxb, kband);                        // the band kmin <= k <= kband (sx_evaluate: 0, kDim)
     if (tid < np) kc[tid] = pts[start + tid].kcap;
     for (int i = tid; i < np * csw; i += EVAL_T) {
         const int p = i / csw, k = i - p * csw;
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(EVAL_T) void k_evaluate(const double *__restrict__ 
         for (int c = 0; c < EVAL_CT; c++) {
             const int col = col0 + c * EVAL_T;
             czm[c] = zm; cblk[c] = blk;
-            on[c] = col < ncol && blk <= live && blk != 1;
+            on[c] = col < ncol && blk <= live && blk != 1 && (blk >> 1) >= kmin;
 #pragma unroll
             for (int j = 0; j < 4; j++) a[c][j] = on[c] ? Av[(int64_t)j * C + col] : 0.0;
             zm += q; blk += rem;
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(EVAL_T) void k_evaluate(const double *__restrict__ 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-static EvalGeom geom_of(const sx_handle *h) {
+EvalGeom eval_geom_of(const sx_handle *h) {
     EvalGeom g;
     g.has_l = h->has_l; g.has_z = h->has_z; g.nc = h->nc; g.cell0 = h->cell0; g.ncells = h->ncells; g.uniform_L = h->uniform_L;
     g.kDim = h->kDim; g.nz = h->nz; g.Zb = h->Zb; g.xmin = h->xmin; g.xmax = h->xmax; g.DX = h->DX; g.zmin = h->zmin; g.zmax = h->zmax;
@@ -239,13 +240,22 @@ static EvalState *eval_state(sx_handle *h) {
     return st;
 }
 
+// the vertical classes and the per-variable class table (device), for sx_harmonics
+bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls) {
+    EvalState *st = eval_state(h);
+    if (!st) return false;
+    vert = &st->vert;
+    d_vcls = st->d_vcls;
+    return true;
+}
+
 static size_t eval_lds_bytes(int P, int csw, int Zb) {
     return sizeof(double) * ((size_t)2 * P * csw + (size_t)P * 3 * Zb + (size_t)P * 12 + 4 * EVAL_P * 7) + sizeof(int) * EVAL_P;
 }
 
 // one launch: the points [p0, p0 + n) of the call
 static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const double *points, int64_t n_all, int64_t p0, int n, int flags,
-                       double *out) {
+                       int kmin, int kband, double *out) {
     const int ncls = std::max<int>(1, (int)st->vert.size()), Zb = h->has_z ? h->Zb : 1;
     const long double two_pi = 8.0L * atanl(1.0L);
     std::vector<EvalPt> pts(n);
@@ -294,7 +304,8 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
         int j = i, kmax = 0;
         while (j < n && j - i < P && pts[j].cell == pts[i].cell) kmax = std::max(kmax, pts[j++].kcap);
         batches.push_back(make_int2(i, j - i));
-        cols += (double)Zb * (h->has_l ? 2 * kmax + 1 : 1);
+        const int khi = std::min(kmax, kband);                       // live blocks: k = 0 is one, every k >= 1 two
+        cols += (double)Zb * (h->has_l ? (kmin > 0 ? std::max(0, 2 * (khi - kmin + 1)) : 2 * khi + 1) : 1);
         i = j;
     }
     st->last_bytes += 8.0 * 4.0 * cols * h->V;
@@ -310,7 +321,7 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
     for (int m = 0; m < 7; m++) sl.s[m] = h->slot[m];
     timer_begin(h, timer_id(h, "k_evaluate"));
     hipLaunchKernelGGL(k_evaluate, dim3((unsigned)batches.size(), (unsigned)h->V), dim3(EVAL_T), eval_lds_bytes(P, csw, Zb), h->stream, h->d_A,
-                       h->C, st->d_pts, st->d_batch, st->d_wz, st->d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, sl, st->d_res, (int64_t)n, h->V);
+                       h->C, st->d_pts, st->d_batch, st->d_wz, st->d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, kmin, kband, sl, st->d_res, (int64_t)n, h->V);
     HIPCHK(hipGetLastError());
     timer_end(h);
     std::vector<double> res(nres);
@@ -327,14 +338,12 @@ using namespace sx;
 
 extern "C" {
 
-int sx_evaluate(sx_handle *h, const double *points, int64_t n_points, int32_t flags, double *out) {
-    clear_error();
-    if (!h) { set_error("null handle"); return 1; }
+static int evaluate_band(sx_handle *h, const double *points, int64_t n_points, int32_t flags, int kmin, int kband, double *out) {
     if (n_points < 0) { set_error("sx_evaluate: n_points is negative"); return 1; }
     if (flags != SX_EVAL_RING_K && flags != SX_EVAL_ALL_K) { set_error("sx_evaluate: flags must be SX_EVAL_RING_K or SX_EVAL_ALL_K"); return 1; }
     if (n_points == 0) return 0;
     if (!points || !out) { set_error("sx_evaluate: null argument"); return 1; }
-    const EvalGeom g = geom_of(h);
+    const EvalGeom g = eval_geom_of(h);
     std::string why;
     for (int64_t i = 0; i < n_points; i++) {
         const double lam = h->has_l ? points[n_points + i] : 0.0, z = h->has_z ? points[(int64_t)(h->ncoord - 1) * n_points + i] : 0.0;
@@ -347,9 +356,22 @@ int sx_evaluate(sx_handle *h, const double *points, int64_t n_points, int32_t fl
     std::vector<double> tmp((size_t)n_points * h->V * h->D);
     st->last_bytes = 0;
     for (int64_t p0 = 0; p0 < n_points; p0 += EVAL_CHUNK)
-        if (!eval_chunk(h, st, g, points, n_points, p0, (int)std::min<int64_t>(EVAL_CHUNK, n_points - p0), flags, tmp.data())) return 1;
+        if (!eval_chunk(h, st, g, points, n_points, p0, (int)std::min<int64_t>(EVAL_CHUNK, n_points - p0), flags, kmin, kband, tmp.data())) return 1;
     std::memcpy(out, tmp.data(), sizeof(double) * tmp.size());
     return error_status();
+}
+
+int sx_evaluate(sx_handle *h, const double *points, int64_t n_points, int32_t flags, double *out) {
+    clear_error();
+    if (!h) { set_error("null handle"); return 1; }
+    return evaluate_band(h, points, n_points, flags, 0, h->kDim, out);
+}
+
+int sx_evaluate_band(sx_handle *h, const double *points, int64_t n_points, int32_t flags, int32_t kmin, int32_t kmax, double *out) {
+    clear_error();
+    if (!h) { set_error("null handle"); return 1; }
+    if (kmin < 0 || kmax < kmin) { set_error("sx_evaluate_band: need 0 <= kmin <= kmax"); return 1; }
+    return evaluate_band(h, points, n_points, flags, kmin, std::min<int>(kmax, h->kDim), out);
 }
 
 int sx_eval_basis(const sx_grid_desc *gd, int32_t var, const double *point, int32_t flags, int32_t *node0, double *w_r, int32_t *kcap,

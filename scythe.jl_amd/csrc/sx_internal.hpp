@@ -292,6 +292,7 @@ struct sx_handle {
     void *iface_state = nullptr;              // interface-only patch solve (sx_iface.hip)
     void *pcr_state = nullptr;                // parallel-cyclic-reduction tables and launch lists (sx_pcr.hip)
     void *eval_state = nullptr;               // sx_evaluate's vertical classes and device scratch, made on first use (sx_eval.hip)
+    void *harm_state = nullptr;               // sx_harmonics' device scratch, made on first use (sx_harmonics.hip)
     void *reduce_state = nullptr;             // sx_reduce's work list, weights and ring-sum scratch, made on first use (sx_reduce.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
@@ -364,6 +365,10 @@ void iface_release(sx_handle *h);
 void pcr_release(sx_handle *h);
 void eval_release(sx_handle *h);
 double eval_last_bytes(const sx_handle *h);   // A bytes the last sx_evaluate read
+EvalGeom eval_geom_of(const sx_handle *h);
+bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls);   // sx_evaluate's vertical classes, made on first use
+void harm_release(sx_handle *h);
+double harm_last_bytes(const sx_handle *h);   // A bytes the last sx_harmonics read
 void reduce_release(sx_handle *h);
 double reduce_last_bytes(const sx_handle *h);   // plane bytes the last sx_reduce read
 bool rz_fused(const sx_handle *h);

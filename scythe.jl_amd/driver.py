@@ -428,7 +428,7 @@ class ModelRun:
             out.append(g.physical)
         return np.concatenate(out, axis=0)
 
-    def evaluate(self, points, all_k=False):
+    def evaluate(self, points, all_k=False, k_band=None):
         """Grid.evaluate over the local tiles: every point goes to the local tile that contains its radius (a shared edge to the
         lower tile).  Returns (values [n, V, D], held [n] bool): held marks the points this process holds; the rows of the others
         are zero (write_output's convention: each process deals with its local tiles)."""
@@ -446,7 +446,29 @@ class ModelRun:
             hi = patch.xmax if c0 + n == patch.num_cells else patch.xmin + (c0 + n) * DX
             sel = np.nonzero((p[:, 0] >= lo) & (p[:, 0] <= hi) & ~held)[0]
             if len(sel):
-                out[sel] = g.evaluate(p[sel], all_k)
+                out[sel] = g.evaluate(p[sel], all_k, k_band)
+                held[sel] = True
+        return out, held
+
+    def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
+        """Grid.harmonics over the local tiles: every radius goes to the local tile that contains it (a shared edge to the lower
+        tile, as in evaluate).  Returns (values [n_r, n_z, kDim + 1, V, n_slots] complex, held [n_r] bool); the rows of radii no
+        local tile holds are zero."""
+        patch = self.patch
+        r = np.asarray(radii, dtype=np.float64).reshape(-1)
+        g0 = self.tiles[0]
+        n_z = 1 if heights is None else np.asarray(heights).size
+        n_slots = len(set(slots))                                  # Grid.harmonics refuses what is no set of slot names
+        out = np.zeros((len(r), n_z, int(g0.dims.kDim) + 1, g0.V, n_slots), dtype=np.complex128)
+        held = np.zeros(len(r), dtype=bool)
+        DX = (patch.xmax - patch.xmin) / patch.num_cells
+        for t, g in sorted(zip(self.tile_ids, self.tiles)):
+            c0, n = self.layout.cell0[t], self.layout.ncells[t]
+            lo = patch.xmin if c0 == 0 else patch.xmin + c0 * DX
+            hi = patch.xmax if c0 + n == patch.num_cells else patch.xmin + (c0 + n) * DX
+            sel = np.nonzero((r >= lo) & (r <= hi) & ~held)[0]
+            if len(sel):
+                out[sel] = g.harmonics(r[sel], heights, all_k, slots)
                 held[sel] = True
         return out, held
 

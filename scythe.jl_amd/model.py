@@ -321,20 +321,46 @@ class Grid:
         L.check(self._lib.sx_get_patch_spectral_a(self._h, out.ctypes.data_as(L.P_D)))
         return out
 
-    def evaluate(self, points, all_k=False):
+    def evaluate(self, points, all_k=False, k_band=None):
         """The spectral state (the A coefficients the tile holds now) at arbitrary points of the tile: points [n, n_coord] with
         columns r[, lambda][, z] as getGridpoints returns them -> ndarray [n, V, D], slots as in `physical` (sx_evaluate).
         all_k=False cuts the azimuthal series at the kmax of the last ring at or below each radius, as tileTransform! does on the
-        rings; all_k=True sums every wavenumber of the patch."""
+        rings; all_k=True sums every wavenumber of the patch.  k_band=(kmin, kmax) sums the wavenumbers kmin <= k <= kmax only
+        (sx_evaluate_band): (2, 2) is the wave-2 part of every field."""
         nc = int(self.dims.n_coord)
         p = np.asarray(points, dtype=np.float64)
         p = np.asfortranarray(p.reshape(-1, nc) if p.ndim != 2 else p)
         if p.shape[1] != nc:
             raise ValueError("points must have %d coordinate column(s)" % nc)
         out = np.zeros((p.shape[0], self.V, self.D), order="F")
-        L.check(self._lib.sx_evaluate(self._h, p.ctypes.data_as(L.P_D), p.shape[0], L.EVAL_ALL_K if all_k else L.EVAL_RING_K,
-                                      out.ctypes.data_as(L.P_D)))
+        flags = L.EVAL_ALL_K if all_k else L.EVAL_RING_K
+        if k_band is None:
+            L.check(self._lib.sx_evaluate(self._h, p.ctypes.data_as(L.P_D), p.shape[0], flags, out.ctypes.data_as(L.P_D)))
+        else:
+            L.check(self._lib.sx_evaluate_band(self._h, p.ctypes.data_as(L.P_D), p.shape[0], flags, int(k_band[0]), int(k_band[1]),
+                                               out.ctypes.data_as(L.P_D)))
         return out
+
+    def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
+        """The azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: complex128 ndarray indexed
+        [ir, iz, k, v, s], k = 0 .. kDim, s over `slots` in the order u, r, rr, z, zz (a view of the library's buffer).  The state is
+        Re sum_k eps_k c_k e^{i k lambda}, eps_0 = 1, eps_k = 2; on a ring of the grid c_k is the discrete transform of the ring's
+        values.  heights stays None on a grid without a vertical (iz has length 1).  all_k as for evaluate: entries above the
+        wavenumber cap of a radius are zero."""
+        names = [s for s in L.HARM_SLOTS if s in slots]
+        if not names or len(names) != len(set(slots)) or set(slots) - set(L.HARM_SLOTS):
+            raise ValueError("slots must be a non-empty subset of %s" % (L.HARM_SLOTS,))
+        mask = sum(1 << L.HARM_SLOTS.index(s) for s in names)
+        r = np.ascontiguousarray(np.asarray(radii, dtype=np.float64).reshape(-1))
+        z = None if heights is None else np.ascontiguousarray(np.asarray(heights, dtype=np.float64).reshape(-1))
+        nz = 1 if z is None else len(z)
+        K = int(self.dims.kDim) + 1
+        out = np.zeros((2 * K, nz, len(r), self.V, len(names)), order="F")
+        L.check(self._lib.sx_harmonics(self._h, r.ctypes.data_as(L.P_D), len(r), None if z is None else z.ctypes.data_as(L.P_D),
+                                       0 if z is None else len(z), L.EVAL_ALL_K if all_k else L.EVAL_RING_K, mask,
+                                       out.ctypes.data_as(L.P_D)))
+        c = out.T.view(np.complex128)                     # C-contiguous [s, v, ir, iz, 2K] -> [s, v, ir, iz, K]
+        return c.transpose(2, 3, 4, 1, 0)
 
     def reduce(self, terms, kind="domain", source="physical"):
         """Integrals or azimuthal means of field products on the device (sx_reduce).  terms: a list of
