@@ -304,6 +304,36 @@ enum { SX_HARM_U = 1, SX_HARM_R = 2, SX_HARM_RR = 4, SX_HARM_Z = 8, SX_HARM_ZZ =
 int sx_harmonics(sx_handle *h, const double *radii, int32_t n_r, const double *heights, int32_t n_z,
                  int32_t flags, int32_t slot_mask, double *out);
 
+/* --- azimuthal power and cross spectra of the state --------------------------------------------------------------------
+ * How much variance, energy or flux sits in each azimuthal wavenumber, per ring and for the domain, from A alone.
+ * A pair is two planes (var_a, slot_a), (var_b, slot_b): var 1-based, slot 0..4 = u, r, rr, z, zz, the five slots of sx_harmonics with
+ * their radial weights and vertical rows.  n_pairs <= 16 per call; a pair with a == b is a power spectrum.
+ * At tile ring i (the radius sx_get_gridpoints prints, truncation SX_EVAL_RING_K: kcap = kmax[ring], as sx_tile_transform) and level
+ * j (the Chebyshev-Gauss-Lobatto height sx_get_gridpoints prints)
+ *     P_k(i, j) = eps_k Re(c_k^a conj(c_k^b)) = eps_k (a[2k] b[2k] + a[2k + 1] b[2k + 1]),   eps_0 = 1, eps_k = 2 for k >= 1,
+ * a[blk], b[blk] the per-block harmonic values sx_harmonics returns at (r_i, z_j); block 1 is padding, is never read and counts as 0.
+ * Entries with k > kmax[ring] are exact zeros; on a grid without an azimuth kDim = 0 and P_0 is the pointwise product.
+ * Kind.  SX_SPEC_RING: out[kDim + 1, tile ring, n_pairs] column-major = sum_level w_z[level] P_k(ring, level) (without a vertical: P_k
+ * itself), the radius-wavenumber diagram.  SX_SPEC_DOMAIN: out[kDim + 1, n_pairs] = sum_ring 2 pi w_r[ring] (the ring value above),
+ * this tile's share of the domain integral per wavenumber.  w_r, w_z are the arrays sx_reduce_weights returns and 2 pi stands for
+ * w_l[ring] L[ring] (1 on a grid without an azimuth, as in sx_reduce).  Tiles own disjoint cells: a patch spectrum is the sum of the
+ * tile results (domain kind) or their concatenation (ring kind).  Level-resolved spectra are what sx_harmonics gives.
+ * Identity (Parseval; every ring table has 2 kmax[ring] < L[ring]): sum_k out_domain[k, p] equals sx_reduce(SX_REDUCE_DOMAIN,
+ * SX_REDUCE_PHYSICAL) of the one-term program field(a) field(b) after sx_tile_transform, and sum_k out_ring[k, ring, p] equals the
+ * w_z-weighted level sum of its SX_REDUCE_AZIMUTH result.
+ * Refused, with a message and before anything is written to out: a null pointer with a non-zero count; n_pairs < 0 or > 16; an unknown
+ * kind; a var or slot out of range; a z / zz slot on a grid without a vertical; a grid whose b_zDim exceeds 128 (as sx_harmonics).
+ * n_pairs == 0 succeeds and writes nothing.
+ * Sums are double-double, each by a fixed lane in a fixed order that depends on the grid and the pair list alone (no floating-point
+ * atomics): two calls on the same data agree bitwise, and a pair's result does not depend on the other pairs of the call.
+ * Runs on the handle's stream and returns after the copy-out; reads A only: `physical`, var_np1, the tendency history, the B arrays
+ * and captured graphs stay as they are (a deferred diagnostic variable is brought up to date first, as for every reader of A). */
+enum { SX_SPEC_RING = 0, SX_SPEC_DOMAIN = 1 };
+int sx_spectrum(sx_handle *h, int32_t kind, int32_t n_pairs, const int32_t *pairs /*[n_pairs][4] = var_a, slot_a, var_b, slot_b*/,
+                double *out);
+/* the validator sx_spectrum itself calls: refuses what sx_spectrum refuses of a pair list.  Pure host helper, no handle and no device */
+int sx_spectrum_check(const sx_grid_desc *grid, int32_t n_pairs, const int32_t *pairs);
+
 /* --- integrals and azimuthal means of field products ------------------------------------------------------------------
  * On-device diagnostics: budgets and azimuthal means / eddy covariances without pulling `physical` to the host.
  * Integrand program: n_terms <= 64 monomial terms feed n_out <= 16 outputs.  Term t is

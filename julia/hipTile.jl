@@ -189,6 +189,20 @@ function harmonicsDevice(mtile::HipModelTile, radii::Vector{Float64}, heights::U
     return out
 end
 
+# azimuthal power and cross spectra of the state (sx_spectrum): pairs[4, n_pairs] Int32, column p = var_a, slot_a, var_b, slot_b (var
+# 1-based, slot 0..4 = u, r, rr, z, zz as in harmonicsDevice).  domain = false: [kDim + 1, tile rings, n_pairs], the sum over the levels
+# of w_z eps_k real(c_k^a conj(c_k^b)) at every ring; domain = true: [kDim + 1, n_pairs], the rings summed with 2 pi w_r (the tile's
+# share of the domain integral per wavenumber; the sum over k is the integral of the product)
+function spectrumDevice(mtile::HipModelTile, pairs::Matrix{Int32}; domain::Bool = false)
+    d = Ref{SxDims}()
+    sxcheck(ccall((:sx_get_dims, libsx), Cint, (Ptr{Cvoid}, Ref{SxDims}), mtile.handle, d))
+    n = size(pairs, 2)
+    out = domain ? zeros(Float64, d[].kDim + 1, n) : zeros(Float64, d[].kDim + 1, d[].tile_rDim, n)
+    sxcheck(ccall((:sx_spectrum, libsx), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Int32}, Ptr{Float64}),
+                  mtile.handle, domain ? 1 : 0, n, pairs, out))
+    return out
+end
+
 function patchSpectral(mtile::HipModelTile)
     sxcheck(ccall((:sx_get_patch_spectral_a, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}),
                   mtile.handle, mtile.patchSpectral))

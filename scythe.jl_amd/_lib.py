@@ -12,6 +12,7 @@ GEOM = {"R": 0, "RZ": 1, "RL": 2, "RLZ": 3}
 BC = {"R0": 0, "R1T0": 1, "R1T1": 2, "R1T2": 3, "R2T10": 4, "R2T20": 5, "R3": 6, "PERIODIC": 7}
 EVAL_RING_K, EVAL_ALL_K = 0, 1      # SX_EVAL_*
 HARM_SLOTS = ("u", "r", "rr", "z", "zz")          # SX_HARM_*: bit i of slot_mask
+SPEC_KIND = {"ring": 0, "domain": 1}             # SX_SPEC_RING / SX_SPEC_DOMAIN
 REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_AZIMUTH
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
 SLOTS = {"R": ["", "r", "rr"], "RZ": ["", "r", "rr", "z", "zz"], "RL": ["", "r", "rr", "l", "ll"],
@@ -113,6 +114,8 @@ SYMBOLS = {
     "sx_evaluate_band": (C.c_int, [_H, P_D, C.c_int64, C.c_int32, C.c_int32, C.c_int32, P_D]),
     "sx_eval_basis": (C.c_int, [C.POINTER(GridDesc), C.c_int32, P_D, C.c_int32, P_I32, P_D, P_I32, P_D]),
     "sx_harmonics": (C.c_int, [_H, P_D, C.c_int32, P_D, C.c_int32, C.c_int32, C.c_int32, P_D]),
+    "sx_spectrum": (C.c_int, [_H, C.c_int32, C.c_int32, P_I32, P_D]),
+    "sx_spectrum_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, P_I32]),
     "sx_reduce": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D]),
     "sx_reduce_weights": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, P_D]),
     "sx_reduce_planes": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32, P_I32]),

@@ -179,7 +179,7 @@ static const EqSet *eq_set(int id) {
     return nullptr;
 }
 
-static int default_bzdim(int zDim) {
+int default_bzdim(int zDim) {
     int b = (int)std::floor((2.0 * zDim - 1.0) / 3.0) + 1;
     return std::min(zDim, b);
 }
@@ -733,6 +733,7 @@ int sx_destroy(sx_handle *h) {
     eval_release(h);
     harm_release(h);
     reduce_release(h);
+    spec_release(h);
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -837,11 +838,10 @@ int sx_get_gridpoints(const sx_handle *h, double *out) {
     std::vector<double> z(h->nz, 0.0);
     if (h->has_z)
         for (int n = 0; n < h->nz; n++)
-            z[n] = std::cos(n * M_PI / (h->nz - 1)) * (-0.5 * (h->zmax - h->zmin)) + 0.5 * (h->zmin + h->zmax);
+            z[n] = level_height(h->zmin, h->zmax, h->nz, n);
     int64_t p = 0;
     for (int i = 0; i < h->nrings; i++) {
-        const int mu = i % MUBAR, c = h->cell0 + i / MUBAR;
-        const double r = h->xmin + h->DX * (c + 0.5 + gauss_offset(mu));
+        const double r = ring_radius(h->xmin, h->DX, h->cell0, i);
         for (int l = 0; l < h->hL[i]; l++) {
             const double lam = h->hoff[i] + 2.0 * M_PI * l / h->hL[i];
             for (int k = 0; k < h->nz; k++, p++) {
@@ -1437,6 +1437,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_rz_forward") b = w * N * V + w * S_tile;            // read var_np1, write the tile's B rows
     else if (k == "k_evaluate") b = eval_last_bytes(h);                  // the last call's batches x 4 rows x live columns of A
     else if (k == "k_harmonics") b = harm_last_bytes(h);                // the last call's radii x 4 rows x b_zDim x (2 kcap + 1) of A
+    else if (k == "k_spectrum") b = spec_last_bytes(h);                  // the last call's rings x distinct planes x 4 rows x b_zDim x (2 kmax + 1) of A
     else if (k == "k_reduce") b = reduce_last_bytes(h);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
     *bytes = b;
     return 0;

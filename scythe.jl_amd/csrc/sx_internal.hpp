@@ -76,6 +76,11 @@ inline double gauss_offset(int mu) {
     const double o = std::sqrt(3.0 / 5.0) / 2.0;
     return mu == 0 ? -o : mu == 1 ? 0.0 : o;
 }
+// the radius of tile ring i and the height of level n as sx_get_gridpoints prints them
+inline double ring_radius(double xmin, double DX, int cell0, int i) { return xmin + DX * (cell0 + i / MUBAR + 0.5 + gauss_offset(i % MUBAR)); }
+inline double level_height(double zmin, double zmax, int nz, int n) {
+    return std::cos(n * M_PI / (nz - 1)) * (-0.5 * (zmax - zmin)) + 0.5 * (zmin + zmax);
+}
 void quad_weights(double DX, double w[MUBAR]);
 int bc_rank(int bc);
 bool build_spline_class(int nc, double DX, double l_q, int bcl, int bcr, SplineClass &out, std::string &err);
@@ -294,6 +299,7 @@ struct sx_handle {
     void *eval_state = nullptr;               // sx_evaluate's vertical classes and device scratch, made on first use (sx_eval.hip)
     void *harm_state = nullptr;               // sx_harmonics' device scratch, made on first use (sx_harmonics.hip)
     void *reduce_state = nullptr;             // sx_reduce's work list, weights and ring-sum scratch, made on first use (sx_reduce.hip)
+    void *spec_state = nullptr;               // sx_spectrum's ring and level tables and scratch, made on first use (sx_spectrum.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
     std::vector<int> hcls;                    // host copy of d_cls: [v][2] -> class of (k = 0, k >= 1)
@@ -371,6 +377,10 @@ void harm_release(sx_handle *h);
 double harm_last_bytes(const sx_handle *h);   // A bytes the last sx_harmonics read
 void reduce_release(sx_handle *h);
 double reduce_last_bytes(const sx_handle *h);   // plane bytes the last sx_reduce read
+int default_bzdim(int zDim);                    // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)
+bool desc_ok(const sx_grid_desc *gd, const char *who);   // what every pure host helper refuses of a descriptor (sx_reduce.hip)
+void spec_release(sx_handle *h);
+double spec_last_bytes(const sx_handle *h);     // A bytes the last sx_spectrum read
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);
 void launch_rz_forward(sx_handle *h);

@@ -250,7 +250,7 @@ static ReduceState *reduce_state(sx_handle *h) {
     return st;
 }
 
-static bool desc_ok(const sx_grid_desc *gd, const char *who) {
+bool desc_ok(const sx_grid_desc *gd, const char *who) {
     if (!gd) { set_error(std::string(who) + ": null argument"); return false; }
     if (gd->abi_version != SX_ABI_VERSION) { set_error("sx_grid_desc.abi_version mismatch"); return false; }
     if (gd->geometry < SX_GEOM_R || gd->geometry > SX_GEOM_RLZ) { set_error("Unknown geometry"); return false; }

@@ -509,6 +509,18 @@ class ModelRun:
         rs, z = self._ring_axes
         return rs.copy(), z.copy(), np.concatenate(means, axis=0)
 
+    def spectrum(self, pairs, kind="ring"):
+        """Azimuthal power and cross spectra over the local tiles (Grid.spectrum; reads A: no transform is run).  kind="domain":
+        ndarray [kDim + 1, n_pairs], the tile results summed in tile order.  kind="ring": [kDim + 1, rings, n_pairs], the rings of
+        the local tiles concatenated in tile order (azimuthal_mean's ring axis)."""
+        parts = [g.spectrum(pairs, kind) for g in self._tiles_in_order()]
+        if kind == "ring":
+            return np.concatenate(parts, axis=1)
+        total = np.zeros_like(parts[0])
+        for p in parts:
+            total = total + p
+        return total
+
     def patch_spectral(self):
         """mtile.patchSpectral as the master pulls it from a worker for output (src/semiimplicit.jl:288-293): the patch's A
         coefficients [s_patch, V].  With the reference's protocol every tile holds the whole patch; with the transposed solve a

@@ -362,6 +362,22 @@ class Grid:
         c = out.T.view(np.complex128)                     # C-contiguous [s, v, ir, iz, 2K] -> [s, v, ir, iz, K]
         return c.transpose(2, 3, 4, 1, 0)
 
+    def spectrum(self, pairs, kind="ring"):
+        """Azimuthal power and cross spectra of the state on the device (sx_spectrum), from the A coefficients the tile holds now.
+        pairs: a list of ((var_a, slot_a), (var_b, slot_b)), var a name or a 1-based index, slot one of u r rr z zz or 0 .. 4 (the
+        slots of harmonics); a pair with a == b is a power spectrum; at most 16 pairs.  kind="ring": float64 ndarray
+        [kDim + 1, tile rings, n_pairs], sum_level w_z eps_k Re(c_k^a conj(c_k^b)) at every ring - the radius-wavenumber diagram.
+        kind="domain": [kDim + 1, n_pairs], the rings summed with 2 pi w_r: this tile's share of the domain integral per wavenumber.
+        The sum over k is what reduce gives for the product field(a) field(b) (Parseval)."""
+        packed = pack_spectrum_pairs(self.patch_params, pairs)
+        if kind not in L.SPEC_KIND:
+            raise ValueError("kind must be 'ring' or 'domain'")
+        K = int(self.dims.kDim) + 1
+        shape = (K, int(self.dims.tile_rDim), len(packed)) if kind == "ring" else (K, len(packed))
+        out = np.zeros(shape, order="F")
+        L.check(self._lib.sx_spectrum(self._h, L.SPEC_KIND[kind], len(packed), packed.ctypes.data_as(L.P_I32), out.ctypes.data_as(L.P_D)))
+        return out
+
     def reduce(self, terms, kind="domain", source="physical"):
         """Integrals or azimuthal means of field products on the device (sx_reduce).  terms: a list of
         (out, coef, r_power, [(var, slot), ...]): coef * r^r_power * the product of the named fields is added to output `out`; var a
@@ -622,6 +638,31 @@ def reduce_planes(patch: GridParameters, terms, source="physical", tile_cell0=0,
     L.check(L.load().sx_reduce_planes(C.byref(d), L.REDUCE_SOURCE[source], len(coef), packed.ctypes.data_as(L.P_I32), n_out,
                                       planes.ctypes.data_as(L.P_I32), C.byref(n)))
     return planes[:n.value].copy()
+
+
+# ----------------------------------------------------------------------------- azimuthal power and cross spectra (sx_spectrum)
+def pack_spectrum_pairs(patch: GridParameters, pairs):
+    """pairs -> int32 [n, 4] = var_a, slot_a, var_b, slot_b as sx_spectrum reads them; variable and slot names are resolved against
+    the patch, everything else is left to the library to refuse."""
+    packed = np.zeros((len(pairs), 4), dtype=np.int32)
+    for i, pair in enumerate(pairs):
+        if len(pair) != 2:
+            raise ValueError("pair %d is no ((var, slot), (var, slot))" % i)
+        for s, (var, slot) in enumerate(pair):
+            if isinstance(var, str) and var not in patch.vars:
+                raise ValueError("pair %d: unknown variable %r" % (i, var))
+            if isinstance(slot, str) and slot not in L.HARM_SLOTS:
+                raise ValueError("pair %d: %r is none of the slots %s" % (i, slot, L.HARM_SLOTS))
+            packed[i, 2 * s] = patch.vars[var] if isinstance(var, str) else int(var)
+            packed[i, 2 * s + 1] = L.HARM_SLOTS.index(slot) if isinstance(slot, str) else int(slot)
+    return packed
+
+
+def spectrum_check(patch: GridParameters, pairs, tile_cell0=0, tile_num_cells=None):
+    """Raises what Grid.spectrum would refuse of a pair list, on the host (sx_spectrum_check: no handle, no device)."""
+    d, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    packed = pack_spectrum_pairs(patch, pairs)
+    L.check(L.load().sx_spectrum_check(C.byref(d), len(packed), packed.ctypes.data_as(L.P_I32)))
 
 
 def invariants(model: ModelParameters):
