@@ -334,6 +334,47 @@ int sx_spectrum(sx_handle *h, int32_t kind, int32_t n_pairs, const int32_t *pair
 /* the validator sx_spectrum itself calls: refuses what sx_spectrum refuses of a pair list.  Pure host helper, no handle and no device */
 int sx_spectrum_check(const sx_grid_desc *grid, int32_t n_pairs, const int32_t *pairs);
 
+/* --- Lagrangian parcels ----------------------------------------------------------------------------------------------------
+ * Tracer points that move with the model on the device: positions, history and status live in device memory and one kernel launch
+ * (k_parcels) per step forms every weight from the positions, sums the velocity from A and moves the parcels.
+ * A parcel is a point (r[, lambda][, z]) in the coordinates of sx_get_gridpoints.  Three 1-based variable indices (var_r, var_l, var_z)
+ * name the velocity components; 0 = no motion along that coordinate; a non-zero index for a coordinate the geometry lacks is refused.
+ * All three are speeds (length per time): var_l is the tangential wind, not an angular rate.
+ * Velocity: the value slot of those variables at the parcel, summed from the A coefficients the handle holds now with the SX_EVAL_ALL_K
+ * truncation (smooth in r: a path sees no ring-to-ring jumps) and sx_evaluate's vertical series and boundary-condition projection:
+ * what sx_evaluate(..., SX_EVAL_ALL_K) returns in slot 0, up to rounding.
+ * Motion.  R / RZ: dx/dt = u, dz/dt = w.  RL / RLZ, in Cartesian form so that the centre is an ordinary point: X = r cos lambda,
+ * Y = r sin lambda, dX/dt = u cos lambda - v sin lambda, dY/dt = u sin lambda + v cos lambda, afterwards r = hypot(X, Y) and
+ * lambda = atan2(Y, X) kept in (-pi, pi]; at r == 0 lambda = 0.  The history holds the Cartesian velocity, not (u, v).
+ * Time stepping: every parcel counts its own steps - Euler, then AB2, from the third step AB3, with explicit_timestep's coefficients
+ * (src/semiimplicit.jl:672-698) - and every step makes one velocity evaluation.
+ * Leaving: a parcel whose update has r outside the tile's radial extent or z outside [zmin, zmax] stays at its last inside position and
+ * keeps a status, 0 active, 1 left radially, 2 left vertically (radially wins); it is never evaluated again.  Exception: on an R / RZ
+ * grid whose var_r variable has PERIODIC conditions on both sides x wraps into [xmin, xmax).
+ * One-tile patches are the intended use: a tile's parcels that cross its edge are frozen, not handed to the neighbour.
+ *
+ * sx_parcels_set creates or replaces the set (step counters 0); positions[n, n_coord] column-major.  n == 0 removes the set and frees
+ * its memory.  Refused before anything is touched - an existing set stays as it is: a NaN / Inf coordinate, an r or z out of range, a
+ * variable index out of range or for a missing coordinate, a null pointer with n > 0.  lambda may be any finite real; it is reduced
+ * into (-pi, pi] in extended precision on the host.
+ * sx_parcels_advance enqueues ONE kernel on the handle's stream and returns: no allocation, no copy, no synchronisation.  It reads A and
+ * the parcel arrays and writes the parcel arrays only: `physical`, var_np1, the tendency history, the B arrays and captured graphs stay
+ * as they are (a deferred diagnostic variable that is a velocity component is brought up to date first, as for every reader of A).
+ * A non-finite dt is refused; without a set the call succeeds and does nothing.  A parcel's path does not depend on how many other
+ * parcels the set holds or on their order (bitwise): which lane sums which column, and the order of the reduction, follow from the grid.
+ * sx_parcels_get synchronises and copies out positions[n, n_coord], the velocity last evaluated [n, n_coord] (u[, v][, w], zero for an
+ * index 0) and status[n]; any pointer may be NULL.  sx_parcels_count gives n (0 without a set).
+ * sx_parcels_get_state / sx_parcels_set_state: positions, velocity, both history levels, counters, status and the three variable
+ * indices as an opaque blob of sx_parcels_state_size doubles (0 without a set) for a handle created from the same descriptors; a run
+ * resumed from it (together with sx_set_state) continues bitwise.  sx_kernel_bytes("k_parcels") gives the A bytes of the last advance. */
+int sx_parcels_set(sx_handle *h, int64_t n, const double *positions, int32_t var_r, int32_t var_l, int32_t var_z);
+int sx_parcels_count(const sx_handle *h, int64_t *n);
+int sx_parcels_advance(sx_handle *h, double dt);
+int sx_parcels_get(sx_handle *h, double *positions, double *velocity, int32_t *status);
+int sx_parcels_state_size(const sx_handle *h, int64_t *n_doubles);
+int sx_parcels_get_state(sx_handle *h, double *out);
+int sx_parcels_set_state(sx_handle *h, const double *in, int64_t n_doubles);
+
 /* --- integrals and azimuthal means of field products ------------------------------------------------------------------
  * On-device diagnostics: budgets and azimuthal means / eddy covariances without pulling `physical` to the host.
  * Integrand program: n_terms <= 64 monomial terms feed n_out <= 16 outputs.  Term t is

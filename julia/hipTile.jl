@@ -203,6 +203,44 @@ function spectrumDevice(mtile::HipModelTile, pairs::Matrix{Int32}; domain::Bool 
     return out
 end
 
+# Lagrangian parcels (sx_parcels_*): tracer points that live on the device and move with the model's Adams-Bashforth scheme.
+# points[n, n_coord] with columns r[, lambda][, z]; var_r / var_l / var_z = 1-based variable index of the velocity component along
+# each coordinate (speeds; var_l the tangential wind), 0 = no motion.  An empty points matrix removes the set
+function setParcels!(mtile::HipModelTile, points::Matrix{Float64}; var_r::Integer = 0, var_l::Integer = 0, var_z::Integer = 0)
+    sxcheck(ccall((:sx_parcels_set, libsx), Cint, (Ptr{Cvoid}, Int64, Ptr{Float64}, Int32, Int32, Int32),
+                  mtile.handle, size(points, 1), points, var_r, var_l, var_z))
+end
+
+# one step of every active parcel from the A coefficients the tile holds now: ONE kernel on the tile's stream, no synchronisation.
+# Call it BEFORE advanceTimestep of the same step, so that the parcels see the A of time n
+function advanceParcels!(mtile::HipModelTile, dt::Float64)
+    sxcheck(ccall((:sx_parcels_advance, libsx), Cint, (Ptr{Cvoid}, Float64), mtile.handle, dt))
+end
+
+# (positions [n, n_coord], velocity last evaluated [n, n_coord], status [n]: 0 active, 1 left radially, 2 left vertically)
+function getParcels(mtile::HipModelTile)
+    d = Ref{SxDims}()
+    sxcheck(ccall((:sx_get_dims, libsx), Cint, (Ptr{Cvoid}, Ref{SxDims}), mtile.handle, d))
+    n = Ref{Int64}(0)
+    sxcheck(ccall((:sx_parcels_count, libsx), Cint, (Ptr{Cvoid}, Ref{Int64}), mtile.handle, n))
+    pos, vel, status = zeros(Float64, n[], d[].n_coord), zeros(Float64, n[], d[].n_coord), zeros(Int32, n[])
+    sxcheck(ccall((:sx_parcels_get, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), mtile.handle, pos, vel, status))
+    return pos, vel, status
+end
+
+# restart blob of the parcel set (beside sx_get_state's blob of the model): a run resumed from both continues bitwise
+function getParcelState(mtile::HipModelTile)
+    n = Ref{Int64}(0)
+    sxcheck(ccall((:sx_parcels_state_size, libsx), Cint, (Ptr{Cvoid}, Ref{Int64}), mtile.handle, n))
+    blob = zeros(Float64, n[])
+    n[] > 0 && sxcheck(ccall((:sx_parcels_get_state, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}), mtile.handle, blob))
+    return blob
+end
+
+function setParcelState!(mtile::HipModelTile, blob::Vector{Float64})
+    sxcheck(ccall((:sx_parcels_set_state, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64), mtile.handle, blob, length(blob)))
+end
+
 function patchSpectral(mtile::HipModelTile)
     sxcheck(ccall((:sx_get_patch_spectral_a, libsx), Cint, (Ptr{Cvoid}, Ptr{Float64}),
                   mtile.handle, mtile.patchSpectral))

@@ -8,6 +8,6 @@ from .model import (CubicBSpline, Chebyshev, GridParameters, ModelParameters, Gr
                     spectrum_check, pack_spectrum_pairs)
 from .driver import (PatchLayout, LocalExchange, DistExchange, A2ALayout, LocalA2AExchange, DistA2AExchange, LibExchange, LocalLibExchange, ModelRun,
                      integrate_model)
-from .io import read_physical_grid, write_output, write_gridded_output
+from .io import read_physical_grid, write_output, write_gridded_output, write_parcels
 from . import thermodynamics, reference_state
 from .reference_state import ReferenceState, Chebyshev1D

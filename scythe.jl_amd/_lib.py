@@ -116,6 +116,13 @@ SYMBOLS = {
     "sx_harmonics": (C.c_int, [_H, P_D, C.c_int32, P_D, C.c_int32, C.c_int32, C.c_int32, P_D]),
     "sx_spectrum": (C.c_int, [_H, C.c_int32, C.c_int32, P_I32, P_D]),
     "sx_spectrum_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, P_I32]),
+    "sx_parcels_set": (C.c_int, [_H, C.c_int64, P_D, C.c_int32, C.c_int32, C.c_int32]),
+    "sx_parcels_count": (C.c_int, [_H, P_I64]),
+    "sx_parcels_advance": (C.c_int, [_H, C.c_double]),
+    "sx_parcels_get": (C.c_int, [_H, P_D, P_D, P_I32]),
+    "sx_parcels_state_size": (C.c_int, [_H, P_I64]),
+    "sx_parcels_get_state": (C.c_int, [_H, P_D]),
+    "sx_parcels_set_state": (C.c_int, [_H, P_D, C.c_int64]),
     "sx_reduce": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D]),
     "sx_reduce_weights": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, P_D]),
     "sx_reduce_planes": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32, P_I32]),

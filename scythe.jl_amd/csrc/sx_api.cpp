@@ -734,6 +734,7 @@ int sx_destroy(sx_handle *h) {
     harm_release(h);
     reduce_release(h);
     spec_release(h);
+    parcels_release(h);
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -1438,6 +1439,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_evaluate") b = eval_last_bytes(h);                  // the last call's batches x 4 rows x live columns of A
     else if (k == "k_harmonics") b = harm_last_bytes(h);                // the last call's radii x 4 rows x b_zDim x (2 kcap + 1) of A
     else if (k == "k_spectrum") b = spec_last_bytes(h);                  // the last call's rings x distinct planes x 4 rows x b_zDim x (2 kmax + 1) of A
+    else if (k == "k_parcels") b = parcels_last_bytes(h);                // the last advance's parcels x velocity variables x 4 rows x b_zDim x (2 kDim + 1) of A
     else if (k == "k_reduce") b = reduce_last_bytes(h);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
     *bytes = b;
     return 0;

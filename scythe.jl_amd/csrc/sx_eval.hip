@@ -175,8 +175,8 @@ EvalGeom eval_geom_of(const sx_handle *h) {
     return g;
 }
 
-// what both entry points refuse; coordinates r[, lambda][, z]
-static bool point_ok(const EvalGeom &g, double r, double lam, double z, std::string &why) {
+// what both entry points (and sx_parcels_set) refuse; coordinates r[, lambda][, z]
+bool eval_point_ok(const EvalGeom &g, double r, double lam, double z, std::string &why) {
     if (!std::isfinite(r) || !std::isfinite(lam) || !std::isfinite(z)) { why = "a coordinate is NaN or Inf"; return false; }
     if (!(r >= g.tile_lo() && r <= g.tile_hi())) {
         why = "r = " + std::to_string(r) + " outside the tile's extent [" + std::to_string(g.tile_lo()) + ", " + std::to_string(g.tile_hi()) + "]";
@@ -241,9 +241,10 @@ static EvalState *eval_state(sx_handle *h) {
 }
 
 // the vertical classes and the per-variable class table (device), for sx_harmonics
-bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls) {
+bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls, const std::vector<int> **vcls) {
     EvalState *st = eval_state(h);
     if (!st) return false;
+    if (vcls) *vcls = &st->vcls;
     vert = &st->vert;
     d_vcls = st->d_vcls;
     return true;
@@ -347,7 +348,7 @@ static int evaluate_band(sx_handle *h, const double *points, int64_t n_points, i
     std::string why;
     for (int64_t i = 0; i < n_points; i++) {
         const double lam = h->has_l ? points[n_points + i] : 0.0, z = h->has_z ? points[(int64_t)(h->ncoord - 1) * n_points + i] : 0.0;
-        if (!point_ok(g, points[i], lam, z, why)) { set_error("sx_evaluate: point " + std::to_string(i) + ": " + why); return 1; }
+        if (!eval_point_ok(g, points[i], lam, z, why)) { set_error("sx_evaluate: point " + std::to_string(i) + ": " + why); return 1; }
     }
     EvalState *st = eval_state(h);
     if (!st) return 1;
@@ -404,7 +405,7 @@ int sx_eval_basis(const sx_grid_desc *gd, int32_t var, const double *point, int3
     }
     const double r = point[0], lam = g.has_l ? point[1] : 0.0, z = g.has_z ? point[1 + g.has_l] : 0.0;
     std::string why;
-    if (!point_ok(g, r, lam, z, why)) { set_error("sx_eval_basis: " + why); return 1; }
+    if (!eval_point_ok(g, r, lam, z, why)) { set_error("sx_eval_basis: " + why); return 1; }
     int n0;
     double w[3][4];
     eval_radial(g, r, n0, w);

@@ -132,6 +132,15 @@ struct CellConsts {
     int gcell0;           // patch index of the tile's first cell
 };
 
+// explicit_timestep (src/semiimplicit.jl:672-698): var_np1 from the value u, its tendency e and the tendencies e1, e2 of the two
+// steps before (Euler at t = 1, AB2 at t = 2, AB3 from then on).  Stated once: the equation-set kernels (sx_physics.hip) and the
+// parcel kernel (sx_parcels.hip) step with it.
+__device__ __forceinline__ double ab_value(int t, double ts, double u, double e, double e1, double e2) {
+    if (t == 1) return u + (ts * e);
+    if (t == 2) return u + (0.5 * ts) * ((3.0 * e) - e1);
+    return u + ((ts / 12.0) * ((23.0 * e) - (16.0 * e1) + (5.0 * e2)));
+}
+
 struct ColJob {
     int64_t in_off, out_off, mat_off;
 };
@@ -299,6 +308,7 @@ struct sx_handle {
     void *eval_state = nullptr;               // sx_evaluate's vertical classes and device scratch, made on first use (sx_eval.hip)
     void *harm_state = nullptr;               // sx_harmonics' device scratch, made on first use (sx_harmonics.hip)
     void *reduce_state = nullptr;             // sx_reduce's work list, weights and ring-sum scratch, made on first use (sx_reduce.hip)
+    void *parcel_state = nullptr;             // the parcel set and the vertical operators of its kernel (sx_parcels.hip)
     void *spec_state = nullptr;               // sx_spectrum's ring and level tables and scratch, made on first use (sx_spectrum.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
@@ -372,7 +382,11 @@ void pcr_release(sx_handle *h);
 void eval_release(sx_handle *h);
 double eval_last_bytes(const sx_handle *h);   // A bytes the last sx_evaluate read
 EvalGeom eval_geom_of(const sx_handle *h);
-bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls);   // sx_evaluate's vertical classes, made on first use
+bool eval_point_ok(const EvalGeom &g, double r, double lam, double z, std::string &why);   // what sx_evaluate refuses of a point
+void parcels_release(sx_handle *h);
+double parcels_last_bytes(const sx_handle *h);   // A bytes of the last sx_parcels_advance
+// sx_evaluate's vertical classes, made on first use; vcls: the host copy of the per-variable class table
+bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls, const std::vector<int> **vcls = nullptr);
 void harm_release(sx_handle *h);
 double harm_last_bytes(const sx_handle *h);   // A bytes the last sx_harmonics read
 void reduce_release(sx_handle *h);

@@ -38,14 +38,7 @@ struct PhysArgsT {
 template <class A>
 __device__ __forceinline__ void diag_step(const A &a, int v, int64_t p, double u) { a.np1[(int64_t)v * a.N + p] = u; }
 
-// explicit_timestep (src/semiimplicit.jl:672-698): var_np1 from the value u, its tendency e and the tendencies e1, e2 of the two
-// steps before (Euler at t = 1, AB2 at t = 2, AB3 from then on)
-__device__ __forceinline__ double ab_value(int t, double ts, double u, double e, double e1, double e2) {
-    if (t == 1) return u + (ts * e);
-    if (t == 2) return u + (0.5 * ts) * ((3.0 * e) - e1);
-    return u + ((ts / 12.0) * ((23.0 * e) - (16.0 * e1) + (5.0 * e2)));
-}
-// the same with its loads and stores; history arrays are rotated by the host instead of copied
+// explicit_timestep: ab_value (sx_internal.hpp, shared with the parcel kernel) with its loads and stores; history arrays are rotated by the host instead of copied
 template <class A>
 __device__ __forceinline__ double ab_step(const A &a, int v, int64_t p, double u, double en) {
     const int64_t o = (int64_t)v * a.N + p;

@@ -362,6 +362,7 @@ class ModelRun:
                 raise ValueError("exchange must be 'a2a', 'iface' or 'gather'")
         self.t = 0
         self._ring_axes = None      # azimuthal_mean's (r, z) axes, formed on first use
+        self._parcels = False       # set_parcels attached a parcel set: step() moves it
 
     def _bind_streams(self, device):
         """Kernels of a tile run on ITS stream; torch's collectives order themselves against torch's CURRENT stream.  Hand
@@ -412,6 +413,12 @@ class ModelRun:
     def step(self):
         """One pass of model_loop's body (src/semiimplicit.jl:268-297) without the output branch."""
         self.t += 1
+        if self._parcels:
+            # the parcels move with the A of time n: their kernel goes on the tile's stream BEFORE the step, whose banded solve - the
+            # only writer of A, on that same stream - therefore follows it; with SX_OVERLAP=1 the second stream forks after it and
+            # never writes A (DESIGN.md 12)
+            self._check_stream()
+            self.tiles[0].advance_parcels(self.model.ts)
         if self.num_tiles == 1 and self.exchange is None:
             self._check_stream()
             self.tiles[0].step(self.t)          # sx_step = sx_advance + sx_spline_transform (one hipGraph launch with SX_GRAPH=1)
@@ -449,6 +456,19 @@ class ModelRun:
                 out[sel] = g.evaluate(p[sel], all_k, k_band)
                 held[sel] = True
         return out, held
+
+    def set_parcels(self, points, velocity):
+        """Attach Lagrangian parcels to the run (Grid.set_parcels): from now on step() moves them with the model's time step, from the
+        A coefficients of time n, before the step rewrites A.  One-tile patches only: a parcel that crosses a tile edge would have
+        to be handed to the neighbour, which is not implemented."""
+        if self.num_tiles > 1:
+            raise ValueError("set_parcels: one-tile patches only (num_tiles = %d): parcels are not handed across tiles" % self.num_tiles)
+        self.tiles[0].set_parcels(points, velocity)
+        self._parcels = self.tiles[0].n_parcels > 0
+
+    def parcels(self):
+        """(positions, velocity, status) of the run's parcels (Grid.parcels)"""
+        return self.tiles[0].parcels()
 
     def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
         """Grid.harmonics over the local tiles: every radius goes to the local tile that contains it (a shared edge to the lower
@@ -555,7 +575,12 @@ class ModelRun:
         """Restart file of the local tiles after step self.t (one .npz; with one process per GPU every rank writes its
         own path).  The reference restarts from a physical_out CSV only, i.e. with an Euler / AB2 start-up; this keeps
         the AB3 history so that the continued run is bit-identical to an uninterrupted one."""
-        np.savez(path, t=self.t, tile_ids=np.array(self.tile_ids), **{"tile%d" % i: g.get_state() for i, g in zip(self.tile_ids, self.tiles)})
+        extra = {"tile%d" % i: g.get_state() for i, g in zip(self.tile_ids, self.tiles)}
+        for i, g in zip(self.tile_ids, self.tiles):       # a parcel set travels with its tile; without one the file is what it always was
+            blob = g.get_parcel_state()
+            if blob is not None:
+                extra["parcels%d" % i] = blob
+        np.savez(path, t=self.t, tile_ids=np.array(self.tile_ids), **extra)
 
     def load_checkpoint(self, path):
         with np.load(path) as z:
@@ -563,6 +588,11 @@ class ModelRun:
                 raise ValueError("checkpoint holds tiles %s, this run holds %s" % (list(z["tile_ids"]), self.tile_ids))
             for i, g in zip(self.tile_ids, self.tiles):
                 g.set_state(z["tile%d" % i])
+                if "parcels%d" % i in z.files:
+                    g.set_parcel_state(z["parcels%d" % i])
+                else:
+                    g.set_parcels(np.zeros((0, len(self.patch.geometry))), [None] * len(self.patch.geometry))
+            self._parcels = any(g.n_parcels > 0 for g in self.tiles)
             self.t = int(z["t"])
 
     def close(self):

@@ -118,3 +118,16 @@ def write_gridded_output(run, model, time, points, names=None):
     header = _COORD[gp.geometry] + [n + _SUFFIX[s] for s in slots for n in names]
     np.savetxt(path, arr, delimiter=",", header=",".join(header), comments="", fmt="%.17g")
     return path
+
+
+def write_parcels(run, time):
+    """The run's Lagrangian parcels (ModelRun.parcels) as parcels_out_<tag>.csv beside physical_out_<tag>.csv: one row per parcel,
+    the coordinate columns r[, l][, z], the velocity last evaluated as vel_r[, vel_l][, vel_z], and status (0 active, 1 left
+    radially, 2 left vertically)."""
+    model = run.model
+    coord = _COORD[model.grid_params.geometry]
+    pos, vel, status = run.parcels()
+    path = os.path.join(model.output_dir, "parcels_out_%s.csv" % output_time_tag(time))
+    arr = np.concatenate([pos, vel, status[:, None].astype(np.float64)], axis=1)
+    np.savetxt(path, arr, delimiter=",", header=",".join(coord + ["vel_" + c for c in coord] + ["status"]), comments="", fmt="%.17g")
+    return path

@@ -341,6 +341,67 @@ class Grid:
                                                out.ctypes.data_as(L.P_D)))
         return out
 
+    # -- Lagrangian parcels (sx_parcels_*)
+    def _parcel_var(self, v):
+        """1-based variable index of a velocity component given by name, by 1-based index, or None / 0 (no motion)"""
+        if v is None or (isinstance(v, (int, np.integer)) and int(v) == 0):
+            return 0
+        if isinstance(v, str):
+            names = self.patch_params.var_names()
+            if v not in names:
+                raise ValueError("velocity variable %r is not one of %s" % (v, names))
+            return names.index(v) + 1
+        return int(v)
+
+    def set_parcels(self, points, velocity):
+        """Create or replace the tile's parcel set: points [n, n_coord] with columns r[, lambda][, z] as getGridpoints returns them,
+        velocity = one entry per coordinate, in that order (R: (u,), RZ: (u, w), RL: (u, v), RLZ: (u, v, w)), each a variable name, a
+        1-based variable index, or None / 0 for no motion along that coordinate.  The components are speeds: the azimuthal one is
+        the tangential wind.  An empty `points` removes the set.  Refusals leave an existing set as it is (sx_parcels_set)."""
+        nc = int(self.dims.n_coord)
+        p = np.asarray(points, dtype=np.float64)
+        p = np.asfortranarray(p.reshape(-1, nc) if p.ndim != 2 else p)
+        if p.shape[1] != nc:
+            raise ValueError("points must have %d coordinate column(s)" % nc)
+        vel = [velocity] if isinstance(velocity, (str, int, np.integer)) or velocity is None else list(velocity)
+        if len(vel) != nc:
+            raise ValueError("velocity must name %d component(s), one per coordinate of a %s grid" % (nc, self.patch_params.geometry))
+        var = dict(zip(self.patch_params.geometry.lower(), (self._parcel_var(v) for v in vel)))
+        L.check(self._lib.sx_parcels_set(self._h, p.shape[0], p.ctypes.data_as(L.P_D), var.get("r", 0), var.get("l", 0), var.get("z", 0)))
+
+    def advance_parcels(self, dt):
+        """One step of every active parcel with the A coefficients the tile holds now: one kernel on the tile's stream, no
+        synchronisation (sx_parcels_advance).  Without a set it does nothing."""
+        L.check(self._lib.sx_parcels_advance(self._h, float(dt)))
+
+    @property
+    def n_parcels(self):
+        n = C.c_int64(0)
+        L.check(self._lib.sx_parcels_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def parcels(self):
+        """(positions [n, n_coord], velocity [n, n_coord] as last evaluated, status [n] int32: 0 active, 1 left radially, 2 left
+        vertically); empty arrays without a set.  Synchronises."""
+        n, nc = self.n_parcels, int(self.dims.n_coord)
+        pos, vel, st = np.zeros((n, nc), order="F"), np.zeros((n, nc), order="F"), np.zeros(n, dtype=np.int32)
+        L.check(self._lib.sx_parcels_get(self._h, pos.ctypes.data_as(L.P_D), vel.ctypes.data_as(L.P_D), st.ctypes.data_as(L.P_I32)))
+        return pos, vel, st
+
+    def get_parcel_state(self):
+        """Restart blob of the parcel set (sx_parcels_get_state), or None without a set"""
+        n = C.c_int64(0)
+        L.check(self._lib.sx_parcels_state_size(self._h, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros(n.value)
+        L.check(self._lib.sx_parcels_get_state(self._h, out.ctypes.data_as(L.P_D)))
+        return out
+
+    def set_parcel_state(self, blob):
+        b = np.ascontiguousarray(blob, dtype=np.float64)
+        L.check(self._lib.sx_parcels_set_state(self._h, b.ctypes.data_as(L.P_D), b.size))
+
     def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
         """The azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: complex128 ndarray indexed
         [ir, iz, k, v, s], k = 0 .. kDim, s over `slots` in the order u, r, rr, z, zz (a view of the library's buffer).  The state is
