@@ -730,11 +730,7 @@ int sx_destroy(sx_handle *h) {
     comm_release(h);
     iface_release(h);
     pcr_release(h);
-    eval_release(h);
-    harm_release(h);
-    reduce_release(h);
-    spec_release(h);
-    parcels_release(h);
+    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels: their device memory goes with them
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -1410,6 +1406,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     const double out_planes = h->last_mask_full ? planes(h->mask_full_bits, h->mask_full_val) : planes(h->mask_eq_bits, h->mask_eq_val);
     const double eq_planes = planes(h->mask_eq_bits, h->mask_eq_val), node_planes = planes(h->mask_node_bits, h->mask_node_val);
     const bool node = h->node_mode && h->node_active;
+    auto diag_bytes = [&](int which) { return h->diag[which] ? h->diag[which]->last_bytes : 0.0; };
     const double fin = node ? (double)h->R_in / h->nrings : 1.0;   // fraction of rings on the ring-wise path
     // node-space units actually transformed and read: cell c of the outer rings combines nodes c .. c + 3 and the first such cell is
     // R_in / 3, so nodes [R_in / 3, nbt) - 132 of 174 at the bench grid; the nodes below feed the ring-wise inner rings only
@@ -1436,11 +1433,11 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_condensation") b = w * N * (6.0 + 3.0);       // read s, xi, mu, mu_c, mu_r, qss of var_np1; write s, mu, mu_c
     else if (k == "k_rz_inverse") b = w * S_tile + N * out_planes;       // read the tile's A rows, write the requested physical planes
     else if (k == "k_rz_forward") b = w * N * V + w * S_tile;            // read var_np1, write the tile's B rows
-    else if (k == "k_evaluate") b = eval_last_bytes(h);                  // the last call's batches x 4 rows x live columns of A
-    else if (k == "k_harmonics") b = harm_last_bytes(h);                // the last call's radii x 4 rows x b_zDim x (2 kcap + 1) of A
-    else if (k == "k_spectrum") b = spec_last_bytes(h);                  // the last call's rings x distinct planes x 4 rows x b_zDim x (2 kmax + 1) of A
-    else if (k == "k_parcels") b = parcels_last_bytes(h);                // the last advance's parcels x velocity variables x 4 rows x b_zDim x (2 kDim + 1) of A
-    else if (k == "k_reduce") b = reduce_last_bytes(h);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
+    else if (k == "k_evaluate") b = diag_bytes(DIAG_EVAL);                  // the last call's batches x 4 rows x live columns of A
+    else if (k == "k_harmonics") b = diag_bytes(DIAG_HARM);                // the last call's radii x 4 rows x b_zDim x (2 kcap + 1) of A
+    else if (k == "k_spectrum") b = diag_bytes(DIAG_SPEC);                  // the last call's rings x distinct planes x 4 rows x b_zDim x (2 kmax + 1) of A
+    else if (k == "k_parcels") b = diag_bytes(DIAG_PARCELS);                // the last advance's parcels x velocity variables x 4 rows x b_zDim x (2 kDim + 1) of A
+    else if (k == "k_reduce") b = diag_bytes(DIAG_REDUCE);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
     *bytes = b;
     return 0;
 }

@@ -1,7 +1,7 @@
 // sx_evaluate / sx_eval_basis: the spectral state sampled at arbitrary points (include/scythe_hip.h).
 //
 // u(r, lambda, z) = sum A[zm, blk, node] phi_node(r) F_blk(lambda) C_zm(z).  The host forms, per point, what depends on r and z
-// (the 4 radial weights of phi, phi', phi'', the wavenumber cap, the vertical weight rows: eval_radial / eval_kcap /
+// (the 4 radial weights of phi, phi', phi'', the wavenumber cap, the vertical weight rows: eval_radial_pt /
 // eval_vert_weights of sx_setup.cpp, the functions sx_eval_basis returns) and sorts the points by radial cell; the kernel does the
 // sum over A.  That sum reads 4 node rows x (2 kcap + 1) blocks x b_zDim modes per (point, variable) - 2 MB per point at the bench
 // grid - so a workgroup takes up to EVAL_P points of ONE cell and loads each A element once for all of them: threads stride over the
@@ -30,15 +30,11 @@ struct EvalPt {          // one point as the kernel reads it (sorted by cell)
 
 struct EvalSlots { int s[7]; };     // u r rr l ll z zz -> slot of `physical`, -1 = the geometry has none
 
-struct EvalState {
-    std::vector<EvalVert> vert;     // vertical boundary-condition classes
-    std::vector<int> vcls;          // [V] class of each variable
-    int *d_vcls = nullptr;
-    EvalPt *d_pts = nullptr;
-    int2 *d_batch = nullptr;
-    double *d_wz = nullptr, *d_res = nullptr;
-    size_t cap_pts = 0, cap_batch = 0, cap_wz = 0, cap_res = 0;
-    double last_bytes = 0;
+struct EvalState : DiagState {
+    EvalClasses cls;
+    DevBuf<EvalPt> d_pts;
+    DevBuf<int2> d_batch;
+    DevBuf<double> d_wz, d_res;
 };
 
 // 2 pi as a double and the remainder, for the reduction of k lambda
@@ -168,20 +164,20 @@ __global__ __launch_bounds__(EVAL_T) void k_evaluate(const double *__restrict__ 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-EvalGeom eval_geom_of(const sx_handle *h) {
-    EvalGeom g;
-    g.has_l = h->has_l; g.has_z = h->has_z; g.nc = h->nc; g.cell0 = h->cell0; g.ncells = h->ncells; g.uniform_L = h->uniform_L;
-    g.kDim = h->kDim; g.nz = h->nz; g.Zb = h->Zb; g.xmin = h->xmin; g.xmax = h->xmax; g.DX = h->DX; g.zmin = h->zmin; g.zmax = h->zmax;
-    return g;
-}
+// what both entry points (and sx_parcels_set, sx_harmonics) refuse; coordinates r[, lambda][, z]
+static const char *const NOT_FINITE = "a coordinate is NaN or Inf";
 
-// what both entry points (and sx_parcels_set) refuse; coordinates r[, lambda][, z]
-bool eval_point_ok(const EvalGeom &g, double r, double lam, double z, std::string &why) {
-    if (!std::isfinite(r) || !std::isfinite(lam) || !std::isfinite(z)) { why = "a coordinate is NaN or Inf"; return false; }
+bool eval_radius_ok(const EvalGeom &g, double r, std::string &why) {
+    if (!std::isfinite(r)) { why = NOT_FINITE; return false; }
     if (!(r >= g.tile_lo() && r <= g.tile_hi())) {
         why = "r = " + std::to_string(r) + " outside the tile's extent [" + std::to_string(g.tile_lo()) + ", " + std::to_string(g.tile_hi()) + "]";
         return false;
     }
+    return true;
+}
+
+bool eval_height_ok(const EvalGeom &g, double z, std::string &why) {
+    if (!std::isfinite(z)) { why = NOT_FINITE; return false; }
     if (g.has_z && !(z >= g.zmin && z <= g.zmax)) {
         why = "z = " + std::to_string(z) + " outside [" + std::to_string(g.zmin) + ", " + std::to_string(g.zmax) + "]";
         return false;
@@ -189,65 +185,51 @@ bool eval_point_ok(const EvalGeom &g, double r, double lam, double z, std::strin
     return true;
 }
 
-void eval_release(sx_handle *h) {
-    EvalState *st = (EvalState *)h->eval_state;
-    if (!st) return;
-    hipFree(st->d_vcls); hipFree(st->d_pts); hipFree(st->d_batch); hipFree(st->d_wz); hipFree(st->d_res);
-    delete st;
-    h->eval_state = nullptr;
+static bool eval_point_ok(const EvalGeom &g, double r, double lam, double z, std::string &why) {
+    if (!std::isfinite(r) || !std::isfinite(lam) || !std::isfinite(z)) { why = NOT_FINITE; return false; }      // before any range
+    return eval_radius_ok(g, r, why) && eval_height_ok(g, z, why);
 }
 
-double eval_last_bytes(const sx_handle *h) { return h->eval_state ? ((const EvalState *)h->eval_state)->last_bytes : 0.0; }
-
-template <class T>
-static bool grow(T **p, size_t &cap, size_t need) {
-    if (need <= cap) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr; cap = 0;
-    const size_t n = need + need / 4;
-    if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) { set_error("sx_evaluate: hipMalloc of the scratch failed"); return false; }
-    cap = n;
+// every point of pts [n_coord][n] lies in the tile; a refusal reads "<who>: <noun> i: <why>"
+bool eval_points_ok(const sx_handle *h, const double *pts, int64_t n, const char *who, const char *noun) {
+    const EvalGeom g = eval_geom_of(h);
+    std::string why;
+    for (int64_t i = 0; i < n; i++) {
+        const double lam = h->has_l ? pts[n + i] : 0.0, z = h->has_z ? pts[(int64_t)(h->ncoord - 1) * n + i] : 0.0;
+        if (!eval_point_ok(g, pts[i], lam, z, why)) { set_error(std::string(who) + ": " + noun + " " + std::to_string(i) + ": " + why); return false; }
+    }
     return true;
 }
 
 static EvalState *eval_state(sx_handle *h) {
-    if (h->eval_state) return (EvalState *)h->eval_state;
-    EvalState *st = new EvalState();
-    st->vcls.assign(h->V, 0);
+    if (h->diag[DIAG_EVAL]) return diag_state<EvalState>(h, DIAG_EVAL);
+    std::unique_ptr<EvalState> st(new EvalState());
+    EvalClasses &k = st->cls;
+    k.vcls.assign(h->V, 0);
     std::string err;
     if (h->has_z) {
         for (int v = 0; v < h->V; v++) {
             int found = -1;
-            for (size_t c = 0; c < st->vert.size(); c++)
-                if (st->vert[c].bcb == h->bcb[v] && st->vert[c].bct == h->bct[v]) found = (int)c;
+            for (size_t c = 0; c < k.vert.size(); c++)
+                if (k.vert[c].bcb == h->bcb[v] && k.vert[c].bct == h->bct[v]) found = (int)c;
             if (found < 0) {
                 EvalVert ev;
-                if (!build_eval_vert(h->zmin, h->zmax, h->nz, h->Zb, h->bcb[v], h->bct[v], ev, err)) { set_error(err); delete st; return nullptr; }
-                st->vert.push_back(ev);
-                found = (int)st->vert.size() - 1;
+                if (!build_eval_vert(h->zmin, h->zmax, h->nz, h->Zb, h->bcb[v], h->bct[v], ev, err)) { set_error(err); return nullptr; }
+                k.vert.push_back(ev);
+                found = (int)k.vert.size() - 1;
             }
-            st->vcls[v] = found;
+            k.vcls[v] = found;
         }
     }
-    if (hipMalloc((void **)&st->d_vcls, sizeof(int) * h->V) != hipSuccess ||
-        hipMemcpy(st->d_vcls, st->vcls.data(), sizeof(int) * h->V, hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("sx_evaluate: hipMalloc of the scratch failed");
-        if (st->d_vcls) hipFree(st->d_vcls);
-        delete st;
-        return nullptr;
-    }
-    h->eval_state = st;
-    return st;
+    if (!k.d_vcls.upload(k.vcls, "sx_evaluate: hipMalloc of the scratch failed")) return nullptr;
+    h->diag[DIAG_EVAL] = std::move(st);
+    return diag_state<EvalState>(h, DIAG_EVAL);
 }
 
-// the vertical classes and the per-variable class table (device), for sx_harmonics
-bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls, const std::vector<int> **vcls) {
+// the vertical classes and the per-variable class table, for sx_harmonics, sx_spectrum and sx_parcels_set as well
+const EvalClasses *eval_classes(sx_handle *h) {
     EvalState *st = eval_state(h);
-    if (!st) return false;
-    if (vcls) *vcls = &st->vcls;
-    vert = &st->vert;
-    d_vcls = st->d_vcls;
-    return true;
+    return st ? &st->cls : nullptr;
 }
 
 static size_t eval_lds_bytes(int P, int csw, int Zb) {
@@ -257,7 +239,8 @@ static size_t eval_lds_bytes(int P, int csw, int Zb) {
 // one launch: the points [p0, p0 + n) of the call
 static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const double *points, int64_t n_all, int64_t p0, int n, int flags,
                        int kmin, int kband, double *out) {
-    const int ncls = std::max<int>(1, (int)st->vert.size()), Zb = h->has_z ? h->Zb : 1;
+    const std::vector<EvalVert> &vert = st->cls.vert;
+    const int ncls = std::max<int>(1, (int)vert.size()), Zb = h->has_z ? h->Zb : 1;
     const long double two_pi = 8.0L * atanl(1.0L);
     std::vector<EvalPt> pts(n);
     std::vector<double> wz;
@@ -268,10 +251,7 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
         const double lam = h->has_l ? points[n_all + p0 + i] : 0.0;
         const double z = h->has_z ? points[(int64_t)(h->ncoord - 1) * n_all + p0 + i] : 0.0;
         EvalPt &e = pts[i];
-        double w[3][4];
-        eval_radial(g, r, e.cell, w);
-        std::memcpy(e.wr, w, sizeof(w));
-        e.kcap = eval_kcap(g, r, flags);
+        eval_radial_pt(g, r, flags, e.wr, e.cell, e.kcap);
         const long double lr = remainderl((long double)lam, two_pi);
         e.lh = (double)lr;
         e.ll = (double)(lr - (long double)e.lh);
@@ -286,7 +266,7 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
                 const int row = (int)zrow.size();
                 zrow.emplace(key, row);
                 wz.resize((size_t)(row + 1) * ncls * 3 * Zb);
-                for (int c = 0; c < ncls; c++) eval_vert_weights(st->vert[c], h->zmin, h->zmax, h->nz, Zb, z, &wz[((size_t)row * ncls + c) * 3 * Zb]);
+                for (int c = 0; c < ncls; c++) eval_vert_weights(vert[c], h->zmin, h->zmax, h->nz, Zb, z, &wz[((size_t)row * ncls + c) * 3 * Zb]);
                 e.zi = row;
             } else {
                 e.zi = it->second;
@@ -311,8 +291,8 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
     }
     st->last_bytes += 8.0 * 4.0 * cols * h->V;
     const size_t nres = (size_t)n * h->V * h->D;
-    if (!grow(&st->d_pts, st->cap_pts, pts.size()) || !grow(&st->d_batch, st->cap_batch, batches.size()) ||
-        !grow(&st->d_wz, st->cap_wz, wz.size()) || !grow(&st->d_res, st->cap_res, nres))
+    const char *who = "sx_evaluate";
+    if (!st->d_pts.grow(pts.size(), who) || !st->d_batch.grow(batches.size(), who) || !st->d_wz.grow(wz.size(), who) || !st->d_res.grow(nres, who))
         return false;
     HIPCHK(hipMemcpyAsync(st->d_pts, pts.data(), sizeof(EvalPt) * pts.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(st->d_batch, batches.data(), sizeof(int2) * batches.size(), hipMemcpyHostToDevice, h->stream));
@@ -322,7 +302,7 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
     for (int m = 0; m < 7; m++) sl.s[m] = h->slot[m];
     timer_begin(h, timer_id(h, "k_evaluate"));
     hipLaunchKernelGGL(k_evaluate, dim3((unsigned)batches.size(), (unsigned)h->V), dim3(EVAL_T), eval_lds_bytes(P, csw, Zb), h->stream, h->d_A,
-                       h->C, st->d_pts, st->d_batch, st->d_wz, st->d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, kmin, kband, sl, st->d_res, (int64_t)n, h->V);
+                       h->C, st->d_pts, st->d_batch, st->d_wz, st->cls.d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, kmin, kband, sl, st->d_res, (int64_t)n, h->V);
     HIPCHK(hipGetLastError());
     timer_end(h);
     std::vector<double> res(nres);
@@ -344,12 +324,8 @@ static int evaluate_band(sx_handle *h, const double *points, int64_t n_points, i
     if (flags != SX_EVAL_RING_K && flags != SX_EVAL_ALL_K) { set_error("sx_evaluate: flags must be SX_EVAL_RING_K or SX_EVAL_ALL_K"); return 1; }
     if (n_points == 0) return 0;
     if (!points || !out) { set_error("sx_evaluate: null argument"); return 1; }
+    if (!eval_points_ok(h, points, n_points, "sx_evaluate", "point")) return 1;
     const EvalGeom g = eval_geom_of(h);
-    std::string why;
-    for (int64_t i = 0; i < n_points; i++) {
-        const double lam = h->has_l ? points[n_points + i] : 0.0, z = h->has_z ? points[(int64_t)(h->ncoord - 1) * n_points + i] : 0.0;
-        if (!eval_point_ok(g, points[i], lam, z, why)) { set_error("sx_evaluate: point " + std::to_string(i) + ": " + why); return 1; }
-    }
     EvalState *st = eval_state(h);
     if (!st) return 1;
     flush_diag(h);
@@ -378,40 +354,21 @@ int sx_evaluate_band(sx_handle *h, const double *points, int64_t n_points, int32
 int sx_eval_basis(const sx_grid_desc *gd, int32_t var, const double *point, int32_t flags, int32_t *node0, double *w_r, int32_t *kcap,
                   double *w_z) {
     clear_error();
-    if (!gd || !point) { set_error("sx_eval_basis: null argument"); return 1; }
-    if (gd->abi_version != SX_ABI_VERSION) { set_error("sx_grid_desc.abi_version mismatch"); return 1; }
-    if (gd->geometry < SX_GEOM_R || gd->geometry > SX_GEOM_RLZ) { set_error("Unknown geometry"); return 1; }
-    if (gd->num_cells < 3 || gd->nvars < 1 || !(gd->xmax > gd->xmin)) { set_error("invalid grid parameters"); return 1; }
-    if (gd->tile_cell0 < 0 || gd->tile_num_cells < 1 || gd->tile_cell0 + gd->tile_num_cells > gd->num_cells) { set_error("tile range outside the patch"); return 1; }
+    if (!point) { set_error("sx_eval_basis: null argument"); return 1; }
+    if (!desc_ok(gd, "sx_eval_basis")) return 1;
     if (var < 1 || var > gd->nvars) { set_error("sx_eval_basis: var is 1-based and at most nvars"); return 1; }
     if (flags != SX_EVAL_RING_K && flags != SX_EVAL_ALL_K) { set_error("sx_eval_basis: flags must be SX_EVAL_RING_K or SX_EVAL_ALL_K"); return 1; }
-    EvalGeom g;
-    g.has_l = gd->geometry == SX_GEOM_RL || gd->geometry == SX_GEOM_RLZ;
-    g.has_z = gd->geometry == SX_GEOM_RZ || gd->geometry == SX_GEOM_RLZ;
-    g.nc = gd->num_cells; g.cell0 = gd->tile_cell0; g.ncells = gd->tile_num_cells;
-    g.uniform_L = g.has_l ? gd->ring_uniform_L : 0;
-    g.xmin = gd->xmin; g.xmax = gd->xmax; g.DX = (gd->xmax - gd->xmin) / gd->num_cells;
-    for (int r = 0; r < MUBAR * g.nc; r++) {
-        int L, km;
-        double off;
-        ring_table(g.has_l, g.uniform_L, r + 1, L, km, off);
-        g.kDim = std::max(g.kDim, km);
-    }
-    if (g.has_z) {
-        g.nz = gd->zDim;
-        g.Zb = gd->b_zDim > 0 ? gd->b_zDim : std::min(gd->zDim, (2 * gd->zDim - 1) / 3 + 1);
-        g.zmin = gd->zmin; g.zmax = gd->zmax;
-        if (g.nz < 4 || g.Zb > g.nz || !(g.zmax > g.zmin)) { set_error("invalid vertical grid (need zDim >= 4, b_zDim <= zDim, zmax > zmin)"); return 1; }
-    }
+    const EvalGeom g = desc_geom(gd);
+    if (g.has_z && (g.nz < 4 || g.Zb > g.nz || !(g.zmax > g.zmin))) { set_error("invalid vertical grid (need zDim >= 4, b_zDim <= zDim, zmax > zmin)"); return 1; }
     const double r = point[0], lam = g.has_l ? point[1] : 0.0, z = g.has_z ? point[1 + g.has_l] : 0.0;
     std::string why;
     if (!eval_point_ok(g, r, lam, z, why)) { set_error("sx_eval_basis: " + why); return 1; }
-    int n0;
-    double w[3][4];
-    eval_radial(g, r, n0, w);
+    int n0, kc;
+    double w[12];
+    eval_radial_pt(g, r, flags, w, n0, kc);
     if (node0) *node0 = n0;
     if (w_r) std::memcpy(w_r, w, sizeof(w));
-    if (kcap) *kcap = eval_kcap(g, r, flags);
+    if (kcap) *kcap = kc;
     if (g.has_z && w_z) {
         // the class's extended-precision operators are built per call (the projection and two N x N x Zb products, O(N^3)): fine
         // for a helper that checks weights; sx_evaluate builds them once per handle

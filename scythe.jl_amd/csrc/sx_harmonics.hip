@@ -3,8 +3,8 @@
 // The A coefficients already are the decomposition: block 2k / 2k + 1 holds the real / imaginary part of wavenumber k, so
 //   c_k(r, z) = sum_node sum_zm (A[zm, 2k, node] + i A[zm, 2k + 1, node]) phi_node(r) Wz[zm](z)
 // is a radial spline evaluation times a vertical operator row - no Fourier transform, nothing but A is read.  The host forms what
-// depends on r (the 4 radial weights of phi, phi', phi'' and the wavenumber cap: eval_radial / eval_kcap, the functions sx_evaluate
-// uses) and on z (the rows of the vertical operator: eval_vert_weights), the kernel does the two sums:
+// depends on r (the 4 radial weights of phi, phi', phi'' and the wavenumber cap: eval_radial_pt, the function sx_evaluate
+// uses) and on z (the rows of the vertical operator, packed by height_tiles), the kernel does the two sums:
 //   stage 1, radial    s_d[zm][blk] = sum_{j < 4} w_d[j] A[cell + j][v, zm, blk]          d = phi, phi', phi''
 //   stage 2, vertical  out_slot[zj][blk] = sum_zm Wz_row[zj][zm] s_d[zm][blk]             a (n_z x b_zDim) (b_zDim x K2) product
 // A wave owns 16 blocks of one (radius, variable).  Stage 1 leaves s_d in registers in the B-operand layout of
@@ -22,16 +22,9 @@ namespace sx {
 constexpr int HARM_T = 256;                         // 4 waves x 16 blocks
 constexpr size_t HARM_SCRATCH = (size_t)256 << 20;  // device result bytes per launch aimed at (one radius always fits)
 
-struct HarmPt {          // one radius as the kernel reads it (sorted by cell)
-    double wr[12];       // [3][4] phi, phi', phi'' at nodes cell .. cell + 3
-    int cell, kcap, orig, pad;   // patch row of the first node; wavenumber cap; index in the chunk
-};
-
-struct HarmState {
-    HarmPt *d_pts = nullptr;
-    double *d_wz = nullptr, *d_res = nullptr;
-    size_t cap_pts = 0, cap_wz = 0, cap_res = 0;
-    double last_bytes = 0;
+struct HarmState : DiagState {
+    DevBuf<RadialPt> d_pts;         // the radii of a launch, sorted by cell
+    DevBuf<double> d_wz, d_res;
 };
 
 typedef double harm_d4 __attribute__((ext_vector_type(4)));
@@ -40,7 +33,7 @@ typedef double harm_d4 __attribute__((ext_vector_type(4)));
 // wz [cls][height tile][row 3][Zp][16 heights], Zp = b_zDim rounded up to 4: a tile is one contiguous piece, and the A operand of
 // K step ks, row `row` is tile[row Zp 16 + 64 ks + lane].  res [slot][v][radius][height][KO].
 template <int KS, bool DR>
-__global__ __launch_bounds__(HARM_T) void k_harmonics(const double *__restrict__ A, int64_t C, const HarmPt *__restrict__ pts,
+__global__ __launch_bounds__(HARM_T) void k_harmonics(const double *__restrict__ A, int64_t C, const RadialPt *__restrict__ pts,
                                                       const double *__restrict__ wz, const int *__restrict__ vcls, int nht, int Zb,
                                                       int K2, int KO, int has_l, int mask, int nz, int nrc, int V,
                                                       double *__restrict__ res) {
@@ -48,7 +41,7 @@ __global__ __launch_bounds__(HARM_T) void k_harmonics(const double *__restrict__
     __shared__ double tile[3 * KS * 4 * 16];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, kk = lane >> 4;
     const int v = blockIdx.z, Zp = (Zb + 3) & ~3;
-    const HarmPt *__restrict__ pt = pts + blockIdx.y;
+    const RadialPt *__restrict__ pt = pts + blockIdx.y;
     const int cell = pt->cell, live = has_l ? 2 * pt->kcap + 1 : 0, orig = pt->orig;
     const int blk = (blockIdx.x * 4 + wave) * 16 + n;
     const bool on = blk < K2 && blk <= live && blk != 1;       // block 1 is the padding block: never read
@@ -106,27 +99,6 @@ __global__ __launch_bounds__(HARM_T) void k_harmonics(const double *__restrict__
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-void harm_release(sx_handle *h) {
-    HarmState *st = (HarmState *)h->harm_state;
-    if (!st) return;
-    hipFree(st->d_pts); hipFree(st->d_wz); hipFree(st->d_res);
-    delete st;
-    h->harm_state = nullptr;
-}
-
-double harm_last_bytes(const sx_handle *h) { return h->harm_state ? ((const HarmState *)h->harm_state)->last_bytes : 0.0; }
-
-template <class T>
-static bool harm_grow(T **p, size_t &cap, size_t need) {
-    if (need <= cap) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr; cap = 0;
-    const size_t n = need + need / 4;
-    if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) { set_error("sx_harmonics: hipMalloc of the scratch failed"); return false; }
-    cap = n;
-    return true;
-}
-
 struct HarmLaunch {
     const double *wz;
     const int *vcls;
@@ -147,20 +119,17 @@ static void harm_launch_ks(sx_handle *h, HarmState *st, const HarmLaunch &a, int
 // one launch: the radii [r0, r0 + n) of the call; tmp [KO, nz, n_r, V, nslots] column-major
 static bool harm_chunk(sx_handle *h, HarmState *st, const EvalGeom &g, const double *radii, int n_all, int r0, int n, int flags,
                        const HarmLaunch &a, double *tmp) {
-    std::vector<HarmPt> pts(n);
+    std::vector<RadialPt> pts(n);
     for (int i = 0; i < n; i++) {
-        HarmPt &e = pts[i];
-        double w[3][4];
-        eval_radial(g, radii[r0 + i], e.cell, w);
-        std::memcpy(e.wr, w, sizeof(w));
-        e.kcap = eval_kcap(g, radii[r0 + i], flags);
+        RadialPt &e = pts[i];
+        eval_radial_pt(g, radii[r0 + i], flags, e.wr, e.cell, e.kcap);
         e.orig = i;
         e.pad = 0;
         st->last_bytes += 8.0 * 4.0 * a.Zb * (h->has_l ? 2 * e.kcap + 1 : 1) * h->V;
     }
     // by cell (neighbouring workgroups then read the same 4 rows); within a cell the caller's order
-    std::stable_sort(pts.begin(), pts.end(), [](const HarmPt &x, const HarmPt &y) { return x.cell < y.cell; });
-    HIPCHK(hipMemcpyAsync(st->d_pts, pts.data(), sizeof(HarmPt) * n, hipMemcpyHostToDevice, h->stream));
+    std::stable_sort(pts.begin(), pts.end(), [](const RadialPt &x, const RadialPt &y) { return x.cell < y.cell; });
+    HIPCHK(hipMemcpyAsync(st->d_pts, pts.data(), sizeof(RadialPt) * n, hipMemcpyHostToDevice, h->stream));
     if (error_status()) return false;
     timer_begin(h, timer_id(h, "k_harmonics"));
     if (a.Zb <= 16) harm_launch_ks<4>(h, st, a, n);
@@ -199,31 +168,19 @@ int sx_harmonics(sx_handle *h, const double *radii, int32_t n_r, const double *h
     if (h->has_z && n_z > 0 && !heights) { set_error("sx_harmonics: null argument"); return 1; }
     if (h->Zb > 128) { set_error("sx_harmonics: b_zDim above 128 is not supported"); return 1; }
     const EvalGeom g = eval_geom_of(h);
-    for (int i = 0; i < n_z; i++) {
-        const double z = heights[i];
-        if (!std::isfinite(z)) { set_error("sx_harmonics: height " + std::to_string(i) + " is NaN or Inf"); return 1; }
-        if (!(z >= g.zmin && z <= g.zmax)) {
-            set_error("sx_harmonics: height " + std::to_string(i) + ": z = " + std::to_string(z) + " outside [" + std::to_string(g.zmin) + ", " + std::to_string(g.zmax) + "]");
-            return 1;
-        }
-    }
+    std::string why;
+    for (int i = 0; i < n_z; i++)
+        if (!eval_height_ok(g, heights[i], why)) { set_error("sx_harmonics: height " + std::to_string(i) + ": " + why); return 1; }
     if (n_r > 0 && !radii) { set_error("sx_harmonics: null argument"); return 1; }
-    for (int i = 0; i < n_r; i++) {
-        const double r = radii[i];
-        if (!std::isfinite(r)) { set_error("sx_harmonics: radius " + std::to_string(i) + " is NaN or Inf"); return 1; }
-        if (!(r >= g.tile_lo() && r <= g.tile_hi())) {
-            set_error("sx_harmonics: radius " + std::to_string(i) + ": r = " + std::to_string(r) + " outside the tile's extent [" + std::to_string(g.tile_lo()) + ", " + std::to_string(g.tile_hi()) + "]");
-            return 1;
-        }
-    }
+    for (int i = 0; i < n_r; i++)
+        if (!eval_radius_ok(g, radii[i], why)) { set_error("sx_harmonics: radius " + std::to_string(i) + ": " + why); return 1; }
     const int nz = h->has_z ? n_z : 1;
     if (n_r == 0 || nz == 0) return 0;
     if (!out) { set_error("sx_harmonics: null argument"); return 1; }
-    const std::vector<EvalVert> *vert;
-    const int *d_vcls;
-    if (!eval_classes(h, vert, d_vcls)) return 1;
-    if (!h->harm_state) h->harm_state = new HarmState();
-    HarmState *st = (HarmState *)h->harm_state;
+    const EvalClasses *cls = eval_classes(h);
+    if (!cls) return 1;
+    if (!h->diag[DIAG_HARM]) h->diag[DIAG_HARM].reset(new HarmState());
+    HarmState *st = diag_state<HarmState>(h, DIAG_HARM);
     flush_diag(h);
 
     HarmLaunch a;
@@ -233,27 +190,17 @@ int sx_harmonics(sx_handle *h, const double *radii, int32_t n_r, const double *h
     a.nslots = __builtin_popcount((unsigned)slot_mask);
     a.nz = nz;
     a.nht = (nz + 15) / 16;
-    // the height weight table, once per call: [cls][height tile][row][Zp][16], zero-padded in heights and modes
-    const int ncls = std::max<int>(1, (int)vert->size()), Zp = (a.Zb + 3) & ~3;
-    std::vector<double> wz((size_t)ncls * a.nht * 3 * Zp * 16, 0.0), w3((size_t)3 * a.Zb);
-    for (int c = 0; c < ncls; c++)
-        for (int zj = 0; zj < nz; zj++) {
-            if (h->has_z) eval_vert_weights((*vert)[c], h->zmin, h->zmax, h->nz, a.Zb, heights[zj], w3.data());
-            else w3 = {1.0, 0.0, 0.0};
-            for (int row = 0; row < 3; row++)
-                for (int zm = 0; zm < a.Zb; zm++)
-                    wz[((((size_t)c * a.nht + zj / 16) * 3 + row) * Zp + zm) * 16 + zj % 16] = w3[(size_t)row * a.Zb + zm];
-        }
+    // the height weight table, once per call
+    const std::vector<double> wz = height_tiles(cls->vert, heights, nz, h->zmin, h->zmax, h->nz, a.Zb);
     const size_t per_r = (size_t)a.nslots * h->V * nz * a.KO;
     // radii per launch: the scratch bound, and the y extent of a grid
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>({(size_t)n_r, HARM_SCRATCH / (per_r * sizeof(double)), (size_t)32768}));
-    if (!harm_grow(&st->d_pts, st->cap_pts, (size_t)chunk) || !harm_grow(&st->d_wz, st->cap_wz, wz.size()) ||
-        !harm_grow(&st->d_res, st->cap_res, per_r * chunk))
-        return 1;
+    const char *who = "sx_harmonics";
+    if (!st->d_pts.grow((size_t)chunk, who) || !st->d_wz.grow(wz.size(), who) || !st->d_res.grow(per_r * chunk, who)) return 1;
     HIPCHK(hipMemcpyAsync(st->d_wz, wz.data(), sizeof(double) * wz.size(), hipMemcpyHostToDevice, h->stream));
     if (error_status()) return 1;
     a.wz = st->d_wz;
-    a.vcls = d_vcls;
+    a.vcls = cls->d_vcls;
     // the results of every launch are held back until all of them have succeeded: a failed call writes nothing to out
     std::vector<double> tmp(per_r * n_r);
     st->last_bytes = 0;

@@ -1,8 +1,11 @@
 // Internal declarations of libscythe_hip.so (not part of the ABI).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -91,8 +94,8 @@ bool build_helmholtz(const ChebOps &w, double pxi_bar, double tau, std::vector<d
                      std::string &err);
 void ring_table(int has_l, int uniform_L, int ri /*1-based patch ring*/, int &L, int &kmax, double &off);
 
-// ---- evaluation at arbitrary points (sx_setup.cpp: the weights; sx_eval.hip: sx_eval_basis, sx_evaluate and its kernel) ------
-struct EvalGeom {       // what the weights of one point depend on: from a descriptor (sx_eval_basis) or a handle (sx_evaluate)
+// ---- evaluation at arbitrary points (sx_setup.cpp: the geometry, the weights; sx_eval.hip: sx_eval_basis, sx_evaluate and its kernel) ------
+struct EvalGeom {       // what the weights of one point depend on: from a descriptor (desc_geom) or a handle (eval_geom_of)
     int has_l = 0, has_z = 0, nc = 0, cell0 = 0, ncells = 0, uniform_L = 0, kDim = 0, nz = 1, Zb = 1;
     double xmin = 0, xmax = 0, DX = 0, zmin = 0, zmax = 0;
     double tile_lo() const { return cell0 == 0 ? xmin : xmin + cell0 * DX; }
@@ -102,12 +105,67 @@ struct EvalVert {       // one vertical boundary-condition class
     int bcb = 0, bct = 0;
     std::vector<long double> W[3];   // [nz][Zb]  CA, Dc CA, Dc Dc CA
 };
-void eval_radial(const EvalGeom &g, double r, int &node0, double w[3][4]);
-int eval_kcap(const EvalGeom &g, double r, int flags);
+struct RadialPt {       // one radius as k_harmonics and k_spectrum read it
+    double wr[12];      // [3][4] phi, phi', phi'' at nodes cell .. cell + 3
+    int cell, kcap, orig, pad;   // patch row of the first node; wavenumber cap; index in the chunk (k_harmonics)
+};
+static_assert(sizeof(RadialPt) == 112 && offsetof(RadialPt, cell) == 96 && offsetof(RadialPt, kcap) == 100 && offsetof(RadialPt, orig) == 104,
+              "k_harmonics and k_spectrum read this layout");
+bool desc_ok(const sx_grid_desc *gd, const char *who);   // what every pure host helper refuses of a descriptor
+EvalGeom desc_geom(const sx_grid_desc *gd);              // of a descriptor that desc_ok has passed (vertical fields: the caller checks them)
+// phi, phi', phi'' at the 4 nodes of r's cell ([3][4]), that cell, and the wavenumber cap, as the kernels' point records hold them
+void eval_radial_pt(const EvalGeom &g, double r, int flags, double (&wr)[12], int &cell, int &kcap);
 bool build_eval_vert(double zmin, double zmax, int nz, int Zb, int bcb, int bct, EvalVert &out, std::string &err);
 void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int Zb, double z, double *w /*[3][Zb]*/);
+// eval_vert_weights of n heights as k_harmonics and k_spectrum stage them: [cls][height tile][row 3][Zp][16 heights], Zp = Zb rounded
+// up to 4, zero-padded in heights and modes.  No classes (a grid without a vertical): one class, one height, the row {1, 0, 0}.
+std::vector<double> height_tiles(const std::vector<EvalVert> &vert, const double *heights, int n, double zmin, double zmax, int nz, int Zb);
 // quadrature weights of sx_reduce's domain integral (sx_setup.cpp); reads the geometry fields of g only (not kDim, Zb)
 void reduce_weights(const EvalGeom &g, double *w_r /*[3 ncells]*/, double *w_l /*[3 ncells]*/, double *w_z /*[nz]*/);
+
+// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*) ----
+template <class T>
+struct DevBuf {         // owns one device array; reads as the pointer
+    T *p = nullptr;
+    size_t cap = 0;     // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return p; }
+    void release() { if (p) hipFree(p); p = nullptr; cap = 0; }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); }
+    bool alloc(size_t n) {      // replaces what is there
+        release();
+        if (hipMalloc((void **)&p, n * sizeof(T)) != hipSuccess) { p = nullptr; return false; }
+        cap = n;
+        return true;
+    }
+    // scratch that follows the size of the call: kept while it is large enough, replaced with a quarter to spare
+    bool grow(size_t need, const char *who) {
+        if (need <= cap || alloc(need + need / 4)) return true;
+        set_error(std::string(who) + ": hipMalloc of the scratch failed");
+        return false;
+    }
+    // a table sized once (synchronous copy); err: the whole error text
+    bool upload(const T *v, size_t n, const char *err) {
+        if (alloc(std::max<size_t>(n, 1)) && (!n || hipMemcpy(p, v, sizeof(T) * n, hipMemcpyHostToDevice) == hipSuccess)) return true;
+        release();
+        set_error(err);
+        return false;
+    }
+    bool upload(const std::vector<T> &v, const char *err) { return upload(v.data(), v.size(), err); }
+};
+struct DiagState {      // what one of these entry points keeps with the handle: made on first use, deleted by sx_destroy
+    double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
+    virtual ~DiagState() = default;
+};
+enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
+struct EvalClasses {    // the vertical boundary-condition classes of a handle's variables (eval_classes)
+    std::vector<EvalVert> vert;       // empty without a vertical
+    std::vector<int> vcls;            // [V] class of each variable
+    DevBuf<int> d_vcls;
+};
 
 // ---- device-side tables handed to the kernels -----------------------------------------------------------------------
 // `physical` [slot][v][N] and the node-space transforms G [slot][v][NG] as the kernels see them: the VALUE slot (slot 0)
@@ -305,11 +363,7 @@ struct sx_handle {
     void *comm_state = nullptr;               // RCCL exchange state (sx_comm.cpp)
     void *iface_state = nullptr;              // interface-only patch solve (sx_iface.hip)
     void *pcr_state = nullptr;                // parallel-cyclic-reduction tables and launch lists (sx_pcr.hip)
-    void *eval_state = nullptr;               // sx_evaluate's vertical classes and device scratch, made on first use (sx_eval.hip)
-    void *harm_state = nullptr;               // sx_harmonics' device scratch, made on first use (sx_harmonics.hip)
-    void *reduce_state = nullptr;             // sx_reduce's work list, weights and ring-sum scratch, made on first use (sx_reduce.hip)
-    void *parcel_state = nullptr;             // the parcel set and the vertical operators of its kernel (sx_parcels.hip)
-    void *spec_state = nullptr;               // sx_spectrum's ring and level tables and scratch, made on first use (sx_spectrum.hip)
+    std::unique_ptr<sx::DiagState> diag[sx::DIAG_COUNT];   // states of the diagnostics entry points, made on first use (sx_eval.hip ... sx_parcels.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
     std::vector<int> hcls;                    // host copy of d_cls: [v][2] -> class of (k = 0, k >= 1)
@@ -379,22 +433,16 @@ void flush_diag(sx_handle *h);
 void graphs_release(sx_handle *h);
 void iface_release(sx_handle *h);
 void pcr_release(sx_handle *h);
-void eval_release(sx_handle *h);
-double eval_last_bytes(const sx_handle *h);   // A bytes the last sx_evaluate read
+template <class S>
+inline S *diag_state(const sx_handle *h, int which) { return static_cast<S *>(h->diag[which].get()); }
 EvalGeom eval_geom_of(const sx_handle *h);
-bool eval_point_ok(const EvalGeom &g, double r, double lam, double z, std::string &why);   // what sx_evaluate refuses of a point
-void parcels_release(sx_handle *h);
-double parcels_last_bytes(const sx_handle *h);   // A bytes of the last sx_parcels_advance
-// sx_evaluate's vertical classes, made on first use; vcls: the host copy of the per-variable class table
-bool eval_classes(sx_handle *h, const std::vector<EvalVert> *&vert, const int *&d_vcls, const std::vector<int> **vcls = nullptr);
-void harm_release(sx_handle *h);
-double harm_last_bytes(const sx_handle *h);   // A bytes the last sx_harmonics read
-void reduce_release(sx_handle *h);
-double reduce_last_bytes(const sx_handle *h);   // plane bytes the last sx_reduce read
+sx_grid_desc desc_of(const sx_handle *h);      // the handle's grid as the pure host validators read it (no boundary conditions)
+// what sx_evaluate refuses of a point: its radius, its height; the two and a finite lambda, of every point of a list
+bool eval_radius_ok(const EvalGeom &g, double r, std::string &why);
+bool eval_height_ok(const EvalGeom &g, double z, std::string &why);
+bool eval_points_ok(const sx_handle *h, const double *pts /*[n_coord][n]*/, int64_t n, const char *who, const char *noun);
+const EvalClasses *eval_classes(sx_handle *h);   // made on first use (sx_eval.hip); null when that failed
 int default_bzdim(int zDim);                    // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)
-bool desc_ok(const sx_grid_desc *gd, const char *who);   // what every pure host helper refuses of a descriptor (sx_reduce.hip)
-void spec_release(sx_handle *h);
-double spec_last_bytes(const sx_handle *h);     // A bytes the last sx_spectrum read
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);
 void launch_rz_forward(sx_handle *h);

@@ -175,34 +175,17 @@ __global__ __launch_bounds__(PARCEL_T) void k_parcels(ParcelArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct ParcelState {
+struct ParcelState : DiagState {
     int64_t n = 0;
     int var[3] = {0, 0, 0};              // 1-based (var_r, var_l, var_z), 0 = no motion
-    double *d_f = nullptr;               // pos | vel | h1 | h2, [n_coord][n] each
-    int *d_i = nullptr;                  // cnt | status
-    double *d_ca = nullptr;              // vertical classes, uploaded once per handle
+    DevBuf<double> d_f;                  // pos | vel | h1 | h2, [n_coord][n] each
+    DevBuf<int> d_i;                     // cnt | status
+    DevBuf<double> d_ca;                 // vertical classes, uploaded once per handle
     int cls[3] = {0, 0, 0};
-    double last_bytes = 0;
+    void drop_set() { d_f.release(); d_i.release(); n = 0; }      // the caller has synchronised the stream
 };
 
-static ParcelState *pstate(const sx_handle *h) { return (ParcelState *)h->parcel_state; }
-
-static void parcel_free_set(ParcelState *st) {
-    if (st->d_f) hipFree(st->d_f);
-    if (st->d_i) hipFree(st->d_i);
-    st->d_f = nullptr; st->d_i = nullptr; st->n = 0;
-}
-
-void parcels_release(sx_handle *h) {
-    ParcelState *st = pstate(h);
-    if (!st) return;
-    parcel_free_set(st);
-    if (st->d_ca) hipFree(st->d_ca);
-    delete st;
-    h->parcel_state = nullptr;
-}
-
-double parcels_last_bytes(const sx_handle *h) { return pstate(h) ? pstate(h)->last_bytes : 0.0; }
+static ParcelState *pstate(const sx_handle *h) { return diag_state<ParcelState>(h, DIAG_PARCELS); }
 
 static int parcel_threads(const sx_handle *h) { return (int64_t)h->Zb * h->K2 <= PARCEL_WAVE_COLS ? PARCEL_T_SMALL : PARCEL_T; }
 static size_t parcel_lds(const sx_handle *h) {
@@ -227,55 +210,35 @@ static bool parcel_vars_ok(const sx_handle *h, const int var[3], const char *who
 static ParcelState *parcel_prepare(sx_handle *h, const int var[3], int cls[3]) {
     ParcelState *st = pstate(h);
     if (parcel_lds(h) > PARCEL_LDS_MAX) { set_error("sx_parcels: the weights of one parcel do not fit the LDS (kDim or zDim too large)"); return nullptr; }
+    const EvalClasses *k = h->has_z ? eval_classes(h) : nullptr;
+    if (h->has_z && !k) return nullptr;
     if (!st) {
-        st = new ParcelState();
-        if (h->has_z) {
-            const std::vector<EvalVert> *vert = nullptr;
-            const int *d_vcls = nullptr;
-            if (!eval_classes(h, vert, d_vcls)) { delete st; return nullptr; }
+        std::unique_ptr<ParcelState> made(new ParcelState());
+        if (k) {
             const size_t per = (size_t)h->nz * h->Zb;
-            std::vector<double> ca(vert->size() * per);
-            for (size_t c = 0; c < vert->size(); c++)
-                for (size_t q = 0; q < per; q++) ca[c * per + q] = (double)(*vert)[c].W[0][q];
-            if (hipMalloc((void **)&st->d_ca, sizeof(double) * ca.size()) != hipSuccess ||
-                hipMemcpy(st->d_ca, ca.data(), sizeof(double) * ca.size(), hipMemcpyHostToDevice) != hipSuccess) {
-                set_error("sx_parcels: hipMalloc of the vertical operators failed");
-                if (st->d_ca) hipFree(st->d_ca);
-                delete st;
-                return nullptr;
-            }
+            std::vector<double> ca(k->vert.size() * per);
+            for (size_t c = 0; c < k->vert.size(); c++)
+                for (size_t q = 0; q < per; q++) ca[c * per + q] = (double)k->vert[c].W[0][q];
+            if (!made->d_ca.upload(ca, "sx_parcels: hipMalloc of the vertical operators failed")) return nullptr;
         }
-        h->parcel_state = st;
+        h->diag[DIAG_PARCELS] = std::move(made);
+        st = pstate(h);
     }
-    for (int m = 0; m < 3; m++) cls[m] = 0;
-    if (h->has_z) {
-        const std::vector<EvalVert> *vert = nullptr;
-        const std::vector<int> *vcls = nullptr;
-        const int *d_vcls = nullptr;
-        if (!eval_classes(h, vert, d_vcls, &vcls)) return nullptr;
-        for (int m = 0; m < 3; m++)
-            if (var[m] != 0) cls[m] = (*vcls)[var[m] - 1];
-    }
+    for (int m = 0; m < 3; m++) cls[m] = k && var[m] != 0 ? k->vcls[var[m] - 1] : 0;
     return st;
 }
 
 // replace the set's arrays by f [4][n_coord][n] and ic [2][n] (host), all or nothing
 static bool parcel_install(sx_handle *h, ParcelState *st, int64_t n, const int var[3], const int cls[3], const double *f, const int *ic) {
-    double *d_f = nullptr;
-    int *d_i = nullptr;
-    const size_t nf = (size_t)4 * h->ncoord * n, ni = (size_t)2 * n;
-    if (hipMalloc((void **)&d_f, sizeof(double) * nf) != hipSuccess || hipMalloc((void **)&d_i, sizeof(int) * ni) != hipSuccess ||
-        hipMemcpy(d_f, f, sizeof(double) * nf, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_i, ic, sizeof(int) * ni, hipMemcpyHostToDevice) != hipSuccess) {
+    DevBuf<double> d_f;
+    DevBuf<int> d_i;
+    const char *err = "sx_parcels: hipMalloc of the parcel arrays failed";
+    if (!d_f.upload(f, (size_t)4 * h->ncoord * n, err) || !d_i.upload(ic, (size_t)2 * n, err)) {
         (void)hipGetLastError();
-        if (d_f) hipFree(d_f);
-        if (d_i) hipFree(d_i);
-        set_error("sx_parcels: hipMalloc of the parcel arrays failed");
         return false;
     }
     HIPCHK(hipStreamSynchronize(h->stream));      // a step of the set that goes may still be in flight
-    parcel_free_set(st);
-    st->d_f = d_f; st->d_i = d_i; st->n = n;
+    st->d_f.swap(d_f); st->d_i.swap(d_i); st->n = n;      // the set that goes is freed on return
     for (int m = 0; m < 3; m++) { st->var[m] = var[m]; st->cls[m] = cls[m]; }
     st->last_bytes = 0;
     return true;
@@ -293,20 +256,15 @@ int sx_parcels_set(sx_handle *h, int64_t n, const double *positions, int32_t var
     if (n < 0) { set_error("sx_parcels_set: n is negative"); return 1; }
     if (n == 0) {
         ParcelState *st = pstate(h);
-        if (st && st->n) { HIPCHK(hipStreamSynchronize(h->stream)); parcel_free_set(st); }
+        if (st && st->n) { HIPCHK(hipStreamSynchronize(h->stream)); st->drop_set(); }
         return error_status();
     }
     if (!positions) { set_error("sx_parcels_set: null argument"); return 1; }
     if (n > 0x7fffffff) { set_error("sx_parcels_set: more than 2^31 - 1 parcels"); return 1; }
     const int var[3] = {var_r, var_l, var_z};
     if (!parcel_vars_ok(h, var, "sx_parcels_set")) return 1;
-    const EvalGeom g = eval_geom_of(h);
+    if (!eval_points_ok(h, positions, n, "sx_parcels_set", "parcel")) return 1;
     const int nco = h->ncoord;
-    std::string why;
-    for (int64_t i = 0; i < n; i++) {
-        const double lam = h->has_l ? positions[n + i] : 0.0, z = h->has_z ? positions[(int64_t)(nco - 1) * n + i] : 0.0;
-        if (!eval_point_ok(g, positions[i], lam, z, why)) { set_error("sx_parcels_set: parcel " + std::to_string(i) + ": " + why); return 1; }
-    }
     int cls[3];
     ParcelState *st = parcel_prepare(h, var, cls);
     if (!st) return 1;
@@ -416,19 +374,13 @@ int sx_parcels_set_state(sx_handle *h, const double *in, int64_t n_doubles) {
     }
     if (!parcel_vars_ok(h, var, "sx_parcels_set_state")) return 1;
     const size_t nf = (size_t)4 * h->ncoord * n, ni = (size_t)2 * n;
-    const EvalGeom g = eval_geom_of(h);
-    std::string why;
     std::vector<int> ic(ni);
     for (size_t q = 0; q < ni; q++) {
         const double x = in[PARCEL_HDR + nf + q];
         if (!(x >= 0.0 && x <= 2147483647.0) || (q >= (size_t)n && x > 2.0)) { set_error(bad); return 1; }
         ic[q] = (int)x;
     }
-    for (int64_t i = 0; i < n; i++) {              // the kernel indexes A by the position: it must lie in the tile
-        const double *p = in + PARCEL_HDR;
-        const double lam = h->has_l ? p[n + i] : 0.0, z = h->has_z ? p[(int64_t)(h->ncoord - 1) * n + i] : 0.0;
-        if (!eval_point_ok(g, p[i], lam, z, why)) { set_error("sx_parcels_set_state: parcel " + std::to_string(i) + ": " + why); return 1; }
-    }
+    if (!eval_points_ok(h, in + PARCEL_HDR, n, "sx_parcels_set_state", "parcel")) return 1;      // the kernel indexes A by the position
     int cls[3];
     ParcelState *st = parcel_prepare(h, var, cls);
     if (!st) return 1;

@@ -34,17 +34,15 @@ struct RedProg {
 
 struct RedItem { int ring, lam0, nlam, pad; };
 
-struct ReduceState {
-    RedItem *d_items = nullptr;     // ring pieces (grids with an azimuth) or whole rings
-    int *d_first = nullptr;         // [nrings + 1] first piece of each ring
-    double *d_wrl = nullptr, *d_wz = nullptr;   // w_r w_l per ring, w_z per level
-    double2 *d_part = nullptr;      // [piece][output][level] (hi, lo)
-    double2 *d_part2 = nullptr;     // [RED_OUT][blocks2] sums of the domain kind's first level
+struct ReduceState : DiagState {
+    DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth) or whole rings
+    DevBuf<int> d_first;            // [nrings + 1] first piece of each ring
+    DevBuf<double> d_wrl, d_wz;     // w_r w_l per ring, w_z per level
+    DevBuf<double2> d_part;         // [piece][output][level] (hi, lo)
+    DevBuf<double2> d_part2;        // [RED_OUT][blocks2] sums of the domain kind's first level
     int blocks2 = 1;                // workgroups per output of k_reduce_domain: 4 (piece, level) entries per thread, at most 64
-    double *d_out = nullptr;
-    size_t cap_part = 0, cap_out = 0;
+    DevBuf<double> d_out;
     int n_items = 0;
-    double last_bytes = 0;
 };
 
 // (hi, lo) += x, the rounding error of the sum kept in lo (Knuth's two-sum: no ordering of |hi|, |x| assumed)
@@ -181,48 +179,10 @@ __global__ void k_reduce_domain_sum(const double2 *__restrict__ part2, int block
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-void reduce_release(sx_handle *h) {
-    ReduceState *st = (ReduceState *)h->reduce_state;
-    if (!st) return;
-    hipFree(st->d_items); hipFree(st->d_first); hipFree(st->d_wrl); hipFree(st->d_wz); hipFree(st->d_part); hipFree(st->d_part2); hipFree(st->d_out);
-    delete st;
-    h->reduce_state = nullptr;
-}
-
-double reduce_last_bytes(const sx_handle *h) { return h->reduce_state ? ((const ReduceState *)h->reduce_state)->last_bytes : 0.0; }
-
-template <class T>
-static bool to_device(T **p, const std::vector<T> &v) {
-    if (hipMalloc((void **)p, sizeof(T) * std::max<size_t>(v.size(), 1)) != hipSuccess ||
-        (!v.empty() && hipMemcpy(*p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("sx_reduce: hipMalloc / hipMemcpy of the work list failed");
-        return false;
-    }
-    return true;
-}
-
-template <class T>
-static bool grow(T **p, size_t &cap, size_t need) {
-    if (need <= cap) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr; cap = 0;
-    const size_t n = need + need / 4;
-    if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) { set_error("sx_reduce: hipMalloc of the scratch failed"); return false; }
-    cap = n;
-    return true;
-}
-
-static EvalGeom reduce_geom(const sx_handle *h) {
-    EvalGeom g;
-    g.has_l = h->has_l; g.has_z = h->has_z; g.nc = h->nc; g.cell0 = h->cell0; g.ncells = h->ncells; g.uniform_L = h->uniform_L;
-    g.nz = h->nz; g.xmin = h->xmin; g.xmax = h->xmax; g.DX = h->DX; g.zmin = h->zmin; g.zmax = h->zmax;
-    return g;
-}
-
 // the work list and the weights: functions of the grid alone, made once per handle
 static ReduceState *reduce_state(sx_handle *h) {
-    if (h->reduce_state) return (ReduceState *)h->reduce_state;
-    ReduceState *st = new ReduceState();
+    if (h->diag[DIAG_REDUCE]) return diag_state<ReduceState>(h, DIAG_REDUCE);
+    std::unique_ptr<ReduceState> st(new ReduceState());
     std::vector<RedItem> items;
     std::vector<int> first(h->nrings + 1, 0);
     const int G = RED_T / h->nz;         // lambdas per stride (nz <= 256: sx_create)
@@ -237,37 +197,16 @@ static ReduceState *reduce_state(sx_handle *h) {
     }
     first[h->nrings] = (int)items.size();
     std::vector<double> wr(h->nrings), wl(h->nrings), wz(h->nz, 1.0), wrl(h->nrings);
-    reduce_weights(reduce_geom(h), wr.data(), wl.data(), wz.data());
+    reduce_weights(eval_geom_of(h), wr.data(), wl.data(), wz.data());
     for (int i = 0; i < h->nrings; i++) wrl[i] = wr[i] * wl[i];
     st->n_items = (int)items.size();
     st->blocks2 = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)items.size() * h->nz + 4 * RED_TF - 1) / (4 * RED_TF)));
-    h->reduce_state = st;
-    if (!to_device(&st->d_items, items) || !to_device(&st->d_first, first) || !to_device(&st->d_wrl, wrl) || !to_device(&st->d_wz, wz) ||
-        !to_device(&st->d_part2, std::vector<double2>((size_t)RED_OUT * st->blocks2))) {
-        reduce_release(h);
+    const char *err = "sx_reduce: hipMalloc / hipMemcpy of the work list failed";
+    if (!st->d_items.upload(items, err) || !st->d_first.upload(first, err) || !st->d_wrl.upload(wrl, err) || !st->d_wz.upload(wz, err) ||
+        !st->d_part2.upload(std::vector<double2>((size_t)RED_OUT * st->blocks2), err))
         return nullptr;
-    }
-    return st;
-}
-
-bool desc_ok(const sx_grid_desc *gd, const char *who) {
-    if (!gd) { set_error(std::string(who) + ": null argument"); return false; }
-    if (gd->abi_version != SX_ABI_VERSION) { set_error("sx_grid_desc.abi_version mismatch"); return false; }
-    if (gd->geometry < SX_GEOM_R || gd->geometry > SX_GEOM_RLZ) { set_error("Unknown geometry"); return false; }
-    if (gd->num_cells < 3 || gd->nvars < 1 || !(gd->xmax > gd->xmin)) { set_error("invalid grid parameters"); return false; }
-    if (gd->tile_cell0 < 0 || gd->tile_num_cells < 1 || gd->tile_cell0 + gd->tile_num_cells > gd->num_cells) { set_error("tile range outside the patch"); return false; }
-    return true;
-}
-
-static EvalGeom desc_geom(const sx_grid_desc *gd) {
-    EvalGeom g;
-    g.has_l = gd->geometry == SX_GEOM_RL || gd->geometry == SX_GEOM_RLZ;
-    g.has_z = gd->geometry == SX_GEOM_RZ || gd->geometry == SX_GEOM_RLZ;
-    g.nc = gd->num_cells; g.cell0 = gd->tile_cell0; g.ncells = gd->tile_num_cells;
-    g.uniform_L = g.has_l ? gd->ring_uniform_L : 0;
-    g.xmin = gd->xmin; g.xmax = gd->xmax; g.DX = (gd->xmax - gd->xmin) / gd->num_cells;
-    g.nz = g.has_z ? gd->zDim : 1; g.zmin = gd->zmin; g.zmax = gd->zmax;
-    return g;
+    h->diag[DIAG_REDUCE] = std::move(st);
+    return diag_state<ReduceState>(h, DIAG_REDUCE);
 }
 
 template <class ST, bool RINGS>
@@ -342,9 +281,7 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
     clear_error();
     if (!h) { set_error("null handle"); return 1; }
     if (kind != SX_REDUCE_DOMAIN && kind != SX_REDUCE_AZIMUTH) { set_error("sx_reduce: kind must be SX_REDUCE_DOMAIN or SX_REDUCE_AZIMUTH"); return 1; }
-    sx_grid_desc gd = {};
-    gd.abi_version = SX_ABI_VERSION; gd.geometry = h->geom; gd.xmin = h->xmin; gd.xmax = h->xmax; gd.num_cells = h->nc; gd.nvars = h->V;
-    gd.tile_cell0 = h->cell0; gd.tile_num_cells = h->ncells;
+    const sx_grid_desc gd = desc_of(h);
     int32_t planes[RED_PLANES][2], n_planes = 0;
     if (sx_reduce_planes(&gd, source, n_terms, terms, n_out, &planes[0][0], &n_planes)) return 1;
     if (n_terms > 0 && !coef) { set_error("sx_reduce: null coef with n_terms > 0"); return 1; }
@@ -376,7 +313,7 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
     for (int o = n_out; o <= RED_OUT; o++) prog.start[o] = (uint8_t)k;
 
     const size_t n_res = kind == SX_REDUCE_AZIMUTH ? (size_t)h->nrings * h->nz * n_out : (size_t)n_out;
-    if (!grow(&st->d_part, st->cap_part, (size_t)st->n_items * n_out * h->nz) || !grow(&st->d_out, st->cap_out, n_res)) return 1;
+    if (!st->d_part.grow((size_t)st->n_items * n_out * h->nz, "sx_reduce") || !st->d_out.grow(n_res, "sx_reduce")) return 1;
     st->last_bytes = 0;
     for (int j = 0; j < n_planes; j++) st->last_bytes += (double)h->N * (source == SX_REDUCE_PHYSICAL && h->f32 && planes[j][1] > 0 ? 4.0 : 8.0);
 

@@ -583,22 +583,53 @@ bool build_helmholtz(const ChebOps &w, double pxi_bar, double tau, std::vector<d
 // The weights sx_evaluate's kernel applies and sx_eval_basis returns (sx_eval.hip), formed in extended precision from the Float64
 // coordinate and rounded once.
 
-// phi, phi', phi'' of the 4 nodes that overlap the cell of r (tile cells only: the tile's A rows are the ones the handle holds);
-// node0 = that cell = the patch row of the first node
-void eval_radial(const EvalGeom &g, double r, int &node0, double w[3][4]) {
-    int c = (int)std::floor((r - g.xmin) / g.DX);
-    c = std::min(std::max(c, g.cell0), g.cell0 + g.ncells - 1);
-    node0 = c;
-    const xreal DX = (xreal)g.DX;
-    for (int j = 0; j < 4; j++) {
-        const xreal delta = ((xreal)r - ((xreal)g.xmin + (xreal)(c - 1 + j) * DX)) / DX;
-        xreal sc = 1.0L;
-        for (int d = 0; d < 3; d++, sc *= DX) w[d][j] = (double)(bspl<xreal>(delta, d) / sc);
+// what every pure host helper refuses of a descriptor
+bool desc_ok(const sx_grid_desc *gd, const char *who) {
+    if (!gd) { set_error(std::string(who) + ": null argument"); return false; }
+    if (gd->abi_version != SX_ABI_VERSION) { set_error("sx_grid_desc.abi_version mismatch"); return false; }
+    if (gd->geometry < SX_GEOM_R || gd->geometry > SX_GEOM_RLZ) { set_error("Unknown geometry"); return false; }
+    if (gd->num_cells < 3 || gd->nvars < 1 || !(gd->xmax > gd->xmin)) { set_error("invalid grid parameters"); return false; }
+    if (gd->tile_cell0 < 0 || gd->tile_num_cells < 1 || gd->tile_cell0 + gd->tile_num_cells > gd->num_cells) { set_error("tile range outside the patch"); return false; }
+    return true;
+}
+
+EvalGeom desc_geom(const sx_grid_desc *gd) {
+    EvalGeom g;
+    g.has_l = gd->geometry == SX_GEOM_RL || gd->geometry == SX_GEOM_RLZ;
+    g.has_z = gd->geometry == SX_GEOM_RZ || gd->geometry == SX_GEOM_RLZ;
+    g.nc = gd->num_cells; g.cell0 = gd->tile_cell0; g.ncells = gd->tile_num_cells;
+    g.uniform_L = g.has_l ? gd->ring_uniform_L : 0;
+    g.xmin = gd->xmin; g.xmax = gd->xmax; g.DX = (gd->xmax - gd->xmin) / gd->num_cells;
+    for (int r = 0; r < MUBAR * g.nc; r++) {
+        int L, km;
+        double off;
+        ring_table(g.has_l, g.uniform_L, r + 1, L, km, off);
+        g.kDim = std::max(g.kDim, km);
     }
+    if (g.has_z) {
+        g.nz = gd->zDim;
+        g.Zb = gd->b_zDim > 0 ? gd->b_zDim : default_bzdim(gd->zDim);
+        g.zmin = gd->zmin; g.zmax = gd->zmax;
+    }
+    return g;
+}
+
+EvalGeom eval_geom_of(const sx_handle *h) {
+    EvalGeom g;
+    g.has_l = h->has_l; g.has_z = h->has_z; g.nc = h->nc; g.cell0 = h->cell0; g.ncells = h->ncells; g.uniform_L = h->uniform_L;
+    g.kDim = h->kDim; g.nz = h->nz; g.Zb = h->Zb; g.xmin = h->xmin; g.xmax = h->xmax; g.DX = h->DX; g.zmin = h->zmin; g.zmax = h->zmax;
+    return g;
+}
+
+sx_grid_desc desc_of(const sx_handle *h) {
+    sx_grid_desc gd = {};
+    gd.abi_version = SX_ABI_VERSION; gd.geometry = h->geom; gd.xmin = h->xmin; gd.xmax = h->xmax; gd.num_cells = h->nc; gd.nvars = h->V;
+    gd.tile_cell0 = h->cell0; gd.tile_num_cells = h->ncells; gd.zDim = h->nz; gd.b_zDim = h->Zb;
+    return gd;
 }
 
 // SX_EVAL_RING_K: kmax of the last patch ring at or below r (ring 1 below the first); SX_EVAL_ALL_K: the patch's kDim
-int eval_kcap(const EvalGeom &g, double r, int flags) {
+static int eval_kcap(const EvalGeom &g, double r, int flags) {
     if (!g.has_l) return 0;
     if (flags == SX_EVAL_ALL_K) return g.kDim;
     const double t = (r - g.xmin) / g.DX;
@@ -613,6 +644,21 @@ int eval_kcap(const EvalGeom &g, double r, int flags) {
     double off;
     ring_table(1, g.uniform_L, ring + 1, L, kmax, off);
     return kmax;
+}
+
+// One radius as the kernels' point records hold it.  wr [3][4]: phi, phi', phi'' of the 4 nodes that overlap the cell of r (tile
+// cells only: the tile's A rows are the ones the handle holds); cell = the patch row of the first node; kcap = eval_kcap
+void eval_radial_pt(const EvalGeom &g, double r, int flags, double (&wr)[12], int &cell, int &kcap) {
+    int c = (int)std::floor((r - g.xmin) / g.DX);
+    c = std::min(std::max(c, g.cell0), g.cell0 + g.ncells - 1);
+    cell = c;
+    const xreal DX = (xreal)g.DX;
+    for (int j = 0; j < 4; j++) {
+        const xreal delta = ((xreal)r - ((xreal)g.xmin + (xreal)(c - 1 + j) * DX)) / DX;
+        xreal sc = 1.0L;
+        for (int d = 0; d < 3; d++, sc *= DX) wr[4 * d + j] = (double)(bspl<xreal>(delta, d) / sc);
+    }
+    kcap = eval_kcap(g, r, flags);
 }
 
 // CA, Dc CA, Dc Dc CA of a vertical boundary-condition class, [nz][Zb] each, kept in extended precision
@@ -644,6 +690,22 @@ void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int
             for (int n = 0; n < nz; n++) acc += t[n] * ev.W[s][(size_t)n * Zb + k];
             w[(size_t)s * Zb + k] = (double)acc;
         }
+}
+
+std::vector<double> height_tiles(const std::vector<EvalVert> &vert, const double *heights, int n, double zmin, double zmax, int nz, int Zb) {
+    const bool has_z = !vert.empty();
+    if (!has_z) { n = 1; Zb = 1; }
+    const int ncls = has_z ? (int)vert.size() : 1, nht = (n + 15) / 16, Zp = (Zb + 3) & ~3;
+    std::vector<double> wz((size_t)ncls * nht * 3 * Zp * 16, 0.0), w3((size_t)3 * Zb, 0.0);
+    w3[0] = 1.0;
+    for (int c = 0; c < ncls; c++)
+        for (int zj = 0; zj < n; zj++) {
+            if (has_z) eval_vert_weights(vert[c], zmin, zmax, nz, Zb, heights[zj], w3.data());
+            for (int row = 0; row < 3; row++)
+                for (int zm = 0; zm < Zb; zm++)
+                    wz[((((size_t)c * nht + zj / 16) * 3 + row) * Zp + zm) * 16 + zj % 16] = w3[(size_t)row * Zb + zm];
+        }
+    return wz;
 }
 
 // ---------------------------------------------------------------------------------------------- quadrature weights of sx_reduce

@@ -21,26 +21,19 @@ constexpr int SPEC_T = 256;           // 4 waves x 16 blocks
 constexpr int SPEC_PAIRS = 16;
 constexpr int SPEC_SEG = 16;          // ring strides of k_spectrum_final
 
-struct SpecPt {          // one ring of the tile
-    double wr[12];       // [3][4] phi, phi', phi'' at nodes cell .. cell + 3
-    int cell, kcap, pad[2];
-};
-
 struct SpecProg {        // the pairs as the kernel reads them: 0-based variable, radial weight set, vertical row of either plane
     int va[SPEC_PAIRS], da[SPEC_PAIRS], ra[SPEC_PAIRS], vb[SPEC_PAIRS], db[SPEC_PAIRS], rb[SPEC_PAIRS], same[SPEC_PAIRS];
 };
 
-struct SpecState {
-    SpecPt *d_pts = nullptr;        // [nrings]
-    double *d_wz = nullptr;         // [cls][height tile][row 3][Zp][16]: eval_vert_weights at the level heights
-    double *d_wlev = nullptr;       // [nht 16] w_z per level, zero-padded
-    double *d_wring = nullptr;      // [nrings] 2 pi w_r
-    double2 *d_part = nullptr;      // [pair][ring][k] (hi, lo), domain kind
-    double *d_out = nullptr;
-    size_t cap_part = 0, cap_out = 0;
+struct SpecState : DiagState {
+    DevBuf<RadialPt> d_pts;         // [nrings] the rings of the tile
+    DevBuf<double> d_wz;            // [cls][height tile][row 3][Zp][16]: height_tiles at the level heights
+    DevBuf<double> d_wlev;          // [nht 16] w_z per level, zero-padded
+    DevBuf<double> d_wring;         // [nrings] 2 pi w_r
+    DevBuf<double2> d_part;         // [pair][ring][k] (hi, lo), domain kind
+    DevBuf<double> d_out;
     int nht = 1;
     std::vector<int> kcap;          // host copy, for sx_kernel_bytes
-    double last_bytes = 0;
 };
 
 typedef double spec_d4 __attribute__((ext_vector_type(4)));
@@ -89,7 +82,7 @@ __device__ inline spec_d4 spec_vertical(const double *row, int lane, int Zb, con
 // grid (tile rings, ceil(KO / 64), pairs).  KS: K steps of 4 modes held in registers (4 KS >= b_zDim).  KO = 2 (kDim + 1).
 // DOMAIN: part [pair][ring][k] (hi, lo); else out [pair][ring][k] = hi + lo.
 template <int KS, bool DOMAIN>
-__global__ __launch_bounds__(SPEC_T) void k_spectrum(const double *__restrict__ A, int64_t C, const SpecPt *__restrict__ pts,
+__global__ __launch_bounds__(SPEC_T) void k_spectrum(const double *__restrict__ A, int64_t C, const RadialPt *__restrict__ pts,
                                                      const double *__restrict__ wz, const double *__restrict__ wlev,
                                                      const int *__restrict__ vcls, int nht, int Zb, int K2, int KO, int has_l,
                                                      SpecProg prog, double *__restrict__ out, double2 *__restrict__ part) {
@@ -98,7 +91,7 @@ __global__ __launch_bounds__(SPEC_T) void k_spectrum(const double *__restrict__ 
     const int ring = blockIdx.x, pr = blockIdx.z, Zp = (Zb + 3) & ~3;
     const int va = prog.va[pr], vb = prog.vb[pr], ra = prog.ra[pr], rb = prog.rb[pr];
     const bool same = prog.same[pr] != 0;
-    const SpecPt *__restrict__ pt = pts + ring;
+    const RadialPt *__restrict__ pt = pts + ring;
     const int cell = pt->cell, live = has_l ? 2 * pt->kcap + 1 : 0;
     const int blk = (blockIdx.y * 4 + wave) * 16 + n;
     const bool on = blk < K2 && blk <= live && blk != 1;       // block 1 is the padding block: never read
@@ -182,74 +175,31 @@ __global__ __launch_bounds__(SPEC_T) void k_spectrum_final(const double2 *__rest
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-void spec_release(sx_handle *h) {
-    SpecState *st = (SpecState *)h->spec_state;
-    if (!st) return;
-    hipFree(st->d_pts); hipFree(st->d_wz); hipFree(st->d_wlev); hipFree(st->d_wring); hipFree(st->d_part); hipFree(st->d_out);
-    delete st;
-    h->spec_state = nullptr;
-}
-
-double spec_last_bytes(const sx_handle *h) { return h->spec_state ? ((const SpecState *)h->spec_state)->last_bytes : 0.0; }
-
-template <class T>
-static bool spec_upload(T **p, const std::vector<T> &v) {
-    if (hipMalloc((void **)p, sizeof(T) * std::max<size_t>(v.size(), 1)) != hipSuccess ||
-        (!v.empty() && hipMemcpy(*p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-        set_error("sx_spectrum: hipMalloc / hipMemcpy of the tables failed");
-        return false;
-    }
-    return true;
-}
-
-template <class T>
-static bool spec_grow(T **p, size_t &cap, size_t need) {
-    if (need <= cap) return true;
-    if (*p) hipFree(*p);
-    *p = nullptr; cap = 0;
-    const size_t n = need + need / 4;
-    if (hipMalloc((void **)p, n * sizeof(T)) != hipSuccess) { set_error("sx_spectrum: hipMalloc of the scratch failed"); return false; }
-    cap = n;
-    return true;
-}
-
 // the rings, the level table and the weights: functions of the grid alone, made once per handle
 static SpecState *spec_state(sx_handle *h, const std::vector<EvalVert> &vert) {
-    if (h->spec_state) return (SpecState *)h->spec_state;
-    SpecState *st = new SpecState();
+    if (h->diag[DIAG_SPEC]) return diag_state<SpecState>(h, DIAG_SPEC);
+    std::unique_ptr<SpecState> st(new SpecState());
     const EvalGeom g = eval_geom_of(h);
-    const int Zb = h->has_z ? h->Zb : 1, Zp = (Zb + 3) & ~3, nz = h->has_z ? h->nz : 1;
+    const int Zb = h->has_z ? h->Zb : 1, nz = h->has_z ? h->nz : 1;
     st->nht = (nz + 15) / 16;
-    std::vector<SpecPt> pts(h->nrings);
+    std::vector<RadialPt> pts(h->nrings);
     st->kcap.resize(h->nrings);
     for (int i = 0; i < h->nrings; i++) {
-        const double r = ring_radius(h->xmin, h->DX, h->cell0, i);
-        double w[3][4];
-        eval_radial(g, r, pts[i].cell, w);
-        std::memcpy(pts[i].wr, w, sizeof(w));
-        pts[i].kcap = st->kcap[i] = eval_kcap(g, r, SX_EVAL_RING_K);
-        pts[i].pad[0] = pts[i].pad[1] = 0;
+        eval_radial_pt(g, ring_radius(h->xmin, h->DX, h->cell0, i), SX_EVAL_RING_K, pts[i].wr, pts[i].cell, pts[i].kcap);
+        st->kcap[i] = pts[i].kcap;
+        pts[i].orig = pts[i].pad = 0;
     }
-    const int ncls = std::max<int>(1, (int)vert.size());
-    std::vector<double> wz((size_t)ncls * st->nht * 3 * Zp * 16, 0.0), w3((size_t)3 * Zb);
-    for (int c = 0; c < ncls; c++)
-        for (int zj = 0; zj < nz; zj++) {
-            if (h->has_z) eval_vert_weights(vert[c], h->zmin, h->zmax, h->nz, Zb, level_height(h->zmin, h->zmax, h->nz, zj), w3.data());
-            else w3 = {1.0, 0.0, 0.0};
-            for (int row = 0; row < 3; row++)
-                for (int zm = 0; zm < Zb; zm++)
-                    wz[((((size_t)c * st->nht + zj / 16) * 3 + row) * Zp + zm) * 16 + zj % 16] = w3[(size_t)row * Zb + zm];
-        }
+    std::vector<double> lev;
+    for (int zj = 0; h->has_z && zj < nz; zj++) lev.push_back(level_height(h->zmin, h->zmax, h->nz, zj));
+    const std::vector<double> wz = height_tiles(vert, lev.data(), nz, h->zmin, h->zmax, h->nz, Zb);
     std::vector<double> wr(h->nrings), wl(h->nrings), wlev((size_t)st->nht * 16, 0.0), wring(h->nrings);
     wlev[0] = 1.0;                                             // without a vertical: one level of weight 1
     reduce_weights(g, wr.data(), wl.data(), wlev.data());
     for (int i = 0; i < h->nrings; i++) wring[i] = wr[i] * (wl[i] * (double)h->hL[i]);      // 2 pi = w_l L (1 without an azimuth)
-    h->spec_state = st;
-    if (!spec_upload(&st->d_pts, pts) || !spec_upload(&st->d_wz, wz) || !spec_upload(&st->d_wlev, wlev) || !spec_upload(&st->d_wring, wring)) {
-        spec_release(h);
-        return nullptr;
-    }
-    return st;
+    const char *err = "sx_spectrum: hipMalloc / hipMemcpy of the tables failed";
+    if (!st->d_pts.upload(pts, err) || !st->d_wz.upload(wz, err) || !st->d_wlev.upload(wlev, err) || !st->d_wring.upload(wring, err)) return nullptr;
+    h->diag[DIAG_SPEC] = std::move(st);
+    return diag_state<SpecState>(h, DIAG_SPEC);
 }
 
 struct SpecLaunch {
@@ -297,23 +247,20 @@ int sx_spectrum(sx_handle *h, int32_t kind, int32_t n_pairs, const int32_t *pair
     clear_error();
     if (!h) { set_error("null handle"); return 1; }
     if (kind != SX_SPEC_RING && kind != SX_SPEC_DOMAIN) { set_error("sx_spectrum: kind must be SX_SPEC_RING or SX_SPEC_DOMAIN"); return 1; }
-    sx_grid_desc gd = {};
-    gd.abi_version = SX_ABI_VERSION; gd.geometry = h->geom; gd.xmin = h->xmin; gd.xmax = h->xmax; gd.num_cells = h->nc; gd.nvars = h->V;
-    gd.tile_cell0 = h->cell0; gd.tile_num_cells = h->ncells; gd.zDim = h->nz; gd.b_zDim = h->Zb;
+    const sx_grid_desc gd = desc_of(h);
     if (sx_spectrum_check(&gd, n_pairs, pairs)) return 1;
     if (n_pairs == 0) return 0;
     if (!out) { set_error("sx_spectrum: null out with n_pairs > 0"); return 1; }
-    const std::vector<EvalVert> *vert;
-    const int *d_vcls;
-    if (!eval_classes(h, vert, d_vcls)) return 1;
-    SpecState *st = spec_state(h, *vert);
+    const EvalClasses *cls = eval_classes(h);
+    if (!cls) return 1;
+    SpecState *st = spec_state(h, cls->vert);
     if (!st) return 1;
     flush_diag(h);
 
     static const int RAD[5] = {0, 1, 2, 0, 0}, ROW[5] = {0, 0, 0, 1, 2};      // slot u, r, rr, z, zz -> radial weights, vertical row
     SpecLaunch a;
     std::memset(&a.prog, 0, sizeof(a.prog));
-    a.vcls = d_vcls;
+    a.vcls = cls->d_vcls;
     a.Zb = h->has_z ? h->Zb : 1;
     a.KO = 2 * (h->kDim + 1);
     a.n_pairs = n_pairs;
@@ -328,7 +275,7 @@ int sx_spectrum(sx_handle *h, int32_t kind, int32_t n_pairs, const int32_t *pair
     const int K = h->kDim + 1;
     const bool domain = kind == SX_SPEC_DOMAIN;
     const size_t n_ring = (size_t)K * h->nrings * n_pairs, n_res = domain ? (size_t)K * n_pairs : n_ring;
-    if (!spec_grow(&st->d_out, st->cap_out, n_res) || (domain && !spec_grow(&st->d_part, st->cap_part, n_ring))) return 1;
+    if (!st->d_out.grow(n_res, "sx_spectrum") || (domain && !st->d_part.grow(n_ring, "sx_spectrum"))) return 1;
     // the A traffic: every distinct (var, slot) plane reads 4 rows x b_zDim x (2 kmax + 1) doubles per ring
     const double n_planes = (double)std::count(plane.begin(), plane.end(), true);
     st->last_bytes = 0;
