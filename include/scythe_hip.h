@@ -375,6 +375,51 @@ int sx_parcels_state_size(const sx_handle *h, int64_t *n_doubles);
 int sx_parcels_get_state(sx_handle *h, double *out);
 int sx_parcels_set_state(sx_handle *h, const double *in, int64_t n_doubles);
 
+/* --- elliptic inversion: streamfunction, velocity potential ------------------------------------------------------------
+ * Solves, for the solution variable and every wavenumber k of the patch (k = 0 only on R / RZ grids),
+ *     (lap_h - alpha) psi = f,    lap_h = (1 / J) d_r (J d_r) - k^2 / r^2  (RL / RLZ, J = r);   d_x^2  (R / RZ, J = 1)
+ * in the weak form, in the patch's own spline basis phi_m (m = 0 .. num_cells + 2), with the 7-diagonal matrices
+ *     S[i][j] = int J phi_i' phi_j' dr     T[i][j] = int phi_i phi_j / r dr (RL / RLZ only)     M[i][j] = int J phi_i phi_j dr
+ *     N[i][j] = int r phi_i phi_j' dr      M0[i][j] = int phi_i phi_j dr
+ * formed on the host in extended precision by Gauss-Legendre quadrature with 8 points per cell (exact for S, M, N, M0; for T the rule
+ * is the definition) and rounded once.  With Gamma_k the boundary-condition projection of the solution variable as splineTransform!
+ * applies it (its bcl_k0 for k = 0, its bcl for k >= 1, its bcr):
+ *     K_k = Gamma_k (S + k^2 T + alpha M) Gamma_k^T  (SPD),     K_k x = -Gamma_k g,     a = Gamma_k^T x
+ * per z-mode and per re / im block; block 1 (Im c_0) is never read and is written as zero.  With c_k = A[2k] + i A[2k + 1] as in
+ * sx_harmonics the right-hand side g is one of
+ *     SX_ELL_FIELD       var_a = the field f:        g = M a_f                                           any geometry; var_b ignored
+ *     SX_ELL_VORTICITY   var_a = u, var_b = v:       r zeta = r v_r + v - u_lambda                       RL / RLZ only
+ *                          g_re = (N + M0) v_re + k M0 u_im      g_im = (N + M0) v_im - k M0 u_re
+ *     SX_ELL_DIVERGENCE  var_a = u, var_b = v:       r delta = r u_r + u + v_lambda                      RL / RLZ only
+ *                          g_re = (N + M0) u_re - k M0 v_im      g_im = (N + M0) u_im + k M0 v_re
+ * No derivative plane and no transform is taken: A is the only input.  The banded Cholesky factor of every K_k is worked out on the
+ * host in extended precision, rounded once and kept with the source handle for the last (alpha, boundary conditions) used.
+ *
+ * sx_elliptic_solve writes the patch A rows of variable var_dst (1-based) of dst - the rows sx_tile_transform / sx_evaluate /
+ * sx_harmonics / sx_spectrum of dst read, so everything the library has then samples psi and its derivatives.  dst may be src itself
+ * (a spare variable of the model) or a one-variable companion handle with SX_EQ_NONE.  Runs on src's stream and returns after the
+ * kernel has completed; reads A of src only (a deferred diagnostic variable is brought up to date first, as for every reader of A)
+ * and writes only var_dst's A columns of dst: `physical`, var_np1, the tendency history, the B arrays, parcels and captured graphs of
+ * both handles and every other variable's A stay bitwise as they are.  No floating-point atomics, a fixed order: two calls agree
+ * bitwise and a column's result does not depend on the launch shape.
+ * Refused, with a message and before anything is written: a null handle; an unknown rhs_kind; a variable index out of range; var_dst
+ * equal to a source variable when dst == src; vorticity / divergence on R / RZ; a src or dst that is not a one-tile patch; a dst that
+ * differs from src in geometry, xmin, xmax, num_cells, ring table, kDim, zDim, b_zDim, zmin or zmax; a source variable whose vertical
+ * (bcb, bct) differs from var_dst's (the z-mode columns are carried over one to one); PERIODIC radial conditions on var_dst; a
+ * non-finite or negative alpha; alpha == 0 with a k = 0 class that fixes the value on neither side (singular); on RL / RLZ with
+ * xmin == 0 a k >= 1 class whose constrained basis does not vanish at r = 0 (decided from Gamma and phi(xmin): int phi phi / r has no
+ * meaning for such a class); a K_k with a non-positive pivot.
+ * sx_kernel_bytes("k_elliptic") gives the source columns in + the destination columns out + the factors of the last solve.
+ *
+ * sx_elliptic_check applies the same host-built factors to ONE right-hand side g for one wavenumber k, with the arithmetic of the
+ * kernel from g on (fold with Gamma_k, the two sweeps, Gamma_k^T): a = Gamma_k^T K_k^-1 (-Gamma_k g).  It refuses what the solve
+ * refuses of a descriptor, and a k outside 0 .. kDim.  Pure host helper (no handle, no device): the matrix construction and the
+ * sweep are testable where there is no GPU. */
+enum { SX_ELL_FIELD = 0, SX_ELL_VORTICITY = 1, SX_ELL_DIVERGENCE = 2 };
+int sx_elliptic_solve(sx_handle *src, int32_t rhs_kind, int32_t var_a, int32_t var_b, double alpha, sx_handle *dst, int32_t var_dst);
+int sx_elliptic_check(const sx_grid_desc *grid, int32_t var_dst, int32_t k, double alpha, const double *g /*[num_cells + 3]*/,
+                      double *a /*[num_cells + 3]*/);
+
 /* --- integrals and azimuthal means of field products ------------------------------------------------------------------
  * On-device diagnostics: budgets and azimuthal means / eddy covariances without pulling `physical` to the host.
  * Integrand program: n_terms <= 64 monomial terms feed n_out <= 16 outputs.  Term t is

@@ -203,6 +203,21 @@ function spectrumDevice(mtile::HipModelTile, pairs::Matrix{Int32}; domain::Bool 
     return out
 end
 
+# elliptic inversion (sx_elliptic_solve): (lap_h - alpha) psi = f from the A coefficients of src, written as the A coefficients of variable
+# var_dst of dst (src itself, or a one-variable companion tile with no equation set).  kind 0: f = variable var_a; 1: the vorticity, 2: the
+# divergence of the wind (u, v) = (var_a, var_b) on an RL / RLZ grid.  The boundary conditions of psi are those of var_dst
+function ellipticSolve!(src::HipModelTile, kind::Integer, var_a::Integer, var_b::Integer, alpha::Float64, dst::HipModelTile, var_dst::Integer)
+    sxcheck(ccall((:sx_elliptic_solve, libsx), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Float64, Ptr{Cvoid}, Int32),
+                  src.handle, kind, var_a, var_b, alpha, dst.handle, var_dst))
+end
+
+# the same for ONE right-hand side column g[num_cells + 3] and wavenumber k on the host (no handle, no device)
+function ellipticCheck(grid::SxGridDesc, var_dst::Integer, k::Integer, alpha::Float64, g::Vector{Float64})
+    a = zeros(Float64, length(g))
+    sxcheck(ccall((:sx_elliptic_check, libsx), Cint, (Ref{SxGridDesc}, Int32, Int32, Float64, Ptr{Float64}, Ptr{Float64}), grid, var_dst, k, alpha, g, a))
+    return a
+end
+
 # Lagrangian parcels (sx_parcels_*): tracer points that live on the device and move with the model's Adams-Bashforth scheme.
 # points[n, n_coord] with columns r[, lambda][, z]; var_r / var_l / var_z = 1-based variable index of the velocity component along
 # each coordinate (speeds; var_l the tangential wind), 0 = no motion.  An empty points matrix removes the set

@@ -13,6 +13,7 @@ BC = {"R0": 0, "R1T0": 1, "R1T1": 2, "R1T2": 3, "R2T10": 4, "R2T20": 5, "R3": 6,
 EVAL_RING_K, EVAL_ALL_K = 0, 1      # SX_EVAL_*
 HARM_SLOTS = ("u", "r", "rr", "z", "zz")          # SX_HARM_*: bit i of slot_mask
 SPEC_KIND = {"ring": 0, "domain": 1}             # SX_SPEC_RING / SX_SPEC_DOMAIN
+ELL_KIND = {"field": 0, "vorticity": 1, "divergence": 2}    # SX_ELL_*
 REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_AZIMUTH
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
 SLOTS = {"R": ["", "r", "rr"], "RZ": ["", "r", "rr", "z", "zz"], "RL": ["", "r", "rr", "l", "ll"],
@@ -123,6 +124,8 @@ SYMBOLS = {
     "sx_parcels_state_size": (C.c_int, [_H, P_I64]),
     "sx_parcels_get_state": (C.c_int, [_H, P_D]),
     "sx_parcels_set_state": (C.c_int, [_H, P_D, C.c_int64]),
+    "sx_elliptic_solve": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, _H, C.c_int32]),
+    "sx_elliptic_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_double, P_D, P_D]),
     "sx_reduce": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D]),
     "sx_reduce_weights": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, P_D]),
     "sx_reduce_planes": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32, P_I32]),

@@ -123,7 +123,27 @@ std::vector<double> height_tiles(const std::vector<EvalVert> &vert, const double
 // quadrature weights of sx_reduce's domain integral (sx_setup.cpp); reads the geometry fields of g only (not kDim, Zb)
 void reduce_weights(const EvalGeom &g, double *w_r /*[3 ncells]*/, double *w_l /*[3 ncells]*/, double *w_z /*[nz]*/);
 
-// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*) ----
+// ---- elliptic inversion (sx_setup.cpp: the matrices and the factors; sx_elliptic.hip: sx_elliptic_solve, sx_elliptic_check, the kernel) ----
+struct EllBands {       // the five 7-diagonal matrices of the patch's spline basis in extended precision: entry (i, j) at [i][j - i + 3]
+    int nb = 0;
+    std::vector<long double> S, T, M, N, M0;     // int J phi' phi', int phi phi / r (RL / RLZ), int J phi phi, int r phi phi', int phi phi
+};
+struct EllClass {       // one boundary-condition class of the solution variable with the factors of its wavenumbers k_lo .. k_hi
+    int bcl = 0, bcr = 0, n = 0, rl = 0, rr = 0, k_lo = 0, k_hi = 0;
+    double gl[3][2] = {}, gr[3][2] = {};         // as SplineClass
+    std::vector<std::vector<std::pair<int, double>>> Gam;
+    // [k - k_lo][nb][4]: row i of the banded Cholesky factor of K_k as L[i][i - 3], L[i][i - 2], L[i][i - 1], 1 / L[i][i] - the layout
+    // of SplineClass::Lband with the reciprocal in the diagonal's place
+    std::vector<double> L;
+};
+void build_elliptic_bands(int has_l, double xmin, double xmax, int nc, EllBands &out);
+// refuses PERIODIC, alpha = 0 with a k = 0 class that fixes the value on neither side, a k >= 1 class that does not vanish at r = 0 on
+// an RL / RLZ grid with xmin = 0 (both decided from Gamma and phi at the ends), and a non-positive pivot
+bool build_elliptic_class(const EllBands &eb, int has_l, double xmin, int bcl, int bcr, int k_lo, int k_hi, double alpha, EllClass &out,
+                          std::string &err);
+void elliptic_apply_host(const EllClass &c, int k, int nb, const double *g /*[nb]*/, double *a /*[nb]*/);
+
+// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve) ----
 template <class T>
 struct DevBuf {         // owns one device array; reads as the pointer
     T *p = nullptr;
@@ -160,7 +180,7 @@ struct DiagState {      // what one of these entry points keeps with the handle:
     double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
     virtual ~DiagState() = default;
 };
-enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
+enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
 struct EvalClasses {    // the vertical boundary-condition classes of a handle's variables (eval_classes)
     std::vector<EvalVert> vert;       // empty without a vertical
     std::vector<int> vcls;            // [V] class of each variable

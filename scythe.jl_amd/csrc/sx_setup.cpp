@@ -67,6 +67,26 @@ static bool boundary_rows(int bc, double g[3][2]) {
     }
 }
 
+// Gamma as sparse rows: free j -> list of (patch row, weight), from the class's rank and boundary rows
+static std::vector<std::vector<std::pair<int, double>>> gamma_rows(const SplineClass &sc, int nb) {
+    const int n = sc.nfree;
+    std::vector<std::vector<std::pair<int, double>>> G(n);
+    if (sc.periodic) {
+        for (int m = 0; m < nb; m++) G[(m - 1 + n) % n].push_back({m, 1.0});
+    } else {
+        for (int j = 0; j < n; j++) G[j].push_back({sc.rl + j, 1.0});
+        for (int i = 0; i < sc.rl; i++) {
+            if (sc.gl[i][0] != 0.0) G[0].push_back({i, sc.gl[i][0]});
+            if (sc.gl[i][1] != 0.0) G[1].push_back({i, sc.gl[i][1]});
+        }
+        for (int i = 0; i < sc.rr; i++) {
+            if (sc.gr[i][0] != 0.0) G[n - 1].push_back({nb - 1 - i, sc.gr[i][0]});
+            if (sc.gr[i][1] != 0.0) G[n - 2].push_back({nb - 1 - i, sc.gr[i][1]});
+        }
+    }
+    return G;
+}
+
 bool build_spline_class(int nc, double DX, double l_q, int bcl, int bcr, SplineClass &out, std::string &err) {
     const int nb = nc + 3;
     out.bcl = bcl;
@@ -104,21 +124,7 @@ bool build_spline_class(int nc, double DX, double l_q, int bcl, int bcr, SplineC
         int dj = j - i + 3;
         return (dj < 0 || dj > 6) ? 0.0 : Pb[(size_t)i * 7 + dj];
     };
-    // Gamma as sparse rows: free j -> list of (full index, weight)
-    std::vector<std::vector<std::pair<int, double>>> G(n);
-    if (out.periodic) {
-        for (int m = 0; m < nb; m++) G[(m - 1 + n) % n].push_back({m, 1.0});
-    } else {
-        for (int j = 0; j < n; j++) G[j].push_back({out.rl + j, 1.0});
-        for (int i = 0; i < out.rl; i++) {
-            if (out.gl[i][0] != 0.0) G[0].push_back({i, out.gl[i][0]});
-            if (out.gl[i][1] != 0.0) G[1].push_back({i, out.gl[i][1]});
-        }
-        for (int i = 0; i < out.rr; i++) {
-            if (out.gr[i][0] != 0.0) G[n - 1].push_back({nb - 1 - i, out.gr[i][0]});
-            if (out.gr[i][1] != 0.0) G[n - 2].push_back({nb - 1 - i, out.gr[i][1]});
-        }
-    }
+    const std::vector<std::vector<std::pair<int, double>>> G = gamma_rows(out, nb);
     // PQ = Gamma P Gamma^T (dense, symmetric)
     std::vector<double> A((size_t)n * n, 0.0);
     for (int a = 0; a < n; a++)
@@ -390,6 +396,180 @@ void cholesky_apply_host(const SplineClass &sc, int nb, const double *b, double 
     for (int m = 0; m < nb; m++) a[m] = 0.0;
     for (int j = 0; j < n; j++)
         for (auto &e : sc.Gam[j]) a[e.first] += (double)((long double)e.second * x[j]);
+}
+
+// ---------------------------------------------------------------------------------------------- elliptic inversion
+// The operators of sx_elliptic_solve (include/scythe_hip.h, "elliptic inversion"): the five 7-diagonal matrices of
+// the patch's spline basis by Gauss-Legendre quadrature with 8 points per cell in extended precision (exact for S, M, N, M0; for
+// T = int phi phi / r the rule is the definition), and per boundary-condition class and wavenumber the banded Cholesky factor of
+// K_k = Gamma (S + k^2 T + alpha M) Gamma^T, worked out in extended precision and rounded once.
+
+// nodes (on [-1, 1]) and weights of the 8-point Gauss-Legendre rule: Newton's iteration on P_8 in extended precision
+static void gauss_legendre8(pxr x[8], pxr w[8]) {
+    const int n = 8;
+    const pxr PI = acosl(-1.0L);
+    for (int i = 0; i < n; i++) {
+        pxr z = cosl(PI * ((pxr)i + 0.75L) / ((pxr)n + 0.5L)), dp = 1.0L;
+        for (int it = 0; it < 100; it++) {
+            pxr p0 = 1.0L, p1 = z;
+            for (int j = 2; j <= n; j++) { const pxr p2 = ((2 * j - 1) * z * p1 - (j - 1) * p0) / j; p0 = p1; p1 = p2; }
+            dp = n * (z * p1 - p0) / (z * z - 1.0L);
+            const pxr dz = p1 / dp;
+            z -= dz;
+            if (fabsl(dz) < 1e-19L) break;
+        }
+        pxr p0 = 1.0L, p1 = z;
+        for (int j = 2; j <= n; j++) { const pxr p2 = ((2 * j - 1) * z * p1 - (j - 1) * p0) / j; p0 = p1; p1 = p2; }
+        dp = n * (z * p1 - p0) / (z * z - 1.0L);
+        x[i] = z;
+        w[i] = 2.0L / ((1.0L - z * z) * dp * dp);
+    }
+}
+
+void build_elliptic_bands(int has_l, double xmin, double xmax, int nc, EllBands &eb) {
+    const int nb = nc + 3;
+    eb.nb = nb;
+    std::vector<pxr> *all[5] = {&eb.S, &eb.T, &eb.M, &eb.N, &eb.M0};
+    for (auto *m : all) m->assign((size_t)nb * 7, 0.0L);
+    pxr gx[8], gw[8];
+    gauss_legendre8(gx, gw);
+    const pxr DX = ((pxr)xmax - (pxr)xmin) / (pxr)nc;
+    for (int c = 0; c < nc; c++)
+        for (int q = 0; q < 8; q++) {
+            const pxr t = 0.5L * (1.0L + gx[q]), r = (pxr)xmin + ((pxr)c + t) * DX, w = 0.5L * DX * gw[q];   // t: position in the cell
+            const pxr J = has_l ? r : 1.0L;
+            pxr ph[4], dph[4];
+            for (int j = 0; j < 4; j++) { ph[j] = bspl<pxr>(t + 1.0L - j, 0); dph[j] = bspl<pxr>(t + 1.0L - j, 1) / DX; }   // node c + j
+            for (int i = 0; i < 4; i++)
+                for (int j = 0; j < 4; j++) {
+                    const size_t e = (size_t)(c + i) * 7 + (j - i + 3);
+                    eb.S[e] += w * J * dph[i] * dph[j];
+                    eb.M[e] += w * J * ph[i] * ph[j];
+                    eb.M0[e] += w * ph[i] * ph[j];
+                    eb.N[e] += w * r * ph[i] * dph[j];
+                    if (has_l) eb.T[e] += w * ph[i] * ph[j] / r;
+                }
+        }
+}
+
+// the value of every constrained basis function (row of Gamma) at the left / right end of the patch is zero
+static bool ell_vanishes(const std::vector<std::vector<std::pair<int, double>>> &G, int nb, bool right) {
+    for (const auto &row : G) {
+        pxr s = 0.0L;
+        for (const auto &e : row) {
+            const int d = right ? e.first - (nb - 2) : e.first - 1;     // node offset from the end node, in cells
+            s += (pxr)e.second * bspl<pxr>((pxr)-d, 0);
+        }
+        if (fabsl(s) > 1e-12L) return false;
+    }
+    return true;
+}
+
+bool build_elliptic_class(const EllBands &eb, int has_l, double xmin, int bcl, int bcr, int k_lo, int k_hi, double alpha, EllClass &out,
+                          std::string &err) {
+    const int nb = eb.nb;
+    if (bcl == SX_BC_PERIODIC || bcr == SX_BC_PERIODIC) { err = "PERIODIC radial boundary conditions on the solution variable are not supported"; return false; }
+    SplineClass sc;
+    sc.bcl = bcl; sc.bcr = bcr;
+    sc.rl = bc_rank(bcl); sc.rr = bc_rank(bcr);
+    if (sc.rl < 0 || sc.rr < 0 || !boundary_rows(bcl, sc.gl) || !boundary_rows(bcr, sc.gr)) { err = "unknown radial boundary condition code"; return false; }
+    sc.nfree = nb - sc.rl - sc.rr;
+    const int n = sc.nfree;
+    if (n < 4) { err = "too few cells for the requested boundary conditions"; return false; }
+    const auto G = gamma_rows(sc, nb);
+    const bool zero_l = ell_vanishes(G, nb, false), zero_r = ell_vanishes(G, nb, true);
+    if (k_lo == 0 && alpha == 0.0 && !zero_l && !zero_r) {
+        err = "alpha = 0 with wavenumber-0 boundary conditions that fix the value on neither side: the problem is singular";
+        return false;
+    }
+    if (has_l && xmin == 0.0 && k_hi >= 1 && !zero_l) {
+        err = "the boundary conditions of wavenumbers k >= 1 do not make the solution vanish at r = 0: int phi phi / r has no meaning";
+        return false;
+    }
+    out.bcl = bcl; out.bcr = bcr; out.n = n; out.rl = sc.rl; out.rr = sc.rr; out.k_lo = k_lo; out.k_hi = k_hi;
+    std::memcpy(out.gl, sc.gl, sizeof(sc.gl));
+    std::memcpy(out.gr, sc.gr, sizeof(sc.gr));
+    out.Gam = G;
+    out.L.assign((size_t)(k_hi - k_lo + 1) * nb * 4, 0.0);
+    std::vector<pxr> Kb((size_t)n * 4), Lx((size_t)n * 4);       // [a][q]: entry (a, a - q), q = 0 .. 3
+    for (int k = k_lo; k <= k_hi; k++) {
+        const pxr k2 = (pxr)k * (pxr)k, al = (pxr)alpha;
+        auto B = [&](int i, int j) -> pxr {
+            const int d = j - i + 3;
+            if (d < 0 || d > 6) return 0.0L;
+            const size_t e = (size_t)i * 7 + d;
+            return eb.S[e] + k2 * eb.T[e] + al * eb.M[e];
+        };
+        for (int a = 0; a < n; a++)
+            for (int q = 0; q < 4; q++) {
+                pxr s = 0.0L;
+                if (a - q >= 0)
+                    for (const auto &ia : G[a])
+                        for (const auto &jb : G[a - q]) s += (pxr)ia.second * B(ia.first, jb.first) * (pxr)jb.second;
+                Kb[(size_t)a * 4 + q] = s;
+            }
+        for (int j = 0; j < n; j++)
+            for (int i = j; i <= std::min(j + 3, n - 1); i++) {
+                pxr s = Kb[(size_t)i * 4 + (i - j)];
+                for (int c = std::max(0, i - 3); c < j; c++) s -= Lx[(size_t)i * 4 + (i - c)] * Lx[(size_t)j * 4 + (j - c)];
+                if (i == j) {
+                    if (!(s > 0.0L)) { err = "the elliptic operator of wavenumber " + std::to_string(k) + " is not positive definite"; return false; }
+                    Lx[(size_t)j * 4] = sqrtl(s);
+                } else {
+                    Lx[(size_t)i * 4 + (i - j)] = s / Lx[(size_t)j * 4];
+                }
+            }
+        double *Lk = out.L.data() + (size_t)(k - k_lo) * nb * 4;
+        for (int i = 0; i < n; i++) {
+            for (int q = 1; q < 4; q++)
+                if (i - q >= 0) Lk[(size_t)i * 4 + (3 - q)] = (double)Lx[(size_t)i * 4 + q];
+            Lk[(size_t)i * 4 + 3] = (double)(1.0L / Lx[(size_t)i * 4]);
+        }
+    }
+    return true;
+}
+
+// the arithmetic of k_elliptic from the right-hand side on (fold, the two sweeps, expand), operation by operation, on the host
+void elliptic_apply_host(const EllClass &c, int k, int nb, const double *g, double *a) {
+    const int n = c.n, rl = c.rl, rr = c.rr;
+    const double *F = c.L.data() + (size_t)(k - c.k_lo) * nb * 4;
+    double br0 = 0.0, br1 = 0.0, bl0 = 0.0, bl1 = 0.0;
+    for (int q = 0; q < rr; q++) { br0 = std::fma(c.gr[q][0], g[nb - 1 - q], br0); br1 = std::fma(c.gr[q][1], g[nb - 1 - q], br1); }
+    for (int q = 0; q < rl; q++) { bl0 = std::fma(c.gl[q][0], g[q], bl0); bl1 = std::fma(c.gl[q][1], g[q], bl1); }
+    double y1 = 0.0, y2 = 0.0, y3 = 0.0;
+    for (int i = 0; i < n; i++) {
+        double s = g[rl + i];
+        if (i == 0) s += bl0;
+        if (i == 1) s += bl1;
+        if (i == n - 1) s += br0;
+        if (i == n - 2) s += br1;
+        const double *l = F + (size_t)i * 4;
+        double t = std::fma(-l[2], y1, -s);
+        t = std::fma(-l[1], y2, t);
+        t = std::fma(-l[0], y3, t);
+        const double y = t * l[3];
+        y3 = y2; y2 = y1; y1 = y;
+        a[rl + i] = y;
+    }
+    double x1 = 0.0, x2 = 0.0, x3 = 0.0, xl0 = 0.0, xl1 = 0.0, xr0 = 0.0, xr1 = 0.0;
+    const double zero[4] = {0.0, 0.0, 0.0, 0.0};
+    const double *f1 = zero, *f2 = zero, *f3 = zero;
+    for (int i = n - 1; i >= 0; i--) {
+        const double *l = F + (size_t)i * 4;
+        double t = std::fma(-f1[2], x1, a[rl + i]);
+        t = std::fma(-f2[1], x2, t);
+        t = std::fma(-f3[0], x3, t);
+        const double x = t * l[3];
+        x3 = x2; x2 = x1; x1 = x;
+        f3 = f2; f2 = f1; f1 = l;
+        a[rl + i] = x;
+        if (i == 0) xl0 = x;
+        if (i == 1) xl1 = x;
+        if (i == n - 1) xr0 = x;
+        if (i == n - 2) xr1 = x;
+    }
+    for (int q = 0; q < rl; q++) a[q] = std::fma(c.gl[q][1], xl1, c.gl[q][0] * xl0);
+    for (int q = 0; q < rr; q++) a[nb - 1 - q] = std::fma(c.gr[q][1], xr1, c.gr[q][0] * xr0);
 }
 
 // ---------------------------------------------------------------------------------------------- Chebyshev

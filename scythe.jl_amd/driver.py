@@ -492,6 +492,31 @@ class ModelRun:
                 held[sel] = True
         return out, held
 
+    # the wind variables (u, v) of the equation sets that have a horizontal wind by name
+    _WIND = {"Oneway_ShallowWater_Slab": ("u", "v"), "Twoway_ShallowWater_Slab": ("u", "v"), "LinearShallowWaterRL": ("u", "v")}
+
+    def _invert_wind(self, kind, u, v, alpha, into, var):
+        if self.num_tiles > 1:
+            raise ValueError("%s: one-tile patches only (num_tiles = %d)" % (kind, self.num_tiles))
+        if u is None or v is None:
+            if self.model.equation_set not in self._WIND:
+                raise ValueError("%s: name the wind variables u and v of equation set %r" % (kind, self.model.equation_set))
+            u, v = self._WIND[self.model.equation_set]
+        self._check_stream()
+        return self.tiles[0].invert((kind, u, v), alpha, into, var)
+
+    def streamfunction(self, u=None, v=None, alpha=0.0, into=None, var=1):
+        """The streamfunction psi of the wind, lap psi = vorticity, solved on the device from the A coefficients of time n
+        (Grid.invert): returns the Grid that holds psi (a cached one-variable companion unless `into` names one; psi = 0 at the outer
+        edge by default).  The rotational wind is (-psi_l / r, psi_r).  u, v: variable names or 1-based indices; the slab and linear
+        shallow-water sets know theirs.  One-tile RL / RLZ patches."""
+        return self._invert_wind("vorticity", u, v, alpha, into, var)
+
+    def velocity_potential(self, u=None, v=None, alpha=0.0, into=None, var=1):
+        """The velocity potential chi of the wind, lap chi = divergence (Grid.invert); the divergent wind is (chi_r, chi_l / r).
+        Arguments as for streamfunction.  With into=None it shares streamfunction's companion: pass a Grid of your own to keep both."""
+        return self._invert_wind("divergence", u, v, alpha, into, var)
+
     def _tiles_in_order(self):
         """the local tiles by tile number"""
         return [g for _, g in sorted(zip(self.tile_ids, self.tiles), key=lambda tg: tg[0])]

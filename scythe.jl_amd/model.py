@@ -241,6 +241,8 @@ class Grid:
             storage=patch.storage)
 
     def close(self):
+        for g in self.__dict__.pop("_companions", {}).values():
+            g.close()
         if getattr(self, "_h", None):
             self._lib.sx_destroy(self._h)
             self._h = None
@@ -401,6 +403,33 @@ class Grid:
     def set_parcel_state(self, blob):
         b = np.ascontiguousarray(blob, dtype=np.float64)
         L.check(self._lib.sx_parcels_set_state(self._h, b.ctypes.data_as(L.P_D), b.size))
+
+    # -- elliptic inversion (sx_elliptic_solve)
+    def invert(self, rhs, alpha=0.0, into=None, var=1):
+        """Solve (lap_h - alpha) psi = f on the device from the A coefficients the tile holds now (sx_elliptic_solve) and write the
+        A coefficients of psi into variable `var` (a name or a 1-based index) of the Grid `into`; returns that Grid, on which
+        evaluate, harmonics, spectrum and tileTransform_ + physical then sample psi and its derivatives.
+        rhs = ("field", f), ("vorticity", u, v) or ("divergence", u, v), the variables by name or 1-based index: f itself, or the
+        vorticity v_r + v / r - u_l / r resp. the divergence u_r + u / r + v_l / r of the wind (u, v) (RL / RLZ grids).
+        into=None makes a one-variable companion (companion_grid: psi = 0 at the outer edge, regular at the centre, the vertical
+        conditions of the first source variable) on first use and keeps it; into=self writes a spare variable of this Grid.
+        The boundary conditions of psi are those of the destination variable.  One-tile patches only."""
+        if not isinstance(rhs, (tuple, list)) or not rhs or rhs[0] not in L.ELL_KIND or len(rhs) != (2 if rhs[0] == "field" else 3):
+            raise ValueError("rhs must be ('field', f), ('vorticity', u, v) or ('divergence', u, v)")
+        src = [self._parcel_var(v) for v in rhs[1:]]
+        if into is None:
+            names = self.patch_params.var_names()
+            if not 1 <= src[0] <= len(names):
+                raise ValueError("variable index %d out of range" % src[0])
+            n0 = names[src[0] - 1]
+            key = (bc_name((self.patch_params.BCB or {}).get(n0, "R0"), _CHEB_BCS), bc_name((self.patch_params.BCT or {}).get(n0, "R0"), _CHEB_BCS))
+            cache = self.__dict__.setdefault("_companions", {})
+            if key not in cache:
+                cache[key] = companion_grid(self.patch_params, bcb=key[0], bct=key[1])
+            into = cache[key]
+        dst = into.patch_params.vars[var] if isinstance(var, str) else int(var)
+        L.check(self._lib.sx_elliptic_solve(self._h, L.ELL_KIND[rhs[0]], src[0], src[1] if len(src) > 1 else 0, float(alpha), into._h, dst))
+        return into
 
     def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
         """The azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: complex128 ndarray indexed
@@ -619,6 +648,30 @@ def createGrid(gp: GridParameters, model: Optional[ModelParameters] = None):
     if gp.geometry == "Z":
         raise ValueError("Z column model not implemented yet")     # src/spectralGrid.jl:86-88
     return Grid(gp, model)
+
+
+def companion_grid(gp: GridParameters, bcl="R1T0", bcl_k0="R1T1", bcr="R1T0", bcb="R0", bct="R0", name="psi"):
+    """A one-variable Grid (no equation set) of the same geometry as the patch `gp`, to receive the solution of Grid.invert.
+    The defaults pose the streamfunction / velocity potential of a vortex: zero at the outer edge (bcr), the wavenumbers k >= 1
+    zero at the centre (bcl), the azimuthal mean with zero slope there (bcl_k0).  bcb / bct must be those of the source variables."""
+    one = GridParameters(geometry=gp.geometry, xmin=gp.xmin, xmax=gp.xmax, num_cells=gp.num_cells, l_q=gp.l_q, BCL={name: bcl},
+                         BCR={name: bcr}, BCL_k0={name: bcl_k0}, zmin=gp.zmin, zmax=gp.zmax, zDim=gp.zDim, b_zDim=gp.b_zDim,
+                         BCB={name: bcb}, BCT={name: bct}, vars={name: 1}, ring_uniform_L=gp.ring_uniform_L)
+    return Grid(one, None)
+
+
+def elliptic_check(patch: GridParameters, var, k, alpha, g):
+    """The host statement of Grid.invert for ONE right-hand side column g [num_cells + 3] and wavenumber k, with the boundary
+    conditions of variable `var` (name or 1-based index) of the patch: a = Gamma_k^T K_k^-1 (-Gamma_k g) through the factors the
+    device kernel applies (sx_elliptic_check: no handle, no device).  Raises what Grid.invert would refuse of the patch."""
+    d, keep = grid_desc(patch)
+    v = patch.vars[var] if isinstance(var, str) else int(var)
+    rhs = np.ascontiguousarray(g, dtype=np.float64)
+    if rhs.shape != (patch.num_cells + 3,):
+        raise ValueError("g must have num_cells + 3 entries")
+    a = np.zeros_like(rhs)
+    L.check(L.load().sx_elliptic_check(C.byref(d), v, int(k), float(alpha), rhs.ctypes.data_as(L.P_D), a.ctypes.data_as(L.P_D)))
+    return a
 
 
 def getGridpoints(grid: Grid):
