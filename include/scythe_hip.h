@@ -462,6 +462,78 @@ int sx_reduce_weights(const sx_grid_desc *grid, double *w_r /*[3 tile_num_cells]
 int sx_reduce_planes(const sx_grid_desc *grid, int32_t source, int32_t n_terms, const int32_t *terms,
                      int32_t n_out, int32_t *planes /*[16][2]*/, int32_t *n_planes);
 
+/* --- extrema of field programs, refined to sub-grid accuracy -----------------------------------------------------------
+ * How strong is the vortex and where is it: the extrema of a field program over the gridpoints with their locations (sx_extrema), and
+ * the refinement of a gridpoint extremum to the stationary point of the continuous spectral function (sx_extremum_refine).
+ *
+ * sx_extrema.  Program and source are exactly those of sx_reduce (the same terms[n_terms][11], the same limits, SX_REDUCE_PHYSICAL /
+ * SX_REDUCE_STATE, validated by sx_reduce_planes itself: whatever sx_reduce refuses is refused here, before anything is written).
+ * Output o at a gridpoint is q_o = sum of its terms coef r^p prod field, in plain fp64 in term order starting from +0.0 (nothing is
+ * summed across points); with storage_f32 the derivative slots are read in the type they are stored in.
+ * SX_EXT_DOMAIN: val[2, n_out], idx[2, n_out] column-major, row 0 the minimum and row 1 the maximum over this tile's gridpoints.
+ * SX_EXT_AZIMUTH: val[2, tile ring, level, n_out] and idx of the same shape, the ring faster than the level as in sx_reduce: minimum and
+ * maximum over lambda at every ring and level (R / RZ grids: the pointwise value and its own index).
+ * idx is the 0-based row of sx_get_gridpoints: pt = (first[ring] + l) * zDim + z.
+ * Order.  Candidates are compared as (value, index): ties go to the lowest point index, -0.0 == +0.0 is a tie (val is the value AT idx, up to the sign of a zero: an output starts from +0.0, so -0.0 comes back as +0.0),
+ * and a NaN comes before every number: if the integrand is NaN at any point of a set, both results of that set are NaN with idx the
+ * lowest NaN point (Julia's findmax).  This order is total, so folding with it is associative and commutative: the result is unique,
+ * not merely repeatable - it cannot depend on the launch shape, the ring pieces or the workgroup count.  No atomics.
+ * Runs on the handle's stream and returns after the copy-out; reads only: `physical`, var_np1, the tendency history, A, B, parcels and
+ * captured graphs stay as they are, and it does not run the tile transform.  sx_kernel_bytes("k_extrema") gives the planes named x
+ * n_points x their element size of the last call.
+ *
+ * sx_extremum_refine finds, for the value slot of variable var (1-based), the stationary point of u(r, lambda, z) nearest to each of
+ * the n start points start[n, n_coord] (column-major, the coordinates of sx_get_gridpoints) by a safeguarded Newton iteration that
+ * runs inside ONE kernel launch (k_refine), one workgroup per point.  u and its 9 derivatives of order <= 2 (the mixed ones included)
+ * are summed from the A coefficients the handle holds now with the SX_EVAL_ALL_K truncation (smooth in r, as for the parcels) and
+ * sx_evaluate's vertical series and boundary-condition projection.  Lane count and reduction order are those of k_parcels, chosen from
+ * the grid alone: a point's result is bitwise independent of the other points of the call.  lambda of a start within [-2 pi, 2 pi] (every
+ * gridpoint's) is used as given, so a frozen lambda comes back bitwise; outside, it is reduced into (-pi, pi] in extended precision on the
+ * host; a lambda that moves is kept in (-pi, pi].  Every iteration evaluates the derivatives at the position and takes the step of sx_newton_step;
+ * after the last step one more evaluation is made, so that value[n] and grad[n, n_coord] (u_r[, u_lambda][, u_z], native coordinates,
+ * as the r, l, z slots of sx_evaluate) are those AT pos[n, n_coord].  iters[n] counts the steps taken.
+ * free_mask names the coordinates that move; a frozen coordinate keeps its start value (freeze z when the gridpoint extremum sits on
+ * the top or bottom level, freeze lambda for the radius of maximum wind along a ray).  free_mask == 0 evaluates value and gradient at
+ * the starts: status 0, iters 0.  tol <= 0 selects 1e-9, max_iter <= 0 selects 20.
+ * status:  0 converged, pos = the stationary point;  1 the step left the tile radially, 2 vertically: pos = the last inside position;
+ *   3 inside the pole zone (r < 1e-6 DX on an RL / RLZ tile whose first cell starts at xmin == 0, with r and lambda free): pos as it
+ *   is - the Cartesian transform divides by r and has no accuracy left there, and stopping bounds the error at 1e-6 DX, which is where
+ *   an axisymmetric vortex centred on the pole ends; a start at r == 0 returns 3 at once;  4 the reduced Hessian is not definite in
+ *   the sense `want` asks for (SX_EXT_MAX: every pivot of its L D L^T < 0; SX_EXT_MIN: > 0; SX_EXT_ANY: finite and non-zero), or the
+ *   step is not finite: no step is taken, pos = the current position;  5 max_iter steps taken: pos = the last position.
+ * Refused, with a message and before anything is written: a null pointer with n > 0; var out of range; want not in {-1, 0, 1}; a
+ * free_mask bit for a coordinate the geometry lacks (or an unknown bit); a NaN / Inf or out-of-range start (as sx_evaluate); a
+ * non-finite tol; a handle that is not a one-tile patch; a grid whose weights do not fit the 64 KB of LDS of one workgroup:
+ * 2 (kDim + 1) + zDim + 3 b_zDim + 48 > 8192 doubles.
+ * Reads A only (a deferred diagnostic variable is brought up to date first, as for every reader of A): `physical`, var_np1, the
+ * tendency history, the B arrays, parcels and captured graphs stay bitwise as they are.  sx_kernel_bytes("k_refine") gives the A bytes of
+ * the last call: 4 node rows x the variable's columns (the padding block left out) x evaluations (steps + 1), summed over the points.
+ *
+ * sx_newton_step is lane 0's arithmetic on the host (pure helper, no handle and no device; the same function compiled for both): from
+ * pos[n_coord] and d[10] = u, u_r, u_l, u_z, u_rr, u_rl, u_rz, u_ll, u_lz, u_zz (entries of a coordinate the geometry lacks: 0) it
+ * forms the step and the decision; *status = -1 means "took a step, go on".
+ *   Coordinates: the free native ones, except that on RL / RLZ with r and lambda both free the (r, lambda) block is transformed to
+ *   Cartesian (X, Y) by the chain rule - u_X = u_r c - u_l s / r, u_XX = c^2 u_rr - 2 s c a + s^2 b, u_YY = s^2 u_rr + 2 s c a + c^2 b,
+ *   u_XY = s c (u_rr - b) + (c^2 - s^2) a with a = u_rl / r - u_l / r^2, b = u_r / r + u_ll / r^2, u_Xz = u_rz c - u_lz s / r and the Y
+ *   counterparts - and the step is taken in (X, Y[, z]), so the centre is an ordinary point; afterwards r = hypot, lambda = atan2
+ *   kept in (-pi, pi], 0 at r == 0.  Rows and columns of frozen coordinates are deleted, the <= 3 x 3 system H step = -grad is solved
+ *   by L D L^T without pivoting, and the pivots decide the definiteness.
+ *   Safeguards: the whole step is scaled by ONE factor so that its horizontal length (hypot(dX, dY), |dr|, or r |dlambda| when only
+ *   lambda is free) is <= DX and |dz| <= (zmax - zmin) / 8.  Converged (status 0, new_pos = the position after the step): horizontal
+ *   length <= tol DX and |dz| <= tol (zmax - zmin).  Leaving (1, 2; radially wins) and the other stops return new_pos = pos.
+ * Refused: a null pointer; what every host helper refuses of a descriptor; want, free_mask, tol as above; a NaN / Inf or out-of-range
+ * pos. */
+enum { SX_EXT_DOMAIN = 0, SX_EXT_AZIMUTH = 1 };
+enum { SX_EXT_MIN = -1, SX_EXT_ANY = 0, SX_EXT_MAX = 1 };
+enum { SX_EXT_FREE_R = 1, SX_EXT_FREE_L = 2, SX_EXT_FREE_Z = 4 };
+int sx_extrema(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const double *coef, const int32_t *terms,
+               int32_t n_out, double *val, int64_t *idx);
+int sx_extremum_refine(sx_handle *h, int32_t var, int32_t want, int32_t free_mask, double tol, int32_t max_iter,
+                       int64_t n, const double *start /*[n, n_coord]*/, double *pos /*[n, n_coord]*/, double *value /*[n]*/,
+                       double *grad /*[n, n_coord]*/, int32_t *status /*[n]*/, int32_t *iters /*[n]*/);
+int sx_newton_step(const sx_grid_desc *grid, int32_t want, int32_t free_mask, double tol, const double *pos /*[n_coord]*/,
+                   const double *d /*[10]*/, double *new_pos /*[n_coord]*/, int32_t *status);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

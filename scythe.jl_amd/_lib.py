@@ -16,6 +16,9 @@ SPEC_KIND = {"ring": 0, "domain": 1}             # SX_SPEC_RING / SX_SPEC_DOMAIN
 ELL_KIND = {"field": 0, "vorticity": 1, "divergence": 2}    # SX_ELL_*
 REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_AZIMUTH
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
+EXT_KIND = {"domain": 0, "azimuth": 1}           # SX_EXT_DOMAIN / SX_EXT_AZIMUTH
+EXT_WANT = {"min": -1, "any": 0, "max": 1}       # SX_EXT_MIN / SX_EXT_ANY / SX_EXT_MAX
+EXT_FREE = {"r": 1, "l": 2, "z": 4}              # SX_EXT_FREE_R / SX_EXT_FREE_L / SX_EXT_FREE_Z
 SLOTS = {"R": ["", "r", "rr"], "RZ": ["", "r", "rr", "z", "zz"], "RL": ["", "r", "rr", "l", "ll"],
          "RLZ": ["", "r", "rr", "l", "ll", "z", "zz"]}     # derivative slots of `physical` by geometry
 PARAM_ORDER = ["g", "K", "Cd", "Hfree", "Hb", "f", "S1", "c_0", "Kh", "Um", "Vm", "Pxi_bar", "H"]
@@ -129,6 +132,9 @@ SYMBOLS = {
     "sx_reduce": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D]),
     "sx_reduce_weights": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, P_D]),
     "sx_reduce_planes": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32, P_I32]),
+    "sx_extrema": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D, P_I64]),
+    "sx_extremum_refine": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, P_D, P_D, P_D, P_D, P_I32, P_I32]),
+    "sx_newton_step": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_double, P_D, P_D, P_D, P_I32]),
 }
 
 _lib = None

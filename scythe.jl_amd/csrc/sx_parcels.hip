@@ -16,9 +16,7 @@
 
 namespace sx {
 
-constexpr int PARCEL_T = 256;             // lanes per parcel on grids with many columns (the bench grid: ~11,000 per variable)
-constexpr int PARCEL_T_SMALL = 64;        // one wave: rl_cha_bell2024's 601 columns are 10 per lane
-constexpr int PARCEL_WAVE_COLS = 1024;
+// PARCEL_T, PARCEL_T_SMALL, PARCEL_WAVE_COLS and parcel_threads: sx_internal.hpp (k_refine of sx_extrema.hip takes the same lanes)
 constexpr size_t PARCEL_LDS_MAX = 64 * 1024;
 static const double PARCEL_MAGIC = 7.7012e7;
 constexpr int PARCEL_HDR = 6;             // blob header: magic, n, n_coord, var_r, var_l, var_z
@@ -187,7 +185,6 @@ struct ParcelState : DiagState {
 
 static ParcelState *pstate(const sx_handle *h) { return diag_state<ParcelState>(h, DIAG_PARCELS); }
 
-static int parcel_threads(const sx_handle *h) { return (int64_t)h->Zb * h->K2 <= PARCEL_WAVE_COLS ? PARCEL_T_SMALL : PARCEL_T; }
 static size_t parcel_lds(const sx_handle *h) {
     return sizeof(double) * (2 * (size_t)(h->kDim + 1) + (h->has_z ? h->nz : 1) + 3 * (size_t)h->Zb + 3 * (PARCEL_T / 64));
 }

@@ -12,27 +12,14 @@
 //
 // The program is a kernel ARGUMENT (constant memory, scalar loads: its indices are uniform), terms sorted by output so that the
 // accumulators are indexed statically.
-#include "sx_internal.hpp"
+#include "sx_redprog.hpp"
 #include <algorithm>
 #include <cstring>
 
 namespace sx {
 
-constexpr int RED_T = 256;          // threads per workgroup of k_reduce
 constexpr int RED_TF = 1024;        // threads per workgroup of k_reduce_final's domain sum
-constexpr int RED_ITERS = 32;       // strides of a workgroup over its piece of a ring: pieces per ring = ceil(strides / RED_ITERS)
-constexpr int RED_TERMS = 64, RED_OUT = 16, RED_PLANES = 16, RED_FACTORS = 4, RED_TERM_W = 11;
-
-struct RedProg {
-    double coef[RED_TERMS];
-    int8_t p[RED_TERMS], nf[RED_TERMS];
-    uint8_t f[RED_TERMS][RED_FACTORS];      // plane of each factor
-    uint8_t start[RED_OUT + 1];             // terms of output o: [start[o], start[o + 1])
-    uint8_t pvar[RED_PLANES], pslot[RED_PLANES];   // 0-based variable, slot
-    int n_planes, n_out;
-};
-
-struct RedItem { int ring, lam0, nlam, pad; };
+// RED_T, RED_ITERS, the limits, RedProg, RedItem, the work list and the plane loads: sx_redprog.hpp (shared with sx_extrema)
 
 struct ReduceState : DiagState {
     DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth) or whole rings
@@ -61,24 +48,12 @@ template <class ST>
 __device__ inline void reduce_point(const Planes<ST> &P, int V, int64_t N, int64_t pt, double r, const RedProg &g, double (&hi)[RED_OUT],
                                     double (&lo)[RED_OUT]) {
     double val[RED_PLANES];
-#pragma unroll
-    for (int j = 0; j < RED_PLANES; j++) {
-        val[j] = 0.0;
-        if (j < g.n_planes) {
-            const int v = g.pvar[j], s = g.pslot[j];
-            val[j] = s == 0 ? P.val[(int64_t)v * N + pt] : (double)P.der[((int64_t)(s - 1) * V + v) * N + pt];
-        }
-    }
+    red_load_planes<ST>(P, V, N, pt, g, val);
     const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
 #pragma unroll
     for (int o = 0; o < RED_OUT; o++) {
         for (int t = g.start[o]; t < g.start[o + 1]; t++) {       // empty at o >= n_out
-            const int p = g.p[t], nf = g.nf[t];
-            double x = g.coef[t];
-            if (p != 0) x *= p == 1 ? r : p == 2 ? rr : p == -1 ? ri : rri;
-#pragma unroll
-            for (int f = 0; f < RED_FACTORS; f++)
-                if (f < nf) x *= val[g.f[t][f]];
+            const double x = red_term(g, t, val, r, rr, ri, rri);
             dd_add(hi[o], lo[o], x);
         }
     }
@@ -184,18 +159,8 @@ static ReduceState *reduce_state(sx_handle *h) {
     if (h->diag[DIAG_REDUCE]) return diag_state<ReduceState>(h, DIAG_REDUCE);
     std::unique_ptr<ReduceState> st(new ReduceState());
     std::vector<RedItem> items;
-    std::vector<int> first(h->nrings + 1, 0);
-    const int G = RED_T / h->nz;         // lambdas per stride (nz <= 256: sx_create)
-    for (int i = 0; i < h->nrings; i++) {
-        first[i] = (int)items.size();
-        const int L = h->hL[i];
-        const int strides = (L + G - 1) / G, pieces = h->has_l ? (strides + RED_ITERS - 1) / RED_ITERS : 1;
-        for (int c = 0; c < pieces; c++) {
-            const int l0 = (int)((int64_t)L * c / pieces), l1 = (int)((int64_t)L * (c + 1) / pieces);
-            items.push_back(RedItem{i, l0, l1 - l0, 0});
-        }
-    }
-    first[h->nrings] = (int)items.size();
+    std::vector<int> first;
+    red_items(h, items, first);
     std::vector<double> wr(h->nrings), wl(h->nrings), wz(h->nz, 1.0), wrl(h->nrings);
     reduce_weights(eval_geom_of(h), wr.data(), wl.data(), wz.data());
     for (int i = 0; i < h->nrings; i++) wrl[i] = wr[i] * wl[i];
@@ -292,30 +257,11 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
 
     // the program as the kernel reads it: terms by output (their order within an output kept), factors as plane numbers
     RedProg prog;
-    std::memset(&prog, 0, sizeof(prog));
-    prog.n_planes = n_planes; prog.n_out = n_out;
-    for (int j = 0; j < n_planes; j++) { prog.pvar[j] = (uint8_t)(planes[j][0] - 1); prog.pslot[j] = (uint8_t)planes[j][1]; }
-    int k = 0;
-    for (int o = 0; o < n_out; o++) {
-        prog.start[o] = (uint8_t)k;
-        for (int t = 0; t < n_terms; t++) {
-            const int32_t *q = terms + (size_t)t * RED_TERM_W;
-            if (q[0] != o) continue;
-            prog.coef[k] = coef[t]; prog.p[k] = (int8_t)q[1]; prog.nf[k] = (int8_t)q[2];
-            for (int f = 0; f < q[2]; f++) {
-                int j = 0;
-                while (planes[j][0] != q[3 + f] || planes[j][1] != q[3 + RED_FACTORS + f]) j++;
-                prog.f[k][f] = (uint8_t)j;
-            }
-            k++;
-        }
-    }
-    for (int o = n_out; o <= RED_OUT; o++) prog.start[o] = (uint8_t)k;
+    red_pack(prog, planes, n_planes, n_terms, coef, terms, n_out);
 
     const size_t n_res = kind == SX_REDUCE_AZIMUTH ? (size_t)h->nrings * h->nz * n_out : (size_t)n_out;
     if (!st->d_part.grow((size_t)st->n_items * n_out * h->nz, "sx_reduce") || !st->d_out.grow(n_res, "sx_reduce")) return 1;
-    st->last_bytes = 0;
-    for (int j = 0; j < n_planes; j++) st->last_bytes += (double)h->N * (source == SX_REDUCE_PHYSICAL && h->f32 && planes[j][1] > 0 ? 4.0 : 8.0);
+    st->last_bytes = red_bytes(h, source, planes, n_planes);
 
     timer_begin(h, timer_id(h, "k_reduce"));
     const unsigned flat_blocks = (unsigned)((h->N + RED_T - 1) / RED_T);

@@ -6,12 +6,15 @@ patch solve on every worker (:285).  Here a tile is a libscythe_hip handle and t
 buffers: halo rows by point-to-point send/recv, owned rows by an in-place all-gather, both over
 torch.distributed (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU tests).
 """
+import collections
 import os
 import time
 
 import numpy as np
 
 from .model import (Grid, GridParameters, ModelParameters, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
+
+Located = collections.namedtuple("Located", "pos value status")
 
 
 class PatchLayout:
@@ -362,6 +365,7 @@ class ModelRun:
                 raise ValueError("exchange must be 'a2a', 'iface' or 'gather'")
         self.t = 0
         self._ring_axes = None      # azimuthal_mean's (r, z) axes, formed on first use
+        self._points = None         # the local tiles' gridpoints [n, n_coord] in tile order (extrema's rows), formed on first use
         self._parcels = False       # set_parcels attached a parcel set: step() moves it
 
     def _bind_streams(self, device):
@@ -553,6 +557,76 @@ class ModelRun:
             means.append(g.reduce(terms, "azimuth", source))
         rs, z = self._ring_axes
         return rs.copy(), z.copy(), np.concatenate(means, axis=0)
+
+    def gridpoints(self):
+        """The gridpoints of the local tiles in tile order, [n, n_coord]: the rows extrema's idx names (formed once and kept)"""
+        if self._points is None:
+            pts = [getGridpoints(g) for g in self._tiles_in_order()]
+            self._points = np.concatenate([p.reshape(len(p), -1) for p in pts], axis=0)
+        return self._points
+
+    def extrema(self, terms, kind="domain", source="physical"):
+        """Minimum and maximum of field programs over the local tiles, with their locations (Grid.extrema): (val, idx), idx a row
+        of self.gridpoints().  kind="domain": [2, n_out], the tile results folded in tile order with Grid.extrema's own order
+        (value, then the lower row; a NaN wins).  kind="azimuth": [2, rings, levels, n_out], the rings of the local tiles
+        concatenated in tile order.  source="physical" runs tileTransform! on every local tile first."""
+        vals, idxs, off = [], [], 0
+        for g in self._tiles_in_order():
+            if source == "physical":
+                g.tileTransform_()
+            v, i = g.extrema(terms, kind, source)
+            vals.append(v)
+            idxs.append(i + off)
+            off += g.N
+        if kind != "domain":
+            return np.concatenate(vals, axis=1), np.concatenate(idxs, axis=1)
+        val, idx = vals[0].copy(), idxs[0].copy()
+        for v, i in zip(vals[1:], idxs[1:]):       # later tiles hold higher rows: they win only when strictly better, or NaN first
+            for w, better in ((0, v[0] < val[0]), (1, v[1] > val[1])):
+                take = (better | np.isnan(v[w])) & ~np.isnan(val[w])
+                val[w], idx[w] = np.where(take, v[w], val[w]), np.where(take, i[w], idx[w])
+        return val, idx
+
+    def _one_tile(self, what):
+        if self.num_tiles > 1:
+            raise ValueError("%s: one-tile patches only (num_tiles = %d)" % (what, self.num_tiles))
+        self._check_stream()
+        return self.tiles[0]
+
+    def locate(self, var, want="min", source="state", refine=True):
+        """The one-call centre or peak: one domain scan of variable `var` (name or 1-based index) for its minimum (want="min") or
+        maximum ("max"), then the refinement of that gridpoint to the stationary point of the continuous state
+        (Grid.refine_extremum) with every coordinate free - z frozen when the gridpoint lies on the lowest or highest level.
+        Returns Located(pos [n_coord], value, status): status as refine_extremum gives it; refine=False returns the gridpoint, its
+        value and status 0.  source="state" scans var_np1 (no transform), "physical" runs tileTransform! first.  One-tile patches."""
+        if want not in ("min", "max"):
+            raise ValueError("want must be 'min' or 'max'")
+        g = self._one_tile("locate")
+        val, idx = self.extrema([(0, 1.0, 0, [(var, "")])], "domain", source)
+        w = 0 if want == "min" else 1
+        row = int(idx[w, 0])
+        start = self.gridpoints()[row]
+        if not refine:
+            return Located(start.copy(), float(val[w, 0]), 0)
+        free = self.patch.geometry.lower()
+        if "z" in free and row % self.patch.zDim in (0, self.patch.zDim - 1):
+            free = free.replace("z", "")
+        res = g.refine_extremum(var, start[None, :], want, free)
+        return Located(res.pos[0].copy(), float(res.value[0]), int(res.status[0]))
+
+    def radius_of_maximum(self, var, level=None, source="state"):
+        """The radius of the maximum of variable `var` (the radius of maximum wind for the tangential wind): the azimuth kind's
+        maxima over lambda at every ring (Grid.extrema) on `level` (0-based; None: the level that holds the largest), the ring of
+        the largest, then the refinement along that ray - lambda and z frozen at the gridpoint's (Grid.refine_extremum).
+        Returns Located(pos [n_coord], value, status); pos[0] is the radius.  One-tile patches."""
+        g = self._one_tile("radius_of_maximum")
+        val, idx = self.extrema([(0, 1.0, 0, [(var, "")])], "azimuth", source)
+        mx = val[1, :, :, 0] if level is None else val[1, :, int(level):int(level) + 1, 0]
+        ring, lev = np.unravel_index(int(np.argmax(mx)), mx.shape)
+        row = int(idx[1, ring, lev if level is None else int(level), 0])
+        start = self.gridpoints()[row]
+        res = g.refine_extremum(var, start[None, :], "max", "r")
+        return Located(res.pos[0].copy(), float(res.value[0]), int(res.status[0]))
 
     def spectrum(self, pairs, kind="ring"):
         """Azimuthal power and cross spectra over the local tiles (Grid.spectrum; reads A: no transform is run).  kind="domain":

@@ -10,6 +10,7 @@ underscore.  Every object that computes anything is a thin wrapper over a libscy
   createModelTile     src/semiimplicit.jl:44-124
   advanceTimestep     src/semiimplicit.jl:301-332
 """
+import collections
 import ctypes as C
 import math
 from dataclasses import dataclass, field
@@ -485,6 +486,45 @@ class Grid:
                                     packed.ctypes.data_as(L.P_I32), n_out, out.ctypes.data_as(L.P_D)))
         return out
 
+    def extrema(self, terms, kind="domain", source="physical"):
+        """Minimum and maximum of field programs over the tile's gridpoints, with their locations, on the device (sx_extrema).
+        terms, source: as for reduce (the same programs, packed by pack_reduce_program).  Returns (val, idx): kind="domain":
+        float64 / int64 ndarrays [2, n_out], row 0 the minimum and row 1 the maximum; kind="azimuth": [2, tile rings, levels,
+        n_out], minimum and maximum over lambda at every ring and level.  idx holds 0-based rows of getGridpoints(self).  Ties go to
+        the lowest row (-0.0 == +0.0 is a tie); a NaN anywhere in a set makes both of its results NaN, with the lowest NaN row."""
+        coef, packed, n_out = pack_reduce_program(self.patch_params, terms)
+        if kind not in L.EXT_KIND or source not in L.REDUCE_SOURCE:
+            raise ValueError("kind must be 'domain' or 'azimuth', source 'physical' or 'state'")
+        nz = max(int(self.dims.zDim), 1)
+        shape = (2, n_out) if kind == "domain" else (2, int(self.dims.tile_rDim), nz, n_out)
+        val, idx = np.zeros(shape, order="F"), np.zeros(shape, dtype=np.int64, order="F")
+        L.check(self._lib.sx_extrema(self._h, L.EXT_KIND[kind], L.REDUCE_SOURCE[source], len(coef), coef.ctypes.data_as(L.P_D),
+                                     packed.ctypes.data_as(L.P_I32), n_out, val.ctypes.data_as(L.P_D), idx.ctypes.data_as(L.P_I64)))
+        return val, idx
+
+    def refine_extremum(self, var, points, want="max", free=None, tol=None, max_iter=None):
+        """The stationary point of variable `var` (a name or a 1-based index) nearest to each of `points` [n, n_coord], by Newton's
+        iteration on the continuous spectral state, on the device (sx_extremum_refine; reads the A coefficients the tile holds now).
+        want: "max", "min" or "any"; free: the coordinates that move, a string of r / l / z (default: all of the geometry) or a
+        mask of SX_EXT_FREE_* bits - a frozen coordinate keeps its start value.  Returns Refined(pos [n, n_coord], value [n],
+        grad [n, n_coord], status [n], iters [n]); status 0 converged, 1 / 2 left the tile radially / vertically, 3 inside the pole
+        zone, 4 Hessian not definite as `want` asks, 5 max_iter reached.  One-tile patches only."""
+        nc = int(self.dims.n_coord)
+        p = np.asarray(points, dtype=np.float64)
+        p = np.asfortranarray(p.reshape(-1, nc) if p.ndim != 2 else p)
+        if p.shape[1] != nc:
+            raise ValueError("points must have %d coordinate column(s)" % nc)
+        if want not in L.EXT_WANT:
+            raise ValueError("want must be 'max', 'min' or 'any'")
+        n = p.shape[0]
+        pos, grad = np.zeros((n, nc), order="F"), np.zeros((n, nc), order="F")
+        value, status, iters = np.zeros(n), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        L.check(self._lib.sx_extremum_refine(self._h, self._parcel_var(var), L.EXT_WANT[want], free_mask(self.patch_params, free),
+                                             0.0 if tol is None else float(tol), 0 if max_iter is None else int(max_iter), n,
+                                             p.ctypes.data_as(L.P_D), pos.ctypes.data_as(L.P_D), value.ctypes.data_as(L.P_D),
+                                             grad.ctypes.data_as(L.P_D), status.ctypes.data_as(L.P_I32), iters.ctypes.data_as(L.P_I32)))
+        return Refined(pos, value, grad, status, iters)
+
     # -- operators
     def spectralTransform_(self):
         L.check(self._lib.sx_spectral_transform(self._h))
@@ -752,6 +792,37 @@ def reduce_planes(patch: GridParameters, terms, source="physical", tile_cell0=0,
     L.check(L.load().sx_reduce_planes(C.byref(d), L.REDUCE_SOURCE[source], len(coef), packed.ctypes.data_as(L.P_I32), n_out,
                                       planes.ctypes.data_as(L.P_I32), C.byref(n)))
     return planes[:n.value].copy()
+
+
+# ----------------------------------------------------------------------------- extrema and their refinement (sx_extrema, sx_extremum_refine)
+Refined = collections.namedtuple("Refined", "pos value grad status iters")
+
+
+def free_mask(patch: GridParameters, free=None):
+    """SX_EXT_FREE_* mask from a string of r / l / z, a mask, or None = every coordinate of the geometry"""
+    if free is None:
+        free = patch.geometry.lower()
+    if isinstance(free, str):
+        if set(free) - set(L.EXT_FREE):
+            raise ValueError("free must be made of the letters r, l, z")
+        return sum(L.EXT_FREE[c] for c in set(free))
+    return int(free)
+
+
+def newton_step(patch: GridParameters, pos, d, want="max", free=None, tol=None, tile_cell0=0, tile_num_cells=None):
+    """One step of refine_extremum's iteration on the host (sx_newton_step): pos [n_coord], d [10] = u, u_r, u_l, u_z, u_rr, u_rl,
+    u_rz, u_ll, u_lz, u_zz -> (new_pos [n_coord], status), status -1 = took a step, go on."""
+    desc, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    p = np.ascontiguousarray(np.atleast_1d(pos), dtype=np.float64)
+    dd = np.ascontiguousarray(d, dtype=np.float64)
+    if len(p) != len(patch.geometry) or dd.shape != (10,):
+        raise ValueError("pos must have %d coordinate(s) and d 10 entries" % len(patch.geometry))
+    if want not in L.EXT_WANT:
+        raise ValueError("want must be 'max', 'min' or 'any'")
+    out, st = np.zeros(len(p)), C.c_int32(-2)
+    L.check(L.load().sx_newton_step(C.byref(desc), L.EXT_WANT[want], free_mask(patch, free), 0.0 if tol is None else float(tol),
+                                    p.ctypes.data_as(L.P_D), dd.ctypes.data_as(L.P_D), out.ctypes.data_as(L.P_D), C.byref(st)))
+    return out, int(st.value)
 
 
 # ----------------------------------------------------------------------------- azimuthal power and cross spectra (sx_spectrum)
