@@ -179,8 +179,13 @@ int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_
  *   SX_PLAN_ZINV     vertical inverse:  in = geometry, zDim, K2, storage_f32 == 2;  out = CT, grid_x
  *   SX_PLAN_PCR      parallel-cyclic-reduction solve:  in = largest block-row count of the spline classes, num_cells + 3, K2,
  *                    (variable, z-mode) groups of the launch;  out = R, log2 R, threads;  kernel: empty
+ *   SX_PLAN_FORWARD_CELLS  whether spectralTransform! runs as k_fl_forward_cells + k_nodes_z (the forward FFT kernel sums its ring spectra
+ *                    into the spline nodes itself; SX_SBW_MFMA=2: never; by default only on launches that fill a round of CUs with segments of at least 9 cells, SX_SBW_MFMA=3: wherever the kernels apply) and that pair's shapes:  in = geometry, zDim, b_zDim, K2,
+ *                    variables of the handle, tile cells, storage_f32 == 2, ring_uniform_L (0: native rings);
+ *                    out = taken (0 / 1), S (cells per radial segment), segments, threads, nodes per k_nodes_z workgroup, node runs;
+ *                    kernel: "k_fl_forward_cells<log2 L>", empty where the pair is not taken (SX_PLAN_FORWARD then names the launch)
  * Pure host helper (no handle, no device): the tests name the launch shapes they cover from it; never on the step path. */
-enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2 };
+enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2, SX_PLAN_FORWARD_CELLS = 3 };
 int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap);
 
 /* --- state in / out (host pointers, reference layouts) ------------------------------------------------------------- */
@@ -628,7 +633,9 @@ int sx_reset_timers(sx_handle *h);
 int sx_timer_only(sx_handle *h, const char *name);
 /* names[i] borrowed static strings; ms[i] accumulated milliseconds; calls[i] launches. Returns count via n. */
 int sx_get_timers(sx_handle *h, int32_t max, const char **names, double *ms, int64_t *calls, int32_t *n);
-/* algorithmic bytes of one launch of the named kernel (SURVEY.md 8(d) accounting), 0 if unknown */
+/* algorithmic bytes of one launch of the named kernel (SURVEY.md 8(d) accounting), 0 if unknown.  Three names report the handle's
+ * device allocations instead: "alloc.d_Fl" (ring spectra; 0 where k_fl_forward_cells + k_nodes_z are taken and they are never
+ * allocated), "alloc.d_Fn" (node spectra and edge partials of that pair; 0 otherwise), "alloc.total" (everything sx_create allocated) */
 int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes);
 
 #ifdef __cplusplus

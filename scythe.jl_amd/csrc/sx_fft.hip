@@ -671,6 +671,138 @@ k_fl_forward_fft(const double *__restrict__ np1, FT *__restrict__ Fl, const int 
     }
 }
 
+// Forward transform summed into the spline nodes where the spectrum is produced (uniform rings up to 256 points, 16-level chunks).
+// One workgroup = (16-level chunk, variable, radial segment of S cells).  It walks the segment's 3 S rings in ascending order; per ring
+// it does what k_fl_forward_fft does (tile in one burst of 16-byte non-temporal loads, transform through LDS, untangling of the two
+// packed levels, phase factor, 1 / L) but keeps the spectrum in registers: each lane multiplies its wavenumbers (k = t, t + T; two
+// levels each) by the ring's four radial weights wq * phi (k_sbw_mfma's) and adds them to the four open node sums of the current cell -
+// 4 nodes x 2 k x 2 levels x (re, im) = 32 doubles per lane.  Leaving cell c closes node c: it is stored once, [node][v][level][K2]
+// with 16-byte stores, and the sums move down by one.  The ring spectra (Fl) never exist.  Summation order per node is k_sbw_mfma's
+// (cells ascending, rings ascending); a node whose cells lie in two segments is the sum of two partials: the three nodes still open
+// at the end of a segment go to the side array Fe[segment][3] and k_nodes_z adds them to the next segment's first three nodes (the
+// last segment's are the tile's three trailing nodes and go to Fn).  No atomics, no memset, no warm-up cells.
+// Two LDS sets: ring i + 1 is staged into the other set, so one LDS-only workgroup barrier per ring orders everything - a set is
+// rewritten two rings after its last (wave-local) read, and the barrier of the ring in between lies between the two.  The next
+// ring's tile loads are issued before the current ring's transform and stay in flight across it.
+// Registers: the open node sums are 64 VGPRs and the tile in flight 16 on top of the transform's ~50: at the 128 of two 512-thread
+// workgroups per CU the kernel spilled 73 of them (45 without the tile in flight), and a spill reload drains the in-order memory
+// counter, so it runs as ONE workgroup per CU (186 VGPRs at 256 points, no scratch) and leans on the tile in flight for overlap.
+template <int LOGL>
+__global__ void __launch_bounds__((FftCfg<LOGL>::FNP * FftCfg<LOGL>::LPT < 64 ? 64 : FftCfg<LOGL>::FNP * FftCfg<LOGL>::LPT), 2)
+k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, double *__restrict__ Fe, const int *__restrict__ kmaxr,
+                   const int64_t *__restrict__ pstart, const double2 *__restrict__ twg, const int64_t *__restrict__ phoff,
+                   const double2 *__restrict__ ph, const double *__restrict__ phi, const double *__restrict__ wq,
+                   int V, int nz, int K2, int64_t N, int ncells, int S) {
+    constexpr int L = 1 << LOGL, T = FftCfg<LOGL>::LPT, NK = FftCfg<LOGL>::NK, PPT = L / T;
+    constexpr int FZC = FftCfg<LOGL>::FZC, FNP = FftCfg<LOGL>::FNP, LOGZ = FftCfg<LOGL>::LOGZ, SKEW = FftCfg<LOGL>::SKEW;
+    static_assert(LOGL <= 8 && NK == 2 && PPT == 4, "one butterfly per lane and pass: rings of at most 256 points");
+    typedef double dv2 __attribute__((ext_vector_type(2)));
+    extern __shared__ double2 smf[];
+    const int z0 = blockIdx.x * FZC, v = blockIdx.y, seg = blockIdx.z;
+    const int ca = seg * S, cb = min(ca + S, ncells);
+    const int tid = threadIdx.x;
+    const int f = tid / T, t = tid - f * T;
+    const bool active = f < FNP;                           // = tid < FNP * T: at 16 points half of the one wave has no transform
+    const int za = 2 * f;
+    const int zp = tid & (FNP - 1);
+    const int64_t plane = (int64_t)V * nz * K2;            // one node's [v][level][K2] spectra
+    Twiddles<LOGL> tw;
+    tw.template init<-1>(twg, t);
+    const double *xb = np1 + (int64_t)v * N + z0 + 2 * zp;
+    const double inv = 1.0 / L;
+    double acc[4][NK][4];                                  // [open node][wavenumber][level a re, im, level b re, im]
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+        for (int q = 0; q < NK; q++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) acc[j][q][e] = 0.0;
+    // the tile's FNP * L level pairs are PPT = 4 per staging thread: pair e = tid + i FNP T is levels (2 zp, 2 zp + 1) of ring point e / FNP
+    dv2 t2[PPT];
+    auto issue = [&](int ring) {
+        const double *x = xb + pstart[ring] * nz;
+#pragma unroll
+        for (int i = 0; i < PPT; i++)
+            t2[i] = __builtin_nontemporal_load(reinterpret_cast<const dv2 *>(x + (int64_t)((tid + i * FNP * T) >> (LOGZ - 1)) * nz));
+    };
+    auto store_node = [&](double *row, int j) {            // row: the node's [level z0][K2] of this variable
+        if (!active) return;
+#pragma unroll
+        for (int q = 0; q < NK; q++) {
+            const int k = t + q * T;
+            if (2 * k + 1 < K2) {
+                stpair(row + (int64_t)za * K2 + 2 * k, make_double2(acc[j][q][0], acc[j][q][1]));
+                stpair(row + (int64_t)(za + 1) * K2 + 2 * k, make_double2(acc[j][q][2], acc[j][q][3]));
+            }
+        }
+    };
+    const int64_t rowoff = ((int64_t)v * nz + z0) * K2;
+    int par = 0;
+    if (active) issue(ca * MUBAR);
+    for (int c = ca; c < cb; c++) {
+#pragma unroll 1
+        for (int mu = 0; mu < MUBAR; mu++) {
+            const int ring = c * MUBAR + mu;
+            double2 *set = smf + par * FNP * (L + SKEW);
+            par ^= 1;
+            if (active) {
+#pragma unroll
+                for (int i = 0; i < PPT; i++) set[zp * (L + SKEW) + ((tid + i * FNP * T) >> (LOGZ - 1))] = make_double2(t2[i].x, t2[i].y);
+            }
+            // this ring's phase factors in front of the next ring's tile: the memory counter retires in issue order, and the phase
+            // factors are waited for right after the transform while the tile may take until the next ring
+            const int km = kmaxr[ring];
+            const double2 *phr = ph + phoff[ring];
+            double2 phq[NK];
+#pragma unroll
+            for (int q = 0; q < NK; q++) phq[q] = phr[min(t + q * T, km)];      // beyond the truncation: a valid address, the value is dropped
+            asm volatile("" ::: "memory");
+            if (active && ring + 1 < cb * MUBAR) issue(ring + 1);
+            asm volatile("" ::: "memory");
+            lds_barrier();
+            double2 *X = set + (active ? f : 0) * (L + SKEW);
+            fft_inplace<LOGL, -1, true>(X, tw, t, active);
+            if (active) {
+                const double w = wq[ring];
+                const double wj[4] = {w * phi[(int64_t)ring * 4], w * phi[(int64_t)ring * 4 + 1], w * phi[(int64_t)ring * 4 + 2], w * phi[(int64_t)ring * 4 + 3]};
+#pragma unroll
+                for (int q = 0; q < NK; q++) {
+                    const int k = t + q * T;
+                    if (k > km) continue;                  // not part of this ring's spectrum
+                    const double2 wk = X[k], wn = X[(L - k) & (L - 1)];
+                    // Xa = (W_k + conj W_{-k}) / 2,  Xb = (W_k - conj W_{-k}) / (2i)
+                    double2 xa = make_double2(0.5 * (wk.x + wn.x), 0.5 * (wk.y - wn.y));
+                    double2 xb2 = make_double2(0.5 * (wk.y + wn.y), -0.5 * (wk.x - wn.x));
+                    double x4[4];
+                    if (k == 0) {
+                        x4[0] = xa.x * inv; x4[1] = 0.0; x4[2] = xb2.x * inv; x4[3] = 0.0;
+                    } else {
+                        const double2 pw = cconj(phq[q]);                   // e^{-ik off}
+                        xa = cmul(xa, pw);
+                        xb2 = cmul(xb2, pw);
+                        x4[0] = xa.x * inv; x4[1] = xa.y * inv; x4[2] = xb2.x * inv; x4[3] = xb2.y * inv;
+                    }
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+#pragma unroll
+                        for (int e = 0; e < 4; e++) acc[j][q][e] += wj[j] * x4[e];
+                }
+            }
+        }
+        // node c is complete as far as this segment goes; the three above it stay open
+        store_node(Fn + (int64_t)c * plane + rowoff, 0);
+#pragma unroll
+        for (int q = 0; q < NK; q++)
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                acc[0][q][e] = acc[1][q][e]; acc[1][q][e] = acc[2][q][e]; acc[2][q][e] = acc[3][q][e]; acc[3][q][e] = 0.0;
+            }
+    }
+    double *edge = (cb == ncells) ? Fn + (int64_t)ncells * plane : Fe + (int64_t)seg * 3 * plane;
+#pragma unroll
+    for (int j = 0; j < 3; j++) store_node(edge + (int64_t)j * plane + rowoff, j);
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 static int ilog2(int n) { int l = 0; while ((1 << l) < n) l++; return l; }
 
@@ -819,6 +951,34 @@ void launch_node_fft(sx_handle *h) {
     const int j0 = h->R_in / MUBAR;
     InvTarget tg{h->d_G, h->d_nphi, h->d_nkmax, h->d_npstart, h->d_nphoff, h->nbt - j0, h->nbt, h->NG, 1, j0};
     launch_inv_any(h, h->d_mask_node, tg);
+    timer_end(h);
+}
+
+template <int LOGL>
+static void launch_fwd_cells(sx_handle *h, const CellsPlan &p) {
+    const int L = 1 << LOGL;
+    const size_t lds = fft_lds(L, 2);
+    if (lds > 65536)
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_cells<LOGL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    dim3 g(h->nz / fft_fzc(L), h->v_cnt, p.segs);
+    // the variable window [v_lo, v_lo + v_cnt) through the base pointers, as in launch_fwd
+    const int64_t plane = (int64_t)h->V * h->nz * h->K2, flo = (int64_t)h->v_lo * h->nz * h->K2;
+    hipLaunchKernelGGL(k_fl_forward_cells<LOGL>, g, dim3(p.threads), lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N, h->d_Fn + flo,
+                       h->d_Fn + (int64_t)h->nbt * plane + flo, h->d_kmax, h->d_pstart, h->d_tw, h->d_phoff, h->d_ph, h->d_phi, h->d_wq,
+                       h->V, h->nz, h->K2, h->N, h->ncells, p.S);
+}
+
+void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {
+    const int id = timer_id(h, "k_fl_forward");
+    timer_begin(h, id);
+    switch (p.logL) {
+        case 4: launch_fwd_cells<4>(h, p); break;
+        case 5: launch_fwd_cells<5>(h, p); break;
+        case 6: launch_fwd_cells<6>(h, p); break;
+        case 7: launch_fwd_cells<7>(h, p); break;
+        default: launch_fwd_cells<8>(h, p); break;
+    }
+    HIPCHK(hipGetLastError());
     timer_end(h);
 }
 

@@ -252,7 +252,11 @@ struct Switches {
     int dft_classes = 0;    // SX_DFT_CLASSES=n: launch classes of the older DFT kernels (experiments; <= 0: the launcher's own count)
     int fuse_zinv = 0;      // SX_FUSE_ZINV=1: vertical inverse inside the node FFT kernel (measured slower: sx_fft.hip)
     int zinv_ct = 0;        // SX_ZINV_CT=n: column tiles per wave of k_zinv (A/B; values without a kernel take the default: plan_zinv)
-    int sbw_mfma = 1;       // k_sbw_mfma (matrix-core vertical contraction, operator in registers) for zDim 64 / 32 (SX_SBW_MFMA=0: k_sbw)
+    // k_sbw_mfma (matrix-core vertical contraction, operator in registers) for zDim 64 / 32 (SX_SBW_MFMA=0: k_sbw).  1 also takes the
+    // forward pair that sums the ring spectra into the spline nodes inside the FFT kernel where it applies (k_fl_forward_cells +
+    // k_nodes_z: plan_fwd_cells, by default on launches of the measured kind only); SX_SBW_MFMA=2: k_sbw_mfma over ring spectra through d_Fl
+    // everywhere, the A/B and cross-check form; SX_SBW_MFMA=3: the forward pair wherever its kernels apply, small tiles included
+    int sbw_mfma = 1;
     int sbw_prefetch = 0;   // k_sbw requests the next cell's ring spectra before contracting the current node (SX_SBW_PF=0: off)
     // zDim 64: 256-thread workgroups of 32 blocks, two per CU - one loads while the other contracts (0.127 -> 0.118 ms;
     // SX_SBW_T256=0 restores the 512-thread form)
@@ -286,10 +290,21 @@ struct ZinvPlan {
     bool f32 = false;                     // OT of k_colmat_mfma: float (fp32 spectra) or double
     int CT = 1, grid_x = 0;               // column tiles per wave, ceil(K2 / (64 CT))
 };
+// k_fl_forward_cells + k_nodes_z in place of the forward FFT kernel + the matrix-core sliding-window kernel (on: the pair is taken)
+struct CellsPlan {
+    bool on = false;
+    int logL = 0, threads = 0;            // forward kernel: log2 of the ring length, threads per workgroup
+    int S = 0, segs = 0;                  // cells per radial segment (>= 3: a node lies in at most two segments), segments
+    SbKernel zk = SbKernel::refused;      // k_nodes_z's shape is the sliding-window kernel's: mfma_32 / mfma_64 / mfma_64_t256 / mfma_128
+    int zthreads = 0, bw = 0, nps = 0, zsegs = 0;   // k_nodes_z: threads, wavenumber blocks per workgroup, nodes per workgroup, node runs
+};
 struct PcrPlan { int R = 1, logR = 0, threads = 64; };
 constexpr int PCR_IPT = 4;     // row items (patch row, column) per thread while k_solve_pcr loads B and stores A: nb * R <= 4 * blockDim (plan_pcr)
 SbPlan plan_sb(int geometry, int nz, int Zb, int K2, int v_cnt, int ncells, int sp32, const Switches &sw);
 ZinvPlan plan_zinv(int geometry, int nz, int K2, int sp32, const Switches &sw);
+// nvars: ALL the handle's variables (the segment length must not depend on the variable window: one side array serves every launch);
+// v_cnt: the window k_nodes_z covers; uniform_L: the ring table's uniform length, 0 for native rings
+CellsPlan plan_fwd_cells(int geometry, int nz, int Zb, int K2, int nvars, int v_cnt, int ncells, int sp32, int uniform_L, const Switches &sw);
 PcrPlan plan_pcr(int nblk_max, int b_rDim, int K2, int ngroups, const Switches &sw);
 std::string kernel_name(SbKernel k);      // "k_sbw_mfma<64, 32, 256>", ...; empty for `refused`
 std::string kernel_name(const ZinvPlan &p);   // "k_colmat_mfma<8, double, 4>", ...; empty for `none`
@@ -366,7 +381,10 @@ struct sx_handle {
     int f32 = 0;   // fp32 storage of the derivative slots of d_phys / d_G (typed by the launchers)
     int sp32 = 0;  // storage_f32 = 2: the spectral transform intermediates d_Az and d_Fl are fp32 as well (fp64 accumulation)
     double *d_Az = nullptr, *d_phys = nullptr, *d_np1 = nullptr, *d_E[3] = {}, *d_I[3] = {};
-    double *d_Fl = nullptr;
+    double *d_Fl = nullptr;     // ring spectra; not allocated where cells.on
+    sx::CellsPlan cells;        // forward pair of the handle (plan_fwd_cells with v_cnt = V; the launchers re-plan for their window)
+    double *d_Fn = nullptr;     // cells.on: node spectra [nbt][V][nz][K2], then the open edge partials of every segment but the last [segs - 1][3][V][nz][K2]
+    size_t fl_bytes = 0, fn_bytes = 0;   // device bytes of d_Fl / d_Fn
     double *d_phi = nullptr, *d_wq = nullptr;
     int *d_L = nullptr, *d_kmax = nullptr;
     int64_t *d_pstart = nullptr, *d_twoff = nullptr, *d_phoff = nullptr;
@@ -431,6 +449,7 @@ void launch_fl_forward_dft(sx_handle *h);
 void launch_rl_inverse_fft(sx_handle *h, const int *d_mask, int n_rings = -1);
 void launch_node_fft(sx_handle *h);
 void launch_fl_forward_fft(sx_handle *h);
+void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p);
 void launch_physics(sx_handle *h, int t);
 void launch_inverse_and_physics(sx_handle *h, int t);
 void launch_copy_slot0(sx_handle *h);

@@ -576,6 +576,88 @@ k_sbw_mfma(const FT *__restrict__ Fl, double *__restrict__ B, const double *__re
     SBW_END();
 }
 
+// The vertical contraction of k_sbw_mfma on its own, over the node spectra k_fl_forward_cells leaves (sx_fft.hip): a workgroup walks a
+// run of nodes for one (variable, BW wavenumber blocks); per node it reads the [NZ levels][BW] tile once - where the node is one of
+// the first three of a forward segment behind the first, plus the previous segment's open partial, the earlier segment first -
+// and contracts it with CB on the f64 matrix cores exactly as k_sbw_mfma does (operator fragments in LDS, same K order), into
+// d_Btile's layout.  The next node's tile is requested before the current one is contracted.
+template <int NZ, int BW = 64, int THREADS = 512>
+__global__ void __launch_bounds__(THREADS, 2)
+k_nodes_z(const double *__restrict__ Fn, const double *__restrict__ Fe, double *__restrict__ B, const double *__restrict__ CB,
+          int nbt, int V, int Zb, int K2, int64_t C, int S, int fsegs, int nps) {
+    constexpr int NG = THREADS / BW;
+    constexpr int ZPT = NZ / NG, KS = NZ / 4, LS = BW + 16;
+    constexpr int MTMAX = BW == 64 ? 4 : 6;
+    __shared__ double As[NZ * LS];
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lb = threadIdx.x & (BW - 1);
+    const int g = BW == 64 ? wv : (int)(threadIdx.x / BW);
+    const int blk = blockIdx.x * BW + lb;
+    const int v = blockIdx.y;
+    const bool ok = blk < K2;
+    const int na = blockIdx.z * nps, nb = min(na + nps, nbt);
+    const int64_t plane = (int64_t)V * NZ * K2;
+    const int64_t base = ((int64_t)v * NZ + g) * K2 + (ok ? blk : 0);
+    const int MT = (Zb + 15) / 16, mhalf = (MT + 1) / 2;
+    const int nt = BW == 64 ? (wv & 3) : (wv & 1);
+    const int mt0 = BW == 64 ? (wv < 4 ? 0 : mhalf) : (wv >> 1);
+    const int mt1 = BW == 64 ? mt0 + 1 : mt0 + THREADS / 128;
+    const int nmt = BW == 64 ? (wv < 4 ? mhalf : MT - mhalf) : (mt0 >= MT ? 0 : mt1 < MT ? 2 : 1);
+    const int n = lane & 15, kk = lane >> 4;
+    __shared__ double Af[MTMAX * KS * 64];               // operator fragments [row tile][K step][lane], as in k_sbw_mfma
+    for (int e = threadIdx.x; e < MT * KS * 64; e += blockDim.x) {
+        const int l = e & 63, js = (e >> 6) % KS, mt = e / (64 * KS);
+        const int m = mt * 16 + (l & 15);
+        Af[e] = (m < Zb) ? CB[(int64_t)m * NZ + 4 * js + (l >> 4)] : 0.0;
+    }
+    const double *af0 = Af + (size_t)(nmt > 0 ? mt0 : 0) * KS * 64 + lane, *af1 = Af + (size_t)(nmt > 1 ? mt1 : 0) * KS * 64 + lane;
+    double xn[ZPT], en[ZPT];
+    // node nd is node j of forward segment sg; j < 3 behind the first segment: the previous segment's open partial j belongs to it
+    auto fetch = [&](int nd) {
+        if (nd >= nb) return;
+        const int sg = min(nd / S, fsegs - 1), j = nd - sg * S;
+        const double *src = Fn + (int64_t)nd * plane + base;
+#pragma unroll
+        for (int i = 0; i < ZPT; i++) xn[i] = src[(int64_t)(NG * i) * K2];
+        if (sg > 0 && j < 3) {                             // workgroup-uniform
+            const double *es = Fe + (int64_t)((sg - 1) * 3 + j) * plane + base;
+#pragma unroll
+            for (int i = 0; i < ZPT; i++) en[i] = es[(int64_t)(NG * i) * K2];
+#pragma unroll
+            for (int i = 0; i < ZPT; i++) xn[i] = en[i] + xn[i];
+        }
+    };
+    fetch(na);
+    for (int c = na; c < nb; c++) {
+        __syncthreads();                // the previous node's tile has been consumed (first node: the operator fragments are in place)
+#pragma unroll
+        for (int i = 0; i < ZPT; i++) As[(g + NG * i) * LS + lb] = xn[i];
+        __syncthreads();
+        fetch(c + 1);                   // in flight while node c goes through the matrix cores
+        colmat_d4 o0 = {0.0, 0.0, 0.0, 0.0}, o1 = o0;
+        const double *xb = As + kk * LS + nt * 16 + n;
+        if (nmt > 0) {
+#pragma unroll
+            for (int js = 0; js < KS; js++) {
+                const double b = xb[(4 * js) * LS];
+                o0 = __builtin_amdgcn_mfma_f64_16x16x4f64(af0[js * 64], b, o0, 0, 0, 0);
+                if (nmt > 1) o1 = __builtin_amdgcn_mfma_f64_16x16x4f64(af1[js * 64], b, o1, 0, 0, 0);
+            }
+        }
+        // D[row = kk + 4 r][col = n]
+        const int col = blockIdx.x * BW + nt * 16 + n;
+        if (col < K2) {
+            double *dst = B + (int64_t)c * C + (int64_t)v * Zb * K2 + col;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const int m0 = mt0 * 16 + kk + 4 * r, m1 = mt1 * 16 + kk + 4 * r;
+                if (nmt > 0 && m0 < Zb) dst[(int64_t)m0 * K2] = o0[r];
+                if (nmt > 1 && m1 < Zb) dst[(int64_t)m1 * K2] = o1[r];
+            }
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ B -> A banded SPD solve
 // One lane per right-hand side (column); rows are contiguous across lanes so every load/store is coalesced.
 // a = Gamma^T (L L^T)^-1 Gamma b with L banded (half-bandwidth 3) plus, for PERIODIC, three dense last rows.
@@ -959,8 +1041,15 @@ void launch_rl_inverse(sx_handle *h, bool full) {
     timer_end(h);
 }
 
+// the forward pair for the launch's variable window, or off (plan_fwd_cells: sx_plan.cpp)
+static CellsPlan cells_plan(const sx_handle *h) {
+    if (!h->cells.on) return CellsPlan();
+    return plan_fwd_cells(h->geom, h->nz, h->Zb, h->K2, h->V, h->v_cnt, h->ncells, h->sp32, h->uniform_L, h->sw);
+}
+
 void launch_fl_forward(sx_handle *h) {
     if (rz_fused(h)) return;                        // RZ: k_rz_forward reads var_np1 itself (no azimuth, nothing to transform)
+    if (const CellsPlan cp = cells_plan(h); cp.on) { launch_fl_forward_cells(h, cp); return; }
     if (fft_path_ok(h)) { launch_fl_forward_fft(h); return; }
     if (dft_mfma_ok(h)) { launch_fl_forward_dft(h); return; }
     const int id = timer_id(h, "k_fl_forward");
@@ -978,7 +1067,26 @@ void launch_fl_forward(sx_handle *h) {
     timer_end(h);
 }
 
+static void launch_nodes_z(sx_handle *h, const CellsPlan &p) {
+    const int id = timer_id(h, "k_sbz");
+    timer_begin(h, id);
+    dim3 g((h->K2 + p.bw - 1) / p.bw, h->v_cnt, p.zsegs);
+    const int64_t plane = (int64_t)h->V * h->nz * h->K2, flo = (int64_t)h->v_lo * h->nz * h->K2, blo = (int64_t)h->v_lo * h->Zb * h->K2;
+#define NODES_Z(...) hipLaunchKernelGGL((__VA_ARGS__), g, dim3(p.zthreads), 0, h->stream, h->d_Fn + flo, h->d_Fn + (int64_t)h->nbt * plane + flo, \
+                                        h->d_Btile + blo, h->d_CB, h->nbt, h->V, h->Zb, h->K2, h->C, p.S, p.segs, p.nps); break
+    switch (p.zk) {
+    case SbKernel::mfma_32: NODES_Z(k_nodes_z<32>);
+    case SbKernel::mfma_64: NODES_Z(k_nodes_z<64>);
+    case SbKernel::mfma_64_t256: NODES_Z(k_nodes_z<64, 32, 256>);
+    default: NODES_Z(k_nodes_z<128, 32>);
+    }
+#undef NODES_Z
+    HIPCHK(hipGetLastError());
+    timer_end(h);
+}
+
 void launch_sb(sx_handle *h) {
+    if (const CellsPlan cp = cells_plan(h); cp.on) { launch_nodes_z(h, cp); return; }
     const SbPlan p = plan_sb(h->geom, h->nz, h->Zb, h->K2, h->v_cnt, h->ncells, h->sp32, h->sw);
     if (p.kernel == SbKernel::rz_forward) { launch_rz_forward(h); return; }
     if (p.kernel == SbKernel::refused) { set_error("launch_sb: fp32 ring spectra (storage_f32 = 2) need the matrix-core sliding-window kernel"); return; }

@@ -39,6 +39,50 @@ SbPlan plan_sb(int geometry, int nz, int Zb, int K2, int v_cnt, int ncells, int 
     return p;
 }
 
+// spectralTransform! as k_fl_forward_cells + k_nodes_z: wherever the forward FFT kernel and the fp64 matrix-core sliding-window kernel
+// are both taken today, on rings of at most 256 points (at 512 a lane carries four wavenumbers: 64 doubles of open node sums, which
+// leave the transform no registers).  Everything else - native rings, RL, RZ, fp32 spectra, SX_SBW_MFMA=2 - keeps its kernels.
+// By default only launches of the measured kind take it: segments of at least 9 cells that fill three quarters of a round of CUs
+// (the bench grid).  On small tiles - an 8-way split's 21 cells: S = 3, 168 workgroups, each a serial chain of 9 rings at ~7,000
+// cycles a ring - the one-workgroup-per-CU kernel is a latency chain: forced there, k_fl_forward doubles, k_sbz gains less, and the
+// slowest tile of the 8-tile step gets 1.2 % slower (profiles/r05/ab_forward_cells.txt); SX_SBW_MFMA=3 takes the pair wherever its kernels apply (tests, A/B at other shapes).
+CellsPlan plan_fwd_cells(int geometry, int nz, int Zb, int K2, int nvars, int v_cnt, int ncells, int sp32, int uniform_L, const Switches &sw) {
+    CellsPlan p;
+    const int L = uniform_L;
+    if (sw.sbw_mfma == 2 || geometry != SX_GEOM_RLZ || sp32 || L < 16 || L > 256 || (L & (L - 1)) || nz % 16) return p;
+    const SbPlan sb = plan_sb(geometry, nz, Zb, K2, v_cnt, ncells, sp32, sw);
+    using K = SbKernel;
+    if (sb.kernel != K::mfma_32 && sb.kernel != K::mfma_64 && sb.kernel != K::mfma_64_t256 && sb.kernel != K::mfma_128) return p;
+    p.on = true;
+    while ((1 << p.logL) < L) p.logL++;
+    p.threads = std::max(64, 8 * std::min(L / 4, 64));
+    // Segment length: a workgroup's time is proportional to the cells it walks, every workgroup of the launch walks the same number,
+    // and a CU holds one 512-thread workgroup (its registers: sx_fft.hip), so the launch takes ceil(workgroups / 256) rounds of S
+    // cells: the S with the smallest rounds x (S + 1), see below.  At least 3 cells: a node then
+    // lies in at most two segments.  Bench grid (171 cells, 4 chunks, 6 variables): S = 18, 10 segments, 240 workgroups in one round
+    // (measured on one MI355X with the segment length forced, steps/s of the bench step: S = 3 990, 5 999, 6 1013, 9 1026, 12 979, 18 1036).
+    // Each segment also stores three edge rows on top of its S node rows and starts with a tile load nothing hides: one cell's worth
+    // per round, which orders the measured lengths as measured (cost 24, 24, 21, 20, 26, 19 for S = 3, 5, 6, 9, 12, 18).
+    const int wg_per_seg = (nz / 16) * nvars, slots = 256;
+    int64_t best = 0;
+    for (int s = 3; s <= 24; s++) {
+        const int segs = (ncells + s - 1) / s;
+        const int64_t cost = (int64_t)((wg_per_seg * segs + slots - 1) / slots) * (std::min(s, ncells) + 1);
+        if (p.S == 0 || cost < best) { best = cost; p.S = s; }
+    }
+    p.segs = (ncells + p.S - 1) / p.S;
+    if (sw.sbw_mfma != 3 && (p.S < 9 || 4 * wg_per_seg * p.segs < 3 * slots)) return CellsPlan();
+    // k_nodes_z: the sliding-window kernel's workgroup shape over runs of whole nodes, about one round of workgroups (the operator
+    // fragments are fetched into LDS once per workgroup)
+    p.zk = sb.kernel;
+    p.zthreads = sb.threads;
+    p.bw = sb.bw;
+    const int nbt = ncells + 3, runs = std::max(1, (p.bw == 32 ? 512 : 256) / std::max(1, sb.groups));
+    p.nps = std::max(1, (nbt + runs - 1) / runs);
+    p.zsegs = (nbt + p.nps - 1) / p.nps;
+    return p;
+}
+
 // the vertical inverse into Az (k_zinv)
 ZinvPlan plan_zinv(int geometry, int nz, int K2, int sp32, const Switches &sw) {
     ZinvPlan p;
