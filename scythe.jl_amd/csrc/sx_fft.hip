@@ -37,8 +37,21 @@ template <int LOGL, int HL = 0> struct FftCfg {
 #ifdef SX_PHASES
 __device__ long long *g_fft_dbg = nullptr;
 #define FFT_STAMP(i) do { if (NODE && threadIdx.x == 0 && g_fft_dbg) g_fft_dbg[((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
+// ... and of k_fl_forward_cells: [workgroup][8] = cycles of wave 0 summed over the workgroup's rings in 0 tile landed and written to
+// LDS, 1 workgroup barrier, 2 transform, 3 untangling + node sums, 4 node stores issued (per cell and the three edge nodes); 5 entry
+// to the first ring; 6 rings walked; 7 entry to exit (profiles/phases_cells.py)
+__device__ long long *g_cells_dbg = nullptr;
+#define CELLS_PHASES_BEGIN() long long cp_acc_[6] = {0, 0, 0, 0, 0, 0}, cp_rings_ = 0; asm volatile("" ::: "memory"); const long long cp_t0_ = (long long)__builtin_readcyclecounter(); long long cp_last_ = cp_t0_
+#define CELLS_STAMP(i) do { asm volatile("" ::: "memory"); const long long n_ = (long long)__builtin_readcyclecounter(); asm volatile("" ::: "memory"); cp_acc_[i] += n_ - cp_last_; cp_last_ = n_; } while (0)
+#define CELLS_RING() (cp_rings_++)
+#define CELLS_PHASES_END() do { if (threadIdx.x == 0 && g_cells_dbg) { long long *d_ = g_cells_dbg + ((int64_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8; \
+    for (int i_ = 0; i_ < 6; i_++) d_[i_] = cp_acc_[i_]; d_[6] = cp_rings_; d_[7] = cp_last_ - cp_t0_; } } while (0)
 #else
 #define FFT_STAMP(i) do { } while (0)
+#define CELLS_PHASES_BEGIN() do { } while (0)
+#define CELLS_STAMP(i) do { } while (0)
+#define CELLS_RING() do { } while (0)
+#define CELLS_PHASES_END() do { } while (0)
 #endif
 
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -214,9 +227,10 @@ __device__ __forceinline__ void fft_transpose4(double2 (&v)[4], int lane) {
     fft_swap2<HI>(v[0], v[2], lane); fft_swap2<HI>(v[1], v[3], lane);
     fft_swap2<HI - 1>(v[0], v[1], lane); fft_swap2<HI - 1>(v[2], v[3], lane);
 }
-// decimation-in-frequency radix-4 butterfly, inverse sign: y_q = (sum_p a_p i^{pq}) w^q
+// decimation-in-frequency radix-4 butterfly: y_q = (sum_p a_p (SIGN i)^{pq}) w^q; SIGN = +1 inverse, -1 forward (w conjugated by the caller)
+template <int SIGN = +1>
 __device__ __forceinline__ void fft_bfly_dif(double2 (&v)[4], double2 w1, bool tw) {
-    const double2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]), t2 = cadd(v[1], v[3]), t3 = cmuli(csub(v[1], v[3]), +1);
+    const double2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]), t2 = cadd(v[1], v[3]), t3 = cmuli(csub(v[1], v[3]), SIGN);
     const double2 y0 = cadd(t0, t2);
     double2 y1 = cadd(t1, t3), y2 = csub(t0, t2), y3 = csub(t1, t3);
     if (tw) {
@@ -234,6 +248,16 @@ __device__ __forceinline__ void fft_reg256_inverse(double2 (&v)[4], const double
     fft_bfly_dif(v, w[2], true);
     fft_transpose4<1>(v, lane);
     fft_bfly_dif(v, w[0], false);
+}
+// the mirror: X[l] = sum_n x[n] e^{-2 pi i n l / 256}, same layouts; w[] are the conjugates of fft_reg256_inverse's
+__device__ __forceinline__ void fft_reg256_forward(double2 (&v)[4], const double2 (&w)[3], int lane) {
+    fft_bfly_dif<-1>(v, w[0], true);
+    fft_transpose4<5>(v, lane);
+    fft_bfly_dif<-1>(v, w[1], true);
+    fft_transpose4<3>(v, lane);
+    fft_bfly_dif<-1>(v, w[2], true);
+    fft_transpose4<1>(v, lane);
+    fft_bfly_dif<-1>(v, w[0], false);
 }
 __device__ __forceinline__ double2 fft_bpermute(double2 v, int src_lane) {
     const FftQ q = fft_toq(v);
@@ -673,7 +697,7 @@ k_fl_forward_fft(const double *__restrict__ np1, FT *__restrict__ Fl, const int 
 
 // Forward transform summed into the spline nodes where the spectrum is produced (uniform rings up to 256 points, 16-level chunks).
 // One workgroup = (16-level chunk, variable, radial segment of S cells).  It walks the segment's 3 S rings in ascending order; per ring
-// it does what k_fl_forward_fft does (tile in one burst of 16-byte non-temporal loads, transform through LDS, untangling of the two
+// it does what k_fl_forward_fft does (tile in one burst of 16-byte non-temporal loads, transform, untangling of the two
 // packed levels, phase factor, 1 / L) but keeps the spectrum in registers: each lane multiplies its wavenumbers (k = t, t + T; two
 // levels each) by the ring's four radial weights wq * phi (k_sbw_mfma's) and adds them to the four open node sums of the current cell -
 // 4 nodes x 2 k x 2 levels x (re, im) = 32 doubles per lane.  Leaving cell c closes node c: it is stored once, [node][v][level][K2]
@@ -684,18 +708,37 @@ k_fl_forward_fft(const double *__restrict__ np1, FT *__restrict__ Fl, const int 
 // Two LDS sets: ring i + 1 is staged into the other set, so one LDS-only workgroup barrier per ring orders everything - a set is
 // rewritten two rings after its last (wave-local) read, and the barrier of the ring in between lies between the two.  The next
 // ring's tile loads are issued before the current ring's transform and stay in flight across it.
+// Round 6, measured with the phase stamps below (profiles/r06/phases_forward_cells_*.txt; per ring and workgroup, wave 0):
+//   REG (256 points, SX_FFT_REG, default on): the staged tile is already the input layout of the register-resident passes
+//   (v[q] = x[t + 64 q]), so the transform is one LDS read, fft_reg256_forward, and one write-back of the digit-reversed bins into the
+//   same region, from which the untangling reads bins k and L - k as before - the lanes keep their wavenumbers k = t, t + T, and the
+//   node sums, the truncation test and store_node are untouched.  Transform 2,819 -> 1,553 cycles, ring 6,495 -> 5,506.  SX_FFT_REG=0 and shorter rings
+//   keep fft_inplace and give the bits they gave.
+//   A per-segment LDS table of kmax, phase offset and wq * phi (no small loads in the loop) was measured and taken out: no gain
+//   (DESIGN.md 4).  The tile in flight stays at depth one; depth two is not measured.
 // Registers: the open node sums are 64 VGPRs and the tile in flight 16 on top of the transform's ~50: at the 128 of two 512-thread
 // workgroups per CU the kernel spilled 73 of them (45 without the tile in flight), and a spill reload drains the in-order memory
-// counter, so it runs as ONE workgroup per CU (186 VGPRs at 256 points, no scratch) and leans on the tile in flight for overlap.
-template <int LOGL>
+// counter, so it runs as ONE workgroup per CU (200 VGPRs at 256 points with the register passes, 186 without, no scratch) and leans
+// on the tile in flight for overlap.
+// complex elements between the transform regions of an LDS set of this kernel; with the register passes ring point / bin l sits at
+// l + (l >> 4) as in the inverse kernel's copy-out sets, so that the write-back of the digit-reversed bins (16 lanes of a row: bins
+// 4 a + 16 b) is free of bank conflicts.  The kernel and its launcher (LDS size) both take it from here.
+template <int LOGL, bool REG> struct CellsCfg {
+    static constexpr int SKEW = REG ? (1 << LOGL) / 16 + 2 : FftCfg<LOGL>::SKEW;
+    static constexpr size_t LDS = sizeof(double2) * 2 * FftCfg<LOGL>::FNP * ((1 << LOGL) + SKEW);      // two sets
+};
+
+template <int LOGL, bool REG = false>
 __global__ void __launch_bounds__((FftCfg<LOGL>::FNP * FftCfg<LOGL>::LPT < 64 ? 64 : FftCfg<LOGL>::FNP * FftCfg<LOGL>::LPT), 2)
 k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, double *__restrict__ Fe, const int *__restrict__ kmaxr,
                    const int64_t *__restrict__ pstart, const double2 *__restrict__ twg, const int64_t *__restrict__ phoff,
                    const double2 *__restrict__ ph, const double *__restrict__ phi, const double *__restrict__ wq,
                    int V, int nz, int K2, int64_t N, int ncells, int S) {
     constexpr int L = 1 << LOGL, T = FftCfg<LOGL>::LPT, NK = FftCfg<LOGL>::NK, PPT = L / T;
-    constexpr int FZC = FftCfg<LOGL>::FZC, FNP = FftCfg<LOGL>::FNP, LOGZ = FftCfg<LOGL>::LOGZ, SKEW = FftCfg<LOGL>::SKEW;
+    constexpr int FZC = FftCfg<LOGL>::FZC, FNP = FftCfg<LOGL>::FNP, LOGZ = FftCfg<LOGL>::LOGZ, SKEW = CellsCfg<LOGL, REG>::SKEW;
     static_assert(LOGL <= 8 && NK == 2 && PPT == 4, "one butterfly per lane and pass: rings of at most 256 points");
+    static_assert(!REG || LOGL == 8, "register-resident passes: 256-point transforms");
+    auto at = [](int l) { return REG ? l + (l >> 4) : l; };
     typedef double dv2 __attribute__((ext_vector_type(2)));
     extern __shared__ double2 smf[];
     const int z0 = blockIdx.x * FZC, v = blockIdx.y, seg = blockIdx.z;
@@ -707,7 +750,9 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
     const int zp = tid & (FNP - 1);
     const int64_t plane = (int64_t)V * nz * K2;            // one node's [v][level][K2] spectra
     Twiddles<LOGL> tw;
-    tw.template init<-1>(twg, t);
+    double2 wreg[3];                                       // REG: conjugates of fft_reg256_inverse's three twiddles
+    if constexpr (REG) { wreg[0] = cconj(twg[t]); wreg[1] = cconj(twg[4 * (t & 15)]); wreg[2] = cconj(twg[16 * (t & 3)]); }
+    else tw.template init<-1>(twg, t);
     const double *xb = np1 + (int64_t)v * N + z0 + 2 * zp;
     const double inv = 1.0 / L;
     double acc[4][NK][4];                                  // [open node][wavenumber][level a re, im, level b re, im]
@@ -738,7 +783,9 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
     };
     const int64_t rowoff = ((int64_t)v * nz + z0) * K2;
     int par = 0;
+    CELLS_PHASES_BEGIN();
     if (active) issue(ca * MUBAR);
+    CELLS_STAMP(5);
     for (int c = ca; c < cb; c++) {
 #pragma unroll 1
         for (int mu = 0; mu < MUBAR; mu++) {
@@ -747,8 +794,9 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
             par ^= 1;
             if (active) {
 #pragma unroll
-                for (int i = 0; i < PPT; i++) set[zp * (L + SKEW) + ((tid + i * FNP * T) >> (LOGZ - 1))] = make_double2(t2[i].x, t2[i].y);
+                for (int i = 0; i < PPT; i++) set[zp * (L + SKEW) + at((tid + i * FNP * T) >> (LOGZ - 1))] = make_double2(t2[i].x, t2[i].y);
             }
+            CELLS_STAMP(0);
             // this ring's phase factors in front of the next ring's tile: the memory counter retires in issue order, and the phase
             // factors are waited for right after the transform while the tile may take until the next ring
             const int km = kmaxr[ring];
@@ -760,8 +808,23 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
             if (active && ring + 1 < cb * MUBAR) issue(ring + 1);
             asm volatile("" ::: "memory");
             lds_barrier();
+            CELLS_STAMP(1);
             double2 *X = set + (active ? f : 0) * (L + SKEW);
-            fft_inplace<LOGL, -1, true>(X, tw, t, active);
+            if constexpr (REG) {
+                // the staged tile IS the register passes' input layout, v[q] = x[t + 64 q]; the digit-reversed bins go back to the
+                // same region (bins k and L - k of the untangling sit in different lanes)
+                double2 v4[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) v4[q] = X[at(t + 64 * q)];
+                wave_sync();
+                fft_reg256_forward(v4, wreg, t);
+                const int lb = (t >> 4) + 4 * ((t >> 2) & 3) + 16 * (t & 3);
+#pragma unroll
+                for (int q = 0; q < 4; q++) X[at(lb + 64 * q)] = v4[q];
+                wave_sync();
+            } else
+                fft_inplace<LOGL, -1, true>(X, tw, t, active);
+            CELLS_STAMP(2);
             if (active) {
                 const double w = wq[ring];
                 const double wj[4] = {w * phi[(int64_t)ring * 4], w * phi[(int64_t)ring * 4 + 1], w * phi[(int64_t)ring * 4 + 2], w * phi[(int64_t)ring * 4 + 3]};
@@ -769,7 +832,7 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
                 for (int q = 0; q < NK; q++) {
                     const int k = t + q * T;
                     if (k > km) continue;                  // not part of this ring's spectrum
-                    const double2 wk = X[k], wn = X[(L - k) & (L - 1)];
+                    const double2 wk = X[at(k)], wn = X[at((L - k) & (L - 1))];
                     // Xa = (W_k + conj W_{-k}) / 2,  Xb = (W_k - conj W_{-k}) / (2i)
                     double2 xa = make_double2(0.5 * (wk.x + wn.x), 0.5 * (wk.y - wn.y));
                     double2 xb2 = make_double2(0.5 * (wk.y + wn.y), -0.5 * (wk.x - wn.x));
@@ -788,9 +851,12 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
                         for (int e = 0; e < 4; e++) acc[j][q][e] += wj[j] * x4[e];
                 }
             }
+            CELLS_STAMP(3);
+            CELLS_RING();
         }
         // node c is complete as far as this segment goes; the three above it stay open
         store_node(Fn + (int64_t)c * plane + rowoff, 0);
+        CELLS_STAMP(4);
 #pragma unroll
         for (int q = 0; q < NK; q++)
 #pragma unroll
@@ -801,6 +867,8 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
     double *edge = (cb == ncells) ? Fn + (int64_t)ncells * plane : Fe + (int64_t)seg * 3 * plane;
 #pragma unroll
     for (int j = 0; j < 3; j++) store_node(edge + (int64_t)j * plane + rowoff, j);
+    CELLS_STAMP(4);
+    CELLS_PHASES_END();
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
@@ -922,16 +990,20 @@ void launch_rl_inverse_fft(sx_handle *h, const int *d_mask, int n_rings) {
 
 // node-space inverse ("radial last", uniform rings): one transform set per radial node instead of per ring
 #ifdef SX_PHASES
-static long long *g_fft_buf = nullptr;
-static int64_t g_fft_n = 0;
-void fft_phases_dump() {
-    const char *path = getenv("SX_FFT_PHASES_OUT");
-    if (!path || !g_fft_buf) return;
-    std::vector<long long> hst((size_t)g_fft_n * 8);
+static long long *g_fft_buf = nullptr, *g_cells_buf = nullptr;
+static int64_t g_fft_n = 0, g_cells_n = 0;
+static void phases_dump_one(const char *var, const long long *buf, int64_t n) {
+    const char *path = getenv(var);
+    if (!path || !buf) return;
+    std::vector<long long> hst((size_t)n * 8);
     hipDeviceSynchronize();
-    hipMemcpy(hst.data(), g_fft_buf, sizeof(long long) * hst.size(), hipMemcpyDeviceToHost);
+    hipMemcpy(hst.data(), buf, sizeof(long long) * hst.size(), hipMemcpyDeviceToHost);
     FILE *f = fopen(path, "wb");
     if (f) { fwrite(hst.data(), sizeof(long long), hst.size(), f); fclose(f); }
+}
+void fft_phases_dump() {
+    phases_dump_one("SX_FFT_PHASES_OUT", g_fft_buf, g_fft_n);
+    phases_dump_one("SX_CELLS_PHASES_OUT", g_cells_buf, g_cells_n);      // the LAST k_fl_forward_cells launch
 }
 #endif
 
@@ -954,18 +1026,33 @@ void launch_node_fft(sx_handle *h) {
     timer_end(h);
 }
 
-template <int LOGL>
-static void launch_fwd_cells(sx_handle *h, const CellsPlan &p) {
+template <int LOGL, bool REG>
+static void launch_fwd_cells_v(sx_handle *h, const CellsPlan &p) {
     const int L = 1 << LOGL;
-    const size_t lds = fft_lds(L, 2);
+    const size_t lds = CellsCfg<LOGL, REG>::LDS;
     if (lds > 65536)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_cells<LOGL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_cells<LOGL, REG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     dim3 g(h->nz / fft_fzc(L), h->v_cnt, p.segs);
+#ifdef SX_PHASES
+    if (const int64_t n = (int64_t)g.x * g.y * g.z; n > g_cells_n) {      // stamps of the LAST launch: sized for the largest grid so far
+        if (g_cells_buf) { hipDeviceSynchronize(); hipFree(g_cells_buf); }
+        g_cells_n = n;
+        hipMalloc(&g_cells_buf, sizeof(long long) * g_cells_n * 8);
+        hipMemset(g_cells_buf, 0, sizeof(long long) * g_cells_n * 8);
+        hipMemcpyToSymbol(HIP_SYMBOL(g_cells_dbg), &g_cells_buf, sizeof(g_cells_buf));
+    }
+#endif
     // the variable window [v_lo, v_lo + v_cnt) through the base pointers, as in launch_fwd
     const int64_t plane = (int64_t)h->V * h->nz * h->K2, flo = (int64_t)h->v_lo * h->nz * h->K2;
-    hipLaunchKernelGGL(k_fl_forward_cells<LOGL>, g, dim3(p.threads), lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N, h->d_Fn + flo,
+    hipLaunchKernelGGL((k_fl_forward_cells<LOGL, REG>), g, dim3(p.threads), lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N, h->d_Fn + flo,
                        h->d_Fn + (int64_t)h->nbt * plane + flo, h->d_kmax, h->d_pstart, h->d_tw, h->d_phoff, h->d_ph, h->d_phi, h->d_wq,
                        h->V, h->nz, h->K2, h->N, h->ncells, p.S);
+}
+
+template <int LOGL>
+static void launch_fwd_cells(sx_handle *h, const CellsPlan &p) {
+    if constexpr (LOGL == 8) { if (h->sw.fft_reg) { launch_fwd_cells_v<LOGL, true>(h, p); return; } }
+    launch_fwd_cells_v<LOGL, false>(h, p);
 }
 
 void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {

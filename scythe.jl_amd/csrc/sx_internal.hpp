@@ -242,7 +242,7 @@ struct Switches {
     int use_graph = 0;      // SX_GRAPH=1: hipGraph replay of a one-tile step (sx_step), one instantiated graph per history rotation
     int node_mode = 1;      // SX_NODE_MODE=0: ring-wise inverse everywhere (sx_create decides where the node-space form applies at all)
     int defer_diag = 0;     // SX_DEFER_DIAG=1: asks for sx_handle::defer_diag (sx_create decides whether the handle qualifies)
-    int fft_reg = 1;        // 256-point inverse transforms: register-resident passes with lane swaps (SX_FFT_REG=0: every pass through LDS)
+    int fft_reg = 1;        // 256-point transforms of the inverse kernels and of k_fl_forward_cells: register-resident passes with lane swaps (SX_FFT_REG=0: every pass through LDS)
     int dft_mfma = 1;       // native rings: the matrix-core DFT kernels (SX_DFT_MFMA=0: scalar kernels instead, debugging)
     int dft_half_wg = 1;    // eighth-wave kernel as two 256-thread workgroups per CU where one set + half a twiddle table fit 80 KB (SX_DFT_HALFWG=0: one 512-thread workgroup)
     int dft_eighth = 2;     // merged kernel: eighth-wave units of two planes (round 4; SX_DFT_EIGHTH=0: quarter-wave units of up to four)
