@@ -18,7 +18,8 @@ def timer_name(kernel):
     k = kernel.split("(")[0].replace("void ", "").replace("sx::", "")
     base, _, targs = k.partition("<")
     targs = targs.rstrip(">").replace(" ", "").split(",") if targs else []
-    if base == "k_rl_inverse_fft":           # <LOGL, COPYOUT, NODE, ST>
+    if base == "k_rl_inverse_fft":           # <LOGL, ST, NODE, AT, FUSE, REG>; the CSVs recorded up to r06 carry the nine-argument
+                                             # <LOGL, COPYOUT, NODE, ST, AT, HL, SETS, FUSE, REG>: NODE is the third in both
         return "k_node_fft" if targs[2] in ("true", "1") else "k_rl_inverse"
     if base == "k_phys_hrbl_mfma":           # ring-wise HRBL kernel: the inner rings when the cell kernel takes the rest
         return "k_phys_hrbl_inner"

@@ -6,8 +6,8 @@
 // A transform of length L is owned by min(L/4, 64) lanes of ONE wave, so every pass is wave-local: in-place radix-4
 // autosort passes through a 16 B x L LDS region (+ one radix-2 pass when log2 L is odd), twiddles held in registers,
 // no workgroup barrier inside a transform (at L = 512 a lane carries two butterflies per pass).
-//   inverse: the last pass stores straight to the reference physical layout (z innermost): each lane writes the
-//            16-byte (z, z+1) pair of its ring points; the 8 waves of the workgroup complete every 128-byte line.
+//   inverse: the transformed tile leaves LDS in the reference physical layout (z innermost): each thread stores the
+//            16-byte (z, z+1) pair of a ring point, consecutive lanes cover the 16 levels of a point = one 128-byte line.
 //   forward: the workgroup first stages the [ring point][16 levels] tile through LDS with full 128-byte loads.
 #include "sx_internal.hpp"
 #include <cstdlib>
@@ -23,14 +23,15 @@ namespace sx {
 // arrive as whole 128-byte lines (8 levels per workgroup - 64-byte pieces - held the L = 512 kernels at 3.2 TB/s).
 // SKEW: complex elements between transform regions (bank spreading when L < 256; 0 at L = 512 so that the two LDS sets
 // of the inverse are exactly 64 KB).
-// HL = 1 halves the lanes per transform (two butterflies per lane and pass already at L = 256: 256-thread workgroups whose
-// waves carry twice the independent work; used by the inverse kernels, see launch_inv).
-template <int LOGL, int HL = 0> struct FftCfg {
-    static constexpr int FZC = 16, FNP = FZC / 2, LOGZ = 4, SKEW = (LOGL <= 8) ? 2 : 0;
+constexpr int FFT_FZC = 16;
+template <int LOGL> struct FftCfg {
+    static constexpr int FZC = FFT_FZC, FNP = FZC / 2, LOGZ = 4, SKEW = (LOGL <= 8) ? 2 : 0;
     static constexpr int L4 = (1 << LOGL) / 4;
-    static constexpr int LPT = (L4 > 64 ? 64 : L4) >> HL;      // lanes per transform
+    static constexpr int LPT = L4 > 64 ? 64 : L4;      // lanes per transform
     static constexpr int NB = L4 / LPT;                // radix-4 butterflies per lane and pass
     static constexpr int NK = 2 * NB;                  // wavenumbers (k < L / 2) per lane
+    static constexpr int THREADS = FNP * LPT < 64 ? 64 : FNP * LPT;                          // FNP transforms x LPT lanes
+    static constexpr size_t LDS = sizeof(double2) * FNP * ((1 << LOGL) + SKEW);              // one set of FNP transform regions
 };
 
 // phase stamps of the diagnostic build (-DSX_PHASES): [workgroup][8] cycle counts of the NODE inverse kernel, dumped by sx_destroy
@@ -75,9 +76,9 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 
-template <int LOGL, int HL = 0>
+template <int LOGL>
 struct Twiddles {
-    static constexpr int L = 1 << LOGL, NP4 = LOGL / 2, LPT = FftCfg<LOGL, HL>::LPT, NB = FftCfg<LOGL, HL>::NB;
+    static constexpr int L = 1 << LOGL, NP4 = LOGL / 2, LPT = FftCfg<LOGL>::LPT, NB = FftCfg<LOGL>::NB;
     double2 w1[NP4 > 1 ? NP4 - 1 : 1][NB]; // w2 = w1^2, w3 = w1^3 are formed on the fly (registers are the scarce resource)
     double2 r2[2 * NB];                    // final radix-2 pass (odd log2 L): butterflies j = t + c LPT
     // SIGN = +1: e^{+i...} (inverse), -1: forward.  t = lane within the transform.  The radix-4 twiddle of butterfly
@@ -106,17 +107,11 @@ struct Twiddles {
     }
 };
 
-// In-place radix-4 passes on X (L complex, owned by LPT lanes of one wave, lane index t, NB butterflies per lane).
-// All passes but the last are done here; `last` receives the outputs of the final pass:
-//   last(index, value) for the 4 (radix-4 ending) or 2 (radix-2 ending) outputs of each butterfly of this lane.
-struct NoSink {
-    __device__ void operator()(int, double2) const {}
-};
-
-// TO_LDS = true: the final pass is written back to X as well (natural order), `last` is not called.
-template <int LOGL, int SIGN, bool TO_LDS = false, class F = NoSink, int HL = 0>
-__device__ __forceinline__ void fft_inplace(double2 *X, const Twiddles<LOGL, HL> &tw, int t, bool active, F last = F()) {
-    constexpr int L = 1 << LOGL, NBF = L / 4, NP4 = LOGL / 2, LPT = FftCfg<LOGL, HL>::LPT, NB = FftCfg<LOGL, HL>::NB;
+// In-place radix-4 passes on X (L complex, owned by LPT lanes of one wave, lane index t, NB butterflies per lane), + one radix-2
+// pass when log2 L is odd.  Every pass, the last included, is written back to X: the result is there in natural order.
+template <int LOGL, int SIGN>
+__device__ __forceinline__ void fft_inplace(double2 *X, const Twiddles<LOGL> &tw, int t, bool active) {
+    constexpr int L = 1 << LOGL, NBF = L / 4, NP4 = LOGL / 2, LPT = FftCfg<LOGL>::LPT, NB = FftCfg<LOGL>::NB;
     int Ns = 1;
 #pragma unroll
     for (int p = 0; p < NP4; p++) {
@@ -137,13 +132,6 @@ __device__ __forceinline__ void fft_inplace(double2 *X, const Twiddles<LOGL, HL>
                 j0[b] = ((j - k) << 2) + k;
             }
         }
-        if (!TO_LDS && p == NP4 - 1 && !(LOGL & 1)) {
-            if (active) {
-#pragma unroll
-                for (int b = 0; b < NB; b++) { last(j0[b], y0[b]); last(j0[b] + Ns, y1[b]); last(j0[b] + 2 * Ns, y2[b]); last(j0[b] + 3 * Ns, y3[b]); }
-            }
-            return;
-        }
         wave_sync();      // every lane has read its inputs before any lane overwrites them
         if (active) {
 #pragma unroll
@@ -162,17 +150,12 @@ __device__ __forceinline__ void fft_inplace(double2 *X, const Twiddles<LOGL, HL>
                 lo[c] = cadd(a0, a1); hi[c] = csub(a0, a1);
             }
         }
-        if (TO_LDS) {
-            wave_sync();
-            if (active) {
+        wave_sync();
+        if (active) {
 #pragma unroll
-                for (int c = 0; c < 2 * NB; c++) { X[t + c * LPT] = lo[c]; X[t + c * LPT + L / 2] = hi[c]; }
-            }
-            wave_sync();
-        } else if (active) {
-#pragma unroll
-            for (int c = 0; c < 2 * NB; c++) { last(t + c * LPT, lo[c]); last(t + c * LPT + L / 2, hi[c]); }
+            for (int c = 0; c < 2 * NB; c++) { X[t + c * LPT] = lo[c]; X[t + c * LPT + L / 2] = hi[c]; }
         }
+        wave_sync();
     }
 }
 
@@ -228,7 +211,7 @@ __device__ __forceinline__ void fft_transpose4(double2 (&v)[4], int lane) {
     fft_swap2<HI - 1>(v[0], v[1], lane); fft_swap2<HI - 1>(v[2], v[3], lane);
 }
 // decimation-in-frequency radix-4 butterfly: y_q = (sum_p a_p (SIGN i)^{pq}) w^q; SIGN = +1 inverse, -1 forward (w conjugated by the caller)
-template <int SIGN = +1>
+template <int SIGN>
 __device__ __forceinline__ void fft_bfly_dif(double2 (&v)[4], double2 w1, bool tw) {
     const double2 t0 = cadd(v[0], v[2]), t1 = csub(v[0], v[2]), t2 = cadd(v[1], v[3]), t3 = cmuli(csub(v[1], v[3]), SIGN);
     const double2 y0 = cadd(t0, t2);
@@ -239,26 +222,23 @@ __device__ __forceinline__ void fft_bfly_dif(double2 (&v)[4], double2 w1, bool t
     }
     v[0] = y0; v[1] = y1; v[2] = y2; v[3] = y3;
 }
-// w[0] = e^{+2 pi i lane / 256}, w[1] = e^{+2 pi i (lane & 15) / 64}, w[2] = e^{+2 pi i (lane & 3) / 16}
-__device__ __forceinline__ void fft_reg256_inverse(double2 (&v)[4], const double2 (&w)[3], int lane) {
-    fft_bfly_dif(v, w[0], true);
+// X[l] = sum_n x[n] e^{SIGN 2 pi i n l / 256}: SIGN = +1 inverse, -1 forward.  w[0] = e^{SIGN 2 pi i lane / 256},
+// w[1] = e^{SIGN 2 pi i (lane & 15) / 64}, w[2] = e^{SIGN 2 pi i (lane & 3) / 16}
+template <int SIGN>
+__device__ __forceinline__ void fft_reg256(double2 (&v)[4], const double2 (&w)[3], int lane) {
+    fft_bfly_dif<SIGN>(v, w[0], true);
     fft_transpose4<5>(v, lane);
-    fft_bfly_dif(v, w[1], true);
+    fft_bfly_dif<SIGN>(v, w[1], true);
     fft_transpose4<3>(v, lane);
-    fft_bfly_dif(v, w[2], true);
+    fft_bfly_dif<SIGN>(v, w[2], true);
     fft_transpose4<1>(v, lane);
-    fft_bfly_dif(v, w[0], false);
+    fft_bfly_dif<SIGN>(v, w[0], false);
 }
-// the mirror: X[l] = sum_n x[n] e^{-2 pi i n l / 256}, same layouts; w[] are the conjugates of fft_reg256_inverse's
-__device__ __forceinline__ void fft_reg256_forward(double2 (&v)[4], const double2 (&w)[3], int lane) {
-    fft_bfly_dif<-1>(v, w[0], true);
-    fft_transpose4<5>(v, lane);
-    fft_bfly_dif<-1>(v, w[1], true);
-    fft_transpose4<3>(v, lane);
-    fft_bfly_dif<-1>(v, w[2], true);
-    fft_transpose4<1>(v, lane);
-    fft_bfly_dif<-1>(v, w[0], false);
-}
+// first of the four bins a lane holds after fft_reg256: v[q] = X[fft_lb(lane) + 64 q]
+__device__ __forceinline__ int fft_lb(int lane) { return (lane >> 4) + 4 * ((lane >> 2) & 3) + 16 * (lane & 3); }
+// LDS index of ring point / bin l in a transform region that the register passes write: one element of padding per 16, so that
+// the 16 lanes of a row - bins 4 a + 16 b - fall into 16 different 16-byte bank groups (stride = 2 mod 16 for the readers)
+__device__ __forceinline__ int fft_pad(int l) { return l + (l >> 4); }
 __device__ __forceinline__ double2 fft_bpermute(double2 v, int src_lane) {
     const FftQ q = fft_toq(v);
     FftQ r;
@@ -275,18 +255,29 @@ __device__ __forceinline__ double2 ldpair(const float *p) { const float2 v = *re
 __device__ __forceinline__ void stpair(double *p, double2 v) { *reinterpret_cast<double2 *>(p) = v; }
 __device__ __forceinline__ void stpair(float *p, double2 v) { *reinterpret_cast<float2 *>(p) = make_float2((float)v.x, (float)v.y); }
 
-// HL / SETS: lanes per transform halved (256-thread workgroups at L = 256) / LDS sets (2: the copy-out of a slot overlaps the
-// next slot's transform inside the workgroup; 1: half the LDS, the overlap comes from more workgroups per CU instead).
-// Only (0, 2) is launched: measured at the bench grid (round 3) HL = 1 with one set 0.148 / 0.153 ms (node / ring-wise), with two
-// sets 0.160 / 0.173 ms, against 0.130 / 0.135 ms - 168 VGPRs with 18-40 spilled registers at three waves per SIMD; at 512 points
-// (config 5) the node kernel with ONE set and 128 registers (two workgroups per CU instead of one): 1.60 against 1.22 ms.
-// FUSE (node mode, L <= 256, b_zDim <= 64): the vertical inverse runs INSIDE this kernel - the workgroup forms its
-// [16 levels x K2] coefficient slab as Mz[v][sz][16 x b_zDim] . A[node][v][b_zDim x K2] on the f64 matrix cores (8 waves x 2
-// column tiles of 16 wavenumber blocks, operands straight from L2), through the LDS set the next slot is about to stage,
-// into the lanes' registers; `Az` of the node-space units is never written or read (k_zinv then only serves the ring-wise rings).
+// Two real sequences ride one complex transform: level a in the real part, level b in the imaginary part.
+struct BinPair { double2 k, n; };         // bins k and L - k of the packed spectrum W
+// inverse: W = Za + i Zb at bin k and conj(Za) + i conj(Zb) at bin L - k from the levels' coefficients, multiplied by (ik)^ld for
+// the ld-th lambda derivative.  At k = 0 the callers put zero into the Nyquist bin instead of `n`.
+__device__ __forceinline__ BinPair packed_bins(double2 aq, double2 bq, int k, int ld) {
+    double2 c = aq, e = bq;
+    if (ld == 1) { c = make_double2(-k * aq.y, k * aq.x); e = make_double2(-k * bq.y, k * bq.x); }
+    else if (ld == 2) { const double qq = -(double)k * k; c.x *= qq; c.y *= qq; e.x *= qq; e.y *= qq; }
+    return {make_double2(c.x - e.y, c.y + e.x), make_double2(c.x + e.y, e.x - c.y)};
+}
+
+// LDS of the kernel, for the kernel and its launcher: two sets of FNP transform regions SKEW apart and, behind them, the twiddle
+// table of the register passes (REG: three 256-point passes x 64 lanes, at 512 points + 4 x 64 of the radix-2 pass in front).
+// REG: the regions only serve the copy-out, ring point l sits at fft_pad(l).
+template <int LOGL, bool REG> struct InvCfg {
+    static constexpr int SKEW = REG ? (1 << LOGL) / 16 + 2 : FftCfg<LOGL>::SKEW;
+    static constexpr int SET = FftCfg<LOGL>::FNP * ((1 << LOGL) + SKEW);                     // complex elements of one set
+    static constexpr int TW2 = 3 * 64, NTW = REG ? TW2 + (LOGL == 9 ? 4 * 64 : 0) : 0;       // start of the radix-2 twiddles; table length
+    static constexpr size_t LDS = sizeof(double2) * (2 * SET + NTW);
+};
 typedef double fft_d4 __attribute__((ext_vector_type(4)));
-template <int LOGL, int COPYOUT, bool NODE, class ST, class AT = double, int HL = 0, int SETS = 2, bool FUSE = false, bool REG = false>
-__global__ void __launch_bounds__(512 >> HL, HL ? 3 : (LOGL <= 8 || SETS == 1) ? 4 : 2)      // waves per SIMD: at L = 512 one workgroup per CU with two LDS sets (2 x 64 KB, 4 wavenumbers per lane), two with one set
+template <int LOGL, class ST, bool NODE, class AT = double, bool FUSE = false, bool REG = false>
+__global__ void __launch_bounds__(512, LOGL <= 8 ? 4 : 2)      // waves per SIMD: at L = 512 one workgroup per CU (2 x 64 KB of LDS, 4 wavenumbers per lane)
 k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi,
                  const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const double2 *__restrict__ twg,
                  const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, const int *__restrict__ slotmask,
@@ -296,12 +287,10 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
                  int unit0 = 0) {
     // NODE: the "rings" are radial NODES (uniform ring tables only): one Az row per unit, no radial combination;
     // the output is the node-space array G that the equation-set kernel combines with the basis weights itself.
-    constexpr int L = 1 << LOGL, T = FftCfg<LOGL, HL>::LPT, NK = FftCfg<LOGL, HL>::NK;
-    constexpr int FZC = FftCfg<LOGL, HL>::FZC, FNP = FftCfg<LOGL, HL>::FNP, LOGZ = FftCfg<LOGL, HL>::LOGZ;
-    // REG: the transform's LDS region only serves the copy-out; ring point l sits at l + (l >> 4), so that the 16 lanes of a row -
-    // points 4 a + 16 b after the last register pass - fall into 16 different 16-byte bank groups (stride = 2 mod 16 for the readers)
-    constexpr int SKEW = REG ? L / 16 + 2 : FftCfg<LOGL, HL>::SKEW;
-    static_assert(!REG || ((LOGL == 8 || LOGL == 9) && HL == 0 && COPYOUT && !FUSE), "register-resident passes: 256- and 512-point transforms with copy-out");
+    constexpr int L = 1 << LOGL, T = FftCfg<LOGL>::LPT, NK = FftCfg<LOGL>::NK;
+    constexpr int FZC = FftCfg<LOGL>::FZC, FNP = FftCfg<LOGL>::FNP, LOGZ = FftCfg<LOGL>::LOGZ;
+    constexpr int SKEW = InvCfg<LOGL, REG>::SKEW, SET = InvCfg<LOGL, REG>::SET, TW2 = InvCfg<LOGL, REG>::TW2;
+    static_assert(!REG || ((LOGL == 8 || LOGL == 9) && !FUSE), "register-resident passes: 256- and 512-point transforms");
     extern __shared__ double2 smf[];
     FFT_STAMP(0);
     int nslot = 0;
@@ -327,7 +316,7 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
     // twiddles and phase factors are fetched BEHIND the first group's coefficient loads (below): the memory counter retires
     // in issue order, and the coefficients are what the first transform waits for.  (Phase stamps: a third of a
     // workgroup's time used to pass before its first transform started - three dependent round trips.)
-    Twiddles<LOGL, HL> tw;
+    Twiddles<LOGL> tw;
     bool setup_done = false;
     const int j0 = NODE ? ring : ring / MUBAR;
     const double2 *phr = ph + phoff[ring];
@@ -363,7 +352,7 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
             constexpr int TPW = ((L / 16 > 0 ? L / 16 : 1) + NWV - 1) / NWV;                        // column tiles (16 wavenumber blocks) per wave
             constexpr int SST = 2 * (L + SKEW) * FNP / FZC;      // row stride (doubles) of the slab: the set's 16-byte elements as 16 rows
             const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n16 = lane & 15, kk4 = lane >> 4;
-            double *S = reinterpret_cast<double *>(smf + ((COPYOUT && SETS == 2) ? par * FNP * (L + SKEW) : 0));
+            double *S = reinterpret_cast<double *>(smf + par * SET);
             const double *arow = Asrc + (int64_t)j0 * Astride + (int64_t)v * Zb * K2;
             const double *mop = MzT + ((int64_t)v * 3 + sz) * Zb * nz + z0 + n16;
             constexpr int KH = 8;                              // operands in halves of 8 K steps: 32 VGPRs live instead of 64
@@ -445,12 +434,12 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
                         // wave writes the whole table and reads back its own writes, no workgroup barrier), not in 12 registers: at the 128
                         // registers of a two-workgroups-per-CU kernel they cost a spilled address, and every reload of it drained the
                         // memory counter - i.e. waited for the previous slot's copy-out stores
-                        double2 *wl = smf + SETS * FNP * (L + SKEW);
+                        double2 *wl = smf + 2 * SET;
                         constexpr int S2 = L / 256;                     // the 256-point passes' angles in a table of L entries
                         wl[tt] = twg[S2 * tt]; wl[64 + tt] = twg[S2 * 4 * (tt & 15)]; wl[128 + tt] = twg[S2 * 16 * (tt & 3)];
                         if (LOGL == 9) {                                // the radix-2 pass in front: e^{+2 pi i (t + 64 q) / 512}
 #pragma unroll
-                            for (int q = 0; q < 4; q++) wl[192 + 64 * q + tt] = twg[tt + 64 * q];
+                            for (int q = 0; q < 4; q++) wl[TW2 + 64 * q + tt] = twg[tt + 64 * q];
                         }
                     } else tw.template init<+1>(twg, tt);
                     if (!NODE) {
@@ -477,21 +466,16 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
         for (int ld = 0; ld < 3; ld++) {
             if (!(ld == 0 ? n0 : ld == 1 ? n1 : n2)) continue;
             const int slot = ld == 0 ? sl0 : ld == 1 ? sl1 : sl2;
-            double2 *set = smf + ((COPYOUT && SETS == 2) ? par * FNP * (L + SKEW) : 0);
+            double2 *set = smf + par * SET;
             double2 *X = set + f * (L + SKEW);
             par ^= 1;
-            if (COPYOUT && SETS == 1 && nslot > 0) lds_barrier();     // the previous slot's copy-out has read this (only) set
             if constexpr (REG) {
                 // packed spectrum W = Za + i Zb of this lane's wavenumbers k = t + 64 q (q < NK) and of their mirrors L - k
                 double2 wk[NK], mir[NK];
 #pragma unroll
                 for (int q = 0; q < NK; q++) {
-                    const int k = kq[q];
-                    double2 c = aq[q], e = bq[q];
-                    if (ld == 1) { c = make_double2(-k * aq[q].y, k * aq[q].x); e = make_double2(-k * bq[q].y, k * bq[q].x); }
-                    else if (ld == 2) { const double qq = -(double)k * k; c.x *= qq; c.y *= qq; e.x *= qq; e.y *= qq; }
-                    wk[q] = make_double2(c.x - e.y, c.y + e.x);
-                    mir[q] = k > 0 ? make_double2(c.x + e.y, e.x - c.y) : make_double2(0.0, 0.0);      // k = 0: the Nyquist bin, zero
+                    const BinPair w = packed_bins(aq[q], bq[q], kq[q], ld);
+                    wk[q] = w.k; mir[q] = kq[q] > 0 ? w.n : make_double2(0.0, 0.0);
                 }
                 // the upper half of the input, x[t + 64 q] for q >= NK, are mirrors W[L - k] that lane 64 - t holds: its wavenumber
                 // q' feeds q = 2 NK - 1 - q'; lane 0 keeps its own: x[L / 2] = 0 (Nyquist), x[64 (2 NK - q')] = W[L - 64 q']
@@ -499,16 +483,16 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
                 double2 r[NK];
 #pragma unroll
                 for (int q = 0; q < NK; q++) r[q] = fft_bpermute(mir[q], src);
-                const double2 *wl = smf + SETS * FNP * (L + SKEW);
+                const double2 *wl = smf + 2 * SET;
                 const double2 wreg[3] = {wl[t], wl[64 + t], wl[128 + t]};
-                const int lb = (t >> 4) + 4 * ((t >> 2) & 3) + 16 * (t & 3);
+                const int lb = fft_lb(t);
                 if constexpr (LOGL == 8) {
                     double2 v[4] = {wk[0], wk[1], t == 0 ? r[0] : r[1], t == 0 ? r[1] : r[0]};
-                    fft_reg256_inverse(v, wreg, t);
+                    fft_reg256<+1>(v, wreg, t);
                     if (nslot == 0) FFT_STAMP(2); else if (nslot == 1) FFT_STAMP(5);
                     if (active) {
 #pragma unroll
-                        for (int q = 0; q < 4; q++) { const int l = lb + 64 * q; X[l + (l >> 4)] = v[q]; }
+                        for (int q = 0; q < 4; q++) X[fft_pad(lb + 64 * q)] = v[q];
                     }
                 } else {
                     // 512 points: one radix-2 pass in registers (x[m] +- x[m + 256], the difference turned by e^{+2 pi i m / 512}),
@@ -518,17 +502,17 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
 #pragma unroll
                     for (int q = 0; q < 4; q++) {
                         ev[q] = cadd(wk[q], hi[q]);
-                        od[q] = cmul(csub(wk[q], hi[q]), wl[192 + 64 * q + t]);
+                        od[q] = cmul(csub(wk[q], hi[q]), wl[TW2 + 64 * q + t]);
                     }
-                    fft_reg256_inverse(ev, wreg, t);
-                    fft_reg256_inverse(od, wreg, t);
+                    fft_reg256<+1>(ev, wreg, t);
+                    fft_reg256<+1>(od, wreg, t);
                     if (nslot == 0) FFT_STAMP(2); else if (nslot == 1) FFT_STAMP(5);
                     if (active) {
 #pragma unroll
                         for (int q = 0; q < 4; q++) {
                             const int l = 2 * (lb + 64 * q);
-                            X[l + (l >> 4)] = ev[q];
-                            X[l + 1 + ((l + 1) >> 4)] = od[q];
+                            X[fft_pad(l)] = ev[q];
+                            X[fft_pad(l + 1)] = od[q];
                         }
                     }
                 }
@@ -537,73 +521,50 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
 #pragma unroll
                 for (int q = 0; q < NK; q++) {
                     const int k = kq[q];
-                    double2 c = aq[q], e = bq[q];
-                    if (ld == 1) {                                     // multiply by ik
-                        c = make_double2(-k * aq[q].y, k * aq[q].x); e = make_double2(-k * bq[q].y, k * bq[q].x);
-                    } else if (ld == 2) {                              // multiply by -k^2
-                        const double qq = -(double)k * k;
-                        c.x *= qq; c.y *= qq; e.x *= qq; e.y *= qq;
-                    }
-                    // W = Za + i Zb at bin k, conj(Za) + i conj(Zb) at bin L - k; Nyquist bin is zero
-                    X[k] = make_double2(c.x - e.y, c.y + e.x);
-                    if (k > 0) X[L - k] = make_double2(c.x + e.y, e.x - c.y);
+                    const BinPair w = packed_bins(aq[q], bq[q], k, ld);
+                    X[k] = w.k;
+                    if (k > 0) X[L - k] = w.n;
                     else X[L / 2] = make_double2(0.0, 0.0);
                 }
             }
             if (!REG) wave_sync();
-            if (COPYOUT) {
-                // last pass goes back to LDS, then the whole workgroup writes full 128-byte lines
-                if constexpr (!REG) {
-                    fft_inplace<LOGL, +1, true, NoSink, HL>(X, tw, t, active);
-                    if (nslot == 0) FFT_STAMP(2); else if (nslot == 1) FFT_STAMP(5);
-                }
-                lds_barrier();       // also orders the previous slot's copy-out reads (other set) before that set is restaged
-                if (nslot == 0) FFT_STAMP(3);
-                // thread -> (level pair zp, ring point l0 + (2 * 512 / FZC) i): a transform's LDS element l IS the pair of levels
-                // (2 zp, 2 zp + 1) of ring point l, so it leaves as one 16-byte store (8 bytes for fp32-stored slots);
-                // consecutive lanes cover the FZC levels of one point = one 128-byte line.  16 B per lane matters: at 8 B
-                // per lane the vector-memory pipe of a CU moves ~7 B/clk, about half of what the kernel needs.
-                const int zp = threadIdx.x & (FNP - 1);
-                const double2 *src2 = set + zp * (L + SKEW);
-                auto copy_out = [&](auto *out) {
-                    using OT = decltype(+out[0]);
-                    typedef OT ov2 __attribute__((ext_vector_type(2)));
-                    if (pair_ok && 2 * zp + 1 < zc) {
-#pragma unroll 4
-                        for (int l = threadIdx.x >> (LOGZ - 1); l < L; l += (int)(blockDim.x >> (LOGZ - 1))) {
-                            const double2 y = src2[REG ? l + (l >> 4) : l];
-                            ov2 o2;
-                            o2.x = (OT)y.x; o2.y = (OT)y.y;
-                            __builtin_nontemporal_store(o2, reinterpret_cast<ov2 *>(out + (int64_t)l * nz + 2 * zp));
-                        }
-                    } else if (2 * zp < zc) {      // odd zDim (pairs not 16-byte aligned) or the last level of an odd chunk
-                        const bool two = 2 * zp + 1 < zc;
-                        for (int l = threadIdx.x >> (LOGZ - 1); l < L; l += (int)(blockDim.x >> (LOGZ - 1))) {
-                            const double2 y = src2[REG ? l + (l >> 4) : l];
-                            __builtin_nontemporal_store((OT)y.x, out + (int64_t)l * nz + 2 * zp);
-                            if (two) __builtin_nontemporal_store((OT)y.y, out + (int64_t)l * nz + 2 * zp + 1);
-                        }
-                    }
-                };
-                if (slot == 0) copy_out(phys.val + (int64_t)v * N + p0 * nz + z0);
-                else copy_out(phys.der + ((int64_t)(slot - 1) * V + v) * N + p0 * nz + z0);
-                if (nslot == 0) FFT_STAMP(4); else if (nslot == 1) FFT_STAMP(6);
-                nslot++;
-            } else {
-                const int64_t o0 = p0 * nz + z0 + za;
-                auto sink = [&](int l, double2 y) {
-                    if (slot == 0) {
-                        double *o = phys.val + (int64_t)v * N + o0 + (int64_t)l * nz;
-                        if (pair_ok && hasb) *reinterpret_cast<double2 *>(o) = y;
-                        else { o[0] = y.x; if (hasb) o[1] = y.y; }
-                    } else {
-                        ST *o = phys.der + ((int64_t)(slot - 1) * V + v) * N + o0 + (int64_t)l * nz;
-                        o[0] = (ST)y.x; if (hasb) o[1] = (ST)y.y;
-                    }
-                };
-                fft_inplace<LOGL, +1, false, decltype(sink), HL>(X, tw, t, active, sink);
-                wave_sync();      // the region is rewritten by the next slot
+            // last pass goes back to LDS, then the whole workgroup writes full 128-byte lines
+            if constexpr (!REG) {
+                fft_inplace<LOGL, +1>(X, tw, t, active);
+                if (nslot == 0) FFT_STAMP(2); else if (nslot == 1) FFT_STAMP(5);
             }
+            lds_barrier();       // also orders the previous slot's copy-out reads (other set) before that set is restaged
+            if (nslot == 0) FFT_STAMP(3);
+            // thread -> (level pair zp, ring point l0 + (2 * 512 / FZC) i): a transform's LDS element l IS the pair of levels
+            // (2 zp, 2 zp + 1) of ring point l, so it leaves as one 16-byte store (8 bytes for fp32-stored slots);
+            // consecutive lanes cover the FZC levels of one point = one 128-byte line.  16 B per lane matters: at 8 B
+            // per lane the vector-memory pipe of a CU moves ~7 B/clk, about half of what the kernel needs.
+            const int zp = threadIdx.x & (FNP - 1);
+            const double2 *src2 = set + zp * (L + SKEW);
+            auto copy_out = [&](auto *out) {
+                using OT = decltype(+out[0]);
+                typedef OT ov2 __attribute__((ext_vector_type(2)));
+                if (pair_ok && 2 * zp + 1 < zc) {
+#pragma unroll 4
+                    for (int l = threadIdx.x >> (LOGZ - 1); l < L; l += (int)(blockDim.x >> (LOGZ - 1))) {
+                        const double2 y = src2[REG ? fft_pad(l) : l];
+                        ov2 o2;
+                        o2.x = (OT)y.x; o2.y = (OT)y.y;
+                        __builtin_nontemporal_store(o2, reinterpret_cast<ov2 *>(out + (int64_t)l * nz + 2 * zp));
+                    }
+                } else if (2 * zp < zc) {      // odd zDim (pairs not 16-byte aligned) or the last level of an odd chunk
+                    const bool two = 2 * zp + 1 < zc;
+                    for (int l = threadIdx.x >> (LOGZ - 1); l < L; l += (int)(blockDim.x >> (LOGZ - 1))) {
+                        const double2 y = src2[REG ? fft_pad(l) : l];
+                        __builtin_nontemporal_store((OT)y.x, out + (int64_t)l * nz + 2 * zp);
+                        if (two) __builtin_nontemporal_store((OT)y.y, out + (int64_t)l * nz + 2 * zp + 1);
+                    }
+                }
+            };
+            if (slot == 0) copy_out(phys.val + (int64_t)v * N + p0 * nz + z0);
+            else copy_out(phys.der + ((int64_t)(slot - 1) * V + v) * N + p0 * nz + z0);
+            if (nslot == 0) FFT_STAMP(4); else if (nslot == 1) FFT_STAMP(6);
+            nslot++;
         }
     }
     FFT_STAMP(7);
@@ -670,7 +631,7 @@ k_fl_forward_fft(const double *__restrict__ np1, FT *__restrict__ Fl, const int 
     __syncthreads();
     double2 *X = smf + (f < FNP ? f : 0) * (L + SKEW);
     // forward transform; the last pass leaves the spectrum in LDS (the untangling needs bins k and L - k)
-    fft_inplace<LOGL, -1, true>(X, tw, t, active);
+    fft_inplace<LOGL, -1>(X, tw, t, active);
     if (!active) return;
     const double2 *phr = ph + phoff[ring];
     const double inv = 1.0 / L;
@@ -710,7 +671,7 @@ k_fl_forward_fft(const double *__restrict__ np1, FT *__restrict__ Fl, const int 
 // ring's tile loads are issued before the current ring's transform and stay in flight across it.
 // Round 6, measured with the phase stamps below (profiles/r06/phases_forward_cells_*.txt; per ring and workgroup, wave 0):
 //   REG (256 points, SX_FFT_REG, default on): the staged tile is already the input layout of the register-resident passes
-//   (v[q] = x[t + 64 q]), so the transform is one LDS read, fft_reg256_forward, and one write-back of the digit-reversed bins into the
+//   (v[q] = x[t + 64 q]), so the transform is one LDS read, fft_reg256<-1>, and one write-back of the digit-reversed bins into the
 //   same region, from which the untangling reads bins k and L - k as before - the lanes keep their wavenumbers k = t, t + T, and the
 //   node sums, the truncation test and store_node are untouched.  Transform 2,819 -> 1,553 cycles, ring 6,495 -> 5,506.  SX_FFT_REG=0 and shorter rings
 //   keep fft_inplace and give the bits they gave.
@@ -724,12 +685,12 @@ k_fl_forward_fft(const double *__restrict__ np1, FT *__restrict__ Fl, const int 
 // l + (l >> 4) as in the inverse kernel's copy-out sets, so that the write-back of the digit-reversed bins (16 lanes of a row: bins
 // 4 a + 16 b) is free of bank conflicts.  The kernel and its launcher (LDS size) both take it from here.
 template <int LOGL, bool REG> struct CellsCfg {
-    static constexpr int SKEW = REG ? (1 << LOGL) / 16 + 2 : FftCfg<LOGL>::SKEW;
-    static constexpr size_t LDS = sizeof(double2) * 2 * FftCfg<LOGL>::FNP * ((1 << LOGL) + SKEW);      // two sets
+    static constexpr int SKEW = InvCfg<LOGL, REG>::SKEW;
+    static constexpr size_t LDS = sizeof(double2) * 2 * InvCfg<LOGL, REG>::SET;      // two sets
 };
 
 template <int LOGL, bool REG = false>
-__global__ void __launch_bounds__((FftCfg<LOGL>::FNP * FftCfg<LOGL>::LPT < 64 ? 64 : FftCfg<LOGL>::FNP * FftCfg<LOGL>::LPT), 2)
+__global__ void __launch_bounds__(FftCfg<LOGL>::THREADS, 2)
 k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, double *__restrict__ Fe, const int *__restrict__ kmaxr,
                    const int64_t *__restrict__ pstart, const double2 *__restrict__ twg, const int64_t *__restrict__ phoff,
                    const double2 *__restrict__ ph, const double *__restrict__ phi, const double *__restrict__ wq,
@@ -738,7 +699,7 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
     constexpr int FZC = FftCfg<LOGL>::FZC, FNP = FftCfg<LOGL>::FNP, LOGZ = FftCfg<LOGL>::LOGZ, SKEW = CellsCfg<LOGL, REG>::SKEW;
     static_assert(LOGL <= 8 && NK == 2 && PPT == 4, "one butterfly per lane and pass: rings of at most 256 points");
     static_assert(!REG || LOGL == 8, "register-resident passes: 256-point transforms");
-    auto at = [](int l) { return REG ? l + (l >> 4) : l; };
+    auto at = [](int l) { return REG ? fft_pad(l) : l; };
     typedef double dv2 __attribute__((ext_vector_type(2)));
     extern __shared__ double2 smf[];
     const int z0 = blockIdx.x * FZC, v = blockIdx.y, seg = blockIdx.z;
@@ -750,7 +711,7 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
     const int zp = tid & (FNP - 1);
     const int64_t plane = (int64_t)V * nz * K2;            // one node's [v][level][K2] spectra
     Twiddles<LOGL> tw;
-    double2 wreg[3];                                       // REG: conjugates of fft_reg256_inverse's three twiddles
+    double2 wreg[3];                                       // REG: the three twiddles of fft_reg256<-1>
     if constexpr (REG) { wreg[0] = cconj(twg[t]); wreg[1] = cconj(twg[4 * (t & 15)]); wreg[2] = cconj(twg[16 * (t & 3)]); }
     else tw.template init<-1>(twg, t);
     const double *xb = np1 + (int64_t)v * N + z0 + 2 * zp;
@@ -817,13 +778,13 @@ k_fl_forward_cells(const double *__restrict__ np1, double *__restrict__ Fn, doub
 #pragma unroll
                 for (int q = 0; q < 4; q++) v4[q] = X[at(t + 64 * q)];
                 wave_sync();
-                fft_reg256_forward(v4, wreg, t);
-                const int lb = (t >> 4) + 4 * ((t >> 2) & 3) + 16 * (t & 3);
+                fft_reg256<-1>(v4, wreg, t);
+                const int lb = fft_lb(t);
 #pragma unroll
                 for (int q = 0; q < 4; q++) X[at(lb + 64 * q)] = v4[q];
                 wave_sync();
             } else
-                fft_inplace<LOGL, -1, true>(X, tw, t, active);
+                fft_inplace<LOGL, -1>(X, tw, t, active);
             CELLS_STAMP(2);
             if (active) {
                 const double w = wq[ring];
@@ -889,10 +850,6 @@ bool fft_fused_zinv(const sx_handle *h) {
     return h->sw.fuse_zinv && h->node_mode && h->has_z && h->uniform_L <= 256 && h->Zb <= 64 && h->nz % 16 == 0 && !h->sp32;
 }
 
-static int fft_fzc(int) { return 16; }
-static size_t fft_lds(int L, int sets = 1, bool reg = false) { return sizeof(double2) * ((size_t)sets * (fft_fzc(L) / 2) * (L + (reg ? L / 16 + 2 : L <= 256 ? 2 : 0)) + (reg ? (L == 512 ? 448 : 192) : 0)); }
-static int fft_threads(int L, int hl = 0) { return std::max(64, (fft_fzc(L) / 2) * (std::min(L / 4, 64) >> hl)); }       // FNP transforms x LPT lanes
-
 struct InvTarget {          // where an inverse ring launch writes and which unit tables it uses
     double *out;            // physical [slot][v][N] or node-space G [slot][v][NG]
     const double *phi;      // [3][n_phi][4]
@@ -904,51 +861,38 @@ struct InvTarget {          // where an inverse ring launch writes and which uni
     int unit0 = 0;          // first unit of the launch (the node-space launch skips the nodes only the ring-wise inner rings read)
 };
 
+// the one launch of k_rl_inverse_fft; FUSE: the vertical inverse's operands instead of Az
+template <int LOGL, class ST, bool NODE, class AT, bool FUSE = false, bool REG = false>
+static void launch_inv_k(sx_handle *h, const int *d_mask, const InvTarget &tg, const double *az, int64_t azrow) {
+    const auto kernel = k_rl_inverse_fft<LOGL, ST, NODE, AT, FUSE, REG>;
+    constexpr size_t lds = InvCfg<LOGL, REG>::LDS;
+    if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const dim3 g((h->nz + FFT_FZC - 1) / FFT_FZC, tg.n_units, h->V);
+    hipLaunchKernelGGL(kernel, g, dim3(FftCfg<LOGL>::THREADS), lds, h->stream, reinterpret_cast<const AT *>(az),
+                       planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart, h->d_tw, tg.phoff, h->d_ph, d_mask, h->V, h->nz,
+                       h->nsz, h->K2, tg.n_phi, tg.N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],
+                       h->slot[6], FUSE ? h->d_A + (int64_t)h->cell0 * h->C : nullptr, FUSE ? (int64_t)h->C : 0,
+                       FUSE ? h->d_MzT : nullptr, FUSE ? h->Zb : 0, tg.unit0);
+}
+
+// SX_FFT_REG (default on): register-resident passes at 256 and 512 points
+template <int LOGL, class ST, bool NODE, class AT>
+static void launch_inv_v(sx_handle *h, const int *d_mask, const InvTarget &tg, const double *az, int64_t azrow) {
+    if constexpr (LOGL == 8 || LOGL == 9) { if (h->sw.fft_reg) { launch_inv_k<LOGL, ST, NODE, AT, false, true>(h, d_mask, tg, az, azrow); return; } }
+    launch_inv_k<LOGL, ST, NODE, AT>(h, d_mask, tg, az, azrow);
+}
+
 template <int LOGL>
 static void launch_inv(sx_handle *h, const int *d_mask, const InvTarget &tg, const double *az, int64_t azrow) {
-    const int L = 1 << LOGL;
-    dim3 g((h->nz + fft_fzc(L) - 1) / fft_fzc(L), tg.n_units, h->V);
-#define INV_LAUNCH_V(NODE, ST, AT, HL, SETS)                                                                                         \
-    do {                                                                                                                             \
-        if (fft_lds(L, SETS) > 65536)                                                                                                \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, HL, SETS>),           \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds(L, SETS)));                        \
-        hipLaunchKernelGGL((k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, HL, SETS>), g, dim3(fft_threads(L, HL)), fft_lds(L, SETS), h->stream, \
-                           reinterpret_cast<const AT *>(az), planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart,          \
-                           h->d_tw, tg.phoff, h->d_ph, d_mask, h->V, h->nz, h->nsz, h->K2, tg.n_phi, tg.N, azrow, h->slot[0],        \
-                           h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5], h->slot[6], nullptr, (int64_t)0, nullptr, 0,  \
-                           tg.unit0);                                                                                                \
-    } while (0)
-#define INV_LAUNCH_REG(NODE, ST, AT)                                                                                                 \
-    do {                                                                                                                             \
-        constexpr int RS = 2;                                                                                                        \
-        if (fft_lds(L, RS, true) > 65536)                                                                                            \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, 0, RS, false, true>), \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)fft_lds(L, RS, true)));                    \
-        hipLaunchKernelGGL((k_rl_inverse_fft<LOGL, 1, NODE, ST, AT, 0, RS, false, true>), g, dim3(fft_threads(L, 0)), fft_lds(L, RS, true), h->stream, \
-                           reinterpret_cast<const AT *>(az), planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart,          \
-                           h->d_tw, tg.phoff, h->d_ph, d_mask, h->V, h->nz, h->nsz, h->K2, tg.n_phi, tg.N, azrow, h->slot[0],        \
-                           h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5], h->slot[6], nullptr, (int64_t)0, nullptr, 0,  \
-                           tg.unit0);                                                                                                \
-    } while (0)
-#define INV_LAUNCH(NODE, ST, AT)                                                                                                     \
-    do {                                                                                                                             \
-        if constexpr (LOGL == 8 || LOGL == 9) { if (h->sw.fft_reg) { INV_LAUNCH_REG(NODE, ST, AT); break; } }                                        \
-        INV_LAUNCH_V(NODE, ST, AT, 0, 2);                                                                                            \
-    } while (0)
-#define INV_LAUNCH_FUSED(ST)                                                                                                         \
-    hipLaunchKernelGGL((k_rl_inverse_fft<LOGL, 1, true, ST, double, 0, 2, true>), g, dim3(fft_threads(L)), fft_lds(L, 2), h->stream,  \
-                       az, planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart, h->d_tw, tg.phoff, h->d_ph, d_mask, h->V,   \
-                       h->nz, h->nsz, h->K2, tg.n_phi, tg.N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4],       \
-                       h->slot[5], h->slot[6], h->d_A + (int64_t)h->cell0 * h->C, h->C, h->d_MzT, h->Zb, tg.unit0)
-    if (tg.node_mode && fft_fused_zinv(h)) { if (LOGL <= 8) { if (h->f32) INV_LAUNCH_FUSED(float); else INV_LAUNCH_FUSED(double); } }
-    else if (h->sp32) { if (tg.node_mode) INV_LAUNCH(true, float, float); else INV_LAUNCH(false, float, float); }     // storage_f32 = 2
-    else if (h->f32) { if (tg.node_mode) INV_LAUNCH(true, float, double); else INV_LAUNCH(false, float, double); }
-    else { if (tg.node_mode) INV_LAUNCH(true, double, double); else INV_LAUNCH(false, double, double); }
-#undef INV_LAUNCH_FUSED
-#undef INV_LAUNCH
-#undef INV_LAUNCH_REG
-#undef INV_LAUNCH_V
+    if (tg.node_mode && fft_fused_zinv(h)) {
+        if (LOGL <= 8) { if (h->f32) launch_inv_k<LOGL, float, true, double, true>(h, d_mask, tg, az, azrow); else launch_inv_k<LOGL, double, true, double, true>(h, d_mask, tg, az, azrow); }
+    } else if (h->sp32) {      // storage_f32 = 2
+        if (tg.node_mode) launch_inv_v<LOGL, float, true, float>(h, d_mask, tg, az, azrow); else launch_inv_v<LOGL, float, false, float>(h, d_mask, tg, az, azrow);
+    } else if (h->f32) {
+        if (tg.node_mode) launch_inv_v<LOGL, float, true, double>(h, d_mask, tg, az, azrow); else launch_inv_v<LOGL, float, false, double>(h, d_mask, tg, az, azrow);
+    } else {
+        if (tg.node_mode) launch_inv_v<LOGL, double, true, double>(h, d_mask, tg, az, azrow); else launch_inv_v<LOGL, double, false, double>(h, d_mask, tg, az, azrow);
+    }
 }
 
 static void launch_inv_any(sx_handle *h, const int *d_mask, const InvTarget &tg) {
@@ -968,13 +912,12 @@ static void launch_inv_any(sx_handle *h, const int *d_mask, const InvTarget &tg)
 
 template <int LOGL>
 static void launch_fwd(sx_handle *h, dim3 g) {
-    const int L = 1 << LOGL;
     if (h->sp32)
-        hipLaunchKernelGGL((k_fl_forward_fft<LOGL, float>), g, dim3(fft_threads(L)), fft_lds(L), h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
+        hipLaunchKernelGGL((k_fl_forward_fft<LOGL, float>), g, dim3(FftCfg<LOGL>::THREADS), FftCfg<LOGL>::LDS, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
                            reinterpret_cast<float *>(h->d_Fl) + (int64_t)h->v_lo * h->nz * h->K2,
                            h->d_kmax, h->d_pstart, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N);
     else       // the variable window [v_lo, v_lo + v_cnt) (sx_internal.hpp): blockIdx.y counts from v_lo through the base pointers
-        hipLaunchKernelGGL((k_fl_forward_fft<LOGL, double>), g, dim3(fft_threads(L)), fft_lds(L), h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
+        hipLaunchKernelGGL((k_fl_forward_fft<LOGL, double>), g, dim3(FftCfg<LOGL>::THREADS), FftCfg<LOGL>::LDS, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
                            h->d_Fl + (int64_t)h->v_lo * h->nz * h->K2, h->d_kmax,
                            h->d_pstart, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N);
 }
@@ -1012,7 +955,7 @@ void launch_node_fft(sx_handle *h) {
     timer_begin(h, id);
 #ifdef SX_PHASES
     if (!g_fft_buf) {
-        g_fft_n = (int64_t)((h->nz + fft_fzc(h->uniform_L) - 1) / fft_fzc(h->uniform_L)) * h->V * h->nbt;
+        g_fft_n = (int64_t)((h->nz + FFT_FZC - 1) / FFT_FZC) * h->V * h->nbt;
         hipMalloc(&g_fft_buf, sizeof(long long) * g_fft_n * 8);
         hipMemset(g_fft_buf, 0, sizeof(long long) * g_fft_n * 8);
         hipMemcpyToSymbol(HIP_SYMBOL(g_fft_dbg), &g_fft_buf, sizeof(g_fft_buf));
@@ -1028,11 +971,10 @@ void launch_node_fft(sx_handle *h) {
 
 template <int LOGL, bool REG>
 static void launch_fwd_cells_v(sx_handle *h, const CellsPlan &p) {
-    const int L = 1 << LOGL;
     const size_t lds = CellsCfg<LOGL, REG>::LDS;
     if (lds > 65536)
         HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_cells<LOGL, REG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    dim3 g(h->nz / fft_fzc(L), h->v_cnt, p.segs);
+    dim3 g(h->nz / FFT_FZC, h->v_cnt, p.segs);
 #ifdef SX_PHASES
     if (const int64_t n = (int64_t)g.x * g.y * g.z; n > g_cells_n) {      // stamps of the LAST launch: sized for the largest grid so far
         if (g_cells_buf) { hipDeviceSynchronize(); hipFree(g_cells_buf); }
@@ -1072,8 +1014,7 @@ void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {
 void launch_fl_forward_fft(sx_handle *h) {
     const int id = timer_id(h, "k_fl_forward");
     timer_begin(h, id);
-    const int fzc = fft_fzc(h->uniform_L);
-    dim3 g((h->nz + fzc - 1) / fzc, h->v_cnt, h->nrings);
+    dim3 g((h->nz + FFT_FZC - 1) / FFT_FZC, h->v_cnt, h->nrings);
     switch (ilog2(h->uniform_L)) {
         case 4: launch_fwd<4>(h, g); break;
         case 5: launch_fwd<5>(h, g); break;
