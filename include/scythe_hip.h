@@ -188,6 +188,18 @@ int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_
 enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2, SX_PLAN_FORWARD_CELLS = 3 };
 int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap);
 
+/* The work lists of the native-ring DFT launches (csrc/sx_dft.hip) of a tile of cells cell0 .. cell0 + num_cells - 1 with Springsteel's
+ * ragged rings: pairs (tile ring, x) in launch order, most expensive first; items[2 cap] receives them where cap holds them all
+ * (items may be null: counts only; too small a cap is an error); counts[0] = pairs, counts[1] = of which - listed first - pairs of rings with kmax > 319.
+ *   SX_DFT_LIST_RLZ         RLZ grids: x = variable; planes[n_vars] = derivative planes asked of each variable (0: no pair; the forward
+ *                           list is the one with 1 everywhere)
+ *   SX_DFT_LIST_RL_INVERSE  RL grids, inverse: x = part of 8 row tiles of the quarter ring (n_vars, planes: not read)
+ *   SX_DFT_LIST_RL_FORWARD  RL grids, forward: x = part of 128 wavenumbers
+ * Pure host helper (no handle, no device): the tests compare the lists with the rule stated here; never on the step path. */
+enum { SX_DFT_LIST_RLZ = 0, SX_DFT_LIST_RL_INVERSE = 1, SX_DFT_LIST_RL_FORWARD = 2 };
+int sx_dft_work_list(int32_t kind, int32_t cell0, int32_t num_cells, int32_t n_vars, const int32_t *planes, int32_t *items, int64_t cap,
+                     int32_t *counts);
+
 /* --- state in / out (host pointers, reference layouts) ------------------------------------------------------------- */
 /* read_physical_grid -> physical[:, v, 1]  (src/semiimplicit.jl:134): values[n_points, n_vars] */
 int sx_set_physical_values(sx_handle *h, const double *values);

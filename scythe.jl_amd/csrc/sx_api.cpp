@@ -66,6 +66,17 @@ static bool upload(sx_handle *h, T **p, const std::vector<T> &v) {
     return true;
 }
 
+// (ring, variable) work list of the native-ring DFT kernels on RLZ grids: cost = ring length squared x planes of the variable (none:
+// no item).  Rings whose coefficient sets do not fit the LDS in one piece (kmax > 319) go first - nbig items - and take the chunked
+// kernels (sx_dft.hip); the rest keeps the single-pass kernels, sized for ITS largest ring.
+template <class Planes>
+static DftItems rlz_dft_items(const std::vector<int> &hL, const std::vector<int> &hkmax, int V, Planes planes, int &nbig) {
+    DftItems it = dft_work_items((int)hL.size(), [&](int) { return V; }, [&](int r, int v) { return (int64_t)hL[r] * hL[r] * planes(v); });
+    const auto big = [&](const std::array<int, 2> &e) { return hkmax[e[0]] > DFT_KMAX_SINGLE; };
+    nbig = (int)(std::stable_partition(it.begin(), it.end(), big) - it.begin());
+    return it;
+}
+
 static std::vector<double> transpose(const std::vector<double> &m, int n) {
     std::vector<double> t((size_t)n * n);
     for (int i = 0; i < n; i++)
@@ -631,27 +642,13 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
             // decreasing cost (ring length squared x planes of the variable) so that the cheap ones fill the tail;
             // variables without a requested slot get no workgroup at all.
             for (int which = 0; which < 3; which++) {
-                std::vector<std::array<int64_t, 3>> it;          // (cost, ring, v)
-                for (int r = 0; r < h->nrings; r++)
-                    for (int v = 0; v < h->V; v++) {
-                        const int planes = which == 2 ? 1 : __builtin_popcount(which == 0 ? eq[v] : full[v]);
-                        if (planes == 0) continue;
-                        it.push_back({(int64_t)h->hL[r] * h->hL[r] * planes, r, v});
-                    }
-                std::stable_sort(it.begin(), it.end(), [](const auto &a, const auto &b) { return a[0] > b[0]; });
-                // rings whose coefficient sets do not fit the LDS in one piece (kmax > 319) go first and take the chunked
-                // kernels (sx_dft.hip); the rest keeps the single-pass kernels, sized for ITS largest ring
-                std::stable_partition(it.begin(), it.end(), [&](const auto &e) { return h->hkmax[e[1]] > DFT_KMAX_SINGLE; });
-                std::vector<int> flat;
-                int nbig = 0;
-                for (const auto &e : it) {
-                    flat.push_back((int)e[1]); flat.push_back((int)e[2]);
-                    if (h->hkmax[e[1]] > DFT_KMAX_SINGLE) nbig++;
-                    else { h->dft_lcap_small = std::max(h->dft_lcap_small, h->hL[e[1]]); h->dft_kcap_small = std::max(h->dft_kcap_small, h->hkmax[e[1]]); }
+                const DftItems it = rlz_dft_items(h->hL, h->hkmax, h->V, [&](int v) { return which == 2 ? 1 : __builtin_popcount(which == 0 ? eq[v] : full[v]); },
+                                                  h->n_dft_big[which]);
+                for (size_t i = h->n_dft_big[which]; i < it.size(); i++) {
+                    h->dft_lcap_small = std::max(h->dft_lcap_small, h->hL[it[i][0]]);
+                    h->dft_kcap_small = std::max(h->dft_kcap_small, h->hkmax[it[i][0]]);
                 }
-                h->n_dft_big[which] = nbig;
-                h->n_dft_items[which] = (int)it.size();
-                if (!upload(h, &h->d_dft_items[which], flat)) FAIL();
+                if (!dft_upload_items(h, it, &h->d_dft_items[which], &h->n_dft_items[which], true)) FAIL();
             }
         }
         // node-space ("radial last") inverse: uniform power-of-two rings + the MFMA HRBL kernel
@@ -814,6 +811,29 @@ int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, 
         out[0] = p.R; out[1] = p.logR; out[2] = p.threads;
     }
     if (kernel && kernel_cap > 0) snprintf(kernel, (size_t)kernel_cap, "%s", name.c_str());
+    return 0;
+}
+
+constexpr int DFT_LIST_MAX_CELLS = 100000;      // far beyond any patch (the LDS-resident twiddle table ends at 426 cells); keeps 3 x cells in int
+int sx_dft_work_list(int32_t kind, int32_t cell0, int32_t num_cells, int32_t n_vars, const int32_t *planes, int32_t *items, int64_t cap,
+                     int32_t *counts) {
+    clear_error();
+    if (!counts || (kind == SX_DFT_LIST_RLZ && !planes)) { set_error("sx_dft_work_list: null argument"); return 1; }
+    if (kind < SX_DFT_LIST_RLZ || kind > SX_DFT_LIST_RL_FORWARD) { set_error("sx_dft_work_list: unknown kind " + std::to_string(kind)); return 1; }
+    if (cell0 < 0 || num_cells < 1 || (kind == SX_DFT_LIST_RLZ && n_vars < 1)) { set_error("sx_dft_work_list: dimensions must be positive"); return 1; }
+    if ((int64_t)cell0 + num_cells > DFT_LIST_MAX_CELLS) { set_error("sx_dft_work_list: more than " + std::to_string(DFT_LIST_MAX_CELLS) + " cells"); return 1; }
+    std::vector<int> hL(num_cells * MUBAR), hkmax(hL.size());
+    for (size_t i = 0; i < hL.size(); i++) {
+        double off;
+        ring_table(1, 0, cell0 * MUBAR + (int)i + 1, hL[i], hkmax[i], off);
+    }
+    int nbig = 0;
+    const DftItems it = kind == SX_DFT_LIST_RLZ ? rlz_dft_items(hL, hkmax, n_vars, [&](int v) { return planes[v]; }, nbig)
+                                                : rlq_items(hL, hkmax, kind == SX_DFT_LIST_RL_INVERSE ? 0 : 1);
+    counts[0] = (int32_t)it.size(); counts[1] = nbig;
+    if (!items) return 0;
+    if (cap < (int64_t)it.size()) { set_error("sx_dft_work_list: items holds " + std::to_string(cap) + " pairs, the list has " + std::to_string(it.size())); return 1; }
+    for (size_t i = 0; i < it.size(); i++) { items[2 * i] = it[i][0]; items[2 * i + 1] = it[i][1]; }
     return 0;
 }
 

@@ -49,6 +49,20 @@ __device__ __forceinline__ int wrap_add(int m, int step, int L) {
     return (int)min(t, t - (unsigned)L);
 }
 
+// Dynamic LDS of a kernel, in doubles: the ring's twiddle table [lcap] (cos, sin)(2 pi m / L) first, then n equal tiles.  The kernel
+// takes the pointers from it, the launcher the byte count.
+struct TableTiles {
+    size_t lcap, tile;      // ring points the table is sized for (the launch's longest ring), doubles per tile
+    int n;
+    __host__ __device__ double2 *table(double *sm) const { return reinterpret_cast<double2 *>(sm); }
+    __host__ __device__ double *at(double *sm, int t) const { return sm + 2 * lcap + t * tile; }
+    size_t bytes() const { return sizeof(double) * (2 * lcap + n * tile); }
+};
+// cosine and sine coefficients [rows][stride] of the inverse kernels
+__host__ __device__ inline TableTiles lds_coef(int lcap, int rows, int stride) { return {(size_t)lcap, (size_t)rows * stride, 2}; }
+// [parity][cosine / sine part][rows][CST] folded ring points of the quarter-wave forward kernels
+__host__ __device__ inline TableTiles lds_fold(int lcap, int rows) { return {(size_t)lcap, (size_t)rows * CST, 4}; }
+
 // ------------------------------------------------------------------------------------------------ inverse
 // One row-tile pair of the half ring: rows l0 / l1 (clamped), angle index m = (k l) mod L advancing by 4 l per K step.
 struct RowPair {
@@ -63,42 +77,143 @@ struct RowPair {
     }
 };
 
+// ------------------------------------------------------------------------------------------------ steps the kernels share
+// The ring's twiddle table into the LDS (tw: the ring's table).  HALF: the first half of it, negated - the half table holds -tw[m]
+// (the fetch's sign mask is then one AND, see dft_unit8).
+template <bool HALF = false>
+__device__ __forceinline__ void load_twiddles(double2 *twl, const double2 *__restrict__ tw, int L, int tid) {
+    for (int m = tid; m < (HALF ? L / 2 : L); m += blockDim.x) {
+        double2 t = tw[m];
+        if (HALF) { t.x = -t.x; t.y = -t.y; }
+        twl[m] = t;
+    }
+}
+
+// The ring tables every kernel reads (kernel argument, by value): ring length and kmax, first point of the ring, offset of the ring's
+// twiddle table (cos, sin)(2 pi m / L) in tw, offset of its phase references e^{+i k off}, k = 0 .. kmax, in ph
+struct RingTables {
+    const int *Lr, *kmaxr;
+    const int64_t *pstart, *twoff;
+    const double2 *tw;
+    const int64_t *phoff;
+    const double2 *ph;
+};
+
+// Radial evaluation of one coefficient of a ring: the rows r0 .. r3 = (Re, Im) at the four spline nodes of the ring's cell, weighted
+// with f (phi, phi' or phi'' at the ring's radius), then the phase reference w = e^{+i k off} and the factor 2 of a real series;
+// k = 0 has a real part only.  (The order of the operations is part of the result: the library is built without contraction.)
+__device__ __forceinline__ double2 radial_coef(const double2 &r0, const double2 &r1, const double2 &r2, const double2 &r3, double f0, double f1,
+                                               double f2, double f3, int k, const double2 &w) {
+    double cr = f0 * r0.x + f1 * r1.x + f2 * r2.x + f3 * r3.x, ci = 0.0;
+    if (k > 0) {
+        ci = f0 * r0.y + f1 * r1.y + f2 * r2.y + f3 * r3.y;
+        const double tr = cr * w.x - ci * w.y;
+        ci = 2.0 * (cr * w.y + ci * w.x);
+        cr = 2.0 * tr;
+    }
+    return make_double2(cr, ci);
+}
+
+// Coefficient sets q of the RLZ kernels: (sz, d) = (0,0) value, (0,1) d/dr, (0,2) d2/dr2, (1,0) d/dz, (2,0) d2/dz2; the value set also
+// serves d/dlambda and d2/dlambda2 (i k and -k^2, formed while loading the B operand).
+struct DftSlots {                     // kernel argument, by value
+    int u, r, rr, l, ll, z, zz;       // sx_handle::slot[]
+    __device__ __forceinline__ int of_set(int q) const { return (q == 0) ? u : (q == 1) ? r : (q == 2) ? rr : (q == 3) ? z : zz; }
+};
+struct SetNeed {                      // what a variable with slot mask `mask` needs of set q
+    int slot0;                        // the set's own slot
+    bool own, l, ll;
+    __device__ __forceinline__ SetNeed(const DftSlots &s, int q, int mask)
+        : slot0(s.of_set(q)), own((mask >> slot0) & 1), l((q == 0) && ((mask >> s.l) & 1)), ll((q == 0) && ((mask >> s.ll) & 1)) {}
+    __device__ __forceinline__ bool any() const { return own || l || ll; }
+};
+
+// One K step of the quarter-wave inverse on the accumulators of parity par: six matrix-core instructions per fetched twiddle t0 when
+// the set's own plane, d/dlambda and d2/dlambda2 are all asked for.  bc, bs: this lane's cosine / sine coefficient, kd its wavenumber.
+struct QuarterAcc { dft_d4 pu[2], qu[2], pl[2], ql[2], pll[2], qll[2]; };
+__device__ __forceinline__ void quarter_kstep(QuarterAcc &a, int par, const SetNeed &nd, const double2 &t0, double bc, double bs, double &kd) {
+    if (nd.own) {
+        a.pu[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, bc, a.pu[par], 0, 0, 0);
+        a.qu[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, bs, a.qu[par], 0, 0, 0);
+    }
+    if (nd.l) {                                     // i k (cr + i ci): cosine part -k ci, sine part k cr
+        a.pl[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, -kd * bs, a.pl[par], 0, 0, 0);
+        a.ql[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, kd * bc, a.ql[par], 0, 0, 0);
+    }
+    if (nd.ll) {
+        const double k2 = -(kd * kd);
+        a.pll[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, k2 * bc, a.pll[par], 0, 0, 0);
+        a.qll[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, k2 * bs, a.qll[par], 0, 0, 0);
+    }
+    kd += 8.0;
+}
+
+// Stores of the quarter-wave inverse kernels for one variable v and one column (level z0 + i: zi; grids without levels: nz = 1, zi = 0).
+template <class ST> struct Scatter {
+    Planes<ST> phys;
+    int V, v;
+    int64_t N, p0;                    // points of a plane; the ring's first point
+    int nz, zi, L;
+    // slot 0 is the value plane (always double), the others are derivative planes of the storage type
+    __device__ __forceinline__ void put(int slot, int64_t pt, double val) const {
+        if (slot == 0) phys.val[(int64_t)v * N + pt] = val;
+        else phys.der[((int64_t)(slot - 1) * V + v) * N + pt] = (ST)val;
+    }
+    // the four ring points l, L - l, L/2 - l, L/2 + l of row lo = l <= L/4 from the even / odd wavenumbers' cosine and sine sums (see
+    // k_rl_inverse_dft); the rows 0 and L/4 have two points each
+    __device__ __forceinline__ void put4(int slot, int lo, double Pe, double Po, double Qe, double Qo) const {
+        const int Lh = L / 2, Lq = L / 4;
+        const double Ps = Pe + Po, Pd = Pe - Po, Qs = Qe + Qo, Qd = Qe - Qo;
+        put(slot, (p0 + lo) * nz + zi, Ps - Qs);
+        if (lo > 0) put(slot, (p0 + (L - lo)) * nz + zi, Ps + Qs);
+        if (lo < Lq) {
+            put(slot, (p0 + (Lh - lo)) * nz + zi, Pd + Qd);
+            if (lo > 0) put(slot, (p0 + (Lh + lo)) * nz + zi, Pd - Qd);
+        }
+    }
+};
+
+// One coefficient of the forward transform from its sums sr = ac, si = -as: the phase reference w = e^{-i k off} and inv = 1 / L
+// (k = 0 has a real part only), stored as a 16-byte (Re, Im) pair.
+__device__ __forceinline__ void forward_store(double sr, double si, const double2 &w, double inv, int k, double *dst) {
+    double2 out;
+    if (k == 0) out = make_double2(sr * inv, 0.0);
+    else out = make_double2((sr * w.x + si * w.y) * inv, (si * w.x - sr * w.y) * inv);
+    *reinterpret_cast<double2 *>(dst) = out;
+}
+
 template <class ST>
 __global__ void __launch_bounds__(512)
-k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi, const int *__restrict__ Lr,
-                 const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                 const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V,
-                 int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow, int s_u, int s_r, int s_rr, int s_l, int s_ll,
-                 int s_z, int s_zz, const int *__restrict__ slotmask, const int *__restrict__ items, int lcap, int kcap4) {
+k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi, RingTables rt, int V,
+                 int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow, DftSlots slots, const int *__restrict__ slotmask, const int *__restrict__ items, int lcap, int kcap4) {
     extern __shared__ double sm[];
     // (ring, variable) from the work list: most expensive first - workgroups are dispatched in blockIdx order, a ring's work
     // grows with its square and a variable's with its planes, so the cheap items fill the tail of the launch
     const int ring = items[2 * blockIdx.y], v = items[2 * blockIdx.y + 1], z0 = blockIdx.x * DZC;
     const int mask = slotmask[v];
     const int zc = min(DZC, nz - z0);
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2;
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lh = L / 2;
     const int K4 = (km + 1 + 3) & ~3;                           // wavenumber rows 0..km, padded to the MFMA K step
-    double2 *twl = reinterpret_cast<double2 *>(sm);             // [L]   (cos, sin)(2 pi m / L)
-    double *Cc = sm + 2 * (size_t)lcap;                         // [K4][CST] cosine coefficients
-    double *Cs = Cc + (size_t)kcap4 * CST;                      // [K4][CST] sine coefficients (row 0 = 0)
+    const TableTiles lay = lds_coef(lcap, kcap4, CST);
+    double2 *twl = lay.table(sm);                               // [L]   (cos, sin)(2 pi m / L)
+    double *Cc = lay.at(sm, 0), *Cs = lay.at(sm, 1);            // [K4][CST] cosine, sine coefficients (sine row 0 = 0)
     const int j0 = ring / MUBAR;
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
     [[maybe_unused]] const long long dbg_t0 = DFT_NOW();
     [[maybe_unused]] long long dbg_stage = 0, dbg_mm = 0, dbg_st = 0, dbg_tiles = 0, dbg_nmfma = 0;
 #ifdef SX_PHASES
     const long long dbg_r0 = (long long)__builtin_amdgcn_s_memrealtime();
 #endif
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
 
     // coefficient sets q: (sz, d) = (0,0) (0,1) (0,2) (1,0) (2,0); only those with a requested slot
     int qs[5], nq = 0;
     for (int q = 0; q < 5; q++) {
         const int sz = q < 3 ? 0 : q - 2;
         if (sz >= nsz) break;
-        const int sl = (q == 0) ? s_u : (q == 1) ? s_r : (q == 2) ? s_rr : (q == 3) ? s_z : s_zz;
-        if (((mask >> sl) & 1) || (q == 0 && (((mask >> s_l) | (mask >> s_ll)) & 1))) qs[nq++] = q;
+        if (SetNeed(slots, q, mask).any()) qs[nq++] = q;
     }
     // Staging of a set: thread -> (level zz, wavenumber kq + 32 b): the 4 radial rows of a wavenumber come as 16-byte (Re, Im)
     // pairs, KB wavenumbers per thread and batch (the rolled form waited for each wavenumber's 8 scalar loads on its own).
@@ -126,19 +241,10 @@ k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *_
         for (int b = 0; b < KB; b++) {
             const int k = k0 + kq + 32 * b;
             if (k >= K4 || zz >= DZC) continue;
-            double cr = 0.0, ci = 0.0;
-            if (zin && k <= km) {
-                cr = f0 * raw[b][0].x + f1 * raw[b][1].x + f2 * raw[b][2].x + f3 * raw[b][3].x;
-                if (k > 0) {
-                    ci = f0 * raw[b][0].y + f1 * raw[b][1].y + f2 * raw[b][2].y + f3 * raw[b][3].y;
-                    const double2 w = phr[k];               // e^{+i k off}
-                    const double tr = cr * w.x - ci * w.y;
-                    ci = 2.0 * (cr * w.y + ci * w.x);
-                    cr = 2.0 * tr;
-                }
-            }
-            Cc[k * CST + zz] = cr;
-            Cs[k * CST + zz] = ci;
+            double2 c = make_double2(0.0, 0.0);
+            if (zin && k <= km) c = radial_coef(raw[b][0], raw[b][1], raw[b][2], raw[b][3], f0, f1, f2, f3, k, phr[k]);
+            Cc[k * CST + zz] = c.x;
+            Cs[k * CST + zz] = c.y;
         }
     };
     double2 raw0[KB][4];
@@ -146,9 +252,9 @@ k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *_
 
     for (int qi = 0; qi < nq; qi++) {
         const int q = qs[qi];
-        const int slot0 = (q == 0) ? s_u : (q == 1) ? s_r : (q == 2) ? s_rr : (q == 3) ? s_z : s_zz;
-        const bool need0 = (mask >> slot0) & 1;
-        const bool needl = (q == 0) && ((mask >> s_l) & 1), needll = (q == 0) && ((mask >> s_ll) & 1);
+        const SetNeed nd(slots, q, mask);
+        const int slot0 = nd.slot0;
+        const bool need0 = nd.own, needl = nd.l, needll = nd.ll;
         [[maybe_unused]] const long long dbg_t1 = DFT_NOW();
         __syncthreads();                                        // the previous set has been consumed (and twl is complete)
         consume(q, 0, raw0);
@@ -177,8 +283,7 @@ k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *_
             [[maybe_unused]] const long long dbg_t2 = DFT_NOW();
             dbg_tiles++;
             dbg_nmfma += (long long)(((km / 2 + 1 + 3) >> 2) + (km >= 1 ? (((km - 1) / 2 + 1 + 3) >> 2) : 0)) * 2 * ((need0 ? 1 : 0) + (needl ? 1 : 0) + (needll ? 1 : 0));
-            dft_d4 z4 = {0.0, 0.0, 0.0, 0.0};
-            dft_d4 pu[2] = {z4, z4}, qu[2] = {z4, z4}, pl[2] = {z4, z4}, ql[2] = {z4, z4}, pll[2] = {z4, z4}, qll[2] = {z4, z4};
+            QuarterAcc acc = {};
 #pragma unroll
             for (int par = 0; par < 2; par++) {
                 if (km < par) continue;
@@ -192,30 +297,18 @@ k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *_
                     const bool kin = k < K4;
                     const double2 t0 = twl[m];
                     const double bc = kin ? Cc[k * CST + i] : 0.0, bs = kin ? Cs[k * CST + i] : 0.0;
-                    if (need0) {
-                        pu[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, bc, pu[par], 0, 0, 0);
-                        qu[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, bs, qu[par], 0, 0, 0);
-                    }
-                    if (needl) {                                    // i k (cr + i ci): cosine part -k ci, sine part k cr
-                        pl[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, -kd * bs, pl[par], 0, 0, 0);
-                        ql[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, kd * bc, ql[par], 0, 0, 0);
-                    }
-                    if (needll) {
-                        const double k2 = -(kd * kd);
-                        pll[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, k2 * bc, pll[par], 0, 0, 0);
-                        qll[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, k2 * bs, qll[par], 0, 0, 0);
-                    }
-                    kd += 8.0;
+                    quarter_kstep(acc, par, nd, t0, bc, bs, kd);
                     m = wrap_add(m, sm8, L);
                 }
             }
             // D tile: lane holds column n = lane & 15 (level), rows (lane >> 4) + 4 r (points l of the quarter ring)
 #ifdef SX_PHASES
-            asm volatile("s_nop 0" : "+v"(pu[0]), "+v"(qu[0]), "+v"(pu[1]), "+v"(qu[1]));      // the accumulators are final here
+            asm volatile("s_nop 0" : "+v"(acc.pu[0]), "+v"(acc.qu[0]), "+v"(acc.pu[1]), "+v"(acc.qu[1]));      // the accumulators are final here
 #endif
             [[maybe_unused]] const long long dbg_t3 = DFT_NOW();
             dbg_mm += dbg_t3 - dbg_t2;
             if (i < zc) {
+                // this kernel's own copy of Scatter::put / put4: with Scatter the double instance takes 220 VGPRs instead of 218
                 auto put = [&](int slot, int64_t pt, double val) {
                     if (slot == 0) phys.val[(int64_t)v * N + pt] = val;
                     else phys.der[((int64_t)(slot - 1) * V + v) * N + pt] = (ST)val;
@@ -233,9 +326,9 @@ k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *_
                 for (int r = 0; r < 4; r++) {
                     const int lo = mt * 16 + kk + 4 * r;
                     if (lo > Lq) continue;
-                    if (need0) put4(slot0, lo, pu[0][r], pu[1][r], qu[0][r], qu[1][r]);
-                    if (needl) put4(s_l, lo, pl[0][r], pl[1][r], ql[0][r], ql[1][r]);
-                    if (needll) put4(s_ll, lo, pll[0][r], pll[1][r], qll[0][r], qll[1][r]);
+                    if (need0) put4(slot0, lo, acc.pu[0][r], acc.pu[1][r], acc.qu[0][r], acc.qu[1][r]);
+                    if (needl) put4(slots.l, lo, acc.pl[0][r], acc.pl[1][r], acc.ql[0][r], acc.ql[1][r]);
+                    if (needll) put4(slots.ll, lo, acc.pll[0][r], acc.pll[1][r], acc.qll[0][r], acc.qll[1][r]);
                 }
             }
             dbg_st += DFT_NOW() - dbg_t3;
@@ -265,16 +358,28 @@ k_rl_inverse_dft(const double *__restrict__ Az, Planes<ST> phys, const double *_
 // SX_DFT_MERGE=0 (read at sx_create) keeps the kernel above.
 struct DftUnitOut { int slot[4]; };      // output slots of the unit's planes: A plain, A ik, A -k^2, B (-1: not in this unit)
 
+// The planes of a unit: MA = which of plain / i k / -k^2 of set A (bits 1, 2, 4), HASB = set B's plane.  NP of them, and the accumulator
+// index of each (compile-time: a running counter inside the loop put the arrays into scratch memory).
+template <int MA, bool HASB> struct UnitPlanes {
+    static constexpr int NP = ((MA & 1) ? 1 : 0) + ((MA & 2) ? 1 : 0) + ((MA & 4) ? 1 : 0) + (HASB ? 1 : 0);
+    static constexpr int I1 = 0, I2 = (MA & 1) ? 1 : 0, I4 = I2 + ((MA & 2) ? 1 : 0), IB = I4 + ((MA & 4) ? 1 : 0);
+    static __device__ __forceinline__ void slots_of(const DftUnitOut &o, int (&slots)[NP]) {      // accumulator -> output slot
+        if (MA & 1) slots[I1] = o.slot[0];
+        if (MA & 2) slots[I2] = o.slot[1];
+        if (MA & 4) slots[I4] = o.slot[2];
+        if (HASB) slots[IB] = o.slot[3];
+    }
+};
+
 template <int MA, bool HASB, class ST>
 __device__ __forceinline__ void dft_unit(const double2 *__restrict__ twl, const double *__restrict__ CcA, const double *__restrict__ CsA,
                                          const double *__restrict__ CcB, const double *__restrict__ CsB, Planes<ST> phys, int V, int v, int64_t N,
                                          int64_t p0, int nz, int z0, int zc, int L, int km, int K4, int mt, int lane, const DftUnitOut &o) {
     const int i = lane & 15, kk = lane >> 4;
-    const int Lh = L / 2, Lq = L / 4;
+    const int Lq = L / 4;
     const int lrow = min(mt * 16 + i, Lq);
-    constexpr int NP = ((MA & 1) ? 1 : 0) + ((MA & 2) ? 1 : 0) + ((MA & 4) ? 1 : 0) + (HASB ? 1 : 0);
-    // accumulator index of each plane (compile-time: a running counter inside the loop put the arrays into scratch memory)
-    constexpr int I1 = 0, I2 = (MA & 1) ? 1 : 0, I4 = I2 + ((MA & 2) ? 1 : 0), IB = I4 + ((MA & 4) ? 1 : 0);
+    using UP = UnitPlanes<MA, HASB>;
+    constexpr int NP = UP::NP, I1 = UP::I1, I2 = UP::I2, I4 = UP::I4, IB = UP::IB;
     dft_d4 P[NP][2], Q[NP][2];
 #pragma unroll
     for (int p = 0; p < NP; p++)
@@ -316,29 +421,15 @@ __device__ __forceinline__ void dft_unit(const double2 *__restrict__ twl, const 
         }
     }
     if (i >= zc) return;
-    auto put = [&](int slot, int64_t pt, double val) {
-        if (slot == 0) phys.val[(int64_t)v * N + pt] = val;
-        else phys.der[((int64_t)(slot - 1) * V + v) * N + pt] = (ST)val;
-    };
+    const Scatter<ST> out{phys, V, v, N, p0, nz, z0 + i, L};
     int slots[NP];
-    if (MA & 1) slots[I1] = o.slot[0];
-    if (MA & 2) slots[I2] = o.slot[1];
-    if (MA & 4) slots[I4] = o.slot[2];
-    if (HASB) slots[IB] = o.slot[3];
+    UP::slots_of(o, slots);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int lo = mt * 16 + kk + 4 * r;
         if (lo > Lq) continue;
 #pragma unroll
-        for (int p = 0; p < NP; p++) {
-            const double Ps = P[p][0][r] + P[p][1][r], Pd = P[p][0][r] - P[p][1][r], Qs = Q[p][0][r] + Q[p][1][r], Qd = Q[p][0][r] - Q[p][1][r];
-            put(slots[p], (p0 + lo) * nz + z0 + i, Ps - Qs);
-            if (lo > 0) put(slots[p], (p0 + (L - lo)) * nz + z0 + i, Ps + Qs);
-            if (lo < Lq) {
-                put(slots[p], (p0 + (Lh - lo)) * nz + z0 + i, Pd + Qd);
-                if (lo > 0) put(slots[p], (p0 + (Lh + lo)) * nz + z0 + i, Pd - Qd);
-            }
-        }
+        for (int p = 0; p < NP; p++) out.put4(slots[p], lo, P[p][0][r], P[p][1][r], Q[p][0][r], Q[p][1][r]);
     }
 }
 
@@ -361,8 +452,8 @@ __device__ __forceinline__ void dft_unit8(const double2 *__restrict__ twl, const
     const int Lh = L / 2, M = L / 4, Mh = M / 2;
     [[maybe_unused]] const long long dbg_l0 = DFT_NOW();
     const int lrow = min(mt * 16 + i, Mh);
-    constexpr int NP = ((MA & 1) ? 1 : 0) + ((MA & 2) ? 1 : 0) + ((MA & 4) ? 1 : 0) + (HASB ? 1 : 0);
-    constexpr int I1 = 0, I2 = (MA & 1) ? 1 : 0, I4 = I2 + ((MA & 2) ? 1 : 0), IB = I4 + ((MA & 4) ? 1 : 0);
+    using UP = UnitPlanes<MA, HASB>;
+    constexpr int NP = UP::NP, I1 = UP::I1, I2 = UP::I2, I4 = UP::I4, IB = UP::IB;
     dft_d4 Ec[NP][2], Es[NP][2], Oc[NP][2], Os[NP][2];       // E*[plane][class 0 / 2], O*[plane][rows l / rows M - l]
 #pragma unroll
     for (int p = 0; p < NP; p++)
@@ -377,15 +468,11 @@ __device__ __forceinline__ void dft_unit8(const double2 *__restrict__ twl, const
     // them in memory (profiles/r04/eighth_wave_alignment.txt); this form is 0.905-0.912 ms at eight different offsets.  An odd step
     // count runs one step on zero rows (the staged rows end at a multiple of 32); the last request goes one step beyond them (inside
     // the LDS allocation: the launcher adds 32 rows; the values are not used).
-    // Twiddle fetch: index (k l) mod L advanced by add, subtract, unsigned minimum.  HT: the table holds -tw[m] for m < L / 2; with
+    // Twiddle fetch: index (k l) mod L advanced by add, subtract, unsigned minimum (wrap_add).  HT: the table holds -tw[m] for m < L / 2; with
     // u = m - L/2 the entry is min(m, u) (unsigned) and the value's sign the sign bit of u - an XOR mask applied to the pair once it
     // has arrived (in the matrix-core block, not at the request).  Every vector instruction here is time the matrix pipe stands still
     // (an MFMA holds its SIMD's vector issue port), see DESIGN.md 7.
     auto flip = [](double x, int mask) __attribute__((always_inline)) { return __hiloint2double(__double2hiint(x) ^ mask, __double2loint(x)); };
-    auto advance = [&](int &m, int step) __attribute__((always_inline)) {
-        const unsigned t = (unsigned)(m + step);
-        m = (int)min(t, t - (unsigned)L);
-    };
     auto tw_req = [&](int m, int &mask) __attribute__((always_inline)) {
         if constexpr (!HT) { mask = 0; return twl[m]; }
         else {
@@ -409,7 +496,7 @@ __device__ __forceinline__ void dft_unit8(const double2 *__restrict__ twl, const
             x.t = tw_req(m, x.sm);
             if (MA != 0) { x.ac = CcA[ko]; x.as = CsA[ko]; }
             if (HASB) { x.bc = CcB[ko]; x.bs = CsB[ko]; }
-            advance(m, s8);
+            m = wrap_add(m, s8, L);
             ko += 8 * CST;
         };
         auto hold = [&](OddOps &x) __attribute__((always_inline)) {      // the values exist from here on (an opaque use: the loads cannot move past it)
@@ -462,8 +549,8 @@ __device__ __forceinline__ void dft_unit8(const double2 *__restrict__ twl, const
             x.t0 = tw_req(m0, x.sm0); x.t2 = tw_req(m2, x.sm2);
             if (MA != 0) { x.ac0 = CcA[ko]; x.as0 = CsA[ko]; x.ac2 = CcA[ko + 2 * CST]; x.as2 = CsA[ko + 2 * CST]; }
             if (HASB) { x.bc0 = CcB[ko]; x.bs0 = CsB[ko]; x.bc2 = CcB[ko + 2 * CST]; x.bs2 = CsB[ko + 2 * CST]; }
-            advance(m0, s16);
-            advance(m2, s16);
+            m0 = wrap_add(m0, s16, L);
+            m2 = wrap_add(m2, s16, L);
             ko += 16 * CST;
         };
         auto hold = [&](EvenOps &x) __attribute__((always_inline)) {
@@ -514,10 +601,7 @@ __device__ __forceinline__ void dft_unit8(const double2 *__restrict__ twl, const
     dbg_loops += DFT_NOW() - dbg_l0;
     if (i >= zc) return;
     int slots[NP];
-    if (MA & 1) slots[I1] = o.slot[0];
-    if (MA & 2) slots[I2] = o.slot[1];
-    if (MA & 4) slots[I4] = o.slot[2];
-    if (HASB) slots[IB] = o.slot[3];
+    UP::slots_of(o, slots);
     // Stores through a per-plane base pointer (this lane's level of the ring's point 0) and 32-bit point offsets: the 64-bit
     // multiply-add per stored value of the first version was vector-ALU time the matrix pipe stood still for.  (The caller runs the
     // plane chunks of a tile in a loop: an opaque copy of the tile index keeps the compiler from hoisting the offsets out of that
@@ -559,48 +643,50 @@ __device__ __forceinline__ void dft_unit8(const double2 *__restrict__ twl, const
 // pass, the table behind the set - TWO workgroups per CU, each on its own (ring, variable, level chunk): while one stages a set, drains its
 // stores or waits at a barrier, the other has the matrix pipes to itself.  (One 512-thread workgroup owns a CU's whole LDS; nothing ran
 // under the 45 % of its time that are not matrix-core loops.)
+// Dynamic LDS of the kernel, in doubles: [lcap] twiddles, then the sets - a cosine and a sine tile [kz][CST] each - and, for eighth-wave
+// units, 32 rows more: the pipelined loops request one K step beyond the staged rows.  HT: the ONE set first, then [lcap / 2] twiddles
+// (that last request then lands in the table instead of needing rows of its own).
+template <bool HT> struct MergedLds {
+    size_t lcap, kz;
+    __host__ __device__ size_t tile() const { return kz * CST; }
+    __host__ __device__ double2 *table(double *sm) const { return reinterpret_cast<double2 *>(HT ? sm + 2 * tile() : sm); }
+    __host__ __device__ void sets(double *sm, double *(&C)[2][2]) const {      // [set A / B][cosine / sine] coefficient tiles
+        C[0][0] = HT ? sm : sm + 2 * lcap;
+        C[0][1] = C[0][0] + tile(); C[1][0] = C[0][1] + tile(); C[1][1] = C[1][0] + tile();
+    }
+    size_t bytes(int nsets, bool e8) const { return sizeof(double) * (HT ? 2 * tile() + lcap : 2 * lcap + 2 * nsets * tile() + (e8 ? 32 * CST : 0)); }
+};
+
 template <class ST, int NPM, bool HT = false>      // NPM = 0: quarter-wave units, any plane set; 2: eighth-wave units of at most NPM planes
 __global__ void __launch_bounds__(512)
-k_rl_inverse_dft_merged(const double *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi, const int *__restrict__ Lr,
-                        const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                        const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V,
-                        int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow, int s_u, int s_r, int s_rr, int s_l, int s_ll,
-                        int s_z, int s_zz, const int *__restrict__ slotmask, const int *__restrict__ items, int lcap, int kcap4, int two_sets) {
+k_rl_inverse_dft_merged(const double *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi, RingTables rt, int V,
+                        int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow, DftSlots slots, const int *__restrict__ slotmask, const int *__restrict__ items, int lcap, int kcap4, int two_sets) {
     constexpr bool E8 = NPM > 0;
     extern __shared__ double sm[];
     const int ring = items[2 * blockIdx.y], v = items[2 * blockIdx.y + 1], z0 = blockIdx.x * DZC;
     const int mask = slotmask[v];
     const int zc = min(DZC, nz - z0);
-    const int L = Lr[ring], km = kmaxr[ring];
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring];
     // a K step of parity p touches wavenumbers 8 js + 2 kk + p, js < ceil(nk_p / 4): rows 0 .. Kz - 1 are staged (zeros beyond km), so the
     // loops carry neither a clamp nor a select
     // (eighth-wave units: classes k = 0 / 2 mod 4 advance by 16 per K step, two steps per loop iteration: rows up to the next multiple of 32)
     const int K4 = E8 ? 32 * ((km + 1 + 31) / 32) : 8 * ((km / 2 + 1 + 3) / 4);
-    // [L] twiddles, then the sets; HT: the ONE set first, then [L / 2] twiddles (the pipelined loops' last request, one step beyond
-    // the set's rows, then lands in the table instead of needing rows of its own)
-    double2 *twl = reinterpret_cast<double2 *>(HT ? sm + (size_t)2 * kcap4 * CST : sm);
+    const MergedLds<HT> lay{(size_t)lcap, (size_t)kcap4};
+    double2 *twl = lay.table(sm);
     double *Cset[2][2];                                         // [set A / B][cosine / sine] coefficient tiles [K4][CST]
-    Cset[0][0] = HT ? sm : sm + 2 * (size_t)lcap;
-    Cset[0][1] = Cset[0][0] + (size_t)kcap4 * CST;
-    Cset[1][0] = Cset[0][1] + (size_t)kcap4 * CST;
-    Cset[1][1] = Cset[1][0] + (size_t)kcap4 * CST;
+    lay.sets(sm, Cset);
     const int j0 = ring / MUBAR;
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
-    for (int m = tid; m < (HT ? L / 2 : L); m += blockDim.x) {
-        double2 t = tw[twoff[ring] + m];
-        if (HT) { t.x = -t.x; t.y = -t.y; }                     // the half table holds -tw[m] (the fetch's sign mask is then one AND, see dft_unit8)
-        twl[m] = t;
-    }
+    load_twiddles<HT>(twl, rt.tw + rt.twoff[ring], L, tid);
 
     // stored sets q: (sz, d) = (0,0) value [planes u, d/dlambda, d2/dlambda2], (0,1) d/dr, (0,2) d2/dr2, (1,0) d/dz, (2,0) d2/dz2.
     // Everything about the passes lives in scalars (bit fields), not in indexed private arrays (those would sit in scratch memory).
     auto has = [&](int sl) { return sl >= 0 && ((mask >> sl) & 1); };
-    const int ma_u = (has(s_u) ? 1 : 0) | (has(s_l) ? 2 : 0) | (has(s_ll) ? 4 : 0);
+    const int ma_u = (has(slots.u) ? 1 : 0) | (has(slots.l) ? 2 : 0) | (has(slots.ll) ? 4 : 0);
     // bit q of `need`: set q is needed; singles = sets 1 .. 4
-    int need = (ma_u ? 1 : 0) | (has(s_r) ? 2 : 0) | (has(s_rr) ? 4 : 0) | ((nsz > 1 && has(s_z)) ? 8 : 0) | ((nsz > 2 && has(s_zz)) ? 16 : 0);
-    auto slot_of = [&](int q) { return q == 1 ? s_r : q == 2 ? s_rr : q == 3 ? s_z : s_zz; };
+    int need = (ma_u ? 1 : 0) | (has(slots.r) ? 2 : 0) | (has(slots.rr) ? 4 : 0) | ((nsz > 1 && has(slots.z)) ? 8 : 0) | ((nsz > 2 && has(slots.zz)) ? 16 : 0);
     // Staging of a set (as in k_rl_inverse_dft): thread -> (level zz, wavenumber kq + 32 b), the 4 radial rows as 16-byte (Re, Im)
     // pairs, KB wavenumbers per thread and batch: 256 wavenumbers of a set - every ring of a <= 85-cell patch whole - are requested in ONE
     // burst (128 registers that are free while no accumulator lives).  (No request-ahead across passes here: its registers are the fourth plane's.)
@@ -625,19 +711,10 @@ k_rl_inverse_dft_merged(const double *__restrict__ Az, Planes<ST> phys, const do
             for (int b = 0; b < KB; b++) {
                 const int k = k0 + kq + NQ * b;
                 if (k >= K4 || zz >= DZC) continue;
-                double cr = 0.0, ci = 0.0;
-                if (zin && k <= km) {
-                    cr = f0 * raw[b][0].x + f1 * raw[b][1].x + f2 * raw[b][2].x + f3 * raw[b][3].x;
-                    if (k > 0) {
-                        ci = f0 * raw[b][0].y + f1 * raw[b][1].y + f2 * raw[b][2].y + f3 * raw[b][3].y;
-                        const double2 w = phr[k];               // e^{+i k off}
-                        const double tr = cr * w.x - ci * w.y;
-                        ci = 2.0 * (cr * w.y + ci * w.x);
-                        cr = 2.0 * tr;
-                    }
-                }
-                Cc[k * CST + zz] = cr;
-                Cs[k * CST + zz] = ci;
+                double2 c = make_double2(0.0, 0.0);
+                if (zin && k <= km) c = radial_coef(raw[b][0], raw[b][1], raw[b][2], raw[b][3], f0, f1, f2, f3, k, phr[k]);
+                Cc[k * CST + zz] = c.x;
+                Cs[k * CST + zz] = c.y;
             }
         }
     };
@@ -670,7 +747,7 @@ k_rl_inverse_dft_merged(const double *__restrict__ Az, Planes<ST> phys, const do
         const int maf = qa == 0 ? ma_u : 1;
         const bool hb = qb >= 0;
         DftUnitOut of;
-        of.slot[0] = qa == 0 ? s_u : slot_of(qa); of.slot[1] = s_l; of.slot[2] = s_ll; of.slot[3] = hb ? slot_of(qb) : -1;
+        of.slot[0] = slots.of_set(qa); of.slot[1] = slots.l; of.slot[2] = slots.ll; of.slot[3] = hb ? slots.of_set(qb) : -1;
         // one unit = (row tile, plane subset): dispatch to the instance whose plane set is compiled in
         auto run = [&](int mt, int ma, bool b) {
 #define DFT_U(MA_, B_)                                                                                                                 \
@@ -756,62 +833,49 @@ constexpr int KCH = 256;      // wavenumbers per staged chunk (a multiple of 8: 
 
 template <class ST>
 __global__ void __launch_bounds__(512)
-k_rl_inverse_dft_big(const double *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi, const int *__restrict__ Lr,
-                     const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                     const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V,
-                     int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow, int s_u, int s_r, int s_rr, int s_l, int s_ll,
-                     int s_z, int s_zz, const int *__restrict__ slotmask, const int *__restrict__ items, int lcap) {
+k_rl_inverse_dft_big(const double *__restrict__ Az, Planes<ST> phys, const double *__restrict__ phi, RingTables rt, int V,
+                     int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow, DftSlots slots, const int *__restrict__ slotmask, const int *__restrict__ items, int lcap) {
     extern __shared__ double sm[];
     const int ring = items[2 * blockIdx.y], v = items[2 * blockIdx.y + 1], z0 = blockIdx.x * DZC;
     const int mask = slotmask[v];
     const int zc = min(DZC, nz - z0);
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2, Lq = L / 4;
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lq = L / 4;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
     const int mt = blockIdx.z * nw + wave;                       // this wave's row tile of the quarter ring
     if ((int)blockIdx.z * nw * 16 > Lq) return;                  // no row tile group here (uniform for the workgroup)
     const bool rows = mt * 16 <= Lq;
-    double2 *twl = reinterpret_cast<double2 *>(sm);             // [L]
-    double *Cc = sm + 2 * (size_t)lcap;                         // [KCH][CST]
-    double *Cs = Cc + (size_t)KCH * CST;
+    const TableTiles lay = lds_coef(lcap, KCH, CST);
+    double2 *twl = lay.table(sm);                               // [L]
+    double *Cc = lay.at(sm, 0), *Cs = lay.at(sm, 1);            // [KCH][CST]
     const int j0 = ring / MUBAR;
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
     const int i = lane & 15, kk = lane >> 4;
     const int lrow = min(mt * 16 + i, Lq);
     const int sm8 = (int)(((int64_t)8 * lrow) % L);
     for (int q = 0; q < 5; q++) {
         const int sz = q < 3 ? 0 : q - 2, d = q < 3 ? q : 0;
         if (sz >= nsz) break;
-        const int slot0 = (q == 0) ? s_u : (q == 1) ? s_r : (q == 2) ? s_rr : (q == 3) ? s_z : s_zz;
-        const bool need0 = (mask >> slot0) & 1;
-        const bool needl = (q == 0) && ((mask >> s_l) & 1), needll = (q == 0) && ((mask >> s_ll) & 1);
-        if (!need0 && !needl && !needll) continue;
+        const SetNeed nd(slots, q, mask);
+        if (!nd.any()) continue;
         const double *pf = phi + ((int64_t)d * nrings + ring) * 4;
         const double f0 = pf[0], f1 = pf[1], f2 = pf[2], f3 = pf[3];
-        dft_d4 z4 = {0.0, 0.0, 0.0, 0.0};
-        dft_d4 pu[2] = {z4, z4}, qu[2] = {z4, z4}, pl[2] = {z4, z4}, ql[2] = {z4, z4}, pll[2] = {z4, z4}, qll[2] = {z4, z4};
+        QuarterAcc acc = {};
         for (int kc0 = 0; kc0 <= km; kc0 += KCH) {
             __syncthreads();                                    // the previous chunk has been consumed (and twl is complete)
             // stage wavenumbers kc0 .. kc0 + KCH - 1: thread -> (level, wavenumber), 4 radial rows as 16-byte (Re, Im) pairs
             for (int e = tid; e < KCH * DZC; e += blockDim.x) {
                 const int zz = (e >> 5) & (DZC - 1), kl = (e & 31) + 32 * (e >> 9), k = kc0 + kl;     // 32 consecutive wavenumbers of a level per half wave
-                double cr = 0.0, ci = 0.0;
+                double2 c = make_double2(0.0, 0.0);
                 if (zz < zc && k <= km) {
                     const double *a = Az + (int64_t)j0 * azrow + (((int64_t)v * nsz + sz) * nz + (z0 + zz)) * K2 + 2 * k;
                     const double2 r0 = *reinterpret_cast<const double2 *>(a), r1 = *reinterpret_cast<const double2 *>(a + azrow),
                                   r2 = *reinterpret_cast<const double2 *>(a + 2 * azrow), r3 = *reinterpret_cast<const double2 *>(a + 3 * azrow);
-                    cr = f0 * r0.x + f1 * r1.x + f2 * r2.x + f3 * r3.x;
-                    if (k > 0) {
-                        ci = f0 * r0.y + f1 * r1.y + f2 * r2.y + f3 * r3.y;
-                        const double2 w = phr[k];               // e^{+i k off}
-                        const double tr = cr * w.x - ci * w.y;
-                        ci = 2.0 * (cr * w.y + ci * w.x);
-                        cr = 2.0 * tr;
-                    }
+                    c = radial_coef(r0, r1, r2, r3, f0, f1, f2, f3, k, phr[k]);
                 }
-                Cc[kl * CST + zz] = cr;
-                Cs[kl * CST + zz] = ci;
+                Cc[kl * CST + zz] = c.x;
+                Cs[kl * CST + zz] = c.y;
             }
             __syncthreads();
             if (!rows) continue;
@@ -826,45 +890,20 @@ k_rl_inverse_dft_big(const double *__restrict__ Az, Planes<ST> phys, const doubl
                     const bool kin = k <= kend;
                     const double2 t0 = twl[m];
                     const double bc = kin ? Cc[(k - kc0) * CST + i] : 0.0, bs = kin ? Cs[(k - kc0) * CST + i] : 0.0;
-                    if (need0) {
-                        pu[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, bc, pu[par], 0, 0, 0);
-                        qu[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, bs, qu[par], 0, 0, 0);
-                    }
-                    if (needl) {
-                        pl[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, -kd * bs, pl[par], 0, 0, 0);
-                        ql[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, kd * bc, ql[par], 0, 0, 0);
-                    }
-                    if (needll) {
-                        const double k2 = -(kd * kd);
-                        pll[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.x, k2 * bc, pll[par], 0, 0, 0);
-                        qll[par] = __builtin_amdgcn_mfma_f64_16x16x4f64(t0.y, k2 * bs, qll[par], 0, 0, 0);
-                    }
-                    kd += 8.0;
+                    quarter_kstep(acc, par, nd, t0, bc, bs, kd);
                     m = wrap_add(m, sm8, L);
                 }
             }
         }
         if (!rows || i >= zc) continue;
-        auto put = [&](int slot, int64_t pt, double val) {
-            if (slot == 0) phys.val[(int64_t)v * N + pt] = val;
-            else phys.der[((int64_t)(slot - 1) * V + v) * N + pt] = (ST)val;
-        };
-        auto put4 = [&](int slot, int lo, double Pe, double Po, double Qe, double Qo) {
-            const double Ps = Pe + Po, Pd = Pe - Po, Qs = Qe + Qo, Qd = Qe - Qo;
-            put(slot, (p0 + lo) * nz + z0 + i, Ps - Qs);
-            if (lo > 0) put(slot, (p0 + (L - lo)) * nz + z0 + i, Ps + Qs);
-            if (lo < Lq) {
-                put(slot, (p0 + (Lh - lo)) * nz + z0 + i, Pd + Qd);
-                if (lo > 0) put(slot, (p0 + (Lh + lo)) * nz + z0 + i, Pd - Qd);
-            }
-        };
+        const Scatter<ST> out{phys, V, v, N, p0, nz, z0 + i, L};
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int lo = mt * 16 + kk + 4 * r;
             if (lo > Lq) continue;
-            if (need0) put4(slot0, lo, pu[0][r], pu[1][r], qu[0][r], qu[1][r]);
-            if (needl) put4(s_l, lo, pl[0][r], pl[1][r], ql[0][r], ql[1][r]);
-            if (needll) put4(s_ll, lo, pll[0][r], pll[1][r], qll[0][r], qll[1][r]);
+            if (nd.own) out.put4(nd.slot0, lo, acc.pu[0][r], acc.pu[1][r], acc.qu[0][r], acc.qu[1][r]);
+            if (nd.l) out.put4(slots.l, lo, acc.pl[0][r], acc.pl[1][r], acc.ql[0][r], acc.ql[1][r]);
+            if (nd.ll) out.put4(slots.ll, lo, acc.pll[0][r], acc.pll[1][r], acc.qll[0][r], acc.qll[1][r]);
         }
     }
 }
@@ -883,9 +922,7 @@ constexpr int CSTP = 17;      // row stride of the 16-column coefficient tile
 
 template <class ST>
 __global__ void __launch_bounds__(512)
-k_rl_inverse_dft_planes(const double *__restrict__ A, Planes<ST> phys, const double *__restrict__ phi, const int *__restrict__ Lr,
-                        const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                        const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V,
+k_rl_inverse_dft_planes(const double *__restrict__ A, Planes<ST> phys, const double *__restrict__ phi, RingTables rt, int V,
                         int K2, int nrings, int64_t N, int64_t arow, PlaneGroups pgs, int ring0, int lcap, int kch4) {
     extern __shared__ double sm[];
     const PlaneCols &pc = pgs.g[blockIdx.z];
@@ -893,17 +930,18 @@ k_rl_inverse_dft_planes(const double *__restrict__ A, Planes<ST> phys, const dou
     // row tiles are split over gridDim.y workgroups, each staging the (small) coefficient tiles for itself
     const int ring = ring0 + blockIdx.x;
     const int part = blockIdx.y, nparts = gridDim.y;
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2;
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lh = L / 2;
     if (part * (int)(blockDim.x >> 6) * 16 > Lh) return;        // nothing for this part (uniform for the workgroup)
     const int K4 = (km + 1 + 3) & ~3;
-    double2 *twl = reinterpret_cast<double2 *>(sm);
-    double *Cc = sm + 2 * (size_t)lcap;                         // [kch4][CSTP]: wavenumbers pass through in chunks of kch4
-    double *Cs = Cc + (size_t)kch4 * CSTP;                      //   (one chunk for kmax <= 319; longer rings keep their accumulators across chunks)
+    const TableTiles lay = lds_coef(lcap, kch4, CSTP);
+    double2 *twl = lay.table(sm);
+    double *Cc = lay.at(sm, 0), *Cs = lay.at(sm, 1);            // [kch4][CSTP]: wavenumbers pass through in chunks of kch4
+                                                                //   (one chunk for kmax <= 319; longer rings keep their accumulators across chunks)
     const int j0 = ring / MUBAR;
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
     const double *pf = phi + (int64_t)ring * 4;
     const int i = lane & 15, kk = lane >> 4;
     // ONE pair of row tiles per wave (the launcher gives the ring ceil(tiles / 16) workgroups of 8 waves)
@@ -917,6 +955,8 @@ k_rl_inverse_dft_planes(const double *__restrict__ A, Planes<ST> phys, const dou
         __syncthreads();                                        // the previous chunk has been consumed (and twl is complete)
         for (int e = tid; e < nkc * CSTP; e += blockDim.x) { Cc[e] = 0.0; Cs[e] = 0.0; }
         __syncthreads();
+        // the radial evaluation and the stores below are this kernel's own copies of radial_coef and Scatter::put: with them (16-byte row
+        // loads) the kernel takes 86 VGPRs instead of 88, and a helper that moves a kernel's registers stays out of it
         for (int e = tid; e < V * kn; e += blockDim.x) {
             const int kl = e % kn, k = kc0 + kl, v = e / kn;
             const double *a = A + (int64_t)j0 * arow + (int64_t)v * K2 + 2 * k;
@@ -987,29 +1027,29 @@ k_rl_inverse_dft_planes(const double *__restrict__ A, Planes<ST> phys, const dou
 // across chunks.  Re and Im of a wavenumber end in the same lane, so the result is stored as 16-byte pairs.
 constexpr int LCH = 128;      // half-ring points per staged chunk
 constexpr int NTW = 3;        // wavenumber tiles per wave: 8 waves x 3 x 16 = 384 wavenumbers > kmax <= 319
+// sums Xs and differences Xd [LCH][CST] of the half-ring forward kernel
+__host__ __device__ inline TableTiles lds_half(int lcap) { return {(size_t)lcap, (size_t)LCH * CST, 2}; }
 
 __global__ void __launch_bounds__(512)
-k_fl_forward_dft(const double *__restrict__ np1, double *__restrict__ Fl, const int *__restrict__ Lr,
-                 const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                 const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V, int nz,
+k_fl_forward_dft(const double *__restrict__ np1, double *__restrict__ Fl, RingTables rt, int V, int nz,
                  int K2, int64_t N, int ring0, int lcap, int planes, int ntw) {
     // planes = 0: the 16 MFMA rows are vertical levels of variable blockIdx.y (RLZ / RZ: z innermost in var_np1).
     // planes = 1: grids without a vertical dimension - the rows are the V variables of the ring (var_np1 is [v][point]).
     extern __shared__ double sm[];
     const int ring = ring0 + blockIdx.z, v = planes ? 0 : blockIdx.y, z0 = planes ? 0 : blockIdx.x * DZC;
     const int zc = planes ? V : min(DZC, nz - z0);
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2;
-    double2 *twl = reinterpret_cast<double2 *>(sm);             // [L]
-    double *Xs = sm + 2 * (size_t)lcap;                         // [LCH][CST]
-    double *Xd = Xs + (size_t)LCH * CST;
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lh = L / 2;
+    const TableTiles lay = lds_half(lcap);
+    double2 *twl = lay.table(sm);                               // [L]
+    double *Xs = lay.at(sm, 0), *Xd = lay.at(sm, 1);            // [LCH][CST]
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
     // planes mode: the ring's wavenumber tiles are split over gridDim.y workgroups (a workgroup per ring would leave most
     // of the chip idle on RL grids); tile of (wave, q) = (part * ntw + q) * nw + wave, part = 0 otherwise
     const int tile0 = planes ? (int)blockIdx.y * ntw * nw : 0;      // ntw <= NTW wavenumber tiles per wave
     if (tile0 * 16 > km) return;
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
     const int n = lane & 15, kk = lane >> 4;
     dft_d4 ac[NTW], as[NTW];
 #pragma unroll
@@ -1048,7 +1088,7 @@ k_fl_forward_dft(const double *__restrict__ np1, double *__restrict__ Fl, const 
             }
         }
     }
-    // D tile: lane holds column n (wavenumber of the tile), rows kk + 4 r.  sr = ac, si = -as; phase reference e^{-i k off}
+    // D tile: lane holds column n (wavenumber of the tile), rows kk + 4 r
     const double inv = 1.0 / L;
 #pragma unroll
     for (int q = 0; q < NTW; q++) {
@@ -1061,13 +1101,8 @@ k_fl_forward_dft(const double *__restrict__ np1, double *__restrict__ Fl, const 
         for (int r = 0; r < 4; r++) {
             const int zz = kk + 4 * r;
             if (zz >= zc) continue;
-            const double sr = ac[q][r], si = -as[q][r];
-            double2 out;
-            if (k == 0) out = make_double2(sr * inv, 0.0);
-            else out = make_double2((sr * w.x + si * w.y) * inv, (si * w.x - sr * w.y) * inv);
             // Fl [ring][v][z][blk]: row zz is level z0 + zz of variable v, or (planes) variable zz of a grid with nz = 1
-            double *dst = Fl + (planes ? (int64_t)ring * V + zz : ((int64_t)ring * V + v) * nz + z0 + zz) * K2 + 2 * k;
-            *reinterpret_cast<double2 *>(dst) = out;
+            forward_store(ac[q][r], -as[q][r], w, inv, k, Fl + (planes ? (int64_t)ring * V + zz : ((int64_t)ring * V + v) * nz + z0 + zz) * K2 + 2 * k);
         }
     }
 }
@@ -1088,20 +1123,19 @@ constexpr int LCQ = 64;       // quarter-ring points per staged chunk (RL grids)
 constexpr int LCZ = SX_LCZ;   // the same for k_fl_forward_dft_q (RLZ grids; measured: 64: 0.265 ms, 96: 0.262, 128 - one workgroup per CU by LDS: 0.399)
 
 __global__ void __launch_bounds__(512)
-k_fl_forward_dft_q(const double *__restrict__ np1, double *__restrict__ Fl, const int *__restrict__ Lr,
-                   const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                   const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V, int nz,
+k_fl_forward_dft_q(const double *__restrict__ np1, double *__restrict__ Fl, RingTables rt, int V, int nz,
                    int K2, int64_t N, const int *__restrict__ items, int lcap) {
     extern __shared__ double sm[];
     const int ring = items[2 * blockIdx.y], v = items[2 * blockIdx.y + 1], z0 = blockIdx.x * DZC;      // largest ring first (see the inverse)
     const int zc = min(DZC, nz - z0);
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2, Lq = L / 4;
-    double2 *twl = reinterpret_cast<double2 *>(sm);             // [L]
-    double *F = sm + 2 * (size_t)lcap;                          // [parity][cosine / sine part][LCZ][CST]
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lh = L / 2, Lq = L / 4;
+    const TableTiles lay = lds_fold(lcap, LCZ);
+    double2 *twl = lay.table(sm);                               // [L]
+    double *F = lay.at(sm, 0);                                  // [parity][cosine / sine part][LCZ][CST]
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;      // (scalar: the per-tile tests below are then scalar branches, not exec masks)
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
     const int n = lane & 15, kk = lane >> 4;
     // rings with more than 4 x NTW tiles per parity (kmax > 383) spread their tiles over gridDim.z workgroups, each folding
     // the ring for itself; blockIdx.z = 0 is all there is for the others
@@ -1182,7 +1216,7 @@ k_fl_forward_dft_q(const double *__restrict__ np1, double *__restrict__ Fl, cons
             }
         }
     }
-    // D tile: lane holds column n (wavenumber of the tile), rows kk + 4 r.  sr = ac, si = -as; phase reference e^{-i k off}
+    // D tile: lane holds column n (wavenumber of the tile), rows kk + 4 r
     const double inv = 1.0 / L;
 #pragma unroll
     for (int q = 0; q < NTW; q++) {
@@ -1193,12 +1227,7 @@ k_fl_forward_dft_q(const double *__restrict__ np1, double *__restrict__ Fl, cons
         for (int r = 0; r < 4; r++) {
             const int zz = kk + 4 * r;
             if (zz >= zc) continue;
-            const double sr = ac[q][r], si = -as[q][r];
-            double2 out;
-            if (k == 0) out = make_double2(sr * inv, 0.0);
-            else out = make_double2((sr * w.x + si * w.y) * inv, (si * w.x - sr * w.y) * inv);
-            double *dst = Fl + (((int64_t)ring * V + v) * nz + z0 + zz) * K2 + 2 * k;
-            *reinterpret_cast<double2 *>(dst) = out;
+            forward_store(ac[q][r], -as[q][r], w, inv, k, Fl + (((int64_t)ring * V + v) * nz + z0 + zz) * K2 + 2 * k);
         }
     }
 }
@@ -1213,22 +1242,20 @@ constexpr int KCHQ = 96;      // wavenumbers per staged chunk of the RL inverse 
 
 template <class ST, int NG>
 __global__ void __launch_bounds__(512)
-k_rl_inverse_dft_planes_q(const double *__restrict__ A, Planes<ST> phys, const double *__restrict__ phi, const int *__restrict__ Lr,
-                          const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                          const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V,
+k_rl_inverse_dft_planes_q(const double *__restrict__ A, Planes<ST> phys, const double *__restrict__ phi, RingTables rt, int V,
                           int K2, int nrings, int64_t N, int64_t arow, PlaneGroups pgs, const int *__restrict__ items, int lcap) {
     extern __shared__ double sm[];
     const int ring = items[2 * blockIdx.x], part = items[2 * blockIdx.x + 1];
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2, Lq = L / 4;
-    double2 *twl = reinterpret_cast<double2 *>(sm);
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lh = L / 2, Lq = L / 4;
     constexpr int CW = NG * CSTP;                              // row stride of the merged coefficient tile: NG groups of 16 (+1) columns
-    double *Cc = sm + 2 * (size_t)lcap;                         // [KCHQ][CW]
-    double *Cs = Cc + (size_t)KCHQ * CW;
+    const TableTiles lay = lds_coef(lcap, KCHQ, CW);
+    double2 *twl = lay.table(sm);
+    double *Cc = lay.at(sm, 0), *Cs = lay.at(sm, 1);            // [KCHQ][CW]
     const int j0 = ring / MUBAR;
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nw = blockDim.x >> 6;
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
     const double *pf = phi + (int64_t)ring * 4;
     const int i = lane & 15, kk = lane >> 4;
     const int mt = part * nw + wave;                            // this wave's row tile of the quarter ring (points mt * 16 .. + 15 of 0 .. L/4)
@@ -1245,6 +1272,8 @@ k_rl_inverse_dft_planes_q(const double *__restrict__ A, Planes<ST> phys, const d
         __syncthreads();                                        // the previous chunk has been consumed (and twl is complete)
         for (int e = tid; e < KCHQ * CW; e += blockDim.x) { Cc[e] = 0.0; Cs[e] = 0.0; }
         __syncthreads();
+        // the radial evaluation and the stores below are this kernel's own copies of radial_coef and Scatter::put4: with them the registers
+        // are the same but the six instances grow by 18 to 37 % of code (5,964 -> 7,060 ... 9,224 -> 12,620 bytes)
         for (int e = tid; e < V * kn; e += blockDim.x) {
             const int kl = e % kn, k = kc0 + kl, v = e / kn;
             const double *a = A + (int64_t)j0 * arow + (int64_t)v * K2 + 2 * k;
@@ -1326,19 +1355,18 @@ k_rl_inverse_dft_planes_q(const double *__restrict__ A, Planes<ST> phys, const d
 // one PART of a ring's wavenumbers - wave w: parity w & 1, tile (w >> 1) + 4 part of 16 wavenumbers of that parity, i.e. 128
 // wavenumbers per workgroup - and folds the ring for itself.
 __global__ void __launch_bounds__(512)
-k_fl_forward_dft_qp(const double *__restrict__ np1, double *__restrict__ Fl, const int *__restrict__ Lr,
-                    const int *__restrict__ kmaxr, const int64_t *__restrict__ pstart, const int64_t *__restrict__ twoff,
-                    const double2 *__restrict__ tw, const int64_t *__restrict__ phoff, const double2 *__restrict__ ph, int V,
+k_fl_forward_dft_qp(const double *__restrict__ np1, double *__restrict__ Fl, RingTables rt, int V,
                     int K2, int64_t N, const int *__restrict__ items, int lcap) {
     extern __shared__ double sm[];
     const int ring = items[2 * blockIdx.x], part = items[2 * blockIdx.x + 1];
-    const int L = Lr[ring], km = kmaxr[ring], Lh = L / 2, Lq = L / 4;
-    double2 *twl = reinterpret_cast<double2 *>(sm);             // [L]
-    double *F = sm + 2 * (size_t)lcap;                          // [parity][cosine / sine part][LCQ][CST]
-    const double2 *phr = ph + phoff[ring];
-    const int64_t p0 = pstart[ring];
+    const int L = rt.Lr[ring], km = rt.kmaxr[ring], Lh = L / 2, Lq = L / 4;
+    const TableTiles lay = lds_fold(lcap, LCQ);
+    double2 *twl = lay.table(sm);                               // [L]
+    double *F = lay.at(sm, 0);                                  // [parity][cosine / sine part][LCQ][CST]
+    const double2 *phr = rt.ph + rt.phoff[ring];
+    const int64_t p0 = rt.pstart[ring];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    for (int m = tid; m < L; m += blockDim.x) twl[m] = tw[twoff[ring] + m];
+    load_twiddles(twl, rt.tw + rt.twoff[ring], L, tid);
     const int n = lane & 15, kk = lane >> 4;
     const int par = wave & 1, tq = (wave >> 1) + 4 * part;         // this wave's parity and tile
     const int nk = km >= par ? (km - par) / 2 + 1 : 0;              // wavenumbers of this parity
@@ -1393,17 +1421,25 @@ k_fl_forward_dft_qp(const double *__restrict__ np1, double *__restrict__ Fl, con
     for (int r = 0; r < 4; r++) {
         const int zz = kk + 4 * r;
         if (zz >= V) continue;
-        const double sr = ac[r], si = -as[r];
-        double2 out;
-        if (k == 0) out = make_double2(sr * inv, 0.0);
-        else out = make_double2((sr * w.x + si * w.y) * inv, (si * w.x - sr * w.y) * inv);
-        *reinterpret_cast<double2 *>(Fl + ((int64_t)ring * V + zz) * K2 + 2 * k) = out;
+        forward_store(ac[r], -as[r], w, inv, k, Fl + ((int64_t)ring * V + zz) * K2 + 2 * k);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ launchers
 // grids without a vertical dimension: columns = (variable, plane)
 static bool dft_planes(const sx_handle *h) { return !h->has_z; }
+static int level_chunks(const sx_handle *h) { return (h->nz + DZC - 1) / DZC; }      // gridDim.x of the RLZ kernels
+
+static RingTables ring_tables(const sx_handle *h) { return {h->d_L, h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph}; }
+static DftSlots dft_slots(const sx_handle *h) { return {h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5], h->slot[6]}; }
+
+// every launch of this file: the kernel's dynamic LDS limit, the launch on the handle's stream, the launch error
+template <class... KA, class... A>
+static void launch(sx_handle *h, void (*kern)(KA...), dim3 grid, int threads, size_t lds, A... args) {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, h->stream, args...);
+    HIPCHK(hipGetLastError());
+}
 
 bool dft_mfma_ok(const sx_handle *h) {
     if (!h->has_l || fft_path_ok(h)) return false;
@@ -1430,30 +1466,57 @@ static void for_ring_classes(sx_handle *h, int n_rings, F f, int max_classes = 4
     }
 }
 
+// A work list as the kernels read it: int pairs on the device, and their number.  counted: the bytes go into sx_handle::dev_bytes
+// ("alloc.total": what sx_create allocated) - the lists of sx_create do, the RL lists, made at the first launch, never did
+bool dft_upload_items(sx_handle *h, const DftItems &it, int **d_items, int *n_items, bool counted) {
+    void *d = nullptr;
+    const size_t bytes = sizeof(int) * std::max<size_t>(2 * it.size(), 1);
+    if (hipMalloc(&d, bytes) != hipSuccess || (!it.empty() && hipMemcpy(d, it.data(), sizeof(int) * 2 * it.size(), hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("work list upload failed");
+        return false;
+    }
+    h->allocs.push_back(d);
+    if (counted) h->dev_bytes += bytes;
+    *n_items = (int)it.size();
+    *d_items = (int *)d;
+    return true;
+}
+
 // (ring, part) work lists of the quarter-wave RL kernels, most expensive ring first: [0] inverse - a part is 8 row tiles of the
 // quarter ring (one per wave); [1] forward - a part is 128 wavenumbers (4 tiles of 16 per parity)
+DftItems rlq_items(const std::vector<int> &hL, const std::vector<int> &hkmax, int which) {
+    return dft_work_items((int)hL.size(),
+                          [&](int r) { return which == 0 ? (hL[r] / 4 / 16 + 1 + 7) / 8 : (hkmax[r] + 1 + 127) / 128; },
+                          [&](int r, int) { return (int64_t)hL[r]; });
+}
+
 static bool rlq_lists(sx_handle *h) {
     if (h->d_rlq_items[0]) return true;
-    for (int which = 0; which < 2; which++) {
-        std::vector<std::array<int64_t, 3>> it;       // (cost, ring, part)
-        for (int r = 0; r < h->nrings; r++) {
-            const int tiles = h->hL[r] / 4 / 16 + 1;
-            const int parts = which == 0 ? (tiles + 7) / 8 : (h->hkmax[r] + 1 + 127) / 128;
-            for (int p = 0; p < parts; p++) it.push_back({(int64_t)h->hL[r], r, p});
-        }
-        std::stable_sort(it.begin(), it.end(), [](const auto &a, const auto &b) { return a[0] > b[0]; });
-        std::vector<int> flat;
-        for (const auto &e : it) { flat.push_back((int)e[1]); flat.push_back((int)e[2]); }
-        void *d = nullptr;
-        if (hipMalloc(&d, sizeof(int) * flat.size()) != hipSuccess || hipMemcpy(d, flat.data(), sizeof(int) * flat.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            set_error("RL work list upload failed");
-            return false;
-        }
-        h->allocs.push_back(d);
-        h->n_rlq_items[which] = (int)it.size();
-        h->d_rlq_items[which] = (int *)d;
-    }
+    for (int which = 0; which < 2; which++)
+        if (!dft_upload_items(h, rlq_items(h->hL, h->hkmax, which), &h->d_rlq_items[which], &h->n_rlq_items[which], false)) return false;
     return true;
+}
+
+template <class ST>
+static void rl_inverse_planes(sx_handle *h, const PlaneGroups &pgs) {
+    const double *a = h->d_A + (int64_t)h->cell0 * h->C;
+    auto go = [&](auto kern, dim3 grid, size_t lds, auto... tail) {
+        launch(h, kern, grid, 512, lds, a, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, ring_tables(h), h->V, h->K2, h->nrings, h->N, h->C, pgs, tail...);
+    };
+    if (h->sw.rl_quarter && pgs.ng <= 3) {
+        // one launch over (ring, part) items, most expensive first; a part = 8 row tiles of the quarter ring (one per wave)
+        if (!rlq_lists(h)) return;
+        const int lcap = h->L_max;
+        go(pgs.ng == 1 ? k_rl_inverse_dft_planes_q<ST, 1> : pgs.ng == 2 ? k_rl_inverse_dft_planes_q<ST, 2> : k_rl_inverse_dft_planes_q<ST, 3>,
+           dim3(h->n_rlq_items[0]), lds_coef(lcap, KCHQ, pgs.ng * CSTP).bytes(), h->d_rlq_items[0], lcap);
+        return;
+    }
+    // two launch classes only: each launch is as long as its largest ring's workgroup, so more classes mostly add tails
+    for_ring_classes(h, h->nrings, [&](int r0, int nr, int lcap, int kcap) {
+        const int kcap4 = std::min((kcap + 1 + 3) & ~3, KCH);                               // wavenumbers staged per chunk
+        const int nsplit = std::max(1, ((lcap / 2 + 16) / 16 + 15) / 16);                   // 8 waves x ONE pair of row tiles of the half ring each
+        go(k_rl_inverse_dft_planes<ST>, dim3(nr, nsplit, pgs.ng), lds_coef(lcap, kcap4, CSTP).bytes(), r0, lcap, kcap4);
+    }, 2);
 }
 
 static void launch_rl_inverse_dft_planes(sx_handle *h, bool full) {
@@ -1477,44 +1540,8 @@ static void launch_rl_inverse_dft_planes(sx_handle *h, bool full) {
     }
     if (pc.n > 0) push();                       // V <= 8 variables x 5 planes = 40 columns at most: 3 groups
     if (pgs.ng == 0) return;
-    if (h->sw.rl_quarter && pgs.ng <= 3) {
-        // one launch over (ring, part) items, most expensive first; a part = 8 row tiles of the quarter ring (one per wave)
-        if (!rlq_lists(h)) return;
-        const double *a = h->d_A + (int64_t)h->cell0 * h->C;
-        const int lcap = h->L_max;
-#define DFT_INVQ(ST, NG)                                                                                                             \
-        {                                                                                                                            \
-            const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * KCHQ * NG * CSTP);                                   \
-            auto kern = k_rl_inverse_dft_planes_q<ST, NG>;                                                                           \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(kern, dim3(h->n_rlq_items[0]), dim3(512), lds, h->stream, a, planes_of<ST>(h->d_phys, h->V, h->N),    \
-                               h->d_phi, h->d_L, h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->K2,      \
-                               h->nrings, h->N, h->C, pgs, h->d_rlq_items[0], lcap);                                                 \
-        }
-        if (h->f32) { if (pgs.ng == 1) DFT_INVQ(float, 1) else if (pgs.ng == 2) DFT_INVQ(float, 2) else DFT_INVQ(float, 3) }
-        else { if (pgs.ng == 1) DFT_INVQ(double, 1) else if (pgs.ng == 2) DFT_INVQ(double, 2) else DFT_INVQ(double, 3) }
-#undef DFT_INVQ
-        HIPCHK(hipGetLastError());
-        return;
-    }
-    const double *a = h->d_A + (int64_t)h->cell0 * h->C;
-    // two launch classes only: each launch is as long as its largest ring's workgroup, so more classes mostly add tails
-    for_ring_classes(h, h->nrings, [&](int r0, int nr, int lcap, int kcap) {
-        const int kcap4 = std::min((kcap + 1 + 3) & ~3, KCH);                               // wavenumbers staged per chunk
-        const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * kcap4 * CSTP);
-        const int nsplit = std::max(1, ((lcap / 2 + 16) / 16 + 15) / 16);                   // 8 waves x ONE pair of row tiles of the half ring each
-#define DFT_INVP(ST)                                                                                                                 \
-        {                                                                                                                            \
-            auto kern = k_rl_inverse_dft_planes<ST>;                                                                                 \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(kern, dim3(nr, nsplit, pgs.ng), dim3(512), lds, h->stream, a, planes_of<ST>(h->d_phys, h->V, h->N),   \
-                               h->d_phi, h->d_L, h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->K2,      \
-                               h->nrings, h->N, h->C, pgs, r0, lcap, kcap4);                                                                \
-        }
-        if (h->f32) DFT_INVP(float) else DFT_INVP(double)
-#undef DFT_INVP
-        HIPCHK(hipGetLastError());
-    }, 2);
+    if (h->f32) rl_inverse_planes<float>(h, pgs);
+    else rl_inverse_planes<double>(h, pgs);
 }
 
 #ifdef SX_PHASES
@@ -1533,103 +1560,58 @@ void dft_phases_dump() {
 void dft_phases_dump() {}
 #endif
 
+// RLZ grids: ONE launch over the (ring, variable) work list, most expensive first (four launches by ring size, rings in
+// increasing order: 1.63 ms; one launch, largest first: 1.41 ms - the large rings no longer form the tail)
+template <class ST>
+static void rlz_inverse(sx_handle *h, const int *d_mask) {
+    const double *az = h->has_z ? h->d_Az : h->d_A + (int64_t)h->cell0 * h->C;
+    const int64_t azrow = h->has_z ? (int64_t)h->V * 3 * h->nz * h->K2 : h->C;
+    const int which = d_mask == h->d_mask_full ? 1 : 0;
+    const int nbig = h->n_dft_big[which];
+    auto go = [&](auto kern, dim3 grid, int threads, size_t lds, const int *items, auto... tail) {
+        launch(h, kern, grid, threads, lds, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, ring_tables(h), h->V, h->nz, h->nsz, h->K2, h->nrings, h->N, azrow, dft_slots(h), d_mask, items, tail...);
+    };
+    if (nbig > 0) {      // rings with kmax > 319 (listed first): wavenumbers in chunks, one group of 8 row tiles per workgroup
+        const int lcapb = h->L_max;
+        go(k_rl_inverse_dft_big<ST>, dim3(level_chunks(h), nbig, (lcapb / 4 / 16 + 1 + 7) / 8), 512, lds_coef(lcapb, KCH, CST).bytes(),
+           h->d_dft_items[which], lcapb);
+    }
+    const int lcap = h->dft_lcap_small;
+    const dim3 g(level_chunks(h), h->n_dft_items[which] - nbig, 1);
+    if (g.y == 0) return;
+    const int *items = h->d_dft_items[which] + 2 * nbig;
+    if (!h->sw.dft_merge) {
+        const int kcap4 = (h->dft_kcap_small + 1 + 3) & ~3;
+        go(k_rl_inverse_dft<ST>, g, 512, lds_coef(lcap, kcap4, CST).bytes(), items, lcap, kcap4);
+        return;
+    }
+    const bool e8 = h->sw.dft_eighth != 0;
+    const int kz = e8 ? 32 * ((h->dft_kcap_small + 1 + 31) / 32) : 8 * ((h->dft_kcap_small / 2 + 1 + 3) / 4);          // rows a K step can touch (see the kernel)
+    // two 256-thread workgroups per CU (HT) where one set + half the twiddle table fit 80 KB
+    const size_t ldsh = MergedLds<true>{(size_t)lcap, (size_t)kz}.bytes(1, e8);
+    if (e8 && h->sw.dft_half_wg && ldsh <= 80 * 1024) {
+        go(k_rl_inverse_dft_merged<ST, 2, true>, g, 256, ldsh, items, lcap, kz, 0);
+        return;
+    }
+    const MergedLds<false> lay{(size_t)lcap, (size_t)kz};
+    const int two = lay.bytes(2, e8) <= 160 * 1024 ? 1 : 0;            // two coefficient sets beside the twiddle table: kmax <= ~260
+    go(e8 ? k_rl_inverse_dft_merged<ST, 2> : k_rl_inverse_dft_merged<ST, 0>, g, 512, lay.bytes(two ? 2 : 1, e8), items, lcap, kz, two);
+}
+
 void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
     const int id = timer_id(h, "k_rl_inverse");
     timer_begin(h, id);
 #ifdef SX_PHASES
     if (!g_dft_buf && !dft_planes(h)) {
-        g_dft_n = (int64_t)((h->nz + DZC - 1) / DZC) * h->V * h->nrings;
+        g_dft_n = (int64_t)level_chunks(h) * h->V * h->nrings;
         hipMalloc(&g_dft_buf, sizeof(long long) * g_dft_n * 8);
         hipMemset(g_dft_buf, 0, sizeof(long long) * g_dft_n * 8);
         hipMemcpyToSymbol(HIP_SYMBOL(g_dft_dbg), &g_dft_buf, sizeof(g_dft_buf));
     }
 #endif
-    if (dft_planes(h)) {
-        launch_rl_inverse_dft_planes(h, d_mask == h->d_mask_full);
-        timer_end(h);
-        return;
-    }
-    const double *az = h->has_z ? h->d_Az : h->d_A + (int64_t)h->cell0 * h->C;
-    const int64_t azrow = h->has_z ? (int64_t)h->V * 3 * h->nz * h->K2 : h->C;
-    {
-        // ONE launch over the (ring, variable) work list, most expensive first (four launches by ring size, rings in
-        // increasing order: 1.63 ms; one launch, largest first: 1.41 ms - the large rings no longer form the tail)
-        const int which = d_mask == h->d_mask_full ? 1 : 0;
-        const int nbig = h->n_dft_big[which];
-        if (nbig > 0) {      // rings with kmax > 319 (listed first): wavenumbers in chunks, one group of 8 row tiles per workgroup
-            const int lcapb = h->L_max;
-            const size_t ldsb = sizeof(double) * (2 * (size_t)lcapb + (size_t)2 * KCH * CST);
-            dim3 gb((h->nz + DZC - 1) / DZC, nbig, (lcapb / 4 / 16 + 1 + 7) / 8);
-#define DFT_INVB(ST)                                                                                                                 \
-            {                                                                                                                        \
-                auto kern = k_rl_inverse_dft_big<ST>;                                                                                \
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb)); \
-                hipLaunchKernelGGL(kern, gb, dim3(512), ldsb, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L, \
-                                   h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2,     \
-                                   h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],   \
-                                   h->slot[6], d_mask, h->d_dft_items[which], lcapb);                                                \
-            }
-            if (h->f32) DFT_INVB(float) else DFT_INVB(double)
-#undef DFT_INVB
-            HIPCHK(hipGetLastError());
-        }
-        const int lcap = h->dft_lcap_small, kcap4 = (h->dft_kcap_small + 1 + 3) & ~3;
-        const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * kcap4 * CST);
-        dim3 g((h->nz + DZC - 1) / DZC, h->n_dft_items[which] - nbig, 1);
-        if (g.y == 0) { timer_end(h); return; }
-        if (h->sw.dft_merge) {
-            const bool e8 = h->sw.dft_eighth != 0;
-            const int kz = e8 ? 32 * ((h->dft_kcap_small + 1 + 31) / 32) : 8 * ((h->dft_kcap_small / 2 + 1 + 3) / 4);          // rows a K step can touch (see the kernel)
-            const size_t pad = e8 ? sizeof(double) * 32 * CST : 0;     // the pipelined loops request one K step beyond the staged rows
-            const size_t lds2 = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * kz * CST) + pad;
-            const int two = lds2 <= 160 * 1024 ? 1 : 0;            // two coefficient sets beside the twiddle table: kmax <= ~260
-            const size_t ldsm = two ? lds2 : sizeof(double) * (2 * (size_t)lcap + (size_t)2 * kz * CST) + pad;
-            // two 256-thread workgroups per CU (HT) where one set + half the twiddle table fit 80 KB
-            const size_t ldsh = sizeof(double) * ((size_t)2 * kz * CST + (size_t)lcap);
-            if (e8 && h->sw.dft_half_wg && ldsh <= 80 * 1024) {
-#define DFT_INVH(ST)                                                                                                                 \
-                {                                                                                                                    \
-                    auto kern = k_rl_inverse_dft_merged<ST, 2, true>;                                                                \
-                    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsh)); \
-                    hipLaunchKernelGGL(kern, g, dim3(256), ldsh, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L, \
-                                       h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2, \
-                                       h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5], \
-                                       h->slot[6], d_mask, h->d_dft_items[which] + 2 * nbig, lcap, kz, 0);                           \
-                }
-                if (h->f32) DFT_INVH(float) else DFT_INVH(double)
-#undef DFT_INVH
-                HIPCHK(hipGetLastError());
-                timer_end(h);
-                return;
-            }
-#define DFT_INVM(ST)                                                                                                                 \
-            {                                                                                                                        \
-                auto kern = e8 ? k_rl_inverse_dft_merged<ST, 2> : k_rl_inverse_dft_merged<ST, 0>;                                    \
-                HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsm)); \
-                hipLaunchKernelGGL(kern, g, dim3(512), ldsm, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L,  \
-                                   h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2,     \
-                                   h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],   \
-                                   h->slot[6], d_mask, h->d_dft_items[which] + 2 * nbig, lcap, kz, two);                             \
-            }
-            if (h->f32) DFT_INVM(float) else DFT_INVM(double)
-#undef DFT_INVM
-            HIPCHK(hipGetLastError());
-            timer_end(h);
-            return;
-        }
-#define DFT_INV(ST)                                                                                                                  \
-        {                                                                                                                            \
-            auto kern = k_rl_inverse_dft<ST>;                                                                                        \
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            hipLaunchKernelGGL(kern, g, dim3(512), lds, h->stream, az, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_L,       \
-                               h->d_kmax, h->d_pstart, h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->nsz, h->K2,         \
-                               h->nrings, h->N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],       \
-                               h->slot[6], d_mask, h->d_dft_items[which] + 2 * nbig, lcap, kcap4);                                   \
-        }
-        if (h->f32) DFT_INV(float) else DFT_INV(double)
-#undef DFT_INV
-        HIPCHK(hipGetLastError());
-    }
+    if (dft_planes(h)) launch_rl_inverse_dft_planes(h, d_mask == h->d_mask_full);
+    else if (h->f32) rlz_inverse<float>(h, d_mask);
+    else rlz_inverse<double>(h, d_mask);
     timer_end(h);
 }
 
@@ -1638,17 +1620,13 @@ void launch_fl_forward_dft(sx_handle *h) {
     timer_begin(h, id);
     const int planes = dft_planes(h) ? 1 : 0;
     const bool half = h->sw.dft_half != 0;      // A/B: the half-ring kernel
+    auto go = [&](auto kern, dim3 grid, size_t lds, auto... tail) {
+        launch(h, kern, grid, 512, lds, h->d_np1, h->d_Fl, ring_tables(h), h->V, tail...);
+    };
     if (planes && h->sw.rl_quarter && rlq_lists(h)) {      // RL grids: quarter-wave fold, one launch over (ring, part) items
         const int lcap = h->L_max;
-        const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * LCQ * CST);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_qp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_fl_forward_dft_qp, dim3(h->n_rlq_items[1]), dim3(512), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
-                           h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->K2, h->N, h->d_rlq_items[1], lcap);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
-        return;
-    }
-    if (!planes && !half) {          // quarter-wave form; 4 waves x NTW tiles x 16 = 192 wavenumbers per parity >= (kmax <= 319) / 2 + 1
+        go(k_fl_forward_dft_qp, dim3(h->n_rlq_items[1]), lds_fold(lcap, LCQ).bytes(), h->K2, h->N, h->d_rlq_items[1], lcap);
+    } else if (!planes && !half) {   // quarter-wave form; 4 waves x NTW tiles x 16 = 192 wavenumbers per parity >= (kmax <= 319) / 2 + 1
         // ONE launch over the work list (four launches by ring size, each with its own tail: 0.32 -> 0.29 ms)
         // rings with kmax > 319 (listed first) in their own launch: the wavenumber tiles of a ring spread over gridDim.z
         // workgroups (12 tiles of 16 wavenumbers per parity each); the others as before, sized for their largest ring
@@ -1658,28 +1636,17 @@ void launch_fl_forward_dft(sx_handle *h) {
             if (n == 0) continue;
             const int lcap = part == 0 ? h->L_max : h->dft_lcap_small;
             const int kparts = part == 0 ? ((h->kmax_max / 2 + 1 + 15) / 16 + 4 * NTW - 1) / (4 * NTW) : 1;
-            const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)4 * LCZ * CST);
-            dim3 g((h->nz + DZC - 1) / DZC, n, kparts);
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft_q), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k_fl_forward_dft_q, g, dim3(512), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
-                               h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N, h->d_dft_items[2] + (part == 0 ? 0 : 2 * nbig), lcap);
-            HIPCHK(hipGetLastError());
+            go(k_fl_forward_dft_q, dim3(level_chunks(h), n, kparts), lds_fold(lcap, LCZ).bytes(), h->nz, h->K2, h->N,
+               h->d_dft_items[2] + (part == 0 ? 0 : 2 * nbig), lcap);
         }
-        timer_end(h);
-        return;
+    } else {
+        for_ring_classes(h, h->nrings, [&](int r0, int nr, int lcap, int kcap) {
+            // planes: one wavenumber tile per wave, the ring's (kmax + 1) / 16 tiles spread over gridDim.y workgroups of 8 waves
+            const int ntw = planes ? 1 : NTW;
+            go(k_fl_forward_dft, dim3(planes ? 1 : level_chunks(h), planes ? ((kcap + 1 + 15) / 16 + 7) / 8 : h->V, nr), lds_half(lcap).bytes(),
+               h->nz, h->K2, h->N, r0, lcap, planes, ntw);
+        }, planes ? 2 : 4);
     }
-    for_ring_classes(h, h->nrings, [&](int r0, int nr, int lcap, int) {
-        const size_t lds = sizeof(double) * (2 * (size_t)lcap + (size_t)2 * LCH * CST);
-        // planes: one wavenumber tile per wave, the ring's (kmax + 1) / 16 tiles spread over gridDim.y workgroups of 8 waves
-        const int ntw = planes ? 1 : NTW;
-        int kcap = 0;
-        for (int i = r0; i < r0 + nr; i++) kcap = std::max(kcap, h->hkmax[i]);
-        dim3 g(planes ? 1 : (h->nz + DZC - 1) / DZC, planes ? ((kcap + 1 + 15) / 16 + 7) / 8 : h->V, nr);
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fl_forward_dft), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_fl_forward_dft, g, dim3(512), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
-                           h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N, r0, lcap, planes, ntw);
-        HIPCHK(hipGetLastError());
-    }, planes ? 2 : 4);
     timer_end(h);
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -444,6 +445,25 @@ inline bool mfma_shape(const sx_handle *h, bool zb_bound = false) {
 }
 bool fft_fused_zinv(const sx_handle *h);
 bool dft_mfma_ok(const sx_handle *h);
+// work lists of the native-ring DFT launches (sx_dft.hip): (ring, x) items, most expensive first; x is a variable (RLZ) or a part (RL)
+using DftItems = std::vector<std::array<int, 2>>;
+// the items (ring, x), x < nparts(ring), whose cost(ring, x) is positive, in order of decreasing cost - workgroups are dispatched in
+// blockIdx order, so the cheap items fill the tail of the launch; equal costs keep the order (ring, x)
+template <class NParts, class Cost>
+DftItems dft_work_items(int nrings, NParts nparts, Cost cost) {
+    std::vector<std::array<int64_t, 3>> it;       // (cost, ring, x)
+    for (int r = 0; r < nrings; r++)
+        for (int x = 0, n = nparts(r); x < n; x++) {
+            const int64_t c = cost(r, x);
+            if (c > 0) it.push_back({c, r, x});
+        }
+    std::stable_sort(it.begin(), it.end(), [](const auto &a, const auto &b) { return a[0] > b[0]; });
+    DftItems out;
+    for (const auto &e : it) out.push_back({(int)e[1], (int)e[2]});
+    return out;
+}
+bool dft_upload_items(sx_handle *h, const DftItems &it, int **d_items, int *n_items, bool counted);
+DftItems rlq_items(const std::vector<int> &hL, const std::vector<int> &hkmax, int which);      // RL grids: [0] inverse, [1] forward
 void launch_rl_inverse_dft(sx_handle *h, const int *d_mask);
 void launch_fl_forward_dft(sx_handle *h);
 void launch_rl_inverse_fft(sx_handle *h, const int *d_mask, int n_rings = -1);
