@@ -551,6 +551,67 @@ int sx_extremum_refine(sx_handle *h, int32_t var, int32_t want, int32_t free_mas
 int sx_newton_step(const sx_grid_desc *grid, int32_t want, int32_t free_mask, double tol, const double *pos /*[n_coord]*/,
                    const double *d /*[10]*/, double *new_pos /*[n_coord]*/, int32_t *status);
 
+/* --- level crossings of field programs along rays: wind radii -----------------------------------------------------------
+ * How large is the vortex: the radii at which a field program crosses given levels along rays (the radius of gale-force wind per
+ * azimuth, the radius of a height or vorticity contour).
+ * Program: exactly sx_reduce's (the same terms[n_terms][11], coef and limits, validated by sx_reduce_planes itself with the slot rules of
+ * SX_REDUCE_PHYSICAL) with ONE output: every term's out is 0.  A ray q is (lambda_q, z_q): rays[n_rays, n_coord - 1] column-major; a grid
+ * without an azimuth has no lambda, one without a vertical no z; an R grid has no ray coordinate at all (rays is not read, every ray is
+ * the one ray).  On ray q
+ *     g_q(r) = sum_t coef[t] r^p_t prod_f field(var_f, slot_f)(r, lambda_q, z_q)
+ * in plain fp64, in term order, starting from +0.0 (as sx_extrema forms it), every field the CONTINUOUS spectral function of sx_evaluate
+ * with the SX_EVAL_ALL_K truncation (smooth in r, as for the parcels and sx_extremum_refine) and sx_evaluate's vertical series and
+ * boundary-condition projection, summed from the A coefficients the handle holds now.  For each of the n_levels <= 8 levels c_j the
+ * call returns the radii where d = g_q(r) - c_j changes sign, ordered outward.
+ * Stage 1, k_ray_profiles.  Along a ray the sums over lambda and z do not depend on r, so a field on a ray is a cubic spline in r with
+ * the coefficients P[m] = sum_blk sum_zm A[zm, blk, m] F_blk^(sl)(lambda_q) Wz^(sz)[zm](z_q), m over the tile's num_cells + 3 patch
+ * rows: the ray's profile.  Slots u, r, rr share the profile (sl, sz) = (0, 0) and differ in phi, phi', phi''; l, ll take F', F''; z, zz
+ * the vertical rows 1, 2: at most 16 profiles, numbered in the order the program first names them.  Per variable the profiles of all
+ * rays are ONE matrix product [rows x columns] [columns x rays] on the f64 matrix cores; the ray weights are formed on the device with
+ * k_parcels' arithmetic (a lambda within [-2 pi, 2 pi] is used as given; outside, it is reduced into (-pi, pi] in extended precision on
+ * the host).  The order of the sum over the columns depends on the grid alone, and ray tiles are padded with zero weights: a ray's
+ * profile is bitwise independent of the other rays of the call and of their number.
+ * Stage 2, k_crossings, one wave per ray.  Stations: the tile's inner end, its 3 tile_num_cells radial gridpoints (the doubles
+ * sx_get_gridpoints returns) and its outer end, n_st = 3 tile_num_cells + 2, taken by the lanes in chunks of 64.  g at a radius is, per
+ * plane, the 4-node spline sum of the profile with the weights phi, phi' / DX, phi'' / DX^2 of sx_eval_basis formed in plain fp64
+ * from delta = (r - x_node) / DX, then the program.  With neg(d) = (d < 0), the interval [s_i, s_i+1] holds a crossing when
+ * neg(d_i) != neg(d_i+1) and neither value is NaN: an exact zero counts as non-negative, so a root exactly on a station is counted
+ * once.  dir is +1 where d rises outward and -1 where it falls.  An interval with a NaN end holds no crossing and sets bit 0 of the
+ * ray's status.  LIMIT: two sign changes inside one station interval are not seen.
+ * Refinement, one lane per crossing: a bracketed iteration on d from the profiles that always keeps the sign change between its inner
+ * end a and outer end b - false position through (a, ga), (b, gb), where an end that stays twice in a row has its g halved (Illinois); the
+ * trial point is the midpoint a + (b - a) / 2 instead when the false position is not strictly inside, or when the step before did not
+ * halve the bracket.  It stops when b - a <= tol DX, when d == 0 exactly at an end or at a trial point, or after max_iter steps (bit 1
+ * of status; a NaN at a trial point: bit 2), and returns the end with the smaller |d|, the inner one on a tie.  tol <= 0 selects 1e-9,
+ * max_iter <= 0 selects 60.
+ * Results, column-major: radius[max_cross, n_levels, n_rays] and dir of the same shape hold the first max_cross crossings outward, unused
+ * entries NaN and 0; count[n_levels, n_rays] is the number of crossings FOUND and may exceed max_cross; status[n_rays]; profiles (may be
+ * NULL) [num_cells + 3, n_profiles, n_rays].  No atomics and nothing is summed across rays: the result for a ray and a level is bitwise
+ * independent of the other rays and levels of the call and of the launch shape.
+ * Refused, with a message and before anything is written: a null pointer with a non-zero count; whatever sx_reduce_planes refuses;
+ * a term whose out is not 0; n_levels outside [1, 8]; max_cross outside [1, 16]; a NaN / Inf ray coordinate or level, or a z out of
+ * range; a non-finite tol; more than 2^20 rays; a negative r_power on an RL / RLZ tile whose first station is r == 0; a handle that is
+ * not a one-tile patch; a grid whose ray weights do not fit the 64 KB of LDS of one workgroup:
+ * 32 (kDim + 1) + 48 b_zDim + 16 zDim + 576 > 8192 doubles (no azimuth: without the first term; no vertical: b_zDim = 1, zDim = 0).
+ * n_rays == 0 succeeds and writes nothing.
+ * Runs on the handle's stream and returns after the copy-out; reads A only (a deferred diagnostic variable is brought up to date first,
+ * as for every reader of A): `physical`, var_np1, the tendency history, the B arrays, parcels and captured graphs stay bitwise as they
+ * are.  sx_kernel_bytes("k_ray_profiles") gives the A columns of the variables named and the ray coordinates in + the profiles out of
+ * the last call, sx_kernel_bytes("k_crossings") the profiles in + the results out.
+ *
+ * sx_bracket_step is one step of that refinement on the host (pure helper, no handle and no device; the same function compiled for
+ * both).  state[7] = a, d(a), b, d(b), ga, gb, x and flags[2] = the end the last step replaced (-1 inner, +1 outer, 0 none), whether
+ * the next trial is a bisection; both are read and written.  first != 0: state[0..3] holds a station interval; the helper sets
+ * the rest and, unless the bracket is finished already, the first trial point x (fx is ignored).  first == 0: fx = d(x) enters.
+ * *status: 0 finished, -1 evaluate d at x and call again, 2 fx is NaN (the bracket stays).  width_tol is tol DX.  The result is a when
+ * |d(a)| <= |d(b)|, else b.  Refused: a null pointer; a non-finite width_tol; a bracket that is not finite with a <= b or over which d
+ * does not change sign; a trial point outside the bracket. */
+int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_t *terms, int64_t n_rays,
+                 const double *rays /*[n_rays, n_coord - 1]*/, int32_t n_levels, const double *levels, double tol, int32_t max_iter,
+                 int32_t max_cross, double *radius /*[max_cross, n_levels, n_rays]*/, int32_t *dir /*same shape*/,
+                 int32_t *count /*[n_levels, n_rays]*/, int32_t *status /*[n_rays]*/, double *profiles /*may be NULL*/);
+int sx_bracket_step(double *state /*[7]*/, int32_t *flags /*[2]*/, int32_t first, double fx, double width_tol, int32_t *status);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

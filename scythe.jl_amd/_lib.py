@@ -136,6 +136,9 @@ SYMBOLS = {
     "sx_extrema": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D, P_I64]),
     "sx_extremum_refine": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int64, P_D, P_D, P_D, P_D, P_I32, P_I32]),
     "sx_newton_step": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_double, P_D, P_D, P_D, P_I32]),
+    "sx_crossings": (C.c_int, [_H, C.c_int32, P_D, P_I32, C.c_int64, P_D, C.c_int32, P_D, C.c_double, C.c_int32, C.c_int32, P_D, P_I32, P_I32,
+                                P_I32, P_D]),
+    "sx_bracket_step": (C.c_int, [P_D, P_I32, C.c_int32, C.c_double, C.c_double, P_I32]),
 }
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)

@@ -1,0 +1,514 @@
+// sx_crossings / sx_bracket_step: the radii at which a field program crosses given levels along rays (include/scythe_hip.h,
+// DESIGN.md 15).
+//
+// Along a ray (lambda, z) the azimuthal and vertical sums of the spectral state do not depend on r: the state on the ray is a cubic
+// spline in r whose coefficients, the ray's PROFILE, are one contraction of A,
+//   P[prof][q][m] = sum_col A[m][var, col] W[col][q],   W[col][q] = F_blk^(sl)(lambda_q) Wz^(sz)[zm](z_q),   col = (zm, blk),
+// a [rows x ncol] [ncol x n_rays] product per variable.  k_ray_profiles runs it on the f64 matrix cores: a wave owns 16 patch rows x
+// 16 rays of one variable, stages 16 x CROSS_KC tiles of A through LDS (coalesced row pieces in, the A-operand layout lane =
+// (col & 3) * 16 + row out), forms the B operand - the ray weights - on the fly from the wave's tables of cos / sin k lambda and of
+// the vertical rows (k_parcels' arithmetic), and keeps one accumulator per (lambda order, z order) the program names.  The K order is
+// col = 0, 1, 2, ... whatever the rays are, columns of the matrix product do not mix, and a ray tile is padded with zero weights: a
+// ray's profile is bitwise independent of the other rays of the call and of their number.
+//
+// k_crossings: one wave per ray.  Lanes take the stations (inner end, radial gridpoints, outer end) in chunks of 64, evaluate the
+// program from the profiles (4 multiply-adds per plane), compare neighbours (the last lane's value is carried into the next chunk),
+// number the crossings of a level outward with a ballot, and every crossing is refined by its own lane with bracket_step - the
+// function sx_bracket_step runs on the host.  No atomics, nothing summed across rays.
+#include "sx_redprog.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace sx {
+
+constexpr int CROSS_LEVELS = 8, CROSS_MAX = 16;
+constexpr int CROSS_KINDS = 5;            // profile kinds of a variable: value, d/dlambda, d2/dlambda2, d/dz, d2/dz2
+constexpr int CROSS_KC = 32;              // columns of A per staged tile: 8 K steps
+constexpr int CROSS_AS = 36;              // row stride of the staged tile in doubles
+constexpr size_t CROSS_LDS_MAX = 64 * 1024;
+constexpr int64_t CROSS_RAYS_MAX = (int64_t)1 << 20;
+
+typedef double cross_d4 __attribute__((ext_vector_type(4)));
+
+// ---- stage 1: the ray profiles -----------------------------------------------------------------------------------------------------
+struct ProfVar {
+    int var, cls;                         // 0-based variable, its vertical class
+    int prof[CROSS_KINDS];                // profile number of each kind, -1 = not named
+};
+struct ProfArgs {
+    const double *A;                      // [b_rDim][C]
+    const double *w3;                     // [ncls][3][nz][Zb] CA, Dc CA, Dc Dc CA (null without a vertical)
+    const double *rays;                   // [n_coord - 1][n_rays]: lambda[, z]; |lambda| <= 2 pi
+    double *P;                            // [n_rays][nprof][rows]
+    int64_t C;
+    int n_rays, rows, row0, nprof, Zb, nz, K2, kDim, has_l, has_z;
+    double zmin, zmax;
+    ProfVar v[RED_PLANES];
+};
+
+// doubles of LDS: cs [kDim + 1][16] double2 (grids with an azimuth) | wz [3][Zb][16] | tz [nz][16] | sA [16][CROSS_AS]
+static size_t prof_lds(const sx_handle *h) {
+    const size_t Zb = h->has_z ? h->Zb : 1, nz = h->has_z ? h->nz : 0;
+    return sizeof(double) * ((h->has_l ? 32 * (size_t)(h->kDim + 1) : 0) + 48 * Zb + 16 * nz + 16 * CROSS_AS);
+}
+
+// grid (ceil(rows / 16), ceil(n_rays / 16), variables named)
+__global__ __launch_bounds__(64) void k_ray_profiles(ProfArgs a) {
+    extern __shared__ double lds[];
+    double2 *cs = reinterpret_cast<double2 *>(lds);
+    double *wz = lds + (a.has_l ? 32 * (size_t)(a.kDim + 1) : 0);
+    double *tz = wz + 48 * (size_t)a.Zb;
+    double *sA = tz + 16 * (size_t)(a.has_z ? a.nz : 0);
+    const int lane = threadIdx.x, j = lane & 15, kk = lane >> 4;
+    const int m0 = blockIdx.x * 16, q0 = blockIdx.y * 16;
+    const ProfVar pv = a.v[blockIdx.z];
+
+    // ---- the weights of the 16 rays (as k_parcels forms them; a ray beyond the call's takes lambda = 0, the lowest level, and no weight)
+    if (a.has_l)
+        for (int e = lane; e < 16 * (a.kDim + 1); e += 64) {
+            const int k = e >> 4, q = q0 + (e & 15);
+            const double lam = q < a.n_rays ? a.rays[q] : 0.0;
+            double s, c;
+            sincos((double)k * lam, &s, &c);   // |lambda| <= 2 pi: the product is off by at most 2 k pi eps
+            cs[e] = make_double2(c, s);
+        }
+    if (a.has_z) {
+        const double mid = (a.zmin + a.zmax) / 2.0, half = (a.zmax - a.zmin) / 2.0;
+        const double *zr = a.rays + (a.has_l ? (int64_t)a.n_rays : 0);
+        for (int e = lane; e < 16 * a.nz; e += 64) {
+            const int n = e >> 4, q = q0 + (e & 15);
+            const double z = q < a.n_rays ? zr[q] : a.zmin;
+            const double x = fmin(fmax((z - mid) / (-half), -1.0), 1.0);
+            const double th = acos(x);
+            tz[e] = ((n == 0 || n == a.nz - 1) ? 1.0 : 2.0) * cos((double)n * th);
+        }
+        __syncthreads();
+        const double *w3 = a.w3 + (size_t)pv.cls * 3 * a.nz * a.Zb;
+        for (int e = lane; e < 48 * a.Zb; e += 64) {
+            const int m = e / (16 * a.Zb), zm = (e - m * 16 * a.Zb) >> 4, jj = e & 15;
+            const bool need = m == 0 ? (pv.prof[0] >= 0 || pv.prof[1] >= 0 || pv.prof[2] >= 0) : pv.prof[2 + m] >= 0;
+            double acc = 0.0;
+            if (need) {
+                const double *w = w3 + (size_t)m * a.nz * a.Zb + zm;
+                for (int n = 0; n < a.nz; n++) acc = fma(tz[n * 16 + jj], w[(size_t)n * a.Zb], acc);
+            }
+            wz[e] = acc;
+        }
+    } else {
+        if (lane < 48) wz[lane] = lane < 16 ? 1.0 : 0.0;           // Zb = 1 without a vertical
+    }
+
+    // ---- the product: K = the columns of the variable in their own order, 4 per step
+    cross_d4 acc[CROSS_KINDS];
+#pragma unroll
+    for (int p = 0; p < CROSS_KINDS; p++) acc[p] = cross_d4{0.0, 0.0, 0.0, 0.0};
+    const int ncol = a.Zb * a.K2;
+    const double *__restrict__ Av = a.A + (int64_t)a.row0 * a.C + (int64_t)pv.var * ncol;
+    const bool ray_on = q0 + j < a.n_rays;
+    const int cl = lane & 31, rh = lane >> 5;
+    for (int c0 = 0; c0 < ncol; c0 += CROSS_KC) {
+        __syncthreads();                                           // the tile (and, the first time, the weights) of the pass before
+        const int col = c0 + cl;
+        const bool col_on = col < ncol && !(a.has_l && col % a.K2 == 1);      // block 1 is the padding block: never read
+#pragma unroll
+        for (int rr = 0; rr < 8; rr++) {
+            const int row = 2 * rr + rh;
+            sA[row * CROSS_AS + cl] = col_on && m0 + row < a.rows ? Av[(int64_t)(m0 + row) * a.C + col] : 0.0;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < CROSS_KC / 4; s++) {
+            if (c0 + 4 * s >= ncol) break;                         // uniform
+            const int kc = c0 + 4 * s + kk;
+            const bool on = kc < ncol;
+            const int kcl = on ? kc : ncol - 1;
+            const int zm = kcl / a.K2, blk = kcl - zm * a.K2;
+            const double av = sA[j * CROSS_AS + 4 * s + kk];       // A operand: row lane & 15, column lane >> 4
+            // F_blk and its lambda derivatives: block 0 is 1; Re k: 2 cos, -2 k sin, -2 k^2 cos; Im k: -2 sin, -2 k cos, 2 k^2 sin
+            double F0 = 1.0, F1 = 0.0, F2 = 0.0;
+            if (a.has_l) {
+                const int k = blk >> 1;
+                const double2 t = cs[k * 16 + j];
+                const double kd = (double)k;
+                const double x = (blk & 1) ? -t.y : t.x, y = (blk & 1) ? -t.x : -t.y;
+                F0 = blk == 0 ? 1.0 : 2.0 * x; F1 = 2.0 * kd * y; F2 = -(kd * kd) * F0;
+            }
+            const bool live = on && ray_on && !(a.has_l && blk == 1);
+            const double z0 = live ? wz[zm * 16 + j] : 0.0;
+            if (pv.prof[0] >= 0) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, F0 * z0, acc[0], 0, 0, 0);
+            if (pv.prof[1] >= 0) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, F1 * z0, acc[1], 0, 0, 0);
+            if (pv.prof[2] >= 0) acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, F2 * z0, acc[2], 0, 0, 0);
+            if (pv.prof[3] >= 0) acc[3] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, live ? F0 * wz[(a.Zb + zm) * 16 + j] : 0.0, acc[3], 0, 0, 0);
+            if (pv.prof[4] >= 0) acc[4] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, live ? F0 * wz[(2 * a.Zb + zm) * 16 + j] : 0.0, acc[4], 0, 0, 0);
+        }
+    }
+    // C / D layout of v_mfma_f64_16x16x4: column lane & 15, row (lane >> 4) + 4 reg
+    if (!ray_on) return;
+#pragma unroll
+    for (int p = 0; p < CROSS_KINDS; p++) {
+        if (pv.prof[p] < 0) continue;
+        double *__restrict__ dst = a.P + ((int64_t)(q0 + j) * a.nprof + pv.prof[p]) * a.rows;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int m = m0 + kk + 4 * r;
+            if (m < a.rows) dst[m] = acc[p][r];
+        }
+    }
+}
+
+// ---- what host and device share: the stations, the basis, the bracket step -------------------------------------------------------
+struct CrossGeom {
+    double xmin, DX, lo, hi;              // the tile's radial extent as eval_radius_ok reads it
+    int cell0, ncells, n_st;              // stations: lo, the 3 ncells radial gridpoints, hi
+};
+
+// the radius of station s: the doubles sx_get_gridpoints prints (ring_radius) between the tile's ends
+__host__ __device__ inline double cross_station(const CrossGeom &G, int s) {
+    if (s <= 0) return G.lo;
+    if (s >= G.n_st - 1) return G.hi;
+    const int i = s - 1, mu = i % MUBAR;
+    const double o = sqrt(3.0 / 5.0) / 2.0;
+    return G.xmin + G.DX * (G.cell0 + i / MUBAR + 0.5 + (mu == 0 ? -o : mu == 1 ? 0.0 : o));
+}
+
+// d-th derivative of the cardinal cubic B-spline (bspl of sx_setup.cpp)
+__host__ __device__ inline double cross_bspl(double delta, int d) {
+    const double z = fabs(delta);
+    if (z >= 2.0) return 0.0;
+    const double s = delta > 0 ? 1.0 : -1.0;
+    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
+    if (d == 0) return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
+    if (d == 1) return -s * (p * p / 2.0 - 2.0 * q * q);
+    return p - 4.0 * q;
+}
+
+// phi, phi', phi'' of the 4 nodes of r's cell (sx_eval_basis' statement in plain fp64); returns the cell = patch row of the first node
+__host__ __device__ inline int cross_basis(const CrossGeom &G, double r, double (&phi)[3][4]) {
+    int cell = (int)floor((r - G.xmin) / G.DX);
+    cell = cell < G.cell0 ? G.cell0 : cell > G.cell0 + G.ncells - 1 ? G.cell0 + G.ncells - 1 : cell;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const double delta = (r - (G.xmin + (double)(cell - 1 + j) * G.DX)) / G.DX;
+        phi[0][j] = cross_bspl(delta, 0);
+        phi[1][j] = cross_bspl(delta, 1) / G.DX;
+        phi[2][j] = cross_bspl(delta, 2) / (G.DX * G.DX);
+    }
+    return cell;
+}
+
+// The bracket of one crossing: d = g - c changes sign between a (inner) and b (outer); fa, fb are d there, ga, gb the values the false
+// position is drawn through (an end kept twice in a row has its value halved: Illinois), x the trial point whose d the next step takes
+struct Bracket {
+    double a, fa, b, fb, ga, gb, x;
+    int side, bis;                        // the end the last step replaced (-1 inner, +1 outer, 0 none yet); next trial by bisection
+};
+__host__ __device__ inline bool bracket_done(const Bracket &B, double wtol) { return B.fa == 0.0 || B.fb == 0.0 || !(B.b - B.a > wtol); }
+__host__ __device__ inline void bracket_trial(Bracket &B) {
+    double x = B.b - (B.gb * (B.b - B.a)) / (B.gb - B.ga);
+    if (B.bis || !(x > B.a && x < B.b)) x = B.a + 0.5 * (B.b - B.a);
+    B.x = x;
+}
+// 0: finished, -1: evaluate d at x and step
+__host__ __device__ inline int bracket_start(Bracket &B, double wtol) {
+    B.ga = B.fa; B.gb = B.fb; B.side = 0; B.bis = 0; B.x = B.a;
+    if (bracket_done(B, wtol)) return 0;
+    bracket_trial(B);
+    return -1;
+}
+// One step with fx = d(x): 0 finished, -1 go on, 2 fx is NaN (the bracket stays).  The bracket always holds the sign change; a step
+// that does not halve it is followed by a bisection.
+__host__ __device__ inline int bracket_step(Bracket &B, double fx, double wtol) {
+    if (fx != fx) return 2;
+    const double w0 = B.b - B.a;
+    if (fx == 0.0) { B.a = B.b = B.x; B.fa = B.fb = B.ga = B.gb = 0.0; return 0; }
+    if ((fx < 0.0) == (B.fa < 0.0)) {
+        B.a = B.x; B.fa = B.ga = fx;
+        if (B.side < 0) B.gb *= 0.5;
+        B.side = -1;
+    } else {
+        B.b = B.x; B.fb = B.gb = fx;
+        if (B.side > 0) B.ga *= 0.5;
+        B.side = 1;
+    }
+    B.bis = B.b - B.a > 0.5 * w0;
+    if (bracket_done(B, wtol)) return 0;
+    bracket_trial(B);
+    return -1;
+}
+// the end with the smaller |d|, the inner one on a tie
+__host__ __device__ inline double bracket_root(const Bracket &B) { return fabs(B.fa) <= fabs(B.fb) ? B.a : B.b; }
+
+// ---- stage 2: scan and refine ------------------------------------------------------------------------------------------------------
+struct CrossArgs {
+    const double *P;                      // [n_rays][nprof][rows]
+    double *radius;                       // [n_rays][n_levels][max_cross] as the caller's column-major [max_cross, n_levels, n_rays]
+    int *dir, *count, *status;            // as radius; [n_rays][n_levels]; [n_rays]
+    RedProg g;
+    uint8_t pprof[RED_PLANES], pd[RED_PLANES];     // plane -> profile number, radial order 0 .. 2
+    double level[CROSS_LEVELS];
+    double wtol;                          // tol DX
+    int n_rays, rows, nprof, n_levels, max_iter, max_cross;
+    CrossGeom G;
+};
+
+// g_q(r): the planes from the ray's profiles, then the program in term order from +0.0
+__device__ inline double cross_value(const CrossArgs &a, const double *__restrict__ Pq, double r) {
+    double phi[3][4];
+    const int cell = cross_basis(a.G, r, phi);
+    double val[RED_PLANES];
+#pragma unroll
+    for (int j = 0; j < RED_PLANES; j++) {
+        val[j] = 0.0;
+        if (j < a.g.n_planes) {
+            const double *__restrict__ p = Pq + (int64_t)a.pprof[j] * a.rows + (cell - a.G.cell0);
+            const int d = a.pd[j];
+            double w[4];
+#pragma unroll
+            for (int n = 0; n < 4; n++) w[n] = d == 0 ? phi[0][n] : d == 1 ? phi[1][n] : phi[2][n];
+            val[j] = fma(w[3], p[3], fma(w[2], p[2], fma(w[1], p[1], w[0] * p[0])));
+        }
+    }
+    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
+    double q = 0.0;
+    for (int t = a.g.start[0]; t < a.g.start[1]; t++) q += red_term(a.g, t, val, r, rr, ri, rri);
+    return q;
+}
+
+// grid (n_rays), one wave
+__global__ __launch_bounds__(64) void k_crossings(CrossArgs a) {
+    __shared__ int s_cnt[CROSS_LEVELS];
+    const int lane = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    const double *__restrict__ Pq = a.P + q * a.nprof * a.rows;
+    double *__restrict__ rad = a.radius + q * a.n_levels * a.max_cross;
+    int *__restrict__ dir = a.dir + q * a.n_levels * a.max_cross;
+    int cnt[CROSS_LEVELS];
+#pragma unroll
+    for (int j = 0; j < CROSS_LEVELS; j++) cnt[j] = 0;
+    int status = 0;
+    double carry_g = 0.0, carry_r = 0.0;
+    for (int base = 0; base < a.G.n_st; base += 64) {
+        const int s = base + lane;
+        const bool has = s < a.G.n_st;
+        const double r = cross_station(a.G, has ? s : a.G.n_st - 1);
+        const double g = cross_value(a, Pq, r);
+        double gp = __shfl_up(g, 1, 64), rp = __shfl_up(r, 1, 64);
+        if (lane == 0) { gp = carry_g; rp = carry_r; }            // the chunk before ended on station base - 1
+        carry_g = __shfl(g, 63, 64); carry_r = __shfl(r, 63, 64);
+        const bool iv = has && s > 0;                              // this lane owns the interval [s - 1, s]
+#pragma unroll
+        for (int j = 0; j < CROSS_LEVELS; j++) {
+            if (j >= a.n_levels) break;
+            const double c = a.level[j];
+            const double d0 = gp - c, d1 = g - c;
+            const bool nan = iv && (d0 != d0 || d1 != d1);
+            const bool cross = iv && !nan && ((d0 < 0.0) != (d1 < 0.0));
+            if (__ballot(nan)) status |= 1;
+            const unsigned long long mask = __ballot(cross);
+            const int pos = cnt[j] + __popcll(mask & ((1ull << lane) - 1ull));
+            cnt[j] += __popcll(mask);
+            if (cross && pos < a.max_cross) {
+                Bracket B;
+                B.a = rp; B.fa = d0; B.b = r; B.fb = d1;
+                int st = bracket_start(B, a.wtol);
+                for (int it = 0; st < 0 && it < a.max_iter; it++) st = bracket_step(B, cross_value(a, Pq, B.x) - c, a.wtol);
+                if (st != 0) status |= st < 0 ? 2 : 4;
+                rad[j * a.max_cross + pos] = bracket_root(B);
+                dir[j * a.max_cross + pos] = d0 < 0.0 ? 1 : -1;
+            }
+        }
+    }
+    // bits 1 and 2 are a lane's own: fold them over the wave
+    status = (status & 1) | (__ballot(status & 2) ? 2 : 0) | (__ballot(status & 4) ? 4 : 0);
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < CROSS_LEVELS; j++)
+            if (j < a.n_levels) { s_cnt[j] = cnt[j]; a.count[q * a.n_levels + j] = cnt[j]; }
+        a.status[q] = status;
+    }
+    __syncthreads();
+    for (int e = lane; e < a.n_levels * a.max_cross; e += 64) {    // the entries no crossing took
+        const int j = e / a.max_cross, pos = e - j * a.max_cross;
+        if (pos >= s_cnt[j]) { rad[e] = __builtin_nan(""); dir[e] = 0; }
+    }
+}
+
+// ---- host -----------------------------------------------------------------------------------------------------------------------
+struct CrossState : DiagState {          // last_bytes: k_ray_profiles'
+    double cross_bytes = 0;             // k_crossings'
+    DevBuf<double> d_w3;                // [ncls][3][nz][Zb], uploaded once per handle
+    bool w3_ready = false;
+    DevBuf<double> d_rays, d_P, d_rad;
+    DevBuf<int> d_i;                    // dir | count | status
+};
+
+double crossings_bytes(const sx_handle *h, bool scan) {
+    const CrossState *st = diag_state<CrossState>(h, DIAG_CROSSINGS);
+    return !st ? 0.0 : scan ? st->cross_bytes : st->last_bytes;
+}
+
+static CrossGeom cross_geom(const EvalGeom &g) {
+    CrossGeom G;
+    G.xmin = g.xmin; G.DX = g.DX; G.lo = g.tile_lo(); G.hi = g.tile_hi();
+    G.cell0 = g.cell0; G.ncells = g.ncells; G.n_st = MUBAR * g.ncells + 2;
+    return G;
+}
+
+}  // namespace sx
+
+using namespace sx;
+
+extern "C" {
+
+int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_t *terms, int64_t n_rays, const double *rays,
+                 int32_t n_levels, const double *levels, double tol, int32_t max_iter, int32_t max_cross, double *radius, int32_t *dir,
+                 int32_t *count, int32_t *status, double *profiles) {
+    clear_error();
+    if (!h) { set_error("null handle"); return 1; }
+    const char *who = "sx_crossings";
+    const sx_grid_desc gd = desc_of(h);
+    int32_t planes[RED_PLANES][2], n_planes = 0;
+    if (sx_reduce_planes(&gd, SX_REDUCE_PHYSICAL, n_terms, terms, 1, &planes[0][0], &n_planes)) return 1;      // one output: out = 0 in every term
+    if (n_terms > 0 && !coef) { set_error("sx_crossings: null coef with n_terms > 0"); return 1; }
+    if (n_levels < 1 || n_levels > CROSS_LEVELS) { set_error("sx_crossings: n_levels must be 1 .. 8"); return 1; }
+    if (max_cross < 1 || max_cross > CROSS_MAX) { set_error("sx_crossings: max_cross must be 1 .. 16"); return 1; }
+    if (!levels) { set_error("sx_crossings: null levels"); return 1; }
+    if (n_rays < 0) { set_error("sx_crossings: n_rays is negative"); return 1; }
+    if (n_rays > CROSS_RAYS_MAX) { set_error("sx_crossings: more than 2^20 rays in one call"); return 1; }
+    if (!std::isfinite(tol)) { set_error("sx_crossings: tol is NaN or Inf"); return 1; }
+    for (int j = 0; j < n_levels; j++)
+        if (!std::isfinite(levels[j])) { set_error("sx_crossings: level " + std::to_string(j) + " is NaN or Inf"); return 1; }
+    if (h->ncells != h->nc) { set_error("sx_crossings: one-tile patches only"); return 1; }
+    const EvalGeom g = eval_geom_of(h);
+    if (h->has_l && g.tile_lo() == 0.0)
+        for (int t = 0; t < n_terms; t++)
+            if (terms[(size_t)t * RED_TERM_W + 1] < 0) { set_error("sx_crossings: a negative r_power on a tile whose first station is r == 0"); return 1; }
+    if (prof_lds(h) > CROSS_LDS_MAX) {
+        set_error("sx_crossings: the weights of one ray tile do not fit the LDS (need 32 (kDim + 1) + 48 b_zDim + 16 zDim + 576 <= 8192 doubles)");
+        return 1;
+    }
+    const int nrc = h->ncoord - 1;                 // coordinates of a ray
+    if (n_rays > 0 && ((nrc > 0 && !rays) || !radius || !dir || !count || !status)) { set_error("sx_crossings: null argument with n_rays > 0"); return 1; }
+    std::string why;
+    for (int64_t i = 0; i < n_rays; i++) {
+        if (h->has_l && !std::isfinite(rays[i])) { set_error("sx_crossings: ray " + std::to_string(i) + ": a coordinate is NaN or Inf"); return 1; }
+        if (h->has_z && !eval_height_ok(g, rays[(int64_t)(nrc - 1) * n_rays + i], why)) { set_error("sx_crossings: ray " + std::to_string(i) + ": " + why); return 1; }
+    }
+    if (n_rays == 0) return 0;
+
+    // the profiles the planes need: (variable, kind), numbered in first-use order and grouped by variable
+    ProfArgs pa;
+    std::memset(&pa, 0, sizeof(pa));
+    CrossArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    int nv = 0, nprof = 0;
+    for (int j = 0; j < n_planes; j++) {
+        int m = 0;
+        while (h->slot[m] != planes[j][1]) m++;    // u r rr l ll z zz
+        const int kind = m < 3 ? 0 : m - 2, var = planes[j][0] - 1;
+        int v = 0;
+        while (v < nv && pa.v[v].var != var) v++;
+        if (v == nv) {
+            pa.v[v].var = var;
+            for (int k = 0; k < CROSS_KINDS; k++) pa.v[v].prof[k] = -1;
+            nv++;
+        }
+        if (pa.v[v].prof[kind] < 0) pa.v[v].prof[kind] = nprof++;
+        ca.pprof[j] = (uint8_t)pa.v[v].prof[kind];
+        ca.pd[j] = (uint8_t)(m < 3 ? m : 0);
+    }
+    const EvalClasses *k = h->has_z ? eval_classes(h) : nullptr;
+    if (h->has_z && !k) return 1;
+    if (!h->diag[DIAG_CROSSINGS]) h->diag[DIAG_CROSSINGS].reset(new CrossState());
+    CrossState *st = diag_state<CrossState>(h, DIAG_CROSSINGS);
+    const int Zb = h->has_z ? h->Zb : 1, nz = h->has_z ? h->nz : 1, rows = h->nbt;
+    if (k && !st->w3_ready) {
+        const size_t per = (size_t)3 * nz * Zb;
+        std::vector<double> w3(k->vert.size() * per);
+        for (size_t c = 0; c < k->vert.size(); c++)
+            for (int m = 0; m < 3; m++)
+                for (size_t e = 0; e < (size_t)nz * Zb; e++) w3[c * per + (size_t)m * nz * Zb + e] = (double)k->vert[c].W[m][e];
+        if (!st->d_w3.upload(w3, "sx_crossings: hipMalloc of the vertical operators failed")) return 1;
+        st->w3_ready = true;
+    }
+    for (int v = 0; v < nv; v++) pa.v[v].cls = k ? k->vcls[pa.v[v].var] : 0;
+
+    const size_t n_ray = (size_t)std::max(nrc, 1) * n_rays, n_P = (size_t)std::max(nprof, 1) * rows * n_rays;
+    const size_t n_rad = (size_t)max_cross * n_levels * n_rays, n_int = n_rad + (size_t)n_levels * n_rays + n_rays;
+    if (!st->d_rays.grow(n_ray, who) || !st->d_P.grow(n_P, who) || !st->d_rad.grow(n_rad, who) || !st->d_i.grow(n_int, who)) return 1;
+    std::vector<double> r0(n_ray, 0.0);
+    if (nrc > 0) std::memcpy(r0.data(), rays, sizeof(double) * nrc * n_rays);
+    if (h->has_l) {                                // a lambda outside [-2 pi, 2 pi] into (-pi, pi], in extended precision as sx_extremum_refine does
+        const long double two_pi = 8.0L * atanl(1.0L);
+        for (int64_t i = 0; i < n_rays; i++) {
+            if (std::fabs(rays[i]) <= 6.283185307179586) continue;
+            double l = (double)remainderl((long double)rays[i], two_pi);
+            if (l <= -M_PI) l = M_PI;
+            r0[i] = l;
+        }
+    }
+    flush_diag(h);                                 // as for every reader of A
+    HIPCHK(hipMemcpyAsync(st->d_rays, r0.data(), sizeof(double) * n_ray, hipMemcpyHostToDevice, h->stream));
+    if (error_status()) return 1;
+
+    pa.A = h->d_A; pa.w3 = k ? (const double *)st->d_w3 : nullptr; pa.rays = st->d_rays; pa.P = st->d_P;
+    pa.C = h->C; pa.n_rays = (int)n_rays; pa.rows = rows; pa.row0 = h->cell0; pa.nprof = nprof;
+    pa.Zb = Zb; pa.nz = nz; pa.K2 = h->K2; pa.kDim = h->kDim; pa.has_l = h->has_l; pa.has_z = h->has_z;
+    pa.zmin = h->zmin; pa.zmax = h->zmax;
+    // A columns of the variables named (the padding block left out) and the ray coordinates in, the profiles out
+    st->last_bytes = nv == 0 ? 0.0 : 8.0 * ((double)rows * Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv + (double)nrc * n_rays + (double)rows * nprof * n_rays);
+    if (nv > 0) {
+        timer_begin(h, timer_id(h, "k_ray_profiles"));
+        hipLaunchKernelGGL(k_ray_profiles, dim3((unsigned)((rows + 15) / 16), (unsigned)((n_rays + 15) / 16), (unsigned)nv), dim3(64), prof_lds(h),
+                           h->stream, pa);
+        HIPCHK(hipGetLastError());
+        timer_end(h);
+    }
+
+    ca.P = st->d_P; ca.radius = st->d_rad; ca.dir = st->d_i; ca.count = st->d_i + n_rad; ca.status = st->d_i + n_rad + (size_t)n_levels * n_rays;
+    red_pack(ca.g, planes, n_planes, n_terms, coef, terms, 1);
+    for (int j = 0; j < n_levels; j++) ca.level[j] = levels[j];
+    ca.G = cross_geom(g);
+    ca.wtol = (tol <= 0.0 ? 1e-9 : tol) * h->DX;
+    ca.n_rays = (int)n_rays; ca.rows = rows; ca.nprof = nprof; ca.n_levels = n_levels;
+    ca.max_iter = max_iter <= 0 ? 60 : max_iter; ca.max_cross = max_cross;
+    // the profiles in; radii, directions, counts and status out
+    st->cross_bytes = 8.0 * (double)rows * nprof * n_rays + 12.0 * (double)n_rad + 4.0 * ((double)n_levels + 1.0) * n_rays;
+    timer_begin(h, timer_id(h, "k_crossings"));
+    hipLaunchKernelGGL(k_crossings, dim3((unsigned)n_rays), dim3(64), 0, h->stream, ca);
+    HIPCHK(hipGetLastError());
+    timer_end(h);
+
+    std::vector<double> rr(n_rad), rp(profiles ? (size_t)nprof * rows * n_rays : 0);      // held back until the call has succeeded: a failed call writes nothing
+    std::vector<int> ri(n_int);
+    HIPCHK(hipMemcpyAsync(rr.data(), st->d_rad, sizeof(double) * n_rad, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ri.data(), st->d_i, sizeof(int) * n_int, hipMemcpyDeviceToHost, h->stream));
+    if (!rp.empty()) HIPCHK(hipMemcpyAsync(rp.data(), st->d_P, sizeof(double) * rp.size(), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (error_status()) return 1;
+    std::memcpy(radius, rr.data(), sizeof(double) * n_rad);
+    std::memcpy(dir, ri.data(), sizeof(int) * n_rad);
+    std::memcpy(count, ri.data() + n_rad, sizeof(int) * n_levels * n_rays);
+    std::memcpy(status, ri.data() + n_rad + (size_t)n_levels * n_rays, sizeof(int) * n_rays);
+    if (!rp.empty()) std::memcpy(profiles, rp.data(), sizeof(double) * rp.size());
+    return 0;
+}
+
+int sx_bracket_step(double *state, int32_t *flags, int32_t first, double fx, double width_tol, int32_t *status) {
+    clear_error();
+    if (!state || !flags || !status) { set_error("sx_bracket_step: null argument"); return 1; }
+    if (!std::isfinite(width_tol)) { set_error("sx_bracket_step: width_tol is NaN or Inf"); return 1; }
+    Bracket B;
+    B.a = state[0]; B.fa = state[1]; B.b = state[2]; B.fb = state[3]; B.ga = state[4]; B.gb = state[5]; B.x = state[6];
+    B.side = flags[0]; B.bis = flags[1];
+    if (!std::isfinite(B.a) || !std::isfinite(B.b) || !(B.a <= B.b)) { set_error("sx_bracket_step: the bracket needs finite a <= b"); return 1; }
+    if (B.fa != B.fa || B.fb != B.fb || ((B.fa < 0.0) == (B.fb < 0.0) && B.a < B.b)) { set_error("sx_bracket_step: d does not change sign over the bracket"); return 1; }
+    if (!first && !(B.x >= B.a && B.x <= B.b)) { set_error("sx_bracket_step: the trial point lies outside the bracket"); return 1; }
+    *status = first ? bracket_start(B, width_tol) : bracket_step(B, fx, width_tol);
+    state[0] = B.a; state[1] = B.fa; state[2] = B.b; state[3] = B.fb; state[4] = B.ga; state[5] = B.gb; state[6] = B.x;
+    flags[0] = B.side; flags[1] = B.bis;
+    return 0;
+}
+
+}  // extern "C"

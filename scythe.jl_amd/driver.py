@@ -15,6 +15,7 @@ import numpy as np
 from .model import (Grid, GridParameters, ModelParameters, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
 
 Located = collections.namedtuple("Located", "pos value status")
+WindRadii = collections.namedtuple("WindRadii", "thresholds azimuths radii quadrants")
 
 
 class PatchLayout:
@@ -627,6 +628,67 @@ class ModelRun:
         start = self.gridpoints()[row]
         res = g.refine_extremum(var, start[None, :], "max", "r")
         return Located(res.pos[0].copy(), float(res.value[0]), int(res.status[0]))
+
+    def _rays(self, azimuths, height):
+        """[n, n_coord - 1] ray coordinates lambda[, z] of the patch's geometry from azimuths and one height"""
+        geo = self.patch.geometry
+        lam = np.atleast_1d(np.asarray(azimuths if azimuths is not None else [0.0], dtype=np.float64))
+        cols = [lam] if "L" in geo else []
+        if "Z" in geo:
+            if height is None:
+                raise ValueError("a grid with a vertical needs a height")
+            cols.append(np.full(len(lam), float(height)))
+        elif height is not None:
+            raise ValueError("the grid has no vertical: height must be None")
+        return np.stack(cols, axis=1) if cols else np.zeros((len(lam), 0))
+
+    def radius_where(self, terms, level, azimuths, height=None, which="outermost"):
+        """The radius at which the one-output program `terms` (as for Grid.reduce) crosses `level` along the ray of every azimuth
+        at `height` (Grid.crossings, up to 16 crossings per ray kept).  which="outermost" / "innermost": ndarray [n_azimuths], NaN
+        where the ray has no crossing (or, outermost, more than 16); which="all": (radius [16, n_azimuths] outward, NaN-padded,
+        dir of that shape, count [n_azimuths]).  Reads the A coefficients as they stand; one-tile patches."""
+        if which not in ("outermost", "innermost", "all"):
+            raise ValueError("which must be 'outermost', 'innermost' or 'all'")
+        g = self._one_tile("radius_where")
+        rays = self._rays(azimuths, height)
+        res = g.crossings(terms, [level], rays if rays.shape[1] else len(rays), max_cross=16)
+        rad, cnt = res.radius[:, 0, :], res.count[0]
+        if which == "all":
+            return rad, res.dir[:, 0, :], cnt
+        if which == "innermost":
+            return rad[0].copy()
+        kept = (cnt >= 1) & (cnt <= 16)
+        return np.where(kept, rad[np.clip(cnt - 1, 0, 15), np.arange(len(cnt))], np.nan)
+
+    def wind_radii(self, u_var, v_var, thresholds, n_azimuths=360, height=None, quadrants=True):
+        """Wind radii (R34 / R50 / R64 ...): for every threshold the radius of the outermost crossing along each of n_azimuths
+        equally spaced rays at which the speed^2 = u^2 + v^2 of the wind (u_var, v_var) FALLS outward through threshold^2
+        (Grid.crossings, the first 16 crossings of a ray).  Returns WindRadii(thresholds, azimuths [n], radii [n_thresholds, n] with
+        NaN where a ray has no such crossing, quadrants [n_thresholds, 4] or None): the largest radius over the rays of the NE, SE,
+        SW and NW quadrant (lambda in [0, pi/2), [3 pi/2, 2 pi), [pi, 3 pi/2), [pi/2, pi): lambda = 0 points east, counter-clockwise),
+        NaN where no ray of the quadrant crosses.  One-tile patches."""
+        g = self._one_tile("wind_radii")
+        thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        n = int(n_azimuths)
+        lam = 2.0 * np.pi * np.arange(n) / n
+        rays = self._rays(lam, height)
+        prog = [(0, 1.0, 0, [(u_var, ""), (u_var, "")]), (0, 1.0, 0, [(v_var, ""), (v_var, "")])]
+        radii = np.full((len(thr), n), np.nan)
+        for j0 in range(0, len(thr), 8):
+            res = g.crossings(prog, thr[j0:j0 + 8] ** 2, rays if rays.shape[1] else n, max_cross=16)
+            falling = np.where(res.dir == -1, res.radius, -np.inf)           # [16, levels, n], outward: the last falling one is the largest
+            best = falling.max(axis=0)
+            radii[j0:j0 + 8] = np.where(np.isfinite(best), best, np.nan)
+        quad = None
+        if quadrants:
+            q = np.floor(lam / (np.pi / 2.0)).astype(int) % 4                # 0 NE, 1 NW, 2 SW, 3 SE
+            quad = np.full((len(thr), 4), np.nan)
+            for col, which in enumerate((0, 3, 2, 1)):
+                sel = radii[:, q == which]
+                ok = ~np.isnan(sel)
+                if sel.shape[1]:
+                    quad[:, col] = np.where(ok.any(axis=1), np.where(ok, sel, -np.inf).max(axis=1), np.nan)
+        return WindRadii(thr, lam, radii, quad)
 
     def spectrum(self, pairs, kind="ring"):
         """Azimuthal power and cross spectra over the local tiles (Grid.spectrum; reads A: no transform is run).  kind="domain":

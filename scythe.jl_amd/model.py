@@ -525,6 +525,44 @@ class Grid:
                                              grad.ctypes.data_as(L.P_D), status.ctypes.data_as(L.P_I32), iters.ctypes.data_as(L.P_I32)))
         return Refined(pos, value, grad, status, iters)
 
+    def crossings(self, terms, levels, rays, tol=None, max_iter=None, max_cross=4, return_profiles=False):
+        """The radii at which a field program crosses `levels` along rays, on the device (sx_crossings; reads the A coefficients the
+        tile holds now).  terms: a one-output program as for reduce (every out 0); rays [n_rays, n_coord - 1] with columns
+        lambda[, z] (an R grid: the number of rays, or None for one); levels: up to 8.  Returns Crossings(radius [max_cross, n_levels,
+        n_rays], dir of the same shape, count [n_levels, n_rays], status [n_rays], profiles): the first max_cross crossings of every
+        level outward (unused entries NaN, dir 0), dir +1 where the program rises outward through the level and -1 where it falls,
+        count the number found (it may exceed max_cross), status bit 0: a NaN on the ray, bit 1: a refinement ran out of
+        iterations, bit 2: it met a NaN.  profiles: [num_cells + 3, n_profiles, n_rays] with return_profiles, else None.
+        One-tile patches only."""
+        coef, packed, n_out = pack_reduce_program(self.patch_params, terms)
+        nrc = int(self.dims.n_coord) - 1
+        if nrc == 0:
+            n = 1 if rays is None else int(rays) if np.ndim(rays) == 0 else len(rays)
+            q = np.zeros((n, 0))
+        else:
+            q = np.asarray(rays, dtype=np.float64)
+            q = np.asfortranarray(q.reshape(-1, nrc) if q.ndim != 2 else q)
+            if q.shape[1] != nrc:
+                raise ValueError("rays must have %d coordinate column(s)" % nrc)
+            n = q.shape[0]
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.float64)
+        nl, mc = len(lev), int(max_cross)
+        shape = (max(mc, 0), nl, n)
+        radius, dirs = np.full(shape, np.nan, order="F"), np.zeros(shape, dtype=np.int32, order="F")
+        count, status = np.zeros((nl, n), dtype=np.int32, order="F"), np.zeros(n, dtype=np.int32)
+        prof = None
+        if return_profiles:
+            planes = reduce_planes(self.patch_params, terms) if len(coef) else np.zeros((0, 2), dtype=np.int32)
+            slots = L.SLOTS[self.patch_params.geometry]
+            keys = {(int(v), {"": 0, "r": 0, "rr": 0, "l": 1, "ll": 2, "z": 3, "zz": 4}[slots[int(s)]]) for v, s in planes}
+            prof = np.zeros((int(self.dims.b_rDim), len(keys), n), order="F")
+        L.check(self._lib.sx_crossings(self._h, len(coef), coef.ctypes.data_as(L.P_D), packed.ctypes.data_as(L.P_I32), n,
+                                       q.ctypes.data_as(L.P_D) if nrc else None, nl, lev.ctypes.data_as(L.P_D),
+                                       0.0 if tol is None else float(tol), 0 if max_iter is None else int(max_iter), mc,
+                                       radius.ctypes.data_as(L.P_D), dirs.ctypes.data_as(L.P_I32), count.ctypes.data_as(L.P_I32),
+                                       status.ctypes.data_as(L.P_I32), prof.ctypes.data_as(L.P_D) if prof is not None else None))
+        return Crossings(radius, dirs, count, status, prof)
+
     # -- operators
     def spectralTransform_(self):
         L.check(self._lib.sx_spectral_transform(self._h))
@@ -823,6 +861,24 @@ def newton_step(patch: GridParameters, pos, d, want="max", free=None, tol=None, 
     L.check(L.load().sx_newton_step(C.byref(desc), L.EXT_WANT[want], free_mask(patch, free), 0.0 if tol is None else float(tol),
                                     p.ctypes.data_as(L.P_D), dd.ctypes.data_as(L.P_D), out.ctypes.data_as(L.P_D), C.byref(st)))
     return out, int(st.value)
+
+
+# ----------------------------------------------------------------------------- level crossings along rays (sx_crossings)
+Crossings = collections.namedtuple("Crossings", "radius dir count status profiles")
+
+
+def bracket_step(state, flags, fx=0.0, width_tol=0.0, first=False):
+    """One step of Grid.crossings' refinement on the host (sx_bracket_step): state [7] = a, d(a), b, d(b), ga, gb, x and flags [2] =
+    (end replaced last, bisect next) -> (new state, new flags, status); first=True starts from the station interval in state[:4];
+    status 0 finished, -1 evaluate d at state[6] and step again, 2 fx is NaN."""
+    s = np.zeros(7)
+    s[:len(state)] = np.asarray(state, dtype=np.float64)
+    f = np.zeros(2, dtype=np.int32)
+    f[:len(flags)] = np.asarray(flags, dtype=np.int32)
+    st = C.c_int32(-2)
+    L.check(L.load().sx_bracket_step(s.ctypes.data_as(L.P_D), f.ctypes.data_as(L.P_I32), 1 if first else 0, float(fx), float(width_tol),
+                                     C.byref(st)))
+    return s, f, int(st.value)
 
 
 # ----------------------------------------------------------------------------- azimuthal power and cross spectra (sx_spectrum)
