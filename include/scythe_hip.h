@@ -612,6 +612,47 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
                  int32_t *count /*[n_levels, n_rays]*/, int32_t *status /*[n_rays]*/, double *profiles /*may be NULL*/);
 int sx_bracket_step(double *state /*[7]*/, int32_t *flags /*[2]*/, int32_t first, double fx, double width_tol, int32_t *status);
 
+/* --- histograms of field programs: CFADs, areas, quantiles -------------------------------------------------------------
+ * How much of the domain holds which values: the area inside an isotach, integrated kinetic energy above thresholds, contoured
+ * frequency-by-altitude diagrams, percentiles - without pulling `physical` to the host.
+ * Program and source are exactly those of sx_reduce (the same terms[n_terms][11] and coef, SX_REDUCE_PHYSICAL / SX_REDUCE_STATE with
+ * their slot rules, validated by sx_reduce_planes itself; with storage_f32 the derivative slots are read in the type they are stored
+ * in), with 1 <= n_out <= 4:
+ *   output 0 is the binned quantity q, formed per gridpoint as sx_extrema forms an output: plain fp64, term order, from +0.0 - a host
+ *     twin in float64 reproduces every point's slot exactly;
+ *   outputs 1 .. n_out - 1 are integrands g_j: per point every term is multiplied by the point's weight without a rounding of the
+ *     product (fma) and added in double-double, as in sx_reduce: the roundings of a sum are sx_reduce's;
+ *   sums[:, 0, :] is the measure: the sum of the weights themselves.
+ * Slots.  n_bins + 3 per group, 1 <= n_bins <= 64, edges[n_bins + 1] finite and strictly increasing: slot 0 underflow (q < edges[0],
+ * -inf included), slot 1 + b holds edges[b] <= q < edges[b + 1], slot n_bins + 1 overflow (q >= edges[n_bins], +inf included), slot
+ * n_bins + 2 holds NaN.  The slot is the number of edges <= q, found by bisection with exact fp64 comparisons - never by arithmetic on
+ * (q - e0) / width; -0.0 compares equal to 0.0.  sx_distribution_slot is that rule on the host (pure helper, no handle and no
+ * device; the same function compiled for both).
+ * Kind.  SX_DIST_DOMAIN: one group, weight w_r w_l w_z of sx_reduce_weights: this tile's share of the patch distribution (tiles
+ * add).  SX_DIST_LEVEL: one group per level, weight w_r w_l, the horizontal area on each level: the CFAD; on a grid without a
+ * vertical it has one group and equals SX_DIST_DOMAIN.
+ * count[n_bins + 3, groups] (column-major, the slot fastest) is the number of gridpoints per slot; sums[n_bins + 3, n_out, groups] the
+ * measure and the integrals over the points of each slot.  An empty slot returns exactly 0 and +0.0.
+ * Determinism.  count is exact.  sums use no floating-point atomics: each is accumulated in double-double in an order that depends on
+ * the grid, n_bins and the slots the data falls into alone (a fixed lane tree per wave and slot, the waves of a workgroup in wave
+ * order, a fixed number of workgroups in block order): two calls on the same data agree bitwise.
+ * Refused, with a message and before anything is written: a null pointer with a non-zero count; whatever sx_reduce_planes refuses;
+ * n_out outside [1, 4]; n_bins outside [1, 64]; an edge that is NaN / Inf or not strictly above its predecessor; an unknown kind;
+ * SX_DIST_LEVEL where the bins of every level do not fit the LDS of one workgroup:
+ *     zDim (n_bins + 3) (16 n_out + 4) + 8 (n_bins + 1) > 163840 bytes (the 160 KB of one compute unit)
+ * (64 levels x 64 bins with one integrand fit, 64 levels x 40 bins with three do not).  sx_distribution_check refuses the
+ * same on the host (pure helper, no handle and no device).
+ * sx_distribution runs on the handle's stream and returns after the copy-out; it reads only: `physical`, var_np1, the tendency
+ * history, A, B, parcels and captured graphs stay as they are, and it does not run the tile transform.  Multi-tile handles are allowed.
+ * sx_kernel_bytes("k_distribution") gives the planes named x n_points x their element size of the last call. */
+enum { SX_DIST_DOMAIN = 0, SX_DIST_LEVEL = 1 };
+int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out,
+                    int32_t n_bins, const double *edges /*[n_bins + 1]*/, int64_t *count /*[n_bins + 3, groups]*/,
+                    double *sums /*[n_bins + 3, n_out, groups]*/);
+int sx_distribution_slot(int32_t n_bins, const double *edges /*[n_bins + 1]*/, double q, int32_t *slot);
+int sx_distribution_check(const sx_grid_desc *grid, int32_t kind, int32_t source, int32_t n_terms, const int32_t *terms, int32_t n_out,
+                          int32_t n_bins, const double *edges /*[n_bins + 1]*/);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

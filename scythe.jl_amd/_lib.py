@@ -16,6 +16,7 @@ SPEC_KIND = {"ring": 0, "domain": 1}             # SX_SPEC_RING / SX_SPEC_DOMAIN
 ELL_KIND = {"field": 0, "vorticity": 1, "divergence": 2}    # SX_ELL_*
 REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_AZIMUTH
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
+DIST_KIND = {"domain": 0, "level": 1}              # SX_DIST_DOMAIN / SX_DIST_LEVEL
 EXT_KIND = {"domain": 0, "azimuth": 1}           # SX_EXT_DOMAIN / SX_EXT_AZIMUTH
 EXT_WANT = {"min": -1, "any": 0, "max": 1}       # SX_EXT_MIN / SX_EXT_ANY / SX_EXT_MAX
 EXT_FREE = {"r": 1, "l": 2, "z": 4}              # SX_EXT_FREE_R / SX_EXT_FREE_L / SX_EXT_FREE_Z
@@ -139,6 +140,9 @@ SYMBOLS = {
     "sx_crossings": (C.c_int, [_H, C.c_int32, P_D, P_I32, C.c_int64, P_D, C.c_int32, P_D, C.c_double, C.c_int32, C.c_int32, P_D, P_I32, P_I32,
                                 P_I32, P_D]),
     "sx_bracket_step": (C.c_int, [P_D, P_I32, C.c_int32, C.c_double, C.c_double, P_I32]),
+    "sx_distribution": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_D, P_I64, P_D]),
+    "sx_distribution_slot": (C.c_int, [C.c_int32, P_D, C.c_double, P_I32]),
+    "sx_distribution_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_int32, P_I32, C.c_int32, C.c_int32, P_D]),
 }
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)

@@ -1,4 +1,4 @@
-// What sx_reduce (sx_reduce.hip) and sx_extrema (sx_extrema.hip) share: the integrand program as the kernels read it, the ring pieces
+// What sx_reduce (sx_reduce.hip), sx_extrema (sx_extrema.hip) and sx_distribution (sx_distribution.hip) share: the integrand program as the kernels read it, the ring pieces
 // a workgroup takes, and the loads of the planes a program names at one point.  Stated once so that the two entry points accept, pack
 // and read a program identically.
 #pragma once
@@ -44,6 +44,17 @@ __device__ inline double red_term(const RedProg &g, int t, const double (&val)[R
     for (int f = 0; f < RED_FACTORS; f++)
         if (f < nf) x *= val[g.f[t][f]];
     return x;
+}
+
+// the double-double sums of sx_reduce and sx_distribution: (hi, lo) += x, the rounding error of the sum kept in lo (Knuth's two-sum: no ordering of |hi|, |x| assumed)
+__device__ inline void dd_add(double &hi, double &lo, double x) {
+    const double s = hi + x, b = s - hi;
+    lo += (hi - (s - b)) + (x - b);
+    hi = s;
+}
+__device__ inline void dd_add(double &hi, double &lo, double xh, double xl) {
+    dd_add(hi, lo, xh);
+    lo += xl;
 }
 
 // the work list: ring pieces (grids with an azimuth) or whole rings; first [nrings + 1] = first piece of each ring.  A function of the

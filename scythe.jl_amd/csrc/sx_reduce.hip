@@ -19,7 +19,7 @@
 namespace sx {
 
 constexpr int RED_TF = 1024;        // threads per workgroup of k_reduce_final's domain sum
-// RED_T, RED_ITERS, the limits, RedProg, RedItem, the work list and the plane loads: sx_redprog.hpp (shared with sx_extrema)
+// RED_T, RED_ITERS, the limits, RedProg, RedItem, the work list, the plane loads and dd_add: sx_redprog.hpp (shared with sx_extrema, sx_distribution)
 
 struct ReduceState : DiagState {
     DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth) or whole rings
@@ -31,17 +31,6 @@ struct ReduceState : DiagState {
     DevBuf<double> d_out;
     int n_items = 0;
 };
-
-// (hi, lo) += x, the rounding error of the sum kept in lo (Knuth's two-sum: no ordering of |hi|, |x| assumed)
-__device__ inline void dd_add(double &hi, double &lo, double x) {
-    const double s = hi + x, b = s - hi;
-    lo += (hi - (s - b)) + (x - b);
-    hi = s;
-}
-__device__ inline void dd_add(double &hi, double &lo, double xh, double xl) {
-    dd_add(hi, lo, xh);
-    lo += xl;
-}
 
 // One point: load the planes, evaluate the terms.  pt < N is the caller's business.
 template <class ST>

@@ -12,10 +12,13 @@ import time
 
 import numpy as np
 
-from .model import (Grid, GridParameters, ModelParameters, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
+from .model import (Distribution, Grid, GridParameters, ModelParameters, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
 
 Located = collections.namedtuple("Located", "pos value status")
 WindRadii = collections.namedtuple("WindRadii", "thresholds azimuths radii quadrants")
+Cfad = collections.namedtuple("Cfad", "frac under over nan area edges")
+Exceedance = collections.namedtuple("Exceedance", "thresholds measure integral")
+Quantile = collections.namedtuple("Quantile", "lo hi passes nan_count measure")
 
 
 class PatchLayout:
@@ -587,6 +590,90 @@ class ModelRun:
                 take = (better | np.isnan(v[w])) & ~np.isnan(val[w])
                 val[w], idx[w] = np.where(take, v[w], val[w]), np.where(take, i[w], idx[w])
         return val, idx
+
+    def distribution(self, terms, edges, kind="domain", source="physical"):
+        """Histogram of a field program over the local tiles (Grid.distribution): Distribution(count, measure, sums, edges), the
+        counts of the tiles added exactly and their sums in tile order.  source="physical" runs tileTransform! on every local
+        tile first."""
+        total = None
+        for g in self._tiles_in_order():
+            if source == "physical":
+                g.tileTransform_()
+            d = g.distribution(terms, edges, kind, source)
+            total = d if total is None else Distribution(total.count + d.count, total.measure + d.measure, total.sums + d.sums, d.edges)
+        return total
+
+    def cfad(self, var_or_terms, edges, normalize=True, source="physical"):
+        """Contoured frequency-by-altitude diagram of a variable (name or 1-based index) or of a one-output program: Cfad(frac
+        [n_bins, zDim], under [zDim], over [zDim], nan [zDim], area [zDim], edges): per level the fraction of the horizontal area
+        whose value lies in each bin, and the fractions below edges[0], at or above edges[-1] and NaN - every column of frac sums
+        to 1 with its three outside fractions.  normalize=False returns the areas themselves.  One column on a grid without a
+        vertical."""
+        terms = var_or_terms if isinstance(var_or_terms, (list, tuple)) else [(0, 1.0, 0, [(var_or_terms, "")])]
+        d = self.distribution(terms, edges, "level", source)
+        area = d.measure.sum(axis=0)
+        m = d.measure / area[None, :] if normalize else d.measure
+        return Cfad(m[1:-2].copy(), m[0].copy(), m[-2].copy(), m[-1].copy(), area, d.edges)
+
+    def exceedance(self, terms, thresholds, integrand=None, source="physical"):
+        """Measure, and optionally integral, of {q >= c} for each of up to 65 increasing thresholds c, q the one-output program
+        `terms`: ONE Grid.distribution call per tile with the thresholds as edges, cumulative sums from the top slot down, NaN
+        points excluded.  integrand: the terms of one integrand (their `out` is ignored).  Returns Exceedance(thresholds, measure
+        [n], integral [n] or None): area on R / RL grids, volume with a vertical."""
+        thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        edges = thr if len(thr) > 1 else np.array([thr[0], np.nextafter(thr[0], np.inf)])
+        prog = [(0, c, p, f) for _, c, p, f in terms] + [(1, c, p, f) for _, c, p, f in (integrand or [])]
+        d = self.distribution(prog, edges, "domain", source)
+        top_down = np.cumsum(d.sums[-2:0:-1, :, 0], axis=0)[::-1]           # row i: slots i + 1 .. overflow
+        top_down = top_down[:len(thr)] if len(thr) > 1 else top_down[:1]
+        return Exceedance(thr, top_down[:, 0].copy(), top_down[:, 1].copy() if integrand else None)
+
+    def integrated_kinetic_energy(self, u, v, thresholds, density=1.0, source="physical"):
+        """Integrated kinetic energy above wind-speed thresholds (IKE at 18 / 26 / 33 m/s): q = u^2 + v^2 is binned at
+        thresholds^2 and 1/2 density (u^2 + v^2) integrated over {speed >= threshold} (exceedance).  Returns Exceedance(thresholds,
+        measure, integral)."""
+        thr = np.atleast_1d(np.asarray(thresholds, dtype=np.float64))
+        q = [(0, 1.0, 0, [(u, ""), (u, "")]), (0, 1.0, 0, [(v, ""), (v, "")])]
+        ke = [(1, 0.5 * float(density), 0, [(u, ""), (u, "")]), (1, 0.5 * float(density), 0, [(v, ""), (v, "")])]
+        res = self.exceedance(q, thr ** 2, ke, source)
+        return Exceedance(thr, res.measure, res.integral)
+
+    def quantile(self, terms, p, tol=1e-6, max_passes=8, source="physical"):
+        """The measure-weighted p-quantile of the one-output program `terms`, bracketed by repeated histograms: Quantile(lo, hi,
+        passes, nan_count, measure) with measure{q < lo} <= p M < measure{q < hi}, M the measure of the non-NaN points.  The first
+        edges are 64 uniform bins from the minimum to one ulp above the maximum (extrema); every later pass re-bins the slot that
+        holds p M, until hi - lo <= tol (max - min), the slot holds one point, the edges can no longer be made strictly increasing
+        or max_passes are taken.  NaN points are counted, not ranked (with a NaN present the first edges span all doubles in
+        decades instead)."""
+        val, _ = self.extrema(terms, "domain", source)
+        mn, mx = float(val[0, 0]), float(val[1, 0])
+        if np.isfinite(mn) and np.isfinite(mx):
+            edges = np.linspace(mn, np.nextafter(mx, np.inf), 65)
+            edges[0], edges[-1] = mn, np.nextafter(mx, np.inf)
+            span = mx - mn
+        else:
+            pw = 10.0 ** np.linspace(-300.0, 300.0, 32)
+            edges, span = np.concatenate([-pw[::-1], [0.0], pw]), 0.0
+        lo = hi = np.nan
+        passes = nan_count = 0
+        M = 0.0
+        while passes < max_passes and (np.diff(edges) > 0).all() and np.isfinite(edges).all():
+            d = self.distribution(terms, edges, "domain", source)
+            passes += 1
+            m, c = d.measure[:-1, 0], d.count[:-1, 0]
+            cum = np.concatenate([[0.0], np.cumsum(m)])                      # cum[k] = measure{q in a slot below k}
+            if passes == 1:
+                M, nan_count = float(cum[-1]), int(d.count[-1, 0])
+            inside = np.nonzero((cum[:-1] <= p * M) & (p * M < cum[1:]))[0]
+            k = int(inside[0]) if len(inside) else int(np.nonzero(c)[0][-1]) if c.any() else 0
+            if k < 1 or k > len(edges) - 1:                                  # outside the edges: the bracket of the pass before stands
+                break
+            lo, hi = float(edges[k - 1]), float(edges[k])
+            if hi - lo <= tol * span or c[k] == 1:
+                break
+            edges = np.linspace(lo, hi, 65)
+            edges[0], edges[-1] = lo, hi
+        return Quantile(lo, hi, passes, nan_count, M)
 
     def _one_tile(self, what):
         if self.num_tiles > 1:

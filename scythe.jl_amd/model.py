@@ -502,6 +502,27 @@ class Grid:
                                      packed.ctypes.data_as(L.P_I32), n_out, val.ctypes.data_as(L.P_D), idx.ctypes.data_as(L.P_I64)))
         return val, idx
 
+    def distribution(self, terms, edges, kind="domain", source="physical"):
+        """Histogram of a field program over the tile's gridpoints, on the device (sx_distribution).  terms, source: as for reduce
+        (packed by pack_reduce_program), 1 to 4 outputs: output 0 is the binned quantity q, outputs 1 .. 3 are integrands.  edges
+        [n_bins + 1], finite and strictly increasing, n_bins <= 64.  Slots: 0 q < edges[0], 1 + b edges[b] <= q < edges[b + 1],
+        n_bins + 1 q >= edges[-1], n_bins + 2 NaN.  kind="domain": one group, weights w_r w_l w_z (this tile's share: tiles add);
+        kind="level": one group per level, weights w_r w_l (the horizontal area).  Returns Distribution(count int64 [n_bins + 3,
+        groups], measure [n_bins + 3, groups] the sum of the weights, sums [n_bins + 3, n_out, groups] whose column 0 is the
+        measure and column j the integral of integrand j over the points of the slot, edges).  Bitwise repeatable."""
+        coef, packed, n_out = pack_reduce_program(self.patch_params, terms)
+        if kind not in L.DIST_KIND or source not in L.REDUCE_SOURCE:
+            raise ValueError("kind must be 'domain' or 'level', source 'physical' or 'state'")
+        e = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+        nb = len(e) - 1
+        groups = max(int(self.dims.zDim), 1) if kind == "level" else 1
+        count = np.zeros((max(nb, 0) + 3, groups), dtype=np.int64, order="F")
+        sums = np.zeros((max(nb, 0) + 3, max(n_out, 1), groups), order="F")
+        L.check(self._lib.sx_distribution(self._h, L.DIST_KIND[kind], L.REDUCE_SOURCE[source], len(coef), coef.ctypes.data_as(L.P_D),
+                                          packed.ctypes.data_as(L.P_I32), n_out, nb, e.ctypes.data_as(L.P_D),
+                                          count.ctypes.data_as(L.P_I64), sums.ctypes.data_as(L.P_D)))
+        return Distribution(count, sums[:, 0, :].copy(), sums, e)
+
     def refine_extremum(self, var, points, want="max", free=None, tol=None, max_iter=None):
         """The stationary point of variable `var` (a name or a 1-based index) nearest to each of `points` [n, n_coord], by Newton's
         iteration on the continuous spectral state, on the device (sx_extremum_refine; reads the A coefficients the tile holds now).
@@ -879,6 +900,30 @@ def bracket_step(state, flags, fx=0.0, width_tol=0.0, first=False):
     L.check(L.load().sx_bracket_step(s.ctypes.data_as(L.P_D), f.ctypes.data_as(L.P_I32), 1 if first else 0, float(fx), float(width_tol),
                                      C.byref(st)))
     return s, f, int(st.value)
+
+
+# ----------------------------------------------------------------------------- histograms of field programs (sx_distribution)
+Distribution = collections.namedtuple("Distribution", "count measure sums edges")
+
+
+def distribution_slot(edges, q):
+    """The slot of q among len(edges) + 2 on the host (sx_distribution_slot): 0 below edges[0], 1 + b for edges[b] <= q < edges[b + 1],
+    n_bins + 1 at or above edges[-1], n_bins + 2 for a NaN - the rule Grid.distribution's kernel applies, compiled from the same
+    function."""
+    e = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+    s = C.c_int32(-1)
+    L.check(L.load().sx_distribution_slot(len(e) - 1, e.ctypes.data_as(L.P_D), float(q), C.byref(s)))
+    return int(s.value)
+
+
+def distribution_check(patch: GridParameters, terms, edges, kind="domain", source="physical", tile_cell0=0, tile_num_cells=None):
+    """Raises what Grid.distribution would refuse of a call, on the host (sx_distribution_check)."""
+    d, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    coef, packed, n_out = pack_reduce_program(patch, terms)
+    e = np.ascontiguousarray(np.atleast_1d(edges), dtype=np.float64)
+    L.check(L.load().sx_distribution_check(C.byref(d), L.DIST_KIND[kind] if isinstance(kind, str) else int(kind),
+                                           L.REDUCE_SOURCE[source] if isinstance(source, str) else int(source), len(coef),
+                                           packed.ctypes.data_as(L.P_I32), n_out, len(e) - 1, e.ctypes.data_as(L.P_D)))
 
 
 # ----------------------------------------------------------------------------- azimuthal power and cross spectra (sx_spectrum)
