@@ -653,6 +653,56 @@ int sx_distribution_slot(int32_t n_bins, const double *edges /*[n_bins + 1]*/, d
 int sx_distribution_check(const sx_grid_desc *grid, int32_t kind, int32_t source, int32_t n_terms, const int32_t *terms, int32_t n_out,
                           int32_t n_bins, const double *edges /*[n_bins + 1]*/);
 
+/* --- vortex-centred azimuthal harmonics and wind profiles ---------------------------------------------------------------
+ * Every other azimuthal diagnostic is taken about the grid's centre; a vortex that has drifted from it mixes its symmetric part with a
+ * spurious wave 1 there.  sx_vortex_harmonics takes the harmonics about a given centre (sx_extremum_refine finds one).  RL and RLZ
+ * grids, one-tile patches.
+ * centre = (x0, y0) in the Cartesian frame x = r cos lambda, y = r sin lambda; radii[n_rho] >= 0 measured from the centre; heights[n_z]
+ * (a grid without a vertical: NULL and 0, as for sx_harmonics); n_az samples per circle at phi_j = 2 pi j / n_az:
+ *     x_j = x0 + rho cos phi_j,  y_j = y0 + rho sin phi_j,  r_j = hypot(x_j, y_j),  lambda_j = atan2(y_j, x_j) in (-pi, pi], 0 at r == 0
+ * (the rules of the parcels).  The state is summed from the A coefficients the handle holds now with the SX_EVAL_ALL_K truncation
+ * (smooth in r) and sx_evaluate's vertical series, boundary-condition classes and clamped radial cell, value slot only, and
+ *     c_k(rho_i, z_l) = (1 / n_az) sum_j f(x_j, y_j, z_l) e^{-i k phi_j},   k = 0 .. kmax,
+ * in the convention of sx_harmonics: f = Re sum_k eps_k c_k e^{i k phi}, eps_0 = 1, eps_k = 2.
+ * fields[n_fields][3] = kind, var_a, var_b (1-based), n_fields <= 8:
+ *   SX_VORTEX_SCALAR  one output, the value of var_a (var_b is ignored);
+ *   SX_VORTEX_WIND    (var_a, var_b) are the grid's radial and tangential wind (u, v); TWO outputs, the radial and the tangential wind
+ *                     about the centre: rad_j + i tan_j = (u_j + i v_j) e^{i (lambda_j - phi_j)}.  With motion = (cx, cy) the storm
+ *                     motion is subtracted, in closed form and from wave 1 alone: c_1 -= (cx - i cy) / 2 (radial), (cy + i cx) / 2
+ *                     (tangential).
+ * n_out = scalar fields + 2 wind fields, in field order, radial before tangential.  out[2 (kmax + 1), n_z, n_rho, n_out] column-major,
+ * re / im interleaved.  status[n_rho]: 0 computed; 1 the circle leaves the tile's radial extent [lo, hi], decided on the host in
+ * closed form: with d = hypot(x0, y0) and tol = 8 eps (d + rho + hi),  d + rho > hi + tol,  or  lo > 0 and |d - rho| < lo - tol  (a
+ * circle tangent to the edge is inside; a sample an ulp beyond the edge is evaluated in the clamped last cell).  Such a circle gets no
+ * workgroup and its outputs are NaN.
+ * The Fourier sum commutes with the vertical product: k_vortex_rings accumulates sum_j e^{-i k phi_j} q_j g_v[j][zm] over the vertical
+ * MODES (g_v: the sums over nodes and wavenumber blocks at sample j, one pass over 4 node rows of A for all distinct source variables
+ * of the call; e^{-i k phi_j} from an n_az-entry table formed on the host in extended precision, indexed by (k j) mod n_az), and
+ * k_vortex_finish applies the value rows of the vertical operator at the n_z heights once, to (kmax + 1) b_zDim numbers instead of
+ * n_az n_z samples.  No atomics, fixed orders that depend on the grid and on (n_az, kmax, fields) alone: a circle's result is bitwise
+ * the same alone, among other circles and in a second call, and an output's does not depend on the other fields of the call.
+ * Refused, with a message and before anything is written: a NaN or Inf in centre, motion, radii or heights; a negative radius; a height
+ * outside [zmin, zmax]; n_az < 4, not a multiple of 4, or > 4096; kmax < 0, 2 kmax >= n_az or kmax > 32; n_fields outside 1 .. 8; an
+ * unknown kind; a variable index out of range; a null pointer with a non-zero count; an R or RZ grid; a handle that is not a one-tile
+ * patch; accumulators that do not fit the 64 KB of LDS of one workgroup (n_acc = 1 per scalar, 4 per wind field; n_src = the distinct
+ * variables named):  2 (kDim + 1) + 2 n_acc (kmax + 1) b_zDim + n_src b_zDim > 8192  or  4 (kmax + 1) b_zDim > 8192 doubles.
+ * n_rho == 0 succeeds and writes nothing.
+ * Runs on the handle's stream and returns after the copy-out; reads A only (a deferred diagnostic variable is brought up to date first,
+ * as for every reader of A): `physical`, var_np1, the tendency history, the B arrays, parcels and captured graphs stay bitwise as they
+ * are.  sx_kernel_bytes("k_vortex_rings") gives the A bytes of the last call, counted per sample point as k_parcels counts them: live
+ * circles x n_az x distinct source variables x 4 rows x b_zDim x (2 kDim + 1) x 8.  Timers k_vortex_rings, k_vortex_finish.
+ *
+ * sx_vortex_check is the host statement of the same validation (everything above that a descriptor decides: not motion, not heights)
+ * and of the circle rule: n_out and status[n_rho] as the call would return them.  Pure host helper (no handle, no device). */
+enum { SX_VORTEX_SCALAR = 0, SX_VORTEX_WIND = 1 };
+int sx_vortex_harmonics(sx_handle *h, const double centre[2], const double *motion /*[2] or NULL*/,
+                        const double *radii, int32_t n_rho, const double *heights, int32_t n_z,
+                        int32_t n_az, int32_t kmax, int32_t n_fields, const int32_t *fields /*[n_fields][3]*/,
+                        double *out /*[2 (kmax + 1), n_z, n_rho, n_out] column-major, re / im interleaved*/,
+                        int32_t *status /*[n_rho]*/);
+int sx_vortex_check(const sx_grid_desc *grid, const double centre[2], const double *radii, int32_t n_rho,
+                    int32_t n_az, int32_t kmax, int32_t n_fields, const int32_t *fields, int32_t *n_out, int32_t *status);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

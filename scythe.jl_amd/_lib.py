@@ -17,6 +17,7 @@ ELL_KIND = {"field": 0, "vorticity": 1, "divergence": 2}    # SX_ELL_*
 REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_AZIMUTH
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
 DIST_KIND = {"domain": 0, "level": 1}              # SX_DIST_DOMAIN / SX_DIST_LEVEL
+VORTEX_SCALAR, VORTEX_WIND = 0, 1                # SX_VORTEX_*
 EXT_KIND = {"domain": 0, "azimuth": 1}           # SX_EXT_DOMAIN / SX_EXT_AZIMUTH
 EXT_WANT = {"min": -1, "any": 0, "max": 1}       # SX_EXT_MIN / SX_EXT_ANY / SX_EXT_MAX
 EXT_FREE = {"r": 1, "l": 2, "z": 4}              # SX_EXT_FREE_R / SX_EXT_FREE_L / SX_EXT_FREE_Z
@@ -143,6 +144,8 @@ SYMBOLS = {
     "sx_distribution": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_D, P_I64, P_D]),
     "sx_distribution_slot": (C.c_int, [C.c_int32, P_D, C.c_double, P_I32]),
     "sx_distribution_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_int32, P_I32, C.c_int32, C.c_int32, P_D]),
+    "sx_vortex_harmonics": (C.c_int, [_H, P_D, P_D, P_D, C.c_int32, P_D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_I32, P_D, P_I32]),
+    "sx_vortex_check": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_I32, P_I32, P_I32]),
 }
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)

@@ -144,7 +144,7 @@ bool build_elliptic_class(const EllBands &eb, int has_l, double xmin, int bcl, i
                           std::string &err);
 void elliptic_apply_host(const EllClass &c, int k, int nb, const double *g /*[nb]*/, double *a /*[nb]*/);
 
-// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution) ----
+// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics) ----
 template <class T>
 struct DevBuf {         // owns one device array; reads as the pointer
     T *p = nullptr;
@@ -181,7 +181,7 @@ struct DiagState {      // what one of these entry points keeps with the handle:
     double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
     virtual ~DiagState() = default;
 };
-enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
+enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
 struct EvalClasses {    // the vertical boundary-condition classes of a handle's variables (eval_classes)
     std::vector<EvalVert> vert;       // empty without a vertical
     std::vector<int> vcls;            // [V] class of each variable
@@ -507,6 +507,13 @@ constexpr int PARCEL_T = 256;             // lanes per point on grids with many 
 constexpr int PARCEL_T_SMALL = 64;        // one wave: rl_cha_bell2024's 601 columns are 10 per lane
 constexpr int PARCEL_WAVE_COLS = 1024;
 inline int parcel_threads(const sx_handle *h) { return (int64_t)h->Zb * h->K2 <= PARCEL_WAVE_COLS ? PARCEL_T_SMALL : PARCEL_T; }
+// value of the cardinal cubic B-spline (bspl of sx_setup.cpp, d = 0) as k_parcels and k_vortex_rings form it from a point's own radius
+__device__ inline double parcel_bspl(double delta) {
+    const double z = fabs(delta);
+    if (z >= 2.0) return 0.0;
+    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
+    return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
+}
 double extrema_bytes(const sx_handle *h, bool refine);   // bytes of the last sx_extrema (k_extrema) / sx_extremum_refine (k_refine)
 double crossings_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_crossings: k_ray_profiles / k_crossings (sx_crossings.hip)
 int default_bzdim(int zDim);                    // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)

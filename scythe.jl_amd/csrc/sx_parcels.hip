@@ -16,7 +16,8 @@
 
 namespace sx {
 
-// PARCEL_T, PARCEL_T_SMALL, PARCEL_WAVE_COLS and parcel_threads: sx_internal.hpp (k_refine of sx_extrema.hip takes the same lanes)
+// PARCEL_T, PARCEL_T_SMALL, PARCEL_WAVE_COLS, parcel_threads and parcel_bspl: sx_internal.hpp (k_refine of sx_extrema.hip takes the same lanes,
+// k_vortex_rings of sx_vortex.hip the same spline arithmetic)
 constexpr size_t PARCEL_LDS_MAX = 64 * 1024;
 static const double PARCEL_MAGIC = 7.7012e7;
 constexpr int PARCEL_HDR = 6;             // blob header: magic, n, n_coord, var_r, var_l, var_z
@@ -32,14 +33,6 @@ struct ParcelArgs {
     int ncoord, Zb, nz, K2, kDim, cell_lo, cell_hi, wrap;
     double xmin, DX, lo, hi, wlo, wlen, zmin, zmax, dt;
 };
-
-// value of the cardinal cubic B-spline (bspl of sx_setup.cpp, d = 0)
-__device__ inline double parcel_bspl(double delta) {
-    const double z = fabs(delta);
-    if (z >= 2.0) return 0.0;
-    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
-    return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
-}
 
 // LDS (doubles): cs [kDim + 1] double2 | t [nz] | wz [3][Zb] | red [waves][3]
 __global__ __launch_bounds__(PARCEL_T) void k_parcels(ParcelArgs a) {

@@ -16,6 +16,7 @@ from .model import (Distribution, Grid, GridParameters, ModelParameters, calcTil
 
 Located = collections.namedtuple("Located", "pos value status")
 WindRadii = collections.namedtuple("WindRadii", "thresholds azimuths radii quadrants")
+VortexProfile = collections.namedtuple("VortexProfile", "centre radii radial tangential wave1 wave2 status")
 Cfad = collections.namedtuple("Cfad", "frac under over nan area edges")
 Exceedance = collections.namedtuple("Exceedance", "thresholds measure integral")
 Quantile = collections.namedtuple("Quantile", "lo hi passes nan_count measure")
@@ -715,6 +716,43 @@ class ModelRun:
         start = self.gridpoints()[row]
         res = g.refine_extremum(var, start[None, :], "max", "r")
         return Located(res.pos[0].copy(), float(res.value[0]), int(res.status[0]))
+
+    def vortex_profile(self, wind=None, centre=None, radii=None, heights=None, kmax=2, motion=None):
+        """The wind profile of the vortex about ITS centre (Grid.vortex_harmonics): wind = (u, v), the grid's radial and tangential
+        wind by name or 1-based index (the slab and linear shallow-water sets know theirs); centre = (x0, y0), Cartesian, default
+        locate("h", "min") - the refined minimum of h; radii from the centre (default: the patch's ring radii that fit between the
+        centre and the outer edge); heights as for harmonics.  Returns VortexProfile(centre, radii, radial [n_rho, n_z], tangential
+        [n_rho, n_z]: the azimuthal means Re c_0 about the centre; wave1, wave2 [2, n_rho, n_z]: the amplitudes 2 |c_k| of the
+        radial and the tangential wind (NaN above kmax); status [n_rho]: 1 where the circle leaves the patch and the row is NaN).
+        With motion = (cx, cy) the storm motion is taken out of wave 1.  Reads the A coefficients as they stand; one-tile patches."""
+        g = self._one_tile("vortex_profile")
+        if wind is None:
+            if self.model.equation_set not in self._WIND:
+                raise ValueError("vortex_profile: name the wind variables (u, v) of equation set %r" % self.model.equation_set)
+            wind = self._WIND[self.model.equation_set]
+        if centre is None:
+            pos = self.locate("h", "min").pos
+            centre = (pos[0] * np.cos(pos[1]), pos[0] * np.sin(pos[1]))
+        centre = np.asarray(centre, dtype=np.float64).reshape(-1)
+        if radii is None:
+            DX = (self.patch.xmax - self.patch.xmin) / self.patch.num_cells
+            n = int(np.floor((self.patch.xmax - float(np.hypot(centre[0], centre[1]))) / DX))
+            radii = DX * np.arange(max(n, 0) + 1)
+        radii = np.asarray(radii, dtype=np.float64).reshape(-1)
+        c, status = g.vortex_harmonics(centre, radii, heights, [("wind", wind[0], wind[1])], kmax=kmax, motion=motion)
+        amp = [2.0 * np.abs(c[:, :, :, k]) if k <= kmax else np.full(c.shape[:3], np.nan) for k in (1, 2)]
+        return VortexProfile(centre, radii, c[0, :, :, 0].real.copy(), c[1, :, :, 0].real.copy(), amp[0], amp[1], status)
+
+    def radius_of_maximum_about(self, centre, radii, wind=None, height=None):
+        """The radius of maximum wind about `centre` = (x0, y0): the largest azimuthal-mean tangential wind (Re c_0 of
+        vortex_profile) among the given radii, at `height` on a grid with a vertical.  Returns (radius, value); circles that leave
+        the patch do not take part.  One-tile patches."""
+        p = self.vortex_profile(wind, centre, radii, None if height is None else [height], kmax=0)
+        vt = np.where(p.status == 0, p.tangential[:, 0], -np.inf)
+        if not np.isfinite(vt).any():
+            raise ValueError("radius_of_maximum_about: no circle lies inside the patch")
+        i = int(np.argmax(vt))
+        return float(p.radii[i]), float(vt[i])
 
     def _rays(self, azimuths, height):
         """[n, n_coord - 1] ray coordinates lambda[, z] of the patch's geometry from azimuths and one height"""

@@ -453,6 +453,37 @@ class Grid:
         c = out.T.view(np.complex128)                     # C-contiguous [s, v, ir, iz, 2K] -> [s, v, ir, iz, K]
         return c.transpose(2, 3, 4, 1, 0)
 
+    def vortex_harmonics(self, centre, radii, heights=None, fields=("h",), n_az=None, kmax=4, motion=None):
+        """The azimuthal harmonics of the state about `centre` = (x0, y0) in the Cartesian frame x = r cos lambda, y = r sin lambda,
+        not about the grid's centre, on the device (sx_vortex_harmonics; reads the A coefficients the tile holds now).  radii are
+        measured from the centre; heights stays None on a grid without a vertical.  fields: variable names (or 1-based indices) and
+        ("wind", u, v) triples naming the grid's radial and tangential wind; a wind field gives TWO outputs, the radial and the
+        tangential wind about the centre, with the storm motion `motion` = (cx, cy) subtracted when given.  n_az samples per circle
+        (a multiple of 4; default: the smallest multiple of 4 above kDim + kmax, which does not alias when the centre is the grid's).
+        Returns (c, status): c complex128 [n_out, n_rho, n_z, kmax + 1] with f = Re sum_k eps_k c_k e^{i k phi}, eps_0 = 1, eps_k = 2;
+        status int32 [n_rho], 0 computed, 1 the circle leaves the tile (its outputs are NaN).  One-tile RL / RLZ patches."""
+        packed, n_out = pack_vortex_fields(self.patch_params, fields)
+        r = np.ascontiguousarray(np.asarray(radii, dtype=np.float64).reshape(-1))
+        z = None if heights is None else np.ascontiguousarray(np.asarray(heights, dtype=np.float64).reshape(-1))
+        nz = 1 if z is None else len(z)
+        if n_az is None:
+            n_az = default_vortex_n_az(int(self.dims.kDim), kmax)
+        c0 = np.ascontiguousarray(np.asarray(centre, dtype=np.float64).reshape(-1))
+        if len(c0) != 2:
+            raise ValueError("centre must be (x0, y0)")
+        m = None if motion is None else np.ascontiguousarray(np.asarray(motion, dtype=np.float64).reshape(-1))
+        if m is not None and len(m) != 2:
+            raise ValueError("motion must be (cx, cy)")
+        K = max(int(kmax), 0) + 1
+        out = np.zeros((2 * K, nz, len(r), n_out), order="F")
+        status = np.zeros(len(r), dtype=np.int32)
+        L.check(self._lib.sx_vortex_harmonics(self._h, c0.ctypes.data_as(L.P_D), None if m is None else m.ctypes.data_as(L.P_D),
+                                              r.ctypes.data_as(L.P_D), len(r), None if z is None else z.ctypes.data_as(L.P_D),
+                                              0 if z is None else len(z), int(n_az), int(kmax), len(packed), packed.ctypes.data_as(L.P_I32),
+                                              out.ctypes.data_as(L.P_D), status.ctypes.data_as(L.P_I32)))
+        c = out.T.view(np.complex128)                     # C-contiguous [n_out, n_rho, n_z, 2 K] -> [n_out, n_rho, n_z, K]
+        return c, status
+
     def spectrum(self, pairs, kind="ring"):
         """Azimuthal power and cross spectra of the state on the device (sx_spectrum), from the A coefficients the tile holds now.
         pairs: a list of ((var_a, slot_a), (var_b, slot_b)), var a name or a 1-based index, slot one of u r rr z zz or 0 .. 4 (the
@@ -924,6 +955,55 @@ def distribution_check(patch: GridParameters, terms, edges, kind="domain", sourc
     L.check(L.load().sx_distribution_check(C.byref(d), L.DIST_KIND[kind] if isinstance(kind, str) else int(kind),
                                            L.REDUCE_SOURCE[source] if isinstance(source, str) else int(source), len(coef),
                                            packed.ctypes.data_as(L.P_I32), n_out, len(e) - 1, e.ctypes.data_as(L.P_D)))
+
+
+# ----------------------------------------------------------------------------- vortex-centred harmonics (sx_vortex_harmonics)
+def pack_vortex_fields(patch: GridParameters, fields):
+    """fields -> (int32 [n, 3] = kind, var_a, var_b as sx_vortex_harmonics reads them, n_out): a variable name or 1-based index is a
+    scalar field, ("wind", u, v) a wind field with two outputs; names are resolved against the patch, the rest is left to the library"""
+    fields = [fields] if isinstance(fields, (str, int, np.integer)) else list(fields)
+    if len(fields) == 3 and fields[0] == "wind" and "wind" not in patch.vars:
+        fields = [tuple(fields)]
+
+    def var(v, i):
+        if isinstance(v, str) and v not in patch.vars:
+            raise ValueError("field %d: unknown variable %r" % (i, v))
+        return patch.vars[v] if isinstance(v, str) else int(v)
+
+    packed = np.zeros((len(fields), 3), dtype=np.int32)
+    n_out = 0
+    for i, f in enumerate(fields):
+        if isinstance(f, (tuple, list)):
+            if len(f) != 3 or f[0] != "wind":
+                raise ValueError("field %d is neither a variable nor ('wind', u, v)" % i)
+            packed[i] = L.VORTEX_WIND, var(f[1], i), var(f[2], i)
+            n_out += 2
+        else:
+            packed[i] = L.VORTEX_SCALAR, var(f, i), 0
+            n_out += 1
+    return packed, n_out
+
+
+def default_vortex_n_az(kDim, kmax):
+    """the smallest multiple of 4 above kDim + kmax: the state holds wavenumbers up to kDim, so about the grid's own centre no
+    harmonic k <= kmax is aliased"""
+    return 4 * ((int(kDim) + max(int(kmax), 0)) // 4 + 1)
+
+
+def vortex_check(patch: GridParameters, centre, radii, fields=("h",), n_az=16, kmax=4, tile_cell0=0, tile_num_cells=None):
+    """What Grid.vortex_harmonics would do with a call, on the host (sx_vortex_check: no handle, no device): raises what it refuses
+    of the grid, the centre, the radii, n_az, kmax and the fields; returns (n_out, status int32 [n_rho]) with the circle rule."""
+    d, keep = grid_desc(patch, tile_cell0, tile_num_cells)
+    packed, _ = pack_vortex_fields(patch, fields)
+    r = np.ascontiguousarray(np.asarray(radii, dtype=np.float64).reshape(-1))
+    c0 = np.ascontiguousarray(np.asarray(centre, dtype=np.float64).reshape(-1))
+    if len(c0) != 2:
+        raise ValueError("centre must be (x0, y0)")
+    status = np.zeros(len(r), dtype=np.int32)
+    n_out = C.c_int32(-1)
+    L.check(L.load().sx_vortex_check(C.byref(d), c0.ctypes.data_as(L.P_D), r.ctypes.data_as(L.P_D), len(r), int(n_az), int(kmax),
+                                     len(packed), packed.ctypes.data_as(L.P_I32), C.byref(n_out), status.ctypes.data_as(L.P_I32)))
+    return int(n_out.value), status
 
 
 # ----------------------------------------------------------------------------- azimuthal power and cross spectra (sx_spectrum)
