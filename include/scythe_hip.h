@@ -162,6 +162,14 @@ int sx_calc_tile_sizes(const sx_grid_desc *patch, int32_t n_tiles, double *out);
 int sx_cheb_column_ops(double zmin, double zmax, int32_t zDim, int32_t b_zDim, int32_t bcb, int32_t bct, double *z,
                        double *rec, double *dz, double *dzz, double *integ);
 
+/* The two operators of semiimplicit_adjustment's column solve (src/semiimplicit.jl:586-595, 768-781) exactly as sx_create builds
+ * them for a model with these levels, vertical boundary conditions of w, Pxi_bar and tau (0.5 ts at t = 1, 1.25 ts after): W maps the
+ * right-hand side g to the values of w, X to dw/dz; dense [zDim x zDim] row-major.  The Helmholtz matrix is inverted in extended
+ * precision and rounded once, so two assemblies agree to cond(H) x 2^-64 only, not to the last bit: a host-side check of the
+ * semi-implicit kernels has to read the operators the device holds, which are these.  Pure host helper; either output may be NULL. */
+int sx_semi_column_ops(double zmin, double zmax, int32_t zDim, int32_t b_zDim, int32_t bcb, int32_t bct, double pxi_bar, double tau,
+                       double *W, double *X);
+
 /* splineTransform!'s arithmetic for ONE right-hand side on the host, two ways: through the parallel-cyclic-reduction tables the
  * device kernel k_solve_pcr applies (csrc/sx_pcr.hip: elimination blocks of the constant matrix Gamma (P + eps_q Q) Gamma^T worked
  * out once in extended precision, applied level by level in double) and through the banded Cholesky factors the serial kernel
@@ -257,7 +265,11 @@ int sx_advance(sx_handle *h, int32_t t);
  * stream and the B buffers' pointers: sx_set_stream (to another stream), sx_bind_tile_b (to another buffer) and sx_bind_patch_b drop
  * them, and the next sx_step captures again. */
 int sx_step(sx_handle *h, int32_t t);
-/* physical_model only (src/semiimplicit.jl:357-363) on the current tile.physical */
+/* physical_model only (src/semiimplicit.jl:357-363) on the current tile.physical.
+ * What the call covers: the equation set's tendency and the explicit step (Euler at t = 1, AB2 at t = 2, AB3 from t = 3) into
+ * var_np1, then the semi-implicit adjustment where the model has it and condensation_adjustment for rainfall_test, in that order.
+ * The shallow-water sets also write their diagnostic w into physical[:, 6, 1] (1-based); no other plane of `physical` changes.
+ * t = 1 restarts the tendency history. */
 int sx_physics(sx_handle *h, int32_t t);
 /* checkCFL (src/semiimplicit.jl:737-751): flag = 1 if any NaN in the model state (scans var_np1, which every
  * sx_advance / sx_set_physical_values leaves complete; a NaN in physical[:, v, 1] always reaches it) */

@@ -233,12 +233,24 @@ class Cheb:
             proj = proj - Cm.T @ Gi @ Cm
         CAx = proj @ pad                                # b -> a
         f64 = lambda m: np.asarray(m, dtype=np.float64)
-        self._x = dict(T=Tx, Dc=Dcx, TD=TDx, TDD=TDDx, CA=CAx, CB=CBx)   # extended-precision factors (Helmholtz assembly, inverse_xp)
+        self._x = dict(T=Tx, Dc=Dcx, TD=TDx, TDD=TDDx, CA=CAx, CB=CBx, Ic=Ic)   # extended-precision factors (Helmholtz assembly, inverse_xp)
         self.T, self.Dc, self.CBm, self.CAm, self.Ic = f64(Tx), f64(Dcx), f64(CBx), f64(CAx), f64(Ic)
         self.M = [f64(Tx @ CAx), f64(TDx @ CAx), f64(TDDx @ CAx)]       # b -> values, d/dz, d2/dz2
         self.Mint = f64(Tx @ Ic @ CAx)                                     # b -> integral from the bottom
         # full column operators values -> values (CB, CA, then CI / CIx / CIInt), products taken before rounding
         self.Vrec, self.Vdz, self.Vint = f64(Tx @ CAx @ CBx), f64(TDx @ CAx @ CBx), f64(Tx @ Ic @ CAx @ CBx)
+        self._xops = {}
+
+    def op(self, name, dtype=np.float64):
+        """Column operator values -> values ("Vrec", "Vdz", "Vint") in the precision of the data it is applied to: the Float64
+        matrix (products taken in extended precision, rounded once) or, for longdouble data, the unrounded product itself."""
+        if np.dtype(dtype) != np.dtype(XP):
+            return getattr(self, name)
+        if name not in self._xops:
+            x = self._x
+            left = dict(Vrec=x["T"], Vdz=x["TD"], Vint=x["T"] @ x["Ic"])[name]
+            self._xops[name] = left @ x["CA"] @ x["CB"]
+        return self._xops[name]
 
     # dense collocation matrices used by calc_Helmholtz_semiimplicit_matrix (src/semiimplicit.jl:772-775)
     def dct_matrix(self):
@@ -632,10 +644,17 @@ def inverse_extended(H):
     return A[:, n:]
 
 
-def semi_matrices(ch, pxi_bar, tau):
-    """g -> w values (T H^-1) and g -> dw/dz values (T Dc H^-1) as double matrices."""
-    Hinv = inverse_extended(helmholtz_matrix(ch, pxi_bar, tau, extended=True))
-    return np.asarray(ch._x["T"] @ Hinv, dtype=np.float64), np.asarray(ch._x["TD"] @ Hinv, dtype=np.float64)
+def semi_matrices(ch, pxi_bar, tau, dtype=np.float64):
+    """g -> w values (T H^-1) and g -> dw/dz values (T Dc H^-1) as double matrices; for longdouble data the unrounded
+    extended-precision products.  The inverse is kept per (pxi_bar, tau) on the column."""
+    key = (XP(pxi_bar), XP(tau))
+    cache = ch.__dict__.setdefault("_semi", {})
+    if key not in cache:
+        Hinv = inverse_extended(helmholtz_matrix(ch, pxi_bar, tau, extended=True))
+        cache[key] = (ch._x["T"] @ Hinv, ch._x["TD"] @ Hinv)
+    if np.dtype(dtype) == np.dtype(XP):
+        return cache[key]
+    return tuple(np.asarray(m, dtype=np.float64) for m in cache[key])
 
 
 # ----------------------------------------------------------------------------- moist thermodynamics (Euler_test, rainfall_test)
@@ -649,9 +668,32 @@ TH["rho_d0"] = 100.0 * TH["p_0"] / (TH["T_0"] * TH["Rd"])
 TH["rho_v0"] = 100.0 * (6.112 * np.exp(17.67 * (TH["T_0"] - 273.15) / ((TH["T_0"] - 273.15) + 243.5))) / (TH["T_0"] * TH["Rv"])
 
 
+# Data-dependent branches: with BRANCHES a list, every branch of the equation sets appends the quantity whose sign decides it (the
+# margin), in evaluation order; tests/physics.py reads it to tell which points sit too close to a branch to have one expected value.
+# The max(q, 0) clamps of th_collection, th_f_ventilation, th_rain_evaporation and th_sedimentation are not logged: q there is a
+# product of non-negative factors, the clamp is continuous, and a flip moves the result by no more than the margin.
+BRANCHES = None
+
+
+# Rounded intermediates: exp, sqrt and pow results that the sets later subtract from one another (rho_t - rhobar is
+# exp(xi + xibar) (1 + q_v) - exp(xibar) (1 + q_vbar): xibar cancels in the exact result, its rounding does not).  With INTERMEDIATE a
+# callable, each such result passes through it (tests/physics.py perturbs them one at a time, as it does the inputs).
+INTERMEDIATE = None
+
+
+def _v(x):
+    return x if INTERMEDIATE is None else INTERMEDIATE(x)
+
+
+def _br(cond, margin):
+    if BRANCHES is not None:
+        BRANCHES.append(np.asarray(margin))
+    return cond
+
+
 def th_ahyp(mu):                                       # src/thermodynamics.jl:190-198
     q0 = TH["q0"]
-    return np.where(mu < 0.0, 0.0, np.sqrt(mu * mu + q0 * q0) + mu - q0)
+    return _v(np.where(_br(mu < 0.0, mu), 0.0, np.sqrt(mu * mu + q0 * q0) + mu - q0))
 
 
 def th_dmudq(mu, q_v):                                 # :200-203
@@ -659,7 +701,7 @@ def th_dmudq(mu, q_v):                                 # :200-203
 
 
 def th_dry_density(xi):                                # :205-208
-    return TH["rho_d0"] * np.exp(xi)
+    return _v(TH["rho_d0"] * np.exp(xi))
 
 
 def th_temperature(s, rho_d, q_v):                     # :67-80  (L_v(T_0) = L_v0, :41-44)
@@ -668,7 +710,7 @@ def th_temperature(s, rho_d, q_v):                     # :67-80  (L_v(T_0) = L_v
         qf = np.where(q_v != 0.0, (rho_d * q_v / TH["rho_v0"]) ** ((q_v * TH["Rv"]) / Cf), 1.0)
     rf = (rho_d / TH["rho_d0"]) ** (TH["Rd"] / Cf)
     Tf = np.exp((s - (q_v * TH["L_v0"] / TH["T_0"])) / Cf)
-    return TH["T_0"] * Tf * rf * qf
+    return _v(TH["T_0"] * Tf * rf * qf)
 
 
 def th_P_s(Tk, rho_d, q_v):                            # :215-219
@@ -754,14 +796,14 @@ def th_invtau_condensation(Tk, p, N_c, r_c):           # src/microphysics.jl:126
 
 def jl_min(x, y):
     """Julia's scalar min on Float64, elementwise: NaN propagates, -0.0 < 0.0."""
-    x, y = np.broadcast_arrays(np.asarray(x, float), np.asarray(y, float))
-    pick_y = (y < x) | (np.signbit(y) & ~np.signbit(x))
+    x, y = np.broadcast_arrays(np.asarray(x), np.asarray(y))
+    pick_y = _br((y < x) | (np.signbit(y) & ~np.signbit(x)), y - x)
     return np.where(pick_y, np.where(np.isnan(x), x, y), np.where(np.isnan(y), y, x))
 
 
 def jl_max(x, y):
-    x, y = np.broadcast_arrays(np.asarray(x, float), np.asarray(y, float))
-    pick_y = (y > x) | (~np.signbit(y) & np.signbit(x))
+    x, y = np.broadcast_arrays(np.asarray(x), np.asarray(y))
+    pick_y = _br((y > x) | (~np.signbit(y) & np.signbit(x)), y - x)
     return np.where(pick_y, np.where(np.isnan(x), x, y), np.where(np.isnan(y), y, x))
 
 
@@ -782,11 +824,11 @@ def th_s_condensation(q_cond, Tk, rho_d, q_v, q_l, p):    # src/microphysics.jl:
 
 def th_autoconversion(q_c, rho_d):                     # src/microphysics.jl:197-206
     q = 0.001 * (q_c - 0.001)
-    return np.where(q < 0.0, 0.0, q)
+    return np.where(_br(q < 0.0, q), 0.0, q)
 
 
 def th_f_ice(Tk):                                      # src/microphysics.jl:219-227
-    return np.where(Tk < 273.15, 0.2 + 0.8 * (1.0 / np.cosh((273.15 - Tk) / 5.0)), 1.0)
+    return np.where(_br(Tk < 273.15, Tk - 273.15), 0.2 + 0.8 * (1.0 / np.cosh((273.15 - Tk) / 5.0)), 1.0)
 
 
 def th_collection(q_c, q_r, rho_d, Tk):                # src/microphysics.jl:208-217
@@ -810,13 +852,14 @@ def th_sedimentation(q_r, rho_d, Tk):                  # src/microphysics.jl:252
     return np.where(Vt < 0.0, 0.0, Vt)
 
 
-def sedimentation_flux(grid, q_r, rho_d, Tk):
+def sedimentation_flux(grid, q_r, rho_d, Tk, colop=None):
     """Vt_flux = CIx(q_r .* Vt) ./ rho_d through the mu_r column's filtered Chebyshev derivative (src/testModels.jl:521-528);
     zero for every finite state (the library drops it)."""
     nz = grid.zDim
     Vt = th_sedimentation(q_r, rho_d, Tk)
     col = (q_r * Vt).reshape(-1, nz)
-    return (col @ grid.cheb("mu_r").Vdz.T).reshape(-1) / rho_d
+    M = grid.cheb("mu_r").op("Vdz", col.dtype)
+    return (colop("Vdz", M, col) if colop else col @ M.T).reshape(-1) / rho_d
 
 
 def thermo_state(s, xi, mu, mu_c, mu_r, sbar, xibar, mubar):
@@ -853,7 +896,7 @@ def column_isless(a, b):
     diff = ~_isequal(a, b)
     first = np.argmax(diff, axis=1)
     rows = np.arange(a.shape[0])
-    return diff.any(axis=1) & _isless(a[rows, first], b[rows, first])
+    return _br(diff.any(axis=1) & _isless(a[rows, first], b[rows, first]), a[rows, first] - b[rows, first])
 
 
 def column_min(x, y):
@@ -896,13 +939,18 @@ def rain_rates(grid, par, phys):
     return rates
 
 
-def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
+def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None, trig=None):
     """Pointwise tendencies of the in-scope equation sets. phys [N,V,D]; returns (expdot [N,V], impdot [N,V] or None, phys)
     (phys is returned because the shallow-water sets overwrite the diagnostic w in slot 1).  rainfall_test puts its
-    microphysical rates into `rates` if given (rain_rates)."""
+    microphysical rates into `rates` if given (rain_rates).
+    Everything is computed in phys.dtype: Float64 as the model runs, or numpy longdouble (the column operators then are the
+    unrounded extended-precision products, Cheb.op).  col_ops(name, M, x) -> x @ M.T replaces the application of the column
+    operator `name` to the columns x [ncol, nz]; trig = (cos lambda, sin lambda) per column replaces the ones taken of pts."""
     N = phys.shape[0]
-    E = np.zeros((N, grid.V))
+    dt = phys.dtype
+    E = np.zeros((N, grid.V), dtype=dt)
     I = None
+    colop = col_ops or (lambda name, M, x: x @ M.T)
     P = lambda v, s: phys[:, v - 1, grid.slots.index(s)]
     if eq == "LinearAdvection1D":                       # src/testModels.jl:1-20
         E[:, 0] = -(par["c_0"] * P(1, "r")) + (par["K"] * P(1, "rr"))
@@ -926,7 +974,7 @@ def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
         U = 0.78 * np.sqrt((ub * ub) + (vb * vb))
         w = -Hb * ((ub / r) + ubr + (vbl / r))
         phys[:, 5, 0] = w
-        w_ = 0.5 * np.abs(w) - w
+        w_ = 0.5 * np.abs(_br(w, w)) - w
         E[:, 0] = ((-vg * hl / r) + (-ug * hr)) + (-(Hfree + h) * ((ug / r) + ugr + (vgl / r)))
         if eq.startswith("Twoway"):
             E[:, 0] += -(Hfree + h) * w * par["S1"]
@@ -941,8 +989,8 @@ def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
     elif eq == "Oneway_ShallowWater_HeightResolvedBL":   # src/shallowWaterModels.jl:346-511
         nz = grid.zDim
         ch = grid.cheb("h")                              # "h" carries no vertical BC (ref :422-425)
-        Mint = ch.Vint
-        Mdz = ch.Vdz
+        Mint = ch.op("Vint", dt)
+        Mdz = ch.op("Vdz", dt)
         colv = lambda a: a.reshape(-1, nz)
         r, lam, z = colv(pts[:, 0]), colv(pts[:, 1]), colv(pts[:, 2])
         g, Kh, Cd0, Hfree, f, Um, Vm = (par[k] for k in ("g", "Kh", "Cd", "Hfree", "f", "Um", "Vm"))
@@ -955,18 +1003,19 @@ def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
         S = np.sqrt((ubz * ubz) + (vbz * vbz))
         l = 1.0 / ((1.0 / (0.4 * z)) + (1.0 / 80.0))
         Kv = (l ** 2) * S
-        wb = (-((ub / r) + ubr + (vbl / r))) @ Mint.T
+        wb = colop("Vint", Mint, -((ub / r) + ubr + (vbl / r)))
         phys[:, 5, 0] = wb.reshape(-1)
-        sfcu = (Um * np.cos(lam[:, 0])) + (Vm * np.sin(lam[:, 0]))
-        sfcv = (Vm * np.cos(lam[:, 0])) - (Um * np.sin(lam[:, 0]))
+        cosl, sinl = (np.cos(lam[:, 0]), np.sin(lam[:, 0])) if trig is None else trig
+        sfcu = (Um * cosl) + (Vm * sinl)
+        sfcv = (Vm * cosl) - (Um * sinl)
         u10, v10 = ub[:, 1] + sfcu, vb[:, 1] + sfcv
         U10 = np.sqrt(u10 ** 2 + v10 ** 2)
-        Cd = np.where(U10 < 5.2, 1.0e-3, np.where(U10 < 33.6, 4.4e-4 * U10 ** 0.5, Cd0))
+        Cd = np.where(_br(U10 < 5.2, U10 - 5.2), 1.0e-3, np.where(_br(U10 < 33.6, U10 - 33.6), 4.4e-4 * U10 ** 0.5, Cd0))
         fu = Kv * ubz
         fu[:, 0] = Cd * U10 * u10
         fv = Kv * vbz
         fv[:, 0] = Cd * U10 * v10
-        VDu, VDv = fu @ Mdz.T, fv @ Mdz.T
+        VDu, VDv = colop("Vdz", Mdz, fu), colop("Vdz", Mdz, fv)
         E4 = ((-vb * ubl / r) + (-ub * ubr) + (-wb * ubz)) + (-g * hr) + (vb * (f + (vb / r))) + VDu \
             + (Kh * ((ubr / r) + ubrr - (ub / (r * r)) + (ubll / (r * r)) - (2.0 * vbl / (r * r))))
         E5 = ((-vb * vbl / r) + (-ub * vbr) + (-wb * vbz)) + (-g * (hl / r)) + (-ub * (f + (vb / r))) + VDv \
@@ -984,7 +1033,7 @@ def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
         u, w = P(4, "u"), P(5, "u")
         adv = lambda v: (-u * P(v, "r")) + (-w * P(v, "z"))
         dif = lambda v: K * (P(v, "rr") + P(v, "zz"))
-        I = np.zeros((N, grid.V))
+        I = np.zeros((N, grid.V), dtype=dt)
         E[:, 0] = adv(1) + dif(1)
         E[:, 1] = adv(2) - P(4, "r") - P(5, "z")
         I[:, 1] = -P(5, "z")
@@ -1011,7 +1060,7 @@ def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
         rhobar = th_dry_density(xibar) * (1.0 + th_ahyp(mubar))
         rho_p = rho_t - rhobar
         dif = lambda v: K * (P(v, "rr") + P(v, "zz"))
-        I = np.zeros((N, grid.V))
+        I = np.zeros((N, grid.V), dtype=dt)
         E[:, 0] = ((-u * P(1, "r")) + (-w * (P(1, "z") + sbar_z))) + dif(1)
         E[:, 1] = ((-u * P(2, "r")) + (-w * (P(2, "z") + xibar_z))) - P(4, "r") - P(5, "z")
         I[:, 1] = -P(5, "z")
@@ -1057,10 +1106,10 @@ def tendency(grid, eq, par, phys, pts, col_ops=None, rates=None):
         qss_cond = th_dqsdp(Tk, p, rho_d, q_v, q_l) * ((u * dpdx) + (w * (dpdz - rhobar * TH["gravity"]))) - qss * (cloudtau + raintau)
         q_auto = th_autoconversion(q_c, rho_d)
         q_coll = th_collection(q_c, q_r, rho_d, Tk)
-        Vt_flux = sedimentation_flux(grid, q_r, rho_d, Tk)
+        Vt_flux = sedimentation_flux(grid, q_r, rho_d, Tk, colop)
         adv = lambda v, bar_z=0.0: (-u * P(v, "r")) + (-w * (P(v, "z") + bar_z))
         dif = lambda v: K * (P(v, "rr") + P(v, "zz"))
-        I = np.zeros((N, grid.V))
+        I = np.zeros((N, grid.V), dtype=dt)
         E[:, 0] = adv(1, R["sbar_z"]) + (s_cond + s_div) + dif(1)
         E[:, 1] = adv(2, R["xibar_z"]) + (-P(4, "r") - P(5, "z"))
         I[:, 1] = -P(5, "z")
@@ -1134,7 +1183,7 @@ class Model:
             if t == 1:
                 hs["e1"] = np.zeros_like(E)
                 hs["e2"] = np.zeros_like(E)
-            unp1, hs["e1"], hs["e2"] = explicit_timestep(t, self.ts, phys[:, :, 0], E, hs["e1"], hs["e2"])
+            unp1, hs["e1"], hs["e2"] = explicit_timestep(t, self._ts(E.dtype), phys[:, :, 0], E, hs["e1"], hs["e2"])
             if self.semi:
                 unp1 = self._semiimplicit(i, t, unp1, I)
             if self.eq == "rainfall_test":
@@ -1143,9 +1192,18 @@ class Model:
             g.add_tile_to_shared(shared, b, c0, n, i == len(self.tiles) - 1)
         self.A = g.spline_transform(shared)                                  # splineTransform!
 
+    def _ts(self, dtype):
+        """The time step in the precision of the data it multiplies (the Float64 model: the Python float, as ever)."""
+        return self.ts if np.dtype(dtype) == np.float64 else np.dtype(dtype).type(self.ts)
+
+    col_ops = None      # tendency()'s hook, for the column operators of _semiimplicit
+    semi_ops = None     # (W, X) at t = 1 and (W, X) after, given: the operators another implementation holds, instead of semi_matrices
+
     def _semiimplicit(self, i, t, unp1, impdot):
-        """semiimplicit_adjustment (src/semiimplicit.jl:521-597), all columns of tile i at once."""
-        g, ts, hs = self.g, self.ts, self.hist[i]
+        """semiimplicit_adjustment (src/semiimplicit.jl:521-597), all columns of tile i at once, in unp1.dtype."""
+        g, ts, hs = self.g, self._ts(unp1.dtype), self.hist[i]
+        dt = unp1.dtype
+        colop = self.col_ops or (lambda name, M, x: x @ M.T)
         nz = g.zDim
         wi, xi = g.vars["w"] - 1, g.vars["xi"] - 1
         I_n = impdot
@@ -1170,8 +1228,8 @@ class Model:
             star[v] = x.reshape(-1, nz)
         hs["i2"], hs["i1"] = I1.copy(), I_n.copy()
         chx, chw = g.cheb(g.names[xi]), g.cheb(g.names[wi])
-        xi_star = star[xi] @ chx.Vrec.T
-        xi_star_z = tau * self.pxi * (star[xi] @ chx.Vdz.T)
+        xi_star = colop("Vrec", chx.op("Vrec", dt), star[xi])
+        xi_star_z = tau * self.pxi * colop("Vdz", chx.op("Vdz", dt), star[xi])
         gg = xi_star_z - star[wi]
         rhs = np.zeros_like(gg)
         rhs[:, 2:] = gg[:, 1:nz - 1]
@@ -1180,8 +1238,9 @@ class Model:
                 self._lu[tau] = HelmholtzLU(chw, self.pxi, tau)
             w_val, w_z = self._lu[tau].solve(rhs)
         else:
-            W, X = semi_matrices(chw, self.pxi, tau)
-            w_val, w_z = rhs @ W.T, rhs @ X.T
+            W, X = semi_matrices(chw, self.pxi, tau, dt) if self.semi_ops is None else \
+                (np.asarray(m, dtype=dt) for m in self.semi_ops[0 if t == 1 else 1])
+            w_val, w_z = colop("W", W, rhs), colop("X", X, rhs)
         out[:, wi] = w_val.reshape(-1)
         out[:, xi] = (xi_star - tau * w_z).reshape(-1)
         return out

@@ -73,6 +73,7 @@ SYMBOLS = {
     "sx_get_physical": (C.c_int, [_H, P_D]),
     "sx_get_var_np1": (C.c_int, [_H, P_D]),
     "sx_cheb_column_ops": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_D, P_D, P_D, P_D, P_D]),
+    "sx_semi_column_ops": (C.c_int, [C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, P_D, P_D]),
     "sx_index_map_sizes": (C.c_int, [_H, P_I64, P_I64]),
     "sx_index_maps": (C.c_int, [_H, P_I64, P_I64, P_I64, P_I64]),
     "sx_state_size": (C.c_int, [_H, P_I64]),

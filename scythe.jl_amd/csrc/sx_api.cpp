@@ -764,6 +764,20 @@ int sx_cheb_column_ops(double zmin, double zmax, int32_t zDim, int32_t b_zDim, i
     return 0;
 }
 
+int sx_semi_column_ops(double zmin, double zmax, int32_t zDim, int32_t b_zDim, int32_t bcb, int32_t bct, double pxi_bar, double tau,
+                       double *W, double *X) {
+    clear_error();
+    if (zDim < 4 || !(zmax > zmin)) { set_error("sx_semi_column_ops: need zDim >= 4 and zmax > zmin"); return 1; }
+    const int Zb = b_zDim > 0 ? std::min(b_zDim, zDim) : std::min(zDim, (2 * zDim - 1) / 3 + 1);
+    ChebOps o;
+    std::string err;
+    std::vector<double> w, x;
+    if (!build_cheb_ops(zmin, zmax, zDim, Zb, bcb, bct, o, err) || !build_helmholtz(o, pxi_bar, tau, w, x, err)) { set_error(err); return 1; }
+    if (W) std::copy(w.begin(), w.end(), W);
+    if (X) std::copy(x.begin(), x.end(), X);
+    return 0;
+}
+
 int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_q, int32_t bcl, int32_t bcr, const double *b,
                           double *a_pcr, double *a_chol, int32_t *levels) {
     clear_error();

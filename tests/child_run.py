@@ -7,7 +7,7 @@ run_in_child(tmp_path, job, overrides): the child is `python -m tests.child_run 
 to the .npz; the parent compares them with run_job(job) in its own process and with the oracle.  A child that dies on a signal or
 hangs ends the whole session (pytest.exit): after a crashed or hung GPU process nothing more may start on the GPU.
 
-A job is JSON: {"kind": "spline" | "rz_transforms" | "model" | "forward", "cases": [[maker, kwargs, grid overrides(, storage)],
+A job is JSON: {"kind": "spline" | "rz_transforms" | "model" | "forward" | "physics" (tests/physics.py: {"kind", "id"}), "cases": [[maker, kwargs, grid overrides(, storage)],
 ...], "steps": n} with `maker` a function of tests/cases.py and `storage` a GridParameters.storage (default "f64")."""
 import json
 import os
@@ -38,6 +38,9 @@ def run_job(job):
     import scythe_jl_amd as S
     from tests import cases
     out = {}
+    if job["kind"] == "physics":             # sx_physics at t = 1..4 on the case tests/physics.py names (test_gpu_physics.py)
+        from tests import physics
+        return physics.device_run(job["id"])
     for i, spec in enumerate(job["cases"]):
         case = make_case(spec)
         if job["kind"] == "spline":          # splineTransform! on random B (tests/test_gpu_solve.py)
