@@ -715,6 +715,68 @@ int sx_vortex_harmonics(sx_handle *h, const double centre[2], const double *moti
 int sx_vortex_check(const sx_grid_desc *grid, const double centre[2], const double *radii, int32_t n_rho,
                     int32_t n_az, int32_t kmax, int32_t n_fields, const int32_t *fields, int32_t *n_out, int32_t *status);
 
+/* --- statistics of field programs over time: swaths, means, totals ------------------------------------------------------
+ * Per-gridpoint accumulators that live with the handle and are updated on the device, one kernel (k_stats) per sample: the
+ * maximum-wind swath (the largest wind speed each gridpoint has seen, and when), accumulated fields, time means and eddy covariances
+ * over a window, the duration for which a point stayed above a threshold - without pulling `physical` or var_np1 to the host.
+ * A statistics set is a program plus one operation per output.  The program is exactly sx_reduce's (the same terms[n_terms][11], coef
+ * and limits, SX_REDUCE_PHYSICAL / SX_REDUCE_STATE with their slot rules, validated by sx_reduce_planes itself: whatever sx_reduce
+ * refuses is refused here); op[o] belongs to output o < n_out <= 16.  The value of output o at a gridpoint is q_o as sx_extrema forms
+ * it: plain fp64, the terms added in term order starting from +0.0, r^p formed as r, r r, 1 / r or 1 / (r r), the factors multiplied
+ * in order; with storage_f32 the derivative slots are read in the type they are stored in.
+ * A sample is one call sx_stats_accumulate(h, time, weight).  At every gridpoint of the tile and for every output it updates two
+ * doubles, acc[o][2][N] on the device with the point fastest:
+ *   SX_STAT_SUM       (hi, lo)       the double-double sum of weight q: the rounding error of the product is recovered with an fma
+ *                                    (ph = w q, pl = fma(w, q, -ph)) and the pair is added with the two-sum of sx_reduce.  Skipped when
+ *                                    weight == 0.
+ *   SX_STAT_MAX / MIN (value, time)  the running extremum of q and the `time` of the sample that set it.  A later sample replaces the
+ *                                    pair only when its q is strictly greater (MAX) / smaller (MIN): a tie, -0.0 == +0.0 included,
+ *                                    keeps the earlier sample.  A NaN comes before every number (sx_extrema's order): once q is NaN
+ *                                    at a point the pair stays (NaN, time of the first NaN sample).
+ *   SX_STAT_DURATION  (hi, lo)       the double-double sum of weight over the samples with q >= threshold[o], an exact fp64
+ *                                    comparison (a NaN q is not counted).  Skipped when weight == 0.
+ * weight == 0 is the "extrema only" sample: it takes the initial state into a swath without giving it a time weight.  time and
+ * weight must be finite; a negative weight is allowed.
+ * The handle also counts the samples and keeps the double-double sum of the weights (elapsed) and the first and last time.
+ * Empty.  Before the first sample SUM and DURATION pairs are (+0.0, +0.0) and MAX / MIN pairs are (NaN, NaN).  Every point gets every
+ * sample, so one counter per set tells the two NaNs apart: samples == 0 means "empty"; with samples > 0 a NaN value means "q was NaN",
+ * and its time is then a finite sample time.
+ * Nothing is summed across points, there are no atomics: a point's result depends on that point's own sequence of (q, time, weight)
+ * alone, bitwise, not on the launch shape, the other points, the other outputs of the set or the tiling of the patch.
+ *
+ * sx_stats_set validates, packs the program and allocates n_out x 2 x N doubles; all accumulators and counters start empty.  A new set
+ * replaces an old one; n_out == 0 removes the set and frees its memory (the other arguments are then not read).  threshold[n_out] is
+ * read for DURATION outputs only and may be NULL when there is none.
+ * sx_stats_reset keeps the program and empties accumulators and counters (windowed means, hourly totals); without a set it does nothing.
+ * sx_stats_accumulate enqueues ONE kernel on the handle's stream and returns: no allocation, no copy, no synchronisation, no transform.
+ * It reads the planes the program names and reads and writes the accumulators only: `physical`, var_np1, the tendency history, A, the B
+ * arrays, parcels and captured graphs stay bitwise as they are.  With SX_REDUCE_PHYSICAL the caller has run sx_tile_transform, exactly
+ * as for sx_reduce.  It is no part of sx_step's captured graph.  Without a set the call succeeds and launches nothing.
+ * sx_stats_get synchronises and copies out[N, n_out, 2] column-major (the point fastest, then the output, then the slot) and
+ * info[5] = samples, elapsed hi, elapsed lo, first time, last time (the times NaN without a sample); info may be NULL.  In the copy
+ * only, slot 0 of a SUM / DURATION output is hi + lo rounded once and slot 1 the stored lo; the stored pair stays a pair.
+ * sx_stats_describe returns the attached set's source, n_out (0 without a set: nothing else is written), op[16] and threshold[16] (the
+ * first n_out entries; a threshold is 0 where the op has none), so that a restart can be checked; any output pointer may be NULL.
+ * sx_stats_get_state / sx_stats_set_state: program, ops, thresholds, counters and the raw accumulator pairs as an opaque blob of
+ * sx_stats_state_size doubles (0 without a set); a run resumed from it continues bitwise.  A blob taken on a handle with another
+ * number of gridpoints is refused.
+ * Refused, with a message and before anything is written - an existing set, its accumulators and the out buffers stay as they are: a
+ * null pointer with a non-zero count; whatever sx_reduce_planes refuses; an unknown op; a NaN / Inf threshold of a DURATION output; a
+ * NaN / Inf time or weight; sx_stats_get or sx_stats_get_state without a set; an allocation that fails (the message names the bytes
+ * asked for).  Multi-tile handles are allowed: tiles own disjoint points and each accumulates its own.
+ * sx_kernel_bytes("k_stats") gives the bytes of the last sample: the planes named x N x their element size + n_out x N x 32 (every
+ * pair read and written; the outputs a weight == 0 sample skips are counted all the same: an upper bound). */
+enum { SX_STAT_SUM = 0, SX_STAT_MAX = 1, SX_STAT_MIN = 2, SX_STAT_DURATION = 3 };
+int sx_stats_set(sx_handle *h, int32_t source, int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out,
+                 const int32_t *op /*[n_out]*/, const double *threshold /*[n_out] or NULL*/);
+int sx_stats_reset(sx_handle *h);
+int sx_stats_accumulate(sx_handle *h, double time, double weight);
+int sx_stats_get(sx_handle *h, double *out /*[N, n_out, 2] column-major*/, double *info /*[5] or NULL*/);
+int sx_stats_describe(const sx_handle *h, int32_t *source, int32_t *n_out, int32_t *op /*[16]*/, double *threshold /*[16]*/);
+int sx_stats_state_size(const sx_handle *h, int64_t *n_doubles);
+int sx_stats_get_state(sx_handle *h, double *out);
+int sx_stats_set_state(sx_handle *h, const double *in, int64_t n_doubles);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

@@ -7,9 +7,9 @@ from .model import (CubicBSpline, Chebyshev, GridParameters, ModelParameters, Gr
                     cartesian_gridpoints, Program, reduce_weights, reduce_planes, pack_reduce_program, invariants,
                     spectrum_check, pack_spectrum_pairs, companion_grid, elliptic_check, Refined, free_mask, newton_step,
                     Crossings, bracket_step, Distribution, distribution_slot, distribution_check,
-                    pack_vortex_fields, default_vortex_n_az, vortex_check)
+                    pack_vortex_fields, default_vortex_n_az, vortex_check, Statistics, pack_statistics)
 from .driver import (PatchLayout, LocalExchange, DistExchange, A2ALayout, LocalA2AExchange, DistA2AExchange, LibExchange, LocalLibExchange, ModelRun,
-                     integrate_model, Located, WindRadii, Cfad, Exceedance, Quantile, VortexProfile)
-from .io import read_physical_grid, write_output, write_gridded_output, write_parcels
+                     integrate_model, Located, WindRadii, Cfad, Exceedance, Quantile, VortexProfile, Swath)
+from .io import read_physical_grid, write_output, write_gridded_output, write_parcels, write_statistics, statistics_header
 from . import thermodynamics, reference_state
 from .reference_state import ReferenceState, Chebyshev1D

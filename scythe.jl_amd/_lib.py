@@ -18,6 +18,7 @@ REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
 DIST_KIND = {"domain": 0, "level": 1}              # SX_DIST_DOMAIN / SX_DIST_LEVEL
 VORTEX_SCALAR, VORTEX_WIND = 0, 1                # SX_VORTEX_*
+STAT_OP = {"sum": 0, "max": 1, "min": 2, "duration": 3}     # SX_STAT_SUM / SX_STAT_MAX / SX_STAT_MIN / SX_STAT_DURATION
 EXT_KIND = {"domain": 0, "azimuth": 1}           # SX_EXT_DOMAIN / SX_EXT_AZIMUTH
 EXT_WANT = {"min": -1, "any": 0, "max": 1}       # SX_EXT_MIN / SX_EXT_ANY / SX_EXT_MAX
 EXT_FREE = {"r": 1, "l": 2, "z": 4}              # SX_EXT_FREE_R / SX_EXT_FREE_L / SX_EXT_FREE_Z
@@ -147,6 +148,14 @@ SYMBOLS = {
     "sx_distribution_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_int32, P_I32, C.c_int32, C.c_int32, P_D]),
     "sx_vortex_harmonics": (C.c_int, [_H, P_D, P_D, P_D, C.c_int32, P_D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_I32, P_D, P_I32]),
     "sx_vortex_check": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_I32, P_I32, P_I32]),
+    "sx_stats_set": (C.c_int, [_H, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_I32, P_D]),
+    "sx_stats_reset": (C.c_int, [_H]),
+    "sx_stats_accumulate": (C.c_int, [_H, C.c_double, C.c_double]),
+    "sx_stats_get": (C.c_int, [_H, P_D, P_D]),
+    "sx_stats_describe": (C.c_int, [_H, P_I32, P_I32, P_I32, P_D]),
+    "sx_stats_state_size": (C.c_int, [_H, P_I64]),
+    "sx_stats_get_state": (C.c_int, [_H, P_D]),
+    "sx_stats_set_state": (C.c_int, [_H, P_D, C.c_int64]),
 }
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)

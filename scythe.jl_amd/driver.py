@@ -12,7 +12,7 @@ import time
 
 import numpy as np
 
-from .model import (Distribution, Grid, GridParameters, ModelParameters, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
+from .model import (Distribution, Grid, GridParameters, ModelParameters, Statistics, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
 
 Located = collections.namedtuple("Located", "pos value status")
 WindRadii = collections.namedtuple("WindRadii", "thresholds azimuths radii quadrants")
@@ -20,6 +20,7 @@ VortexProfile = collections.namedtuple("VortexProfile", "centre radii radial tan
 Cfad = collections.namedtuple("Cfad", "frac under over nan area edges")
 Exceedance = collections.namedtuple("Exceedance", "thresholds measure integral")
 Quantile = collections.namedtuple("Quantile", "lo hi passes nan_count measure")
+Swath = collections.namedtuple("Swath", "speed time samples")
 
 
 class PatchLayout:
@@ -372,6 +373,7 @@ class ModelRun:
         self._ring_axes = None      # azimuthal_mean's (r, z) axes, formed on first use
         self._points = None         # the local tiles' gridpoints [n, n_coord] in tile order (extrema's rows), formed on first use
         self._parcels = False       # set_parcels attached a parcel set: step() moves it
+        self._stats = None          # set_statistics attached a statistics set: dict(source, every, key); step() samples it
 
     def _bind_streams(self, device):
         """Kernels of a tile run on ITS stream; torch's collectives order themselves against torch's CURRENT stream.  Hand
@@ -431,10 +433,73 @@ class ModelRun:
         if self.num_tiles == 1 and self.exchange is None:
             self._check_stream()
             self.tiles[0].step(self.t)          # sx_step = sx_advance + sx_spline_transform (one hipGraph launch with SX_GRAPH=1)
-            return
+        else:
+            for g in self.tiles:
+                g.advance(self.t)
+            self._exchange_and_solve()
+        if self._stats is not None and self.t % self._stats["every"] == 0:
+            # the sample goes on each tile's stream AFTER the step: var_np1 is then the state of time t, and the next step's first
+            # writer of var_np1 or `physical` is enqueued on that same stream behind it
+            self._sample_statistics(self.t * self.model.ts, self._stats["every"] * self.model.ts)
+
+    def _sample_statistics(self, time, weight):
+        self._check_stream()
         for g in self.tiles:
-            g.advance(self.t)
-        self._exchange_and_solve()
+            if self._stats["source"] == "physical":
+                g.tileTransform_()
+            g.accumulate_statistics(time, weight)
+
+    def set_statistics(self, outputs, source="state", every=1, include_initial=True, ops=None, key=""):
+        """Attach a statistics set to every local tile (Grid.set_statistics): from now on step() takes a sample AFTER every
+        `every`-th step (t % every == 0) with time = t ts and weight = every ts, on each tile's stream and without a
+        synchronisation.  include_initial takes the state as it stands into the extrema with weight 0 (time = t ts), which gives it
+        no time weight.  source="state" reads var_np1 and costs nothing but the kernel; source="physical" runs tileTransform! on
+        the tile before each sample, at that cadence only: one inverse transform per sample, which writes `physical` alone - the
+        step rebuilds `physical` from the A coefficients before it reads it, so the model's evolution cannot change.  An empty
+        `outputs` detaches the set."""
+        if int(every) < 1:
+            raise ValueError("every must be at least 1")
+        for g in self.tiles:
+            g.set_statistics(outputs, source, ops)
+        if self.tiles[0].describe_statistics() is None:
+            self._stats = None
+            return
+        self._stats = dict(source=source, every=int(every), key=str(key))
+        if include_initial:
+            self._sample_statistics(self.t * self.model.ts, 0.0)
+
+    def statistics(self):
+        """The statistics of the local tiles concatenated in tile order: the rows of gridpoints() (Grid.statistics)"""
+        if self._stats is None:
+            raise ValueError("statistics: no statistics set is attached (set_statistics)")
+        self._check_stream()
+        return Statistics.concatenate([g.statistics() for g in self._tiles_in_order()])
+
+    def reset_statistics(self):
+        """Empty the accumulators and counters of every local tile; the set stays attached (windowed means, hourly totals)"""
+        for g in self.tiles:
+            g.reset_statistics()
+
+    def wind_swath(self, u, v, every=1):
+        """The maximum-wind swath: the largest speed sqrt(u^2 + v^2) every gridpoint has seen, and when.  The first call attaches
+        the set - MAX of u^2 + v^2 on var_np1, the state as it stands included - and every call returns Swath(speed [N], time [N],
+        samples) over gridpoints()' rows; the square root is taken on the host.  A run holds ONE statistics set: this replaces
+        another one."""
+        key = "wind_swath:%s:%s" % (u, v)
+        if self._stats is None or self._stats["key"] != key:
+            self.set_statistics([("max", [(1.0, 0, [(u, ""), (u, "")]), (1.0, 0, [(v, ""), (v, "")])])], "state", every, True, key=key)
+        st = self.statistics()
+        return Swath(np.sqrt(st.value[:, 0]), st.time[:, 0].copy(), st.samples)
+
+    def accumulated(self, var, every=1):
+        """The time integral of variable `var` (rain rate -> rain, a flux -> its total).  The first call attaches the set - SUM of
+        var on var_np1, weight every ts per sample - and every call returns (total [N], elapsed) over gridpoints()' rows.  A run
+        holds ONE statistics set: this replaces another one."""
+        key = "accumulated:%s" % (var,)
+        if self._stats is None or self._stats["key"] != key:
+            self.set_statistics([("sum", [(1.0, 0, [(var, "")])])], "state", every, False, key=key)
+        st = self.statistics()
+        return st.value[:, 0].copy(), st.elapsed
 
     def physical(self):
         """tileTransform! on every local tile; returns the concatenated physical array."""
@@ -866,6 +931,10 @@ class ModelRun:
             blob = g.get_parcel_state()
             if blob is not None:
                 extra["parcels%d" % i] = blob
+        if self._stats is not None:                       # so does a statistics set, with the cadence it is sampled at
+            for i, g in zip(self.tile_ids, self.tiles):
+                extra["stats%d" % i] = g.get_statistics_state()
+            extra["stats_every"], extra["stats_key"] = np.array(self._stats["every"]), np.array(self._stats["key"])
         np.savez(path, t=self.t, tile_ids=np.array(self.tile_ids), **extra)
 
     def load_checkpoint(self, path):
@@ -878,7 +947,13 @@ class ModelRun:
                     g.set_parcel_state(z["parcels%d" % i])
                 else:
                     g.set_parcels(np.zeros((0, len(self.patch.geometry))), [None] * len(self.patch.geometry))
+                if "stats%d" % i in z.files:
+                    g.set_statistics_state(z["stats%d" % i])
+                else:
+                    g.set_statistics([])
             self._parcels = any(g.n_parcels > 0 for g in self.tiles)
+            d = self.tiles[0].describe_statistics()
+            self._stats = None if d is None else dict(source=d[0], every=int(z["stats_every"]), key=str(z["stats_key"]))
             self.t = int(z["t"])
 
     def close(self):

@@ -131,3 +131,33 @@ def write_parcels(run, time):
     arr = np.concatenate([pos, vel, status[:, None].astype(np.float64)], axis=1)
     np.savetxt(path, arr, delimiter=",", header=",".join(coord + ["vel_" + c for c in coord] + ["status"]), comments="", fmt="%.17g")
     return path
+
+
+def statistics_header(geometry, ops, names=None):
+    """the columns of write_statistics: the coordinates, one column per output and a <name>_time column after every extremum"""
+    names = list(names) if names else ["%s%d" % (op, o) for o, op in enumerate(ops)]
+    if len(names) != len(ops):
+        raise ValueError("%d names for %d outputs" % (len(names), len(ops)))
+    cols = list(_COORD[geometry])
+    for n, op in zip(names, ops):
+        cols.append(n)
+        if op in ("max", "min"):
+            cols.append(n + "_time")
+    return cols
+
+
+def write_statistics(run, time, names=None):
+    """The run's statistics set (ModelRun.statistics) as statistics_out_<tag>.csv beside physical_out_<tag>.csv: one row per
+    gridpoint of the local tiles, the coordinate columns r[, l][, z] of write_output, then one column per output (default names
+    <op><index>) and, after every "max" / "min" output, the time of the sample that set it."""
+    model = run.model
+    st = run.statistics()
+    header = statistics_header(model.grid_params.geometry, st.ops, names)
+    cols = [run.gridpoints()]
+    for o, op in enumerate(st.ops):
+        cols.append(st.value[:, o:o + 1])
+        if op in ("max", "min"):
+            cols.append(st.time[:, o:o + 1])
+    path = os.path.join(model.output_dir, "statistics_out_%s.csv" % output_time_tag(time))
+    np.savetxt(path, np.concatenate(cols, axis=1), delimiter=",", header=",".join(header), comments="", fmt="%.17g")
+    return path

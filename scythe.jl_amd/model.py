@@ -615,6 +615,65 @@ class Grid:
                                        status.ctypes.data_as(L.P_I32), prof.ctypes.data_as(L.P_D) if prof is not None else None))
         return Crossings(radius, dirs, count, status, prof)
 
+    # -- statistics of field programs over time (sx_stats_*)
+    def set_statistics(self, outputs, source="state", ops=None):
+        """Attach (or replace) the tile's statistics set: per-gridpoint accumulators over time that live on the device
+        (sx_stats_set).  outputs: a list of (op, terms[, threshold]), one entry per output - op one of "sum", "max", "min",
+        "duration", terms the terms of that output as for reduce (their `out` is ignored), threshold for "duration" only - or a
+        Program with ops = one op or (op, threshold) per output of the program.  source="state" reads var_np1 (no transform),
+        "physical" reads `physical` as it stands (call tileTransform_ before every sample).  An empty `outputs` removes the set.
+        Refusals leave an existing set as it is."""
+        if source not in L.REDUCE_SOURCE:
+            raise ValueError("source must be 'physical' or 'state'")
+        coef, packed, n_out, op, thr = pack_statistics(self.patch_params, outputs, ops)
+        L.check(self._lib.sx_stats_set(self._h, L.REDUCE_SOURCE[source], len(coef), coef.ctypes.data_as(L.P_D), packed.ctypes.data_as(L.P_I32),
+                                       n_out, op.ctypes.data_as(L.P_I32), thr.ctypes.data_as(L.P_D)))
+
+    def accumulate_statistics(self, time, weight):
+        """One sample of the attached set from the planes as they stand: one kernel on the tile's stream, no synchronisation
+        (sx_stats_accumulate).  weight = 0 is the "extrema only" sample.  Without a set it does nothing."""
+        L.check(self._lib.sx_stats_accumulate(self._h, float(time), float(weight)))
+
+    def reset_statistics(self):
+        """Empty the accumulators and counters of the attached set; the program stays (sx_stats_reset)"""
+        L.check(self._lib.sx_stats_reset(self._h))
+
+    def describe_statistics(self):
+        """(source, ops, thresholds) of the attached set - names as set_statistics takes them, a threshold None where the op has none -
+        or None without a set (sx_stats_describe)"""
+        src, n = C.c_int32(0), C.c_int32(0)
+        op, thr = np.zeros(16, dtype=np.int32), np.zeros(16)
+        L.check(self._lib.sx_stats_describe(self._h, C.byref(src), C.byref(n), op.ctypes.data_as(L.P_I32), thr.ctypes.data_as(L.P_D)))
+        if n.value == 0:
+            return None
+        names = {v: k for k, v in L.STAT_OP.items()}
+        ops = [names[int(o)] for o in op[:n.value]]
+        return ({v: k for k, v in L.REDUCE_SOURCE.items()}[src.value], ops,
+                [float(t) if o == "duration" else None for o, t in zip(ops, thr[:n.value])])
+
+    def statistics(self):
+        """The attached set's results as a Statistics object (sx_stats_get; synchronises)"""
+        d = self.describe_statistics()
+        if d is None:
+            raise L.ScytheHipError("statistics: the tile has no statistics set")
+        out, info = np.zeros((self.N, len(d[1]), 2), order="F"), np.zeros(5)
+        L.check(self._lib.sx_stats_get(self._h, out.ctypes.data_as(L.P_D), info.ctypes.data_as(L.P_D)))
+        return Statistics.from_raw(out, info, d[1])
+
+    def get_statistics_state(self):
+        """Restart blob of the statistics set (sx_stats_get_state), or None without a set"""
+        n = C.c_int64(0)
+        L.check(self._lib.sx_stats_state_size(self._h, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.zeros(n.value)
+        L.check(self._lib.sx_stats_get_state(self._h, out.ctypes.data_as(L.P_D)))
+        return out
+
+    def set_statistics_state(self, blob):
+        b = np.ascontiguousarray(blob, dtype=np.float64)
+        L.check(self._lib.sx_stats_set_state(self._h, b.ctypes.data_as(L.P_D), b.size))
+
     # -- operators
     def spectralTransform_(self):
         L.check(self._lib.sx_spectral_transform(self._h))
@@ -955,6 +1014,72 @@ def distribution_check(patch: GridParameters, terms, edges, kind="domain", sourc
     L.check(L.load().sx_distribution_check(C.byref(d), L.DIST_KIND[kind] if isinstance(kind, str) else int(kind),
                                            L.REDUCE_SOURCE[source] if isinstance(source, str) else int(source), len(coef),
                                            packed.ctypes.data_as(L.P_I32), n_out, len(e) - 1, e.ctypes.data_as(L.P_D)))
+
+
+# ----------------------------------------------------------------------------- statistics over time (sx_stats_*)
+def pack_statistics(patch: GridParameters, outputs, ops=None):
+    """outputs -> (coef, terms int32 [n, 11], n_out, op int32 [n_out], threshold float64 [n_out]) as sx_stats_set reads them.
+    outputs: a list of (op, terms[, threshold]) - the terms of entry o become the terms of output o, whatever their own `out`
+    says - or, with ops, a program as for Grid.reduce whose output o takes ops[o] = op or (op, threshold).  Raises ValueError for an
+    unknown op, a "duration" without a threshold, a threshold on another op, or ops that do not match the program's outputs."""
+    if ops is None:
+        entries = list(outputs)
+        terms, ops = [], []
+        for o, e in enumerate(entries):
+            if not isinstance(e, (tuple, list)) or len(e) not in (2, 3):
+                raise ValueError("output %d is no (op, terms[, threshold])" % o)
+            terms += [(o,) + tuple(t[-3:]) for t in e[1]]
+            ops.append(e[0] if len(e) == 2 else (e[0], e[2]))
+        n_given = len(entries)
+    else:
+        terms, ops = list(outputs), list(ops)
+        n_given = len(ops)
+    coef, packed, n_out = pack_reduce_program(patch, terms)
+    if n_out > n_given:
+        raise ValueError("the program has %d outputs, ops names %d" % (n_out, n_given))
+    n_out = n_given                    # a trailing output without terms is the constant 0
+    op, thr = np.zeros(max(n_out, 1), dtype=np.int32), np.zeros(max(n_out, 1))
+    for o, e in enumerate(ops):
+        name, t = (e, None) if isinstance(e, str) else (e[0], e[1] if len(e) > 1 else None)
+        if name not in L.STAT_OP:
+            raise ValueError("output %d: op %r is none of %s" % (o, name, sorted(L.STAT_OP)))
+        if (name == "duration") != (t is not None):
+            raise ValueError("output %d: a threshold goes with 'duration', and only with it" % o)
+        op[o], thr[o] = L.STAT_OP[name], 0.0 if t is None else float(t)
+    return coef, packed, n_out, op, thr
+
+
+class Statistics:
+    """Results of a statistics set: value [N, n_out] - the sum (hi + lo) for "sum" / "duration", the extremum for "max" / "min";
+    time [N, n_out] - the time of the sample that set an extremum, NaN for the sum-like ops; residual [N, n_out] - the low word of a
+    sum's stored pair (NaN for extrema); samples, elapsed (the sum of the weights; elapsed_lo its low word), t_first, t_last; ops.
+    samples == 0 means "empty": extremum values are then NaN because nothing was seen, otherwise because q was NaN."""
+
+    def __init__(self, value, time, residual, samples, elapsed, elapsed_lo, t_first, t_last, ops):
+        self.value, self.time, self.residual, self.ops = value, time, residual, list(ops)
+        self.samples, self.elapsed, self.elapsed_lo, self.t_first, self.t_last = samples, elapsed, elapsed_lo, t_first, t_last
+
+    @classmethod
+    def from_raw(cls, out, info, ops):
+        """out [N, n_out, 2] and info [5] as sx_stats_get returns them"""
+        sumlike = np.array([o in ("sum", "duration") for o in ops], dtype=bool)
+        value = np.array(out[:, :, 0], order="F")
+        time = np.where(sumlike[None, :], np.nan, out[:, :, 1])
+        residual = np.where(sumlike[None, :], out[:, :, 1], np.nan)
+        return cls(value, time, residual, int(info[0]), float(info[1] + info[2]), float(info[2]), float(info[3]), float(info[4]), ops)
+
+    def mean(self, o):
+        """value / elapsed of a "sum" output: its time mean over the window"""
+        if self.ops[o] != "sum":
+            raise ValueError("output %d is a %r, not a 'sum'" % (o, self.ops[o]))
+        return self.value[:, o] / self.elapsed
+
+    @classmethod
+    def concatenate(cls, parts):
+        """the tiles of a patch in tile order: the points concatenated; the counters are every tile's"""
+        p0 = parts[0]
+        return cls(np.concatenate([p.value for p in parts], axis=0), np.concatenate([p.time for p in parts], axis=0),
+                   np.concatenate([p.residual for p in parts], axis=0), p0.samples, p0.elapsed, p0.elapsed_lo, p0.t_first, p0.t_last, p0.ops)
 
 
 # ----------------------------------------------------------------------------- vortex-centred harmonics (sx_vortex_harmonics)
