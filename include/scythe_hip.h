@@ -449,6 +449,57 @@ int sx_elliptic_solve(sx_handle *src, int32_t rhs_kind, int32_t var_a, int32_t v
 int sx_elliptic_check(const sx_grid_desc *grid, int32_t var_dst, int32_t k, double alpha, const double *g /*[num_cells + 3]*/,
                       double *a /*[num_cells + 3]*/);
 
+/* --- antiderivatives: radial and vertical --------------------------------------------------------------------------------
+ * The integral of a variable UP TO A POINT, returned as a field that everything else can sample:
+ *     SX_INT_R:  F(r) = int_{xmin}^{r} w f ds (SX_INT_FROM_LOW)   or   int_{r}^{xmax} w f ds (SX_INT_FROM_HIGH),   w = 1 (SX_INT_W_ONE) or
+ *                r (SX_INT_W_R: the integrand r f, on any geometry)
+ *     SX_INT_Z:  F(z) = int_{zmin}^{z} f dz' (FROM_LOW)   or   int_{z}^{zmax} f dz' = F(zmax) - F(z) (FROM_HIGH);   weight must be 0
+ * A of src is the only input and the patch A rows of variable var_dst (1-based) of dst the only output, per (z-mode, re / im block)
+ * column; block 1 (Im c_0) is never read and is written as zero.  dst is src itself (a spare variable) or a one-variable companion
+ * handle with SX_EQ_NONE, as for sx_elliptic_solve.
+ *
+ * Radial.  With f = sum_j a_j phi_j in the patch's spline basis, F is projected onto var_dst's spline space exactly as the model
+ * projects any field - a_dst = Gamma^T (Gamma (P + eps_q Q) Gamma^T)^-1 Gamma b, the B -> A of splineTransform! with var_dst's own class
+ * (its bcl_k0 for k = 0, its bcl for k >= 1, its bcr) AND ITS l_q FILTER, through the Cholesky factor the handle's own solve uses - but
+ * with the EXACT right-hand side b_i = int phi_i F dr, not the 3-point quadrature of the mish.  With Phi_j(r) = int_{xmin}^{r} w phi_j,
+ * c_j = int w phi_j and m_i = int phi_i:
+ *     b_i = sum_{|j - i| <= 3} Pband[i][j] a_j + m_i sum_{j <= i - 4} c_j a_j      (FROM_LOW;  FROM_HIGH: sum_{j >= i + 4}, its own band)
+ * because phi_j ends before phi_i begins for j <= i - 4.  Pband [nb][7], c [nb], m [nb] are formed on the host in extended precision by
+ * 8-point Gauss-Legendre quadrature per cell (exact: phi_i Phi_j is piecewise of degree <= 8), rounded once, and kept with the source
+ * handle for the last (origin, weight, radial conditions of var_dst) used; a second call with the same key uploads nothing.  The running
+ * sum is serial and in a fixed order per column.
+ *
+ * Vertical.  The A columns hold the truncated Chebyshev coefficients b; with the factors of the vertical transform
+ *     Z = CB T Ic CA_src  [b_zDim][b_zDim]   (FROM_LOW: zero at zmin;   FROM_HIGH: CB (1 e_top^T - I) T Ic CA_src)
+ * (CA_src with var_src's (bcb, bct); products in extended precision, rounded once) and A_dst[m][zm][blk] = sum_zm' Z[zm][zm'] A_src[m][zm'][blk]
+ * for every node row and block.  On grids with at least 16 blocks per z-mode and b_zDim <= 64 the product runs on the f64 matrix
+ * cores; otherwise (RZ grids: 1 block) one lane forms one output in a fixed order.
+ *
+ * Runs on src's stream and returns after completion; a deferred diagnostic variable is brought up to date first.  `physical`,
+ * var_np1, the tendency history, B, parcels, statistics, captured graphs of both handles and every other variable's A stay bitwise
+ * as they are.  No atomics, nothing across lanes: two calls agree bitwise, and a column's radial result does not depend on the launch
+ * shape.
+ * Refused, with a message and before anything is written: a null handle; an unknown axis, origin or weight; a variable index out of
+ * range; var_dst == var_src when dst == src; a src or dst that is not a one-tile patch; a dst that differs from src in geometry, xmin,
+ * xmax, num_cells, ring table, kDim, zDim, b_zDim, zmin or zmax; SX_INT_Z on a grid without a vertical; a non-zero weight with SX_INT_Z;
+ * PERIODIC radial conditions on var_dst (SX_INT_R); for SX_INT_R a var_src whose (bcb, bct) differs from var_dst's (the z-mode columns
+ * are carried one to one); for SX_INT_Z a var_src whose radial conditions (bcl, bcl_k0, bcr) differ from var_dst's (the rows are
+ * carried one to one).
+ * sx_kernel_bytes("k_antiderivative_r") gives the source columns in + the destination columns out + the tables + the intermediate
+ * (the right-hand side and the forward sweep's vector each make one round trip through the destination columns: 4 x the live
+ * destination columns); sx_kernel_bytes("k_antiderivative_z") gives 2 x 8 x nb x b_zDim x K2 + Z.
+ *
+ * sx_antiderivative_check states the same for ONE column on the host with the same tables and the kernel's arithmetic operation for
+ * operation (radial: band, running sum, the two sweeps; vertical: the row sums in index order): a_src / a_dst are [num_cells + 3]
+ * (radial, wavenumber k selects var_dst's class) or [b_zDim] (vertical, k only range-checked).  It refuses what the call refuses of a
+ * descriptor, and a k outside 0 .. kDim.  Pure host helper (no handle, no device). */
+enum { SX_INT_R = 0, SX_INT_Z = 1 };
+enum { SX_INT_FROM_LOW = 0, SX_INT_FROM_HIGH = 1 };
+enum { SX_INT_W_ONE = 0, SX_INT_W_R = 1 };          /* radial only: integrand f or r f, on any geometry */
+int sx_antiderivative(sx_handle *src, int32_t var_src, int32_t axis, int32_t origin, int32_t weight, sx_handle *dst, int32_t var_dst);
+int sx_antiderivative_check(const sx_grid_desc *grid, int32_t var_src, int32_t var_dst, int32_t axis, int32_t origin, int32_t weight,
+                            int32_t k, const double *a_src, double *a_dst);
+
 /* --- integrals and azimuthal means of field products ------------------------------------------------------------------
  * On-device diagnostics: budgets and azimuthal means / eddy covariances without pulling `physical` to the host.
  * Integrand program: n_terms <= 64 monomial terms feed n_out <= 16 outputs.  Term t is

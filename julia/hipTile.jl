@@ -218,6 +218,23 @@ function ellipticCheck(grid::SxGridDesc, var_dst::Integer, k::Integer, alpha::Fl
     return a
 end
 
+# antiderivatives (sx_antiderivative): F(r) = int_{xmin}^{r} w f ds (axis 0; weight 0: w = 1, 1: w = r) or F(z) = int_{zmin}^{z} f dz' (axis 1) of
+# variable var_src from the A coefficients of src, written as the A coefficients of variable var_dst of dst (src itself, or a one-variable
+# companion tile with no equation set); origin 1 integrates from xmax / zmax down to the point instead
+function antiderivative!(src::HipModelTile, var_src::Integer, axis::Integer, origin::Integer, weight::Integer, dst::HipModelTile, var_dst::Integer)
+    sxcheck(ccall((:sx_antiderivative, libsx), Cint, (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Ptr{Cvoid}, Int32),
+                  src.handle, var_src, axis, origin, weight, dst.handle, var_dst))
+end
+
+# the same for ONE column a_src (num_cells + 3 entries along r, b_zDim along z) on the host (no handle, no device)
+function antiderivativeCheck(grid::SxGridDesc, var_src::Integer, var_dst::Integer, axis::Integer, origin::Integer, weight::Integer, k::Integer,
+                             a_src::Vector{Float64})
+    a = zeros(Float64, length(a_src))
+    sxcheck(ccall((:sx_antiderivative_check, libsx), Cint, (Ref{SxGridDesc}, Int32, Int32, Int32, Int32, Int32, Int32, Ptr{Float64}, Ptr{Float64}),
+                  grid, var_src, var_dst, axis, origin, weight, k, a_src, a))
+    return a
+end
+
 # Lagrangian parcels (sx_parcels_*): tracer points that live on the device and move with the model's Adams-Bashforth scheme.
 # points[n, n_coord] with columns r[, lambda][, z]; var_r / var_l / var_z = 1-based variable index of the velocity component along
 # each coordinate (speeds; var_l the tangential wind), 0 = no motion.  An empty points matrix removes the set

@@ -14,6 +14,8 @@ EVAL_RING_K, EVAL_ALL_K = 0, 1      # SX_EVAL_*
 HARM_SLOTS = ("u", "r", "rr", "z", "zz")          # SX_HARM_*: bit i of slot_mask
 SPEC_KIND = {"ring": 0, "domain": 1}             # SX_SPEC_RING / SX_SPEC_DOMAIN
 ELL_KIND = {"field": 0, "vorticity": 1, "divergence": 2}    # SX_ELL_*
+INT_AXIS = {"r": 0, "z": 1}                      # SX_INT_R / SX_INT_Z
+INT_ORIGIN = {"low": 0, "high": 1}               # SX_INT_FROM_LOW / SX_INT_FROM_HIGH
 REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_AZIMUTH
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
 DIST_KIND = {"domain": 0, "level": 1}              # SX_DIST_DOMAIN / SX_DIST_LEVEL
@@ -134,6 +136,8 @@ SYMBOLS = {
     "sx_parcels_set_state": (C.c_int, [_H, P_D, C.c_int64]),
     "sx_elliptic_solve": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_double, _H, C.c_int32]),
     "sx_elliptic_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_double, P_D, P_D]),
+    "sx_antiderivative": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _H, C.c_int32]),
+    "sx_antiderivative_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_D, P_D]),
     "sx_reduce": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, P_D]),
     "sx_reduce_weights": (C.c_int, [C.POINTER(GridDesc), P_D, P_D, P_D]),
     "sx_reduce_planes": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32, P_I32]),

@@ -736,7 +736,7 @@ int sx_destroy(sx_handle *h) {
     comm_release(h);
     iface_release(h);
     pcr_release(h);
-    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics: their device memory goes with them
+    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives: their device memory goes with them
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -1487,6 +1487,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_spectrum") b = diag_bytes(DIAG_SPEC);                  // the last call's rings x distinct planes x 4 rows x b_zDim x (2 kmax + 1) of A
     else if (k == "k_parcels") b = diag_bytes(DIAG_PARCELS);                // the last advance's parcels x velocity variables x 4 rows x b_zDim x (2 kDim + 1) of A
     else if (k == "k_elliptic") b = diag_bytes(DIAG_ELLIPTIC);              // the last solve's source columns in + destination columns out + factors
+    else if (k == "k_antiderivative_r" || k == "k_antiderivative_z") b = antiderivative_bytes(h, k == "k_antiderivative_z");   // the last radial / vertical call (sx_antiderivative.hip)
     else if (k == "k_reduce") b = diag_bytes(DIAG_REDUCE);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
     else if (k == "k_extrema") b = extrema_bytes(h, false);                 // the last scan's planes x N x 8 (4 for an fp32-stored plane)
     else if (k == "alloc.d_Fl") b = (double)h->fl_bytes;                     // device bytes of the ring spectra (0: not allocated)

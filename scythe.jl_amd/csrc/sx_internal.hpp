@@ -144,7 +144,32 @@ bool build_elliptic_class(const EllBands &eb, int has_l, double xmin, int bcl, i
                           std::string &err);
 void elliptic_apply_host(const EllClass &c, int k, int nb, const double *g /*[nb]*/, double *a /*[nb]*/);
 
-// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics, sx_stats_*) ----
+// ---- antiderivatives (sx_setup.cpp: the tables; sx_antiderivative.hip: sx_antiderivative, sx_antiderivative_check, the kernels) ----
+// Radial: b_i = int phi_i F dr of F(r) = int_{xmin}^{r} w f (FROM_LOW) or int_{r}^{xmax} w f (FROM_HIGH), f = sum_j a_j phi_j, split into
+// a 7-diagonal band and a running sum (include/scythe_hip.h, "antiderivatives").  The tables are kept in WALK order: step s is patch
+// row s (FROM_LOW, upward) or nb - 1 - s (FROM_HIGH, downward), window slot d of step s is the row of step s - 3 + d, so that the
+// kernel and its host statement are one loop for both origins.
+struct AntiTables {
+    int nb = 0, origin = 0, weight = 0;
+    std::vector<double> P;      // [nb][7]  P[s][d]: int phi_row(s) Phi_row(s - 3 + d) (Psi for FROM_HIGH); 0 outside the patch
+    std::vector<double> c;      // [nb]     c[s] = int w phi_row(s)
+    std::vector<double> m;      // [nb]     m[s] = int phi_row(s)
+};
+void build_antiderivative_tables(double xmin, double xmax, int nc, int origin, int weight, AntiTables &out);
+// The projection that goes with the exact right-hand side: Gamma (P + eps_q Q) Gamma^T of one boundary-condition class with the EXACT
+// Gram matrix P = int phi phi (the model's own P is its 3-point quadrature of it and pairs only with right-hand sides formed by that
+// rule), Q = int phi''' phi''', eps_q from l_q.  sc: ranks, boundary rows and Gamma of the class (no Lband); F: its banded Cholesky factor
+// rows as k_antiderivative_r reads them, [nb][4] = L[i][i - 3], L[i][i - 2], L[i][i - 1], 1 / L[i][i].  Refuses PERIODIC and too few cells.
+bool build_antiderivative_class(double xmin, double xmax, int nc, double l_q, int bcl, int bcr, SplineClass &sc, std::vector<double> &F,
+                                std::string &err);
+// the arithmetic of k_antiderivative_r, operation for operation, on the host: one column a_src [nb] -> a_dst [nb]
+void antiderivative_r_host(const AntiTables &t, const SplineClass &sc, const double *F /*[nb][4]*/, const double *a_src, double *a_dst);
+// Z^T [Kp][Mp] (Kp = b_zDim rounded up to 4, Mp to 16, zero-padded): Z = CB T Ic CA (FROM_LOW, zero at zmin) or CB (1 e_top^T - I) T Ic CA
+// (FROM_HIGH: F(zmax) - F(z)) with CA of the source's (bcb, bct), products in extended precision, rounded once
+bool build_antiderivative_z(double zmin, double zmax, int nz, int Zb, int bcb, int bct, int origin, std::vector<double> &ZT, int &Kp, int &Mp,
+                            std::string &err);
+
+// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics, sx_stats_*, sx_antiderivative) ----
 template <class T>
 struct DevBuf {         // owns one device array; reads as the pointer
     T *p = nullptr;
@@ -181,7 +206,7 @@ struct DiagState {      // what one of these entry points keeps with the handle:
     double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
     virtual ~DiagState() = default;
 };
-enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
+enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_ANTIDERIVATIVE, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
 struct EvalClasses {    // the vertical boundary-condition classes of a handle's variables (eval_classes)
     std::vector<EvalVert> vert;       // empty without a vertical
     std::vector<int> vcls;            // [V] class of each variable
@@ -516,7 +541,8 @@ __device__ inline double parcel_bspl(double delta) {
 }
 double extrema_bytes(const sx_handle *h, bool refine);   // bytes of the last sx_extrema (k_extrema) / sx_extremum_refine (k_refine)
 double crossings_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_crossings: k_ray_profiles / k_crossings (sx_crossings.hip)
-int default_bzdim(int zDim);                    // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)
+double antiderivative_bytes(const sx_handle *h, bool vertical);   // bytes of the last sx_antiderivative along r (k_antiderivative_r) / z (k_antiderivative_z)
+int default_bzdim(int zDim);                   // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);
 void launch_rz_forward(sx_handle *h);

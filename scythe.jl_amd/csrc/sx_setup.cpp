@@ -572,6 +572,180 @@ void elliptic_apply_host(const EllClass &c, int k, int nb, const double *g, doub
     for (int q = 0; q < rr; q++) a[nb - 1 - q] = std::fma(c.gr[q][1], xr1, c.gr[q][0] * xr0);
 }
 
+// ---------------------------------------------------------------------------------------------- antiderivatives
+// The tables of sx_antiderivative along r (include/scythe_hip.h, "antiderivatives").  With Phi_j(r) = int_{xmin}^{r} w phi_j,
+// c_j = int w phi_j and m_i = int phi_i over the patch,  b_i = int phi_i F dr = sum_j a_j int phi_i Phi_j.  phi_j lives on the four cells
+// below node j + 2, so on the support of phi_i:  Phi_j = c_j for j <= i - 4 (phi_j ends before phi_i begins), Phi_j = 0 for j >= i + 4, and
+// only |j - i| <= 3 needs the integral itself: a 7-diagonal band plus m_i times a running sum.  FROM_HIGH: Psi_j = c_j - Phi_j, the constant
+// on the other side.
+// Degrees: on a cell phi is a cubic and w phi of degree 3 (w = 1) or 4 (w = r), so Phi_j is of degree 4 or 5 there and phi_i Phi_j of
+// degree 7 or 8.  The 8-point rule is exact up to degree 15: 8 points per cell for the outer integral, and the same rule on [cell start, r]
+// for Phi_j at each of them (degree 4) - nothing is approximated; the entries carry the rounding of extended precision and are rounded
+// to double once.
+void build_antiderivative_tables(double xmin, double xmax, int nc, int origin, int weight, AntiTables &out) {
+    const int nb = nc + 3;
+    pxr gx[8], gw[8];
+    gauss_legendre8(gx, gw);
+    const pxr DX = ((pxr)xmax - (pxr)xmin) / (pxr)nc;
+    auto phi = [](pxr t, int j) { return bspl<pxr>(t + 1.0L - j, 0); };       // node c + j at position t of cell c
+    // int_0^t w phi_{c + j} over the first t of cell c (in r: the factor DX included)
+    auto part = [&](int c, int j, pxr t) {
+        pxr s = 0.0L;
+        for (int q = 0; q < 8; q++) {
+            const pxr u = 0.5L * t * (1.0L + gx[q]);
+            const pxr r = (pxr)xmin + ((pxr)c + u) * DX;
+            s += 0.5L * t * gw[q] * (weight == SX_INT_W_R ? r : 1.0L) * phi(u, j);
+        }
+        return s * DX;
+    };
+    std::vector<pxr> ctot(nb, 0.0L), mtot(nb, 0.0L), band((size_t)nb * 7, 0.0L);
+    for (int c = 0; c < nc; c++)
+        for (int j = 0; j < 4; j++) {
+            ctot[c + j] += part(c, j, 1.0L);
+            for (int q = 0; q < 8; q++) mtot[c + j] += 0.5L * DX * gw[q] * phi(0.5L * (1.0L + gx[q]), j);
+        }
+    std::vector<pxr> below(nb, 0.0L);           // int w phi_j over the cells below the current one
+    for (int c = 0; c < nc; c++) {
+        for (int q = 0; q < 8; q++) {
+            const pxr t = 0.5L * (1.0L + gx[q]), wq = 0.5L * DX * gw[q];
+            pxr here[4];
+            for (int j = 0; j < 4; j++) here[j] = part(c, j, t);
+            for (int il = 0; il < 4; il++) {
+                const int i = c + il;
+                const pxr pi = wq * phi(t, il);
+                for (int j = std::max(0, i - 3); j <= std::min(nb - 1, i + 3); j++) {
+                    pxr Phi = below[j] + ((j >= c && j <= c + 3) ? here[j - c] : 0.0L);
+                    if (origin == SX_INT_FROM_HIGH) Phi = ctot[j] - Phi;
+                    band[(size_t)i * 7 + (j - i + 3)] += pi * Phi;
+                }
+            }
+        }
+        for (int j = 0; j < 4; j++) below[c + j] += part(c, j, 1.0L);
+    }
+    out.nb = nb; out.origin = origin; out.weight = weight;
+    out.P.assign((size_t)nb * 7, 0.0); out.c.assign(nb, 0.0); out.m.assign(nb, 0.0);
+    for (int s = 0; s < nb; s++) {
+        const int i = origin == SX_INT_FROM_HIGH ? nb - 1 - s : s;
+        out.c[s] = (double)ctot[i];
+        out.m[s] = (double)mtot[i];
+        for (int d = 0; d < 7; d++) out.P[(size_t)s * 7 + d] = (double)band[(size_t)i * 7 + (origin == SX_INT_FROM_HIGH ? 6 - d : d)];
+    }
+}
+
+// The projection that goes with the exact right-hand side: Gamma (P + eps_q Q) Gamma^T with P[i][j] = int phi_i phi_j the exact Gram matrix
+// (build_elliptic_bands' M0) - NOT build_spline_class's P, whose 3-point weights 8 : 5 : 8 define the model's discrete inner product and
+// pair only with right-hand sides formed by the same rule (its diagonal is 0.355 DX where int phi phi is 0.336 DX) - and Q[i][j] =
+// int phi_i''' phi_j''' (phi''' is constant on a cell: any rule is exact) with the class's own eps_q = (l_q DX / 2 pi)^6, Gamma and ranks.
+// Banded Cholesky in extended precision, rounded once: F [nb][4] = L[i][i - 3], L[i][i - 2], L[i][i - 1], 1 / L[i][i].
+bool build_antiderivative_class(double xmin, double xmax, int nc, double l_q, int bcl, int bcr, SplineClass &sc, std::vector<double> &F,
+                                std::string &err) {
+    const int nb = nc + 3;
+    if (bcl == SX_BC_PERIODIC || bcr == SX_BC_PERIODIC) { err = "PERIODIC radial boundary conditions on the destination variable are not supported"; return false; }
+    sc = SplineClass();
+    sc.bcl = bcl; sc.bcr = bcr;
+    sc.rl = bc_rank(bcl); sc.rr = bc_rank(bcr);
+    if (sc.rl < 0 || sc.rr < 0 || !boundary_rows(bcl, sc.gl) || !boundary_rows(bcr, sc.gr)) { err = "unknown radial boundary condition code"; return false; }
+    sc.nfree = nb - sc.rl - sc.rr;
+    const int n = sc.nfree;
+    if (n < 4) { err = "too few cells for the requested boundary conditions"; return false; }
+    sc.Gam = gamma_rows(sc, nb);
+    EllBands eb;
+    build_elliptic_bands(0, xmin, xmax, nc, eb);
+    const pxr DX = ((pxr)xmax - (pxr)xmin) / (pxr)nc, PI = acosl(-1.0L);
+    pxr eps_q = (pxr)l_q * DX / (2.0L * PI);
+    eps_q = eps_q * eps_q * eps_q; eps_q = eps_q * eps_q;
+    std::vector<pxr> B((size_t)nb * 7, 0.0L);
+    for (int c = 0; c < nc; c++)
+        for (int i = 0; i < 4; i++)
+            for (int j = 0; j < 4; j++)
+                B[(size_t)(c + i) * 7 + (j - i + 3)] += DX * bspl<pxr>(1.5L - i, 3) * bspl<pxr>(1.5L - j, 3) / (DX * DX * DX * DX * DX * DX);
+    for (size_t e = 0; e < B.size(); e++) B[e] = eb.M0[e] + eps_q * B[e];
+    auto Bm = [&](int i, int j) -> pxr { const int d = j - i + 3; return (d < 0 || d > 6) ? 0.0L : B[(size_t)i * 7 + d]; };
+    std::vector<pxr> Kb((size_t)n * 4), Lx((size_t)n * 4, 0.0L);       // [a][q]: entry (a, a - q), q = 0 .. 3
+    for (int a = 0; a < n; a++)
+        for (int q = 0; q < 4; q++) {
+            pxr s = 0.0L;
+            if (a - q >= 0)
+                for (const auto &ia : sc.Gam[a])
+                    for (const auto &jb : sc.Gam[a - q]) s += (pxr)ia.second * Bm(ia.first, jb.first) * (pxr)jb.second;
+            Kb[(size_t)a * 4 + q] = s;
+        }
+    for (int j = 0; j < n; j++)
+        for (int i = j; i <= std::min(j + 3, n - 1); i++) {
+            pxr s = Kb[(size_t)i * 4 + (i - j)];
+            for (int c = std::max(0, i - 3); c < j; c++) s -= Lx[(size_t)i * 4 + (i - c)] * Lx[(size_t)j * 4 + (j - c)];
+            if (i == j) {
+                if (!(s > 0.0L)) { err = "the projection matrix of the destination variable is not positive definite"; return false; }
+                Lx[(size_t)j * 4] = sqrtl(s);
+            } else {
+                Lx[(size_t)i * 4 + (i - j)] = s / Lx[(size_t)j * 4];
+            }
+        }
+    F.assign((size_t)nb * 4, 0.0);
+    for (int i = 0; i < n; i++) {
+        for (int q = 1; q < 4; q++)
+            if (i - q >= 0) F[(size_t)i * 4 + (3 - q)] = (double)Lx[(size_t)i * 4 + q];
+        F[(size_t)i * 4 + 3] = (double)(1.0L / Lx[(size_t)i * 4]);
+    }
+    return true;
+}
+
+void antiderivative_r_host(const AntiTables &t, const SplineClass &sc, const double *F, const double *a_src, double *a) {
+    const int nb = t.nb, n = sc.nfree, rl = sc.rl, rr = sc.rr;
+    const bool high = t.origin == SX_INT_FROM_HIGH;
+    auto row = [&](int s) { return high ? nb - 1 - s : s; };
+    auto ld = [&](int s) { return s >= 0 && s < nb ? a_src[row(s)] : 0.0; };
+    // the right-hand side in walk order: band product of the 7-row window, plus m times the sum of what has left the window
+    double w[7], S = 0.0;
+    for (int d = 0; d < 7; d++) w[d] = ld(d - 3);
+    for (int s = 0; s < nb; s++) {
+        double acc = 0.0;
+        for (int d = 0; d < 7; d++) acc = std::fma(t.P[(size_t)s * 7 + d], w[d], acc);
+        a[row(s)] = std::fma(t.m[s], S, acc);
+        S = std::fma(s >= 3 ? t.c[s - 3] : 0.0, w[0], S);
+        for (int d = 0; d < 6; d++) w[d] = w[d + 1];
+        w[6] = ld(s + 4);
+    }
+    // fold with Gamma, L y = Gamma b, L^T x = y, a = Gamma^T x
+    double br0 = 0.0, br1 = 0.0, bl0 = 0.0, bl1 = 0.0;
+    for (int q = 0; q < rr; q++) { br0 = std::fma(sc.gr[q][0], a[nb - 1 - q], br0); br1 = std::fma(sc.gr[q][1], a[nb - 1 - q], br1); }
+    for (int q = 0; q < rl; q++) { bl0 = std::fma(sc.gl[q][0], a[q], bl0); bl1 = std::fma(sc.gl[q][1], a[q], bl1); }
+    double y1 = 0.0, y2 = 0.0, y3 = 0.0;
+    for (int i = 0; i < n; i++) {
+        double s = a[rl + i];
+        if (i == 0) s += bl0;
+        if (i == 1) s += bl1;
+        if (i == n - 1) s += br0;
+        if (i == n - 2) s += br1;
+        const double *l = F + (size_t)i * 4;
+        double v = std::fma(-l[2], y1, s);
+        v = std::fma(-l[1], y2, v);
+        v = std::fma(-l[0], y3, v);
+        const double y = v * l[3];
+        y3 = y2; y2 = y1; y1 = y;
+        a[rl + i] = y;
+    }
+    double x1 = 0.0, x2 = 0.0, x3 = 0.0, xl0 = 0.0, xl1 = 0.0, xr0 = 0.0, xr1 = 0.0;
+    const double zero[4] = {0.0, 0.0, 0.0, 0.0};
+    const double *f1 = zero, *f2 = zero, *f3 = zero;
+    for (int i = n - 1; i >= 0; i--) {
+        const double *l = F + (size_t)i * 4;
+        double v = std::fma(-f1[2], x1, a[rl + i]);
+        v = std::fma(-f2[1], x2, v);
+        v = std::fma(-f3[0], x3, v);
+        const double x = v * l[3];
+        x3 = x2; x2 = x1; x1 = x;
+        f3 = f2; f2 = f1; f1 = l;
+        a[rl + i] = x;
+        if (i == 0) xl0 = x;
+        if (i == 1) xl1 = x;
+        if (i == n - 1) xr0 = x;
+        if (i == n - 2) xr1 = x;
+    }
+    for (int q = 0; q < rl; q++) a[q] = std::fma(sc.gl[q][1], xl1, sc.gl[q][0] * xl0);
+    for (int q = 0; q < rr; q++) a[nb - 1 - q] = std::fma(sc.gr[q][1], xr1, sc.gr[q][0] * xr0);
+}
+
 // ---------------------------------------------------------------------------------------------- Chebyshev
 // The collocation operators are assembled in extended precision and rounded to double once at the end: the
 // second-derivative matrix has entries O(N^4 / Lz^2), and products of double-rounded factors would carry a relative
@@ -661,6 +835,8 @@ static bool cheb_ca(const ChebX &x, int N, int Zb, int bcb, int bct, xmat &CA, s
     return true;
 }
 
+static void cheb_integral(int N, xreal Lz, xmat &Ic);
+
 bool build_cheb_ops(double zmin, double zmax, int nz, int Zb, int bcb, int bct, ChebOps &o, std::string &err) {
     if (nz < 4) { err = "zDim must be >= 4"; return false; }
     o.bcb = bcb;
@@ -676,8 +852,30 @@ bool build_cheb_ops(double zmin, double zmax, int nz, int Zb, int bcb, int bct, 
     xmat CB((size_t)Zb * N);
     for (int k = 0; k < Zb; k++)
         for (int n = 0; n < N; n++) CB[(size_t)k * N + n] = x.T[(size_t)k * N + n] / (2.0L * (N - 1));
-    // coefficient-space integral, zero at the bottom (x = +1 where every T_k = 1)
-    xmat Ic((size_t)N * N, 0.0L);
+    xmat Ic;
+    cheb_integral(N, Lz, Ic);
+    xmat CA;
+    if (!cheb_ca(x, N, Zb, bcb, bct, CA, err)) return false;
+    xmat M0, M1, M2, TI, TICA, Mint, Mdz, Mrec, Mdzz;
+    matmul(x.T, CA, M0, N, N, Zb);
+    matmul(x.TD, CA, M1, N, N, Zb);
+    matmul(x.TDD, CA, M2, N, N, Zb);
+    matmul(x.T, Ic, TI, N, N, N);
+    matmul(TI, CA, TICA, N, N, Zb);
+    matmul(TICA, CB, Mint, N, Zb, N);
+    matmul(M1, CB, Mdz, N, Zb, N);
+    matmul(M0, CB, Mrec, N, Zb, N);
+    matmul(M2, CB, Mdzz, N, Zb, N);
+    o.T = to_double(x.T); o.Dc = to_double(x.Dc); o.CB = to_double(CB); o.CA = to_double(CA);
+    o.M[0] = to_double(M0); o.M[1] = to_double(M1); o.M[2] = to_double(M2);
+    o.Mint = to_double(Mint); o.Mdz = to_double(Mdz); o.Mrec = to_double(Mrec); o.Mdzz = to_double(Mdzz);
+    o.zmin = zmin; o.zmax = zmax;
+    return true;
+}
+
+// coefficient-space integral [N][N], zero at the bottom (x = +1 where every T_k = 1)
+static void cheb_integral(int N, xreal Lz, xmat &Ic) {
+    Ic.assign((size_t)N * N, 0.0L);
     std::vector<xreal> ai(N);
     for (int j = 0; j < N; j++) {
         std::fill(ai.begin(), ai.end(), 0.0L);
@@ -695,22 +893,33 @@ bool build_cheb_ops(double zmin, double zmax, int nz, int Zb, int bcb, int bct, 
         ai[0] = -s;
         for (int i = 0; i < N; i++) Ic[(size_t)i * N + j] = ai[i];
     }
-    xmat CA;
+}
+
+// The operator of sx_antiderivative along z in coefficient space (include/scythe_hip.h, "antiderivatives"): the truncated b
+// coefficients of the source -> those of F.  V = T Ic CA [N][Zb] holds F(z_n) = int_{zmin}^{z_n} per unit source coefficient (ChebOps::Mint
+// before its CB); FROM_HIGH takes F(zmax) - F(z_n), the top level being row N - 1; Z = CB V.  Returned transposed and zero-padded, as
+// k_antiderivative_z reads its operator fragments.
+bool build_antiderivative_z(double zmin, double zmax, int nz, int Zb, int bcb, int bct, int origin, std::vector<double> &ZT, int &Kp, int &Mp,
+                            std::string &err) {
+    if (nz < 4) { err = "zDim must be >= 4"; return false; }
+    const int N = nz;
+    ChebX x;
+    cheb_factors(zmin, zmax, N, x);
+    xmat Ic, CA, TI, V, Z, CB((size_t)Zb * N);
+    cheb_integral(N, (xreal)zmax - (xreal)zmin, Ic);
     if (!cheb_ca(x, N, Zb, bcb, bct, CA, err)) return false;
-    xmat M0, M1, M2, TI, TICA, Mint, Mdz, Mrec, Mdzz;
-    matmul(x.T, CA, M0, N, N, Zb);
-    matmul(x.TD, CA, M1, N, N, Zb);
-    matmul(x.TDD, CA, M2, N, N, Zb);
+    for (int k = 0; k < Zb; k++)
+        for (int n = 0; n < N; n++) CB[(size_t)k * N + n] = x.T[(size_t)k * N + n] / (2.0L * (N - 1));
     matmul(x.T, Ic, TI, N, N, N);
-    matmul(TI, CA, TICA, N, N, Zb);
-    matmul(TICA, CB, Mint, N, Zb, N);
-    matmul(M1, CB, Mdz, N, Zb, N);
-    matmul(M0, CB, Mrec, N, Zb, N);
-    matmul(M2, CB, Mdzz, N, Zb, N);
-    o.T = to_double(x.T); o.Dc = to_double(x.Dc); o.CB = to_double(CB); o.CA = to_double(CA);
-    o.M[0] = to_double(M0); o.M[1] = to_double(M1); o.M[2] = to_double(M2);
-    o.Mint = to_double(Mint); o.Mdz = to_double(Mdz); o.Mrec = to_double(Mrec); o.Mdzz = to_double(Mdzz);
-    o.zmin = zmin; o.zmax = zmax;
+    matmul(TI, CA, V, N, N, Zb);
+    if (origin == SX_INT_FROM_HIGH)
+        for (int n = 0; n < N; n++)         // the top row last: it becomes zero
+            for (int k = 0; k < Zb; k++) V[(size_t)n * Zb + k] = V[(size_t)(N - 1) * Zb + k] - V[(size_t)n * Zb + k];
+    matmul(CB, V, Z, Zb, N, Zb);
+    Kp = (Zb + 3) & ~3; Mp = (Zb + 15) & ~15;
+    ZT.assign((size_t)Kp * Mp, 0.0);
+    for (int i = 0; i < Zb; i++)
+        for (int k = 0; k < Zb; k++) ZT[(size_t)k * Mp + i] = (double)Z[(size_t)i * Zb + k];
     return true;
 }
 

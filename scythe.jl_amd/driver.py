@@ -591,6 +591,39 @@ class ModelRun:
         Arguments as for streamfunction.  With into=None it shares streamfunction's companion: pass a Grid of your own to keep both."""
         return self._invert_wind("divergence", u, v, alpha, into, var)
 
+    def antiderivative(self, var, axis="r", origin="low", weight_r=False, into=None, var_dst=1):
+        """The integral of variable `var` of time n up to a point along r or z, on the device (Grid.antiderivative): returns the
+        Grid that holds it (a cached one-variable companion unless `into` names one), to be sampled like any field.  One-tile
+        patches."""
+        if self.num_tiles > 1:
+            raise ValueError("antiderivative: one-tile patches only (num_tiles = %d)" % self.num_tiles)
+        self._check_stream()
+        return self.tiles[0].antiderivative(var, axis, origin, weight_r, into, var_dst)
+
+    def column_integral(self, var):
+        """int_{zmin}^{zmax} f dz of variable `var` in every column of the grid: (points [columns, n_coord - 1] - r[, lambda] of the
+        columns in gridpoint order -, values [columns]); the vertical antiderivative sampled at zmax with the wavenumber cut of each
+        ring (precipitable water, the mass of a column).  One-tile RZ / RLZ patches."""
+        F = self.antiderivative(var, "z")
+        pts = self.gridpoints()
+        top = pts[self.patch.zDim - 1::self.patch.zDim]
+        return top[:, :-1].copy(), F.evaluate(top)[:, 0, 0]
+
+    def inside_radius(self, var, radii=None):
+        """int_{xmin}^{r} f s ds of the azimuthal mean (wavenumber 0) of variable `var` at the radii given (default: the rings'):
+        (r [n], values [n] or [n, zDim] on a grid with a vertical, at the levels).  2 pi times it is the integral over the disc: the
+        circulation of a vorticity, the mass of a depth.  One-tile patches."""
+        F = self.antiderivative(var, "r", weight_r=True)
+        if radii is None:
+            r = self.gridpoints()[:, 0]
+            radii = r[np.concatenate([[True], r[1:] != r[:-1]])]
+        radii = np.atleast_1d(np.asarray(radii, dtype=np.float64))
+        geo = self.patch.geometry
+        z = self.gridpoints()[:self.patch.zDim, -1] if "Z" in geo else np.zeros(1)
+        cols = [np.repeat(radii, len(z))] + ([np.zeros(len(radii) * len(z))] if "L" in geo else []) + ([np.tile(z, len(radii))] if "Z" in geo else [])
+        val = F.evaluate(np.stack(cols, axis=1), k_band=(0, 0) if "L" in geo else None)[:, 0, 0].reshape(len(radii), len(z))
+        return radii, (val if "Z" in geo else val[:, 0])
+
     def _tiles_in_order(self):
         """the local tiles by tile number"""
         return [g for _, g in sorted(zip(self.tile_ids, self.tiles), key=lambda tg: tg[0])]

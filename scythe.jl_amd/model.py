@@ -432,6 +432,38 @@ class Grid:
         L.check(self._lib.sx_elliptic_solve(self._h, L.ELL_KIND[rhs[0]], src[0], src[1] if len(src) > 1 else 0, float(alpha), into._h, dst))
         return into
 
+    # -- antiderivatives (sx_antiderivative)
+    def antiderivative(self, var, axis="r", origin="low", weight_r=False, dst=None, var_dst=1):
+        """The integral of variable `var` (a name or a 1-based index) up to a point, on the device from the A coefficients the tile
+        holds now (sx_antiderivative), written as the A coefficients of variable `var_dst` of the Grid `dst`; returns that Grid, on
+        which evaluate, harmonics, spectrum, crossings, extrema and tileTransform_ + physical then sample it like any field.
+        axis="r": F(r) = int_{xmin}^{r} f ds (origin="low") or int_{r}^{xmax} f ds ("high"); weight_r=True integrates r f (the area
+        element of a vortex: circulation, enclosed mass).  axis="z": F(z) = int_{zmin}^{z} f dz' or int_{z}^{zmax} f dz'.
+        dst=None makes a one-variable companion on first use and keeps it, one per set of boundary conditions: the source's own
+        vertical and radial conditions carried over, except that along the axis of integration the result is left free (R0) - an
+        integral from xmin does not vanish at xmax.  dst=self writes a spare variable of this Grid.  One-tile patches only."""
+        if axis not in L.INT_AXIS or origin not in L.INT_ORIGIN:
+            raise ValueError("axis must be 'r' or 'z' and origin 'low' or 'high'")
+        src = self._parcel_var(var)
+        if dst is None:
+            gp = self.patch_params
+            names = gp.var_names()
+            if not 1 <= src <= len(names):
+                raise ValueError("variable index %d out of range" % src)
+            n0 = names[src - 1]
+            of = lambda d, table: bc_name((d or {}).get(n0, "R0"), table)
+            bcl, bcr = of(gp.BCL, _SPLINE_BCS), of(gp.BCR, _SPLINE_BCS)
+            bcl0 = bc_name((gp.BCL_k0 or {}).get(n0, (gp.BCL or {}).get(n0, "R0")), _SPLINE_BCS)
+            bcb, bct = of(gp.BCB, _CHEB_BCS), of(gp.BCT, _CHEB_BCS)
+            key = ("R0", "R0", "R0", bcb, bct) if axis == "r" else (bcl, bcl0, bcr, "R0", "R0")
+            cache = self.__dict__.setdefault("_antiderivative_companions", {})
+            if key not in cache:
+                cache[key] = companion_grid(gp, bcl=key[0], bcl_k0=key[1], bcr=key[2], bcb=key[3], bct=key[4], name="F")
+            dst = cache[key]
+        vd = dst.patch_params.vars[var_dst] if isinstance(var_dst, str) else int(var_dst)
+        L.check(self._lib.sx_antiderivative(self._h, src, L.INT_AXIS[axis], L.INT_ORIGIN[origin], int(bool(weight_r)), dst._h, vd))
+        return dst
+
     def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
         """The azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: complex128 ndarray indexed
         [ir, iz, k, v, s], k = 0 .. kDim, s over `slots` in the order u, r, rr, z, zz (a view of the library's buffer).  The state is
@@ -861,6 +893,24 @@ def elliptic_check(patch: GridParameters, var, k, alpha, g):
     a = np.zeros_like(rhs)
     L.check(L.load().sx_elliptic_check(C.byref(d), v, int(k), float(alpha), rhs.ctypes.data_as(L.P_D), a.ctypes.data_as(L.P_D)))
     return a
+
+
+def antiderivative_check(patch: GridParameters, var, var_dst, axis="r", origin="low", weight_r=False, k=0, a_src=None):
+    """The host statement of Grid.antiderivative for ONE column: a_src [num_cells + 3] (axis "r": wavenumber k selects the
+    boundary-condition class of `var_dst`) or [b_zDim] (axis "z"), both variables (names or 1-based indices) of the one patch;
+    the same host-built tables and the device kernel's arithmetic (sx_antiderivative_check: no handle, no device)."""
+    if axis not in L.INT_AXIS or origin not in L.INT_ORIGIN:
+        raise ValueError("axis must be 'r' or 'z' and origin 'low' or 'high'")
+    d, keep = grid_desc(patch)
+    vs, vd = (patch.vars[v] if isinstance(v, str) else int(v) for v in (var, var_dst))
+    col = np.ascontiguousarray(a_src, dtype=np.float64)
+    want = patch.num_cells + 3 if axis == "r" else int(d.b_zDim if d.b_zDim > 0 else 0)
+    if col.ndim != 1 or (want and col.shape != (want,)):
+        raise ValueError("a_src must have %d entries" % want)
+    out = np.zeros_like(col)
+    L.check(L.load().sx_antiderivative_check(C.byref(d), vs, vd, L.INT_AXIS[axis], L.INT_ORIGIN[origin], int(bool(weight_r)), int(k),
+                                             col.ctypes.data_as(L.P_D), out.ctypes.data_as(L.P_D)))
+    return out
 
 
 def getGridpoints(grid: Grid):
