@@ -675,6 +675,73 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
                  int32_t *count /*[n_levels, n_rays]*/, int32_t *status /*[n_rays]*/, double *profiles /*may be NULL*/);
 int sx_bracket_step(double *state /*[7]*/, int32_t *flags /*[2]*/, int32_t first, double fx, double width_tol, int32_t *status);
 
+/* --- isosurfaces of field programs in columns: heights, fields on them ---------------------------------------------------
+ * At what height, and what is there: the heights at which a field program reaches given values in columns (the freezing level, the
+ * top of the inflow layer, a cloud top, an isentropic surface) and other outputs of the program evaluated on that surface.  RZ and
+ * RLZ grids; the transpose of sx_crossings.
+ * Program: exactly sx_reduce's (the same terms[n_terms][11], coef and limits, validated by sx_reduce_planes itself with the slot rules
+ * of SX_REDUCE_PHYSICAL) with 1 + n_carry outputs, 0 <= n_carry <= 8: output 0 is the surface quantity g, outputs 1 .. n_carry are
+ * carried.  Every output is formed in plain fp64, in term order, starting from +0.0.  Column c is (r_c) on RZ and (r_c, lambda_c) on
+ * RLZ: columns[n_cols, n_coord - 1] column-major.  Every field is the CONTINUOUS spectral function of sx_evaluate with the
+ * SX_EVAL_ALL_K truncation, summed from the A coefficients the handle holds now.  For each of the n_levels <= 8 levels c_j the call
+ * returns the heights where d = g(z) - c_j changes sign, ordered upward.
+ * Stage 1, k_column_profiles.  In a column the sums over the radial nodes and over lambda do not depend on z, so a field in a column
+ * is a Chebyshev series in z.  For the profile kind (var, sr, sl), sr the radial and sl the azimuthal derivative order,
+ *     C[zm] = sum_blk sum_{node = cell .. cell + 3} A[zm, blk, node] phi_node^(sr)(r_c) / DX^sr F_blk^(sl)(lambda_c),   zm < b_zDim,
+ * cell the radial cell of r_c.  Slots u, z, zz share (0, 0); r and rr take sr = 1, 2; l and ll take sl = 1, 2: at most 16 kinds per
+ * program, numbered in the order the program first names them (sx_isosurface_check returns the count).  The weights are formed on the
+ * device from the column coordinates with k_parcels' arithmetic: phi in plain fp64 from delta = (r - x_node) / DX, cos / sin of k lambda
+ * (a lambda within [-2 pi, 2 pi] is used as given; outside, it is reduced into (-pi, pi] in extended precision on the host).  The host
+ * sorts the columns by radial cell and cuts each cell's columns into batches of at most 16.  RLZ: per variable and batch the profiles
+ * are ONE product on the f64 matrix cores, z-modes x columns over K = (block, node); the K order is block 0, 2, 3, ... (the padding
+ * block 1 is never read), node 0 .. 3 within a block, whatever the columns are, and a short batch is padded with zero weights.  RZ: K
+ * is the 4 nodes, one lane per output, the same sum.  A column's profile is bitwise independent of the other columns of the call, of
+ * their number and of their order.
+ * Series.  The full series of a profile is a = CA C (zDim coefficients), CA the projection of the variable's (bcb, bct) class that
+ * sx_evaluate and k_parcels use, rounded to fp64 once; a' = Dc a and a'' = Dc a' are its derivatives, Dc the coefficient-space d/dz
+ * rounded to fp64 once.  Every entry of the three is summed in index order from +0.0, product then sum, no fused multiply-add.  A field
+ * at height z is s(z) = sum_n a_n t_n(x), x = (z - mid) / (-Lz / 2) clamped to [-1, 1], t_0 = 1, t_n = 2 T_n, t_{zDim-1} = T_{zDim-1}; the
+ * z and zz slots use a' and a''.  T_n is formed by the RECURRENCE T_0 = 1, T_1 = x, T_{n+1} = 2 x T_n - T_{n-1}, and s is summed for
+ * n ascending from a_0, product then sum, no fused multiply-add: this is the definition (it is not k_parcels' c_n cos(n acos x), whose
+ * rounding differs).  It is ONE function compiled for host and device: the kernel uses it at stations, at trial points and for the
+ * carried outputs, and sx_column_series runs it on the host: out[3] = s, and the same function on a' and a'' formed as above.
+ * Stage 2, k_isosurface, one wave per column.  Stations: the zDim levels, bottom to top (the doubles sx_get_gridpoints returns; the
+ * ends are stations), taken by the lanes in chunks of 64.  values (may be NULL) [zDim, n_cols] receives g at the stations exactly as
+ * the kernel formed it.  Sign rule, NaN rule (bit 0 of the column's status), numbering, refinement and the returned end are
+ * sx_crossings': with neg(d) = (d < 0) the interval [s_i, s_i+1] holds a crossing when neg(d_i) != neg(d_i+1) and neither is NaN, so a
+ * root exactly on a station is counted once; dir is +1 where d rises upward; each crossing is refined by its own lane with the bracket
+ * iteration of sx_bracket_step until b - a <= width_tol = tol (zmax - zmin), d == 0 exactly, or max_iter steps (bit 1; a NaN at a trial
+ * point: bit 2).  tol <= 0 selects 1e-9, max_iter <= 0 selects 60.  The carried outputs are evaluated at the returned height.
+ * LIMIT: two sign changes inside one station interval are not seen.
+ * Results, column-major: height[max_cross, n_levels, n_cols] and dir of the same shape hold the first max_cross crossings upward,
+ * carry[n_carry, max_cross, n_levels, n_cols] the carried outputs there; unused entries are NaN (height, carry) and 0 (dir).
+ * count[n_levels, n_cols] is the number of crossings FOUND and may exceed max_cross; status[n_cols]; profiles (may be NULL)
+ * [b_zDim, n_profiles, n_cols].  carry is NULL if and only if n_carry == 0.
+ * Guarantees.  No atomics, and nothing is summed across columns.  The result for a column and a level is bitwise independent of the
+ * other columns of the call, of their number and order, of the other levels, of n_carry, of whether values / profiles are asked for,
+ * and of the launch shape.  Reads A only (a deferred diagnostic variable is brought up to date first, as for every reader of A):
+ * `physical`, var_np1, the tendency history, the B arrays, parcels, statistics and captured graphs stay bitwise as they are.
+ * Refused, with a message and before anything is written: a null pointer with a non-zero count; whatever sx_reduce_planes refuses; a
+ * term whose out is above n_carry; n_carry outside [0, 8]; n_levels outside [1, 8]; max_cross outside [1, 16]; a grid without a
+ * vertical (R, RL); a NaN / Inf coordinate or level; an r outside the tile's ends; a non-finite tol; more than 2^20 columns; a
+ * negative r_power with a column at r == 0; a handle that is not a one-tile patch; a grid whose per-workgroup tables pass the 64 KB
+ * of LDS: k_column_profiles needs 32 (kDim + 1) + 2304 <= 8192 doubles (RLZ: cos / sin of 16 columns and the staged tile of A),
+ * k_isosurface (planes named + 2) zDim <= 8192 doubles.  n_cols == 0 succeeds and writes nothing.
+ * Runs on the handle's stream and returns after the copy-out.  sx_kernel_bytes("k_column_profiles") gives the live A elements of the
+ * 4 node rows once per batch and variable (RZ: per column and profile) and the column coordinates in + the profiles out of the last
+ * call, sx_kernel_bytes("k_isosurface") the profiles in + heights, directions, carried outputs, counts, status and station values out.
+ *
+ * sx_isosurface_check validates the grid and the program on the host (pure helper, no handle and no device: every refusal above that
+ * needs neither the columns nor the handle) and returns the number of profiles. */
+int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_carry, int64_t n_cols,
+                  const double *columns /*[n_cols, n_coord - 1]: r (RZ); r, lambda (RLZ)*/, int32_t n_levels, const double *levels,
+                  double tol, int32_t max_iter, int32_t max_cross, double *height /*[max_cross, n_levels, n_cols]*/,
+                  int32_t *dir /*same shape*/, int32_t *count /*[n_levels, n_cols]*/, int32_t *status /*[n_cols]*/,
+                  double *carry /*[n_carry, max_cross, n_levels, n_cols]; NULL iff n_carry == 0*/, double *values /*[zDim, n_cols], may be NULL*/,
+                  double *profiles /*[b_zDim, n_profiles, n_cols], may be NULL*/);
+int sx_column_series(int32_t zDim, double zmin, double zmax, const double *a /*[zDim]*/, double z, double *out /*[3]*/);
+int sx_isosurface_check(const sx_grid_desc *grid, int32_t n_terms, const int32_t *terms, int32_t n_carry, int32_t *n_profiles);
+
 /* --- histograms of field programs: CFADs, areas, quantiles -------------------------------------------------------------
  * How much of the domain holds which values: the area inside an isotach, integrated kinetic energy above thresholds, contoured
  * frequency-by-altitude diagrams, percentiles - without pulling `physical` to the host.

@@ -6,7 +6,7 @@ from .model import (CubicBSpline, Chebyshev, GridParameters, ModelParameters, Gr
                     calcTileSizes, num_columns, checkCFL, comm_unique_id, eval_basis, regular_gridpoints,
                     cartesian_gridpoints, Program, reduce_weights, reduce_planes, pack_reduce_program, invariants,
                     spectrum_check, pack_spectrum_pairs, companion_grid, elliptic_check, antiderivative_check, Refined, free_mask, newton_step,
-                    Crossings, bracket_step, Distribution, distribution_slot, distribution_check,
+                    Crossings, bracket_step, Isosurface, isosurface_check, column_series, columns_of, Distribution, distribution_slot, distribution_check,
                     pack_vortex_fields, default_vortex_n_az, vortex_check, Statistics, pack_statistics)
 from .driver import (PatchLayout, LocalExchange, DistExchange, A2ALayout, LocalA2AExchange, DistA2AExchange, LibExchange, LocalLibExchange, ModelRun,
                      integrate_model, Located, WindRadii, Cfad, Exceedance, Quantile, VortexProfile, Swath)

@@ -147,6 +147,10 @@ SYMBOLS = {
     "sx_crossings": (C.c_int, [_H, C.c_int32, P_D, P_I32, C.c_int64, P_D, C.c_int32, P_D, C.c_double, C.c_int32, C.c_int32, P_D, P_I32, P_I32,
                                 P_I32, P_D]),
     "sx_bracket_step": (C.c_int, [P_D, P_I32, C.c_int32, C.c_double, C.c_double, P_I32]),
+    "sx_isosurface": (C.c_int, [_H, C.c_int32, P_D, P_I32, C.c_int32, C.c_int64, P_D, C.c_int32, P_D, C.c_double, C.c_int32, C.c_int32, P_D, P_I32,
+                                 P_I32, P_I32, P_D, P_D, P_D]),
+    "sx_column_series": (C.c_int, [C.c_int32, C.c_double, C.c_double, P_D, C.c_double, P_D]),
+    "sx_isosurface_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, P_I32, C.c_int32, P_I32]),
     "sx_distribution": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_D, P_I64, P_D]),
     "sx_distribution_slot": (C.c_int, [C.c_int32, P_D, C.c_double, P_I32]),
     "sx_distribution_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.c_int32, C.c_int32, P_I32, C.c_int32, C.c_int32, P_D]),

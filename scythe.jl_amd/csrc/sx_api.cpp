@@ -736,7 +736,7 @@ int sx_destroy(sx_handle *h) {
     comm_release(h);
     iface_release(h);
     pcr_release(h);
-    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives: their device memory goes with them
+    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives, isosurfaces: their device memory goes with them
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -1496,6 +1496,8 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_refine") b = extrema_bytes(h, true);                   // the last refinement's evaluations x 4 rows x b_zDim x (2 kDim + 1) of A
     else if (k == "k_ray_profiles") b = crossings_bytes(h, false);          // the last call's A columns of the variables named + ray coordinates in, profiles out
     else if (k == "k_crossings") b = crossings_bytes(h, true);              // ... profiles in, radii, directions, counts and status out
+    else if (k == "k_column_profiles") b = isosurface_bytes(h, false);      // the last call's live A elements of the 4 node rows per batch and variable + column coordinates in, profiles out
+    else if (k == "k_isosurface") b = isosurface_bytes(h, true);            // ... profiles in, heights, directions, carried outputs, counts, status and station values out
     else if (k == "k_distribution") b = diag_bytes(DIAG_DISTRIBUTION);      // the last call's planes x N x 8 (4 for an fp32-stored plane)
     else if (k == "k_vortex_rings") b = diag_bytes(DIAG_VORTEX);            // the last call's live circles x n_az x distinct source variables x 4 rows x b_zDim x (2 kDim + 1) of A
     else if (k == "k_stats") b = diag_bytes(DIAG_STATS);                    // the last sample's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 32

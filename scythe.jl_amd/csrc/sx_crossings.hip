@@ -15,6 +15,7 @@
 // program from the profiles (4 multiply-adds per plane), compare neighbours (the last lane's value is carried into the next chunk),
 // number the crossings of a level outward with a ballot, and every crossing is refined by its own lane with bracket_step - the
 // function sx_bracket_step runs on the host.  No atomics, nothing summed across rays.
+#include "sx_bracket.hpp"
 #include "sx_redprog.hpp"
 #include <algorithm>
 #include <cmath>
@@ -157,7 +158,7 @@ __global__ __launch_bounds__(64) void k_ray_profiles(ProfArgs a) {
     }
 }
 
-// ---- what host and device share: the stations, the basis, the bracket step -------------------------------------------------------
+// ---- what host and device share: the stations, the basis (cross_bspl and the bracket step: sx_bracket.hpp) -------------
 struct CrossGeom {
     double xmin, DX, lo, hi;              // the tile's radial extent as eval_radius_ok reads it
     int cell0, ncells, n_st;              // stations: lo, the 3 ncells radial gridpoints, hi
@@ -170,17 +171,6 @@ __host__ __device__ inline double cross_station(const CrossGeom &G, int s) {
     const int i = s - 1, mu = i % MUBAR;
     const double o = sqrt(3.0 / 5.0) / 2.0;
     return G.xmin + G.DX * (G.cell0 + i / MUBAR + 0.5 + (mu == 0 ? -o : mu == 1 ? 0.0 : o));
-}
-
-// d-th derivative of the cardinal cubic B-spline (bspl of sx_setup.cpp)
-__host__ __device__ inline double cross_bspl(double delta, int d) {
-    const double z = fabs(delta);
-    if (z >= 2.0) return 0.0;
-    const double s = delta > 0 ? 1.0 : -1.0;
-    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
-    if (d == 0) return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
-    if (d == 1) return -s * (p * p / 2.0 - 2.0 * q * q);
-    return p - 4.0 * q;
 }
 
 // phi, phi', phi'' of the 4 nodes of r's cell (sx_eval_basis' statement in plain fp64); returns the cell = patch row of the first node
@@ -196,48 +186,6 @@ __host__ __device__ inline int cross_basis(const CrossGeom &G, double r, double 
     }
     return cell;
 }
-
-// The bracket of one crossing: d = g - c changes sign between a (inner) and b (outer); fa, fb are d there, ga, gb the values the false
-// position is drawn through (an end kept twice in a row has its value halved: Illinois), x the trial point whose d the next step takes
-struct Bracket {
-    double a, fa, b, fb, ga, gb, x;
-    int side, bis;                        // the end the last step replaced (-1 inner, +1 outer, 0 none yet); next trial by bisection
-};
-__host__ __device__ inline bool bracket_done(const Bracket &B, double wtol) { return B.fa == 0.0 || B.fb == 0.0 || !(B.b - B.a > wtol); }
-__host__ __device__ inline void bracket_trial(Bracket &B) {
-    double x = B.b - (B.gb * (B.b - B.a)) / (B.gb - B.ga);
-    if (B.bis || !(x > B.a && x < B.b)) x = B.a + 0.5 * (B.b - B.a);
-    B.x = x;
-}
-// 0: finished, -1: evaluate d at x and step
-__host__ __device__ inline int bracket_start(Bracket &B, double wtol) {
-    B.ga = B.fa; B.gb = B.fb; B.side = 0; B.bis = 0; B.x = B.a;
-    if (bracket_done(B, wtol)) return 0;
-    bracket_trial(B);
-    return -1;
-}
-// One step with fx = d(x): 0 finished, -1 go on, 2 fx is NaN (the bracket stays).  The bracket always holds the sign change; a step
-// that does not halve it is followed by a bisection.
-__host__ __device__ inline int bracket_step(Bracket &B, double fx, double wtol) {
-    if (fx != fx) return 2;
-    const double w0 = B.b - B.a;
-    if (fx == 0.0) { B.a = B.b = B.x; B.fa = B.fb = B.ga = B.gb = 0.0; return 0; }
-    if ((fx < 0.0) == (B.fa < 0.0)) {
-        B.a = B.x; B.fa = B.ga = fx;
-        if (B.side < 0) B.gb *= 0.5;
-        B.side = -1;
-    } else {
-        B.b = B.x; B.fb = B.gb = fx;
-        if (B.side > 0) B.ga *= 0.5;
-        B.side = 1;
-    }
-    B.bis = B.b - B.a > 0.5 * w0;
-    if (bracket_done(B, wtol)) return 0;
-    bracket_trial(B);
-    return -1;
-}
-// the end with the smaller |d|, the inner one on a tie
-__host__ __device__ inline double bracket_root(const Bracket &B) { return fabs(B.fa) <= fabs(B.fb) ? B.a : B.b; }
 
 // ---- stage 2: scan and refine ------------------------------------------------------------------------------------------------------
 struct CrossArgs {

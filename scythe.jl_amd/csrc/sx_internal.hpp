@@ -116,6 +116,7 @@ bool desc_ok(const sx_grid_desc *gd, const char *who);   // what every pure host
 EvalGeom desc_geom(const sx_grid_desc *gd);              // of a descriptor that desc_ok has passed (vertical fields: the caller checks them)
 // phi, phi', phi'' at the 4 nodes of r's cell ([3][4]), that cell, and the wavenumber cap, as the kernels' point records hold them
 void eval_radial_pt(const EvalGeom &g, double r, int flags, double (&wr)[12], int &cell, int &kcap);
+std::vector<double> cheb_dc(double zmin, double zmax, int nz);   // [nz][nz] coefficient-space d/dz (ChebOps::Dc): extended precision, rounded once
 bool build_eval_vert(double zmin, double zmax, int nz, int Zb, int bcb, int bct, EvalVert &out, std::string &err);
 void eval_vert_weights(const EvalVert &ev, double zmin, double zmax, int nz, int Zb, double z, double *w /*[3][Zb]*/);
 // eval_vert_weights of n heights as k_harmonics and k_spectrum stage them: [cls][height tile][row 3][Zp][16 heights], Zp = Zb rounded
@@ -169,7 +170,7 @@ void antiderivative_r_host(const AntiTables &t, const SplineClass &sc, const dou
 bool build_antiderivative_z(double zmin, double zmax, int nz, int Zb, int bcb, int bct, int origin, std::vector<double> &ZT, int &Kp, int &Mp,
                             std::string &err);
 
-// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics, sx_stats_*, sx_antiderivative) ----
+// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics, sx_stats_*, sx_antiderivative, sx_isosurface) ----
 template <class T>
 struct DevBuf {         // owns one device array; reads as the pointer
     T *p = nullptr;
@@ -206,7 +207,7 @@ struct DiagState {      // what one of these entry points keeps with the handle:
     double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
     virtual ~DiagState() = default;
 };
-enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_ANTIDERIVATIVE, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
+enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_ANTIDERIVATIVE, DIAG_ISOSURFACE, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them
 struct EvalClasses {    // the vertical boundary-condition classes of a handle's variables (eval_classes)
     std::vector<EvalVert> vert;       // empty without a vertical
     std::vector<int> vcls;            // [V] class of each variable
@@ -542,6 +543,7 @@ __device__ inline double parcel_bspl(double delta) {
 double extrema_bytes(const sx_handle *h, bool refine);   // bytes of the last sx_extrema (k_extrema) / sx_extremum_refine (k_refine)
 double crossings_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_crossings: k_ray_profiles / k_crossings (sx_crossings.hip)
 double antiderivative_bytes(const sx_handle *h, bool vertical);   // bytes of the last sx_antiderivative along r (k_antiderivative_r) / z (k_antiderivative_z)
+double isosurface_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_isosurface: k_column_profiles / k_isosurface (sx_isosurface.hip)
 int default_bzdim(int zDim);                   // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);

@@ -1050,6 +1050,12 @@ void eval_radial_pt(const EvalGeom &g, double r, int flags, double (&wr)[12], in
     kcap = eval_kcap(g, r, flags);
 }
 
+std::vector<double> cheb_dc(double zmin, double zmax, int nz) {
+    ChebX x;
+    cheb_factors(zmin, zmax, nz, x);
+    return to_double(x.Dc);
+}
+
 // CA, Dc CA, Dc Dc CA of a vertical boundary-condition class, [nz][Zb] each, kept in extended precision
 bool build_eval_vert(double zmin, double zmax, int nz, int Zb, int bcb, int bct, EvalVert &o, std::string &err) {
     if (nz < 4) { err = "zDim must be >= 4"; return false; }

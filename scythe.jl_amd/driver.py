@@ -913,6 +913,52 @@ class ModelRun:
                     quad[:, col] = np.where(ok.any(axis=1), np.where(ok, sel, -np.inf).max(axis=1), np.nan)
         return WindRadii(thr, lam, radii, quad)
 
+    @staticmethod
+    def _pick_height(res, which, rising=None):
+        """[n_cols] row index into res.height[:, 0, :] of the lowest / highest kept crossing (rising: among those with dir == +1,
+        False: -1), -1 where the column has none"""
+        hgt, dr = res.height[:, 0, :], res.dir[:, 0, :]
+        ok = ~np.isnan(hgt) & (True if rising is None else dr == (1 if rising else -1))
+        first = np.argmax(ok, axis=0)
+        last = ok.shape[0] - 1 - np.argmax(ok[::-1], axis=0)
+        return np.where(ok.any(axis=0), first if which == "lowest" else last, -1)
+
+    def height_where(self, terms, level, columns, which="lowest", rising=None):
+        """The height at which the one-output program `terms` (as for Grid.reduce) crosses `level` in every column r[, lambda]
+        (Grid.isosurface, up to 16 crossings per column kept): the vertical radius_where.  which="lowest" / "highest"; rising=True
+        keeps the crossings where the program rises upward through the level, False those where it falls, None all.  Returns
+        ndarray [n_cols], NaN where a column has no such crossing (or, highest, more than 16 crossings).  Reads the A coefficients
+        as they stand; one-tile patches."""
+        if which not in ("lowest", "highest"):
+            raise ValueError("which must be 'lowest' or 'highest'")
+        g = self._one_tile("height_where")
+        res = g.isosurface(terms, [level], columns, max_cross=16)
+        k = self._pick_height(res, which, rising)
+        out = np.where(k >= 0, res.height[np.maximum(k, 0), 0, np.arange(len(k))], np.nan)
+        return np.where((which == "highest") & (res.count[0] > 16), np.nan, out)
+
+    def on_surface(self, surface_terms, level, fields, columns, which="lowest"):
+        """Fields on a surface: the height at which the one-output program `surface_terms` crosses `level` in every column
+        (which="lowest" / "highest" crossing), and `fields` there - variable names (or 1-based indices) or term lists as for
+        Grid.reduce (their `out` is ignored), which become the carried outputs of ONE Grid.isosurface call (at most 8).  Returns
+        (height [n_cols], values [n_fields, n_cols]), NaN where a column has no crossing.  One-tile patches."""
+        if which not in ("lowest", "highest"):
+            raise ValueError("which must be 'lowest' or 'highest'")
+        g = self._one_tile("on_surface")
+        prog = [(0, c, p, f) for (_, c, p, f) in surface_terms]
+        for o, fld in enumerate(fields):
+            terms = [(0, 1.0, 0, [(fld, "")])] if isinstance(fld, (str, int, np.integer)) else fld
+            prog += [(1 + o, c, p, f) for (_, c, p, f) in terms]
+        res = g.isosurface(prog, [level], columns, carry=len(fields), max_cross=16)
+        k = self._pick_height(res, which)
+        cols = np.arange(len(k))
+        none = (k < 0) | ((which == "highest") & (res.count[0] > 16))
+        hgt = np.where(none, np.nan, res.height[np.maximum(k, 0), 0, cols])
+        vals = np.zeros((len(fields), len(k)))
+        if len(fields):
+            vals = np.where(none[None, :], np.nan, res.carry[:, :, 0, :][:, np.maximum(k, 0), cols])
+        return hgt, vals
+
     def spectrum(self, pairs, kind="ring"):
         """Azimuthal power and cross spectra over the local tiles (Grid.spectrum; reads A: no transform is run).  kind="domain":
         ndarray [kDim + 1, n_pairs], the tile results summed in tile order.  kind="ring": [kDim + 1, rings, n_pairs], the rings of

@@ -647,6 +647,40 @@ class Grid:
                                        status.ctypes.data_as(L.P_I32), prof.ctypes.data_as(L.P_D) if prof is not None else None))
         return Crossings(radius, dirs, count, status, prof)
 
+    def isosurface(self, terms, levels, columns, carry=0, tol=None, max_iter=None, max_cross=4, return_values=False, return_profiles=False):
+        """The heights at which a field program crosses `levels` in columns, on the device (sx_isosurface; reads the A coefficients the
+        tile holds now; RZ and RLZ grids).  terms: a program as for reduce with 1 + carry outputs - output 0 is the surface quantity,
+        outputs 1 .. carry are evaluated on the surface; columns [n_cols, n_coord - 1] with columns r[, lambda]; levels: up to 8.
+        Returns Isosurface(height [max_cross, n_levels, n_cols], dir of the same shape, count [n_levels, n_cols], status [n_cols],
+        carry [carry, max_cross, n_levels, n_cols] or None, values [zDim, n_cols] or None, profiles [b_zDim, n_profiles, n_cols] or
+        None): the first max_cross crossings of every level upward (unused entries NaN, dir 0), dir +1 where the program rises
+        upward through the level and -1 where it falls, count the number found (it may exceed max_cross), status bit 0: a NaN in the
+        column, bit 1: a refinement ran out of iterations, bit 2: it met a NaN.  values: the program at the zDim levels, bottom to
+        top, as the kernel formed it.  One-tile patches only."""
+        coef, packed, _ = pack_reduce_program(self.patch_params, terms)
+        ncc = int(self.dims.n_coord) - 1
+        q = np.asarray(columns, dtype=np.float64)
+        q = np.asfortranarray(q.reshape(-1, max(ncc, 1)) if q.ndim != 2 else q)
+        if q.shape[1] != ncc:
+            raise ValueError("columns must have %d coordinate column(s)" % ncc)
+        n, nc = q.shape[0], int(carry)
+        lev = np.ascontiguousarray(np.atleast_1d(levels), dtype=np.float64)
+        nl, mc = len(lev), int(max_cross)
+        shape = (max(mc, 0), nl, n)
+        height, dirs = np.full(shape, np.nan, order="F"), np.zeros(shape, dtype=np.int32, order="F")
+        count, status = np.zeros((nl, n), dtype=np.int32, order="F"), np.zeros(n, dtype=np.int32)
+        car = np.full((nc,) + shape, np.nan, order="F") if nc > 0 else None
+        val = np.zeros((int(self.patch_params.zDim), n), order="F") if return_values else None
+        prof = None
+        if return_profiles:
+            prof = np.zeros((int(self.patch_params.b_zDim), isosurface_check(self.patch_params, terms, nc), n), order="F")
+        ptr = lambda a: a.ctypes.data_as(L.P_D) if a is not None else None
+        L.check(self._lib.sx_isosurface(self._h, len(coef), coef.ctypes.data_as(L.P_D), packed.ctypes.data_as(L.P_I32), nc, n, ptr(q),
+                                        nl, lev.ctypes.data_as(L.P_D), 0.0 if tol is None else float(tol),
+                                        0 if max_iter is None else int(max_iter), mc, ptr(height), dirs.ctypes.data_as(L.P_I32),
+                                        count.ctypes.data_as(L.P_I32), status.ctypes.data_as(L.P_I32), ptr(car), ptr(val), ptr(prof)))
+        return Isosurface(height, dirs, count, status, car, val, prof)
+
     # -- statistics of field programs over time (sx_stats_*)
     def set_statistics(self, outputs, source="state", ops=None):
         """Attach (or replace) the tile's statistics set: per-gridpoint accumulators over time that live on the device
@@ -1040,6 +1074,42 @@ def bracket_step(state, flags, fx=0.0, width_tol=0.0, first=False):
     L.check(L.load().sx_bracket_step(s.ctypes.data_as(L.P_D), f.ctypes.data_as(L.P_I32), 1 if first else 0, float(fx), float(width_tol),
                                      C.byref(st)))
     return s, f, int(st.value)
+
+
+# ----------------------------------------------------------------------------- isosurfaces in columns (sx_isosurface)
+Isosurface = collections.namedtuple("Isosurface", "height dir count status carry values profiles")
+
+
+def isosurface_check(patch: GridParameters, terms, carry=0):
+    """The number of column profiles Grid.isosurface forms for a program with 1 + carry outputs, on the host (sx_isosurface_check:
+    no handle, no device).  Raises what Grid.isosurface would refuse of the grid and the program."""
+    d, keep = grid_desc(patch)
+    coef, packed, _ = pack_reduce_program(patch, terms)
+    n = C.c_int32(-1)
+    L.check(L.load().sx_isosurface_check(C.byref(d), len(coef), packed.ctypes.data_as(L.P_I32), int(carry), C.byref(n)))
+    return int(n.value)
+
+
+def column_series(zmin, zmax, a, z):
+    """(value, d/dz, d2/dz2) at height z of the Chebyshev series with the zDim coefficients `a`, on the host (sx_column_series): the
+    function Grid.isosurface's kernel evaluates at stations, trial points and for the carried outputs."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    out = np.zeros(3)
+    L.check(L.load().sx_column_series(len(a), float(zmin), float(zmax), a.ctypes.data_as(L.P_D), float(z), out.ctypes.data_as(L.P_D)))
+    return out
+
+
+def columns_of(gp: GridParameters, points):
+    """The columns [n_cols, n_coord - 1] = r[, lambda] of gridpoints r[, lambda], z as regular_gridpoints / cartesian_gridpoints
+    list them (z fastest): the z coordinate dropped, every run of rows that share a column kept once."""
+    if "Z" not in gp.geometry:
+        raise ValueError("columns need an RZ or RLZ geometry")
+    p = np.asarray(points, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] not in (len(gp.geometry), len(gp.geometry) - 1):
+        raise ValueError("points must have %d coordinate column(s), or as many without z" % len(gp.geometry))
+    c = p[:, :len(gp.geometry) - 1]
+    keep = np.concatenate([[True], (c[1:] != c[:-1]).any(axis=1)]) if len(c) else np.zeros(0, dtype=bool)
+    return np.ascontiguousarray(c[keep])
 
 
 # ----------------------------------------------------------------------------- histograms of field programs (sx_distribution)
