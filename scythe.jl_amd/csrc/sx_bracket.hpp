@@ -1,22 +1,11 @@
-// What sx_crossings (sx_crossings.hip) and sx_isosurface (sx_isosurface.hip) share: the cardinal cubic B-spline in plain fp64 as both
-// form it on the device, and the bracket iteration that refines one crossing - the function sx_bracket_step runs on the host.  Stated
-// once so that a radius along a ray and a height in a column are refined by the same steps.
+// The bracket iteration that refines one crossing of sx_crossings (a radius along a ray) and sx_isosurface (a height in a column) -
+// the function sx_bracket_step runs on the host.  scan_crossings of sx_point.hpp drives it on the device for both, so that a radius
+// and a height are refined by the same steps.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
 
 namespace sx {
-
-// d-th derivative of the cardinal cubic B-spline (bspl of sx_setup.cpp)
-__host__ __device__ inline double cross_bspl(double delta, int d) {
-    const double z = fabs(delta);
-    if (z >= 2.0) return 0.0;
-    const double s = delta > 0 ? 1.0 : -1.0;
-    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
-    if (d == 0) return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
-    if (d == 1) return -s * (p * p / 2.0 - 2.0 * q * q);
-    return p - 4.0 * q;
-}
 
 // The bracket of one crossing: d = g - c changes sign between a (inner) and b (outer); fa, fb are d there, ga, gb the values the false
 // position is drawn through (an end kept twice in a row has its value halved: Illinois), x the trial point whose d the next step takes

@@ -7,15 +7,14 @@
 // a [rows x ncol] [ncol x n_rays] product per variable.  k_ray_profiles runs it on the f64 matrix cores: a wave owns 16 patch rows x
 // 16 rays of one variable, stages 16 x CROSS_KC tiles of A through LDS (coalesced row pieces in, the A-operand layout lane =
 // (col & 3) * 16 + row out), forms the B operand - the ray weights - on the fly from the wave's tables of cos / sin k lambda and of
-// the vertical rows (k_parcels' arithmetic), and keeps one accumulator per (lambda order, z order) the program names.  The K order is
-// col = 0, 1, 2, ... whatever the rays are, columns of the matrix product do not mix, and a ray tile is padded with zero weights: a
-// ray's profile is bitwise independent of the other rays of the call and of their number.
+// the vertical rows (the functions of sx_point.hpp, which k_parcels runs too), and keeps one accumulator per (lambda order, z order)
+// the program names.  The K order is col = 0, 1, 2, ... whatever the rays are, columns of the matrix product do not mix, and a ray
+// tile is padded with zero weights: a ray's profile is bitwise independent of the other rays of the call and of their number.
 //
-// k_crossings: one wave per ray.  Lanes take the stations (inner end, radial gridpoints, outer end) in chunks of 64, evaluate the
-// program from the profiles (4 multiply-adds per plane), compare neighbours (the last lane's value is carried into the next chunk),
-// number the crossings of a level outward with a ballot, and every crossing is refined by its own lane with bracket_step - the
-// function sx_bracket_step runs on the host.  No atomics, nothing summed across rays.
-#include "sx_bracket.hpp"
+// k_crossings: one wave per ray runs scan_crossings (sx_point.hpp) over the stations (inner end, radial gridpoints, outer end), the
+// program evaluated from the profiles (4 multiply-adds per plane): the crossings of a level are numbered outward and every crossing
+// is refined by its own lane with bracket_step - the function sx_bracket_step runs on the host.  No atomics, nothing summed across rays.
+#include "sx_point.hpp"
 #include "sx_redprog.hpp"
 #include <algorithm>
 #include <cmath>
@@ -23,12 +22,10 @@
 
 namespace sx {
 
-constexpr int CROSS_LEVELS = 8, CROSS_MAX = 16;
 constexpr int CROSS_KINDS = 5;            // profile kinds of a variable: value, d/dlambda, d2/dlambda2, d/dz, d2/dz2
 constexpr int CROSS_KC = 32;              // columns of A per staged tile: 8 K steps
 constexpr int CROSS_AS = 36;              // row stride of the staged tile in doubles
 constexpr size_t CROSS_LDS_MAX = 64 * 1024;
-constexpr int64_t CROSS_RAYS_MAX = (int64_t)1 << 20;
 
 typedef double cross_d4 __attribute__((ext_vector_type(4)));
 
@@ -39,7 +36,7 @@ struct ProfVar {
 };
 struct ProfArgs {
     const double *A;                      // [b_rDim][C]
-    const double *w3;                     // [ncls][3][nz][Zb] CA, Dc CA, Dc Dc CA (null without a vertical)
+    const double *w3;                     // [ncls][3][nz][Zb] CA, Dc CA, Dc Dc CA: EvalClasses::d_w3 (null without a vertical)
     const double *rays;                   // [n_coord - 1][n_rays]: lambda[, z]; |lambda| <= 2 pi
     double *P;                            // [n_rays][nprof][rows]
     int64_t C;
@@ -65,36 +62,21 @@ __global__ __launch_bounds__(64) void k_ray_profiles(ProfArgs a) {
     const int m0 = blockIdx.x * 16, q0 = blockIdx.y * 16;
     const ProfVar pv = a.v[blockIdx.z];
 
-    // ---- the weights of the 16 rays (as k_parcels forms them; a ray beyond the call's takes lambda = 0, the lowest level, and no weight)
-    if (a.has_l)
-        for (int e = lane; e < 16 * (a.kDim + 1); e += 64) {
-            const int k = e >> 4, q = q0 + (e & 15);
-            const double lam = q < a.n_rays ? a.rays[q] : 0.0;
-            double s, c;
-            sincos((double)k * lam, &s, &c);   // |lambda| <= 2 pi: the product is off by at most 2 k pi eps
-            cs[e] = make_double2(c, s);
-        }
+    // ---- the weights of the 16 rays (sx_point.hpp; a ray beyond the call's takes lambda = 0, the lowest level, and no weight)
+    if (a.has_l) az_table16(cs, a.kDim, lane, [&](int jj) { return q0 + jj < a.n_rays ? a.rays[q0 + jj] : 0.0; });
     if (a.has_z) {
-        const double mid = (a.zmin + a.zmax) / 2.0, half = (a.zmax - a.zmin) / 2.0;
         const double *zr = a.rays + (a.has_l ? (int64_t)a.n_rays : 0);
         for (int e = lane; e < 16 * a.nz; e += 64) {
-            const int n = e >> 4, q = q0 + (e & 15);
-            const double z = q < a.n_rays ? zr[q] : a.zmin;
-            const double x = fmin(fmax((z - mid) / (-half), -1.0), 1.0);
-            const double th = acos(x);
-            tz[e] = ((n == 0 || n == a.nz - 1) ? 1.0 : 2.0) * cos((double)n * th);
+            const int q = q0 + (e & 15);
+            const double z = q < a.n_rays ? zr[q] : a.zmin;        // a named local: written as the call's argument it costs 30 VGPRs
+            tz[e] = cheb_entry(e >> 4, a.nz, cheb_theta(a.zmin, a.zmax, z));
         }
         __syncthreads();
         const double *w3 = a.w3 + (size_t)pv.cls * 3 * a.nz * a.Zb;
         for (int e = lane; e < 48 * a.Zb; e += 64) {
             const int m = e / (16 * a.Zb), zm = (e - m * 16 * a.Zb) >> 4, jj = e & 15;
             const bool need = m == 0 ? (pv.prof[0] >= 0 || pv.prof[1] >= 0 || pv.prof[2] >= 0) : pv.prof[2 + m] >= 0;
-            double acc = 0.0;
-            if (need) {
-                const double *w = w3 + (size_t)m * a.nz * a.Zb + zm;
-                for (int n = 0; n < a.nz; n++) acc = fma(tz[n * 16 + jj], w[(size_t)n * a.Zb], acc);
-            }
-            wz[e] = acc;
+            wz[e] = need ? cheb_weight(tz + jj, 16, w3 + (size_t)m * a.nz * a.Zb + zm, a.nz, a.Zb) : 0.0;
         }
     } else {
         if (lane < 48) wz[lane] = lane < 16 ? 1.0 : 0.0;           // Zb = 1 without a vertical
@@ -126,16 +108,10 @@ __global__ __launch_bounds__(64) void k_ray_profiles(ProfArgs a) {
             const int kcl = on ? kc : ncol - 1;
             const int zm = kcl / a.K2, blk = kcl - zm * a.K2;
             const double av = sA[j * CROSS_AS + 4 * s + kk];       // A operand: row lane & 15, column lane >> 4
-            // F_blk and its lambda derivatives: block 0 is 1; Re k: 2 cos, -2 k sin, -2 k^2 cos; Im k: -2 sin, -2 k cos, 2 k^2 sin
             double F0 = 1.0, F1 = 0.0, F2 = 0.0;
-            if (a.has_l) {
-                const int k = blk >> 1;
-                const double2 t = cs[k * 16 + j];
-                const double kd = (double)k;
-                const double x = (blk & 1) ? -t.y : t.x, y = (blk & 1) ? -t.x : -t.y;
-                F0 = blk == 0 ? 1.0 : 2.0 * x; F1 = 2.0 * kd * y; F2 = -(kd * kd) * F0;
-            }
-            const bool live = on && ray_on && !(a.has_l && blk == 1);
+            if (a.has_l) az_factors(blk, cs + j, 16, F0, F1, F2);
+            const bool pad = a.has_l && az_padding(blk);           // ahead of `live`: inside it the call keeps a branch per K step
+            const bool live = on && ray_on && !pad;
             const double z0 = live ? wz[zm * 16 + j] : 0.0;
             if (pv.prof[0] >= 0) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, F0 * z0, acc[0], 0, 0, 0);
             if (pv.prof[1] >= 0) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, F1 * z0, acc[1], 0, 0, 0);
@@ -158,7 +134,7 @@ __global__ __launch_bounds__(64) void k_ray_profiles(ProfArgs a) {
     }
 }
 
-// ---- what host and device share: the stations, the basis (cross_bspl and the bracket step: sx_bracket.hpp) -------------
+// ---- what host and device share: the stations, the basis (point_basis: sx_point.hpp; the bracket step: sx_bracket.hpp) -------------
 struct CrossGeom {
     double xmin, DX, lo, hi;              // the tile's radial extent as eval_radius_ok reads it
     int cell0, ncells, n_st;              // stations: lo, the 3 ncells radial gridpoints, hi
@@ -175,15 +151,8 @@ __host__ __device__ inline double cross_station(const CrossGeom &G, int s) {
 
 // phi, phi', phi'' of the 4 nodes of r's cell (sx_eval_basis' statement in plain fp64); returns the cell = patch row of the first node
 __host__ __device__ inline int cross_basis(const CrossGeom &G, double r, double (&phi)[3][4]) {
-    int cell = (int)floor((r - G.xmin) / G.DX);
-    cell = cell < G.cell0 ? G.cell0 : cell > G.cell0 + G.ncells - 1 ? G.cell0 + G.ncells - 1 : cell;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const double delta = (r - (G.xmin + (double)(cell - 1 + j) * G.DX)) / G.DX;
-        phi[0][j] = cross_bspl(delta, 0);
-        phi[1][j] = cross_bspl(delta, 1) / G.DX;
-        phi[2][j] = cross_bspl(delta, 2) / (G.DX * G.DX);
-    }
+    const int cell = point_cell(G.xmin, G.DX, G.cell0, G.cell0 + G.ncells - 1, r);
+    point_basis<3>(G.xmin, G.DX, cell, r, phi);
     return cell;
 }
 
@@ -194,7 +163,7 @@ struct CrossArgs {
     int *dir, *count, *status;            // as radius; [n_rays][n_levels]; [n_rays]
     RedProg g;
     uint8_t pprof[RED_PLANES], pd[RED_PLANES];     // plane -> profile number, radial order 0 .. 2
-    double level[CROSS_LEVELS];
+    double level[SCAN_LEVELS];
     double wtol;                          // tol DX
     int n_rays, rows, nprof, n_levels, max_iter, max_cross;
     CrossGeom G;
@@ -225,68 +194,17 @@ __device__ inline double cross_value(const CrossArgs &a, const double *__restric
 
 // grid (n_rays), one wave
 __global__ __launch_bounds__(64) void k_crossings(CrossArgs a) {
-    __shared__ int s_cnt[CROSS_LEVELS];
-    const int lane = threadIdx.x;
     const int64_t q = blockIdx.x;
     const double *__restrict__ Pq = a.P + q * a.nprof * a.rows;
-    double *__restrict__ rad = a.radius + q * a.n_levels * a.max_cross;
-    int *__restrict__ dir = a.dir + q * a.n_levels * a.max_cross;
-    int cnt[CROSS_LEVELS];
-#pragma unroll
-    for (int j = 0; j < CROSS_LEVELS; j++) cnt[j] = 0;
-    int status = 0;
-    double carry_g = 0.0, carry_r = 0.0;
-    for (int base = 0; base < a.G.n_st; base += 64) {
-        const int s = base + lane;
-        const bool has = s < a.G.n_st;
-        const double r = cross_station(a.G, has ? s : a.G.n_st - 1);
-        const double g = cross_value(a, Pq, r);
-        double gp = __shfl_up(g, 1, 64), rp = __shfl_up(r, 1, 64);
-        if (lane == 0) { gp = carry_g; rp = carry_r; }            // the chunk before ended on station base - 1
-        carry_g = __shfl(g, 63, 64); carry_r = __shfl(r, 63, 64);
-        const bool iv = has && s > 0;                              // this lane owns the interval [s - 1, s]
-#pragma unroll
-        for (int j = 0; j < CROSS_LEVELS; j++) {
-            if (j >= a.n_levels) break;
-            const double c = a.level[j];
-            const double d0 = gp - c, d1 = g - c;
-            const bool nan = iv && (d0 != d0 || d1 != d1);
-            const bool cross = iv && !nan && ((d0 < 0.0) != (d1 < 0.0));
-            if (__ballot(nan)) status |= 1;
-            const unsigned long long mask = __ballot(cross);
-            const int pos = cnt[j] + __popcll(mask & ((1ull << lane) - 1ull));
-            cnt[j] += __popcll(mask);
-            if (cross && pos < a.max_cross) {
-                Bracket B;
-                B.a = rp; B.fa = d0; B.b = r; B.fb = d1;
-                int st = bracket_start(B, a.wtol);
-                for (int it = 0; st < 0 && it < a.max_iter; it++) st = bracket_step(B, cross_value(a, Pq, B.x) - c, a.wtol);
-                if (st != 0) status |= st < 0 ? 2 : 4;
-                rad[j * a.max_cross + pos] = bracket_root(B);
-                dir[j * a.max_cross + pos] = d0 < 0.0 ? 1 : -1;
-            }
-        }
-    }
-    // bits 1 and 2 are a lane's own: fold them over the wave
-    status = (status & 1) | (__ballot(status & 2) ? 2 : 0) | (__ballot(status & 4) ? 4 : 0);
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < CROSS_LEVELS; j++)
-            if (j < a.n_levels) { s_cnt[j] = cnt[j]; a.count[q * a.n_levels + j] = cnt[j]; }
-        a.status[q] = status;
-    }
-    __syncthreads();
-    for (int e = lane; e < a.n_levels * a.max_cross; e += 64) {    // the entries no crossing took
-        const int j = e / a.max_cross, pos = e - j * a.max_cross;
-        if (pos >= s_cnt[j]) { rad[e] = __builtin_nan(""); dir[e] = 0; }
-    }
+    const int64_t e0 = q * a.n_levels * a.max_cross;
+    const ScanOut o = {a.radius + e0, a.dir + e0, a.count + q * a.n_levels, a.status + q, nullptr, nullptr, 0};
+    scan_crossings(a.G.n_st, a.level, a.n_levels, a.wtol, a.max_iter, a.max_cross, o,
+                   [&](int s) { return cross_station(a.G, s); }, [&](double r) { return cross_value(a, Pq, r); }, [](double, double *) {});
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 struct CrossState : DiagState {          // last_bytes: k_ray_profiles'
     double cross_bytes = 0;             // k_crossings'
-    DevBuf<double> d_w3;                // [ncls][3][nz][Zb], uploaded once per handle
-    bool w3_ready = false;
     DevBuf<double> d_rays, d_P, d_rad;
     DevBuf<int> d_i;                    // dir | count | status
 };
@@ -294,6 +212,22 @@ struct CrossState : DiagState {          // last_bytes: k_ray_profiles'
 double crossings_bytes(const sx_handle *h, bool scan) {
     const CrossState *st = diag_state<CrossState>(h, DIAG_CROSSINGS);
     return !st ? 0.0 : scan ? st->cross_bytes : st->last_bytes;
+}
+
+bool scan_args_ok(const sx_handle *h, const char *who, const char *count, const char *noun, int n_terms, const double *coef, int n_levels,
+                  int max_cross, const double *levels, int64_t n, double tol) {
+    const std::string w = std::string(who) + ": ";
+    if (n_terms > 0 && !coef) { set_error(w + "null coef with n_terms > 0"); return false; }
+    if (n_levels < 1 || n_levels > SCAN_LEVELS) { set_error(w + "n_levels must be 1 .. 8"); return false; }
+    if (max_cross < 1 || max_cross > SCAN_MAX) { set_error(w + "max_cross must be 1 .. 16"); return false; }
+    if (!levels) { set_error(w + "null levels"); return false; }
+    if (n < 0) { set_error(w + count + " is negative"); return false; }
+    if (n > SCAN_COUNT_MAX) { set_error(w + "more than 2^20 " + noun + " in one call"); return false; }
+    if (!std::isfinite(tol)) { set_error(w + "tol is NaN or Inf"); return false; }
+    for (int j = 0; j < n_levels; j++)
+        if (!std::isfinite(levels[j])) { set_error(w + "level " + std::to_string(j) + " is NaN or Inf"); return false; }
+    if (h->ncells != h->nc) { set_error(w + "one-tile patches only"); return false; }
+    return true;
 }
 
 static CrossGeom cross_geom(const EvalGeom &g) {
@@ -318,16 +252,7 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     const sx_grid_desc gd = desc_of(h);
     int32_t planes[RED_PLANES][2], n_planes = 0;
     if (sx_reduce_planes(&gd, SX_REDUCE_PHYSICAL, n_terms, terms, 1, &planes[0][0], &n_planes)) return 1;      // one output: out = 0 in every term
-    if (n_terms > 0 && !coef) { set_error("sx_crossings: null coef with n_terms > 0"); return 1; }
-    if (n_levels < 1 || n_levels > CROSS_LEVELS) { set_error("sx_crossings: n_levels must be 1 .. 8"); return 1; }
-    if (max_cross < 1 || max_cross > CROSS_MAX) { set_error("sx_crossings: max_cross must be 1 .. 16"); return 1; }
-    if (!levels) { set_error("sx_crossings: null levels"); return 1; }
-    if (n_rays < 0) { set_error("sx_crossings: n_rays is negative"); return 1; }
-    if (n_rays > CROSS_RAYS_MAX) { set_error("sx_crossings: more than 2^20 rays in one call"); return 1; }
-    if (!std::isfinite(tol)) { set_error("sx_crossings: tol is NaN or Inf"); return 1; }
-    for (int j = 0; j < n_levels; j++)
-        if (!std::isfinite(levels[j])) { set_error("sx_crossings: level " + std::to_string(j) + " is NaN or Inf"); return 1; }
-    if (h->ncells != h->nc) { set_error("sx_crossings: one-tile patches only"); return 1; }
+    if (!scan_args_ok(h, who, "n_rays", "rays", n_terms, coef, n_levels, max_cross, levels, n_rays, tol)) return 1;
     const EvalGeom g = eval_geom_of(h);
     if (h->has_l && g.tile_lo() == 0.0)
         for (int t = 0; t < n_terms; t++)
@@ -371,15 +296,6 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     if (!h->diag[DIAG_CROSSINGS]) h->diag[DIAG_CROSSINGS].reset(new CrossState());
     CrossState *st = diag_state<CrossState>(h, DIAG_CROSSINGS);
     const int Zb = h->has_z ? h->Zb : 1, nz = h->has_z ? h->nz : 1, rows = h->nbt;
-    if (k && !st->w3_ready) {
-        const size_t per = (size_t)3 * nz * Zb;
-        std::vector<double> w3(k->vert.size() * per);
-        for (size_t c = 0; c < k->vert.size(); c++)
-            for (int m = 0; m < 3; m++)
-                for (size_t e = 0; e < (size_t)nz * Zb; e++) w3[c * per + (size_t)m * nz * Zb + e] = (double)k->vert[c].W[m][e];
-        if (!st->d_w3.upload(w3, "sx_crossings: hipMalloc of the vertical operators failed")) return 1;
-        st->w3_ready = true;
-    }
     for (int v = 0; v < nv; v++) pa.v[v].cls = k ? k->vcls[pa.v[v].var] : 0;
 
     const size_t n_ray = (size_t)std::max(nrc, 1) * n_rays, n_P = (size_t)std::max(nprof, 1) * rows * n_rays;
@@ -387,20 +303,14 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     if (!st->d_rays.grow(n_ray, who) || !st->d_P.grow(n_P, who) || !st->d_rad.grow(n_rad, who) || !st->d_i.grow(n_int, who)) return 1;
     std::vector<double> r0(n_ray, 0.0);
     if (nrc > 0) std::memcpy(r0.data(), rays, sizeof(double) * nrc * n_rays);
-    if (h->has_l) {                                // a lambda outside [-2 pi, 2 pi] into (-pi, pi], in extended precision as sx_extremum_refine does
-        const long double two_pi = 8.0L * atanl(1.0L);
-        for (int64_t i = 0; i < n_rays; i++) {
-            if (std::fabs(rays[i]) <= 6.283185307179586) continue;
-            double l = (double)remainderl((long double)rays[i], two_pi);
-            if (l <= -M_PI) l = M_PI;
-            r0[i] = l;
-        }
-    }
+    if (h->has_l)                                  // a lambda outside [-2 pi, 2 pi] into (-pi, pi]
+        for (int64_t i = 0; i < n_rays; i++)
+            if (std::fabs(rays[i]) > 6.283185307179586) r0[i] = wrap_lambda(rays[i]);
     flush_diag(h);                                 // as for every reader of A
     HIPCHK(hipMemcpyAsync(st->d_rays, r0.data(), sizeof(double) * n_ray, hipMemcpyHostToDevice, h->stream));
     if (error_status()) return 1;
 
-    pa.A = h->d_A; pa.w3 = k ? (const double *)st->d_w3 : nullptr; pa.rays = st->d_rays; pa.P = st->d_P;
+    pa.A = h->d_A; pa.w3 = k ? (const double *)k->d_w3 : nullptr; pa.rays = st->d_rays; pa.P = st->d_P;
     pa.C = h->C; pa.n_rays = (int)n_rays; pa.rows = rows; pa.row0 = h->cell0; pa.nprof = nprof;
     pa.Zb = Zb; pa.nz = nz; pa.K2 = h->K2; pa.kDim = h->kDim; pa.has_l = h->has_l; pa.has_z = h->has_z;
     pa.zmin = h->zmin; pa.zmax = h->zmax;

@@ -201,6 +201,11 @@ bool eval_points_ok(const sx_handle *h, const double *pts, int64_t n, const char
     return true;
 }
 
+double wrap_lambda(double lam) {
+    const double l = (double)remainderl((long double)lam, 8.0L * atanl(1.0L));
+    return l <= -M_PI ? M_PI : l;
+}
+
 static EvalState *eval_state(sx_handle *h) {
     if (h->diag[DIAG_EVAL]) return diag_state<EvalState>(h, DIAG_EVAL);
     std::unique_ptr<EvalState> st(new EvalState());
@@ -221,7 +226,12 @@ static EvalState *eval_state(sx_handle *h) {
             k.vcls[v] = found;
         }
     }
-    if (!k.d_vcls.upload(k.vcls, "sx_evaluate: hipMalloc of the scratch failed")) return nullptr;
+    std::vector<double> w3;             // W[0 .. 2] of every class, rounded once
+    for (const EvalVert &ev : k.vert)
+        for (int m = 0; m < 3; m++)
+            for (long double x : ev.W[m]) w3.push_back((double)x);
+    if (!k.d_vcls.upload(k.vcls, "sx_evaluate: hipMalloc of the scratch failed") || (!w3.empty() && !k.d_w3.upload(w3, "eval_classes: hipMalloc of the vertical operators failed")))
+        return nullptr;
     h->diag[DIAG_EVAL] = std::move(st);
     return diag_state<EvalState>(h, DIAG_EVAL);
 }

@@ -9,8 +9,10 @@
 // total, so the fold is associative and commutative and the result does not depend on which lane folds what.  No atomics.
 //
 // The refinement.  k_refine is k_parcels with derivatives: one workgroup per start point, the same lane count, the same column a lane
-// sums and the same order of the reduction; per iteration it forms the weights from the position, sums the 10 derivatives of order
-// <= 2 in ONE pass over the 4 node rows, and lane 0 takes the step with newton_step - the function sx_newton_step runs on the host.
+// sums and the same order of the reduction, all stated once in sx_point.hpp; per iteration it forms the weights from the position,
+// sums the 10 derivatives of order <= 2 in ONE pass over the 4 node rows, and lane 0 takes the step with newton_step - the function
+// sx_newton_step runs on the host.
+#include "sx_point.hpp"
 #include "sx_redprog.hpp"
 #include <algorithm>
 #include <cmath>
@@ -260,7 +262,7 @@ __host__ __device__ inline int newton_step(const NewtonGeom &G, int want, int ma
 // ---- k_refine --------------------------------------------------------------------------------------------------------------------
 struct RefineArgs {
     const double *A;       // [b_rDim][C]
-    const double *w3;      // [3][nz][Zb] CA, Dc CA, Dc Dc CA of the variable's vertical class
+    const double *w3;      // [3][nz][Zb] CA, Dc CA, Dc Dc CA of the variable's vertical class (EvalClasses::d_w3)
     const double *start;   // [n_coord][n], |lambda| <= 2 pi
     double *pos, *grad;    // [n_coord][n]
     double *value;         // [n]
@@ -270,17 +272,6 @@ struct RefineArgs {
     double xmin, tol;
     NewtonGeom G;
 };
-
-// d-th derivative of the cardinal cubic B-spline (bspl of sx_setup.cpp)
-__device__ inline double refine_bspl(double delta, int d) {
-    const double z = fabs(delta);
-    if (z >= 2.0) return 0.0;
-    const double s = delta > 0 ? 1.0 : -1.0;
-    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
-    if (d == 0) return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
-    if (d == 1) return -s * (p * p / 2.0 - 2.0 * q * q);
-    return p - 4.0 * q;
-}
 
 // LDS (doubles): cs [kDim + 1] double2 | t [nz] | wz [3][Zb] | red [waves][10] | bc [REFINE_BC]
 __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
@@ -292,7 +283,6 @@ __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
     double *bc = red + REFINE_ND * (PARCEL_T / 64);
     const int tid = threadIdx.x, T = blockDim.x;
     const int64_t i = blockIdx.x;
-    const int lane = tid & 63, wave = tid >> 6, nw = T >> 6;
     const int ncol = a.Zb * a.K2;
 
     double r = a.start[(int64_t)a.cr * a.n + i];
@@ -302,34 +292,18 @@ __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
     bool last = false;                      // the evaluation in progress is the one the outputs report
 
     for (;;) {
-        // ---- weights (as k_parcels forms them, with the derivative rows)
-        int cell = (int)floor((r - a.xmin) / a.G.DX);
-        cell = min(max(cell, a.cell_lo), a.cell_hi);
+        // ---- weights (sx_point.hpp), with the derivative rows
+        const int cell = point_cell(a.xmin, a.G.DX, a.cell_lo, a.cell_hi, r);
         double phi[3][4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const double delta = (r - (a.xmin + (double)(cell - 1 + j) * a.G.DX)) / a.G.DX;
-            phi[0][j] = refine_bspl(delta, 0);
-            phi[1][j] = refine_bspl(delta, 1) / a.G.DX;
-            phi[2][j] = refine_bspl(delta, 2) / (a.G.DX * a.G.DX);
-        }
-        for (int k = tid; k <= a.kDim; k += T) {
-            double s, c;
-            sincos((double)k * lam, &s, &c);   // |lambda| <= 2 pi: the product is off by at most 2 k pi eps
-            cs[k] = make_double2(c, s);
-        }
+        point_basis<3>(a.xmin, a.G.DX, cell, r, phi);
+        az_table(cs, a.kDim, lam, tid, T);
         if (a.cz >= 0) {
-            const double mid = (a.G.zmin + a.G.zmax) / 2.0, half = (a.G.zmax - a.G.zmin) / 2.0;
-            const double x = fmin(fmax((z - mid) / (-half), -1.0), 1.0);
-            const double th = acos(x);
-            for (int n = tid; n < a.nz; n += T) tz[n] = ((n == 0 || n == a.nz - 1) ? 1.0 : 2.0) * cos((double)n * th);
+            const double th = cheb_theta(a.G.zmin, a.G.zmax, z);
+            for (int n = tid; n < a.nz; n += T) tz[n] = cheb_entry(n, a.nz, th);
             __syncthreads();
             for (int q = tid; q < 3 * a.Zb; q += T) {
                 const int m = q / a.Zb, zm = q - m * a.Zb;
-                const double *w = a.w3 + (size_t)m * a.nz * a.Zb + zm;
-                double acc = 0.0;
-                for (int n = 0; n < a.nz; n++) acc = fma(tz[n], w[(size_t)n * a.Zb], acc);
-                wz[q] = acc;
+                wz[q] = cheb_weight(tz, 1, a.w3 + (size_t)m * a.nz * a.Zb + zm, a.nz, a.Zb);
             }
         } else {
             if (tid < 3) wz[tid] = tid == 0 ? 1.0 : 0.0;          // Zb = 1 without a vertical
@@ -343,13 +317,9 @@ __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
         const double *__restrict__ Ac = a.A + (int64_t)cell * a.C + (int64_t)a.var * ncol;
         for (int col = tid; col < ncol; col += T) {
             const int zm = col / a.K2, blk = col - zm * a.K2;
-            if (blk == 1) continue;                                   // padding: Im of k = 0
-            const int k = blk >> 1;
-            const double2 t = cs[k];
-            const double kd = (double)k;
-            // F_blk and its lambda derivatives: block 0 is 1; Re k: 2 cos, -2 k sin, -2 k^2 cos; Im k: -2 sin, -2 k cos, 2 k^2 sin
-            const double x = (blk & 1) ? -t.y : t.x, y = (blk & 1) ? -t.x : -t.y;
-            const double F0 = blk == 0 ? 1.0 : 2.0 * x, F1 = 2.0 * kd * y, F2 = -(kd * kd) * F0;
+            if (az_padding(blk)) continue;
+            double F0, F1, F2;
+            az_factors(blk, cs, 1, F0, F1, F2);
             const double *__restrict__ p = Ac + col;
             const double a0 = p[0], a1 = p[a.C], a2 = p[2 * a.C], a3 = p[3 * a.C];
             const double s0 = fma(phi[0][3], a3, fma(phi[0][2], a2, fma(phi[0][1], a1, phi[0][0] * a0)));
@@ -367,24 +337,11 @@ __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
             acc[8] = fma(s0, F1 * z1, acc[8]);
             acc[9] = fma(s0, F0 * z2, acc[9]);
         }
-#pragma unroll
-        for (int m = 0; m < REFINE_ND; m++) {
-            double x = acc[m];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-            if (lane == 0) red[wave * REFINE_ND + m] = x;
-        }
-        __syncthreads();
+        point_sum<REFINE_ND>(acc, red, tid, T);
 
         // ---- lane 0 decides
         if (tid == 0) {
-            double d[REFINE_ND];
-#pragma unroll
-            for (int m = 0; m < REFINE_ND; m++) {
-                double x = red[m];
-                for (int w = 1; w < nw; w++) x += red[w * REFINE_ND + m];
-                d[m] = x;
-            }
+            const double (&d)[REFINE_ND] = acc;
             bool go = false;
             if (!last) {
                 const double pos[3] = {r, lam, z};
@@ -430,8 +387,6 @@ struct ExtremaState : DiagState {      // last_bytes: k_extrema's
     bool scan_ready = false;
     // refinement
     double refine_bytes = 0;        // A bytes of the last sx_extremum_refine
-    DevBuf<double> d_w3;            // [ncls][3][nz][Zb], uploaded once per handle
-    bool w3_ready = false;
     DevBuf<double> d_f;             // start | pos | grad [n_coord][n] each, value [n]
     DevBuf<int> d_i;                // status | iters
 };
@@ -565,32 +520,18 @@ int sx_extremum_refine(sx_handle *h, int32_t var, int32_t want, int32_t free_mas
     ExtremaState *st = extrema_state(h);
     const int nco = h->ncoord, Zb = h->has_z ? h->Zb : 1, nz = h->has_z ? h->nz : 1;
     const size_t per = (size_t)3 * nz * Zb;
-    if (k && !st->w3_ready) {
-        std::vector<double> w3(k->vert.size() * per);
-        for (size_t c = 0; c < k->vert.size(); c++)
-            for (int m = 0; m < 3; m++)
-                for (size_t q = 0; q < (size_t)nz * Zb; q++) w3[c * per + (size_t)m * nz * Zb + q] = (double)k->vert[c].W[m][q];
-        if (!st->d_w3.upload(w3, "sx_extremum_refine: hipMalloc of the vertical operators failed")) return 1;
-        st->w3_ready = true;
-    }
     const size_t blk = (size_t)nco * n;
     if (!st->d_f.grow(3 * blk + n, who) || !st->d_i.grow(2 * (size_t)n, who)) return 1;
     std::vector<double> s0(start, start + blk);
-    if (h->has_l) {                                // a lambda outside [-2 pi, 2 pi] into (-pi, pi], in extended precision as sx_parcels_set does
-        const long double two_pi = 8.0L * atanl(1.0L);
-        for (int64_t i = 0; i < n; i++) {
-            if (std::fabs(start[n + i]) <= 6.283185307179586) continue;      // a gridpoint's lambda is used as given: frozen, it comes back bitwise
-            double l = (double)remainderl((long double)start[n + i], two_pi);
-            if (l <= -M_PI) l = M_PI;
-            s0[n + i] = l;
-        }
-    }
+    if (h->has_l)                                  // a lambda outside [-2 pi, 2 pi] into (-pi, pi]; a gridpoint's is used as given: frozen, it comes back bitwise
+        for (int64_t i = 0; i < n; i++)
+            if (std::fabs(start[n + i]) > 6.283185307179586) s0[n + i] = wrap_lambda(start[n + i]);
     flush_diag(h);                                 // as for every reader of A
     HIPCHK(hipMemcpyAsync(st->d_f, s0.data(), sizeof(double) * blk, hipMemcpyHostToDevice, h->stream));
     if (error_status()) return 1;
 
     RefineArgs a;
-    a.A = h->d_A; a.w3 = k ? st->d_w3 + (size_t)k->vcls[var - 1] * per : nullptr;
+    a.A = h->d_A; a.w3 = k ? k->d_w3 + (size_t)k->vcls[var - 1] * per : nullptr;
     a.start = st->d_f; a.pos = st->d_f + blk; a.grad = st->d_f + 2 * blk; a.value = st->d_f + 3 * blk;
     a.status = st->d_i; a.iters = st->d_i + n;
     a.C = h->C; a.n = n; a.var = var - 1;

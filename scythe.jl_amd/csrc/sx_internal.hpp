@@ -212,6 +212,7 @@ struct EvalClasses {    // the vertical boundary-condition classes of a handle's
     std::vector<EvalVert> vert;       // empty without a vertical
     std::vector<int> vcls;            // [V] class of each variable
     DevBuf<int> d_vcls;
+    DevBuf<double> d_w3;              // [ncls][3][nz][Zb] CA, Dc CA, Dc Dc CA of every class (EvalVert::W rounded once): the point kernels' rows
 };
 
 // ---- device-side tables handed to the kernels -----------------------------------------------------------------------
@@ -527,19 +528,13 @@ bool eval_radius_ok(const EvalGeom &g, double r, std::string &why);
 bool eval_height_ok(const EvalGeom &g, double z, std::string &why);
 bool eval_points_ok(const sx_handle *h, const double *pts /*[n_coord][n]*/, int64_t n, const char *who, const char *noun);
 const EvalClasses *eval_classes(sx_handle *h);   // made on first use (sx_eval.hip); null when that failed
-// lanes of the workgroup that sums one point's columns of A (k_parcels, k_refine): from the grid alone, so that a point's result does
-// not depend on the other points of the launch
-constexpr int PARCEL_T = 256;             // lanes per point on grids with many columns (the bench grid: ~11,000 per variable)
-constexpr int PARCEL_T_SMALL = 64;        // one wave: rl_cha_bell2024's 601 columns are 10 per lane
-constexpr int PARCEL_WAVE_COLS = 1024;
-inline int parcel_threads(const sx_handle *h) { return (int64_t)h->Zb * h->K2 <= PARCEL_WAVE_COLS ? PARCEL_T_SMALL : PARCEL_T; }
-// value of the cardinal cubic B-spline (bspl of sx_setup.cpp, d = 0) as k_parcels and k_vortex_rings form it from a point's own radius
-__device__ inline double parcel_bspl(double delta) {
-    const double z = fabs(delta);
-    if (z >= 2.0) return 0.0;
-    const double p = 2.0 - z, q = z < 1.0 ? 1.0 - z : 0.0;
-    return p * p * p / 6.0 - 4.0 * q * q * q / 6.0;
-}
+// lambda into (-pi, pi], reduced in extended precision (sx_eval.hip).  sx_parcels_set wraps every lambda; sx_extremum_refine,
+// sx_crossings and sx_isosurface only one outside [-2 pi, 2 pi]: a gridpoint's lambda is used as given (frozen, it comes back bitwise)
+double wrap_lambda(double lam);
+// what sx_crossings and sx_isosurface refuse alike of the program's coefficients, the levels, the bounds and the count n of `noun`
+// (count: its argument's name), in the order the header lists (sx_crossings.hip)
+bool scan_args_ok(const sx_handle *h, const char *who, const char *count, const char *noun, int n_terms, const double *coef, int n_levels,
+                  int max_cross, const double *levels, int64_t n, double tol);
 double extrema_bytes(const sx_handle *h, bool refine);   // bytes of the last sx_extrema (k_extrema) / sx_extremum_refine (k_refine)
 double crossings_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_crossings: k_ray_profiles / k_crossings (sx_crossings.hip)
 double antiderivative_bytes(const sx_handle *h, bool vertical);   // bytes of the last sx_antiderivative along r (k_antiderivative_r) / z (k_antiderivative_z)

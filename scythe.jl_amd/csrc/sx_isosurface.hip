@@ -7,17 +7,17 @@
 // k_column_profiles (grids with an azimuth) runs it on the f64 matrix cores per batch of at most 16 columns of one radial cell: a wave
 // owns 16 z-modes x the batch's columns of one variable, stages the live A elements of the cell's 4 node rows through LDS (coalesced
 // block runs in, the A-operand layout out: one K step is the 4 nodes of one block), forms the B operand phi F on the fly from the
-// lane's own spline weights and the wave's table of cos / sin k lambda, and keeps one accumulator per (radial, azimuthal) order the
-// program names.  The K order is block 0, 2, 3, ... (block 1 is the padding block and is never read), node 0 .. 3 within a block,
-// whatever the columns are; columns of the product do not mix and a short batch is padded with zero weights: a column's profile is
-// bitwise independent of the other columns of the call, of their number and of their order.  Without an azimuth (RZ) K is 4 and
-// k_column_profiles_rz takes one lane per output instead.
+// lane's own spline weights and the wave's table of cos / sin k lambda (both sx_point.hpp's), and keeps one accumulator per (radial,
+// azimuthal) order the program names.  The K order is block 0, 2, 3, ... (block 1 is the padding block and is never read), node
+// 0 .. 3 within a block, whatever the columns are; columns of the product do not mix and a short batch is padded with zero
+// weights: a column's profile is bitwise independent of the other columns of the call, of their number and of their order.
+// Without an azimuth (RZ) K is 4 and k_column_profiles_rz takes one lane per output instead.
 //
 // k_isosurface: one wave per column.  The wave expands the profiles into the full series a = CA C, a' = Dc a, a'' = Dc a' in LDS
-// once; lanes then take the stations (the zDim levels, bottom to top) in chunks of 64, evaluate the program from the series with
-// column_series - the function sx_column_series runs on the host -, compare neighbours, number the crossings of a level upward with
-// a ballot, and every crossing is refined by its own lane with bracket_step (sx_bracket.hpp).  No atomics, nothing summed across columns.
-#include "sx_bracket.hpp"
+// once, then runs scan_crossings (sx_point.hpp: the loop k_crossings runs) over the stations (the zDim levels, bottom to top), the
+// program evaluated from the series with column_series - the function sx_column_series runs on the host: the crossings of a level
+// are numbered upward and every crossing is refined by its own lane with bracket_step.  No atomics, nothing summed across columns.
+#include "sx_point.hpp"
 #include "sx_redprog.hpp"
 #include <algorithm>
 #include <cmath>
@@ -26,13 +26,12 @@
 
 namespace sx {
 
-constexpr int ISO_LEVELS = 8, ISO_MAX = 16, ISO_CARRY = 8;
+constexpr int ISO_CARRY = 8;
 constexpr int ISO_KINDS = 5;              // profile kinds of a variable, (sr, sl) = (0, 0) (1, 0) (2, 0) (0, 1) (0, 2)
 constexpr int ISO_BATCH = 16;             // columns of one radial cell per matrix product
 constexpr int ISO_KC = 32;                // blocks of A per staged tile: 32 K steps
 constexpr int ISO_AS = 36;                // row stride of the staged tile in doubles
 constexpr size_t ISO_LDS_MAX = 64 * 1024;
-constexpr int64_t ISO_COLS_MAX = (int64_t)1 << 20;
 
 typedef double iso_d4 __attribute__((ext_vector_type(4)));
 
@@ -51,13 +50,6 @@ __host__ __device__ inline double column_series(int nz, double zmin, double zmax
         tm = t; t = tn;
     }
     return s;
-}
-
-// phi^(d) / DX^d of node `node` of cell `cell` at r, as cross_basis of sx_crossings.hip and k_parcels form it: delta = (r - x_node) / DX
-__host__ __device__ inline double iso_phi(double xmin, double DX, int cell, int node, double r, int d) {
-    const double delta = (r - (xmin + (double)(cell - 1 + node) * DX)) / DX;
-    const double b = cross_bspl(delta, d);
-    return d == 0 ? b : d == 1 ? b / DX : b / (DX * DX);
 }
 
 // ---- stage 1: the column profiles ----------------------------------------------------------------------------------------------------
@@ -98,15 +90,9 @@ __global__ __launch_bounds__(64) void k_column_profiles(ColProfArgs a) {
     if (col_on) {
         const double r = a.cols[a.order[b.first + j]];
 #pragma unroll
-        for (int d = 0; d < 3; d++) phi[d] = iso_phi(a.xmin, a.DX, b.cell, kk, r, d);
+        for (int d = 0; d < 3; d++) phi[d] = point_phi(a.xmin, a.DX, b.cell, kk, r, d);
     }
-    for (int e = lane; e < 16 * (a.kDim + 1); e += 64) {
-        const int k = e >> 4, q = e & 15;
-        const double lam = q < b.n ? a.cols[(int64_t)a.n_cols + a.order[b.first + q]] : 0.0;
-        double s, c;
-        sincos((double)k * lam, &s, &c);       // |lambda| <= 2 pi: the product is off by at most 2 k pi eps
-        cs[e] = make_double2(c, s);
-    }
+    az_table16(cs, a.kDim, lane, [&](int q) { return q < b.n ? a.cols[(int64_t)a.n_cols + a.order[b.first + q]] : 0.0; });
 
     // ---- the product: K = (block, node), one block per step
     iso_d4 acc[ISO_KINDS];
@@ -117,7 +103,7 @@ __global__ __launch_bounds__(64) void k_column_profiles(ColProfArgs a) {
     for (int c0 = 0; c0 < a.K2; c0 += ISO_KC) {
         __syncthreads();                                           // the tile (and, the first time, the table) of the pass before
         const int blk_in = c0 + cl;
-        const bool blk_on = blk_in < a.K2 && blk_in != 1;          // block 1 is the padding block: never read
+        const bool blk_on = blk_in < a.K2 && !az_padding(blk_in);  // never read
 #pragma unroll 4
         for (int rr = 0; rr < 32; rr++) {
             const int row = 2 * rr + rh, node = row >> 4, zm = m0 + (row & 15);
@@ -127,14 +113,10 @@ __global__ __launch_bounds__(64) void k_column_profiles(ColProfArgs a) {
         for (int s = 0; s < ISO_KC; s++) {
             const int blk = c0 + s;
             if (blk >= a.K2) break;                                // uniform
-            if (blk == 1) continue;
+            if (az_padding(blk)) continue;
             const double av = sA[(kk * 16 + j) * ISO_AS + s];      // A operand: row (z-mode) lane & 15, column (node) lane >> 4
-            // F_blk and its lambda derivatives: block 0 is 1; Re k: 2 cos, -2 k sin, -2 k^2 cos; Im k: -2 sin, -2 k cos, 2 k^2 sin
-            const int k = blk >> 1;
-            const double2 t = cs[k * 16 + j];
-            const double kd = (double)k;
-            const double x = (blk & 1) ? -t.y : t.x, y = (blk & 1) ? -t.x : -t.y;
-            const double F0 = blk == 0 ? 1.0 : 2.0 * x, F1 = 2.0 * kd * y, F2 = -(kd * kd) * F0;
+            double F0, F1, F2;
+            az_factors(blk, cs + j, 16, F0, F1, F2);
             if (pv.prof[0] >= 0) acc[0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, phi[0] * F0, acc[0], 0, 0, 0);
             if (pv.prof[1] >= 0) acc[1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, phi[1] * F0, acc[1], 0, 0, 0);
             if (pv.prof[2] >= 0) acc[2] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, phi[2] * F0, acc[2], 0, 0, 0);
@@ -165,12 +147,11 @@ __global__ __launch_bounds__(256) void k_column_profiles_rz(ColProfArgs a) {
     const int zm = (int)(e % a.Zb), p = (int)(e / a.Zb % a.nprof);
     const int64_t c = e / ((int64_t)a.Zb * a.nprof);
     const double r = a.cols[c];
-    int cell = (int)floor((r - a.xmin) / a.DX);
-    cell = min(max(cell, a.cell_lo), a.cell_hi);
+    const int cell = point_cell(a.xmin, a.DX, a.cell_lo, a.cell_hi, r);
     const double *__restrict__ Av = a.A + (int64_t)cell * a.C + ((int64_t)a.pvar[p] * a.Zb + zm) * a.K2;
     double acc = 0.0;
 #pragma unroll
-    for (int node = 0; node < 4; node++) acc = fma(Av[(int64_t)node * a.C], iso_phi(a.xmin, a.DX, cell, node, r, a.psr[p]), acc);
+    for (int node = 0; node < 4; node++) acc = fma(Av[(int64_t)node * a.C], point_phi(a.xmin, a.DX, cell, node, r, a.psr[p]), acc);
     a.P[e] = acc;
 }
 
@@ -184,7 +165,7 @@ struct IsoArgs {
     RedProg g;
     uint8_t pser[RED_PLANES];             // plane -> its series in LDS
     uint8_t fcls[RED_PLANES], fneed[RED_PLANES], fser[RED_PLANES][3];   // profile -> vertical class, z orders named (bits), series of each (n_ser, n_ser + 1: scratch)
-    double level[ISO_LEVELS];
+    double level[SCAN_LEVELS];
     double wtol, zmin, zmax;              // wtol = tol (zmax - zmin)
     int n_cols, nprof, Zb, nz, ncls, n_ser, n_levels, max_iter, max_cross, n_carry;
 };
@@ -206,7 +187,6 @@ __device__ inline double iso_output(const IsoArgs &a, int o, const double (&val)
 // grid (n_cols), one wave
 __global__ __launch_bounds__(64) void k_isosurface(IsoArgs a) {
     extern __shared__ double ser[];       // [n_ser + 2][nz]
-    __shared__ int s_cnt[ISO_LEVELS];
     const int lane = threadIdx.x, nz = a.nz;
     const int64_t q = blockIdx.x;
     const double *__restrict__ Pq = a.P + q * a.nprof * a.Zb;
@@ -244,72 +224,20 @@ __global__ __launch_bounds__(64) void k_isosurface(IsoArgs a) {
     }
 
     const double r = a.cols[q], rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
-    double *__restrict__ hgt = a.height + q * a.n_levels * a.max_cross;
-    int *__restrict__ dir = a.dir + q * a.n_levels * a.max_cross;
-    double *__restrict__ car = a.carry + q * a.n_levels * a.max_cross * a.n_carry;
-    int cnt[ISO_LEVELS];
-#pragma unroll
-    for (int j = 0; j < ISO_LEVELS; j++) cnt[j] = 0;
-    int status = 0;
-    double carry_g = 0.0, carry_z = 0.0;
-    double val[RED_PLANES];
-    for (int base = 0; base < nz; base += 64) {
-        const int s = base + lane;
-        const bool has = s < nz;
-        const double z = zst[has ? s : nz - 1];
-        iso_planes(a, ser, z, val);
-        const double g = iso_output(a, 0, val, r, rr, ri, rri);
-        if (has) a.values[q * nz + s] = g;
-        double gp = __shfl_up(g, 1, 64), zp = __shfl_up(z, 1, 64);
-        if (lane == 0) { gp = carry_g; zp = carry_z; }            // the chunk before ended on station base - 1
-        carry_g = __shfl(g, 63, 64); carry_z = __shfl(z, 63, 64);
-        const bool iv = has && s > 0;                              // this lane owns the interval [s - 1, s]
-#pragma unroll
-        for (int j = 0; j < ISO_LEVELS; j++) {
-            if (j >= a.n_levels) break;
-            const double c = a.level[j];
-            const double d0 = gp - c, d1 = g - c;
-            const bool nan = iv && (d0 != d0 || d1 != d1);
-            const bool cross = iv && !nan && ((d0 < 0.0) != (d1 < 0.0));
-            if (__ballot(nan)) status |= 1;
-            const unsigned long long mask = __ballot(cross);
-            const int pos = cnt[j] + __popcll(mask & ((1ull << lane) - 1ull));
-            cnt[j] += __popcll(mask);
-            if (cross && pos < a.max_cross) {
-                Bracket B;
-                B.a = zp; B.fa = d0; B.b = z; B.fb = d1;
-                int st = bracket_start(B, a.wtol);
-                for (int it = 0; st < 0 && it < a.max_iter; it++) {
-                    iso_planes(a, ser, B.x, val);
-                    st = bracket_step(B, iso_output(a, 0, val, r, rr, ri, rri) - c, a.wtol);
-                }
-                if (st != 0) status |= st < 0 ? 2 : 4;
-                const double zr = bracket_root(B);
-                hgt[j * a.max_cross + pos] = zr;
-                dir[j * a.max_cross + pos] = d0 < 0.0 ? 1 : -1;
-                if (a.n_carry > 0) {
-                    iso_planes(a, ser, zr, val);
-                    for (int o = 0; o < a.n_carry; o++) car[(j * a.max_cross + pos) * a.n_carry + o] = iso_output(a, 1 + o, val, r, rr, ri, rri);
-                }
-            }
-        }
-    }
-    // bits 1 and 2 are a lane's own: fold them over the wave
-    status = (status & 1) | (__ballot(status & 2) ? 2 : 0) | (__ballot(status & 4) ? 4 : 0);
-    if (lane == 0) {
-#pragma unroll
-        for (int j = 0; j < ISO_LEVELS; j++)
-            if (j < a.n_levels) { s_cnt[j] = cnt[j]; a.count[q * a.n_levels + j] = cnt[j]; }
-        a.status[q] = status;
-    }
-    __syncthreads();
-    for (int e = lane; e < a.n_levels * a.max_cross; e += 64) {    // the entries no crossing took
-        const int j = e / a.max_cross, pos = e - j * a.max_cross;
-        if (pos >= s_cnt[j]) {
-            hgt[e] = __builtin_nan(""); dir[e] = 0;
-            for (int o = 0; o < a.n_carry; o++) car[e * a.n_carry + o] = __builtin_nan("");
-        }
-    }
+    const int64_t e0 = q * a.n_levels * a.max_cross;
+    const ScanOut o = {a.height + e0, a.dir + e0, a.count + q * a.n_levels, a.status + q, a.values + q * nz, a.carry + e0 * a.n_carry, a.n_carry};
+    scan_crossings(
+        nz, a.level, a.n_levels, a.wtol, a.max_iter, a.max_cross, o, [&](int s) { return zst[s]; },
+        [&](double z) {
+            double val[RED_PLANES];
+            iso_planes(a, ser, z, val);
+            return iso_output(a, 0, val, r, rr, ri, rri);
+        },
+        [&](double z, double *car) {
+            double val[RED_PLANES];
+            iso_planes(a, ser, z, val);
+            for (int c = 0; c < a.n_carry; c++) car[c] = iso_output(a, 1 + c, val, r, rr, ri, rri);
+        });
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
@@ -428,16 +356,7 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     const EvalGeom g = eval_geom_of(h);
     IsoPlan pl;
     if (iso_plan(&gd, g, who, n_terms, terms, n_carry, pl)) return 1;
-    if (n_terms > 0 && !coef) { set_error("sx_isosurface: null coef with n_terms > 0"); return 1; }
-    if (n_levels < 1 || n_levels > ISO_LEVELS) { set_error("sx_isosurface: n_levels must be 1 .. 8"); return 1; }
-    if (max_cross < 1 || max_cross > ISO_MAX) { set_error("sx_isosurface: max_cross must be 1 .. 16"); return 1; }
-    if (!levels) { set_error("sx_isosurface: null levels"); return 1; }
-    if (n_cols < 0) { set_error("sx_isosurface: n_cols is negative"); return 1; }
-    if (n_cols > ISO_COLS_MAX) { set_error("sx_isosurface: more than 2^20 columns in one call"); return 1; }
-    if (!std::isfinite(tol)) { set_error("sx_isosurface: tol is NaN or Inf"); return 1; }
-    for (int j = 0; j < n_levels; j++)
-        if (!std::isfinite(levels[j])) { set_error("sx_isosurface: level " + std::to_string(j) + " is NaN or Inf"); return 1; }
-    if (h->ncells != h->nc) { set_error("sx_isosurface: one-tile patches only"); return 1; }
+    if (!scan_args_ok(h, who, "n_cols", "columns", n_terms, coef, n_levels, max_cross, levels, n_cols, tol)) return 1;
     if (n_cols > 0 && (!columns || !height || !dir || !count || !status || (n_carry > 0 && !carry))) { set_error("sx_isosurface: null argument with n_cols > 0"); return 1; }
     if (n_carry == 0 && carry) { set_error("sx_isosurface: carry must be NULL when n_carry == 0"); return 1; }
     bool neg_p = false;
@@ -473,19 +392,12 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     // the columns by radial cell (within a cell the caller's order), each cell's in batches of at most 16
     std::vector<double> c0((size_t)ncc * n_cols);
     std::memcpy(c0.data(), columns, sizeof(double) * c0.size());
-    if (h->has_l) {                                // a lambda outside [-2 pi, 2 pi] into (-pi, pi], in extended precision as for the rays
-        const long double two_pi = 8.0L * atanl(1.0L);
-        for (int64_t i = 0; i < n_cols; i++) {
-            const double lam = columns[n_cols + i];
-            if (std::fabs(lam) <= 6.283185307179586) continue;
-            double l = (double)remainderl((long double)lam, two_pi);
-            if (l <= -M_PI) l = M_PI;
-            c0[n_cols + i] = l;
-        }
-    }
+    if (h->has_l)                                  // a lambda outside [-2 pi, 2 pi] into (-pi, pi]
+        for (int64_t i = 0; i < n_cols; i++)
+            if (std::fabs(columns[n_cols + i]) > 6.283185307179586) c0[n_cols + i] = wrap_lambda(columns[n_cols + i]);
     const int cell_lo = h->cell0, cell_hi = h->cell0 + h->ncells - 1;
     std::vector<int> cell(n_cols), idx(n_cols);
-    for (int64_t i = 0; i < n_cols; i++) cell[i] = std::min(std::max((int)std::floor((columns[i] - h->xmin) / h->DX), cell_lo), cell_hi);
+    for (int64_t i = 0; i < n_cols; i++) cell[i] = point_cell(h->xmin, h->DX, cell_lo, cell_hi, columns[i]);
     std::iota(idx.begin(), idx.end(), 0);
     std::vector<IsoBatch> batches;
     if (h->has_l) {

@@ -1,30 +1,29 @@
 // sx_parcels_*: Lagrangian parcels advected with the model on the device (include/scythe_hip.h).
 //
-// The parcel arrays live in HBM; one launch of k_parcels is one step of every active parcel: the kernel forms the parcel's
-// weights from its position (4 spline values, the Chebyshev row t(x) CA of each velocity variable, cos / sin k lambda), sums the
-// two or three velocity variables from A in ONE pass over the 4 node rows (the weights and the sines are shared), and lane 0
-// moves the parcel with the model's Adams-Bashforth scheme (ab_value, sx_internal.hpp).  Nothing is made on the host per step and
-// the launch is the only thing sx_parcels_advance enqueues.
+// The parcel arrays live in HBM; one launch of k_parcels is one step of every active parcel: the kernel forms the parcel's weights
+// from its position with the functions of sx_point.hpp (4 spline values, the Chebyshev row t(x) CA of each velocity variable, cos /
+// sin k lambda), sums the two or three velocity variables from A in ONE pass over the 4 node rows (the weights and the sines are
+// shared), and lane 0 moves the parcel with the model's Adams-Bashforth scheme (ab_value, sx_internal.hpp).  Nothing is made on the
+// host per step and the launch is the only thing sx_parcels_advance enqueues.
 //
 // One workgroup per parcel, PARCEL_T_SMALL lanes (a wave) where a variable has at most PARCEL_WAVE_COLS columns and PARCEL_T
 // lanes above: the choice, the column a lane sums (col = lane, lane + T, ...) and the order of the reduction (butterfly within a
 // wave, waves in order) depend on the grid alone, so a parcel's path is bitwise independent of the other parcels of the set.
-#include "sx_internal.hpp"
+#include "sx_point.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 
 namespace sx {
 
-// PARCEL_T, PARCEL_T_SMALL, PARCEL_WAVE_COLS, parcel_threads and parcel_bspl: sx_internal.hpp (k_refine of sx_extrema.hip takes the same lanes,
-// k_vortex_rings of sx_vortex.hip the same spline arithmetic)
+// PARCEL_T, PARCEL_T_SMALL, PARCEL_WAVE_COLS and parcel_threads: sx_point.hpp (k_refine of sx_extrema.hip takes the same lanes)
 constexpr size_t PARCEL_LDS_MAX = 64 * 1024;
 static const double PARCEL_MAGIC = 7.7012e7;
 constexpr int PARCEL_HDR = 6;             // blob header: magic, n, n_coord, var_r, var_l, var_z
 
 struct ParcelArgs {
     const double *A;       // [b_rDim][C]
-    const double *ca;      // [ncls][nz][Zb] CA of the vertical classes (EvalVert::W[0] rounded once)
+    const double *w3;      // [ncls][3][nz][Zb] EvalClasses::d_w3; row 0 of a class, CA, is read (null without a vertical)
     double *pos, *vel, *h1, *h2;   // [n_coord][n]: position, last evaluated velocity, history levels n - 1 and n - 2
     int *cnt, *status;     // [n] steps taken; 0 active, 1 left radially, 2 left vertically
     int64_t C, n;
@@ -50,30 +49,17 @@ __global__ __launch_bounds__(PARCEL_T) void k_parcels(ParcelArgs a) {
     const double z = a.cz >= 0 ? a.pos[(int64_t)a.cz * a.n + i] : 0.0;
 
     // ---- weights
-    int cell = (int)floor((r - a.xmin) / a.DX);
-    cell = min(max(cell, a.cell_lo), a.cell_hi);
-    double phi[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) phi[j] = parcel_bspl((r - (a.xmin + (double)(cell - 1 + j) * a.DX)) / a.DX);
-    for (int k = tid; k <= a.kDim; k += T) {
-        double s, c;
-        sincos((double)k * lam, &s, &c);   // lambda is kept in (-pi, pi]: the product is off by at most k pi eps
-        cs[k] = make_double2(c, s);
-    }
+    const int cell = point_cell(a.xmin, a.DX, a.cell_lo, a.cell_hi, r);
+    double phi[1][4];
+    point_basis<1>(a.xmin, a.DX, cell, r, phi);
+    az_table(cs, a.kDim, lam, tid, T);     // lambda is kept in (-pi, pi]
     if (a.cz >= 0) {
-        const double mid = (a.zmin + a.zmax) / 2.0, half = (a.zmax - a.zmin) / 2.0;
-        const double x = fmin(fmax((z - mid) / (-half), -1.0), 1.0);
-        const double th = acos(x);
-        for (int n = tid; n < a.nz; n += T) tz[n] = ((n == 0 || n == a.nz - 1) ? 1.0 : 2.0) * cos((double)n * th);
+        const double th = cheb_theta(a.zmin, a.zmax, z);
+        for (int n = tid; n < a.nz; n += T) tz[n] = cheb_entry(n, a.nz, th);
         __syncthreads();
         for (int q = tid; q < 3 * a.Zb; q += T) {
             const int m = q / a.Zb, zm = q - m * a.Zb;
-            double acc = 0.0;
-            if (a.var[m] >= 0) {
-                const double *ca = a.ca + (size_t)a.cls[m] * a.nz * a.Zb + zm;
-                for (int n = 0; n < a.nz; n++) acc = fma(tz[n], ca[(size_t)n * a.Zb], acc);
-            }
-            wz[q] = acc;
+            wz[q] = a.var[m] >= 0 ? cheb_weight(tz, 1, a.w3 + (size_t)a.cls[m] * 3 * a.nz * a.Zb + zm, a.nz, a.Zb) : 0.0;
         }
     } else {
         for (int q = tid; q < 3 * a.Zb; q += T) wz[q] = 1.0;      // Zb = 1 without a vertical
@@ -86,37 +72,23 @@ __global__ __launch_bounds__(PARCEL_T) void k_parcels(ParcelArgs a) {
     const double *__restrict__ Ac = a.A + (int64_t)cell * a.C;
     for (int col = tid; col < ncol; col += T) {
         const int zm = col / a.K2, blk = col - zm * a.K2;
-        if (blk == 1) continue;                                   // padding: Im of k = 0
-        const int k = blk >> 1;
-        const double2 t = cs[k];
-        const double F = blk == 0 ? 1.0 : 2.0 * ((blk & 1) ? -t.y : t.x);      // block 0: 1; 2k: 2 cos; 2k + 1: -2 sin
+        if (az_padding(blk)) continue;
+        const double F = az_factor(blk, cs, 1);
 #pragma unroll
         for (int m = 0; m < 3; m++) {
             if (a.var[m] < 0) continue;
             const double *__restrict__ p = Ac + (int64_t)a.var[m] * ncol + col;
-            const double s = fma(phi[3], p[3 * a.C], fma(phi[2], p[2 * a.C], fma(phi[1], p[a.C], phi[0] * p[0])));
+            const double s = fma(phi[0][3], p[3 * a.C], fma(phi[0][2], p[2 * a.C], fma(phi[0][1], p[a.C], phi[0][0] * p[0])));
             acc[m] = fma(s, F * wz[m * a.Zb + zm], acc[m]);
         }
     }
-    const int lane = tid & 63, wave = tid >> 6, nw = T >> 6;
-#pragma unroll
-    for (int m = 0; m < 3; m++) {
-        double x = acc[m];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-        if (lane == 0) red[wave * 3 + m] = x;
-    }
-    __syncthreads();
+    point_sum<3>(acc, red, tid, T);
     if (tid != 0) return;
 
     // ---- the parcel moves
     double u[3];
 #pragma unroll
-    for (int m = 0; m < 3; m++) {
-        double x = red[m];
-        for (int w = 1; w < nw; w++) x += red[w * 3 + m];
-        u[m] = a.var[m] >= 0 ? x : 0.0;
-    }
+    for (int m = 0; m < 3; m++) u[m] = a.var[m] >= 0 ? acc[m] : 0.0;
     a.vel[(int64_t)a.cr * a.n + i] = u[0];
     if (a.cl >= 0) a.vel[(int64_t)a.cl * a.n + i] = u[1];
     if (a.cz >= 0) a.vel[(int64_t)a.cz * a.n + i] = u[2];
@@ -171,7 +143,6 @@ struct ParcelState : DiagState {
     int var[3] = {0, 0, 0};              // 1-based (var_r, var_l, var_z), 0 = no motion
     DevBuf<double> d_f;                  // pos | vel | h1 | h2, [n_coord][n] each
     DevBuf<int> d_i;                     // cnt | status
-    DevBuf<double> d_ca;                 // vertical classes, uploaded once per handle
     int cls[3] = {0, 0, 0};
     void drop_set() { d_f.release(); d_i.release(); n = 0; }      // the caller has synchronised the stream
 };
@@ -196,22 +167,14 @@ static bool parcel_vars_ok(const sx_handle *h, const int var[3], const char *who
     return true;
 }
 
-// the state of this handle, with the vertical classes on the device; the classes of the set's variables
+// the state of this handle; the classes of the set's variables
 static ParcelState *parcel_prepare(sx_handle *h, const int var[3], int cls[3]) {
     ParcelState *st = pstate(h);
     if (parcel_lds(h) > PARCEL_LDS_MAX) { set_error("sx_parcels: the weights of one parcel do not fit the LDS (kDim or zDim too large)"); return nullptr; }
     const EvalClasses *k = h->has_z ? eval_classes(h) : nullptr;
     if (h->has_z && !k) return nullptr;
     if (!st) {
-        std::unique_ptr<ParcelState> made(new ParcelState());
-        if (k) {
-            const size_t per = (size_t)h->nz * h->Zb;
-            std::vector<double> ca(k->vert.size() * per);
-            for (size_t c = 0; c < k->vert.size(); c++)
-                for (size_t q = 0; q < per; q++) ca[c * per + q] = (double)k->vert[c].W[0][q];
-            if (!made->d_ca.upload(ca, "sx_parcels: hipMalloc of the vertical operators failed")) return nullptr;
-        }
-        h->diag[DIAG_PARCELS] = std::move(made);
+        h->diag[DIAG_PARCELS].reset(new ParcelState());
         st = pstate(h);
     }
     for (int m = 0; m < 3; m++) cls[m] = k && var[m] != 0 ? k->vcls[var[m] - 1] : 0;
@@ -261,14 +224,8 @@ int sx_parcels_set(sx_handle *h, int64_t n, const double *positions, int32_t var
     std::vector<double> f((size_t)4 * nco * n, 0.0);
     std::vector<int> ic((size_t)2 * n, 0);
     std::memcpy(f.data(), positions, sizeof(double) * nco * n);
-    if (h->has_l) {                                // lambda into (-pi, pi], reduced in extended precision as sx_evaluate does
-        const long double two_pi = 8.0L * atanl(1.0L);
-        for (int64_t i = 0; i < n; i++) {
-            double l = (double)remainderl((long double)positions[n + i], two_pi);
-            if (l <= -M_PI) l = M_PI;
-            f[n + i] = l;
-        }
-    }
+    if (h->has_l)                                  // every lambda into (-pi, pi]
+        for (int64_t i = 0; i < n; i++) f[n + i] = wrap_lambda(positions[n + i]);
     if (!parcel_install(h, st, n, var, cls, f.data(), ic.data())) return 1;
     return error_status();
 }
@@ -290,7 +247,9 @@ int sx_parcels_advance(sx_handle *h, double dt) {
     const int nco = h->ncoord;
     const size_t blk = (size_t)nco * st->n;
     ParcelArgs a;
-    a.A = h->d_A; a.ca = st->d_ca;
+    const EvalClasses *k = h->has_z ? eval_classes(h) : nullptr;      // made by parcel_prepare when the set was installed
+    if (h->has_z && !k) return 1;
+    a.A = h->d_A; a.w3 = k ? (const double *)k->d_w3 : nullptr;
     a.pos = st->d_f; a.vel = st->d_f + blk; a.h1 = st->d_f + 2 * blk; a.h2 = st->d_f + 3 * blk;
     a.cnt = st->d_i; a.status = st->d_i + st->n;
     a.C = h->C; a.n = st->n;

@@ -18,10 +18,11 @@
 // and k_vortex_finish applies the vertical rows to (kmax + 1) x b_zDim numbers per accumulator.
 //
 // k_vortex_rings: grid (chunks of VORTEX_CHUNK sample points, live circles), VORTEX_T threads.  A workgroup walks its points in order.
-// Per point every thread forms the position, the 4 spline weights (parcel_bspl) and w; the cos / sin k lambda table goes to LDS as in
-// k_parcels; then ONE pass over the 4 node rows of A serves all distinct source variables of the call: a wave owns whole (variable,
-// zm) rows, its lanes stride over the contiguous blk axis (block 1, the padding, is skipped), a butterfly leaves g_v[zm] in LDS.  Then
-// thread t adds the point's rank-1 update to the entries (acc, k, zm) = t, t + VORTEX_T, ... of H, which it alone touches (LDS), with
+// Per point every thread forms the position, the 4 spline weights and w; the cos / sin k lambda table goes to LDS (both with the
+// functions of sx_point.hpp, as in k_parcels); then ONE pass over the 4 node rows of A serves all distinct source variables of the
+// call: a wave owns whole (variable, zm) rows, its lanes stride over the contiguous blk axis (block 1, the padding, is skipped), a
+// butterfly leaves g_v[zm] in LDS.  Then thread t adds the point's rank-1 update to the entries (acc, k, zm) = t, t + VORTEX_T, ...
+// of H, which it alone touches (LDS), with
 // e^{-i k phi_j} = conj(tab[(k j) mod n_az]) from the n_az-entry table the host forms in extended precision (the index is exact; no
 // device sincos of k phi; cos / sin phi_j of the positions are tab[j]).  The chunk's H goes to scratch.  Every order of summation - the
 // lane a column belongs to, the butterfly, the points of a chunk in order, the chunks in order - depends on the grid and on the call's
@@ -32,7 +33,7 @@
 // = 1 and a row of 1), forms rad = P(u Re w) - P(v Im w), tan = P(u Im w) + P(v Re w), divides by n_az, subtracts the motion, writes.
 //
 // Dynamic LDS, doubles: k_vortex_rings 2 (kDim + 1) + 2 n_acc (kmax + 1) b_zDim + n_src b_zDim; k_vortex_finish 4 (kmax + 1) b_zDim.
-#include "sx_internal.hpp"
+#include "sx_point.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -84,16 +85,10 @@ __global__ __launch_bounds__(VORTEX_T) void k_vortex_rings(VortexRingArgs a) {
         const double r = hypot(x, y);
         double lam = r == 0.0 ? 0.0 : atan2(y, x);
         if (lam <= -M_PI) lam = M_PI;                              // (-pi, pi]
-        int cell = (int)floor((r - a.xmin) / a.DX);
-        cell = min(max(cell, a.cell_lo), a.cell_hi);
-        double phi[4];
-#pragma unroll
-        for (int n = 0; n < 4; n++) phi[n] = parcel_bspl((r - (a.xmin + (double)(cell - 1 + n) * a.DX)) / a.DX);
-        for (int k = tid; k <= a.kDim; k += VORTEX_T) {
-            double s, c;
-            sincos((double)k * lam, &s, &c);
-            cs[k] = make_double2(c, s);
-        }
+        const int cell = point_cell(a.xmin, a.DX, a.cell_lo, a.cell_hi, r);
+        double phi[1][4];
+        point_basis<1>(a.xmin, a.DX, cell, r, phi);
+        az_table(cs, a.kDim, lam, tid, VORTEX_T);
         double sl, cl;
         sincos(lam, &sl, &cl);
         const double wre = (cl * t.x) + (sl * t.y), wim = (sl * t.x) - (cl * t.y);      // w = e^{i lambda} e^{-i phi}
@@ -106,10 +101,9 @@ __global__ __launch_bounds__(VORTEX_T) void k_vortex_rings(VortexRingArgs a) {
             const double *__restrict__ p = Ac + ((int64_t)a.src[s] * a.Zb + zm) * a.K2;
             double acc = 0.0;
             for (int blk = lane; blk < a.K2; blk += 64) {
-                if (blk == 1) continue;                            // padding: Im of k = 0
-                const double2 c = cs[blk >> 1];
-                const double F = blk == 0 ? 1.0 : 2.0 * ((blk & 1) ? -c.y : c.x);      // block 0: 1; 2k: 2 cos; 2k + 1: -2 sin
-                const double sum = fma(phi[3], p[3 * a.C + blk], fma(phi[2], p[2 * a.C + blk], fma(phi[1], p[a.C + blk], phi[0] * p[blk])));
+                if (az_padding(blk)) continue;
+                const double F = az_factor(blk, cs, 1);
+                const double sum = fma(phi[0][3], p[3 * a.C + blk], fma(phi[0][2], p[2 * a.C + blk], fma(phi[0][1], p[a.C + blk], phi[0][0] * p[blk])));
                 acc = fma(sum, F, acc);
             }
 #pragma unroll

@@ -178,8 +178,10 @@ def distance(g, p, q):
 
 
 # ----------------------------------------------------------------------------- the four test grids and their states
-def grid_case(geom):
-    """the smallest grids that exercise every branch: R 8 cells PERIODIC, RZ 6 x zDim 8, RL 6 cells and RLZ 5 x zDim 8 on native rings"""
+def grid_case(geom, wide=False):
+    """the smallest grids that exercise every branch: R 8 cells PERIODIC, RZ 6 x zDim 8, RL 6 cells and RLZ 5 x zDim 8 on native rings;
+    wide (RLZ only): RLZ 12 x zDim 24, whose 16 x 73 = 1,168 columns per variable are the smallest of this family above the 1,024 at which
+    a parcel's workgroup goes from one wave to four (k_parcels with 256 lanes: the waves added in order, the strided table fills)"""
     from tests import cases
     if geom == "R":
         return cases.r_bcs("PERIODIC", "PERIODIC", num_cells=8)
@@ -187,6 +189,9 @@ def grid_case(geom):
         return cases.rz_advection(num_cells=6, zDim=8)
     if geom == "RL":
         return cases.rl_advection(num_cells=6)
+    if wide:
+        assert geom == "RLZ"
+        return cases.rlz_advection(num_cells=12, zDim=24)
     return cases.rlz_advection(num_cells=5, zDim=8)
 
 

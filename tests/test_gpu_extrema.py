@@ -22,11 +22,13 @@ EPS = X.EPS
 CASES = {"rl8": ("rl_slab", dict(num_cells=8)), "rl8_L16": ("rl_slab", dict(num_cells=8, ring_L=16)),
          "rlz6_L16": ("rlz_hrbl", dict(num_cells=6, zDim=10, ring_L=16)), "rlz6": ("rlz_hrbl", dict(num_cells=6, zDim=10)),
          "rz10": ("rz_advection", dict(num_cells=10, zDim=14)), "r24": ("r_bcs", dict(num_cells=24))}
+# for the refinement only: 16 x 73 = 1,168 columns per variable, above the 1,024 at which k_refine goes from one wave to four
+WIDE = {"rlz12_wide": ("rlz_hrbl", dict(num_cells=12, zDim=24))}
 
 
 def _make(name, storage="f64"):
     import scythe_jl_amd as S
-    maker, kw = CASES[name]
+    maker, kw = CASES[name] if name in CASES else WIDE[name]
     case = getattr(cases, maker)(**kw)
     gp, mp = cases.hip_params(case, storage)
     g = cases.oracle_grid(case)
@@ -349,6 +351,8 @@ REFINE = {
     "RL at 3.4 DX": dict(name="rl8", var=1, centre=(3.4 * 3.75e4, -2.2), width=9.0e4, free="rl"),
     "RLZ interior": dict(name="rlz6_L16", var=1, centre=(2.3 * 5.0e4, 1.1), width=1.2e5, zc=900.0, zw=700.0, free="rlz"),
     "RLZ lowest level": dict(name="rlz6", var=1, centre=(2.3 * 5.0e4, 1.1), width=1.2e5, zc=0.0, zw=900.0, free="rl"),
+    "RZ interior": dict(name="rz10", var=1, centre=4.37e3, width=2.5e3, zc=4.2e3, zw=3.0e3, free="rz"),
+    "RLZ interior, 256 lanes": dict(name="rlz12_wide", var=1, centre=(2.3 * 5.0e4, 1.1), width=1.2e5, zc=900.0, zw=700.0, free="rlz"),
 }
 
 

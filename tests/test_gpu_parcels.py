@@ -14,9 +14,13 @@ pytestmark = pytest.mark.gpu
 MARGIN = 8.0
 
 
-def _tile(geom, A):
+# every geometry on its smallest grid, and RLZ on the grid above 1,024 columns per variable (256 lanes per parcel)
+GRIDS = [pytest.param(geom, False, id=geom) for geom in GEOMS] + [pytest.param("RLZ", True, id="RLZ_wide")]
+
+
+def _tile(geom, A, wide=False):
     import scythe_jl_amd as S
-    gp, mp = cases.hip_params(P.grid_case(geom))
+    gp, mp = cases.hip_params(P.grid_case(geom, wide))
     tile = S.Grid(gp, mp)
     tile.set_patch_spectral_a(A)
     return tile
@@ -38,12 +42,12 @@ def _bits(*arrays):
     return b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
 
 
-@pytest.mark.parametrize("geom", GEOMS)
-def test_velocity(geom):
-    g = cases.oracle_grid(P.grid_case(geom))
+@pytest.mark.parametrize("geom,wide", GRIDS)
+def test_velocity(geom, wide):
+    g = cases.oracle_grid(P.grid_case(geom, wide))
     A = P.smooth_state(g, seed=3)
     pts, var = P.special_points(g), P.velocity_vars(g)
-    tile = _tile(geom, A)
+    tile = _tile(geom, A, wide)
     tile.set_parcels(pts, P.VELOCITY[geom])
     tile.enable_timers(True)
     tile.advance_parcels(0.0)
@@ -107,15 +111,15 @@ def _random_run(geom, pts, steps=6, tile=None, A=None, g=None, dt=None):
     return path
 
 
-@pytest.mark.parametrize("geom", GEOMS)
-def test_frozen_random_state_and_independence(geom):
+@pytest.mark.parametrize("geom,wide", GRIDS)
+def test_frozen_random_state_and_independence(geom, wide):
     """67 parcels, 6 steps in a state that does not change: positions against the longdouble twin; the same parcels reversed and
     three of them alone take bitwise the same paths; an empty set advances and reads back empty"""
-    g = cases.oracle_grid(P.grid_case(geom))
+    g = cases.oracle_grid(P.grid_case(geom, wide))
     A = P.smooth_state(g, seed=11)
     pts, var = P.interior_points(g, 67, seed=13), P.velocity_vars(g)
     dt = P.crossing_dt(g, A, pts, var)
-    tile = _tile(geom, A)
+    tile = _tile(geom, A, wide)
     path = _random_run(geom, pts, tile=tile, dt=dt)
     hi = P.Parcels(g, pts, var, xp=True)
     for _ in range(6):
