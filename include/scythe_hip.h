@@ -895,6 +895,46 @@ int sx_stats_state_size(const sx_handle *h, int64_t *n_doubles);
 int sx_stats_get_state(sx_handle *h, double *out);
 int sx_stats_set_state(sx_handle *h, const double *in, int64_t n_doubles);
 
+/* --- field programs projected onto the spectral basis: derived fields as variables --------------------------------------
+ * What turns a program into a variable: sx_project evaluates a field program at the gridpoints of src on the device, writes output o
+ * as the var_np1 plane of variable var_dst[o] (1-based) of the companion handle dst, and runs dst's own forward transform and banded
+ * solve.  dst's variables are then spectral fields like any other - sx_evaluate, sx_harmonics, sx_spectrum, sx_vortex_harmonics,
+ * sx_elliptic_solve (SX_ELL_FIELD), sx_antiderivative, sx_extremum_refine and sx_tile_transform apply to the vorticity, a flux, the
+ * kinetic energy, the forcing of a balance equation.  The projection is the one the model applies to its own nonlinear tendencies:
+ * the same quadrature, the boundary-condition classes of dst's variables, dst's l_q filter and dst's truncation; no new numerics.
+ * Program and source are exactly those of sx_reduce (the same terms[n_terms][11], coef and limits, SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
+ * with their slot rules, validated by sx_reduce_planes itself).  The value of output o at a gridpoint is q_o as sx_extrema and
+ * sx_stats_accumulate form it: plain fp64, the terms added in term order starting from +0.0, r^p formed as r, r r, 1 / r or 1 / (r r),
+ * the factors multiplied in order; with storage_f32 the derivative slots are read in the type they are stored in.  A NaN or Inf is
+ * written as it comes out.  A product of two fields holds wavenumbers and z-modes up to the sum of the factors': what lies beyond
+ * dst's truncation aliases on the mish exactly as it does in the model's own tendencies.
+ * One kernel (k_project: streaming, a lane per two consecutive points where N is even, one otherwise; no atomics, nothing across
+ * lanes) on src's stream; dst's stream waits on an event recorded behind it and then runs launch_fl_forward, launch_sb, launch_solve
+ * for every variable of dst - the launches behind sx_spectral_transform + sx_spline_transform.  No device-wide synchronisation; the
+ * call returns after completion.  With SX_REDUCE_PHYSICAL the caller has run sx_tile_transform, as for sx_reduce; a deferred diagnostic
+ * variable of src is brought up to date first.
+ * Everything of src stays bitwise as it is: `physical`, var_np1, the tendency history, A, B, parcels, statistics, captured graphs.  In
+ * dst var_np1, B and A of every variable are overwritten; dst's `physical` is not touched and is stale until sx_tile_transform.  Two
+ * calls agree bitwise, and one output's coefficients do not depend on what the other outputs of the call are.
+ * Refused, with a message and before anything is written: a null handle; a null coef, terms or var_dst with a non-zero count;
+ * dst == src (the forward chain reads var_np1, which is the model's state); a src or dst that is not a one-tile patch; a dst that
+ * differs from src in geometry, xmin, xmax, num_cells, ring table, zDim, zmin or zmax (b_zDim may differ: the projection truncates as
+ * dst says; kDim follows from the ring table); n_out other than dst's number of variables; a var_dst that is not a permutation of
+ * 1 .. n_out; a dst whose equation set is not SX_EQ_NONE; whatever sx_reduce_planes refuses; an output with no term (its plane would be
+ * zero by accident, not by request).
+ * sx_kernel_bytes("k_project") gives the planes named x N x their element size (8, 4 for an fp32-stored plane) + n_out x N x 8.
+ *
+ * sx_project_check is that validation for two descriptors, on the host (all but the null handles, dst == src and the equation set, which
+ * a descriptor does not carry); sx_project calls it.  sx_project_point states the n_out outputs at ONE point on the host with the
+ * kernel's arithmetic, packed and formed by the code the kernel uses: val[j] is the value of plane (planes[j][0], planes[j][1]) there
+ * and r the point's radius; every plane a term names must be listed.  Pure host helpers (no handle, no device). */
+int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out, sx_handle *dst,
+               const int32_t *var_dst /*[n_out], 1-based, a permutation of 1 .. n_out*/);
+int sx_project_check(const sx_grid_desc *src, const sx_grid_desc *dst, int32_t source, int32_t n_terms, const int32_t *terms, int32_t n_out,
+                     const int32_t *var_dst);
+int sx_project_point(int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out, int32_t n_planes,
+                     const int32_t *planes /*[n_planes][2]*/, const double *val /*[n_planes]*/, double r, double *out /*[n_out]*/);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

@@ -164,6 +164,9 @@ SYMBOLS = {
     "sx_stats_state_size": (C.c_int, [_H, P_I64]),
     "sx_stats_get_state": (C.c_int, [_H, P_D]),
     "sx_stats_set_state": (C.c_int, [_H, P_D, C.c_int64]),
+    "sx_project": (C.c_int, [_H, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, _H, P_I32]),
+    "sx_project_check": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32]),
+    "sx_project_point": (C.c_int, [C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_I32, P_D, C.c_double, P_D]),
 }
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)

@@ -4,6 +4,7 @@
 #pragma once
 #include "sx_internal.hpp"
 #include <cstring>
+#include <type_traits>
 
 namespace sx {
 
@@ -35,8 +36,43 @@ __device__ inline void red_load_planes(const Planes<ST> &P, int V, int64_t N, in
     }
 }
 
-// term t at a point: coef r^p prod field, the factors in the program's order
-__device__ inline double red_term(const RedProg &g, int t, const double (&val)[RED_PLANES], double r, double rr, double ri, double rri) {
+// W consecutive points per lane: one 16-byte access of an fp64 plane (8 of an fp32-stored one) where W = 2
+template <int W> struct StatVec;
+template <> struct StatVec<1> { using d = double; using f = float; };
+template <> struct StatVec<2> { using d = double2; using f = float2; };
+__device__ inline double stat_lane(double v, int) { return v; }
+__device__ inline double stat_lane(float v, int) { return (double)v; }
+__device__ inline double stat_lane(const double2 &v, int k) { return k ? v.y : v.x; }
+__device__ inline double stat_lane(const float2 &v, int k) { return (double)(k ? v.y : v.x); }
+__device__ inline void stat_pack(double &o, const double (&a)[1]) { o = a[0]; }
+__device__ inline void stat_pack(double2 &o, const double (&a)[2]) { o = make_double2(a[0], a[1]); }
+
+// red_load_planes W points wide (k_stats, k_project): the planes of the program at W consecutive points from pt (a multiple of W), one access per plane
+template <class ST, int W>
+__device__ inline void stat_load_planes(const Planes<ST> &P, int V, int64_t N, int64_t pt, const RedProg &g, double (&val0)[RED_PLANES],
+                                        double (&val1)[RED_PLANES]) {
+    using VD = typename StatVec<W>::d;
+    using VS = typename std::conditional<std::is_same<ST, float>::value, typename StatVec<W>::f, VD>::type;
+#pragma unroll
+    for (int j = 0; j < RED_PLANES; j++) {
+        val0[j] = val1[j] = 0.0;
+        if (j < g.n_planes) {
+            const int v = g.pvar[j], s = g.pslot[j];
+            if (s == 0) {
+                const VD x = *reinterpret_cast<const VD *>(P.val + (int64_t)v * N + pt);
+                val0[j] = stat_lane(x, 0);
+                if (W == 2) val1[j] = stat_lane(x, 1);
+            } else {
+                const VS x = *reinterpret_cast<const VS *>(P.der + ((int64_t)(s - 1) * V + v) * N + pt);
+                val0[j] = stat_lane(x, 0);
+                if (W == 2) val1[j] = stat_lane(x, 1);
+            }
+        }
+    }
+}
+
+// term t at a point: coef r^p prod field, the factors in the program's order (also on the host: sx_project_point)
+__host__ __device__ inline double red_term(const RedProg &g, int t, const double (&val)[RED_PLANES], double r, double rr, double ri, double rri) {
     const int p = g.p[t], nf = g.nf[t];
     double x = g.coef[t];
     if (p != 0) x *= p == 1 ? r : p == 2 ? rr : p == -1 ? ri : rri;

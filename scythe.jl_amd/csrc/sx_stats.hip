@@ -14,7 +14,6 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
-#include <type_traits>
 
 namespace sx {
 
@@ -27,40 +26,6 @@ struct StatProg {
     double thr[RED_OUT];
     int8_t op[RED_OUT];
 };
-
-template <int W> struct StatVec;
-template <> struct StatVec<1> { using d = double; using f = float; };
-template <> struct StatVec<2> { using d = double2; using f = float2; };
-__device__ inline double stat_lane(double v, int) { return v; }
-__device__ inline double stat_lane(float v, int) { return (double)v; }
-__device__ inline double stat_lane(const double2 &v, int k) { return k ? v.y : v.x; }
-__device__ inline double stat_lane(const float2 &v, int k) { return (double)(k ? v.y : v.x); }
-__device__ inline void stat_pack(double &o, const double (&a)[1]) { o = a[0]; }
-__device__ inline void stat_pack(double2 &o, const double (&a)[2]) { o = make_double2(a[0], a[1]); }
-
-// red_load_planes W points wide: the planes of the program at W consecutive points from pt (a multiple of W), one access per plane
-template <class ST, int W>
-__device__ inline void stat_load_planes(const Planes<ST> &P, int V, int64_t N, int64_t pt, const RedProg &g, double (&val0)[RED_PLANES],
-                                        double (&val1)[RED_PLANES]) {
-    using VD = typename StatVec<W>::d;
-    using VS = typename std::conditional<std::is_same<ST, float>::value, typename StatVec<W>::f, VD>::type;
-#pragma unroll
-    for (int j = 0; j < RED_PLANES; j++) {
-        val0[j] = val1[j] = 0.0;
-        if (j < g.n_planes) {
-            const int v = g.pvar[j], s = g.pslot[j];
-            if (s == 0) {
-                const VD x = *reinterpret_cast<const VD *>(P.val + (int64_t)v * N + pt);
-                val0[j] = stat_lane(x, 0);
-                if (W == 2) val1[j] = stat_lane(x, 1);
-            } else {
-                const VS x = *reinterpret_cast<const VS *>(P.der + ((int64_t)(s - 1) * V + v) * N + pt);
-                val0[j] = stat_lane(x, 0);
-                if (W == 2) val1[j] = stat_lane(x, 1);
-            }
-        }
-    }
-}
 
 // one sample of one output at one point: (a, b) is (hi, lo) or (value, time); what the header says of the four operations
 __device__ inline void stat_update(int op, double q, double thr, double time, double w, bool first, double &a, double &b) {

@@ -12,7 +12,8 @@ import time
 
 import numpy as np
 
-from .model import (Distribution, Grid, GridParameters, ModelParameters, Statistics, calcTileSizes, checkCFL, comm_unique_id, getGridpoints)
+from .model import (Distribution, Grid, GridParameters, ModelParameters, Statistics, calcTileSizes, checkCFL, comm_unique_id, getGridpoints,
+                    program_of_outputs)
 
 Located = collections.namedtuple("Located", "pos value status")
 WindRadii = collections.namedtuple("WindRadii", "thresholds azimuths radii quadrants")
@@ -579,11 +580,17 @@ class ModelRun:
         self._check_stream()
         return self.tiles[0].invert((kind, u, v), alpha, into, var)
 
-    def streamfunction(self, u=None, v=None, alpha=0.0, into=None, var=1):
+    def streamfunction(self, u=None, v=None, alpha=0.0, into=None, var=1, rhs=None):
         """The streamfunction psi of the wind, lap psi = vorticity, solved on the device from the A coefficients of time n
         (Grid.invert): returns the Grid that holds psi (a cached one-variable companion unless `into` names one; psi = 0 at the outer
         edge by default).  The rotational wind is (-psi_l / r, psi_r).  u, v: variable names or 1-based indices; the slab and linear
-        shallow-water sets know theirs.  One-tile RL / RLZ patches."""
+        shallow-water sets know theirs.  rhs=<terms> solves lap psi = that field program of `physical` instead - an arbitrary
+        forcing, projected first (project).  One-tile RL / RLZ patches."""
+        if rhs is not None:
+            self._one_tile("streamfunction")
+            self._check_stream()
+            self.tiles[0].tileTransform_()
+            return self.tiles[0].invert(rhs, alpha, into, var)
         return self._invert_wind("vorticity", u, v, alpha, into, var)
 
     def velocity_potential(self, u=None, v=None, alpha=0.0, into=None, var=1):
@@ -598,7 +605,32 @@ class ModelRun:
         if self.num_tiles > 1:
             raise ValueError("antiderivative: one-tile patches only (num_tiles = %d)" % self.num_tiles)
         self._check_stream()
+        if isinstance(var, (tuple, list)):          # a field program of `physical`, projected first (Grid.antiderivative)
+            self.tiles[0].tileTransform_()
         return self.tiles[0].antiderivative(var, axis, origin, weight_r, into, var_dst)
+
+    def project(self, outputs, names=None, source="physical", bcs=None, transform=False):
+        """Derived fields as spectral variables (Grid.project): every output - a list of (coef, r_power, [(var, slot), ...]) terms; a
+        list of them, or a dict name -> terms such as field_programs(model) gives - becomes one variable of a companion Grid, which
+        is returned: evaluate, harmonics, spectrum, vortex_harmonics, invert, antiderivative and refine_extremum then apply to the
+        vorticity, a flux or the kinetic energy as to any variable.  The companion is made on first use and kept per (names,
+        conditions); bcs are companion_grid's conditions (default: R0 everywhere).  source="physical" runs tileTransform! on the tile
+        first; source="state" reads var_np1.  transform=True also runs the companion's tileTransform!, so that its `physical` holds
+        the derived fields and their derivatives at the gridpoints.  One-tile patches."""
+        self._one_tile("project")
+        if isinstance(outputs, dict):
+            names, outputs = list(outputs) if names is None else list(names), list(outputs.values())
+        names = ["f%d" % (o + 1) for o in range(len(outputs))] if names is None else list(names)
+        if len(names) != len(outputs):
+            raise ValueError("project: %d names for %d outputs" % (len(names), len(outputs)))
+        self._check_stream()
+        tile = self.tiles[0]
+        if source == "physical":
+            tile.tileTransform_()
+        into = tile.project(program_of_outputs(outputs), tile.project_companion(names, **(bcs or {})), source)
+        if transform:
+            into.tileTransform_()
+        return into
 
     def column_integral(self, var):
         """int_{zmin}^{zmax} f dz of variable `var` in every column of the grid: (points [columns, n_coord - 1] - r[, lambda] of the

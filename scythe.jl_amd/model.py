@@ -414,7 +414,12 @@ class Grid:
         vorticity v_r + v / r - u_l / r resp. the divergence u_r + u / r + v_l / r of the wind (u, v) (RL / RLZ grids).
         into=None makes a one-variable companion (companion_grid: psi = 0 at the outer edge, regular at the centre, the vertical
         conditions of the first source variable) on first use and keeps it; into=self writes a spare variable of this Grid.
+        rhs may also be a field program - a list of (coef, r_power, [(var, slot), ...]) terms read from `physical` as it stands, the
+        forcing of a balance or omega equation - which is projected first (project).
         The boundary conditions of psi are those of the destination variable.  One-tile patches only."""
+        if isinstance(rhs, (tuple, list)) and rhs and not isinstance(rhs[0], str):
+            # a field program as the forcing: projected into a one-variable companion (project), which is then the ("field", 1) source
+            return self.project_companion(["f"]).project_from(self, [(0,) + tuple(t)[-3:] for t in rhs]).invert(("field", 1), alpha, into, var)
         if not isinstance(rhs, (tuple, list)) or not rhs or rhs[0] not in L.ELL_KIND or len(rhs) != (2 if rhs[0] == "field" else 3):
             raise ValueError("rhs must be ('field', f), ('vorticity', u, v) or ('divergence', u, v)")
         src = [self._parcel_var(v) for v in rhs[1:]]
@@ -441,9 +446,14 @@ class Grid:
         element of a vortex: circulation, enclosed mass).  axis="z": F(z) = int_{zmin}^{z} f dz' or int_{z}^{zmax} f dz'.
         dst=None makes a one-variable companion on first use and keeps it, one per set of boundary conditions: the source's own
         vertical and radial conditions carried over, except that along the axis of integration the result is left free (R0) - an
-        integral from xmin does not vanish at xmax.  dst=self writes a spare variable of this Grid.  One-tile patches only."""
+        integral from xmin does not vanish at xmax.  dst=self writes a spare variable of this Grid.  `var` may also be a field
+        program, a list of (coef, r_power, [(var, slot), ...]) terms read from `physical` as it stands (w from the divergence, the mass
+        streamfunction from rho u), which is projected first (project).  One-tile patches only."""
         if axis not in L.INT_AXIS or origin not in L.INT_ORIGIN:
             raise ValueError("axis must be 'r' or 'z' and origin 'low' or 'high'")
+        if isinstance(var, (tuple, list)):
+            # a field program (terms as for invert's rhs): projected into a one-variable companion, which is then the source
+            return self.project_companion(["f"]).project_from(self, [(0,) + tuple(t)[-3:] for t in var]).antiderivative(1, axis, origin, weight_r, dst, var_dst)
         src = self._parcel_var(var)
         if dst is None:
             gp = self.patch_params
@@ -463,6 +473,36 @@ class Grid:
         vd = dst.patch_params.vars[var_dst] if isinstance(var_dst, str) else int(var_dst)
         L.check(self._lib.sx_antiderivative(self._h, src, L.INT_AXIS[axis], L.INT_ORIGIN[origin], int(bool(weight_r)), dst._h, vd))
         return dst
+
+    # -- field programs as variables (sx_project)
+    def project(self, terms, into, source="physical", var_dst=None):
+        """Evaluate a field program at this tile's gridpoints on the device and make its outputs the variables of the companion
+        Grid `into` (sx_project): output o becomes variable var_dst[o] (names or 1-based indices of `into`; default 1, 2, ...), as
+        var_np1 and, through into's own forward transform and banded solve, as B and A coefficients.  terms, source: as for reduce
+        (the same programs, packed by pack_reduce_program against THIS grid).  `into` must have as many variables as the program has
+        outputs, this grid's geometry, extent, cells, ring table and levels (companion_grid(..., names=[...])), and no equation set;
+        its `physical` is stale until into.tileTransform_().  Nothing of this Grid changes.  Returns `into`.  One-tile patches only."""
+        coef, packed, n_out = pack_reduce_program(self.patch_params, terms)
+        if source not in L.REDUCE_SOURCE:
+            raise ValueError("source must be 'physical' or 'state'")
+        vd = _project_var_dst(into.patch_params, n_out, var_dst)
+        L.check(self._lib.sx_project(self._h, L.REDUCE_SOURCE[source], len(coef), coef.ctypes.data_as(L.P_D), packed.ctypes.data_as(L.P_I32),
+                                     n_out, into._h, vd.ctypes.data_as(L.P_I32) if len(vd) else None))
+        return into
+
+    def project_from(self, src, terms, source="physical", var_dst=None):
+        """src.project(terms, self, ...): reads well where the companion is made in the same expression"""
+        return src.project(terms, self, source, var_dst)
+
+    def project_companion(self, names, **bcs):
+        """The companion of this Grid with the variables `names` (companion_grid: every condition R0 unless `bcs` says otherwise -
+        nothing is known of a derived field at the edges), made on first use and kept per (names, conditions)"""
+        bcs = {**dict(bcl="R0", bcl_k0="R0", bcr="R0", bcb="R0", bct="R0"), **bcs}
+        key = ("project", tuple(names), repr(sorted((k, sorted(v.items()) if isinstance(v, dict) else v) for k, v in bcs.items())))
+        cache = self.__dict__.setdefault("_companions", {})
+        if key not in cache:
+            cache[key] = companion_grid(self.patch_params, names=list(names), **bcs)
+        return cache[key]
 
     def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
         """The azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: complex128 ndarray indexed
@@ -905,14 +945,28 @@ def createGrid(gp: GridParameters, model: Optional[ModelParameters] = None):
     return Grid(gp, model)
 
 
-def companion_grid(gp: GridParameters, bcl="R1T0", bcl_k0="R1T1", bcr="R1T0", bcb="R0", bct="R0", name="psi"):
+def companion_grid(gp: GridParameters, bcl="R1T0", bcl_k0="R1T1", bcr="R1T0", bcb="R0", bct="R0", name="psi", names=None):
     """A one-variable Grid (no equation set) of the same geometry as the patch `gp`, to receive the solution of Grid.invert.
     The defaults pose the streamfunction / velocity potential of a vortex: zero at the outer edge (bcr), the wavenumbers k >= 1
-    zero at the centre (bcl), the azimuthal mean with zero slope there (bcl_k0).  bcb / bct must be those of the source variables."""
-    one = GridParameters(geometry=gp.geometry, xmin=gp.xmin, xmax=gp.xmax, num_cells=gp.num_cells, l_q=gp.l_q, BCL={name: bcl},
-                         BCR={name: bcr}, BCL_k0={name: bcl_k0}, zmin=gp.zmin, zmax=gp.zmax, zDim=gp.zDim, b_zDim=gp.b_zDim,
-                         BCB={name: bcb}, BCT={name: bct}, vars={name: 1}, ring_uniform_L=gp.ring_uniform_L)
-    return Grid(one, None)
+    zero at the centre (bcl), the azimuthal mean with zero slope there (bcl_k0).  bcb / bct must be those of the source variables.
+    names=[...] makes a companion with these variables instead (Grid.project writes all of them): every condition is then one name
+    for all variables or a dict by variable (a variable it leaves out: R0)."""
+    return Grid(companion_params(gp, bcl, bcl_k0, bcr, bcb, bct, name, names), None)
+
+
+def companion_params(gp: GridParameters, bcl="R1T0", bcl_k0="R1T1", bcr="R1T0", bcb="R0", bct="R0", name="psi", names=None):
+    """The GridParameters companion_grid creates its Grid from"""
+    if names is not None:
+        names = list(names)
+        if not names or len(set(names)) != len(names):
+            raise ValueError("names must be a non-empty list of distinct variable names")
+        of = lambda c: {n: (c.get(n, "R0") if isinstance(c, dict) else c) for n in names}
+        return GridParameters(geometry=gp.geometry, xmin=gp.xmin, xmax=gp.xmax, num_cells=gp.num_cells, l_q=gp.l_q, BCL=of(bcl), BCR=of(bcr),
+                              BCL_k0=of(bcl_k0), zmin=gp.zmin, zmax=gp.zmax, zDim=gp.zDim, b_zDim=gp.b_zDim, BCB=of(bcb), BCT=of(bct),
+                              vars={n: i + 1 for i, n in enumerate(names)}, ring_uniform_L=gp.ring_uniform_L)
+    return GridParameters(geometry=gp.geometry, xmin=gp.xmin, xmax=gp.xmax, num_cells=gp.num_cells, l_q=gp.l_q, BCL={name: bcl},
+                          BCR={name: bcr}, BCL_k0={name: bcl_k0}, zmin=gp.zmin, zmax=gp.zmax, zDim=gp.zDim, b_zDim=gp.b_zDim,
+                          BCB={name: bcb}, BCT={name: bct}, vars={name: 1}, ring_uniform_L=gp.ring_uniform_L)
 
 
 def elliptic_check(patch: GridParameters, var, k, alpha, g):
@@ -984,7 +1038,7 @@ class Program(list):
 def pack_reduce_program(patch: GridParameters, terms):
     """terms -> (coef float64 [n], terms int32 [n, 11] = out, r_power, n_factors, var[4], slot[4] as sx_reduce reads them, n_out);
     variable and slot names are resolved against the patch, everything else is left to the library to refuse."""
-    slots = L.SLOTS[patch.geometry]
+    slots = L.SLOTS[patch.geometry] if patch is not None else ()      # patch=None: variables and slots by index only (project_point)
     coef = np.zeros(len(terms))
     packed = np.zeros((len(terms), 11), dtype=np.int32)
     for i, (out, c, p, factors) in enumerate(terms):
@@ -993,10 +1047,10 @@ def pack_reduce_program(patch: GridParameters, terms):
         coef[i] = float(c)
         packed[i, :3] = int(out), int(p), len(factors)
         for f, (var, slot) in enumerate(factors):
-            if isinstance(var, str) and var not in patch.vars:
+            if isinstance(var, str) and (patch is None or var not in patch.vars):
                 raise ValueError("term %d: unknown variable %r" % (i, var))
             if isinstance(slot, str) and slot not in slots:
-                raise ValueError("term %d: an %s grid has no slot %r" % (i, patch.geometry, slot))
+                raise ValueError("term %d: an %s grid has no slot %r" % (i, patch.geometry if patch is not None else "unnamed", slot))
             packed[i, 3 + f] = patch.vars[var] if isinstance(var, str) else int(var)
             packed[i, 7 + f] = slots.index(slot) if isinstance(slot, str) else int(slot)
     n_out = int(packed[:, 0].max()) + 1 if len(terms) else 0
@@ -1025,6 +1079,49 @@ def reduce_planes(patch: GridParameters, terms, source="physical", tile_cell0=0,
     L.check(L.load().sx_reduce_planes(C.byref(d), L.REDUCE_SOURCE[source], len(coef), packed.ctypes.data_as(L.P_I32), n_out,
                                       planes.ctypes.data_as(L.P_I32), C.byref(n)))
     return planes[:n.value].copy()
+
+
+# ----------------------------------------------------------------------------- field programs as variables (sx_project)
+def _project_var_dst(dst_patch: GridParameters, n_out, var_dst):
+    """var_dst as sx_project reads it: int32 [n_out], 1-based; names resolved against the destination, default 1 .. n_out"""
+    if var_dst is None:
+        return np.arange(1, n_out + 1, dtype=np.int32)
+    return np.array([dst_patch.vars[v] if isinstance(v, str) else int(v) for v in var_dst], dtype=np.int32)
+
+
+def program_of_outputs(outputs):
+    """A list of outputs, each a list of (coef, r_power, [(var, slot), ...]) terms, as the one term list Grid.project and Grid.reduce
+    read: output o's terms get out = o (a term that already carries an `out` in front loses it)"""
+    return [(o,) + tuple(t)[-3:] for o, terms in enumerate(outputs) for t in terms]
+
+
+def project_check(patch: GridParameters, dst_patch: GridParameters, terms, source="physical", var_dst=None):
+    """What Grid.project refuses of the two patches and the program, on the host (sx_project_check: no handle, no device); raises
+    ScytheHipError with the library's message, returns None when the call would be accepted.  A descriptor carries no equation set
+    and no handle: those two refusals are the call's own."""
+    ds, k1 = grid_desc(patch)
+    dd, k2 = grid_desc(dst_patch)
+    coef, packed, n_out = pack_reduce_program(patch, terms)
+    vd = _project_var_dst(dst_patch, n_out, var_dst)
+    L.check(L.load().sx_project_check(C.byref(ds), C.byref(dd), L.REDUCE_SOURCE[source], len(coef), packed.ctypes.data_as(L.P_I32), n_out,
+                                      vd.ctypes.data_as(L.P_I32) if len(vd) else None))
+
+
+def project_point(terms, planes, values, r):
+    """The outputs of a program at ONE point, on the host with k_project's arithmetic (sx_project_point): float64 [n_out].  terms: as
+    for reduce with variables and slots by index, or a packed (coef, packed, n_out); planes [(var, slot), ...] lists every plane the
+    program names, values [len(planes)] their values at the point, r its radius."""
+    coef, packed, n_out = terms if isinstance(terms, tuple) and len(terms) == 3 and hasattr(terms[1], "shape") else pack_reduce_program(None, terms)
+    coef = np.ascontiguousarray(coef, dtype=np.float64)
+    packed = np.ascontiguousarray(packed, dtype=np.int32)
+    pl = np.ascontiguousarray(np.asarray(planes, dtype=np.int32).reshape(-1, 2))
+    val = np.ascontiguousarray(values, dtype=np.float64)
+    if val.shape != (len(pl),):
+        raise ValueError("values must have one entry per plane")
+    out = np.zeros(int(n_out))
+    L.check(L.load().sx_project_point(len(coef), coef.ctypes.data_as(L.P_D), packed.ctypes.data_as(L.P_I32), int(n_out), len(pl),
+                                      pl.ctypes.data_as(L.P_I32), val.ctypes.data_as(L.P_D), float(r), out.ctypes.data_as(L.P_D)))
+    return out
 
 
 # ----------------------------------------------------------------------------- extrema and their refinement (sx_extrema, sx_extremum_refine)
@@ -1276,6 +1373,12 @@ def spectrum_check(patch: GridParameters, pairs, tile_cell0=0, tile_num_cells=No
     L.check(L.load().sx_spectrum_check(C.byref(d), len(packed), packed.ctypes.data_as(L.P_I32)))
 
 
+def _speed2(wind, coef):
+    """coef (u^2 [+ v^2]) as terms (coef, r_power, factors) of one output: the wind's square, stated once for invariants and
+    field_programs"""
+    return [(coef, 0, [(w, ""), (w, "")]) for w in wind]
+
+
 def invariants(model: ModelParameters):
     """The conserved (or budget) integrals of an equation set as a Program for ModelRun.integrate:
     LinearShallowWater1D  mass = int h, energy = 1/2 int (g h^2 + H u^2);  LinearShallowWaterRL  the same with H (u^2 + v^2);
@@ -1284,14 +1387,34 @@ def invariants(model: ModelParameters):
     pp = {(k if isinstance(k, str) else str(k)).lstrip(":"): v for k, v in model.physical_params.items()}
     if eq in ("LinearShallowWater1D", "LinearShallowWaterRL"):
         g, H = float(pp["g"]), float(pp["H"])
-        terms = [(0, 1.0, 0, [("h", "")]), (1, 0.5 * g, 0, [("h", ""), ("h", "")]), (1, 0.5 * H, 0, [("u", ""), ("u", "")])]
-        if eq == "LinearShallowWaterRL":
-            terms.append((1, 0.5 * H, 0, [("v", ""), ("v", "")]))
+        wind = ("u", "v") if eq == "LinearShallowWaterRL" else ("u",)
+        terms = [(0, 1.0, 0, [("h", "")]), (1, 0.5 * g, 0, [("h", ""), ("h", "")])] + [(1,) + t for t in _speed2(wind, 0.5 * H)]
         return Program(terms, ["mass", "energy"])
     if eq.startswith("LinearAdvection"):
         q = model.grid_params.var_names()[0]
         return Program([(0, 1.0, 0, [(q, "")]), (1, 1.0, 0, [(q, ""), (q, "")])], ["integral", "integral_of_square"])
     raise ValueError("equation set %r has no invariants defined" % eq)
+
+
+def field_programs(model: ModelParameters, u="u", v="v"):
+    """The derived fields of the wind (u, v) as outputs for ModelRun.project (and, through program_of_outputs, for reduce, extrema,
+    distribution, statistics): a dict name -> [(coef, r_power, [(var, slot), ...]), ...] with
+        vorticity       v_r + v / r - u_l / r     divergence      u_r + u / r + v_l / r      (RL / RLZ; on R / RZ: v_r and u_r)
+        kinetic_energy  (u^2 + v^2) / 2           speed2          u^2 + v^2
+    from the patch's geometry.  A grid without `v` (the 1-D sets) gets the u parts and no vorticity."""
+    gp = model.grid_params
+    if u not in gp.vars:
+        raise ValueError("field_programs: the grid has no variable %r" % (u,))
+    wind = (u, v) if v in gp.vars else (u,)
+    polar = "L" in gp.geometry
+    out = {"divergence": [(1.0, 0, [(u, "r")])] + ([(1.0, -1, [(u, "")])] if polar else [])}
+    if len(wind) == 2:
+        out["vorticity"] = [(1.0, 0, [(v, "r")])] + ([(1.0, -1, [(v, "")]), (-1.0, -1, [(u, "l")])] if polar else [])
+        if polar:
+            out["divergence"].append((1.0, -1, [(v, "l")]))
+    out["kinetic_energy"] = _speed2(wind, 0.5)
+    out["speed2"] = _speed2(wind, 1.0)
+    return out
 
 
 def regular_gridpoints(gp: GridParameters, nr, nl=None, nz=None):
