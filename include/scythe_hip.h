@@ -935,6 +935,65 @@ int sx_project_check(const sx_grid_desc *src, const sx_grid_desc *dst, int32_t s
 int sx_project_point(int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out, int32_t n_planes,
                      const int32_t *planes /*[n_planes][2]*/, const double *val /*[n_planes]*/, double r, double *out /*[n_out]*/);
 
+/* --- onto another grid: resize, re-level, re-centre -------------------------------------------------------------------
+ * The restart-at-new-resolution and vortex-following primitive: sx_regrid lays the state of src down on the grid of dst.  It adds no
+ * numerics of its own: the values are the continuous function sx_evaluate defines, the coefficients the projection
+ * sx_spectral_transform + sx_spline_transform apply.
+ *
+ * Value.  Variable v (0-based) of dst receives, at every gridpoint of dst, the value slot of src's variable var_src[v] (1-based; the
+ * same source variable may be named more than once): the function sx_evaluate returns with SX_EVAL_ALL_K - every wavenumber of the
+ * patch at every radius -, summed on the device from the A coefficients src holds now (a deferred diagnostic variable is brought up to
+ * date first).  It is written as dst's var_np1 plane, and dst's own forward chain - what sx_spectral_transform + sx_spline_transform
+ * launch - then runs for every variable of dst, on dst's stream behind an event (as in sx_project).  The call returns after completion.
+ *
+ * What changes.  In dst: var_np1, B and A are overwritten; `physical` and the tendency history are stale - run sx_tile_transform
+ * before reading `physical`, and the next sx_advance / sx_step of dst must be t = 1 (an Euler step: the Adams-Bashforth history belongs
+ * to another grid).  dst may carry any equation set.  src stays bitwise as it is: state, history, `physical`, parcels, statistics.
+ *
+ * Geometry.  R -> R, RZ -> RZ, RL -> RL and RLZ -> RLZ only.  xmin, xmax, num_cells, the ring table, the boundary conditions and l_q of
+ * the two grids are independent.  centre = (x0, y0) is the position of dst's axis in src's Cartesian frame (x = r cos lambda,
+ * y = r sin lambda); it is allowed on RL / RLZ only, and NULL means (0, 0).  A column (r, lambda) of dst lies in src at
+ *     x = x0 + r cos lambda,  y = y0 + r sin lambda,  r_s = hypot(x, y),  lambda_s = atan2(y, x)
+ * in plain fp64, every operation rounded on its own; with centre NULL or exactly (0, 0) the map is the identity on (r, lambda), bit for
+ * bit.  The map is one function compiled for host and device; sx_regrid_columns runs it on the host and returns the source coordinates
+ * of every column of dst in dst's gridpoint order (a column is the zDim consecutive gridpoints of one (r, lambda)):
+ * columns[n_cols, n_h] column-major, n_h = 1 (r_s; R / RZ) or 2 (r_s, lambda_s; RL / RLZ) - n_coord - 1 on a grid with a vertical -,
+ * inside[n_cols], *n_cols the count; any of the three may be NULL (NULL columns and inside: the count alone).  sx_regrid sums at these
+ * same doubles (a lambda_s beyond 2 pi in magnitude - the identity map of a native ring's last points - is reduced into (-pi, pi] in
+ * extended precision before the kernel reads it, as sx_isosurface reduces it).
+ *
+ * Vertical.  dst's [zmin, zmax] must lie within src's; zDim, b_zDim, the level set and the vertical boundary-condition classes may all
+ * differ.  The vertical row is sx_evaluate's: the DCT-I series of CA e_zm of the SOURCE variable's (bcb, bct) class at dst's levels,
+ * formed in extended precision and rounded to fp64 once (the matrix E [zDim_dst][b_zDim_src], cached per level set of dst).
+ *
+ * Outside the source.  A column of dst is outside when its r_s lies outside src's [xmin, xmax] (the ends count as inside); inside[c] = 0
+ * marks it.  outside = SX_REGRID_REFUSE fails the call before anything is written when there is such a column; SX_REGRID_FILL writes
+ * fill[v] at every level of such a column and counts the columns in *n_outside (may be NULL; 0 with SX_REGRID_REFUSE).  fill [dst n_vars]
+ * must then be non-null and finite; with SX_REGRID_REFUSE it is not read.
+ *
+ * Two stages.  Stage 1: the per-column series C[zm] of every source variable named - sx_isosurface's profiles of kind
+ * (0, 0), by its kernels k_column_profiles / k_column_profiles_rz, the inside columns sorted by source cell and batched as there.  Stage
+ * 2, k_regrid_levels: var_np1[z, column, v] = sum_zm E_v[z][zm] C_v[zm][column] on the f64 matrix cores (RLZ; 16 columns x 16 levels per
+ * product, K = zm ascending in one fixed chain, zero-padded to 16 / 4) or one lane per output (R, RL, RZ: the fma chain over zm from
+ * +0.0; without a vertical b_zDim = 1, E = (1) and the stage is a copy).  Which of the two runs follows from the geometry alone.  No
+ * atomics, nothing summed across columns.  Guarantees: two calls agree bitwise; a column's values do not depend on the other columns of
+ * dst; one variable's result does not depend on what the other entries of var_src are.
+ *
+ * Refused, with a message and before any write: null handles; dst == src; either handle not a one-tile patch; geometries that differ; a
+ * centre on R / RZ; a non-finite centre; a null var_src or an entry outside 1 .. src n_vars; an unknown `outside`; more than 2^20 columns
+ * of dst; an invalid vertical grid (4 <= zDim <= 256, b_zDim <= zDim, zmax > zmin, of both) or a dst extent beyond src's; the LDS limit
+ * of k_column_profiles (32 (kDim + 1) + 2304 <= 8192 doubles, src's kDim); with SX_REGRID_REFUSE a column outside; with SX_REGRID_FILL a
+ * null or non-finite fill.  sx_regrid_check is that validation for two descriptors on the host (all but the null handles, dst == src
+ * and fill); sx_regrid calls the same code.  sx_regrid_check and sx_regrid_columns are pure host helpers (no handle, no device).
+ * sx_kernel_bytes(src, "k_regrid_levels") gives the last call's profiles in (b_zDim x inside columns x 8 per variable of dst) + E + the
+ * column table + dst's var_np1 planes out; "k_column_profiles" is not updated by sx_regrid. */
+enum { SX_REGRID_REFUSE = 0, SX_REGRID_FILL = 1 };
+int sx_regrid(sx_handle *src, sx_handle *dst, const double *centre /*[2] or NULL*/, const int32_t *var_src /*[dst n_vars], 1-based*/,
+              int32_t outside, const double *fill /*[dst n_vars] or NULL*/, int64_t *n_outside /*may be NULL*/);
+int sx_regrid_check(const sx_grid_desc *src, const sx_grid_desc *dst, const double *centre, const int32_t *var_src, int32_t outside);
+int sx_regrid_columns(const sx_grid_desc *src, const sx_grid_desc *dst, const double *centre, double *columns /*[n_cols, n_h]*/,
+                      int32_t *inside /*[n_cols]*/, int64_t *n_cols);
+
 /* --- tile <-> patch exchange on the device (src/semiimplicit.jl:320-329, 272-285) ---------------------------------- */
 /* The tile's B coefficients live in a [tile_b_rDim][n_cols] row-major device array (row = radial node).
  * Rows [0, tile_num_cells) are owned (patchIndexMap), rows [tile_num_cells, +3) are the halo sent to the next

@@ -20,6 +20,7 @@ REDUCE_KIND = {"domain": 0, "azimuth": 1}        # SX_REDUCE_DOMAIN / SX_REDUCE_
 REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUCE_STATE
 DIST_KIND = {"domain": 0, "level": 1}              # SX_DIST_DOMAIN / SX_DIST_LEVEL
 VORTEX_SCALAR, VORTEX_WIND = 0, 1                # SX_VORTEX_*
+REGRID_OUTSIDE = {"refuse": 0, "fill": 1}        # SX_REGRID_REFUSE / SX_REGRID_FILL
 STAT_OP = {"sum": 0, "max": 1, "min": 2, "duration": 3}     # SX_STAT_SUM / SX_STAT_MAX / SX_STAT_MIN / SX_STAT_DURATION
 EXT_KIND = {"domain": 0, "azimuth": 1}           # SX_EXT_DOMAIN / SX_EXT_AZIMUTH
 EXT_WANT = {"min": -1, "any": 0, "max": 1}       # SX_EXT_MIN / SX_EXT_ANY / SX_EXT_MAX
@@ -167,6 +168,9 @@ SYMBOLS = {
     "sx_project": (C.c_int, [_H, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, _H, P_I32]),
     "sx_project_check": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32]),
     "sx_project_point": (C.c_int, [C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_I32, P_D, C.c_double, P_D]),
+    "sx_regrid": (C.c_int, [_H, _H, P_D, P_I32, C.c_int32, P_D, P_I64]),
+    "sx_regrid_check": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), P_D, P_I32, C.c_int32]),
+    "sx_regrid_columns": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), P_D, P_D, P_I32, P_I64]),
 }
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)

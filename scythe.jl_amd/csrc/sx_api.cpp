@@ -1502,6 +1502,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_vortex_rings") b = diag_bytes(DIAG_VORTEX);            // the last call's live circles x n_az x distinct source variables x 4 rows x b_zDim x (2 kDim + 1) of A
     else if (k == "k_stats") b = diag_bytes(DIAG_STATS);                    // the last sample's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 32
     else if (k == "k_project") b = diag_bytes(DIAG_PROJECT);                // the last call's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 8
+    else if (k == "k_regrid_levels") b = diag_bytes(DIAG_REGRID);              // the last call's profiles in + E + the column table + the destination's var_np1 planes out
     *bytes = b;
     return 0;
 }

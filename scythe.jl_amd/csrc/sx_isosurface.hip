@@ -17,6 +17,7 @@
 // once, then runs scan_crossings (sx_point.hpp: the loop k_crossings runs) over the stations (the zDim levels, bottom to top), the
 // program evaluated from the series with column_series - the function sx_column_series runs on the host: the crossings of a level
 // are numbered upward and every crossing is refined by its own lane with bracket_step.  No atomics, nothing summed across columns.
+#include "sx_colprof.hpp"
 #include "sx_point.hpp"
 #include "sx_redprog.hpp"
 #include <algorithm>
@@ -27,11 +28,6 @@
 namespace sx {
 
 constexpr int ISO_CARRY = 8;
-constexpr int ISO_KINDS = 5;              // profile kinds of a variable, (sr, sl) = (0, 0) (1, 0) (2, 0) (0, 1) (0, 2)
-constexpr int ISO_BATCH = 16;             // columns of one radial cell per matrix product
-constexpr int ISO_KC = 32;                // blocks of A per staged tile: 32 K steps
-constexpr int ISO_AS = 36;                // row stride of the staged tile in doubles
-constexpr size_t ISO_LDS_MAX = 64 * 1024;
 
 typedef double iso_d4 __attribute__((ext_vector_type(4)));
 
@@ -52,28 +48,7 @@ __host__ __device__ inline double column_series(int nz, double zmin, double zmax
     return s;
 }
 
-// ---- stage 1: the column profiles ----------------------------------------------------------------------------------------------------
-struct IsoVar {
-    int var;                              // 0-based variable
-    int prof[ISO_KINDS];                  // profile number of each kind, -1 = not named
-};
-struct IsoBatch { int first, n, cell, pad; };     // sorted positions [first, first + n) share the radial cell `cell`
-struct ColProfArgs {
-    const double *A;                      // [b_rDim][C]
-    const double *cols;                   // [n_coord - 1][n_cols]: r[, lambda]; |lambda| <= 2 pi
-    const int *order;                     // sorted position -> the caller's column
-    const IsoBatch *batch;
-    double *P;                            // [n_cols][nprof][Zb], the caller's order
-    int64_t C;
-    int n_cols, nprof, Zb, K2, kDim, cell_lo, cell_hi;
-    double xmin, DX;
-    IsoVar v[RED_PLANES];
-    uint8_t pvar[RED_PLANES], psr[RED_PLANES];     // profile -> 0-based variable, radial order (k_column_profiles_rz)
-};
-
-// doubles of LDS: cs [kDim + 1][16] double2 | sA [64][ISO_AS]
-static size_t colprof_lds(int kDim) { return sizeof(double) * (32 * (size_t)(kDim + 1) + 64 * ISO_AS); }
-
+// ---- stage 1: the column profiles (the argument record, the batches and the LDS size: sx_colprof.hpp) ---------------------------------
 // grid (ceil(b_zDim / 16), batches, variables named)
 __global__ __launch_bounds__(64) void k_column_profiles(ColProfArgs a) {
     extern __shared__ double lds[];
@@ -240,6 +215,40 @@ __global__ __launch_bounds__(64) void k_isosurface(IsoArgs a) {
         });
 }
 
+// ---- what sx_regrid shares (sx_colprof.hpp) ------------------------------------------------------------------------------------------
+void colprof_batches(const sx_handle *h, const double *r, int64_t n, std::vector<int> &idx, std::vector<IsoBatch> &batches) {
+    const int cell_lo = h->cell0, cell_hi = h->cell0 + h->ncells - 1;
+    std::vector<int> cell(n);
+    idx.resize(n);
+    batches.clear();
+    for (int64_t i = 0; i < n; i++) cell[i] = point_cell(h->xmin, h->DX, cell_lo, cell_hi, r[i]);
+    std::iota(idx.begin(), idx.end(), 0);
+    if (!h->has_l) return;
+    std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return cell[x] < cell[y]; });
+    for (int i = 0; i < (int)n;) {
+        int j = i;
+        while (j < (int)n && j - i < ISO_BATCH && cell[idx[j]] == cell[idx[i]]) j++;
+        batches.push_back(IsoBatch{i, j - i, cell[idx[i]], 0});
+        i = j;
+    }
+}
+
+void colprof_grid_args(const sx_handle *h, ColProfArgs &pa) {
+    pa.A = h->d_A; pa.C = h->C; pa.Zb = h->Zb; pa.K2 = h->K2; pa.kDim = h->kDim;
+    pa.cell_lo = h->cell0; pa.cell_hi = h->cell0 + h->ncells - 1; pa.xmin = h->xmin; pa.DX = h->DX;
+}
+
+void launch_column_profiles(sx_handle *h, const ColProfArgs &pa, int n_batches, int nv) {
+    timer_begin(h, timer_id(h, "k_column_profiles"));
+    if (h->has_l)
+        hipLaunchKernelGGL(k_column_profiles, dim3((unsigned)((pa.Zb + 15) / 16), (unsigned)n_batches, (unsigned)nv), dim3(64), colprof_lds(h->kDim),
+                           h->stream, pa);
+    else
+        hipLaunchKernelGGL(k_column_profiles_rz, grid1((int64_t)pa.n_cols * pa.nprof * pa.Zb, 256), dim3(256), 0, h->stream, pa);
+    HIPCHK(hipGetLastError());
+    timer_end(h);
+}
+
 // ---- host -----------------------------------------------------------------------------------------------------------------------
 struct IsoState : DiagState {            // last_bytes: k_column_profiles'
     double scan_bytes = 0;              // k_isosurface's
@@ -395,20 +404,9 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     if (h->has_l)                                  // a lambda outside [-2 pi, 2 pi] into (-pi, pi]
         for (int64_t i = 0; i < n_cols; i++)
             if (std::fabs(columns[n_cols + i]) > 6.283185307179586) c0[n_cols + i] = wrap_lambda(columns[n_cols + i]);
-    const int cell_lo = h->cell0, cell_hi = h->cell0 + h->ncells - 1;
-    std::vector<int> cell(n_cols), idx(n_cols);
-    for (int64_t i = 0; i < n_cols; i++) cell[i] = point_cell(h->xmin, h->DX, cell_lo, cell_hi, columns[i]);
-    std::iota(idx.begin(), idx.end(), 0);
+    std::vector<int> idx;
     std::vector<IsoBatch> batches;
-    if (h->has_l) {
-        std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return cell[x] < cell[y]; });
-        for (int i = 0; i < (int)n_cols;) {
-            int j = i;
-            while (j < (int)n_cols && j - i < ISO_BATCH && cell[idx[j]] == cell[idx[i]]) j++;
-            batches.push_back(IsoBatch{i, j - i, cell[idx[i]], 0});
-            i = j;
-        }
-    }
+    colprof_batches(h, columns, n_cols, idx, batches);
     const size_t n_P = (size_t)std::max(nprof, 1) * Zb * n_cols, n_hgt = (size_t)max_cross * n_levels * n_cols;
     const size_t n_car = n_hgt * n_carry, n_val = (size_t)nz * n_cols, n_int = n_hgt + (size_t)n_levels * n_cols + n_cols;
     const size_t n_idx = (size_t)n_cols + 4 * batches.size();
@@ -423,9 +421,9 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
 
     ColProfArgs pa;
     std::memset(&pa, 0, sizeof(pa));
-    pa.A = h->d_A; pa.cols = st->d_cols; pa.order = st->d_idx; pa.batch = reinterpret_cast<const IsoBatch *>(st->d_idx + n_cols); pa.P = st->d_P;
-    pa.C = h->C; pa.n_cols = (int)n_cols; pa.nprof = nprof; pa.Zb = Zb; pa.K2 = h->K2; pa.kDim = h->kDim; pa.cell_lo = cell_lo; pa.cell_hi = cell_hi;
-    pa.xmin = h->xmin; pa.DX = h->DX;
+    colprof_grid_args(h, pa);
+    pa.cols = st->d_cols; pa.order = st->d_idx; pa.batch = reinterpret_cast<const IsoBatch *>(st->d_idx + n_cols); pa.P = st->d_P;
+    pa.n_cols = (int)n_cols; pa.nprof = nprof;
     std::memcpy(pa.v, pl.v, sizeof(pa.v));
     std::memcpy(pa.pvar, pl.pvar, sizeof(pa.pvar));
     std::memcpy(pa.psr, pl.psr, sizeof(pa.psr));
@@ -434,16 +432,7 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     st->last_bytes = nprof == 0 ? 0.0
                                 : 8.0 * (4.0 * Zb * live * (h->has_l ? (double)batches.size() * pl.nv : (double)n_cols * nprof) + (double)ncc * n_cols +
                                          (double)Zb * nprof * n_cols);
-    if (nprof > 0) {
-        timer_begin(h, timer_id(h, "k_column_profiles"));
-        if (h->has_l)
-            hipLaunchKernelGGL(k_column_profiles, dim3((unsigned)((Zb + 15) / 16), (unsigned)batches.size(), (unsigned)pl.nv), dim3(64), colprof_lds(h->kDim),
-                               h->stream, pa);
-        else
-            hipLaunchKernelGGL(k_column_profiles_rz, grid1((int64_t)n_cols * nprof * Zb, 256), dim3(256), 0, h->stream, pa);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
-    }
+    if (nprof > 0) launch_column_profiles(h, pa, (int)batches.size(), pl.nv);
 
     IsoArgs ia;
     std::memset(&ia, 0, sizeof(ia));

@@ -7,6 +7,7 @@ buffers: halo rows by point-to-point send/recv, owned rows by an in-place all-ga
 torch.distributed (backend "nccl" = RCCL over xGMI on the GPU box, "gloo" in the CPU tests).
 """
 import collections
+import dataclasses
 import os
 import time
 
@@ -371,6 +372,8 @@ class ModelRun:
             else:
                 raise ValueError("exchange must be 'a2a', 'iface' or 'gather'")
         self.t = 0
+        self._ab0 = 0               # the step count at which the Adams-Bashforth start-up began: not 0 only in a run that regrid made
+        self._device = device
         self._ring_axes = None      # azimuthal_mean's (r, z) axes, formed on first use
         self._points = None         # the local tiles' gridpoints [n, n_coord] in tile order (extrema's rows), formed on first use
         self._parcels = False       # set_parcels attached a parcel set: step() moves it
@@ -433,10 +436,10 @@ class ModelRun:
             self.tiles[0].advance_parcels(self.model.ts)
         if self.num_tiles == 1 and self.exchange is None:
             self._check_stream()
-            self.tiles[0].step(self.t)          # sx_step = sx_advance + sx_spline_transform (one hipGraph launch with SX_GRAPH=1)
+            self.tiles[0].step(self.t - self._ab0)          # sx_step = sx_advance + sx_spline_transform (one hipGraph launch with SX_GRAPH=1)
         else:
             for g in self.tiles:
-                g.advance(self.t)
+                g.advance(self.t - self._ab0)
             self._exchange_and_solve()
         if self._stats is not None and self.t % self._stats["every"] == 0:
             # the sample goes on each tile's stream AFTER the step: var_np1 is then the state of time t, and the next step's first
@@ -833,6 +836,47 @@ class ModelRun:
         res = g.refine_extremum(var, start[None, :], want, free)
         return Located(res.pos[0].copy(), float(res.value[0]), int(res.status[0]))
 
+    def regrid(self, gp_new, centre=None, outside="refuse", fill=None):
+        """The run continued on another grid (Grid.regrid): a new ModelRun on `gp_new` with the same model and the same variables by
+        name, its state the continuous state of this run at gp_new's gridpoints - a finer or coarser mesh, other levels, a cropped or
+        extended domain, or with centre=(x0, y0) a grid about another axis (RL / RLZ).  The step count t and with it the time are
+        carried; the Adams-Bashforth start-up is restarted (the next steps are Euler, AB2, AB3: the tendency history belongs to the old
+        grid), and `physical` is refreshed by one tileTransform!.  outside, fill: as for Grid.regrid; the number of columns filled is
+        the new run's n_outside.  Parcels and statistics are not carried: a run with either attached raises ValueError (detach them,
+        or read them out first).  This run is left as it is.  One-tile patches."""
+        src = self._one_tile("regrid")
+        if self._parcels or self._stats is not None:
+            raise ValueError("regrid: attached parcels and statistics are not carried onto another grid (detach them first)")
+        keep_ref = self.model.ref_state if not self.model.ref_state_file else None      # a file's reference state is rebuilt for the new levels
+        new = ModelRun(dataclasses.replace(self.model, grid_params=gp_new, ref_state=keep_ref), num_tiles=1, device=self._device)
+        try:
+            new.n_outside = src.regrid(new.tiles[0], centre, None, outside, fill)
+            new.tiles[0].tileTransform_()
+        except Exception:
+            new.close()
+            raise
+        new.t = new._ab0 = self.t
+        return new
+
+    def recentre(self, centre=None, var=None, want="min", **kw):
+        """regrid onto this run's own GridParameters about `centre` (default: self.locate(var, want) - the vortex centre): the model
+        follows its vortex, and every ring truncation sits about the axis again.  kw: regrid's outside and fill; with outside="fill"
+        and no fill every variable takes its azimuthal mean at this grid's outermost ring (azimuthal_mean of the state, averaged over
+        the levels).  Returns the new ModelRun.  One-tile RL / RLZ patches."""
+        self._one_tile("recentre")
+        if "L" not in self.patch.geometry:
+            raise ValueError("recentre: RL and RLZ grids only")
+        if centre is None:
+            if var is None:
+                raise ValueError("recentre: give a centre, or the variable whose extremum is the centre")
+            pos = self.locate(var, want).pos
+            centre = (pos[0] * np.cos(pos[1]), pos[0] * np.sin(pos[1]))
+        if kw.get("outside") == "fill" and kw.get("fill") is None:
+            names = self.patch.var_names()
+            _, _, mean = self.azimuthal_mean([(o, 1.0, 0, [(n, "")]) for o, n in enumerate(names)], "state")
+            kw["fill"] = mean[-1].mean(axis=0)
+        return self.regrid(self.patch, centre, **kw)
+
     def radius_of_maximum(self, var, level=None, source="state"):
         """The radius of the maximum of variable `var` (the radius of maximum wind for the tangential wind): the azimuth kind's
         maxima over lambda at every ring (Grid.extrema) on `level` (0-based; None: the level that holds the largest), the ring of
@@ -1046,7 +1090,7 @@ class ModelRun:
             for i, g in zip(self.tile_ids, self.tiles):
                 extra["stats%d" % i] = g.get_statistics_state()
             extra["stats_every"], extra["stats_key"] = np.array(self._stats["every"]), np.array(self._stats["key"])
-        np.savez(path, t=self.t, tile_ids=np.array(self.tile_ids), **extra)
+        np.savez(path, t=self.t, ab0=self._ab0, tile_ids=np.array(self.tile_ids), **extra)
 
     def load_checkpoint(self, path):
         with np.load(path) as z:
@@ -1066,6 +1110,7 @@ class ModelRun:
             d = self.tiles[0].describe_statistics()
             self._stats = None if d is None else dict(source=d[0], every=int(z["stats_every"]), key=str(z["stats_key"]))
             self.t = int(z["t"])
+            self._ab0 = int(z["ab0"]) if "ab0" in z.files else 0
 
     def close(self):
         for g in self.tiles:

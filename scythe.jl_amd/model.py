@@ -504,6 +504,27 @@ class Grid:
             cache[key] = companion_grid(self.patch_params, names=list(names), **bcs)
         return cache[key]
 
+    # -- onto another grid (sx_regrid)
+    def regrid(self, dst_grid, centre=None, variables=None, outside="refuse", fill=None):
+        """Lay this tile's state down on the Grid `dst_grid` (sx_regrid): every variable of dst_grid receives, at dst_grid's gridpoints,
+        the continuous function evaluate(..., all_k=True) gives of a variable of this grid, as var_np1 and, through dst_grid's own
+        forward transform and banded solve, as B and A.  variables [dst V]: the source variable of each (names or 1-based indices of
+        THIS grid; default: dst_grid's own names looked up here).  centre=(x0, y0): dst_grid's axis in this grid's Cartesian frame
+        (RL / RLZ only; None: the same axis).  Extent, cells, rings, levels and boundary conditions of the two may differ; dst_grid's
+        [zmin, zmax] must lie within this grid's.  outside="refuse" fails when a column of dst_grid lies outside this grid's
+        [xmin, xmax]; "fill" writes fill[v] (a scalar serves every variable) there.  Returns the number of such columns.
+        dst_grid's `physical` and tendency history are stale: its next step must be t = 1.  Nothing of this Grid changes.  One-tile
+        patches only."""
+        if outside not in L.REGRID_OUTSIDE:
+            raise ValueError("outside must be 'refuse' or 'fill'")
+        vs = _regrid_var_src(self.patch_params, dst_grid.patch_params, variables)
+        c = None if centre is None else np.ascontiguousarray(centre, dtype=np.float64).reshape(2)
+        f = None if fill is None else np.ascontiguousarray(np.broadcast_to(np.asarray(fill, dtype=np.float64), (dst_grid.V,)))
+        n = C.c_int64(0)
+        L.check(self._lib.sx_regrid(self._h, dst_grid._h, None if c is None else c.ctypes.data_as(L.P_D), vs.ctypes.data_as(L.P_I32),
+                                    L.REGRID_OUTSIDE[outside], None if f is None else f.ctypes.data_as(L.P_D), C.byref(n)))
+        return int(n.value)
+
     def harmonics(self, radii, heights=None, all_k=False, slots=("u",)):
         """The azimuthal harmonics c_k(r, z) of the state (sx_harmonics) at every radius x every height: complex128 ndarray indexed
         [ir, iz, k, v, s], k = 0 .. kDim, s over `slots` in the order u, r, rr, z, zz (a view of the library's buffer).  The state is
@@ -1122,6 +1143,50 @@ def project_point(terms, planes, values, r):
     L.check(L.load().sx_project_point(len(coef), coef.ctypes.data_as(L.P_D), packed.ctypes.data_as(L.P_I32), int(n_out), len(pl),
                                       pl.ctypes.data_as(L.P_I32), val.ctypes.data_as(L.P_D), float(r), out.ctypes.data_as(L.P_D)))
     return out
+
+
+# ----------------------------------------------------------------------------- onto another grid (sx_regrid)
+def _regrid_var_src(patch: GridParameters, dst_patch: GridParameters, variables):
+    """var_src as sx_regrid reads it: int32 [dst V], 1-based variables of the source; default: the destination's names in the source"""
+    if variables is None:
+        missing = [n for n in dst_patch.var_names() if n not in patch.vars]
+        if missing:
+            raise ValueError("regrid: the source has no variable named %s (pass variables=[...])" % ", ".join(map(repr, missing)))
+        variables = dst_patch.var_names()
+    if len(variables) != len(dst_patch.vars):
+        raise ValueError("regrid: %d source variables for the destination's %d" % (len(variables), len(dst_patch.vars)))
+    return np.array([patch.vars[v] if isinstance(v, str) else int(v) for v in variables], dtype=np.int32)
+
+
+def _regrid_centre(centre):
+    return None if centre is None else np.ascontiguousarray(centre, dtype=np.float64).reshape(2)
+
+
+def regrid_check(patch: GridParameters, dst_patch: GridParameters, centre=None, variables=None, outside="refuse"):
+    """What Grid.regrid refuses of the two patches, the centre, the variables and `outside`, on the host (sx_regrid_check: no handle, no
+    device); raises ScytheHipError with the library's message, returns None when the call would be accepted.  outside may be given as
+    the library's integer."""
+    ds, k1 = grid_desc(patch)
+    dd, k2 = grid_desc(dst_patch)
+    vs = _regrid_var_src(patch, dst_patch, variables)
+    c = _regrid_centre(centre)
+    L.check(L.load().sx_regrid_check(C.byref(ds), C.byref(dd), None if c is None else c.ctypes.data_as(L.P_D), vs.ctypes.data_as(L.P_I32),
+                                     L.REGRID_OUTSIDE.get(outside, outside)))
+
+
+def regrid_columns(gp_src: GridParameters, gp_dst: GridParameters, centre=None):
+    """The coordinates in gp_src of every column of gp_dst about `centre`, in gp_dst's gridpoint order, from the function Grid.regrid
+    sums at (sx_regrid_columns, on the host): (columns [n_cols, 1 or 2] - r_s[, lambda_s] -, inside [n_cols] bool)."""
+    ds, k1 = grid_desc(gp_src)
+    dd, k2 = grid_desc(gp_dst)
+    c = _regrid_centre(centre)
+    cp = None if c is None else c.ctypes.data_as(L.P_D)
+    n = C.c_int64(0)
+    L.check(L.load().sx_regrid_columns(C.byref(ds), C.byref(dd), cp, None, None, C.byref(n)))
+    cols = np.zeros((n.value, 2 if "L" in gp_dst.geometry else 1), order="F")
+    inside = np.zeros(n.value, dtype=np.int32)
+    L.check(L.load().sx_regrid_columns(C.byref(ds), C.byref(dd), cp, cols.ctypes.data_as(L.P_D), inside.ctypes.data_as(L.P_I32), C.byref(n)))
+    return cols, inside.astype(bool)
 
 
 # ----------------------------------------------------------------------------- extrema and their refinement (sx_extrema, sx_extremum_refine)
