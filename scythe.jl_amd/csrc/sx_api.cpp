@@ -736,7 +736,7 @@ int sx_destroy(sx_handle *h) {
     comm_release(h);
     iface_release(h);
     pcr_release(h);
-    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives, isosurfaces: their device memory goes with them
+    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives, isosurfaces, project, regrid, then the scan table the field-program scans share: their device memory goes with them
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);

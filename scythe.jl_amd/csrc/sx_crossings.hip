@@ -186,10 +186,7 @@ __device__ inline double cross_value(const CrossArgs &a, const double *__restric
             val[j] = fma(w[3], p[3], fma(w[2], p[2], fma(w[1], p[1], w[0] * p[0])));
         }
     }
-    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
-    double q = 0.0;
-    for (int t = a.g.start[0]; t < a.g.start[1]; t++) q += red_term(a.g, t, val, r, rr, ri, rri);
-    return q;
+    return red_output(a.g, 0, val, red_pow(r));
 }
 
 // grid (n_rays), one wave

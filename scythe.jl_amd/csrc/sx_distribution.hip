@@ -57,15 +57,14 @@ __device__ inline int dist_point(const Planes<ST> &P, int V, int64_t N, int64_t 
                                  const double *edges, double (&hi)[DIST_OUT], double (&lo)[DIST_OUT]) {
     double val[RED_PLANES];
     red_load_planes<ST>(P, V, N, pt, g, val);
-    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
-    double q = 0.0;
-    for (int t = g.start[0]; t < g.start[1]; t++) q += red_term(g, t, val, r, rr, ri, rri);
+    const RedPow pw = red_pow(r);
+    const double q = red_output(g, 0, val, pw);
     hi[0] = w; lo[0] = 0.0;
 #pragma unroll
     for (int o = 1; o < DIST_OUT; o++) {
         hi[o] = lo[o] = 0.0;
         for (int t = g.start[o]; t < g.start[o + 1]; t++) {       // empty at o >= n_out
-            const double x = red_term(g, t, val, r, rr, ri, rri);
+            const double x = red_term(g, t, val, pw);
             const double ph = w * x, pl = fma(w, x, -ph);
             dd_add(hi[o], lo[o], ph, pl);
         }
@@ -227,32 +226,18 @@ __global__ __launch_bounds__(DIST_FE * DIST_PARTS) void k_distribution_final(con
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct DistState : DiagState {
-    DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth)
-    DevBuf<double> d_wrl, d_wz;     // w_r w_l per ring, w_z per level
+struct DistState : DiagState {      // the work list and the weights: the handle's scan table (sx_redprog.hpp)
     DevBuf<double> d_edges;         // [DIST_BINS + 1]
     DevBuf<double2> d_part;
     DevBuf<unsigned> d_pcnt;
     DevBuf<double> d_sums;
     DevBuf<unsigned long long> d_count;
-    int n_items = 0;
 };
 
-// the work list and the weights: functions of the grid alone, made once per handle
 static DistState *dist_state(sx_handle *h) {
     if (h->diag[DIAG_DISTRIBUTION]) return diag_state<DistState>(h, DIAG_DISTRIBUTION);
     std::unique_ptr<DistState> st(new DistState());
-    std::vector<RedItem> items;
-    std::vector<int> first;
-    red_items(h, items, first);
-    std::vector<double> wr(h->nrings), wl(h->nrings), wz(h->nz, 1.0), wrl(h->nrings);
-    reduce_weights(eval_geom_of(h), wr.data(), wl.data(), wz.data());
-    for (int i = 0; i < h->nrings; i++) wrl[i] = wr[i] * wl[i];
-    st->n_items = (int)items.size();
-    const char *err = "sx_distribution: hipMalloc / hipMemcpy of the work list failed";
-    if (!st->d_items.upload(items, err) || !st->d_wrl.upload(wrl, err) || !st->d_wz.upload(wz, err) ||
-        !st->d_edges.upload(std::vector<double>(DIST_BINS + 1, 0.0), err))
-        return nullptr;
+    if (!st->d_edges.upload(std::vector<double>(DIST_BINS + 1, 0.0), "sx_distribution: hipMalloc / hipMemcpy of the work list failed")) return nullptr;
     h->diag[DIAG_DISTRIBUTION] = std::move(st);
     return diag_state<DistState>(h, DIAG_DISTRIBUTION);
 }
@@ -281,13 +266,6 @@ static bool dist_args_ok(const sx_grid_desc *gd, int kind, int source, int n_ter
         return false;
     }
     return true;
-}
-
-template <class ST, bool RINGS>
-static void launch_dist(sx_handle *h, const double *base, unsigned blocks, size_t lds, const DistArgs &a, const RedProg &prog) {
-    if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_distribution<ST, RINGS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL((k_distribution<ST, RINGS>), dim3(blocks), dim3(RED_T), lds, h->stream, planes_of<ST>(const_cast<double *>(base), h->V, h->N),
-                       a, prog);
 }
 
 }  // namespace sx
@@ -324,16 +302,17 @@ int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms,
     const sx_grid_desc gd = desc_of(h);
     int32_t planes[RED_PLANES][2], n_planes = 0;
     if (!dist_args_ok(&gd, kind, source, n_terms, terms, n_out, n_bins, edges, planes, &n_planes)) return 1;
-    if (n_terms > 0 && !coef) { set_error("sx_distribution: null coef with n_terms > 0"); return 1; }
+    if (!red_coef_ok("sx_distribution", n_terms, coef)) return 1;
     if (!count || !sums) { set_error("sx_distribution: null count or sums"); return 1; }
-    DistState *st = dist_state(h);
+    ScanGrid *sg = scan_grid(h, "sx_distribution", true);
+    DistState *st = sg ? dist_state(h) : nullptr;
     if (!st) return 1;
 
     RedProg prog;
     red_pack(prog, planes, n_planes, n_terms, coef, terms, n_out);
 
     const int level = kind == SX_DIST_LEVEL && h->has_z, groups = level ? h->nz : 1, S = n_bins + 3;
-    const int64_t n_work = h->has_l ? st->n_items : (h->N + RED_T - 1) / RED_T;
+    const int64_t n_work = h->has_l ? sg->n_items : scan_flat_blocks(h);
     const int nwg = (int)std::min<int64_t>(DIST_WG, std::max<int64_t>(1, n_work));
     const size_t EC = (size_t)groups * S, E = EC * n_out;
     if (!st->d_part.grow((size_t)nwg * E, "sx_distribution") || !st->d_pcnt.grow((size_t)nwg * EC, "sx_distribution") ||
@@ -344,19 +323,16 @@ int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms,
     if (error_status()) return 1;
 
     DistArgs a;
-    a.items = st->d_items; a.pstart = h->d_pstart; a.rh = h->d_r; a.wrl = st->d_wrl; a.wz = st->d_wz; a.edges = st->d_edges;
+    a.items = sg->d_items; a.pstart = h->d_pstart; a.rh = h->d_r; a.wrl = sg->d_wrl; a.wz = sg->d_wz; a.edges = st->d_edges;
     a.part = st->d_part; a.pcnt = st->d_pcnt;
     a.N = h->N; a.n_work = n_work; a.V = h->V; a.nz = h->nz; a.n_bins = n_bins; a.level = level;
     const size_t lds = dist_lds_bytes(groups, level ? 1 : RED_T / 64, n_bins, n_out);
     timer_begin(h, timer_id(h, "k_distribution"));
-    if (source == SX_REDUCE_STATE || !h->f32) {
-        const double *base = source == SX_REDUCE_STATE ? h->d_np1 : h->d_phys;
-        if (h->has_l) launch_dist<double, true>(h, base, (unsigned)nwg, lds, a, prog);
-        else launch_dist<double, false>(h, base, (unsigned)nwg, lds, a, prog);
-    } else {
-        if (h->has_l) launch_dist<float, true>(h, h->d_phys, (unsigned)nwg, lds, a, prog);
-        else launch_dist<float, false>(h, h->d_phys, (unsigned)nwg, lds, a, prog);
-    }
+    scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
+        const auto kern = k_distribution<decltype(st_t), decltype(rings)::value>;
+        if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(RED_T), lds, h->stream, P, a, prog);
+    });
     HIPCHK(hipGetLastError());
     timer_end(h);
     timer_begin(h, timer_id(h, "k_distribution_final"));

@@ -45,12 +45,9 @@ template <class ST>
 __device__ inline void ext_point(const Planes<ST> &P, int V, int64_t N, int64_t pt, double r, const RedProg &g, double (&q)[RED_OUT]) {
     double val[RED_PLANES];
     red_load_planes<ST>(P, V, N, pt, g, val);
-    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
+    const RedPow pw = red_pow(r);
 #pragma unroll
-    for (int o = 0; o < RED_OUT; o++) {
-        q[o] = 0.0;
-        for (int t = g.start[o]; t < g.start[o + 1]; t++) q[o] += red_term(g, t, val, r, rr, ri, rri);       // empty at o >= n_out
-    }
+    for (int o = 0; o < RED_OUT; o++) q[o] = red_output(g, o, val, pw);
 }
 
 // RINGS: grid = pieces; a thread's level is tid % nz, its first lambda lam0 + tid / nz, its stride RED_T / nz lambdas.
@@ -378,13 +375,9 @@ __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct ExtremaState : DiagState {      // last_bytes: k_extrema's
-    DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth) or whole rings
-    DevBuf<int> d_first;            // [nrings + 1] first piece of each ring
+struct ExtremaState : DiagState {      // last_bytes: k_extrema's.  The work list: the handle's scan table (sx_redprog.hpp)
     DevBuf<double> d_pv, d_val;     // [2][piece][output][level]; the results
     DevBuf<long long> d_pi, d_idx;
-    int n_items = 0;
-    bool scan_ready = false;
     // refinement
     double refine_bytes = 0;        // A bytes of the last sx_extremum_refine
     DevBuf<double> d_f;             // start | pos | grad [n_coord][n] each, value [n]
@@ -399,12 +392,6 @@ static ExtremaState *extrema_state(sx_handle *h) {
 double extrema_bytes(const sx_handle *h, bool refine) {
     const ExtremaState *st = diag_state<ExtremaState>(h, DIAG_EXTREMA);
     return !st ? 0.0 : refine ? st->refine_bytes : st->last_bytes;
-}
-
-template <class ST, bool RINGS>
-static void launch_scan(sx_handle *h, ExtremaState *st, const double *base, unsigned blocks, const RedProg &prog) {
-    hipLaunchKernelGGL((k_extrema<ST, RINGS>), dim3(blocks), dim3(RED_T), 0, h->stream, planes_of<ST>(const_cast<double *>(base), h->V, h->N), h->V,
-                       h->N, h->nz, st->d_items, h->d_pstart, h->d_r, prog, st->n_items, st->d_pv, st->d_pi);
 }
 
 static size_t refine_lds(const sx_handle *h) {
@@ -441,48 +428,35 @@ int sx_extrema(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, cons
     if (kind != SX_EXT_DOMAIN && kind != SX_EXT_AZIMUTH) { set_error("sx_extrema: kind must be SX_EXT_DOMAIN or SX_EXT_AZIMUTH"); return 1; }
     const sx_grid_desc gd = desc_of(h);
     int32_t planes[RED_PLANES][2], n_planes = 0;
-    if (sx_reduce_planes(&gd, source, n_terms, terms, n_out, &planes[0][0], &n_planes)) return 1;
-    if (n_terms > 0 && !coef) { set_error("sx_extrema: null coef with n_terms > 0"); return 1; }
+    RedProg prog;
+    if (!red_program("sx_extrema", &gd, source, n_terms, coef, terms, n_out, planes, &n_planes, prog)) return 1;
     if (n_out > 0 && (!val || !idx)) { set_error("sx_extrema: null val or idx with n_out > 0"); return 1; }
     if (n_out == 0) return 0;
     ExtremaState *st = extrema_state(h);
-    if (!st->scan_ready) {             // the work list: a function of the grid alone, made once per handle
-        std::vector<RedItem> items;
-        std::vector<int> first;
-        red_items(h, items, first);
-        st->n_items = (int)items.size();
-        const char *err = "sx_extrema: hipMalloc / hipMemcpy of the work list failed";
-        if (!st->d_items.upload(items, err) || !st->d_first.upload(first, err)) return 1;
-        st->scan_ready = true;
-    }
-    RedProg prog;
-    red_pack(prog, planes, n_planes, n_terms, coef, terms, n_out);
+    ScanGrid *sg = scan_grid(h, "sx_extrema", false);
+    if (!sg) return 1;
 
     const size_t n_res = kind == SX_EXT_AZIMUTH ? (size_t)2 * h->nrings * h->nz * n_out : (size_t)2 * n_out;
-    const size_t n_part = (size_t)2 * st->n_items * n_out * h->nz;
+    const size_t n_part = (size_t)2 * sg->n_items * n_out * h->nz;
     if (!st->d_pv.grow(n_part, "sx_extrema") || !st->d_pi.grow(n_part, "sx_extrema") || !st->d_val.grow(n_res, "sx_extrema") ||
         !st->d_idx.grow(n_res, "sx_extrema"))
         return 1;
     st->last_bytes = red_bytes(h, source, planes, n_planes);
 
     timer_begin(h, timer_id(h, "k_extrema"));
-    const unsigned flat_blocks = (unsigned)((h->N + RED_T - 1) / RED_T);
-    if (source == SX_REDUCE_STATE || !h->f32) {
-        const double *base = source == SX_REDUCE_STATE ? h->d_np1 : h->d_phys;
-        if (h->has_l) launch_scan<double, true>(h, st, base, (unsigned)st->n_items, prog);
-        else launch_scan<double, false>(h, st, base, flat_blocks, prog);
-    } else {
-        if (h->has_l) launch_scan<float, true>(h, st, h->d_phys, (unsigned)st->n_items, prog);
-        else launch_scan<float, false>(h, st, h->d_phys, flat_blocks, prog);
-    }
+    scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
+        constexpr bool RINGS = decltype(rings)::value;
+        hipLaunchKernelGGL((k_extrema<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
+                           h->V, h->N, h->nz, sg->d_items, h->d_pstart, h->d_r, prog, sg->n_items, st->d_pv, st->d_pi);
+    });
     HIPCHK(hipGetLastError());
     timer_end(h);
     timer_begin(h, timer_id(h, "k_extrema_final"));
     if (kind == SX_EXT_AZIMUTH)
-        hipLaunchKernelGGL(k_extrema_rings, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_pv, st->d_pi, st->d_first, st->n_items,
+        hipLaunchKernelGGL(k_extrema_rings, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_pv, st->d_pi, sg->d_first, sg->n_items,
                            h->nrings, h->nz, n_out, st->d_val, st->d_idx);
     else
-        hipLaunchKernelGGL(k_extrema_domain, dim3((unsigned)n_out, 2), dim3(EXT_TF), 0, h->stream, st->d_pv, st->d_pi, st->n_items, h->nz, n_out,
+        hipLaunchKernelGGL(k_extrema_domain, dim3((unsigned)n_out, 2), dim3(EXT_TF), 0, h->stream, st->d_pv, st->d_pi, sg->n_items, h->nz, n_out,
                            st->d_val, st->d_idx);
     HIPCHK(hipGetLastError());
     timer_end(h);

@@ -152,12 +152,6 @@ __device__ inline void iso_planes(const IsoArgs &a, const double *ser, double z,
 #pragma unroll
     for (int j = 0; j < RED_PLANES; j++) val[j] = j < a.g.n_planes ? column_series(a.nz, a.zmin, a.zmax, ser + (int)a.pser[j] * a.nz, z) : 0.0;
 }
-// output o in term order from +0.0
-__device__ inline double iso_output(const IsoArgs &a, int o, const double (&val)[RED_PLANES], double r, double rr, double ri, double rri) {
-    double q = 0.0;
-    for (int t = a.g.start[o]; t < a.g.start[o + 1]; t++) q += red_term(a.g, t, val, r, rr, ri, rri);
-    return q;
-}
 
 // grid (n_cols), one wave
 __global__ __launch_bounds__(64) void k_isosurface(IsoArgs a) {
@@ -198,7 +192,7 @@ __global__ __launch_bounds__(64) void k_isosurface(IsoArgs a) {
         }
     }
 
-    const double r = a.cols[q], rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
+    const RedPow pw = red_pow(a.cols[q]);
     const int64_t e0 = q * a.n_levels * a.max_cross;
     const ScanOut o = {a.height + e0, a.dir + e0, a.count + q * a.n_levels, a.status + q, a.values + q * nz, a.carry + e0 * a.n_carry, a.n_carry};
     scan_crossings(
@@ -206,12 +200,12 @@ __global__ __launch_bounds__(64) void k_isosurface(IsoArgs a) {
         [&](double z) {
             double val[RED_PLANES];
             iso_planes(a, ser, z, val);
-            return iso_output(a, 0, val, r, rr, ri, rri);
+            return red_output(a.g, 0, val, pw);
         },
         [&](double z, double *car) {
             double val[RED_PLANES];
             iso_planes(a, ser, z, val);
-            for (int c = 0; c < a.n_carry; c++) car[c] = iso_output(a, 1 + c, val, r, rr, ri, rri);
+            for (int c = 0; c < a.n_carry; c++) car[c] = red_output(a.g, 1 + c, val, pw);
         });
 }
 

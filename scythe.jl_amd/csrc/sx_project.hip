@@ -2,7 +2,7 @@
 // (include/scythe_hip.h).
 //
 // k_project is a streaming, pointwise kernel in the manner of k_stats (sx_stats.hip): a lane takes W consecutive points of the flat
-// [N] array, loads every plane the program names there once, forms the n_out outputs with red_term and stores each into its var_np1
+// [N] array, loads every plane the program names there once, forms the n_out outputs with red_output and stores each into its var_np1
 // plane of the destination.  W = 2 where N is even - every plane of the source and of the destination then starts on a 16-byte
 // boundary, and every access is 16 bytes per lane (8 for an fp32-stored plane) - else 1, the 8-byte form for every point (an odd N
 // puts every other plane off the boundary, so there is no vector body for a scalar tail to follow).  r is the ring table's entry of
@@ -25,19 +25,14 @@ __global__ __launch_bounds__(RED_T) void k_project(Planes<ST> P, int V, int64_t 
     double val0[RED_PLANES], val1[RED_PLANES];            // one array per point: each stays in registers (val1 is not used when W = 1)
     stat_load_planes<ST, W>(P, V, N, pt, g, val0, val1);
     const int64_t col = pt / nz;
-    const double r0 = rh[col], rr0 = r0 * r0, ri0 = 1.0 / r0, rri0 = 1.0 / rr0;
-    double r1 = r0, rr1 = rr0, ri1 = ri0, rri1 = rri0;
-    if (W == 2 && pt + 1 - col * nz == nz) { r1 = rh[col + 1]; rr1 = r1 * r1; ri1 = 1.0 / r1; rri1 = 1.0 / rr1; }
+    const RedPow pw0 = red_pow(rh[col]);
+    RedPow pw1 = pw0;
+    if (W == 2 && pt + 1 - col * nz == nz) pw1 = red_pow(rh[col + 1]);
 #pragma unroll
     for (int o = 0; o < RED_OUT; o++) {
         if (o >= g.n_out) continue;
         double q[W];
-        q[0] = 0.0;
-        if constexpr (W == 2) q[1] = 0.0;
-        for (int t = g.start[o]; t < g.start[o + 1]; t++) {           // one pass over the terms serves both points
-            q[0] += red_term(g, t, val0, r0, rr0, ri0, rri0);
-            if constexpr (W == 2) q[1] += red_term(g, t, val1, r1, rr1, ri1, rri1);
-        }
+        red_output<W>(g, o, val0, val1, pw0, pw1, q);
         VD y;
         stat_pack(y, q);
         *reinterpret_cast<VD *>(out + (int64_t)d.var[o] * N + pt) = y;
@@ -59,21 +54,10 @@ static sx_grid_desc proj_desc(const sx_handle *h) {
 
 // what sx_project and sx_project_check refuse of the pointers
 static bool proj_pointers_ok(const char *who, int n_terms, const double *coef, bool need_coef, const int32_t *terms, int n_out, const int32_t *var_dst) {
-    if (n_terms > 0 && need_coef && !coef) { set_error(std::string(who) + ": null coef with n_terms > 0"); return false; }
+    if (need_coef && !red_coef_ok(who, n_terms, coef)) return false;
     if (n_terms > 0 && !terms) { set_error(std::string(who) + ": null terms with n_terms > 0"); return false; }
     if (n_out > 0 && !var_dst) { set_error(std::string(who) + ": null var_dst with n_out > 0"); return false; }
     return true;
-}
-
-template <class ST>
-static void launch_project(sx_handle *src, const double *base, const RedProg &prog, const ProjDst &pd, double *out) {
-    const int64_t N = src->N;
-    if (N % 2 == 0)
-        hipLaunchKernelGGL((k_project<ST, 2>), grid1(N / 2, RED_T), dim3(RED_T), 0, src->stream, planes_of<ST>(const_cast<double *>(base), src->V, N), src->V, N,
-                           src->nz, src->d_r, prog, pd, out);
-    else
-        hipLaunchKernelGGL((k_project<ST, 1>), grid1(N, RED_T), dim3(RED_T), 0, src->stream, planes_of<ST>(const_cast<double *>(base), src->V, N), src->V, N,
-                           src->nz, src->d_r, prog, pd, out);
 }
 
 }  // namespace sx
@@ -147,12 +131,8 @@ int sx_project_point(int32_t n_terms, const double *coef, const int32_t *terms, 
     red_pack(prog, pl, n_planes, n_terms, coef, terms, n_out);
     double v[RED_PLANES] = {};
     for (int j = 0; j < n_planes; j++) v[j] = val[j];
-    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
-    for (int o = 0; o < n_out; o++) {
-        double q = 0.0;
-        for (int t = prog.start[o]; t < prog.start[o + 1]; t++) q += red_term(prog, t, v, r, rr, ri, rri);
-        out[o] = q;
-    }
+    const RedPow pw = red_pow(r);
+    for (int o = 0; o < n_out; o++) out[o] = red_output(prog, o, v, pw);
     return 0;
 }
 
@@ -167,14 +147,13 @@ int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *co
     const sx_grid_desc gs = proj_desc(src), gd = proj_desc(dst);
     if (sx_project_check(&gs, &gd, source, n_terms, terms, n_out, var_dst)) return 1;
     int32_t planes[RED_PLANES][2] = {}, n_planes = 0;
-    if (sx_reduce_planes(&gs, source, n_terms, terms, n_out, &planes[0][0], &n_planes)) return 1;
+    RedProg prog;
+    if (!red_program(who, &gs, source, n_terms, coef, terms, n_out, planes, &n_planes, prog)) return 1;
     if (!src->diag[DIAG_PROJECT]) src->diag[DIAG_PROJECT].reset(new ProjectState());
     ProjectState *st = diag_state<ProjectState>(src, DIAG_PROJECT);
     if (!st->done) HIPCHK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
     if (error_status()) return 1;
 
-    RedProg prog;
-    red_pack(prog, planes, n_planes, n_terms, coef, terms, n_out);
     ProjDst pd = {};
     for (int o = 0; o < n_out; o++) pd.var[o] = (uint8_t)(var_dst[o] - 1);
 
@@ -183,8 +162,15 @@ int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *co
     if (error_status()) return 1;
     st->last_bytes = red_bytes(src, source, planes, n_planes) + 8.0 * n_out * (double)src->N;
     timer_begin(src, timer_id(src, "k_project"));
-    if (source == SX_REDUCE_STATE || !src->f32) launch_project<double>(src, source == SX_REDUCE_STATE ? src->d_np1 : src->d_phys, prog, pd, dst->d_np1);
-    else launch_project<float>(src, src->d_phys, prog, pd, dst->d_np1);
+    scan_dispatch(src, source, [&](auto st_t, auto, auto P) {      // W = 2 where N is even (above); no RINGS form
+        auto launch = [&](auto width) {
+            constexpr int W = decltype(width)::value;
+            hipLaunchKernelGGL((k_project<decltype(st_t), W>), dim3(scan_flat_blocks(src, W)), dim3(RED_T), 0, src->stream, P, src->V, src->N, src->nz,
+                               src->d_r, prog, pd, dst->d_np1);
+        };
+        if (src->N % 2 == 0) launch(std::integral_constant<int, 2>());
+        else launch(std::integral_constant<int, 1>());
+    });
     HIPCHK(hipGetLastError());
     timer_end(src);
     HIPCHK(hipEventRecord(st->done, src->stream));

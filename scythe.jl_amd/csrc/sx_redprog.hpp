@@ -1,6 +1,8 @@
-// What sx_reduce (sx_reduce.hip), sx_extrema (sx_extrema.hip) and sx_distribution (sx_distribution.hip) share: the integrand program as the kernels read it, the ring pieces
-// a workgroup takes, and the loads of the planes a program names at one point.  Stated once so that the two entry points accept, pack
-// and read a program identically.
+// What the five entry points that evaluate a field program at every gridpoint of a tile share - sx_reduce, sx_extrema,
+// sx_distribution, sx_stats_* and sx_project (sx_<name>.hip): the program as the kernels read it and its acceptance, the loads of the
+// planes it names and its outputs at one point, the scan table of a handle (work list and weights) and the choice of the kernel
+// instantiation.  The walk of a ring piece stays written out in each kernel: as a helper that takes the body as a lambda, the
+// program and the accumulators the body captures went to scratch.
 #pragma once
 #include "sx_internal.hpp"
 #include <cstring>
@@ -8,7 +10,7 @@
 
 namespace sx {
 
-constexpr int RED_T = 256;          // threads per workgroup of k_reduce / k_extrema
+constexpr int RED_T = 256;          // threads per workgroup of the scan kernels
 constexpr int RED_ITERS = 32;       // strides of a workgroup over its piece of a ring: pieces per ring = ceil(strides / RED_ITERS)
 constexpr int RED_TERMS = 64, RED_OUT = 16, RED_PLANES = 16, RED_FACTORS = 4, RED_TERM_W = 11;
 
@@ -71,15 +73,41 @@ __device__ inline void stat_load_planes(const Planes<ST> &P, int V, int64_t N, i
     }
 }
 
+// the powers of r a term may name: r, r^2, 1 / r, 1 / r^2
+struct RedPow { double r, rr, ri, rri; };
+__host__ __device__ inline RedPow red_pow(double r) {
+    const double rr = r * r;
+    return RedPow{r, rr, 1.0 / r, 1.0 / rr};
+}
+
 // term t at a point: coef r^p prod field, the factors in the program's order (also on the host: sx_project_point)
-__host__ __device__ inline double red_term(const RedProg &g, int t, const double (&val)[RED_PLANES], double r, double rr, double ri, double rri) {
+__host__ __device__ inline double red_term(const RedProg &g, int t, const double (&val)[RED_PLANES], const RedPow &pw) {
     const int p = g.p[t], nf = g.nf[t];
+    const double r = pw.r, rr = pw.rr, ri = pw.ri, rri = pw.rri;      // values, so that the choice below compiles to selects, not branches
     double x = g.coef[t];
     if (p != 0) x *= p == 1 ? r : p == 2 ? rr : p == -1 ? ri : rri;
 #pragma unroll
     for (int f = 0; f < RED_FACTORS; f++)
         if (f < nf) x *= val[g.f[t][f]];
     return x;
+}
+
+// output o at a point: the sum of its terms in term order, plain fp64 (0 at o >= n_out: no terms)
+__host__ __device__ __forceinline__ double red_output(const RedProg &g, int o, const double (&val)[RED_PLANES], const RedPow &pw) {
+    double q = 0.0;
+    for (int t = g.start[o]; t < g.start[o + 1]; t++) q += red_term(g, t, val, pw);
+    return q;
+}
+// ... at the W points of stat_load_planes: one pass over the terms serves both points
+template <int W>
+__device__ __forceinline__ void red_output(const RedProg &g, int o, const double (&val0)[RED_PLANES], const double (&val1)[RED_PLANES], const RedPow &pw0,
+                                           const RedPow &pw1, double (&q)[W]) {
+    q[0] = 0.0;
+    if constexpr (W == 2) q[1] = 0.0;
+    for (int t = g.start[o]; t < g.start[o + 1]; t++) {
+        q[0] += red_term(g, t, val0, pw0);
+        if constexpr (W == 2) q[1] += red_term(g, t, val1, pw1);
+    }
 }
 
 // the double-double sums of sx_reduce and sx_distribution: (hi, lo) += x, the rounding error of the sum kept in lo (Knuth's two-sum: no ordering of |hi|, |x| assumed)
@@ -135,11 +163,75 @@ inline void red_pack(RedProg &prog, const int32_t (*planes)[2], int n_planes, in
     for (int o = n_out; o <= RED_OUT; o++) prog.start[o] = (uint8_t)k;
 }
 
-// bytes k_reduce / k_extrema read: the planes named x N x their element size
+// bytes a scan kernel reads: the planes named x N x their element size
 inline double red_bytes(const sx_handle *h, int source, const int32_t (*planes)[2], int n_planes) {
     double b = 0;
     for (int j = 0; j < n_planes; j++) b += (double)h->N * (source == SX_REDUCE_PHYSICAL && h->f32 && planes[j][1] > 0 ? 4.0 : 8.0);
     return b;
 }
+
+// the null-coef refusal in who's name; red_accept: what sx_reduce_planes refuses, then that, and the planes of the program on
+// success; red_program: red_accept + red_pack, for the callers that launch at once
+inline bool red_coef_ok(const char *who, int n_terms, const double *coef) {
+    if (n_terms > 0 && !coef) set_error(std::string(who) + ": null coef with n_terms > 0");
+    return n_terms <= 0 || coef;
+}
+inline bool red_accept(const char *who, const sx_grid_desc *gd, int source, int n_terms, const double *coef, const int32_t *terms, int n_out,
+                       int32_t (*planes)[2], int32_t *n_planes) {
+    return !sx_reduce_planes(gd, source, n_terms, terms, n_out, &planes[0][0], n_planes) && red_coef_ok(who, n_terms, coef);
+}
+inline bool red_program(const char *who, const sx_grid_desc *gd, int source, int n_terms, const double *coef, const int32_t *terms, int n_out,
+                        int32_t (*planes)[2], int32_t *n_planes, RedProg &prog) {
+    if (!red_accept(who, gd, source, n_terms, coef, terms, n_out, planes, n_planes)) return false;
+    red_pack(prog, planes, *n_planes, n_terms, coef, terms, n_out);
+    return true;
+}
+
+// The scan table: work list and quadrature weights, functions of the grid alone, one copy per handle (DIAG_SCAN), fetched per call.
+struct ScanGrid : DiagState {
+    std::vector<RedItem> items;     // the work list on the host (sx_stats: the longest piece)
+    DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth) or whole rings
+    DevBuf<int> d_first;            // [nrings + 1] first piece of each ring
+    DevBuf<double> d_wrl, d_wz;     // w_r w_l per ring, w_z per level; d_wrl is set last: it is there when both are
+    int n_items = 0;
+};
+// made on first use; the weights when a caller first asks for them.  Null, the error set in who's name, when an upload failed
+inline ScanGrid *scan_grid(sx_handle *h, const char *who, bool weights) {
+    ScanGrid *sg = diag_state<ScanGrid>(h, DIAG_SCAN);
+    if (sg && (!weights || sg->d_wrl)) return sg;
+    const std::string err = std::string(who) + ": hipMalloc / hipMemcpy of the work list failed";
+    if (!sg) {
+        std::unique_ptr<ScanGrid> made(new ScanGrid());
+        std::vector<int> first;
+        red_items(h, made->items, first);
+        made->n_items = (int)made->items.size();
+        if (!made->d_items.upload(made->items, err.c_str()) || !made->d_first.upload(first, err.c_str())) return nullptr;
+        h->diag[DIAG_SCAN] = std::move(made);
+        sg = diag_state<ScanGrid>(h, DIAG_SCAN);
+    }
+    if (weights) {
+        std::vector<double> wr(h->nrings), wl(h->nrings), wz(h->nz, 1.0), wrl(h->nrings);
+        reduce_weights(eval_geom_of(h), wr.data(), wl.data(), wz.data());
+        for (int i = 0; i < h->nrings; i++) wrl[i] = wr[i] * wl[i];
+        if (!sg->d_wz.upload(wz, err.c_str()) || !sg->d_wrl.upload(wrl, err.c_str())) return nullptr;
+    }
+    return sg;
+}
+
+// The kernel instantiation of a call.  The state (SX_REDUCE_STATE: var_np1) is always fp64; the derivative slots of `physical` are
+// fp32 on an f32 handle.  Grids with an azimuth walk ring pieces (RINGS).  f(double() or float(), std::true_type or false_type, planes)
+template <class F>
+inline void scan_dispatch(const sx_handle *h, int source, F &&f) {
+    double *base = source == SX_REDUCE_STATE ? h->d_np1 : h->d_phys;
+    auto geometry = [&](auto st) {
+        const auto P = planes_of<decltype(st)>(base, h->V, h->N);
+        if (h->has_l) f(st, std::true_type(), P);
+        else f(st, std::false_type(), P);
+    };
+    if (source == SX_REDUCE_STATE || !h->f32) geometry(double());
+    else geometry(float());
+}
+// workgroups of a flat launch: RED_T lanes, W points each
+inline unsigned scan_flat_blocks(const sx_handle *h, int W = 1) { return (unsigned)((h->N + (int64_t)RED_T * W - 1) / ((int64_t)RED_T * W)); }
 
 }  // namespace sx

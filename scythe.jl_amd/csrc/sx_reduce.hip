@@ -19,17 +19,13 @@
 namespace sx {
 
 constexpr int RED_TF = 1024;        // threads per workgroup of k_reduce_final's domain sum
-// RED_T, RED_ITERS, the limits, RedProg, RedItem, the work list, the plane loads and dd_add: sx_redprog.hpp (shared with sx_extrema, sx_distribution)
+// RED_T, RED_ITERS, the limits, RedProg, RedItem, the scan table (work list, weights), the plane loads and dd_add: sx_redprog.hpp
 
 struct ReduceState : DiagState {
-    DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth) or whole rings
-    DevBuf<int> d_first;            // [nrings + 1] first piece of each ring
-    DevBuf<double> d_wrl, d_wz;     // w_r w_l per ring, w_z per level
     DevBuf<double2> d_part;         // [piece][output][level] (hi, lo)
     DevBuf<double2> d_part2;        // [RED_OUT][blocks2] sums of the domain kind's first level
     int blocks2 = 1;                // workgroups per output of k_reduce_domain: 4 (piece, level) entries per thread, at most 64
     DevBuf<double> d_out;
-    int n_items = 0;
 };
 
 // One point: load the planes, evaluate the terms.  pt < N is the caller's business.
@@ -38,11 +34,11 @@ __device__ inline void reduce_point(const Planes<ST> &P, int V, int64_t N, int64
                                     double (&lo)[RED_OUT]) {
     double val[RED_PLANES];
     red_load_planes<ST>(P, V, N, pt, g, val);
-    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
+    const RedPow pw = red_pow(r);
 #pragma unroll
     for (int o = 0; o < RED_OUT; o++) {
         for (int t = g.start[o]; t < g.start[o + 1]; t++) {       // empty at o >= n_out
-            const double x = red_term(g, t, val, r, rr, ri, rri);
+            const double x = red_term(g, t, val, pw);
             dd_add(hi[o], lo[o], x);
         }
     }
@@ -143,30 +139,15 @@ __global__ void k_reduce_domain_sum(const double2 *__restrict__ part2, int block
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-// the work list and the weights: functions of the grid alone, made once per handle
-static ReduceState *reduce_state(sx_handle *h) {
+// the second level of the domain kind: its size follows from the work list (sg: the handle's scan table)
+static ReduceState *reduce_state(sx_handle *h, const ScanGrid *sg) {
     if (h->diag[DIAG_REDUCE]) return diag_state<ReduceState>(h, DIAG_REDUCE);
     std::unique_ptr<ReduceState> st(new ReduceState());
-    std::vector<RedItem> items;
-    std::vector<int> first;
-    red_items(h, items, first);
-    std::vector<double> wr(h->nrings), wl(h->nrings), wz(h->nz, 1.0), wrl(h->nrings);
-    reduce_weights(eval_geom_of(h), wr.data(), wl.data(), wz.data());
-    for (int i = 0; i < h->nrings; i++) wrl[i] = wr[i] * wl[i];
-    st->n_items = (int)items.size();
-    st->blocks2 = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)items.size() * h->nz + 4 * RED_TF - 1) / (4 * RED_TF)));
-    const char *err = "sx_reduce: hipMalloc / hipMemcpy of the work list failed";
-    if (!st->d_items.upload(items, err) || !st->d_first.upload(first, err) || !st->d_wrl.upload(wrl, err) || !st->d_wz.upload(wz, err) ||
-        !st->d_part2.upload(std::vector<double2>((size_t)RED_OUT * st->blocks2), err))
+    st->blocks2 = (int)std::min<int64_t>(64, std::max<int64_t>(1, ((int64_t)sg->n_items * h->nz + 4 * RED_TF - 1) / (4 * RED_TF)));
+    if (!st->d_part2.upload(std::vector<double2>((size_t)RED_OUT * st->blocks2), "sx_reduce: hipMalloc / hipMemcpy of the work list failed"))
         return nullptr;
     h->diag[DIAG_REDUCE] = std::move(st);
     return diag_state<ReduceState>(h, DIAG_REDUCE);
-}
-
-template <class ST, bool RINGS>
-static void launch_stage1(sx_handle *h, ReduceState *st, const double *base, unsigned blocks, const RedProg &prog) {
-    hipLaunchKernelGGL((k_reduce<ST, RINGS>), dim3(blocks), dim3(RED_T), 0, h->stream, planes_of<ST>(const_cast<double *>(base), h->V, h->N), h->V,
-                       h->N, h->nz, st->d_items, h->d_pstart, h->d_r, prog, st->d_part);
 }
 
 }  // namespace sx
@@ -237,40 +218,33 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
     if (kind != SX_REDUCE_DOMAIN && kind != SX_REDUCE_AZIMUTH) { set_error("sx_reduce: kind must be SX_REDUCE_DOMAIN or SX_REDUCE_AZIMUTH"); return 1; }
     const sx_grid_desc gd = desc_of(h);
     int32_t planes[RED_PLANES][2], n_planes = 0;
-    if (sx_reduce_planes(&gd, source, n_terms, terms, n_out, &planes[0][0], &n_planes)) return 1;
-    if (n_terms > 0 && !coef) { set_error("sx_reduce: null coef with n_terms > 0"); return 1; }
+    RedProg prog;
+    if (!red_program("sx_reduce", &gd, source, n_terms, coef, terms, n_out, planes, &n_planes, prog)) return 1;
     if (n_out > 0 && !out) { set_error("sx_reduce: null out with n_out > 0"); return 1; }
     if (n_out == 0) return 0;
-    ReduceState *st = reduce_state(h);
+    ScanGrid *sg = scan_grid(h, "sx_reduce", true);
+    ReduceState *st = sg ? reduce_state(h, sg) : nullptr;
     if (!st) return 1;
 
-    // the program as the kernel reads it: terms by output (their order within an output kept), factors as plane numbers
-    RedProg prog;
-    red_pack(prog, planes, n_planes, n_terms, coef, terms, n_out);
-
     const size_t n_res = kind == SX_REDUCE_AZIMUTH ? (size_t)h->nrings * h->nz * n_out : (size_t)n_out;
-    if (!st->d_part.grow((size_t)st->n_items * n_out * h->nz, "sx_reduce") || !st->d_out.grow(n_res, "sx_reduce")) return 1;
+    if (!st->d_part.grow((size_t)sg->n_items * n_out * h->nz, "sx_reduce") || !st->d_out.grow(n_res, "sx_reduce")) return 1;
     st->last_bytes = red_bytes(h, source, planes, n_planes);
 
     timer_begin(h, timer_id(h, "k_reduce"));
-    const unsigned flat_blocks = (unsigned)((h->N + RED_T - 1) / RED_T);
-    if (source == SX_REDUCE_STATE || !h->f32) {
-        const double *base = source == SX_REDUCE_STATE ? h->d_np1 : h->d_phys;
-        if (h->has_l) launch_stage1<double, true>(h, st, base, (unsigned)st->n_items, prog);
-        else launch_stage1<double, false>(h, st, base, flat_blocks, prog);
-    } else {
-        if (h->has_l) launch_stage1<float, true>(h, st, h->d_phys, (unsigned)st->n_items, prog);
-        else launch_stage1<float, false>(h, st, h->d_phys, flat_blocks, prog);
-    }
+    scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
+        constexpr bool RINGS = decltype(rings)::value;
+        hipLaunchKernelGGL((k_reduce<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
+                           h->V, h->N, h->nz, sg->d_items, h->d_pstart, h->d_r, prog, st->d_part);
+    });
     HIPCHK(hipGetLastError());
     timer_end(h);
     timer_begin(h, timer_id(h, "k_reduce_final"));
     if (kind == SX_REDUCE_AZIMUTH)
-        hipLaunchKernelGGL(k_reduce_mean, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_part, st->d_first, h->d_L, h->nrings, h->nz,
+        hipLaunchKernelGGL(k_reduce_mean, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_part, sg->d_first, h->d_L, h->nrings, h->nz,
                            n_out, st->d_out);
     else {
-        hipLaunchKernelGGL(k_reduce_domain, dim3((unsigned)n_out, (unsigned)st->blocks2), dim3(RED_TF), 0, h->stream, st->d_part, st->d_items,
-                           st->d_wrl, st->d_wz, st->n_items, h->nz, n_out, st->d_part2);
+        hipLaunchKernelGGL(k_reduce_domain, dim3((unsigned)n_out, (unsigned)st->blocks2), dim3(RED_TF), 0, h->stream, st->d_part, sg->d_items,
+                           sg->d_wrl, sg->d_wz, sg->n_items, h->nz, n_out, st->d_part2);
         hipLaunchKernelGGL(k_reduce_domain_sum, dim3(1), dim3(64), 0, h->stream, st->d_part2, st->blocks2, n_out, st->d_out);
     }
     HIPCHK(hipGetLastError());

@@ -2,13 +2,13 @@
 // DESIGN.md 19).
 //
 // k_stats is a streaming kernel: per sample it reads the planes the program names once, and reads and writes two doubles per output
-// and point.  It walks the ring pieces of red_items (sx_redprog.hpp) so that r is one value per ring, as in k_reduce / k_extrema /
+// and point.  It walks the ring pieces of the handle's scan table (sx_redprog.hpp) so that r is one value per ring, as in k_reduce / k_extrema /
 // k_distribution; a piece is a contiguous run of points (the level fastest), which the threads of a workgroup take in order, W
 // consecutive points (levels) per lane: W = 2 where zDim is even - every access of a plane or an accumulator is then 16 bytes per
 // lane (8 for an fp32-stored plane) - else 1.  gridDim.y workgroups share a piece so that a launch has enough waves to keep loads in
 // flight whatever the ring length.  Grids without an azimuth: lane = W consecutive points of the flat array.
 // Per stride a lane loads every plane first, then, output by output with the output a compile-time index, the accumulator pair,
-// forms q with red_term as ext_point does, updates the pair and stores it.  Nothing is summed across points: no atomics, no LDS, no
+// forms q with red_output as ext_point does, updates the pair and stores it.  Nothing is summed across points: no atomics, no LDS, no
 // cross-lane work, and a point's result cannot depend on which lane or workgroup took it.
 #include "sx_redprog.hpp"
 #include <cmath>
@@ -47,7 +47,7 @@ __device__ inline void stat_points(const Planes<ST> &P, int V, int64_t N, int64_
     using VD = typename StatVec<W>::d;
     double val0[RED_PLANES], val1[RED_PLANES];      // one array per point: each stays in registers (val1 is not used when W = 1)
     stat_load_planes<ST, W>(P, V, N, pt, sp.g, val0, val1);
-    const double rr = r * r, ri = 1.0 / r, rri = 1.0 / rr;
+    const RedPow pw = red_pow(r);
 #pragma unroll
     for (int o = 0; o < RED_OUT; o++) {
         if (o >= sp.g.n_out) continue;
@@ -55,17 +55,13 @@ __device__ inline void stat_points(const Planes<ST> &P, int V, int64_t N, int64_
         if (w == 0.0 && (op == SX_STAT_SUM || op == SX_STAT_DURATION)) continue;      // the "extrema only" sample
         VD *pa = reinterpret_cast<VD *>(acc + (int64_t)(2 * o) * N + pt), *pb = reinterpret_cast<VD *>(acc + (int64_t)(2 * o + 1) * N + pt);
         const VD xa = *pa, xb = *pb;
-        double q0 = 0.0, q1 = 0.0;                        // one pass over the terms serves both points
-        for (int t = sp.g.start[o]; t < sp.g.start[o + 1]; t++) {
-            q0 += red_term(sp.g, t, val0, r, rr, ri, rri);
-            if constexpr (W == 2) q1 += red_term(sp.g, t, val1, r, rr, ri, rri);
-        }
-        double a[W], b[W];
+        double q[W], a[W], b[W];
+        red_output<W>(sp.g, o, val0, val1, pw, pw, q);
         a[0] = stat_lane(xa, 0); b[0] = stat_lane(xb, 0);
-        stat_update(op, q0, sp.thr[o], time, w, first, a[0], b[0]);
+        stat_update(op, q[0], sp.thr[o], time, w, first, a[0], b[0]);
         if constexpr (W == 2) {
             a[1] = stat_lane(xa, 1); b[1] = stat_lane(xb, 1);
-            stat_update(op, q1, sp.thr[o], time, w, first, a[1], b[1]);
+            stat_update(op, q[1], sp.thr[o], time, w, first, a[1], b[1]);
         }
         VD ya, yb;
         stat_pack(ya, a); stat_pack(yb, b);
@@ -102,10 +98,8 @@ __global__ void k_stats_fill(double *__restrict__ acc, int64_t N, int n_out, Sta
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct StatsState : DiagState {     // last_bytes: k_stats'
-    DevBuf<RedItem> d_items;        // ring pieces (grids with an azimuth): a function of the grid alone, made once per handle
-    int n_items = 0, parts = 1;
-    bool items_ready = false;
+struct StatsState : DiagState {     // last_bytes: k_stats'.  The work list: the handle's scan table (sx_redprog.hpp)
+    int parts = 1;                  // workgroups per piece (stat_install)
     // the set
     DevBuf<double> d_acc;           // [n_out][2][N]
     int source = 0, n_terms = 0, n_out = 0, n_planes = 0;
@@ -138,8 +132,7 @@ static void stat_fill(sx_handle *h, StatsState *st, double *acc) {
 static bool stat_args_ok(sx_handle *h, const char *who, int source, int n_terms, const double *coef, const int32_t *terms, int n_out,
                          const int32_t *op, const double *thr, int32_t (*planes)[2], int32_t *n_planes) {
     const sx_grid_desc gd = desc_of(h);
-    if (sx_reduce_planes(&gd, source, n_terms, terms, n_out, &planes[0][0], n_planes)) return false;
-    if (n_terms > 0 && !coef) { set_error(std::string(who) + ": null coef with n_terms > 0"); return false; }
+    if (!red_accept(who, &gd, source, n_terms, coef, terms, n_out, planes, n_planes)) return false;
     if (!op) { set_error(std::string(who) + ": null op with n_out > 0"); return false; }
     for (int o = 0; o < n_out; o++) {
         if (op[o] < SX_STAT_SUM || op[o] > SX_STAT_DURATION) {
@@ -153,25 +146,19 @@ static bool stat_args_ok(sx_handle *h, const char *who, int source, int n_terms,
     return true;
 }
 
-// make the state and its work list; install the validated set with the accumulators `raw` (host, [n_out][2][N]) or empty.  All or
+// make the state and the scan table; install the validated set with the accumulators `raw` (host, [n_out][2][N]) or empty.  All or
 // nothing: a set that is there stays until the new one is complete
 static bool stat_install(sx_handle *h, const char *who, int source, int n_terms, const double *coef, const int32_t *terms, int n_out,
                          const int32_t *op, const double *thr, const int32_t (*planes)[2], int n_planes, const double *raw) {
     if (!h->diag[DIAG_STATS]) h->diag[DIAG_STATS].reset(new StatsState());
     StatsState *st = sstate(h);
-    if (!st->items_ready) {
-        std::vector<RedItem> items;
-        std::vector<int> first;
-        red_items(h, items, first);
-        st->n_items = (int)items.size();
-        if (!st->d_items.upload(items, "sx_stats: hipMalloc / hipMemcpy of the work list failed")) return false;
-        // workgroups per piece: enough for STAT_WG_TARGET workgroups, never more than a piece has strides
-        int longest = 1;
-        for (const RedItem &it : items) longest = std::max(longest, it.nlam * h->nz);
-        const int strides = (longest + RED_T * stat_width(h) - 1) / (RED_T * stat_width(h));
-        st->parts = std::max(1, std::min(strides, (STAT_WG_TARGET + st->n_items - 1) / std::max(st->n_items, 1)));
-        st->items_ready = true;
-    }
+    const ScanGrid *sg = scan_grid(h, "sx_stats", false);
+    if (!sg) return false;
+    // workgroups per piece (a function of the grid alone): enough for STAT_WG_TARGET workgroups, never more than a piece has strides
+    int longest = 1;
+    for (const RedItem &it : sg->items) longest = std::max(longest, it.nlam * h->nz);
+    const int strides = (longest + RED_T * stat_width(h) - 1) / (RED_T * stat_width(h));
+    st->parts = std::max(1, std::min(strides, (STAT_WG_TARGET + sg->n_items - 1) / std::max(sg->n_items, 1)));
     const size_t n_acc = (size_t)2 * n_out * h->N;
     DevBuf<double> d_acc;
     if (!d_acc.alloc(n_acc)) {
@@ -215,25 +202,6 @@ static void stat_drop(sx_handle *h) {
     st->last_bytes = 0;
 }
 
-template <class ST, bool RINGS, int W>
-static void launch_stats(sx_handle *h, StatsState *st, const double *base, dim3 grid, double time, double w) {
-    hipLaunchKernelGGL((k_stats<ST, RINGS, W>), grid, dim3(RED_T), 0, h->stream, planes_of<ST>(const_cast<double *>(base), h->V, h->N), h->V, h->N,
-                       h->nz, st->d_items, h->d_pstart, h->d_r, st->prog, st->d_acc, time, w, st->samples == 0 ? 1 : 0);
-}
-
-template <class ST>
-static void launch_stats(sx_handle *h, StatsState *st, const double *base, double time, double w) {
-    const int W = stat_width(h);
-    const dim3 rings((unsigned)st->n_items, (unsigned)st->parts), flat((unsigned)((h->N + (int64_t)RED_T * W - 1) / ((int64_t)RED_T * W)));
-    if (h->has_l) {
-        if (W == 2) launch_stats<ST, true, 2>(h, st, base, rings, time, w);
-        else launch_stats<ST, true, 1>(h, st, base, rings, time, w);
-    } else {
-        if (W == 2) launch_stats<ST, false, 2>(h, st, base, flat, time, w);
-        else launch_stats<ST, false, 1>(h, st, base, flat, time, w);
-    }
-}
-
 }  // namespace sx
 
 using namespace sx;
@@ -270,10 +238,21 @@ int sx_stats_accumulate(sx_handle *h, double time, double weight) {
     if (!std::isfinite(weight)) { set_error("sx_stats_accumulate: weight is NaN or Inf"); return 1; }
     StatsState *st = sstate(h);
     if (!st || st->n_out == 0) return 0;
+    const ScanGrid *sg = scan_grid(h, "sx_stats", false);      // there since the set was installed
+    if (!sg) return 1;
     st->last_bytes = red_bytes(h, st->source, st->planes, st->n_planes) + 32.0 * st->n_out * (double)h->N;
     timer_begin(h, timer_id(h, "k_stats"));
-    if (st->source == SX_REDUCE_STATE || !h->f32) launch_stats<double>(h, st, st->source == SX_REDUCE_STATE ? h->d_np1 : h->d_phys, time, weight);
-    else launch_stats<float>(h, st, h->d_phys, time, weight);
+    scan_dispatch(h, st->source, [&](auto st_t, auto rings, auto P) {
+        constexpr bool RINGS = decltype(rings)::value;
+        auto launch = [&](auto width) {
+            constexpr int W = decltype(width)::value;
+            const dim3 grid = RINGS ? dim3((unsigned)sg->n_items, (unsigned)st->parts) : dim3(scan_flat_blocks(h, W));
+            hipLaunchKernelGGL((k_stats<decltype(st_t), RINGS, W>), grid, dim3(RED_T), 0, h->stream, P, h->V, h->N, h->nz, sg->d_items, h->d_pstart,
+                               h->d_r, st->prog, st->d_acc, time, weight, st->samples == 0 ? 1 : 0);
+        };
+        if (stat_width(h) == 2) launch(std::integral_constant<int, 2>());
+        else launch(std::integral_constant<int, 1>());
+    });
     HIPCHK(hipGetLastError());
     timer_end(h);
     if (error_status()) return 1;
