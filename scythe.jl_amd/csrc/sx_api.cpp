@@ -229,7 +229,7 @@ static const SwitchRow SWITCHES[] = {
     {"SX_DFT_RLQ", &Switches::rl_quarter, FLAG},
     {"SX_DFT_HALF", &Switches::dft_half, FLAG},
     {"SX_DFT_CLASSES", &Switches::dft_classes, INTEGER},
-    {"SX_FUSE_ZINV", &Switches::fuse_zinv, FLAG},
+    {"SX_FUSE_ZINV", &Switches::fuse_zinv, INTEGER},
     {"SX_ZINV_CT", &Switches::zinv_ct, INTEGER},
     {"SX_SBW_MFMA", &Switches::sbw_mfma, INTEGER},
     {"SX_SBW_PF", &Switches::sbw_prefetch, FLAG},

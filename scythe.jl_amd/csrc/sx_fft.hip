@@ -269,12 +269,27 @@ __device__ __forceinline__ BinPair packed_bins(double2 aq, double2 bq, int k, in
 // LDS of the kernel, for the kernel and its launcher: two sets of FNP transform regions SKEW apart and, behind them, the twiddle
 // table of the register passes (REG: three 256-point passes x 64 lanes, at 512 points + 4 x 64 of the radix-2 pass in front).
 // REG: the regions only serve the copy-out, ring point l sits at fft_pad(l).
+// FUSE: the vertical inverse's coefficient slab - FZC level rows of SST doubles, SST >= L >= K2 - lies over the set the next slot stages
+// (a set's 16-byte elements seen as FZC rows of doubles: exactly one set), so it adds no LDS and the twiddle table stays behind it.
 template <int LOGL, bool REG> struct InvCfg {
     static constexpr int SKEW = REG ? (1 << LOGL) / 16 + 2 : FftCfg<LOGL>::SKEW;
     static constexpr int SET = FftCfg<LOGL>::FNP * ((1 << LOGL) + SKEW);                     // complex elements of one set
+    static constexpr int SST = 2 * ((1 << LOGL) + SKEW) * FftCfg<LOGL>::FNP / FftCfg<LOGL>::FZC;       // slab row stride in doubles
+    static constexpr int SLAB = FftCfg<LOGL>::FZC * SST;                                     // doubles of the slab
+    static_assert(SLAB <= 2 * SET && SST >= (1 << LOGL) && SST % 2 == 0, "the slab fits one set, a row holds L doubles in 16-byte pairs");
     static constexpr int TW2 = 3 * 64, NTW = REG ? TW2 + (LOGL == 9 ? 4 * 64 : 0) : 0;       // start of the radix-2 twiddles; table length
     static constexpr size_t LDS = sizeof(double2) * (2 * SET + NTW);
 };
+// Fused node launch, a one-dimensional grid per variable rank: workgroup id -> (level chunk, node).  The nchunk chunks of one
+// (node, variable) read the same A rows, so they are put on ONE XCD and close in time: id = 8 nchunk g + 8 chunk + x is chunk `chunk`
+// of node 8 g + x.  Assumes what the hardware does today and no interface promises: workgroups start in ascending linear id, and id i
+// goes to XCD i mod 8 (8 XCDs, each with an L2 of its own).  Every rank's plane is a multiple of 8 ids, so x IS the XCD.  If the
+// assumption fails, nothing but the L2 hits is lost.  Nodes beyond the launch's count (a count that is no multiple of 8) return at once.
+// placed = false (SX_FUSE_ZINV=2, the fabric-traffic record's comparison): the unfused grid's order, chunk fastest.
+__device__ __forceinline__ void fused_unit_of(int id, int nchunk, bool placed, int &chunk, int &unit) {
+    if (placed) { const int r = id >> 3; chunk = r % nchunk; unit = 8 * (r / nchunk) + (id & 7); }
+    else { chunk = id % nchunk; unit = id / nchunk; }
+}
 typedef double fft_d4 __attribute__((ext_vector_type(4)));
 template <int LOGL, class ST, bool NODE, class AT = double, bool FUSE = false, bool REG = false>
 __global__ void __launch_bounds__(512, LOGL <= 8 ? 4 : 2)      // waves per SIMD: at L = 512 one workgroup per CU (2 x 64 KB of LDS, 4 wavenumbers per lane)
@@ -284,19 +299,25 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
                  int V, int nz, int nsz, int K2, int nrings, int64_t N, int64_t azrow,
                  int s_u, int s_r, int s_rr, int s_l, int s_ll, int s_z, int s_zz,
                  const double *__restrict__ Asrc = nullptr, int64_t Astride = 0, const double *__restrict__ MzT = nullptr, int Zb = 0,
-                 int unit0 = 0) {
+                 int unit0 = 0, int n_units = 0, int placed = 0) {
     // NODE: the "rings" are radial NODES (uniform ring tables only): one Az row per unit, no radial combination;
     // the output is the node-space array G that the equation-set kernel combines with the basis weights itself.
     constexpr int L = 1 << LOGL, T = FftCfg<LOGL>::LPT, NK = FftCfg<LOGL>::NK;
     constexpr int FZC = FftCfg<LOGL>::FZC, FNP = FftCfg<LOGL>::FNP, LOGZ = FftCfg<LOGL>::LOGZ;
     constexpr int SKEW = InvCfg<LOGL, REG>::SKEW, SET = InvCfg<LOGL, REG>::SET, TW2 = InvCfg<LOGL, REG>::TW2;
-    static_assert(!REG || ((LOGL == 8 || LOGL == 9) && !FUSE), "register-resident passes: 256- and 512-point transforms");
+    static_assert(!REG || LOGL == 8 || (LOGL == 9 && !FUSE), "register-resident passes: 256- and 512-point transforms; fused at 256");
     extern __shared__ double2 smf[];
     FFT_STAMP(0);
     int nslot = 0;
     // grid = (level chunk, ring or node, variable RANK): workgroups are dispatched in blockIdx order, so every unit of the
-    // variable with the most requested slots goes first and the variables with few (or no) slots fill the tail of the launch
-    const int ring = blockIdx.y + unit0, z0 = blockIdx.x * FZC;      // unit0: first ring / node of the launch
+    // variable with the most requested slots goes first and the variables with few (or no) slots fill the tail of the launch.
+    // FUSE: (chunk and node, 1, variable RANK), see fused_unit_of
+    int chunk = blockIdx.x, unit = blockIdx.y;
+    if constexpr (FUSE) {
+        fused_unit_of((int)blockIdx.x, (nz + FZC - 1) / FZC, placed != 0, chunk, unit);
+        if (unit >= n_units) return;
+    }
+    const int ring = unit + unit0, z0 = chunk * FZC;                 // unit0: first ring / node of the launch
     int v = 0;
     for (int u = 0; u < V; u++) {
         const int cu = __popc(slotmask[u]);
@@ -334,6 +355,32 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
         phq[q] = make_double2(1.0, 0.0);
     }
     const bool pair_ok = ((nz & 1) == 0);                          // (z, z+1) pairs are 16-byte aligned
+    // once per workgroup, issued behind the first coefficient (or operand) loads: the twiddles and, ring-wise, the phase factors
+    auto setup = [&]() {
+        asm volatile("" ::: "memory");
+        int tt = t;
+        asm volatile("" : "+v"(tt));               // opaque copy: the table addresses are formed HERE (hoisted out of the
+                                                   // group loop they were spilled, and every reload drained the memory counter)
+        if (REG) {
+            // twiddles of the three register passes: kept in LDS behind the copy-out sets (3 KB, the same for every wave - each
+            // wave writes the whole table and reads back its own writes, no workgroup barrier), not in 12 registers: at the 128
+            // registers of a two-workgroups-per-CU kernel they cost a spilled address, and every reload of it drained the
+            // memory counter - i.e. waited for the previous slot's copy-out stores
+            double2 *wl = smf + 2 * SET;
+            constexpr int S2 = L / 256;                     // the 256-point passes' angles in a table of L entries
+            wl[tt] = twg[S2 * tt]; wl[64 + tt] = twg[S2 * 4 * (tt & 15)]; wl[128 + tt] = twg[S2 * 16 * (tt & 3)];
+            if (LOGL == 9) {                                // the radix-2 pass in front: e^{+2 pi i (t + 64 q) / 512}
+#pragma unroll
+                for (int q = 0; q < 4; q++) wl[TW2 + 64 * q + tt] = twg[tt + 64 * q];
+            }
+        } else tw.template init<+1>(twg, tt);
+        if (!NODE) {
+#pragma unroll
+            for (int q = 0; q < NK; q++) if (inq[q]) phq[q] = phr[tt + q * T];
+        }
+        asm volatile("" ::: "memory");
+        setup_done = true;
+    };
 
     // groups of output slots that share one radial combination: (sz, d) = (0,0): u, l, ll; (0,1): r; (0,2): rr;
     // (1,0): z; (2,0): zz.  The four radial rows are re-read (L2) per group so that only one combination is live.
@@ -350,48 +397,57 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
             // vertical inverse of this group's operator on the matrix cores: D[level][block] = sum_zm Mz[level][zm] A[zm][block]
             constexpr int KSM = 16, NWV = (FNP * T) / 64 > 0 ? (FNP * T) / 64 : 1;                 // K steps (b_zDim <= 64); waves of the workgroup
             constexpr int TPW = ((L / 16 > 0 ? L / 16 : 1) + NWV - 1) / NWV;                        // column tiles (16 wavenumber blocks) per wave
-            constexpr int SST = 2 * (L + SKEW) * FNP / FZC;      // row stride (doubles) of the slab: the set's 16-byte elements as 16 rows
+            constexpr int SST = InvCfg<LOGL, REG>::SST;          // row stride (doubles) of the slab: the set's 16-byte elements as 16 rows
             const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, n16 = lane & 15, kk4 = lane >> 4;
             double *S = reinterpret_cast<double *>(smf + par * SET);
             const double *arow = Asrc + (int64_t)j0 * Astride + (int64_t)v * Zb * K2;
             const double *mop = MzT + ((int64_t)v * 3 + sz) * Zb * nz + z0 + n16;
-            constexpr int KH = 8;                              // operands in halves of 8 K steps: 32 VGPRs live instead of 64
+            constexpr int KH = 4;                              // operands in rounds of 4 K steps
+            // The wave's TPW column tiles walk the K steps together: the operator's operand is the same for every tile and is loaded
+            // once, and the A operands of all tiles of a round are in flight at once - 4 + 4 TPW loads per round trip to L2, three
+            // round trips per group at b_zDim = 43 (tile by tile in rounds of 8 it was four; rounds of 8 for both tiles together
+            // spill: 44 bytes of scratch at 256 points).  Every tile still sums its K steps in ascending order.  Operand addresses walk
+            // forward by 4 rows per K step from an OPAQUE start: formed here, per group (as invariants of the group loop they were
+            // hoisted and spilled)
+            int64_t oa = (int64_t)kk4 * nz;
+            asm volatile("" : "+v"(oa));
+            const double *pa = mop + oa, *pb[TPW];
+            fft_d4 acc[TPW];
+#pragma unroll
+            for (int tt = 0; tt < TPW; tt++) {
+                int64_t ob = (int64_t)kk4 * K2 + min((wave * TPW + tt) * 16 + n16, K2 - 1);
+                asm volatile("" : "+v"(ob));
+                pb[tt] = arow + ob;
+                acc[tt] = fft_d4{0.0, 0.0, 0.0, 0.0};
+            }
+#pragma unroll
+            for (int k0 = 0; k0 < KSM; k0 += KH) {
+                if (4 * k0 >= Zb) break;
+                double am[KH], bm[TPW][KH];
+#pragma unroll
+                for (int ks = 0; ks < KH; ks++) {
+                    const int k = 4 * (k0 + ks) + kk4;
+                    am[ks] = k < Zb ? *pa : 0.0;
+                    pa += 4 * (int64_t)nz;
+#pragma unroll
+                    for (int tt = 0; tt < TPW; tt++) {
+                        bm[tt][ks] = (k < Zb && (wave * TPW + tt) * 16 < K2) ? *pb[tt] : 0.0;
+                        pb[tt] += 4 * (int64_t)K2;
+                    }
+                }
+                if (!setup_done) setup();                      // twiddles behind the first operands
+#pragma unroll
+                for (int tt = 0; tt < TPW; tt++)
+#pragma unroll
+                    for (int ks = 0; ks < KH; ks++)
+                        if (4 * (k0 + ks) < Zb) acc[tt] = __builtin_amdgcn_mfma_f64_16x16x4f64(am[ks], bm[tt][ks], acc[tt], 0, 0, 0);
+            }
 #pragma unroll
             for (int tt = 0; tt < TPW; tt++) {
                 const int tile = wave * TPW + tt;
-                const int blk = min(tile * 16 + n16, K2 - 1);
-                fft_d4 acc = {0.0, 0.0, 0.0, 0.0};
-                // operand addresses walk forward by 4 rows per K step from an OPAQUE start: formed here, per tile and group
-                // (as invariants of the group loop the 64 of them were hoisted and spilled)
-                int64_t oa = (int64_t)kk4 * nz, ob = (int64_t)kk4 * K2 + blk;
-                asm volatile("" : "+v"(oa), "+v"(ob));
-                const double *pa = mop + oa, *pb = arow + ob;
-#pragma unroll
-                for (int k0 = 0; k0 < KSM; k0 += KH) {
-                    if (4 * k0 >= Zb) break;
-                    double am[KH], bm[KH];
-#pragma unroll
-                    for (int ks = 0; ks < KH; ks++) {
-                        const int k = 4 * (k0 + ks) + kk4;
-                        am[ks] = k < Zb ? *pa : 0.0;
-                        bm[ks] = (k < Zb && tile * 16 < K2) ? *pb : 0.0;
-                        pa += 4 * (int64_t)nz; pb += 4 * (int64_t)K2;
-                    }
-                    if (!setup_done) {                         // twiddles behind the first operands (see below)
-                        asm volatile("" ::: "memory");
-                        int tt2 = t;
-                        asm volatile("" : "+v"(tt2));
-                        tw.template init<+1>(twg, tt2);
-                        asm volatile("" ::: "memory");
-                        setup_done = true;
-                    }
-#pragma unroll
-                    for (int ks = 0; ks < KH; ks++)
-                        if (4 * (k0 + ks) < Zb) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(am[ks], bm[ks], acc, 0, 0, 0);
-                }
                 if (tile * 16 < K2) {
 #pragma unroll
-                    for (int r = 0; r < 4; r++) S[(kk4 + 4 * r) * SST + tile * 16 + n16] = acc[r];
+                    for (int r = 0; r < 4; r++) S[(kk4 + 4 * r) * SST + tile * 16 + n16] = acc[tt][r];
                 }
             }
             lds_barrier();
@@ -424,31 +480,7 @@ k_rl_inverse_fft(const AT *__restrict__ Az, Planes<ST> phys, const double *__res
                     x2[r] = ldpair(a0 + r * azrow + 2 * kcq[q0 + 1]);
                     y2[r] = ldpair(b0 + r * azrow + 2 * kcq[q0 + 1]);
                 }
-                if (!setup_done) {                             // ... then, once, the twiddles and phase factors behind them
-                    asm volatile("" ::: "memory");
-                    int tt = t;
-                    asm volatile("" : "+v"(tt));               // opaque copy: the table addresses are formed HERE (hoisted out of the
-                                                               // group loop they were spilled, and every reload drained the memory counter)
-                    if (REG) {
-                        // twiddles of the three register passes: kept in LDS behind the copy-out sets (3 KB, the same for every wave - each
-                        // wave writes the whole table and reads back its own writes, no workgroup barrier), not in 12 registers: at the 128
-                        // registers of a two-workgroups-per-CU kernel they cost a spilled address, and every reload of it drained the
-                        // memory counter - i.e. waited for the previous slot's copy-out stores
-                        double2 *wl = smf + 2 * SET;
-                        constexpr int S2 = L / 256;                     // the 256-point passes' angles in a table of L entries
-                        wl[tt] = twg[S2 * tt]; wl[64 + tt] = twg[S2 * 4 * (tt & 15)]; wl[128 + tt] = twg[S2 * 16 * (tt & 3)];
-                        if (LOGL == 9) {                                // the radix-2 pass in front: e^{+2 pi i (t + 64 q) / 512}
-#pragma unroll
-                            for (int q = 0; q < 4; q++) wl[TW2 + 64 * q + tt] = twg[tt + 64 * q];
-                        }
-                    } else tw.template init<+1>(twg, tt);
-                    if (!NODE) {
-#pragma unroll
-                        for (int q = 0; q < NK; q++) if (inq[q]) phq[q] = phr[tt + q * T];
-                    }
-                    asm volatile("" ::: "memory");
-                    setup_done = true;
-                }
+                if (!setup_done) setup();                      // ... then, once, the twiddles and phase factors behind them
                 double2 a1 = make_double2(0.0, 0.0), b1 = a1, a2 = a1, b2 = a1;
 #pragma unroll
                 for (int r = 0; r < R; r++) {
@@ -840,12 +872,19 @@ bool fft_path_ok(const sx_handle *h) {
     return h->has_l && L >= 16 && L <= 512 && (L & (L - 1)) == 0;   // one transform = min(L/4, 64) lanes of one wave
 }
 
-// SX_FUSE_ZINV=1: node-space units take the vertical inverse inside the inverse FFT kernel (FUSE): 16-level chunks, b_zDim <= 64
-// (16 K steps of the f64 MFMA), rings of at most 256 points (two column tiles per wave), fp64 intermediates.  OFF by default -
-// measured at the bench grid (round 3, A/B/A/B on one box): k_zinv 0.065 -> 0.024 ms (it then only serves the ring-wise
-// rings), Az of the 174 nodes never written or read, but k_node_fft 0.131 -> 0.201 ms: 968 against 987 steps/s.  The
-// matrix-core prologue (per coefficient group four rounds of 16 L2 loads -> 8 MFMAs at the 128 registers the kernel has, an
-// LDS round trip and two workgroup barriers) is serial time in a kernel whose limit is its serial time.
+// Node-space units take the vertical inverse inside the inverse FFT kernel (FUSE): 16-level chunks, b_zDim <= 64 (16 K steps of the
+// f64 MFMA), rings of at most 256 points (two column tiles per wave), fp64 intermediates.  ON by default since round 9
+// (SX_FUSE_ZINV=0: k_zinv writes Az for every node and the node kernel reads it back; profiles/r09/ab_fused_zinv.txt).
+//   Round 3, A/B/A/B on one box, had it slower and off: k_zinv 0.065 -> 0.024 ms, but k_node_fft 0.131 -> 0.201 ms, 968 against 987
+//   steps/s.  That compared the LDS passes behind the prologue with (later) the register passes without it, and every (node,
+//   variable)'s A rows were fetched through the fabric by four XCDs.
+//   Round 9: the prologue in front of the register passes (114 VGPRs, no scratch, 73,216 bytes of LDS: two workgroups per CU), both
+//   column tiles of a wave through the K steps together, the level chunks of a (node, variable) on one XCD (fused_unit_of: fabric
+//   reads of the launch 307 -> 61 MB, L2 hit rate 0.35 -> 0.65).  At the bench grid k_zinv 0.0557 -> 0.0203 ms and k_node_fft
+//   0.0854 -> 0.1213 ms: the pair is what it was (0.1411 -> 0.1416 ms); the prologue is still serial time in a kernel whose limit is
+//   its serial time.  The step gains elsewhere: Az shrinks from 160 to 41 MB written, and the ring-wise inverse, whose code is the
+//   same, runs in 0.1137 ms instead of 0.1261.  1,097 -> 1,119 steps/s, every run of four above every run of the parent.
+//   The results are bit-identical to the pair's: k_zinv sums the K steps on the same matrix-core instruction in the same order.
 bool fft_fused_zinv(const sx_handle *h) {
     return h->sw.fuse_zinv && h->node_mode && h->has_z && h->uniform_L <= 256 && h->Zb <= 64 && h->nz % 16 == 0 && !h->sp32;
 }
@@ -867,12 +906,14 @@ static void launch_inv_k(sx_handle *h, const int *d_mask, const InvTarget &tg, c
     const auto kernel = k_rl_inverse_fft<LOGL, ST, NODE, AT, FUSE, REG>;
     constexpr size_t lds = InvCfg<LOGL, REG>::LDS;
     if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const dim3 g((h->nz + FFT_FZC - 1) / FFT_FZC, tg.n_units, h->V);
+    const int nchunk = (h->nz + FFT_FZC - 1) / FFT_FZC;
+    // FUSE: one dimension per variable rank, whole groups of 8 nodes (fused_unit_of)
+    const dim3 g = FUSE ? dim3(nchunk * 8 * ((tg.n_units + 7) / 8), 1, h->V) : dim3(nchunk, tg.n_units, h->V);
     hipLaunchKernelGGL(kernel, g, dim3(FftCfg<LOGL>::THREADS), lds, h->stream, reinterpret_cast<const AT *>(az),
                        planes_of<ST>(tg.out, h->V, tg.N), tg.phi, tg.kmax, tg.pstart, h->d_tw, tg.phoff, h->d_ph, d_mask, h->V, h->nz,
                        h->nsz, h->K2, tg.n_phi, tg.N, azrow, h->slot[0], h->slot[1], h->slot[2], h->slot[3], h->slot[4], h->slot[5],
                        h->slot[6], FUSE ? h->d_A + (int64_t)h->cell0 * h->C : nullptr, FUSE ? (int64_t)h->C : 0,
-                       FUSE ? h->d_MzT : nullptr, FUSE ? h->Zb : 0, tg.unit0);
+                       FUSE ? h->d_MzT : nullptr, FUSE ? h->Zb : 0, tg.unit0, tg.n_units, h->sw.fuse_zinv != 2);
 }
 
 // SX_FFT_REG (default on): register-resident passes at 256 and 512 points
@@ -885,7 +926,12 @@ static void launch_inv_v(sx_handle *h, const int *d_mask, const InvTarget &tg, c
 template <int LOGL>
 static void launch_inv(sx_handle *h, const int *d_mask, const InvTarget &tg, const double *az, int64_t azrow) {
     if (tg.node_mode && fft_fused_zinv(h)) {
-        if (LOGL <= 8) { if (h->f32) launch_inv_k<LOGL, float, true, double, true>(h, d_mask, tg, az, azrow); else launch_inv_k<LOGL, double, true, double, true>(h, d_mask, tg, az, azrow); }
+        if constexpr (LOGL <= 8) {         // fft_fused_zinv: rings of at most 256 points
+            constexpr bool R8 = LOGL == 8;
+            if (R8 && h->sw.fft_reg) { if (h->f32) launch_inv_k<LOGL, float, true, double, true, R8>(h, d_mask, tg, az, azrow); else launch_inv_k<LOGL, double, true, double, true, R8>(h, d_mask, tg, az, azrow); }
+            else if (h->f32) launch_inv_k<LOGL, float, true, double, true>(h, d_mask, tg, az, azrow);
+            else launch_inv_k<LOGL, double, true, double, true>(h, d_mask, tg, az, azrow);
+        }
     } else if (h->sp32) {      // storage_f32 = 2
         if (tg.node_mode) launch_inv_v<LOGL, float, true, float>(h, d_mask, tg, az, azrow); else launch_inv_v<LOGL, float, false, float>(h, d_mask, tg, az, azrow);
     } else if (h->f32) {
@@ -955,7 +1001,7 @@ void launch_node_fft(sx_handle *h) {
     timer_begin(h, id);
 #ifdef SX_PHASES
     if (!g_fft_buf) {
-        g_fft_n = (int64_t)((h->nz + FFT_FZC - 1) / FFT_FZC) * h->V * h->nbt;
+        g_fft_n = (int64_t)((h->nz + FFT_FZC - 1) / FFT_FZC) * h->V * 8 * ((h->nbt + 7) / 8);      // the fused grid: whole groups of 8 nodes
         hipMalloc(&g_fft_buf, sizeof(long long) * g_fft_n * 8);
         hipMemset(g_fft_buf, 0, sizeof(long long) * g_fft_n * 8);
         hipMemcpyToSymbol(HIP_SYMBOL(g_fft_dbg), &g_fft_buf, sizeof(g_fft_buf));

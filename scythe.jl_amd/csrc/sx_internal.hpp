@@ -278,7 +278,9 @@ struct Switches {
     int rl_quarter = 1;     // RL grids: quarter-wave DFT kernels over one work list (SX_DFT_RLQ=0: the half-ring kernels in two ring classes)
     int dft_half = 0;       // SX_DFT_HALF=1: the half-ring forward DFT kernel on native rings (A/B)
     int dft_classes = 0;    // SX_DFT_CLASSES=n: launch classes of the older DFT kernels (experiments; <= 0: the launcher's own count)
-    int fuse_zinv = 0;      // SX_FUSE_ZINV=1: vertical inverse inside the node FFT kernel (measured slower: sx_fft.hip)
+    // vertical inverse inside the node FFT kernel where fft_fused_zinv holds (sx_fft.hip has the measurements); SX_FUSE_ZINV=0: k_zinv
+    // writes Az for every node and the node FFT kernel reads it back; 2: fused, workgroups in plain grid order (fabric-traffic comparison)
+    int fuse_zinv = 1;
     int zinv_ct = 0;        // SX_ZINV_CT=n: column tiles per wave of k_zinv (A/B; values without a kernel take the default: plan_zinv)
     // k_sbw_mfma (matrix-core vertical contraction, operator in registers) for zDim 64 / 32 (SX_SBW_MFMA=0: k_sbw).  1 also takes the
     // forward pair that sums the ring spectra into the spline nodes inside the FFT kernel where it applies (k_fl_forward_cells +
