@@ -178,6 +178,14 @@ int sx_semi_column_ops(double zmin, double zmax, int32_t zDim, int32_t b_zDim, i
 int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_q, int32_t bcl, int32_t bcr, const double *b,
                           double *a_pcr, double *a_chol, int32_t *levels);
 
+/* The same right-hand side through the tables of the partitioned one-tile solve (k_solve_part, csrc/sx_iface.hip: `parts` row blocks
+ * balanced in unknowns, each with its own factor, coupled through 6 edge values per block), applied in double in the kernel's order,
+ * and through the banded Cholesky factors.  b, a_part, a_chol: [num_cells + 3]; ranges [parts][2] (may be NULL): the first and last
+ * partition whose edge values each partition's correction reads.  Refuses PERIODIC classes and partitions the interface form does not
+ * admit.  Pure host helper: it validates the table construction where there is no GPU; never on the step path. */
+int sx_solve_part_check(int32_t num_cells, double xmin, double xmax, double l_q, int32_t bcl, int32_t bcr, int32_t parts, const double *b,
+                        double *a_part, double *a_chol, int32_t *ranges);
+
 /* The launch shape the library takes for given dimensions, with the SX_* switches as the environment has them now (read by the
  * function sx_create uses): which kernel instantiation - its text, such as "k_sbw_mfma<64, 32, 256>", into kernel[kernel_cap];
  * empty where none runs or the handle would be refused - and its grid arithmetic.  in / out by kind:
@@ -192,8 +200,12 @@ int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_
  *                    variables of the handle, tile cells, storage_f32 == 2, ring_uniform_L (0: native rings);
  *                    out = taken (0 / 1), S (cells per radial segment), segments, threads, nodes per k_nodes_z workgroup, node runs;
  *                    kernel: "k_fl_forward_cells<log2 L>", empty where the pair is not taken (SX_PLAN_FORWARD then names the launch)
+ *   SX_PLAN_SOLVE    the contiguous one-tile B -> A solve:  in = num_cells + 3, any PERIODIC class (0 / 1) + 1, contiguous B (0 / 1) + 1,
+ *                    right-hand sides of the launch;  out = partitions (0: not the partitioned kernel), threads per workgroup;
+ *                    kernel: "k_solve_part" where the launch takes it, else "k_solve" (or k_solve_pcr, where SX_PLAN_PCR's tables exist
+ *                    and the column count is at most SX_PCR_MAXCOLS)
  * Pure host helper (no handle, no device): the tests name the launch shapes they cover from it; never on the step path. */
-enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2, SX_PLAN_FORWARD_CELLS = 3 };
+enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2, SX_PLAN_FORWARD_CELLS = 3, SX_PLAN_SOLVE = 4 };
 int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap);
 
 /* The work lists of the native-ring DFT launches (csrc/sx_dft.hip) of a tile of cells cell0 .. cell0 + num_cells - 1 with Springsteel's

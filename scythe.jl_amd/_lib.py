@@ -71,6 +71,7 @@ SYMBOLS = {
     "sx_get_gridpoints": (C.c_int, [_H, P_D]),
     "sx_calc_tile_sizes": (C.c_int, [C.POINTER(GridDesc), C.c_int32, P_D]),
     "sx_spline_solve_check": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, P_D, P_D, P_D, C.POINTER(C.c_int32)]),
+    "sx_solve_part_check": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, P_D, P_D, P_D, P_I32]),
     "sx_launch_plan": (C.c_int, [C.c_int32, P_I32, P_I32, C.c_char_p, C.c_int32]),
     "sx_dft_work_list": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, P_I32, P_I32, C.c_int64, P_I32]),
     "sx_set_physical_values": (C.c_int, [_H, P_D]),
@@ -175,7 +176,7 @@ SYMBOLS = {
 
 # host-only accessors that the tests call and the product path never does: an earlier build of the same ABI (SCYTHE_HIP_LIB, A/B timing)
 # may lack them; they are bound where present, and calling a missing one raises AttributeError at the call
-OPTIONAL = {"sx_dft_work_list"}
+OPTIONAL = {"sx_dft_work_list", "sx_solve_part_check"}
 
 _lib = None
 

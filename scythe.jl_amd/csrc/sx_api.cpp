@@ -716,6 +716,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
     // deferred diagnostic variable (sx_internal.hpp): one-tile HRBL runs whose forward path is the FFT + matrix-core kernels
     h->defer_diag = h->sw.defer_diag && h->eq == SX_EQ_ONEWAY_SW_HRBL && h->V == 6 && h->ncells == h->nc && mfma_shape(h, true) &&
                     h->sw.sbw_mfma;
+    if (!part_prepare(h)) FAIL();
     if (sx_bind_patch_b(h, nullptr, nullptr)) FAIL();
     *out = h;
     return status();
@@ -799,9 +800,9 @@ int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_
 int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap) {
     clear_error();
     if (!in || !out) { set_error("sx_launch_plan: null argument"); return 1; }
-    if (kind != SX_PLAN_FORWARD && kind != SX_PLAN_ZINV && kind != SX_PLAN_PCR && kind != SX_PLAN_FORWARD_CELLS) { set_error("sx_launch_plan: unknown kind " + std::to_string(kind)); return 1; }
+    if (kind != SX_PLAN_FORWARD && kind != SX_PLAN_ZINV && kind != SX_PLAN_PCR && kind != SX_PLAN_FORWARD_CELLS && kind != SX_PLAN_SOLVE) { set_error("sx_launch_plan: unknown kind " + std::to_string(kind)); return 1; }
     // the dimensions among the inputs (not the geometry in front, not the fp32 flag at the end) divide: positive
-    const int first = kind == SX_PLAN_PCR ? 0 : 1, last = (kind == SX_PLAN_FORWARD || kind == SX_PLAN_FORWARD_CELLS) ? 6 : kind == SX_PLAN_ZINV ? 3 : 4;
+    const int first = (kind == SX_PLAN_PCR || kind == SX_PLAN_SOLVE) ? 0 : 1, last = (kind == SX_PLAN_FORWARD || kind == SX_PLAN_FORWARD_CELLS) ? 6 : kind == SX_PLAN_ZINV ? 3 : 4;
     for (int i = first; i < last; i++)
         if (in[i] < 1) { set_error("sx_launch_plan: dimensions must be positive"); return 1; }
     const Switches sw = read_switches();
@@ -820,6 +821,10 @@ int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, 
         const ZinvPlan p = plan_zinv(in[0], in[1], in[2], in[3], sw);
         name = kernel_name(p);
         out[0] = p.CT; out[1] = p.grid_x;
+    } else if (kind == SX_PLAN_SOLVE) {
+        const int P = plan_solve_part(in[0], in[1] - 1, in[2] - 1, in[3], sw);
+        name = P ? "k_solve_part" : "k_solve";
+        out[0] = P; out[1] = P ? 64 * P : 64;
     } else {
         const PcrPlan p = plan_pcr(in[0], in[1], in[2], in[3], sw);
         out[0] = p.R; out[1] = p.logR; out[2] = p.threads;
@@ -1476,7 +1481,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_fl_forward") b = w * N * V + wi * fl;
     else if (k == "k_sb") b = w * (fl + bz);
     else if (k == "k_sbz") b = wi * fl + w * S_tile;
-    else if (k == "k_solve") b = w * 4.0 * S_patch;                 // read B, write y, read y, write A
+    else if (k == "k_solve") b = w * (h->last_solve_part ? 2.0 : 4.0) * S_patch;   // read B, write y, read y, write A; k_solve_part: B in, A out
     else if (k == "k_semiimplicit") b = w * N * 2.0 * 5.0;
     else if (k == "k_phys_rain") b = N * (eq_planes + w * (4.0 * V + (h->semi ? V : 0.0)));   // as k_phys_pointwise, + impdot
     else if (k == "k_condensation") b = w * N * (6.0 + 3.0);       // read s, xi, mu, mu_c, mu_r, qss of var_np1; write s, mu, mu_c

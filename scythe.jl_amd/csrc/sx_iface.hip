@@ -616,11 +616,299 @@ void iface_release(sx_handle *h) {
     h->iface_state = nullptr;
 }
 
+// ------------------------------------------------------------------------------------------------ the same form inside one workgroup
+// The contiguous, non-periodic one-tile solve (k_solve<true>, sx_kernels.hip) writes its forward-sweep vector y into A and reads it
+// back: 4 x S_patch bytes for B in, A out.  Here the P waves of a workgroup are the "tiles": wave p owns a block of at most NR
+// consecutive unknowns of the same 64 columns, requests all its B rows at entry, runs the tile-local sweeps in
+// registers, and only the 6 edge values of y' per wave cross between waves, through LDS.  B is read once, A is written once.
+//
+//   y'_p = D_p^-1 b'_p                         b' = Gamma b: the boundary-condition rows fold onto the first / last two unknowns, which
+//                                              the first / last wave own, so no row is foreign to its wave (no f, no x of the tile form)
+//   c_p  = sum_s Q_ps y'_I,s                   Q = -R_II T^-1, the edge-value block of the tile form's reduced matrix, 6 x 6 per pair of
+//                                              partitions.  T^-1 decays with the distance between partitions like D^-1 does with the
+//                                              distance between rows: blocks whose largest entry is below 2^-70 of Q's largest (1e-21:
+//                                              a millionth of the last bit of a sum of O(1) terms) are not applied, [slo, shi] per wave
+//   a_p  = y'_p + Z_p c_p                      6 multiply-adds per row
+//
+// The tables come from build_class_ops with a virtual tile table of P row blocks (balanced in unknowns) of the one tile, so factor
+// rows, Z and Q are the extended-precision ones of the multi-GPU form.  Register i of a wave holds unknown u0 + i - off with off = 0
+// except in the last wave, whose block is aligned to the END of the register array: the first and the last two unknowns of the patch,
+// which take the boundary-condition folds, then sit at compile-time indices.  Rows outside the block have zero factor rows (l = 0,
+// 1 / diagonal = 0), so both sweeps run over all NR registers without a branch.
+constexpr int part_meta_ints(int P) { return 3 + (P + 1) + 2 * P; }      // n, rl, rr, u0[P + 1], slo[P], shi[P]
+// per (class, partition): forward rows [NR + 3][4] (l0, l1, l2, 1 / d), backward rows [NR][4] (l(i+1, i), l(i+2, i), l(i+3, i), 1 / d),
+// Z [NR][6], Q [6][6 P]
+constexpr int part_tab_doubles(int P, int NR) { return (NR + 3) * 4 + NR * 4 + NR * 6 + 36 * P; }
+
+template <int P, int NR>
+__device__ __forceinline__ void part_columns(const double *__restrict__ B, double *__restrict__ A, const int *__restrict__ pm,
+                                             const double *__restrict__ g_l, const double *__restrict__ g_r, const double *__restrict__ tab,
+                                             int nb, int64_t stride, int64_t col, bool act, int p, int lane, double *stab, double *sy) {
+    constexpr int TAB = part_tab_doubles(P, NR), OB = (NR + 3) * 4, OZ = OB + NR * 4, OQ = OZ + NR * 6;
+    const int rl = pm[1], rr = pm[2], u0 = pm[3 + p], nt = pm[4 + p] - u0;
+    const int off = p == P - 1 ? NR - nt : 0;
+    double y[NR];                                         // register i <-> unknown u0 + i - off (patch row rl + that) for off <= i < off + nt
+    const double *Bc = B + col;
+    // every right-hand-side row of the wave in one burst; registers outside the block repeat an edge row (no address outside
+    // the block is formed).  The row address walks in the lane's own registers, not as NR wave-uniform addresses in scalar ones
+    {
+        const double *bp = Bc + (int64_t)(rl + u0) * stride;
+#pragma unroll
+        for (int i = 0; i < NR; i++) {
+            if (i > 0) bp += (i > off && i < off + nt) ? stride : 0;
+            y[i] = (bp)[0];
+        }
+    }
+    double bl0 = 0.0, bl1 = 0.0, br0 = 0.0, br1 = 0.0;
+    if (p == 0)
+        for (int q = 0; q < rl; q++) { const double b = (Bc + (int64_t)q * stride)[0]; bl0 = bl0 + g_l[q * 2] * b; bl1 = bl1 + g_l[q * 2 + 1] * b; }
+    if (p == P - 1)
+        for (int q = 0; q < rr; q++) { const double b = (Bc + (int64_t)(nb - 1 - q) * stride)[0]; br0 = br0 + g_r[q * 2] * b; br1 = br1 + g_r[q * 2 + 1] * b; }
+    double *st_ = stab + p * TAB;
+    for (int e = lane * 2; e < TAB; e += 128) *reinterpret_cast<double2 *>(st_ + e) = *reinterpret_cast<const double2 *>(tab + (size_t)p * TAB + e);
+    __syncthreads();
+    // registers outside the block hold a finite copy of an edge row: their factor rows are zero, both sweeps leave 0 there
+    y[0] = y[0] + bl0;
+    y[1] = y[1] + bl1;
+    y[NR - 1] = y[NR - 1] + br0;
+    y[NR - 2] = y[NR - 2] + br1;
+    double y1 = 0.0, y2 = 0.0, y3 = 0.0;
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+        const double4 l = *reinterpret_cast<const double4 *>(st_ + i * 4);
+        double s = y[i] - (l.z * y1 + l.y * y2 + l.x * y3);
+        s = l.w * s;
+        y3 = y2; y2 = y1; y1 = s;
+        y[i] = s;
+    }
+    double x1 = 0.0, x2 = 0.0, x3 = 0.0;
+#pragma unroll
+    for (int i = NR - 1; i >= 0; i--) {
+        const double4 u = *reinterpret_cast<const double4 *>(st_ + OB + i * 4);
+        double s = y[i] - (u.x * x1 + u.y * x2 + u.z * x3);
+        s = u.w * s;
+        x3 = x2; x2 = x1; x1 = s;
+        y[i] = s;
+        const int j = i - off;                       // unknown of the block; its first and last three are the wave's edge values
+        if (j >= 0 && j < nt && (j < 3 || j >= nt - 3)) sy[(p * 6 + (j < 3 ? j : j - (nt - 6))) * 64 + lane] = s;
+    }
+    __syncthreads();
+    double c[6];
+#pragma unroll
+    for (int j = 0; j < 6; j++) c[j] = 0.0;
+    const int slo = pm[4 + P + p], shi = pm[4 + 2 * P + p];
+    for (int s = slo; s <= shi; s++) {
+        double yi[6];
+#pragma unroll
+        for (int k = 0; k < 6; k++) yi[k] = sy[(s * 6 + k) * 64 + lane];
+#pragma unroll
+        for (int j = 0; j < 6; j++)
+#pragma unroll
+            for (int k = 0; k < 6; k++) c[j] = __builtin_fma(st_[OQ + j * 6 * P + s * 6 + k], yi[k], c[j]);
+    }
+    double *Ac = A + col, *ap = Ac + (int64_t)(rl + u0) * stride;
+#pragma unroll
+    for (int i = 0; i < NR; i++) {
+        double a = y[i];
+#pragma unroll
+        for (int j = 0; j < 6; j++) a = __builtin_fma(st_[OZ + i * 6 + j], c[j], a);
+        y[i] = a;
+        if (i > 0) ap += (i > off && i < off + nt) ? stride : 0;
+        if (act && i >= off && i < off + nt) *ap = a;
+    }
+    if (act && p == 0)
+        for (int q = 0; q < rl; q++) (Ac + (int64_t)q * stride)[0] = g_l[q * 2] * y[0] + g_l[q * 2 + 1] * y[1];
+    if (act && p == P - 1)
+        for (int q = 0; q < rr; q++) (Ac + (int64_t)(nb - 1 - q) * stride)[0] = g_r[q * 2] * y[NR - 1] + g_r[q * 2 + 1] * y[NR - 2];
+}
+
+// grid: x = blocks of 64 columns + one block for the k = 0 column (its own class, lane 0 of every wave works),
+// y = (variable, z-mode) group of the window; block = P waves.  Lanes without a column read a valid one and store nothing: every
+// lane reaches both barriers.
+template <int P, int NR>
+__global__ void __launch_bounds__(64 * P)
+k_solve_part(const double *__restrict__ B, double *__restrict__ A, const int *__restrict__ cls, const int *__restrict__ pmeta,
+             const double *__restrict__ gl, const double *__restrict__ gr, const double *__restrict__ tab, int nb, int Zb, int K2, int vz0,
+             int64_t stride) {
+    constexpr int TAB = part_tab_doubles(P, NR), PM = part_meta_ints(P);
+    __shared__ __attribute__((aligned(32))) double stab[P * TAB];
+    __shared__ __attribute__((aligned(16))) double sy[6 * P * 64];
+    const int vz = blockIdx.y, v = (vz0 + vz) / Zb;
+    const bool k0 = (blockIdx.x == gridDim.x - 1);
+    const int p = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int c = cls[v * 2 + (k0 ? 0 : 1)];
+    const int *pm = pmeta + c * PM;
+    const double *tc = tab + (size_t)c * P * TAB;
+    // one column per lane: the k = 0 column of the group (lane 0 works), or the Re / Im columns 2 .. K2 - 1 of the wavenumbers k >= 1
+    const int cb = 2 + blockIdx.x * 64 + lane;
+    const bool act = k0 ? lane == 0 : cb < K2;
+    part_columns<P, NR>(B, A, pm, gl + c * 6, gr + c * 6, tc, nb, stride, (int64_t)vz * K2 + (k0 ? 0 : act ? cb : 2), act, p, lane, stab, sy);
+}
+
+// ---- host: the tables of one class for P partitions of at most NR unknowns.  meta [part_meta_ints(P)], tab [P][part_tab_doubles(P, NR)]
+static bool part_tables_host(const SplineClass &sc, int nb, int P, int NR, int *meta, double *tab, std::string &err) {
+    if (sc.periodic) { err = "partitioned solve: PERIODIC class"; return false; }
+    const int n = sc.nfree, rl = sc.rl, nc = nb - 3, TAB = part_tab_doubles(P, NR), OB = (NR + 3) * 4, OZ = OB + NR * 4, OQ = OZ + NR * 6;
+    std::vector<int> ub(P + 1), cell0(P), ncells(P);
+    for (int t = 0; t <= P; t++) ub[t] = (int)((int64_t)n * t / P);
+    for (int t = 0; t < P; t++) cell0[t] = t == 0 ? 0 : ub[t] + rl;
+    for (int t = 0; t < P; t++) ncells[t] = (t == P - 1 ? nc : cell0[t + 1]) - cell0[t];
+    meta[0] = n; meta[1] = rl; meta[2] = sc.rr;
+    for (int t = 0; t <= P; t++) meta[3 + t] = ub[t];
+    std::fill(tab, tab + (size_t)P * TAB, 0.0);
+    const int RN = IF_R * P, RNp = (RN + 15) / 16 * 16;
+    for (int p = 0; p < P; p++) {
+        if (ncells[p] < 1) { err = "partitioned solve: empty partition"; return false; }
+        ClassOps co;
+        if (!build_class_ops(sc, nb, P, p, cell0.data(), ncells.data(), ncells[p] + 3, co, err)) return false;
+        const int nt = ub[p + 1] - ub[p], off = p == P - 1 ? NR - nt : 0;
+        if (co.nt != nt || nt > NR || co.rowbase != (p == 0 ? rl : 0)) { err = "partitioned solve: unexpected partition"; return false; }
+        double *tp = tab + (size_t)p * TAB;
+        auto L = [&](int i, int q) { return i < nt + 3 ? co.Lf[(size_t)i * 4 + q] : 0.0; };      // rows nt .. nt + 2 are zero
+        for (int j = 0; j < nt; j++) {
+            const int i = j + off;
+            for (int q = 0; q < 4; q++) tp[(size_t)i * 4 + q] = L(j, q);
+            tp[OB + (size_t)i * 4 + 0] = L(j + 1, 2);
+            tp[OB + (size_t)i * 4 + 1] = L(j + 2, 1);
+            tp[OB + (size_t)i * 4 + 2] = L(j + 3, 0);
+            tp[OB + (size_t)i * 4 + 3] = L(j, 3);
+            for (int e = 0; e < IF_E; e++) tp[OZ + (size_t)i * IF_E + e] = co.Z[(size_t)j * IF_E + e];
+        }
+        double qmax = 0.0;
+        std::vector<double> bmax(P, 0.0);
+        for (int j = 0; j < IF_E; j++)
+            for (int s = 0; s < P; s++)
+                for (int k = 0; k < IF_E; k++) {
+                    const double q = co.Q[(size_t)(s * IF_R + k) * RNp + (p * IF_R + j)];
+                    tp[OQ + (size_t)j * IF_E * P + s * IF_E + k] = q;
+                    bmax[s] = std::max(bmax[s], std::fabs(q));
+                }
+        for (int t = 0; t < P; t++)                  // the scale: the largest entry of the whole edge-value block of Q
+            for (int j = 0; j < IF_E; j++)
+                for (int s = 0; s < P * IF_E; s++) qmax = std::max(qmax, std::fabs(co.Q[(size_t)((s / IF_E) * IF_R + s % IF_E) * RNp + (t * IF_R + j)]));
+        int slo = P, shi = -1;
+        for (int s = 0; s < P; s++)
+            if (bmax[s] > std::ldexp(qmax, -70)) { slo = std::min(slo, s); shi = std::max(shi, s); }
+        meta[4 + P + p] = slo;                       // no block above the bar (one partition couples to nothing): slo > shi, c = 0
+        meta[4 + 2 * P + p] = shi;
+    }
+    return true;
+}
+
+// the arithmetic of k_solve_part in the kernel's order, in double, on the host: one column b [nb] -> a [nb]
+static void part_apply_host(const int *meta, const double *tab, int P, int NR, const double (*g_l)[2], const double (*g_r)[2], int nb,
+                            const double *b, double *a) {
+    const int rl = meta[1], rr = meta[2], TAB = part_tab_doubles(P, NR), OB = (NR + 3) * 4, OZ = OB + NR * 4, OQ = OZ + NR * 6;
+    std::vector<double> y((size_t)P * NR, 0.0), yI((size_t)P * IF_E, 0.0);
+    for (int p = 0; p < P; p++) {
+        const int u0 = meta[3 + p], nt = meta[4 + p] - u0, off = p == P - 1 ? NR - nt : 0, row0 = rl + u0 - off;
+        const double *tp = tab + (size_t)p * TAB;
+        double *yp = &y[(size_t)p * NR];
+        for (int i = off; i < off + nt; i++) yp[i] = b[row0 + i];
+        double bl0 = 0, bl1 = 0, br0 = 0, br1 = 0;
+        if (p == 0) for (int q = 0; q < rl; q++) { bl0 = bl0 + g_l[q][0] * b[q]; bl1 = bl1 + g_l[q][1] * b[q]; }
+        if (p == P - 1) for (int q = 0; q < rr; q++) { br0 = br0 + g_r[q][0] * b[nb - 1 - q]; br1 = br1 + g_r[q][1] * b[nb - 1 - q]; }
+        yp[0] += bl0; yp[1] += bl1; yp[NR - 1] += br0; yp[NR - 2] += br1;
+        double y1 = 0, y2 = 0, y3 = 0;
+        for (int i = 0; i < NR; i++) {
+            double s = yp[i] - (tp[i * 4 + 2] * y1 + tp[i * 4 + 1] * y2 + tp[i * 4 + 0] * y3);
+            s = tp[i * 4 + 3] * s;
+            y3 = y2; y2 = y1; y1 = s; yp[i] = s;
+        }
+        double x1 = 0, x2 = 0, x3 = 0;
+        for (int i = NR - 1; i >= 0; i--) {
+            double s = yp[i] - (tp[OB + i * 4 + 0] * x1 + tp[OB + i * 4 + 1] * x2 + tp[OB + i * 4 + 2] * x3);
+            s = tp[OB + i * 4 + 3] * s;
+            x3 = x2; x2 = x1; x1 = s; yp[i] = s;
+            const int j = i - off;
+            if (j >= 0 && j < nt && (j < 3 || j >= nt - 3)) yI[(size_t)p * IF_E + (j < 3 ? j : j - (nt - 6))] = s;
+        }
+    }
+    for (int m = 0; m < nb; m++) a[m] = 0.0;
+    for (int p = 0; p < P; p++) {
+        const int u0 = meta[3 + p], nt = meta[4 + p] - u0, off = p == P - 1 ? NR - nt : 0, row0 = rl + u0 - off;
+        const double *tp = tab + (size_t)p * TAB;
+        double *yp = &y[(size_t)p * NR];
+        double c[IF_E] = {};
+        for (int s = meta[4 + P + p]; s <= meta[4 + 2 * P + p]; s++)
+            for (int j = 0; j < IF_E; j++)
+                for (int k = 0; k < IF_E; k++) c[j] = std::fma(tp[OQ + j * IF_E * P + s * IF_E + k], yI[(size_t)s * IF_E + k], c[j]);
+        for (int i = 0; i < NR; i++) {
+            double v = yp[i];
+            for (int j = 0; j < IF_E; j++) v = std::fma(tp[OZ + i * IF_E + j], c[j], v);
+            yp[i] = v;
+            if (i >= off && i < off + nt) a[row0 + i] = v;
+        }
+        if (p == 0) for (int q = 0; q < rl; q++) a[q] = g_l[q][0] * yp[0] + g_l[q][1] * yp[1];
+        if (p == P - 1) for (int q = 0; q < rr; q++) a[nb - 1 - q] = g_r[q][0] * yp[NR - 1] + g_r[q][1] * yp[NR - 2];
+    }
+}
+
+bool part_prepare(sx_handle *h) {
+    h->part_P = 0;
+    constexpr int P = PART_P, NR = PART_NR;
+    bool periodic = false;
+    for (const SplineClass &sc : h->classes) periodic |= sc.periodic != 0;
+    // the plan with the column count left open: a handle that can never take the kernel builds no tables
+    if (h->ncells != h->nc || !plan_solve_part(h->b_rDim, periodic, 1, INT64_MAX, h->sw)) return true;
+    const int PM = part_meta_ints(P), TAB = part_tab_doubles(P, NR);
+    std::vector<int> meta((size_t)h->ncls * PM);
+    std::vector<double> tab((size_t)h->ncls * P * TAB);
+    std::string err;
+    for (int c = 0; c < h->ncls; c++)
+        if (!part_tables_host(h->classes[c], h->b_rDim, P, NR, &meta[(size_t)c * PM], &tab[(size_t)c * P * TAB], err)) return true;   // keeps k_solve
+    void *dm = nullptr, *dt = nullptr;
+    if (hipMalloc(&dm, sizeof(int) * meta.size()) != hipSuccess || hipMalloc(&dt, sizeof(double) * tab.size()) != hipSuccess) {
+        if (dm) hipFree(dm);
+        set_error("hipMalloc failed (partitioned solve)");
+        return false;
+    }
+    h->allocs.push_back(dm);
+    h->allocs.push_back(dt);
+    h->dev_bytes += sizeof(int) * meta.size() + sizeof(double) * tab.size();
+    if (hipMemcpy(dm, meta.data(), sizeof(int) * meta.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dt, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("hipMemcpy H2D failed");
+        return false;
+    }
+    h->d_part_meta = (int *)dm;
+    h->d_part_tab = (double *)dt;
+    h->part_P = P;
+    return true;
+}
+
+// B, A: the window's first column of the contiguous [b_rDim][C] arrays; vz0: its first patch-level (variable, z-mode) group, ng groups
+void launch_solve_part(sx_handle *h, const double *B, double *A, int vz0, int ng) {
+    const int bx = h->K2 > 1 ? (h->K2 - 2 + 63) / 64 : 0;
+    hipLaunchKernelGGL((k_solve_part<PART_P, PART_NR>), dim3(bx + 1, ng), dim3(64 * PART_P), 0, h->stream, B, A, h->d_cls, h->d_part_meta, h->d_gl, h->d_gr,
+                       h->d_part_tab, h->b_rDim, h->Zb, h->K2, vz0, h->C);
+    HIPCHK(hipGetLastError());
+}
+
 }  // namespace sx
 
 using namespace sx;
 
 extern "C" {
+
+int sx_solve_part_check(int32_t num_cells, double xmin, double xmax, double l_q, int32_t bcl, int32_t bcr, int32_t parts, const double *b,
+                        double *a_part, double *a_chol, int32_t *ranges) {
+    clear_error();
+    if (!b || num_cells < 3 || !(xmax > xmin) || parts < 2 || parts > 16) { set_error("sx_solve_part_check: invalid argument"); return 1; }
+    SplineClass sc;
+    std::string err;
+    const int nb = num_cells + 3;
+    if (!build_spline_class(num_cells, (xmax - xmin) / num_cells, l_q > 0 ? l_q : 2.0, bcl, bcr, sc, err)) { set_error(err); return 1; }
+    const int NR = (sc.nfree + parts - 1) / parts;           // the smallest register array that holds every partition
+    std::vector<int> meta(part_meta_ints(parts));
+    std::vector<double> tab((size_t)parts * part_tab_doubles(parts, NR));
+    if (NR < IF_E || !part_tables_host(sc, nb, parts, NR, meta.data(), tab.data(), err)) { set_error(err.empty() ? "sx_solve_part_check: partitions too small" : err); return 1; }
+    if (a_part) part_apply_host(meta.data(), tab.data(), parts, NR, sc.gl, sc.gr, nb, b, a_part);
+    if (a_chol) cholesky_apply_host(sc, nb, b, a_chol);
+    if (ranges)
+        for (int p = 0; p < parts; p++) { ranges[2 * p] = meta[4 + parts + p]; ranges[2 * p + 1] = meta[4 + 2 * parts + p]; }
+    return 0;
+}
 
 int sx_iface_configure(sx_handle *h, int32_t n, int32_t me, const int32_t *cell0, const int32_t *ncells) {
     clear_error();

@@ -293,7 +293,9 @@ struct Switches {
     int sbw_t256 = 1;
     int sbw_seg = 0;        // SX_SBW_SEG=n: segments per (block group, variable) of the sliding-window kernels (experiments; <= 0: by size)
     int wide = 1;           // 16-byte-per-lane loads / stores in the equation-set kernels (SX_WIDE=0: the 8-byte forms, A/B timing)
-    int solve_pcr = -1;     // SX_SOLVE_PCR: 0 never, 1 wherever the tables exist, -1 by column count
+    // SX_SOLVE_PCR: 0 k_solve everywhere, 1 k_solve_pcr wherever its tables exist, 2 k_solve_part wherever its tables exist and k_solve
+    // elsewhere, -1 by the plans (plan_solve_part, pcr_wanted)
+    int solve_pcr = -1;
     int64_t pcr_maxcols = 16384;   // SX_PCR_MAXCOLS
     int pcr_r = 0;          // SX_PCR_R=n: columns per workgroup of k_solve_pcr (<= 0: by column count)
     int rz_fused = 1;       // RZ grids: the fused radius-on-the-matrix-cores kernels of sx_rz.hip (SX_RZ_FUSED=0: the general kernels)
@@ -336,6 +338,10 @@ ZinvPlan plan_zinv(int geometry, int nz, int K2, int sp32, const Switches &sw);
 // v_cnt: the window k_nodes_z covers; uniform_L: the ring table's uniform length, 0 for native rings
 CellsPlan plan_fwd_cells(int geometry, int nz, int Zb, int K2, int nvars, int v_cnt, int ncells, int sp32, int uniform_L, const Switches &sw);
 PcrPlan plan_pcr(int nblk_max, int b_rDim, int K2, int ngroups, const Switches &sw);
+// k_solve_part (sx_iface.hip): PART_P waves of a workgroup each own a block of at most PART_NR unknowns of the same 64 columns
+constexpr int PART_P = 4, PART_NR = 44;
+// partitions of the one-tile solve over ncols right-hand sides, 0 where the launch keeps k_solve / k_solve_pcr
+int plan_solve_part(int b_rDim, int periodic, int contiguous, int64_t ncols, const Switches &sw);
 std::string kernel_name(SbKernel k);      // "k_sbw_mfma<64, 32, 256>", ...; empty for `refused`
 std::string kernel_name(const ZinvPlan &p);   // "k_colmat_mfma<8, double, 4>", ...; empty for `none`
 
@@ -431,6 +437,11 @@ struct sx_handle {
     void *comm_state = nullptr;               // RCCL exchange state (sx_comm.cpp)
     void *iface_state = nullptr;              // interface-only patch solve (sx_iface.hip)
     void *pcr_state = nullptr;                // parallel-cyclic-reduction tables and launch lists (sx_pcr.hip)
+    // partitioned one-tile solve (k_solve_part, sx_iface.hip): tables of every class, built by sx_create where the plan can take them
+    int part_P = 0;                           // 0: no tables
+    int *d_part_meta = nullptr;
+    double *d_part_tab = nullptr;
+    bool last_solve_part = false;             // the last launch_solve took k_solve_part (sx_kernel_bytes)
     std::unique_ptr<sx::DiagState> diag[sx::DIAG_COUNT];   // states of the diagnostics entry points, made on first use (sx_eval.hip ... sx_parcels.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
@@ -549,6 +560,8 @@ void launch_semi_mfma(sx_handle *h, const SemiArgs &a);
 bool pcr_wanted(sx_handle *h, int64_t ncols);
 void launch_solve_pcr(sx_handle *h, bool linear, const double *Bsrc, const int64_t *boffA, const int64_t *boffB, double *A,
                       const int64_t *aoffA, const int64_t *aoffB, int vz0, int ng, int64_t stride);
+bool part_prepare(sx_handle *h);             // sx_create: the tables of k_solve_part where its plan can apply; false: an upload failed
+void launch_solve_part(sx_handle *h, const double *B, double *A, int vz0, int ng);
 bool tile_table_ok(const sx_handle *h, int n, int me, const int32_t *cell0, const int32_t *ncells);
 #ifdef SX_PHASES
 void phases_dump();

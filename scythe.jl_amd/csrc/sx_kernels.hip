@@ -1145,7 +1145,16 @@ void launch_solve(sx_handle *h) {
     // instead of one wave's serial recurrence per 64 columns
     const bool contiguous = (h->d_Bsrc == h->d_Bfull);
     const int ngroups = contiguous ? h->v_cnt * h->Zb : h->V * h->Zb;
-    if (pcr_wanted(h, (int64_t)ngroups * (h->K2 > 1 ? h->K2 - 1 : 1))) {
+    const int64_t ncols = (int64_t)ngroups * (h->K2 > 1 ? h->K2 - 1 : 1);
+    // contiguous, non-periodic, enough columns to fill the chip: row partitions in one workgroup, y on chip (k_solve_part, sx_iface.hip)
+    h->last_solve_part = h->part_P && plan_solve_part(h->b_rDim, 0, contiguous, ncols, h->sw) == h->part_P;
+    if (h->last_solve_part) {
+        const int64_t clo = (int64_t)h->v_lo * h->Zb * h->K2;
+        launch_solve_part(h, h->d_Bsrc + clo, h->d_A + clo, h->v_lo * h->Zb, ngroups);
+        timer_end(h);
+        return;
+    }
+    if (pcr_wanted(h, ncols)) {
         const int64_t clo = contiguous ? (int64_t)h->v_lo * h->Zb * h->K2 : 0;
         launch_solve_pcr(h, contiguous, h->d_Bsrc + clo, h->d_rowoff, h->d_neg1, h->d_A + clo, h->d_aoff, h->d_neg1,
                          contiguous ? h->v_lo * h->Zb : 0, ngroups, h->C);

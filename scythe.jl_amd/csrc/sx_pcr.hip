@@ -230,7 +230,7 @@ void pcr_release(sx_handle *h) {
 // forces the answer (1: wherever the tables exist); by default launches of up to SX_PCR_MAXCOLS (16384) columns do - above that the
 // lane-per-column kernel fills the chip and streams its rows at the HBM rate.
 bool pcr_wanted(sx_handle *h, int64_t ncols) {
-    if (h->sw.solve_pcr == 0) return false;
+    if (h->sw.solve_pcr == 0 || h->sw.solve_pcr == 2) return false;      // 2: k_solve_part where its plan takes it, k_solve elsewhere
     if (h->sw.solve_pcr != 1 && ncols > h->sw.pcr_maxcols) return false;
     return pcr_state(h)->ok;
 }

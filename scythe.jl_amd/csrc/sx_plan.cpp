@@ -111,6 +111,19 @@ PcrPlan plan_pcr(int nblk_max, int b_rDim, int K2, int ngroups, const Switches &
     return p;
 }
 
+// k_solve_part over `ncols` right-hand sides of the contiguous one-tile solve: the number of partitions, 0 where the launch keeps
+// k_solve / k_solve_pcr.  The interface form needs 9 cells per partition (a partition of a rank-3 class then owns 6 unknowns
+// or more), the register array holds PART_NR unknowns per partition (176 patch rows at most; the bench grid has 174), PERIODIC classes have
+// their corner blocks and keep k_solve.  By default only launches that PCR does not take and that give every SIMD of the chip
+// a wave (1024 waves of 64 columns, PART_P waves per workgroup); SX_SOLVE_PCR=2: wherever the tables exist.
+int plan_solve_part(int b_rDim, int periodic, int contiguous, int64_t ncols, const Switches &sw) {
+    const int P = PART_P, NR = PART_NR;
+    if (sw.solve_pcr == 0 || sw.solve_pcr == 1 || periodic || !contiguous) return 0;
+    if (b_rDim - 3 < 9 * P || b_rDim > P * NR) return 0;
+    if (sw.solve_pcr == 2) return P;
+    return sw.solve_pcr < 0 && ncols > sw.pcr_maxcols && ncols >= (int64_t)1024 * 64 / PART_P ? P : 0;
+}
+
 std::string kernel_name(SbKernel k) {
     static const char *const NAMES[] = {
         "", "k_sb", "k_sbz", "k_rz_forward", "k_sbw<32, false>", "k_sbw<32, true>", "k_sbw<64, false>", "k_sbw<64, true>", "k_sbw<128, false>",
