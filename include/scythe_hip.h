@@ -143,6 +143,12 @@ const char *sx_last_error(void);
 int sx_abi_version(void);
 /* getfield(Scythe, Symbol(equation_set)) (src/semiimplicit.jl:359-361): name -> SX_EQ_*, -1 if not in scope */
 int sx_equation_set_id(const char *name);
+
+/* The planes of `physical` an equation set reads, which are the planes sx_advance's inverse transform produces (sx_tile_transform
+ * produces all): masks[n_vars], bit d set where variable v's slot d (the geometry's slot order: u, r, rr, then l, ll and / or z, zz)
+ * is read; variables beyond the set's own read the value only; a mask of 0 is a variable the step does not transform back at all.
+ * Pure host helper, no handle needed. */
+int sx_equation_slot_masks(int32_t equation_set, int32_t geometry, int32_t n_vars, int32_t *masks);
 int sx_get_dims(const sx_handle *h, sx_dims *out);
 /* launch on this hipStream_t (NULL = default stream) */
 int sx_set_stream(sx_handle *h, void *hip_stream);
@@ -204,8 +210,23 @@ int sx_solve_part_check(int32_t num_cells, double xmin, double xmax, double l_q,
  *                    right-hand sides of the launch;  out = partitions (0: not the partitioned kernel), threads per workgroup;
  *                    kernel: "k_solve_part" where the launch takes it, else "k_solve" (or k_solve_pcr, where SX_PLAN_PCR's tables exist
  *                    and the column count is at most SX_PCR_MAXCOLS)
+ *   SX_PLAN_RZ_INVERSE  tileTransform! on a fused RZ grid (b_zDim <= zDim <= 256):  in = zDim, b_zDim, tile cells, variables,
+ *                    storage_f32 (0 / 1);  out = grid x, grid y, grid z, dynamic LDS bytes, K chunks, 1 where the launch first raises
+ *                    the kernel's dynamic-LDS limit above 64 KB;  kernel: "k_rz_inverse_nodes<double | float>" - grid x = ceil(cells / 13),
+ *                    LDS = 8 (16 Zp + 3 * 16 * 65 + 3 * 39 * 4) bytes with Zp = b_zDim rounded up to its chunks of 32 rows - or, with
+ *                    SX_RZ_INV=0 or where that LDS exceeds 64 KB, "k_rz_inverse<double | float>": grid x = ceil(3 cells / 16),
+ *                    LDS = 8 * 3 * 16 Zp bytes with chunks of 64 rows.  Both: grid y = variables, grid z = ceil(ceil(zDim / 16) / 4)
+ *   SX_PLAN_RZ_FORWARD  spectralTransform! on a fused RZ grid:  in = zDim, b_zDim, tile cells, variables in the window;
+ *                    out = grid x = ceil((cells + 3) / 16), grid y = variables, grid z = ceil(nmt / mt_per_wg), mt_per_wg = min(nmt, 4)
+ *                    with nmt = ceil(b_zDim / 16), K chunks = ceil(zDim / 64), LDS = 8 (16 * 64 chunks + 19 * 3 * 4) bytes;  kernel: "k_rz_forward"
+ *   SX_PLAN_SEMI     the semi-implicit adjustment:  in = zDim, columns;  out = workgroups, threads, level tiles per wave trip, K chunks,
+ *                    dynamic LDS bytes, 1 where the launch first raises the kernel's dynamic-LDS limit above 64 KB;  kernel: "k_semi_mfma" -
+ *                    workgroups = ceil(columns / 16), threads = 64 min(8, ceil(zDim / 16)), that many level tiles per trip, K chunks =
+ *                    ceil(zDim / 64), LDS = 8 * 4 * 16 * 64 chunks bytes - or, with SX_SEMI_MFMA=0, "k_semiimplicit": cpb = max(1, 256 / zDim)
+ *                    columns per workgroup, workgroups = ceil(columns / cpb), threads = cpb zDim, LDS = 8 * 3 threads bytes, 0 tiles and chunks
  * Pure host helper (no handle, no device): the tests name the launch shapes they cover from it; never on the step path. */
-enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2, SX_PLAN_FORWARD_CELLS = 3, SX_PLAN_SOLVE = 4 };
+enum { SX_PLAN_FORWARD = 0, SX_PLAN_ZINV = 1, SX_PLAN_PCR = 2, SX_PLAN_FORWARD_CELLS = 3, SX_PLAN_SOLVE = 4, SX_PLAN_RZ_INVERSE = 5,
+       SX_PLAN_RZ_FORWARD = 6, SX_PLAN_SEMI = 7 };
 int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap);
 
 /* The work lists of the native-ring DFT launches (csrc/sx_dft.hip) of a tile of cells cell0 .. cell0 + num_cells - 1 with Springsteel's

@@ -463,11 +463,19 @@ class Grid:
         return phys
 
 
-def inverse_xp(grid, A, rings, cell0=0):
+def inverse_xp(grid, A, rings, cell0=0, with_scale=False, exact_offsets=False):
     """tileTransform! for the listed patch rings in EXTENDED precision (numpy longdouble) from Float64 A coefficients and
     Float64 gridpoints: the arbiter for "which fp64 evaluation of a derivative slot is closer to the exact one".
-    Returns {ring: phys[L * zDim, V, D]} (longdouble).  Dense and slow on purpose; pass a sample of rings."""
+    Returns {ring: phys[L * zDim, V, D]} (longdouble).  Dense and slow on purpose; pass a sample of rings (on RZ grids, where a
+    ring is one column, all of them cost milliseconds).
+    with_scale = True: (phys, scale), scale[ring][point, v, slot] the same chain evaluated over absolute values,
+    sum_zm |M_sz[z, zm]| sum_blocks |FI| sum_j |phi_d[ring, j]| |A[node + j, v, zm]|: the per-entry condition scale an fp64
+    evaluation of the slot is rounded against (any summation order of its b_zDim + 4 terms, forward_xp's rule).
+    exact_offsets = True: the basis weights at the exact Gauss offsets of the ring inside its cell, delta_j = 3/2 + offset - j, as
+    forward_xp takes them and as a table built once per grid holds them - not at the Float64 gridpoint, whose rounding is
+    (r / DX) 2^-53 in delta and grows with the cell index."""
     g = grid
+    scales = {}
     sl = {s_: i for i, s_ in enumerate(g.slots)}
     out = {}
     xm = XP(g.xmin) + (np.arange(g.b_rDim, dtype=XP) - 1) * XP(g.DX)
@@ -476,6 +484,9 @@ def inverse_xp(grid, A, rings, cell0=0):
         r64 = mish_points(g.xmin, g.DX, c, 1)[ring % MUBAR]                   # the Float64 gridpoint, as handed to the user
         n0 = c                                                                # the 4 spline nodes that overlap this ring's cell: c .. c + 3
         delta = ((XP(r64) - xm[n0:n0 + 4]) / XP(g.DX))[None, :]
+        if exact_offsets:
+            goff = (XP(-1), XP(0), XP(1))[ring % MUBAR] * np.sqrt(XP(3) / XP(5)) / 2
+            delta = (XP(1.5) + goff - np.arange(4, dtype=XP))[None, :]
         PH = [bspline(delta, d)[0] / XP(g.DX) ** d for d in range(3)]        # [4]
         L, km = int(g.L[ring]), int(g.kmax[ring])
         nb = 1 + 2 * km
@@ -488,6 +499,7 @@ def inverse_xp(grid, A, rings, cell0=0):
             FI[1][:, 2 * k - 1], FI[1][:, 2 * k] = -2 * k * sn, -2 * k * cs
             FI[2][:, 2 * k - 1], FI[2][:, 2 * k] = -2 * k * k * cs, 2 * k * k * sn
         phys = np.zeros((L * g.zDim, g.V, g.D), dtype=XP)
+        scale = np.zeros_like(phys) if with_scale else None
         for vi, v in enumerate(g.names):
             Av = A[:, vi].reshape(g.b_zDim, g.K2, -1)[:, :nb, n0:n0 + 4].astype(XP)      # only what this ring reads
             if g.has_z:
@@ -499,15 +511,20 @@ def inverse_xp(grid, A, rings, cell0=0):
                     if sname not in sl:
                         continue
                     f = coef @ FI[ld].T                                       # [zm, lambda]
-                    if g.has_z:
-                        phys[:, vi, sl[sname]] = (Mx[0] @ f).T.reshape(-1)
-                        if sname == "u":
-                            phys[:, vi, sl["z"]] = (Mx[1] @ f).T.reshape(-1)
-                            phys[:, vi, sl["zz"]] = (Mx[2] @ f).T.reshape(-1)
-                    else:
-                        phys[:, vi, sl[sname]] = f.T.reshape(-1)
+                    targets = [(phys, f, lambda m: m)]
+                    if with_scale:
+                        targets.append((scale, (np.abs(Av) @ np.abs(PH[d])) @ np.abs(FI[ld]).T, np.abs))
+                    for dst, ff, fn in targets:
+                        if g.has_z:
+                            dst[:, vi, sl[sname]] = (fn(Mx[0]) @ ff).T.reshape(-1)
+                            if sname == "u":
+                                dst[:, vi, sl["z"]] = (fn(Mx[1]) @ ff).T.reshape(-1)
+                                dst[:, vi, sl["zz"]] = (fn(Mx[2]) @ ff).T.reshape(-1)
+                        else:
+                            dst[:, vi, sl[sname]] = ff.T.reshape(-1)
         out[ring] = phys
-    return out
+        scales[ring] = scale
+    return (out, scales) if with_scale else out
 
 
 def forward_xp(grid, values, cell0=0, ncells=None):
@@ -1188,6 +1205,7 @@ class Model:
                 unp1 = self._semiimplicit(i, t, unp1, I)
             if self.eq == "rainfall_test":
                 unp1 = condensation_adjustment(unp1, self.par, g.zDim, self.elementwise)
+            hs["np1"] = unp1                                                 # var_np1 of the step, kept for comparisons
             b = g.forward(unp1, c0, n)                                       # calcTendency
             g.add_tile_to_shared(shared, b, c0, n, i == len(self.tiles) - 1)
         self.A = g.spline_transform(shared)                                  # splineTransform!

@@ -65,6 +65,7 @@ SYMBOLS = {
     "sx_last_error": (C.c_char_p, []),
     "sx_abi_version": (C.c_int, []),
     "sx_equation_set_id": (C.c_int, [C.c_char_p]),
+    "sx_equation_slot_masks": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P_I32]),
     "sx_get_dims": (C.c_int, [_H, C.POINTER(Dims)]),
     "sx_set_stream": (C.c_int, [_H, C.c_void_p]),
     "sx_synchronize": (C.c_int, [_H]),

@@ -264,6 +264,27 @@ extern "C" {
 const char *sx_last_error(void) { return g_err.c_str(); }
 int sx_abi_version(void) { return SX_ABI_VERSION; }
 
+// the derivative slots of the geometry that variable v of the set reads: bit = slot index (DERIV_SLOTS)
+static int eq_slot_mask(const EqSet &es, int geom, int v) {
+    const int kinds = v < es.min_vars ? es.kinds[v] : KU;
+    int m = 0;
+    for (int k = 0; k < 7; k++)
+        if ((kinds >> k & 1) && DERIV_SLOTS[geom][k] >= 0) m |= 1 << DERIV_SLOTS[geom][k];
+    return m;
+}
+
+int sx_equation_slot_masks(int32_t equation_set, int32_t geometry, int32_t n_vars, int32_t *masks) {
+    clear_error();
+    if (!masks || n_vars < 1 || geometry < SX_GEOM_R || geometry > SX_GEOM_RLZ) { set_error("sx_equation_slot_masks: invalid argument"); return 1; }
+    for (const EqSet &e : EQ_SETS)
+        if (e.id == equation_set) {
+            for (int v = 0; v < n_vars; v++) masks[v] = eq_slot_mask(e, geometry, v);
+            return 0;
+        }
+    set_error("sx_equation_slot_masks: unknown equation set " + std::to_string(equation_set));
+    return 1;
+}
+
 int sx_equation_set_id(const char *name) {
     if (name)
         for (const EqSet &e : EQ_SETS)
@@ -624,11 +645,7 @@ int sx_create(const sx_grid_desc *g, const sx_model_desc *m, sx_handle **out) {
         const int l = h->has_l ? 1 << h->slot[3] : 0, ll = h->has_l ? 1 << h->slot[4] : 0;
         const int z = h->has_z ? 1 << h->slot[5] : 0, zz = h->has_z ? 1 << h->slot[6] : 0;
         std::vector<int> full(h->V, (1 << h->D) - 1), eq(h->V);
-        for (int v = 0; v < h->V; v++) {
-            const int kinds = v < es->min_vars ? es->kinds[v] : KU;
-            for (int k = 0; k < 7; k++)
-                if ((kinds >> k & 1) && h->slot[k] >= 0) eq[v] |= 1 << h->slot[k];
-        }
+        for (int v = 0; v < h->V; v++) eq[v] = eq_slot_mask(*es, h->geom, v);
         for (int v = 0; v < h->V; v++) {
             h->mask_full_bits += __builtin_popcount(full[v]);
             h->mask_eq_bits += __builtin_popcount(eq[v]);
@@ -800,9 +817,11 @@ int sx_spline_solve_check(int32_t num_cells, double xmin, double xmax, double l_
 int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, int32_t kernel_cap) {
     clear_error();
     if (!in || !out) { set_error("sx_launch_plan: null argument"); return 1; }
-    if (kind != SX_PLAN_FORWARD && kind != SX_PLAN_ZINV && kind != SX_PLAN_PCR && kind != SX_PLAN_FORWARD_CELLS && kind != SX_PLAN_SOLVE) { set_error("sx_launch_plan: unknown kind " + std::to_string(kind)); return 1; }
+    if (kind < SX_PLAN_FORWARD || kind > SX_PLAN_SEMI) { set_error("sx_launch_plan: unknown kind " + std::to_string(kind)); return 1; }
     // the dimensions among the inputs (not the geometry in front, not the fp32 flag at the end) divide: positive
-    const int first = (kind == SX_PLAN_PCR || kind == SX_PLAN_SOLVE) ? 0 : 1, last = (kind == SX_PLAN_FORWARD || kind == SX_PLAN_FORWARD_CELLS) ? 6 : kind == SX_PLAN_ZINV ? 3 : 4;
+    const bool rzk = kind == SX_PLAN_RZ_INVERSE || kind == SX_PLAN_RZ_FORWARD || kind == SX_PLAN_SEMI;
+    const int first = (kind == SX_PLAN_PCR || kind == SX_PLAN_SOLVE || rzk) ? 0 : 1;
+    const int last = (kind == SX_PLAN_FORWARD || kind == SX_PLAN_FORWARD_CELLS) ? 6 : kind == SX_PLAN_ZINV ? 3 : kind == SX_PLAN_SEMI ? 2 : 4;
     for (int i = first; i < last; i++)
         if (in[i] < 1) { set_error("sx_launch_plan: dimensions must be positive"); return 1; }
     const Switches sw = read_switches();
@@ -821,6 +840,23 @@ int sx_launch_plan(int32_t kind, const int32_t *in, int32_t *out, char *kernel, 
         const ZinvPlan p = plan_zinv(in[0], in[1], in[2], in[3], sw);
         name = kernel_name(p);
         out[0] = p.CT; out[1] = p.grid_x;
+    } else if (kind == SX_PLAN_RZ_INVERSE) {
+        if (in[1] > in[0] || in[0] > 256) { set_error("sx_launch_plan: the fused RZ kernels take b_zDim <= zDim <= 256"); return 1; }
+        const RzInvPlan p = plan_rz_inverse(in[0], in[1], in[2], in[3], in[4], sw);
+        name = kernel_name(p);
+        const int32_t o[6] = {p.gx, p.gy, p.gz, p.lds, p.chunks, p.attr ? 1 : 0};
+        std::copy(o, o + 6, out);
+    } else if (kind == SX_PLAN_RZ_FORWARD) {
+        if (in[1] > in[0] || in[0] > 256) { set_error("sx_launch_plan: the fused RZ kernels take b_zDim <= zDim <= 256"); return 1; }
+        const RzFwdPlan p = plan_rz_forward(in[0], in[1], in[2], in[3]);
+        name = "k_rz_forward";
+        const int32_t o[6] = {p.gx, p.gy, p.gz, p.mt_per_wg, p.chunks, p.lds};
+        std::copy(o, o + 6, out);
+    } else if (kind == SX_PLAN_SEMI) {
+        const SemiPlan p = plan_semi(in[0], in[1], sw);
+        name = p.mfma ? "k_semi_mfma" : "k_semiimplicit";
+        const int32_t o[6] = {p.wgs, p.threads, p.tiles_per_trip, p.chunks, p.lds, p.attr ? 1 : 0};
+        std::copy(o, o + 6, out);
     } else if (kind == SX_PLAN_SOLVE) {
         const int P = plan_solve_part(in[0], in[1] - 1, in[2] - 1, in[3], sw);
         name = P ? "k_solve_part" : "k_solve";

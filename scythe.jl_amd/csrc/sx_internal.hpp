@@ -342,7 +342,31 @@ PcrPlan plan_pcr(int nblk_max, int b_rDim, int K2, int ngroups, const Switches &
 constexpr int PART_P = 4, PART_NR = 44;
 // partitions of the one-tile solve over ncols right-hand sides, 0 where the launch keeps k_solve / k_solve_pcr
 int plan_solve_part(int b_rDim, int periodic, int contiguous, int64_t ncols, const Switches &sw);
+// The fused RZ kernels and the semi-implicit column solve (sx_rz.hip): one MFMA row tile of RZ_T rings / nodes / columns per workgroup,
+// operator fragments of RZ_KC K steps (4 rows each) in registers at once, RZ_CT = RZ_T - 3 cells per workgroup of the nodes form
+constexpr int RZ_T = 16, RZ_KC = 16, RZ_CT = RZ_T - 3;
+constexpr int RZ_NODES_KC = 8, RZ_NODES_ZS = 65;       // k_rz_inverse_nodes: K steps per chunk, row stride of its Az tile (64 levels + 1)
+constexpr int LDS_DEFAULT_MAX = 65536;                 // dynamic LDS a kernel may ask for without hipFuncAttributeMaxDynamicSharedMemorySize
+struct RzInvPlan {       // tileTransform! on a fused RZ grid
+    bool nodes = true, f32 = false;       // k_rz_inverse_nodes<ST> (13 cells per workgroup) or k_rz_inverse<ST> (16 rings); ST = float / double
+    int gx = 0, gy = 0, gz = 0;           // ceil(cells / 13) or ceil(rings / 16); variables; groups of 4 level tiles (one per wave)
+    int lds = 0, chunks = 0;              // dynamic LDS bytes; K chunks of 32 (nodes form) or 64 (ring-tile form) coefficient rows
+    bool attr = false;                    // the launch raises the kernel's dynamic-LDS limit first (lds > LDS_DEFAULT_MAX)
+};
+struct RzFwdPlan { int gx = 0, gy = 0, gz = 0, mt_per_wg = 0, chunks = 0, lds = 0; };   // k_rz_forward: ceil(nodes / 16), variables, mode-tile groups
+struct SemiPlan {        // semiimplicit_adjustment
+    bool mfma = true;                     // k_semi_mfma (16 columns per workgroup) or k_semiimplicit (256 / zDim columns, at least 1)
+    int wgs = 0, threads = 0;
+    int tiles_per_trip = 0;               // k_semi_mfma: waves = level tiles taken per trip of its `kt += nw` loops; 0 for k_semiimplicit
+    int chunks = 0, lds = 0;              // k_semi_mfma: K chunks of 64 levels; dynamic LDS bytes
+    bool attr = false;
+    int cpb = 0;                          // k_semiimplicit: columns per workgroup
+};
+RzInvPlan plan_rz_inverse(int nz, int Zb, int ncells, int V, int f32, const Switches &sw);
+RzFwdPlan plan_rz_forward(int nz, int Zb, int ncells, int v_cnt);
+SemiPlan plan_semi(int nz, int64_t ncol, const Switches &sw);
 std::string kernel_name(SbKernel k);      // "k_sbw_mfma<64, 32, 256>", ...; empty for `refused`
+std::string kernel_name(const RzInvPlan &p);  // "k_rz_inverse_nodes<double>", "k_rz_inverse<float>", ...
 std::string kernel_name(const ZinvPlan &p);   // "k_colmat_mfma<8, double, 4>", ...; empty for `none`
 
 struct Timer {

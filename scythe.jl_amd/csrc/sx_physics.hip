@@ -1221,12 +1221,9 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
         s.MrecT = h->d_MrecT; s.MdzT = h->d_MdzT; s.WT = h->d_WT[which]; s.XT = h->d_XT[which];
         s.N = h->N; s.nz = h->nz; s.t = t; s.wi = h->w_index - 1; s.xi = h->xi_index - 1;
         s.ts = h->ts; s.tau = h->tau[which]; s.pxi = h->par[SX_P_PXI_BAR];
-        if (h->sw.semi_mfma) launch_semi_mfma(h, s);       // the four column operators on the matrix cores (sx_rz.hip)
-        else {
-            const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
-            const size_t lds = sizeof(double) * 3 * cpb * h->nz;
-            hipLaunchKernelGGL(k_semiimplicit, grid1(h->Nh, cpb), dim3(cpb * h->nz), lds, h->stream, s, cpb);
-        }
+        const SemiPlan sp = plan_semi(h->nz, h->Nh, h->sw);
+        if (sp.mfma) launch_semi_mfma(h, s);               // the four column operators on the matrix cores (sx_rz.hip)
+        else hipLaunchKernelGGL(k_semiimplicit, dim3((unsigned)sp.wgs), dim3(sp.threads), (size_t)sp.lds, h->stream, s, sp.cpb);
         HIPCHK(hipGetLastError());
         timer_end(h);
     }

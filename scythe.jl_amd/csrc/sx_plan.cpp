@@ -1,5 +1,5 @@
 // Launch plans: which kernel instantiation and which grid a launcher takes, as pure functions of plain integers and the
-// switches.  No handle, no device: the launchers (sx_kernels.hip, sx_pcr.hip) dispatch on these, and sx_launch_plan returns
+// switches.  No handle, no device: the launchers (sx_kernels.hip, sx_pcr.hip, sx_rz.hip) dispatch on these, and sx_launch_plan returns
 // them to a caller without a GPU, so the tests name the launch shapes from the same arithmetic that launches them.
 #include "sx_internal.hpp"
 #include <algorithm>
@@ -122,6 +122,78 @@ int plan_solve_part(int b_rDim, int periodic, int contiguous, int64_t ncols, con
     if (b_rDim - 3 < 9 * P || b_rDim > P * NR) return 0;
     if (sw.solve_pcr == 2) return P;
     return sw.solve_pcr < 0 && ncols > sw.pcr_maxcols && ncols >= (int64_t)1024 * 64 / PART_P ? P : 0;
+}
+
+// tileTransform! on a fused RZ grid.  Nodes form (default): workgroup = 13 cells (the 16 nodes they touch) x variable x 4 level tiles;
+// LDS = the A rows [Zp][16] (Zp = b_zDim rounded up to chunks of 32 rows), the Az tile [3][16][65] and the weights [3][39][4].  It is
+// taken while that fits the default dynamic-LDS limit; else, and with SX_RZ_INV=0, the ring-tile form: 16 rings per workgroup,
+// LDS = [3][Zp][16] with chunks of 64 rows, above 64 KB (b_zDim >= 129) with the kernel's limit raised first.
+RzInvPlan plan_rz_inverse(int nz, int Zb, int ncells, int V, int f32, const Switches &sw) {
+    RzInvPlan p;
+    p.f32 = f32 != 0;
+    p.gy = V;
+    p.gz = ((nz + 15) / 16 + 3) / 4;
+    constexpr int CHN = 4 * RZ_NODES_KC, CH = 4 * RZ_KC;
+    const int Zpn = (Zb + CHN - 1) / CHN * CHN;
+    const size_t ldsn = sizeof(double) * ((size_t)Zpn * RZ_T + 3 * RZ_T * RZ_NODES_ZS + 3 * RZ_CT * MUBAR * 4);
+    if (sw.rz_inv && ldsn <= (size_t)LDS_DEFAULT_MAX) {
+        p.gx = (ncells + RZ_CT - 1) / RZ_CT;
+        p.lds = (int)ldsn;
+        p.chunks = Zpn / CHN;
+        return p;
+    }
+    const int Zp = (Zb + CH - 1) / CH * CH;
+    p.nodes = false;
+    p.gx = (ncells * MUBAR + RZ_T - 1) / RZ_T;
+    p.lds = (int)(sizeof(double) * 3 * Zp * RZ_T);
+    p.chunks = Zp / CH;
+    p.attr = p.lds > LDS_DEFAULT_MAX;
+    return p;
+}
+
+// spectralTransform! on a fused RZ grid: workgroup = 16 nodes x variable x group of mt_per_wg tiles of 16 modes (one tile per wave:
+// more workgroups beat fewer restagings at this size); LDS = the radial inner products [Np][16] (Np = zDim rounded up to chunks of
+// 64 levels) and the weights of the 19 cells around the node tile [57][4]
+RzFwdPlan plan_rz_forward(int nz, int Zb, int ncells, int v_cnt) {
+    RzFwdPlan p;
+    constexpr int CH = 4 * RZ_KC;
+    const int Np = (nz + CH - 1) / CH * CH, nmt = (Zb + 15) / 16;
+    p.mt_per_wg = std::min(nmt, 4);
+    p.gx = (ncells + 3 + RZ_T - 1) / RZ_T;
+    p.gy = v_cnt;
+    p.gz = (nmt + p.mt_per_wg - 1) / p.mt_per_wg;
+    p.chunks = Np / CH;
+    p.lds = (int)(sizeof(double) * ((size_t)Np * RZ_T + 19 * MUBAR * 4));
+    return p;
+}
+
+// semiimplicit_adjustment over ncol columns.  k_semi_mfma: 16 columns per workgroup, one wave per tile of 16 levels up to 8 waves (above
+// 128 levels a wave takes a second tile), LDS = four [Kp][16] column tiles (Kp = zDim rounded up to chunks of 64 levels), above 64 KB
+// (zDim > 128) with the kernel's limit raised first.  SX_SEMI_MFMA=0: k_semiimplicit, 256 / zDim whole columns per workgroup (at
+// least one), a thread per level, LDS = three columns each.
+SemiPlan plan_semi(int nz, int64_t ncol, const Switches &sw) {
+    SemiPlan p;
+    p.mfma = sw.semi_mfma != 0;
+    if (!p.mfma) {
+        p.cpb = nz >= 256 ? 1 : 256 / nz;
+        p.wgs = (int)((ncol + p.cpb - 1) / p.cpb);
+        p.threads = p.cpb * nz;
+        p.lds = (int)(sizeof(double) * 3 * p.cpb * nz);
+        return p;
+    }
+    constexpr int CH = 4 * RZ_KC;
+    const int Kp = (nz + CH - 1) / CH * CH, nzt = (nz + 15) / 16;
+    p.wgs = (int)((ncol + RZ_T - 1) / RZ_T);
+    p.tiles_per_trip = std::min(8, nzt);
+    p.threads = 64 * p.tiles_per_trip;
+    p.chunks = Kp / CH;
+    p.lds = (int)(sizeof(double) * 4 * Kp * RZ_T);
+    p.attr = p.lds > LDS_DEFAULT_MAX;
+    return p;
+}
+
+std::string kernel_name(const RzInvPlan &p) {
+    return std::string(p.nodes ? "k_rz_inverse_nodes<" : "k_rz_inverse<") + (p.f32 ? "float" : "double") + ">";
 }
 
 std::string kernel_name(SbKernel k) {

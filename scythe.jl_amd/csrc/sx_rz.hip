@@ -20,8 +20,9 @@
 namespace sx {
 
 typedef double rz_d4 __attribute__((ext_vector_type(4)));
-constexpr int RZ_T = 16;          // rings (inverse) / nodes (forward) per workgroup: one MFMA row tile
-constexpr int RZ_KC = 16;         // K steps whose operator fragments are in registers at once (32 VGPRs)
+// RZ_T = 16 rings (inverse) / nodes (forward) per workgroup: one MFMA row tile; RZ_KC = 16 K steps whose operator fragments are in
+// registers at once (32 VGPRs).  The tile constants are stated once in sx_internal.hpp; the launchers take grid and LDS bytes from
+// sx_plan.cpp, and the kernels round their K extents (Zp, Np, Kp) up to whole chunks by the same rule, from the same constants.
 
 // One MFMA pass of the inverse: NA accumulators (the radial sums at LDS offsets aoff[]) against ONE vertical operator, K in chunks of
 // RZ_KC steps whose operator fragments are requested together; no predicate anywhere in it - the LDS rows beyond b_zDim are zero
@@ -125,7 +126,7 @@ k_rz_inverse(const double *__restrict__ Arows /* tile rows [nbt][C] */, Planes<S
 // read); the result goes back to LDS and the same wave evaluates the 39 rings of the 13 cells from it - 4-term sums with the basis
 // weights, value / d/dr / d2/dr2 from the "value" operator, d/dz and d2/dz2 from the other two - writing 128-byte level runs.
 // 96 instead of 160 MFMAs per wave and a third of the workgroups of the ring-tile form above (k_rz_inverse, kept for SX_RZ_INV=0).
-constexpr int RZ_CT = RZ_T - 3;       // cells per workgroup: their rings need nodes c .. c + 3, i.e. 16 nodes in all
+// RZ_CT = RZ_T - 3 cells per workgroup: their rings need nodes c .. c + 3, i.e. 16 nodes in all
 
 template <int NB, int KC>
 __device__ __forceinline__ void rz_ops_pass(const double *__restrict__ sa, const double *const (&op)[3], int64_t rs, int nrows, int nchunks,
@@ -157,7 +158,7 @@ k_rz_inverse_nodes(const double *__restrict__ Arows /* tile rows [nbt][C] */, Pl
     const int mask = slotmask[v];
     const bool n_u = (mask >> s_u) & 1, n_r = (mask >> s_r) & 1, n_rr = (mask >> s_rr) & 1, n_z = (mask >> s_z) & 1, n_zz = (mask >> s_zz) & 1;
     if (!(n_u || n_r || n_rr || n_z || n_zz)) return;
-    constexpr int KC = 8, CH = 4 * KC, ZS = 65;          // Az row stride: 64 levels per workgroup + 1
+    constexpr int KC = RZ_NODES_KC, CH = 4 * KC, ZS = RZ_NODES_ZS;   // Az row stride: 64 levels per workgroup + 1
     const int Zp = (Zb + CH - 1) / CH * CH, nchunks = Zp / CH;
     const int nrings = ncells * MUBAR;
     double *sA = sm;                                     // [Zp][16]          A rows of the 16 nodes, zero beyond b_zDim / the tile
@@ -404,12 +405,9 @@ k_semi_mfma(SemiArgs a, int64_t ncol) {
 }
 
 void launch_semi_mfma(sx_handle *h, const SemiArgs &a) {
-    const int Kp = (h->nz + 4 * RZ_KC - 1) / (4 * RZ_KC) * (4 * RZ_KC);
-    const size_t lds = sizeof(double) * 4 * Kp * RZ_T;
-    if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_semi_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int nzt = (h->nz + 15) / 16;
-    const int threads = 64 * std::min(8, nzt);
-    hipLaunchKernelGGL(k_semi_mfma, dim3((unsigned)((h->Nh + RZ_T - 1) / RZ_T)), dim3(threads), lds, h->stream, a, h->Nh);
+    const SemiPlan p = plan_semi(h->nz, h->Nh, h->sw);
+    if (p.attr) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_semi_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+    hipLaunchKernelGGL(k_semi_mfma, dim3((unsigned)p.wgs), dim3(p.threads), (size_t)p.lds, h->stream, a, h->Nh);
 }
 
 bool rz_fused(const sx_handle *h) { return h->sw.rz_fused && h->geom == SX_GEOM_RZ && !h->sp32; }
@@ -417,29 +415,23 @@ bool rz_fused(const sx_handle *h) { return h->sw.rz_fused && h->geom == SX_GEOM_
 void launch_rz_inverse(sx_handle *h, const int *d_mask) {
     const int id = timer_id(h, "k_rz_inverse");
     timer_begin(h, id);
-    if (h->sw.rz_inv) {      // A/B: 0 = the ring-tile form
-        const int Zpn = (h->Zb + 31) / 32 * 32;
-        dim3 gn((h->ncells + RZ_CT - 1) / RZ_CT, h->V, ((h->nz + 15) / 16 + 3) / 4);
-        const size_t ldsn = sizeof(double) * ((size_t)Zpn * RZ_T + 3 * RZ_T * 65 + 3 * RZ_CT * MUBAR * 4);
-        const double *arows = h->d_A + (int64_t)h->cell0 * h->C;
-#define RZ_INVN(ST) hipLaunchKernelGGL(k_rz_inverse_nodes<ST>, gn, dim3(256), ldsn, h->stream, arows, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_MzT, \
-                                       d_mask, h->V, h->nz, h->Zb, h->ncells, h->nbt, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
-        if (ldsn <= 65536) {
-            if (h->f32) RZ_INVN(float); else RZ_INVN(double);
-            HIPCHK(hipGetLastError());
-            timer_end(h);
-            return;
-        }
-#undef RZ_INVN
-    }
-    const int Zp = (h->Zb + 4 * RZ_KC - 1) / (4 * RZ_KC) * (4 * RZ_KC);
-    dim3 g((h->nrings + RZ_T - 1) / RZ_T, h->V, ((h->nz + 15) / 16 + 3) / 4);
-    const size_t lds = sizeof(double) * 3 * Zp * RZ_T;
-    if (lds > 65536) {
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    const RzInvPlan p = plan_rz_inverse(h->nz, h->Zb, h->ncells, h->V, h->f32, h->sw);      // SX_RZ_INV=0 (A/B): the ring-tile form
+    const dim3 g(p.gx, p.gy, p.gz);
+    const size_t lds = (size_t)p.lds;
     const double *arows = h->d_A + (int64_t)h->cell0 * h->C;
+    if (p.nodes) {
+#define RZ_INVN(ST) hipLaunchKernelGGL(k_rz_inverse_nodes<ST>, g, dim3(256), lds, h->stream, arows, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_MzT, \
+                                       d_mask, h->V, h->nz, h->Zb, h->ncells, h->nbt, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
+        if (h->f32) RZ_INVN(float); else RZ_INVN(double);
+#undef RZ_INVN
+        HIPCHK(hipGetLastError());
+        timer_end(h);
+        return;
+    }
+    if (p.attr) {
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<double>), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_rz_inverse<float>), hipFuncAttributeMaxDynamicSharedMemorySize, p.lds));
+    }
 #define RZ_INV(ST) hipLaunchKernelGGL(k_rz_inverse<ST>, g, dim3(256), lds, h->stream, arows, planes_of<ST>(h->d_phys, h->V, h->N), h->d_phi, h->d_MzT, \
                                       d_mask, h->V, h->nz, h->Zb, h->nrings, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
     if (h->f32) RZ_INV(float); else RZ_INV(double);
@@ -451,12 +443,9 @@ void launch_rz_inverse(sx_handle *h, const int *d_mask) {
 void launch_rz_forward(sx_handle *h) {
     const int id = timer_id(h, "k_rz_forward");
     timer_begin(h, id);
-    const int Np = (h->nz + 4 * RZ_KC - 1) / (4 * RZ_KC) * (4 * RZ_KC), nmt = (h->Zb + 15) / 16;
-    const int mt_per_wg = std::min(nmt, 4);              // one 16-mode tile per wave; more workgroups beat fewer restagings at this size
-    dim3 g((h->nbt + RZ_T - 1) / RZ_T, h->v_cnt, (nmt + mt_per_wg - 1) / mt_per_wg);
-    const size_t lds = sizeof(double) * (Np * RZ_T + 19 * MUBAR * 4);
-    hipLaunchKernelGGL(k_rz_forward, g, dim3(256), lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N, h->d_Btile + (int64_t)h->v_lo * h->Zb,
-                       h->d_phi, h->d_wq, h->d_CBT, h->ncells, h->nbt, h->V, h->nz, h->Zb, h->N, h->C, mt_per_wg);
+    const RzFwdPlan p = plan_rz_forward(h->nz, h->Zb, h->ncells, h->v_cnt);
+    hipLaunchKernelGGL(k_rz_forward, dim3(p.gx, p.gy, p.gz), dim3(256), (size_t)p.lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
+                       h->d_Btile + (int64_t)h->v_lo * h->Zb, h->d_phi, h->d_wq, h->d_CBT, h->ncells, h->nbt, h->V, h->nz, h->Zb, h->N, h->C, p.mt_per_wg);
     HIPCHK(hipGetLastError());
     timer_end(h);
 }

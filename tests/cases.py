@@ -485,7 +485,7 @@ def sb_launch_geometry(case, env=None, storage="f64", tile=None, v_cnt=None):
     if not kernel:
         return dict(kernel=None, refused="storage_f32 = 2", ncells=ncells, K2=K2)       # sx_create refuses the handle
     if kernel == "k_rz_forward":
-        return dict(kernel=kernel, ncells=ncells, K2=K2)
+        return dict(rz_forward_launch_geometry(case, tile, v_cnt), K2=K2)
     if kernel == "k_sb":
         return dict(kernel=kernel, threads=threads, ncells=ncells, K2=K2)
     if kernel == "k_sbz":
@@ -519,6 +519,103 @@ def zinv_launch_geometry(case, env=None, storage="f64"):
     mfma = kernel != "k_colmat"
     return dict(kernel=kernel, MT=g.zDim // 16 if mfma else None, CT=ct, OT="float" if storage == "f32x" else "double",
                 grid_x=grid_x, tail=K2 % (64 * ct), K2=K2)
+
+
+PLAN_RZ_INVERSE, PLAN_RZ_FORWARD, PLAN_SEMI = 5, 6, 7
+
+
+def _ceil(a, b):
+    return -(-a // b)
+
+
+def rz_inverse_launch_geometry(case, env=None, storage="f64", tile=None):
+    """What launch_rz_inverse (scythe.jl_amd/csrc/sx_rz.hip) launches for tileTransform! on a fused RZ grid, from the library's
+    own plan: kernel text, form ("nodes": 13 cells per workgroup, chunks of 32 coefficient rows; "rings": 16 rings, chunks of
+    64), grid (x, y, z), LDS bytes, K chunks, attr (the over-64 KB dynamic-LDS attribute is set first); and what follows from
+    those inside the kernels: last_x = cells (nodes form) or rings (ring-tile form) of the last workgroup along x, last_waves =
+    waves of the last z-group that own a tile of 16 levels, tail_z = zDim % 16 and tail_k = b_zDim - (chunks - 1) rows of the
+    last K chunk."""
+    g, _, ncells = _handle_dims(case, tile)
+    kernel, (gx, gy, gz, lds, chunks, attr) = launch_plan(PLAN_RZ_INVERSE, g.zDim, g.b_zDim, ncells, g.V, int(storage == "f32"), env=env)
+    nodes = kernel.startswith("k_rz_inverse_nodes")
+    per, rows, n = (13, 32, ncells) if nodes else (16, 64, 3 * ncells)
+    return dict(kernel=kernel, form="nodes" if nodes else "rings", grid=(gx, gy, gz), lds=lds, chunks=chunks, attr=bool(attr),
+                last_x=n - (gx - 1) * per, last_waves=_ceil(g.zDim, 16) - (gz - 1) * 4, tail_z=g.zDim % 16,
+                tail_k=g.b_zDim - (chunks - 1) * rows, ncells=ncells, zDim=g.zDim, b_zDim=g.b_zDim)
+
+
+def rz_forward_launch_geometry(case, tile=None, v_cnt=None):
+    """What launch_rz_forward launches for spectralTransform! on a fused RZ grid, from the library's plan: grid (x: tiles of 16
+    nodes, y: variables, z: groups of mt_per_wg tiles of 16 modes), mt_per_wg, K chunks of 64 levels, LDS bytes; last_x = nodes of
+    the last node tile, tail_z = zDim - 64 (chunks - 1) levels of the last chunk, tail_m = b_zDim % 16."""
+    g, _, ncells = _handle_dims(case, tile)
+    kernel, (gx, gy, gz, mt, chunks, lds) = launch_plan(PLAN_RZ_FORWARD, g.zDim, g.b_zDim, ncells, g.V if v_cnt is None else v_cnt)
+    return dict(kernel=kernel, grid=(gx, gy, gz), mt_per_wg=mt, chunks=chunks, lds=lds, last_x=ncells + 3 - (gx - 1) * 16,
+                tail_z=g.zDim - 64 * (chunks - 1), tail_m=g.b_zDim % 16, ncells=ncells, zDim=g.zDim, b_zDim=g.b_zDim)
+
+
+def semi_launch_geometry(case, env=None):
+    """What the semi-implicit adjustment launches over the case's columns (one tile), from the library's plan: kernel
+    (k_semi_mfma, or k_semiimplicit with SX_SEMI_MFMA=0), workgroups, threads, tiles = level tiles per wave trip, trips =
+    ceil(ceil(zDim / 16) / tiles), K chunks of 64 levels, LDS bytes, attr; last = columns of the last workgroup."""
+    g, _, ncells = _handle_dims(case)
+    ncol = g.tile_npoints(0, ncells) // g.zDim
+    kernel, (wgs, threads, tiles, chunks, lds, attr) = launch_plan(PLAN_SEMI, g.zDim, ncol, env=env)
+    per = 16 if kernel == "k_semi_mfma" else max(1, 256 // g.zDim)
+    return dict(kernel=kernel, wgs=wgs, threads=threads, tiles=tiles, trips=_ceil(_ceil(g.zDim, 16), tiles) if tiles else 0,
+                chunks=chunks, lds=lds, attr=bool(attr), columns=ncol, last=ncol - (wgs - 1) * per, zDim=g.zDim)
+
+
+def inverse_bound_ratio(phys, ref, scale, C, f32=False):
+    """|phys - ref| / (C 2^-53 scale [+ 2^-24 |ref| on the derivative slots of fp32-stored planes]) per entry, [points, V, D] in
+    Float64 (entries of zero bound: 0 where phys equals ref, else inf), and the index of the worst one."""
+    err = np.abs(np.asarray(phys, dtype=O.XP) - ref)
+    bound = O.XP(C) * O.XP(2.0 ** -53) * scale
+    if f32:
+        bound = bound.copy()
+        bound[:, :, 1:] += O.XP(2.0 ** -24) * np.abs(ref[:, :, 1:])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(bound > 0, err / np.where(bound > 0, bound, 1), np.where(err > 0, np.inf, 0.0))
+    q = np.asarray(q, dtype=np.float64)
+    return q, np.unravel_index(int(np.argmax(q)), q.shape)
+
+
+def inverse_reference(case, A, tile=None, exact_offsets=True):
+    """(ref, scale), each [tile points, V, D] longdouble: oracle_np.inverse_xp with its per-entry scale over every ring of the
+    tile (RZ grids: a ring is one column), the basis weights at the exact Gauss offsets (what the library tabulates) unless
+    exact_offsets = False (at the Float64 gridpoints, what the oracles evaluate)."""
+    g, _, ncells = _handle_dims(case, tile)
+    c0 = 0 if tile is None else tile[0]
+    rings = list(g.tile_rings(c0, ncells))
+    ref, sc = O.inverse_xp(g, A, rings, with_scale=True, exact_offsets=exact_offsets)
+    return np.concatenate([ref[r] for r in rings], axis=0), np.concatenate([sc[r] for r in rings], axis=0)
+
+
+def inverse_f64_tables(case, A, tile=None):
+    """The fused RZ inverse as a plain Float64 evaluation from tables formed once in Float64, the way the library forms its own
+    (basis weights bspline(3/2 + Gauss offset - j) / DX^d per ring of a cell, the oracle's once-rounded vertical operators):
+    [tile points, V, D].  The stand-in for a kernel in the CPU check of the per-entry bound."""
+    g, _, ncells = _handle_dims(case, tile)
+    c0 = 0 if tile is None else tile[0]
+    goff = np.array([-np.sqrt(3.0 / 5.0) / 2, 0.0, np.sqrt(3.0 / 5.0) / 2])
+    phi = [np.stack([O.bspline((1.5 + goff[mu] - np.arange(4.0))[None, :], d)[0] * (1.0 / g.DX ** d) for mu in range(3)]) for d in range(3)]
+    sl = {s: i for i, s in enumerate(g.slots)}
+    out = np.zeros((3 * ncells * g.zDim, g.V, g.D))
+    for vi, v in enumerate(g.names):
+        M = g.cheb(v).M
+        Av = A[:, vi].reshape(g.b_zDim, g.b_rDim)
+        for i in range(3 * ncells):
+            c = c0 + i // 3
+            f = [Av[:, c:c + 4] @ phi[d][i % 3] for d in range(3)]
+            pts = slice(i * g.zDim, (i + 1) * g.zDim)
+            for name, val in (("u", M[0] @ f[0]), ("r", M[0] @ f[1]), ("rr", M[0] @ f[2]), ("z", M[1] @ f[0]), ("zz", M[2] @ f[0])):
+                out[pts, vi, sl[name]] = val
+    return out
+
+
+def where_rz(g, idx, cell0=0):
+    """(ring, level, variable, slot) text of an index into an RZ tile's [points, V, D] array"""
+    return "ring %d level %d variable %d slot %s" % (3 * cell0 + idx[0] // g.zDim, idx[0] % g.zDim, idx[1], g.slots[idx[2]])
 
 
 # every instantiation the two launchers can pick

@@ -548,6 +548,37 @@ CASES = {
     "euler_z32_plain": ("rz_euler", dict(num_cells=7, zDim=32), "f64", {"SX_SEMI_MFMA": 0}, (P, SI), {'points': 256, 'semi columns': 8}),
 }
 
+# k_semi_mfma / k_semiimplicit at the level counts where the launch changes: a second and a fourth K chunk of 64 levels, level
+# counts one past a tile (33, 65, 129), the over-64 KB LDS branch and the second trip of the kernel's `kt += nw` loops (zDim > 128);
+# 15 columns (one partial workgroup), 33 (two full and a partial one), 48 (three full).  The ids carry the launch as the library's
+# plan reports it (cases.semi_launch_geometry).  15 columns do not fill a workgroup of 16, so these cases state the point count only
+# (a whole number of 256-point workgroups at 256 levels and at 48 x 128).
+SEMI_SHAPES = [
+    # (maker, cells, zDim, SX_* overrides, tails)
+    ("rz_semiimplicit", 5, 33, None, {'points': 256}),
+    ("rz_semiimplicit", 11, 64, None, {'points': 256, 'semi columns': 16}),
+    ("rz_semiimplicit", 5, 65, None, {'points': 256}),
+    ("rz_semiimplicit", 16, 128, None, {'points': 256, 'semi columns': 16, 'full': True}),
+    ("rz_semiimplicit", 5, 129, None, {'points': 256}),
+    ("rz_semiimplicit", 5, 200, None, {'points': 256}),
+    ("rz_semiimplicit", 5, 256, None, {'points': 256, 'full': True}),
+    ("rz_semiimplicit", 5, 65, {"SX_SEMI_MFMA": 0}, {'points': 256}),
+    ("rz_semiimplicit", 5, 200, {"SX_SEMI_MFMA": 0}, {'points': 256}),
+    ("rz_euler", 5, 64, None, {'points': 256}),
+    ("rz_euler", 5, 128, None, {'points': 256}),
+]
+
+
+def semi_id(maker, nc, nz, env):
+    geo = cases.semi_launch_geometry(getattr(cases, maker)(num_cells=nc, zDim=nz), env)
+    return "%s_n%dz%d-%s-wg%d-last%d-t%d-trips%d-kc%d-lds%d%s" % (
+        maker[3:], nc, nz, geo["kernel"], geo["wgs"], geo["last"], geo["threads"], geo["trips"], geo["chunks"], geo["lds"],
+        "-attr" if geo["attr"] else "")
+
+
+SEMI_CASES = {semi_id(m, nc, nz, env): (m, dict(num_cells=nc, zDim=nz), "f64", env, (P, SI), tails) for m, nc, nz, env, tails in SEMI_SHAPES}
+CASES.update(SEMI_CASES)
+
 # one small case per equation set (the Float64 pin of tests/golden/physics_f64_pin.npz and the mutations of tests/test_physics.py)
 PER_SET = ("adv1d", "adv_rz", "adv_rl", "adv_rlz", "slab_oneway", "slab_twoway", "lsw1d", "lsw_rl", "acoustic", "euler", "hrbl_z10",
            "rain_z12_semi")

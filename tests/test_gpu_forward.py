@@ -31,6 +31,17 @@ def _z(nz, b, nc=4, L=16, maker="rlz_advection"):
     return [maker, {"num_cells": nc, "zDim": nz, "ring_L": L}, {"b_zDim": b}]
 
 
+def rz_fwd_id(geo):
+    """Name fragment of one launch_rz_forward launch, from the library's plan (cases.rz_forward_launch_geometry)."""
+    return "n%dz%db%d-g%dx%dx%d-lastx%d-mt%d-kc%d-tailz%d-tailm%d" % (
+        geo["ncells"], geo["zDim"], geo["b_zDim"], *geo["grid"], geo["last_x"], geo["mt_per_wg"], geo["chunks"], geo["tail_z"], geo["tail_m"])
+
+
+def _rz_fused(nc, nz, b):
+    spec = ["rz_advection", {"num_cells": nc, "zDim": nz}, {"b_zDim": b} if b else {}]
+    return ("rz-fused-" + rz_fwd_id(cases.rz_forward_launch_geometry(make_case(spec))), spec, {}, "f64")
+
+
 # (name, spec, per-handle switches, storage): spec as tests/child_run.make_case takes it
 FWD_CASES = (
     [("z32b%d" % b, _z(32, b), {}, "f64") for b in (16, 17, 22, 32)]
@@ -53,10 +64,16 @@ FWD_CASES = (
     + [("rl-L16", ["rl_advection", {"num_cells": 6, "ring_L": 16}, {}], {}, "f64"),
        ("rz-fused", ["rz_advection", {"num_cells": 7, "zDim": 20}, {}], {}, "f64"),
        ("rz-general", ["rz_advection", {"num_cells": 7, "zDim": 32}, {"b_zDim": 21}], {"SX_RZ_FUSED": "0"}, "f64")]
+    # k_rz_forward beyond one node tile, one K chunk and one mode group: 16 / 17 and 32 / 33 nodes (the 19-cell weight window, both
+    # halves of 8 nodes, zero weights outside the tile), a second chunk of 64 levels, a second group of 4 mode tiles, 4 chunks
+    + [_rz_fused(nc, nz, b)
+       for nc, nz, b in ((13, 20, None), (14, 20, None), (29, 20, None), (30, 20, None), (7, 64, 64), (7, 65, 65), (7, 128, 80), (5, 256, 100))]
 )
 
 # tiles of a patch: each tile's B against forward_xp of its own points
-TILE_CASES = [("native-z32b22-2tiles", _z(32, 22, nc=10, L=None), 2), ("z64b43-L32-3tiles", _z(64, 43, nc=12, L=32), 3)]
+TILE_CASES = [("native-z32b22-2tiles", _z(32, 22, nc=10, L=None), 2), ("z64b43-L32-3tiles", _z(64, 43, nc=12, L=32), 3),
+              # fused RZ: tiles of 14, 13 and 13 cells, cell0 != 0, weight windows that reach outside the tile on both sides
+              ("rz-fused-z20-3tiles", ["rz_advection", {"num_cells": 40, "zDim": 20}, {}], 3)]
 
 # SX_DEFER_DIAG=1 (one-tile HRBL on the FFT path): a step covers the prognostic variables (v_cnt = V - 1); reading B then
 # brings the diagnostic one up to date (v_lo = V - 1, v_cnt = 1)
@@ -252,7 +269,8 @@ def test_forward_projection_of_each_tile(name, spec, ntiles):
         B = g.spectral
         g.close()
         geo = cases.sb_launch_geometry(case, tile=(c0, n))
-        _check_b(case, vals, B, "f64", "%s tile %d (cells %d..%d) %s" % (name, t, c0, c0 + n - 1, sb_id(geo)), c0, n)
+        shape = sb_id(geo) + ("-" + rz_fwd_id(geo) if geo["kernel"] == "k_rz_forward" else "")
+        _check_b(case, vals, B, "f64", "%s tile %d (cells %d..%d) %s" % (name, t, c0, c0 + n - 1, shape), c0, n)
 
 
 @pytest.mark.gpu

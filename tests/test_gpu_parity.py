@@ -319,11 +319,23 @@ def test_rz_fused_matrix_core_transforms_equal_the_general_kernels(monkeypatch, 
     g0.close()
 
 
+# numpy oracle vs C oracle after the same 5 steps of rz_semiimplicit, measured on the CPU, per variable (s, xi, mu, u, w):
+# (max|d var_np1| / max|var_np1|, max|d value| / max|value|).  DESIGN.md section 2 has the table and what follows from it.
+SEMI_ORACLE_SPREAD = {
+    (9, 128): ((9.44e-13, 5.30e-15, 9.44e-13, 1.41e-12, 3.30e-15), (9.09e-13, 5.13e-15, 9.09e-13, 1.54e-12, 3.04e-15)),
+    (5, 200): ((1.17e-09, 4.02e-13, 1.17e-09, 1.21e-09, 9.05e-13), (1.13e-09, 4.11e-13, 1.13e-09, 1.19e-09, 9.20e-13)),
+}
+
+
 @pytest.mark.parametrize("num_cells,zDim", [(8, 12), (10, 33), (6, 64), (9, 128), (5, 200)])
 def test_semi_implicit_adjustment_on_the_matrix_cores_equals_the_scalar_kernel(monkeypatch, num_cells, zDim):
     """semiimplicit_adjustment (src/semiimplicit.jl:521-597): the four column operators as f64-MFMA products of 16 columns
     (k_semi_mfma, csrc/sx_rz.hip, the default) against the scalar kernel (SX_SEMI_MFMA=0) - Euler, AB2 and AB3 steps, level counts
-    that are not multiples of the tile - and against the oracle."""
+    that are not multiples of the tile - and against the oracle.  At 128 and 200 levels every bar is the smaller of the one that
+    was here before (1e-12 (zDim / 64)^4 per variable, 1e-10 (zDim / 128)^4 for the fields) and 10 x the measured spread of the
+    two fp64 oracles + 1e-12 (SEMI_ORACLE_SPREAD, the rule of cases.check_full).  At 200 levels the oracles themselves are
+    1.2e-9 apart in s, mu and u, so there the earlier bars stand (10 x the spread would be wider); xi and w, the variables the
+    two kernels write, are held to 5e-12 and 1e-11 instead of 9.5e-11."""
     case = cases.rz_semiimplicit(num_cells=num_cells, zDim=zDim)
     a = cases.HipModel(case)
     monkeypatch.setenv("SX_SEMI_MFMA", "0")
@@ -335,12 +347,24 @@ def test_semi_implicit_adjustment_on_the_matrix_cores_equals_the_scalar_kernel(m
         orc.step()
     fa, fb = a.run.tiles[0].var_np1, b.run.tiles[0].var_np1
     assert np.isfinite(fa).all()
+    spread = SEMI_ORACLE_SPREAD.get((num_cells, zDim))
     for v in range(fa.shape[1]):
-        # (two summation orders of operators whose norm grows as zDim^4)
-        assert np.abs(fa[:, v] - fb[:, v]).max() <= 1e-12 * max(1.0, (zDim / 64.0) ** 4) * max(np.abs(fb[:, v]).max(), 1e-300), v
+        # (two summation orders of operators whose norm grows as zDim^4); where the spread of the two fp64 oracles is measured,
+        # no wider than cases.check_full's rule on it, 10 x spread + 1e-12
+        bar = 1e-12 * max(1.0, (zDim / 64.0) ** 4)
+        if spread:
+            bar = min(bar, 10.0 * spread[0][v] + 1e-12)
+        d = np.abs(fa[:, v] - fb[:, v]).max() / max(np.abs(fb[:, v]).max(), 1e-300)
+        print("var_np1 variable %d: k_semi_mfma vs k_semiimplicit %.2e (bar %.2e)" % (v, d, bar))
+        assert d <= bar, v
     pa, po = a.physical(), orc.physical()
     # the model fields (beyond 128 levels the column operators' O(zDim^4) norms put two correct fp64 runs further apart than 1e-10)
-    assert cases.rel_err_per_var(pa[:, :, :1], po[:, :, :1]) < TOL * max(1.0, (zDim / 128.0) ** 4)
+    bar = TOL * max(1.0, (zDim / 128.0) ** 4)
+    if spread:
+        bar = min(bar, 10.0 * max(spread[1]) + 1e-12)
+    d = cases.rel_err_per_var(pa[:, :, :1], po[:, :, :1])
+    print("value slot vs the C oracle %.2e (bar %.2e)" % (d, bar))
+    assert d < bar
     if zDim <= 33:          # (beyond that the d2/dz2 slot of two fp64 runs differs by N^4 eps: tests/test_gpu_configs.py treats config 3)
         assert cases.rel_err_per_var(pa, po) < TOL
 

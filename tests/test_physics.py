@@ -73,11 +73,18 @@ def test_library_semi_operators_are_the_oracle_s_to_the_inversion_s_accuracy(cid
             assert np.abs(a - b).max() <= 1e-11 * np.abs(b).max()
 
 
+# the semi-implicit cases at 65, 128 and 200 levels (tests/physics.py SEMI_CASES), default kernel: one twin per level count
+SEMI_DEEP = [c for c, v in physics.SEMI_CASES.items() if v[3] is None and v[1]["zDim"] in (65, 128, 200)]
+
+
 @pytest.mark.parametrize("cid,mutate", [("acoustic", "semi"), ("euler_z16", "semi"), ("rain_z12_semi", "semi"),
-                                        ("rain_z12", "condensation"), ("rain_z12_semi", "condensation")])
+                                        ("rain_z12", "condensation"), ("rain_z12_semi", "condensation")] + [(c, "semi") for c in SEMI_DEEP])
 def test_bound_catches_an_error_inside_the_adjustments(cid, mutate):
     """The bound of w and xi carries the operator sums and up to 3 nz in c: it still bites at 1e-9 inside semiimplicit_adjustment
-    (tau Pxi_bar of xi*_z) and inside condensation_adjustment (its time scale)."""
+    (tau Pxi_bar of xi*_z) and inside condensation_adjustment (its time scale).  At 65, 128 and 200 levels (c = 157, 283 / 311, 427)
+    the same 1e-9 change of tau Pxi_bar is still caught, by a factor of 5000 at 65 levels and 1400 at 200: the size did not have
+    to be lowered.  This, not a bar scaled by zDim^4 on a five-step comparison, is the statement of what the per-point check of
+    k_semi_mfma can see at those level counts."""
     top, where = _run(cid, mutate)
     assert top > 1.0, "%s: the %s error stays inside the bound (worst ratio %.3g)" % (cid, mutate, top)
 
