@@ -348,10 +348,10 @@ int sx_antiderivative(sx_handle *src, int32_t var_src, int32_t axis, int32_t ori
         a.P = st->d_P; a.c = st->d_c; a.m = st->d_m; a.F = st->d_F; a.cls = st->d_cls;
         a.Cs = src->C; a.Cd = dst->C; a.col_s = (int64_t)vs * ncol; a.col_d = (int64_t)vd * ncol;
         a.nb = nb; a.K2 = src->K2; a.ncol = ncol; a.high = origin == SX_INT_FROM_HIGH;
-        timer_begin(src, timer_id(src, "k_antiderivative_r"));
-        hipLaunchKernelGGL(k_antiderivative_r, grid1(ncol, ANT_T), dim3(ANT_T), 0, src->stream, a);
-        HIPCHK(hipGetLastError());
-        timer_end(src);
+        {
+            TimedLaunch scope(src, "k_antiderivative_r");
+            hipLaunchKernelGGL(k_antiderivative_r, grid1(ncol, ANT_T), dim3(ANT_T), 0, src->stream, a);
+        }
         // the live source columns in, the destination columns out, and honestly: b and y each go out to the destination column and come
         // back (2 stores + 2 loads of the live columns); the tables [nb][7 + 1 + 1] and the factor rows [2][nb][4]
         st->bytes_r = 8.0 * nb * (live + ncol + 4.0 * live) + 8.0 * nb * (9.0 + 8.0);
@@ -360,17 +360,17 @@ int sx_antiderivative(sx_handle *src, int32_t var_src, int32_t axis, int32_t ori
         a.A = src->d_A; a.D = dst->d_A; a.ZT = st->d_ZT;
         a.Cs = src->C; a.Cd = dst->C; a.col_s = (int64_t)vs * ncol; a.col_d = (int64_t)vd * ncol;
         a.nb = nb; a.Zb = src->Zb; a.K2 = src->K2; a.Mp = st->Mp;
-        timer_begin(src, timer_id(src, "k_antiderivative_z"));
-        if (src->K2 >= 16 && src->Zb <= 64) {
-            const dim3 g((src->K2 + 15) / 16, nb);
-            if (src->Zb <= 16) hipLaunchKernelGGL(k_antiderivative_z<4>, g, dim3(64), 0, src->stream, a);
-            else if (src->Zb <= 32) hipLaunchKernelGGL(k_antiderivative_z<8>, g, dim3(64), 0, src->stream, a);
-            else hipLaunchKernelGGL(k_antiderivative_z<16>, g, dim3(64), 0, src->stream, a);
-        } else {
-            hipLaunchKernelGGL(k_antiderivative_z_lane, grid1((int64_t)nb * ncol, 256), dim3(256), 0, src->stream, a);
+        {
+            TimedLaunch scope(src, "k_antiderivative_z");
+            if (src->K2 >= 16 && src->Zb <= 64) {
+                const dim3 g((src->K2 + 15) / 16, nb);
+                if (src->Zb <= 16) hipLaunchKernelGGL(k_antiderivative_z<4>, g, dim3(64), 0, src->stream, a);
+                else if (src->Zb <= 32) hipLaunchKernelGGL(k_antiderivative_z<8>, g, dim3(64), 0, src->stream, a);
+                else hipLaunchKernelGGL(k_antiderivative_z<16>, g, dim3(64), 0, src->stream, a);
+            } else {
+                hipLaunchKernelGGL(k_antiderivative_z_lane, grid1((int64_t)nb * ncol, 256), dim3(256), 0, src->stream, a);
+            }
         }
-        HIPCHK(hipGetLastError());
-        timer_end(src);
         st->bytes_z = 2.0 * 8.0 * nb * ncol + 8.0 * src->Zb * src->Zb;
     }
     HIPCHK(hipStreamSynchronize(src->stream));

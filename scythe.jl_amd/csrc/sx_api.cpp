@@ -85,7 +85,7 @@ static std::vector<double> transpose(const std::vector<double> &m, int n) {
 }
 
 // ---- timers
-int timer_id(sx_handle *h, const char *name) {
+static int timer_id(sx_handle *h, const char *name) {
     for (size_t i = 0; i < h->timers.size(); i++)
         if (h->timers[i].name == name || !std::strcmp(h->timers[i].name, name)) return (int)i;
     Timer t;
@@ -105,10 +105,10 @@ static hipEvent_t get_event(sx_handle *h) {
     return e;
 }
 
-void timer_begin(sx_handle *h, int id) {
-    h->timer_skip = false;
+TimedLaunch::TimedLaunch(sx_handle *h, const char *name) : name(name) {
+    const int id = timer_id(h, name);
     if (!h->timers_on) return;
-    if (!h->timer_only.empty() && h->timer_only != h->timers[id].name) { h->timer_skip = true; return; }
+    if (!h->timer_only.empty() && h->timer_only != h->timers[id].name) return;
     if (h->pending.size() >= 8192) timers_flush(h);
     PendingEvent p;
     p.timer = id;
@@ -116,11 +116,14 @@ void timer_begin(sx_handle *h, int id) {
     p.b = get_event(h);
     hipEventRecord(p.a, h->stream);
     h->pending.push_back(p);
+    stream = h->stream;
+    end = p.b;
 }
 
-void timer_end(sx_handle *h) {
-    if (!h->timers_on || h->timer_skip || h->pending.empty()) return;
-    hipEventRecord(h->pending.back().b, h->stream);
+TimedLaunch::~TimedLaunch() {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) set_error(std::string(name) + ": " + hipGetErrorString(e));
+    if (end) hipEventRecord(end, stream);
 }
 
 void timers_flush(sx_handle *h) {

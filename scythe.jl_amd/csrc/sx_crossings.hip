@@ -314,11 +314,11 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     // A columns of the variables named (the padding block left out) and the ray coordinates in, the profiles out
     st->last_bytes = nv == 0 ? 0.0 : 8.0 * ((double)rows * Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv + (double)nrc * n_rays + (double)rows * nprof * n_rays);
     if (nv > 0) {
-        timer_begin(h, timer_id(h, "k_ray_profiles"));
-        hipLaunchKernelGGL(k_ray_profiles, dim3((unsigned)((rows + 15) / 16), (unsigned)((n_rays + 15) / 16), (unsigned)nv), dim3(64), prof_lds(h),
-                           h->stream, pa);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
+        {
+            TimedLaunch scope(h, "k_ray_profiles");
+            hipLaunchKernelGGL(k_ray_profiles, dim3((unsigned)((rows + 15) / 16), (unsigned)((n_rays + 15) / 16), (unsigned)nv), dim3(64), prof_lds(h),
+                               h->stream, pa);
+        }
     }
 
     ca.P = st->d_P; ca.radius = st->d_rad; ca.dir = st->d_i; ca.count = st->d_i + n_rad; ca.status = st->d_i + n_rad + (size_t)n_levels * n_rays;
@@ -330,10 +330,10 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     ca.max_iter = max_iter <= 0 ? 60 : max_iter; ca.max_cross = max_cross;
     // the profiles in; radii, directions, counts and status out
     st->cross_bytes = 8.0 * (double)rows * nprof * n_rays + 12.0 * (double)n_rad + 4.0 * ((double)n_levels + 1.0) * n_rays;
-    timer_begin(h, timer_id(h, "k_crossings"));
-    hipLaunchKernelGGL(k_crossings, dim3((unsigned)n_rays), dim3(64), 0, h->stream, ca);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_crossings");
+        hipLaunchKernelGGL(k_crossings, dim3((unsigned)n_rays), dim3(64), 0, h->stream, ca);
+    }
 
     std::vector<double> rr(n_rad), rp(profiles ? (size_t)nprof * rows * n_rays : 0);      // held back until the call has succeeded: a failed call writes nothing
     std::vector<int> ri(n_int);

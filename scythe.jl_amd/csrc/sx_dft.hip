@@ -1599,8 +1599,7 @@ static void rlz_inverse(sx_handle *h, const int *d_mask) {
 }
 
 void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
-    const int id = timer_id(h, "k_rl_inverse");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_rl_inverse");
 #ifdef SX_PHASES
     if (!g_dft_buf && !dft_planes(h)) {
         g_dft_n = (int64_t)level_chunks(h) * h->V * h->nrings;
@@ -1612,12 +1611,10 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
     if (dft_planes(h)) launch_rl_inverse_dft_planes(h, d_mask == h->d_mask_full);
     else if (h->f32) rlz_inverse<float>(h, d_mask);
     else rlz_inverse<double>(h, d_mask);
-    timer_end(h);
 }
 
 void launch_fl_forward_dft(sx_handle *h) {
-    const int id = timer_id(h, "k_fl_forward");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_fl_forward");
     const int planes = dft_planes(h) ? 1 : 0;
     const bool half = h->sw.dft_half != 0;      // A/B: the half-ring kernel
     auto go = [&](auto kern, dim3 grid, size_t lds, auto... tail) {
@@ -1647,7 +1644,6 @@ void launch_fl_forward_dft(sx_handle *h) {
                h->nz, h->K2, h->N, r0, lcap, planes, ntw);
         }, planes ? 2 : 4);
     }
-    timer_end(h);
 }
 
 }  // namespace sx

@@ -327,19 +327,19 @@ int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms,
     a.part = st->d_part; a.pcnt = st->d_pcnt;
     a.N = h->N; a.n_work = n_work; a.V = h->V; a.nz = h->nz; a.n_bins = n_bins; a.level = level;
     const size_t lds = dist_lds_bytes(groups, level ? 1 : RED_T / 64, n_bins, n_out);
-    timer_begin(h, timer_id(h, "k_distribution"));
-    scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
-        const auto kern = k_distribution<decltype(st_t), decltype(rings)::value>;
-        if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(RED_T), lds, h->stream, P, a, prog);
-    });
-    HIPCHK(hipGetLastError());
-    timer_end(h);
-    timer_begin(h, timer_id(h, "k_distribution_final"));
-    hipLaunchKernelGGL(k_distribution_final, grid1((int64_t)E, DIST_FE), dim3(DIST_FE * DIST_PARTS), 0, h->stream, st->d_part, st->d_pcnt, nwg,
-                       groups, S, n_out, st->d_sums, st->d_count);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_distribution");
+        scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
+            const auto kern = k_distribution<decltype(st_t), decltype(rings)::value>;
+            if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(RED_T), lds, h->stream, P, a, prog);
+        });
+    }
+    {
+        TimedLaunch scope(h, "k_distribution_final");
+        hipLaunchKernelGGL(k_distribution_final, grid1((int64_t)E, DIST_FE), dim3(DIST_FE * DIST_PARTS), 0, h->stream, st->d_part, st->d_pcnt, nwg,
+                           groups, S, n_out, st->d_sums, st->d_count);
+    }
     std::vector<double> rs(E);           // held back until the call has succeeded: a failed call writes nothing
     std::vector<unsigned long long> rc(EC);
     HIPCHK(hipMemcpyAsync(rs.data(), st->d_sums, sizeof(double) * E, hipMemcpyDeviceToHost, h->stream));

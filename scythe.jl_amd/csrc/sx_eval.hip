@@ -310,11 +310,11 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
     if (error_status()) return false;
     EvalSlots sl;
     for (int m = 0; m < 7; m++) sl.s[m] = h->slot[m];
-    timer_begin(h, timer_id(h, "k_evaluate"));
-    hipLaunchKernelGGL(k_evaluate, dim3((unsigned)batches.size(), (unsigned)h->V), dim3(EVAL_T), eval_lds_bytes(P, csw, Zb), h->stream, h->d_A,
-                       h->C, st->d_pts, st->d_batch, st->d_wz, st->cls.d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, kmin, kband, sl, st->d_res, (int64_t)n, h->V);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_evaluate");
+        hipLaunchKernelGGL(k_evaluate, dim3((unsigned)batches.size(), (unsigned)h->V), dim3(EVAL_T), eval_lds_bytes(P, csw, Zb), h->stream, h->d_A,
+                           h->C, st->d_pts, st->d_batch, st->d_wz, st->cls.d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, kmin, kband, sl, st->d_res, (int64_t)n, h->V);
+    }
     std::vector<double> res(nres);
     HIPCHK(hipMemcpyAsync(res.data(), st->d_res, sizeof(double) * nres, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -443,23 +443,23 @@ int sx_extrema(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, cons
         return 1;
     st->last_bytes = red_bytes(h, source, planes, n_planes);
 
-    timer_begin(h, timer_id(h, "k_extrema"));
-    scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
-        constexpr bool RINGS = decltype(rings)::value;
-        hipLaunchKernelGGL((k_extrema<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
-                           h->V, h->N, h->nz, sg->d_items, h->d_pstart, h->d_r, prog, sg->n_items, st->d_pv, st->d_pi);
-    });
-    HIPCHK(hipGetLastError());
-    timer_end(h);
-    timer_begin(h, timer_id(h, "k_extrema_final"));
-    if (kind == SX_EXT_AZIMUTH)
-        hipLaunchKernelGGL(k_extrema_rings, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_pv, st->d_pi, sg->d_first, sg->n_items,
-                           h->nrings, h->nz, n_out, st->d_val, st->d_idx);
-    else
-        hipLaunchKernelGGL(k_extrema_domain, dim3((unsigned)n_out, 2), dim3(EXT_TF), 0, h->stream, st->d_pv, st->d_pi, sg->n_items, h->nz, n_out,
-                           st->d_val, st->d_idx);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_extrema");
+        scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
+            constexpr bool RINGS = decltype(rings)::value;
+            hipLaunchKernelGGL((k_extrema<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
+                               h->V, h->N, h->nz, sg->d_items, h->d_pstart, h->d_r, prog, sg->n_items, st->d_pv, st->d_pi);
+        });
+    }
+    {
+        TimedLaunch scope(h, "k_extrema_final");
+        if (kind == SX_EXT_AZIMUTH)
+            hipLaunchKernelGGL(k_extrema_rings, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_pv, st->d_pi, sg->d_first, sg->n_items,
+                               h->nrings, h->nz, n_out, st->d_val, st->d_idx);
+        else
+            hipLaunchKernelGGL(k_extrema_domain, dim3((unsigned)n_out, 2), dim3(EXT_TF), 0, h->stream, st->d_pv, st->d_pi, sg->n_items, h->nz, n_out,
+                               st->d_val, st->d_idx);
+    }
     std::vector<double> rv(n_res);      // held back until the call has succeeded: a failed call writes nothing
     std::vector<long long> ri(n_res);
     HIPCHK(hipMemcpyAsync(rv.data(), st->d_val, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
@@ -515,10 +515,10 @@ int sx_extremum_refine(sx_handle *h, int32_t var, int32_t want, int32_t free_mas
     a.want = want; a.mask = free_mask; a.max_iter = max_iter <= 0 ? 20 : max_iter;
     a.xmin = h->xmin; a.tol = tol <= 0.0 ? 1e-9 : tol;
     a.G = newton_geom(g);
-    timer_begin(h, timer_id(h, "k_refine"));
-    hipLaunchKernelGGL(k_refine, dim3((unsigned)n), dim3(parcel_threads(h)), refine_lds(h), h->stream, a);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_refine");
+        hipLaunchKernelGGL(k_refine, dim3((unsigned)n), dim3(parcel_threads(h)), refine_lds(h), h->stream, a);
+    }
     std::vector<double> rf(2 * blk + n);          // held back until the call has succeeded: a failed call writes nothing
     std::vector<int> ric(2 * (size_t)n);
     HIPCHK(hipMemcpyAsync(rf.data(), st->d_f + blk, sizeof(double) * rf.size(), hipMemcpyDeviceToHost, h->stream));

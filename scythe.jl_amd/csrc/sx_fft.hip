@@ -953,7 +953,6 @@ static void launch_inv_any(sx_handle *h, const int *d_mask, const InvTarget &tg)
         case 8: launch_inv<8>(h, d_mask, tg, az, azrow); break;
         default: launch_inv<9>(h, d_mask, tg, az, azrow); break;
     }
-    HIPCHK(hipGetLastError());
 }
 
 template <int LOGL>
@@ -970,11 +969,9 @@ static void launch_fwd(sx_handle *h, dim3 g) {
 
 // ring-wise inverse of the first n_rings rings of the tile (all of them by default)
 void launch_rl_inverse_fft(sx_handle *h, const int *d_mask, int n_rings) {
-    const int id = timer_id(h, "k_rl_inverse");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_rl_inverse");
     InvTarget tg{h->d_phys, h->d_phi, h->d_kmax, h->d_pstart, h->d_phoff, n_rings < 0 ? h->nrings : n_rings, h->nrings, h->N, 0};
     launch_inv_any(h, d_mask, tg);
-    timer_end(h);
 }
 
 // node-space inverse ("radial last", uniform rings): one transform set per radial node instead of per ring
@@ -997,8 +994,7 @@ void fft_phases_dump() {
 #endif
 
 void launch_node_fft(sx_handle *h) {
-    const int id = timer_id(h, "k_node_fft");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_node_fft");
 #ifdef SX_PHASES
     if (!g_fft_buf) {
         g_fft_n = (int64_t)((h->nz + FFT_FZC - 1) / FFT_FZC) * h->V * 8 * ((h->nbt + 7) / 8);      // the fused grid: whole groups of 8 nodes
@@ -1012,7 +1008,6 @@ void launch_node_fft(sx_handle *h) {
     const int j0 = h->R_in / MUBAR;
     InvTarget tg{h->d_G, h->d_nphi, h->d_nkmax, h->d_npstart, h->d_nphoff, h->nbt - j0, h->nbt, h->NG, 1, j0};
     launch_inv_any(h, h->d_mask_node, tg);
-    timer_end(h);
 }
 
 template <int LOGL, bool REG>
@@ -1044,8 +1039,7 @@ static void launch_fwd_cells(sx_handle *h, const CellsPlan &p) {
 }
 
 void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {
-    const int id = timer_id(h, "k_fl_forward");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_fl_forward");
     switch (p.logL) {
         case 4: launch_fwd_cells<4>(h, p); break;
         case 5: launch_fwd_cells<5>(h, p); break;
@@ -1053,13 +1047,10 @@ void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {
         case 7: launch_fwd_cells<7>(h, p); break;
         default: launch_fwd_cells<8>(h, p); break;
     }
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 void launch_fl_forward_fft(sx_handle *h) {
-    const int id = timer_id(h, "k_fl_forward");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_fl_forward");
     dim3 g((h->nz + FFT_FZC - 1) / FFT_FZC, h->v_cnt, h->nrings);
     switch (ilog2(h->uniform_L)) {
         case 4: launch_fwd<4>(h, g); break;
@@ -1069,8 +1060,6 @@ void launch_fl_forward_fft(sx_handle *h) {
         case 8: launch_fwd<8>(h, g); break;
         default: launch_fwd<9>(h, g); break;
     }
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 }  // namespace sx

@@ -131,12 +131,12 @@ static bool harm_chunk(sx_handle *h, HarmState *st, const EvalGeom &g, const dou
     std::stable_sort(pts.begin(), pts.end(), [](const RadialPt &x, const RadialPt &y) { return x.cell < y.cell; });
     HIPCHK(hipMemcpyAsync(st->d_pts, pts.data(), sizeof(RadialPt) * n, hipMemcpyHostToDevice, h->stream));
     if (error_status()) return false;
-    timer_begin(h, timer_id(h, "k_harmonics"));
-    if (a.Zb <= 16) harm_launch_ks<4>(h, st, a, n);
-    else if (a.Zb <= 48) harm_launch_ks<12>(h, st, a, n);
-    else harm_launch_ks<32>(h, st, a, n);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_harmonics");
+        if (a.Zb <= 16) harm_launch_ks<4>(h, st, a, n);
+        else if (a.Zb <= 48) harm_launch_ks<12>(h, st, a, n);
+        else harm_launch_ks<32>(h, st, a, n);
+    }
     // device [slot][v][radius of the chunk][height][KO]: per (slot, v) one contiguous piece of the caller's array
     const size_t piece = (size_t)n * a.nz * a.KO;
     for (int q = 0; q < a.nslots * h->V; q++)

@@ -882,7 +882,6 @@ void launch_solve_part(sx_handle *h, const double *B, double *A, int vz0, int ng
     const int bx = h->K2 > 1 ? (h->K2 - 2 + 63) / 64 : 0;
     hipLaunchKernelGGL((k_solve_part<PART_P, PART_NR>), dim3(bx + 1, ng), dim3(64 * PART_P), 0, h->stream, B, A, h->d_cls, h->d_part_meta, h->d_gl, h->d_gr,
                        h->d_part_tab, h->b_rDim, h->Zb, h->K2, vz0, h->C);
-    HIPCHK(hipGetLastError());
 }
 
 }  // namespace sx
@@ -980,16 +979,15 @@ int sx_iface_local(sx_handle *h, void *dev_send) {
     clear_error();
     IfaceState *st = h ? (IfaceState *)h->iface_state : nullptr;
     if (!st || !dev_send) { set_error("sx_iface_local: invalid argument / not configured"); return 1; }
-    const int id = timer_id(h, "k_iface_local");
-    timer_begin(h, id);
-    dim3 g((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb);
+    {
+        TimedLaunch scope(h, "k_iface_local");
+        dim3 g((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb);
 #define IFL_ARGS h->d_Btile, st->d_Y, (double *)dev_send, st->d_owner, st->d_soff, st->d_cw, st->d_cs, h->d_cls, st->d_meta, h->d_gl, h->d_gr, \
                  st->d_Lf, h->nbt, h->Zb, h->K2, h->C
-    if (st->nt_max <= IF_NT_REGS) hipLaunchKernelGGL(k_iface_local<true>, g, dim3(64), sizeof(double) * 4 * (h->nbt + 3), h->stream, IFL_ARGS);
-    else hipLaunchKernelGGL(k_iface_local<false>, g, dim3(64), sizeof(double) * 4 * (h->nbt + 3), h->stream, IFL_ARGS);
+        if (st->nt_max <= IF_NT_REGS) hipLaunchKernelGGL(k_iface_local<true>, g, dim3(64), sizeof(double) * 4 * (h->nbt + 3), h->stream, IFL_ARGS);
+        else hipLaunchKernelGGL(k_iface_local<false>, g, dim3(64), sizeof(double) * 4 * (h->nbt + 3), h->stream, IFL_ARGS);
 #undef IFL_ARGS
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    }
     return error_status();
 }
 
@@ -997,19 +995,18 @@ int sx_iface_reduce(sx_handle *h, const void *dev_recv, void *dev_send) {
     clear_error();
     IfaceState *st = h ? (IfaceState *)h->iface_state : nullptr;
     if (!st || !dev_recv || !dev_send) { set_error("sx_iface_reduce: invalid argument / not configured"); return 1; }
-    const int id = timer_id(h, "k_iface_reduce");
-    timer_begin(h, id);
-    const int ng = st->g1 - st->g0, RN = IF_R * st->n, RNp = (RN + 15) / 16 * 16;
-    if (ng > 0) {
-        const int nchunk = (h->K2 + 63) / 64;        // a block = 4 waves x 16 columns
+    {
+        TimedLaunch scope(h, "k_iface_reduce");
+        const int ng = st->g1 - st->g0, RN = IF_R * st->n, RNp = (RN + 15) / 16 * 16;
+        if (ng > 0) {
+            const int nchunk = (h->K2 + 63) / 64;        // a block = 4 waves x 16 columns
 #define IFR_ARGS dim3(ng * nchunk + ng), dim3(256), 0, h->stream, (const double *)dev_recv, (double *)dev_send, st->d_Q, h->d_cls, st->g0, ng, nchunk, \
                  h->Zb, h->K2, (int64_t)ng * h->K2, RN, RNp
-        if (RN <= 80) hipLaunchKernelGGL(k_iface_reduce<20>, IFR_ARGS);
-        else hipLaunchKernelGGL(k_iface_reduce<40>, IFR_ARGS);
+            if (RN <= 80) hipLaunchKernelGGL(k_iface_reduce<20>, IFR_ARGS);
+            else hipLaunchKernelGGL(k_iface_reduce<40>, IFR_ARGS);
 #undef IFR_ARGS
-        HIPCHK(hipGetLastError());
+        }
     }
-    timer_end(h);
     return error_status();
 }
 
@@ -1017,13 +1014,12 @@ int sx_iface_apply(sx_handle *h, const void *dev_recv) {
     clear_error();
     IfaceState *st = h ? (IfaceState *)h->iface_state : nullptr;
     if (!st || !dev_recv) { set_error("sx_iface_apply: invalid argument / not configured"); return 1; }
-    const int id = timer_id(h, "k_iface_apply");
-    timer_begin(h, id);
-    hipLaunchKernelGGL(k_iface_apply, dim3((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb), dim3(64), sizeof(double) * IF_E * h->nbt, h->stream, st->d_Y, (const double *)dev_recv,
-                       h->d_A + (int64_t)h->cell0 * h->C, st->d_owner, st->d_soff, st->d_cw, st->d_cs, h->d_cls, st->d_meta, h->d_gl, h->d_gr,
-                       st->d_Z, h->nbt, h->Zb, h->K2, h->C);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_iface_apply");
+        hipLaunchKernelGGL(k_iface_apply, dim3((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb), dim3(64), sizeof(double) * IF_E * h->nbt, h->stream, st->d_Y, (const double *)dev_recv,
+                           h->d_A + (int64_t)h->cell0 * h->C, st->d_owner, st->d_soff, st->d_cw, st->d_cs, h->d_cls, st->d_meta, h->d_gl, h->d_gr,
+                           st->d_Z, h->nbt, h->Zb, h->K2, h->C);
+    }
     return error_status();
 }
 

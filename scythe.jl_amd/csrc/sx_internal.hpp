@@ -488,7 +488,6 @@ struct sx_handle {
     std::vector<void *> allocs;
     // timers
     int timers_on = 0;
-    bool timer_skip = false;          // the launch in progress is not timed (sx_timer_only)
     std::string timer_only;           // when set, only this kernel gets its event pair
     std::vector<sx::Timer> timers;
     std::vector<sx::PendingEvent> pending;
@@ -545,9 +544,24 @@ void launch_a2a_pack(sx_handle *h, double *buf, int unpack);
 void launch_halo_add(sx_handle *h, const double *recv);
 void launch_nan_check(sx_handle *h);
 void launch_max_abs(sx_handle *h, unsigned long long *d_out);
-int timer_id(sx_handle *h, const char *name);
-void timer_begin(sx_handle *h, int id);
-void timer_end(sx_handle *h);
+// The bracket of one timed kernel launch (or of the launches one timer name covers): a launcher opens `TimedLaunch scope(h, "k_name");`
+// where its timed region starts and lets the scope end where the region ends, early returns included.  Construction looks the name up
+// (first use appends it: sx_get_timers lists names in that order) and, with timers on and the name not excluded by sx_timer_only,
+// records the begin event on h->stream as it is then.  Destruction checks the launch - a failed one goes to set_error as
+// "k_name: <hip error text>" - and records the scope's own end event on the stream the begin event went to.
+// Scopes do not nest: a launcher called inside its caller's scope (launch_solve_part, launch_solve_pcr, launch_semi_mfma) opens none.
+class TimedLaunch {
+public:
+    TimedLaunch(sx_handle *h, const char *name);
+    ~TimedLaunch();
+    TimedLaunch(const TimedLaunch &) = delete;
+    TimedLaunch &operator=(const TimedLaunch &) = delete;
+
+private:
+    const char *name;
+    hipStream_t stream = nullptr;
+    hipEvent_t end = nullptr;      // null: this launch is not timed
+};
 void timers_flush(sx_handle *h);
 void clear_error();
 int error_status();   // 1 if set_error has been called since the last clear_error

@@ -233,14 +233,14 @@ void colprof_grid_args(const sx_handle *h, ColProfArgs &pa) {
 }
 
 void launch_column_profiles(sx_handle *h, const ColProfArgs &pa, int n_batches, int nv) {
-    timer_begin(h, timer_id(h, "k_column_profiles"));
-    if (h->has_l)
-        hipLaunchKernelGGL(k_column_profiles, dim3((unsigned)((pa.Zb + 15) / 16), (unsigned)n_batches, (unsigned)nv), dim3(64), colprof_lds(h->kDim),
-                           h->stream, pa);
-    else
-        hipLaunchKernelGGL(k_column_profiles_rz, grid1((int64_t)pa.n_cols * pa.nprof * pa.Zb, 256), dim3(256), 0, h->stream, pa);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_column_profiles");
+        if (h->has_l)
+            hipLaunchKernelGGL(k_column_profiles, dim3((unsigned)((pa.Zb + 15) / 16), (unsigned)n_batches, (unsigned)nv), dim3(64), colprof_lds(h->kDim),
+                               h->stream, pa);
+        else
+            hipLaunchKernelGGL(k_column_profiles_rz, grid1((int64_t)pa.n_cols * pa.nprof * pa.Zb, 256), dim3(256), 0, h->stream, pa);
+    }
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
@@ -444,10 +444,10 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     ia.max_iter = max_iter <= 0 ? 60 : max_iter; ia.max_cross = max_cross; ia.n_carry = n_carry;
     // the profiles in; heights, directions, carried outputs, counts, status and the station values out
     st->scan_bytes = 8.0 * (double)Zb * nprof * n_cols + (12.0 + 8.0 * n_carry) * (double)n_hgt + 4.0 * ((double)n_levels + 1.0) * n_cols + 8.0 * (double)n_val;
-    timer_begin(h, timer_id(h, "k_isosurface"));
-    hipLaunchKernelGGL(k_isosurface, dim3((unsigned)n_cols), dim3(64), iso_lds(pl.n_ser, nz), h->stream, ia);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_isosurface");
+        hipLaunchKernelGGL(k_isosurface, dim3((unsigned)n_cols), dim3(64), iso_lds(pl.n_ser, nz), h->stream, ia);
+    }
 
     std::vector<double> ro(n_hgt + n_car + (values ? n_val : 0)), rp(profiles ? (size_t)nprof * Zb * n_cols : 0);   // held back until the call has succeeded: a failed call writes nothing
     std::vector<int> ri(n_int);

@@ -971,8 +971,7 @@ void sbw_phases_dump() {
 
 void launch_zinv(sx_handle *h, bool full) {
     if (!h->has_z || rz_fused(h)) return;          // RZ: the vertical inverse is part of k_rz_inverse (sx_rz.hip)
-    const int id = timer_id(h, "k_zinv");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_zinv");
     const int njobs = full ? h->njobs_zinv_full : h->njobs_zinv_eq;
     h->last_zinv_jobs = njobs;
     if (njobs > 0) {
@@ -980,7 +979,7 @@ void launch_zinv(sx_handle *h, bool full) {
         // Az is then needed only for the nodes the ring-wise inner rings read (cells [0, R_in / 3) -> nodes 0 .. R_in / 3 + 2)
         const int rows = (!full && h->node_mode && fft_fused_zinv(h)) ? (h->R_in > 0 ? std::min(h->nbt, h->R_in / MUBAR + 3) : 0) : h->nbt;
         h->last_zinv_rows = rows;
-        if (rows == 0) { timer_end(h); return; }
+        if (rows == 0) return;
         const ZinvPlan p = plan_zinv(h->geom, h->nz, h->K2, h->sp32, h->sw);
         dim3 g(p.grid_x, njobs, rows);
         const ColJob *jobs = full ? h->d_jobs_zinv_full : h->d_jobs_zinv_eq;
@@ -1002,9 +1001,7 @@ void launch_zinv(sx_handle *h, bool full) {
         }
 #undef ZINV
 #undef ZINV_T
-        HIPCHK(hipGetLastError());
     }
-    timer_end(h);
 }
 
 void launch_rl_inverse(sx_handle *h, bool full) {
@@ -1019,13 +1016,11 @@ void launch_rl_inverse(sx_handle *h, bool full) {
     }
     if (fft_path_ok(h)) { launch_rl_inverse_fft(h, mask); return; }
     if (dft_mfma_ok(h)) { launch_rl_inverse_dft(h, mask); return; }
-    const int id = timer_id(h, "k_rl_inverse");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_rl_inverse");
     const int cstride = (h->kmax_max + 1) | 1;
     const size_t lds = sizeof(double) * 2 * ZC * cstride;
     if (lds > 64 * 1024) {
         set_error("azimuthal inverse transform: rings with " + std::to_string(h->kmax_max) + " wavenumbers are outside every transform path (power-of-two ring tables up to 512 points, ring lengths that are multiples of 4 up to 5120 points, otherwise kmax <= 255)");
-        timer_end(h);
         return;
     }
     const double *az = h->has_z ? h->d_Az : h->d_A + (int64_t)h->cell0 * h->C;
@@ -1037,8 +1032,6 @@ void launch_rl_inverse(sx_handle *h, bool full) {
     if (h->f32) hipLaunchKernelGGL(k_rl_inverse<float>, g, dim3(256), lds, h->stream, az, planes_of<float>(h->d_phys, h->V, h->N), RL_ARGS);
     else hipLaunchKernelGGL(k_rl_inverse<double>, g, dim3(256), lds, h->stream, az, planes_of<double>(h->d_phys, h->V, h->N), RL_ARGS);
 #undef RL_ARGS
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 // the forward pair for the launch's variable window, or off (plan_fwd_cells: sx_plan.cpp)
@@ -1052,8 +1045,7 @@ void launch_fl_forward(sx_handle *h) {
     if (const CellsPlan cp = cells_plan(h); cp.on) { launch_fl_forward_cells(h, cp); return; }
     if (fft_path_ok(h)) { launch_fl_forward_fft(h); return; }
     if (dft_mfma_ok(h)) { launch_fl_forward_dft(h); return; }
-    const int id = timer_id(h, "k_fl_forward");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_fl_forward");
     const int xstride = h->L_max | 1;
     const size_t lds = sizeof(double) * ZC * xstride;
     if (lds > 64 * 1024) {       // the scalar kernel stages a whole ring; longer rings need the matrix-core DFT (lengths that are multiples of 4)
@@ -1063,13 +1055,10 @@ void launch_fl_forward(sx_handle *h) {
     dim3 g((h->nz + ZC - 1) / ZC, h->V, h->nrings);
     hipLaunchKernelGGL(k_fl_forward, g, dim3(256), lds, h->stream, h->d_np1, h->d_Fl, h->d_L, h->d_kmax, h->d_pstart,
                        h->d_twoff, h->d_tw, h->d_phoff, h->d_ph, h->V, h->nz, h->K2, h->N, h->has_l, xstride);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 static void launch_nodes_z(sx_handle *h, const CellsPlan &p) {
-    const int id = timer_id(h, "k_sbz");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_sbz");
     dim3 g((h->K2 + p.bw - 1) / p.bw, h->v_cnt, p.zsegs);
     const int64_t plane = (int64_t)h->V * h->nz * h->K2, flo = (int64_t)h->v_lo * h->nz * h->K2, blo = (int64_t)h->v_lo * h->Zb * h->K2;
 #define NODES_Z(...) hipLaunchKernelGGL((__VA_ARGS__), g, dim3(p.zthreads), 0, h->stream, h->d_Fn + flo, h->d_Fn + (int64_t)h->nbt * plane + flo, \
@@ -1081,8 +1070,6 @@ static void launch_nodes_z(sx_handle *h, const CellsPlan &p) {
     default: NODES_Z(k_nodes_z<128, 32>);
     }
 #undef NODES_Z
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 void launch_sb(sx_handle *h) {
@@ -1090,8 +1077,7 @@ void launch_sb(sx_handle *h) {
     const SbPlan p = plan_sb(h->geom, h->nz, h->Zb, h->K2, h->v_cnt, h->ncells, h->sp32, h->sw);
     if (p.kernel == SbKernel::rz_forward) { launch_rz_forward(h); return; }
     if (p.kernel == SbKernel::refused) { set_error("launch_sb: fp32 ring spectra (storage_f32 = 2) need the matrix-core sliding-window kernel"); return; }
-    const int id = timer_id(h, h->has_z ? "k_sbz" : "k_sb");       // k_sbz: fused with the vertical forward transform
-    timer_begin(h, id);
+    TimedLaunch scope(h, h->has_z ? "k_sbz" : "k_sb");       // k_sbz: fused with the vertical forward transform
     if (p.kernel == SbKernel::sb) {
         const int64_t plane = (int64_t)h->V * h->nz * h->K2;
         dim3 g((unsigned)((plane + 255) / 256), h->nbt);
@@ -1132,14 +1118,11 @@ void launch_sb(sx_handle *h) {
         }
 #undef SBW
     }
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 
 void launch_solve(sx_handle *h) {
-    const int id = timer_id(h, "k_solve");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_solve");
     dim3 g((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb);
     // few right-hand sides (the R grid's one column, RZ grids, small RL patches): LDS-staged parallel cyclic reduction (sx_pcr.hip)
     // instead of one wave's serial recurrence per 64 columns
@@ -1151,14 +1134,12 @@ void launch_solve(sx_handle *h) {
     if (h->last_solve_part) {
         const int64_t clo = (int64_t)h->v_lo * h->Zb * h->K2;
         launch_solve_part(h, h->d_Bsrc + clo, h->d_A + clo, h->v_lo * h->Zb, ngroups);
-        timer_end(h);
         return;
     }
     if (pcr_wanted(h, ncols)) {
         const int64_t clo = contiguous ? (int64_t)h->v_lo * h->Zb * h->K2 : 0;
         launch_solve_pcr(h, contiguous, h->d_Bsrc + clo, h->d_rowoff, h->d_neg1, h->d_A + clo, h->d_aoff, h->d_neg1,
                          contiguous ? h->v_lo * h->Zb : 0, ngroups, h->C);
-        timer_end(h);
         return;
     }
     if (contiguous) {   // internal contiguous B: no offset tables needed; the variable window through the base pointers
@@ -1172,19 +1153,15 @@ void launch_solve(sx_handle *h) {
         hipLaunchKernelGGL(k_solve<false>, g, dim3(64), sizeof(double) * 8 * h->b_rDim, h->stream, h->d_Bsrc, h->d_rowoff, h->d_neg1, h->d_A, h->d_aoff,
                            h->d_neg1, h->d_cls, h->d_cmeta, h->d_gl, h->d_gr, h->d_Lband, h->d_Ldinv, h->d_Larrow, h->b_rDim, h->Zb,
                            h->K2, 0, h->C);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 // transposed solve: my column groups [g0, g1), right-hand sides from the all-to-all receive buffer, solution rows into
 // the all-to-all send buffer (both [tile][row][my columns]; a row shared by two tiles is summed on input, duplicated on output)
 void launch_solve_a2a(sx_handle *h, const double *recv, double *send) {
-    const int id = timer_id(h, "k_solve");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_solve");
     const int ng = h->a2a_g1 - h->a2a_g0;
     if (ng > 0 && pcr_wanted(h, (int64_t)ng * (h->K2 > 1 ? h->K2 - 1 : 1))) {
         launch_solve_pcr(h, false, recv, h->d_a2a_offA, h->d_a2a_offB, send, h->d_a2a_offA, h->d_a2a_offB, h->a2a_g0, ng, 0);
-        timer_end(h);
         return;
     }
     if (ng > 0) {
@@ -1195,29 +1172,21 @@ void launch_solve_a2a(sx_handle *h, const double *recv, double *send) {
         if (single) hipLaunchKernelGGL((k_solve<false, false>), dim3((h->K2 - 2 + 63) / 64 + 1, ng), dim3(64), sizeof(double) * 8 * h->b_rDim, h->stream, A2A_ARGS);
         else hipLaunchKernelGGL((k_solve<false, true>), dim3(bx_pair, ng), dim3(64), sizeof(double) * 8 * h->b_rDim, h->stream, A2A_ARGS);
 #undef A2A_ARGS
-        HIPCHK(hipGetLastError());
     }
-    timer_end(h);
 }
 
 void launch_a2a_pack(sx_handle *h, double *buf, int unpack) {
-    const int id = timer_id(h, unpack ? "k_a2a_unpack" : "k_a2a_pack");
-    timer_begin(h, id);
+    TimedLaunch scope(h, unpack ? "k_a2a_unpack" : "k_a2a_pack");
     dim3 g((unsigned)((h->C + 255) / 256), h->nbt);
     const double *arr = unpack ? h->d_A : h->d_Btile;
     hipLaunchKernelGGL(k_a2a_pack, g, dim3(256), 0, h->stream, arr, buf, h->d_a2a_owner, h->d_a2a_soff, h->d_a2a_cw, h->d_a2a_cs,
                        h->K2, h->C, unpack, (int64_t)(unpack ? h->cell0 : 0));
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 void launch_halo_add(sx_handle *h, const double *recv) {
-    const int id = timer_id(h, "k_halo_add");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_halo_add");
     const int64_t n = 3 * h->C;
     hipLaunchKernelGGL(k_halo_add, grid1(n, 256), dim3(256), 0, h->stream, h->d_Btile, recv, n);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 void launch_max_abs(sx_handle *h, unsigned long long *d_out) {

@@ -264,10 +264,10 @@ int sx_parcels_advance(sx_handle *h, double dt) {
     a.wrap = !h->has_l && st->var[0] != 0 && h->bcl[st->var[0] - 1] == SX_BC_PERIODIC && h->bcr[st->var[0] - 1] == SX_BC_PERIODIC;
     // 4 node rows x every column but the padding block, once per velocity variable and parcel (frozen parcels read nothing: an upper bound)
     st->last_bytes = 8.0 * 4.0 * (double)a.Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv * (double)st->n;
-    timer_begin(h, timer_id(h, "k_parcels"));
-    hipLaunchKernelGGL(k_parcels, dim3((unsigned)st->n), dim3(parcel_threads(h)), parcel_lds(h), h->stream, a);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_parcels");
+        hipLaunchKernelGGL(k_parcels, dim3((unsigned)st->n), dim3(parcel_threads(h)), parcel_lds(h), h->stream, a);
+    }
     return error_status();
 }
 

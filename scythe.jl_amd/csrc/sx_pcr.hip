@@ -285,7 +285,6 @@ void launch_solve_pcr(sx_handle *h, bool linear, const double *Bsrc, const int64
     else
         hipLaunchKernelGGL(k_solve_pcr<false>, dim3(pl.nsegs), dim3(pl.threads), pl.lds, h->stream, Bsrc, boffA, boffB, A, aoffA, aoffB,
                            st->d_classes, pl.d_segs, h->b_rDim, pl.logR, stride);
-    HIPCHK(hipGetLastError());
 }
 
 }  // namespace sx

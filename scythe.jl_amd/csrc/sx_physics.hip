@@ -1154,8 +1154,7 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
         if (h->d_G) a.G = planes_of<ST>(h->d_G, h->V, h->NG);
         a.phi = h->d_phi; a.NG = h->NG; a.L = h->uniform_L; a.nrings = h->nrings;
         if (split > 0 && part != 2) {
-            const int id = timer_id(h, split < h->Nh ? "k_phys_hrbl_inner" : "k_phys_hrbl");
-            timer_begin(h, id);
+            TimedLaunch scope(h, split < h->Nh ? "k_phys_hrbl_inner" : "k_phys_hrbl");
             a.col0 = 0; a.col1 = split;
 #define RING_LAUNCH(NZ_, CPB_)                                                                                                     \
             do {                                                                                                                      \
@@ -1166,12 +1165,9 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
             else if (h->nz == 32) RING_LAUNCH(32, PCPB);
             else RING_LAUNCH(128, 8);
 #undef RING_LAUNCH
-            HIPCHK(hipGetLastError());
-            timer_end(h);
         }
         if (split < h->Nh && part != 1) {
-            const int id = timer_id(h, "k_phys_hrbl");
-            timer_begin(h, id);
+            TimedLaunch scope(h, "k_phys_hrbl");
             a.col0 = split; a.col1 = h->Nh;
             const int ncell = (h->nrings - h->R_in) / MUBAR;         // R_in is a multiple of 3 (sx_create)
 #ifdef SX_PHASES
@@ -1186,34 +1182,22 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
             else if (h->nz == 32) CELL_LAUNCH(32, 8);
             else CELL_LAUNCH(128, 4);   // 512 threads, one workgroup per CU: 12 of 16 MFMA columns (LAM 2: 6 of 16, 3.23 vs 2.58 ms at config 5)
 #undef CELL_LAUNCH
-            HIPCHK(hipGetLastError());
-            timer_end(h);
         }
     } else if (h->eq == SX_EQ_ONEWAY_SW_HRBL) {
-        const int id = timer_id(h, "k_phys_hrbl");
-        timer_begin(h, id);
+        TimedLaunch scope(h, "k_phys_hrbl");
         const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
         const int bs = cpb * h->nz;
         const size_t lds = sizeof(double) * 5 * cpb * h->nz;
         hipLaunchKernelGGL(k_phys_hrbl<ST>, grid1(h->Nh, cpb), dim3(bs), lds, h->stream, a, cpb);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
     } else if (h->eq == SX_EQ_RAINFALL_TEST) {
-        const int id = timer_id(h, "k_phys_rain");
-        timer_begin(h, id);
+        TimedLaunch scope(h, "k_phys_rain");
         hipLaunchKernelGGL(k_phys_rain<ST>, grid1(h->N, 256), dim3(256), 0, h->stream, a);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
     } else {
-        const int id = timer_id(h, "k_phys_pointwise");
-        timer_begin(h, id);
+        TimedLaunch scope(h, "k_phys_pointwise");
         hipLaunchKernelGGL(k_phys_pointwise<ST>, grid1(h->N, 256), dim3(256), 0, h->stream, a);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
     }
     if (h->semi && h->eq != SX_EQ_NONE) {
-        const int id = timer_id(h, "k_semiimplicit");
-        timer_begin(h, id);
+        TimedLaunch scope(h, "k_semiimplicit");
         SemiArgs s;
         s.np1 = h->d_np1;
         s.In = h->d_I[h->rot % 3]; s.I1 = h->d_I[(h->rot + 1) % 3]; s.I2 = h->d_I[(h->rot + 2) % 3];
@@ -1224,17 +1208,12 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
         const SemiPlan sp = plan_semi(h->nz, h->Nh, h->sw);
         if (sp.mfma) launch_semi_mfma(h, s);               // the four column operators on the matrix cores (sx_rz.hip)
         else hipLaunchKernelGGL(k_semiimplicit, dim3((unsigned)sp.wgs), dim3(sp.threads), (size_t)sp.lds, h->stream, s, sp.cpb);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
     }
     if (h->eq == SX_EQ_RAINFALL_TEST) {        // after the explicit and the semi-implicit step (src/testModels.jl:572-580)
-        const int id = timer_id(h, "k_condensation");
-        timer_begin(h, id);
+        TimedLaunch scope(h, "k_condensation");
         const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
         const size_t lds = sizeof(int) * 2 * cpb * (1 + h->nz);
         hipLaunchKernelGGL(k_condensation, grid1(h->Nh, cpb), dim3(cpb * h->nz), lds, h->stream, h->d_np1, h->d_ref, h->N, h->nz, cpb);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
     }
     if (h->eq != SX_EQ_NONE && part != 1) h->rot = (h->rot + 2) % 3;
 }

@@ -161,18 +161,18 @@ int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *co
     HIPCHK(hipStreamSynchronize(dst->stream));      // the destination's own work on var_np1, B and A is complete before another stream writes them
     if (error_status()) return 1;
     st->last_bytes = red_bytes(src, source, planes, n_planes) + 8.0 * n_out * (double)src->N;
-    timer_begin(src, timer_id(src, "k_project"));
-    scan_dispatch(src, source, [&](auto st_t, auto, auto P) {      // W = 2 where N is even (above); no RINGS form
-        auto launch = [&](auto width) {
-            constexpr int W = decltype(width)::value;
-            hipLaunchKernelGGL((k_project<decltype(st_t), W>), dim3(scan_flat_blocks(src, W)), dim3(RED_T), 0, src->stream, P, src->V, src->N, src->nz,
-                               src->d_r, prog, pd, dst->d_np1);
-        };
-        if (src->N % 2 == 0) launch(std::integral_constant<int, 2>());
-        else launch(std::integral_constant<int, 1>());
-    });
-    HIPCHK(hipGetLastError());
-    timer_end(src);
+    {
+        TimedLaunch scope(src, "k_project");
+        scan_dispatch(src, source, [&](auto st_t, auto, auto P) {      // W = 2 where N is even (above); no RINGS form
+            auto launch = [&](auto width) {
+                constexpr int W = decltype(width)::value;
+                hipLaunchKernelGGL((k_project<decltype(st_t), W>), dim3(scan_flat_blocks(src, W)), dim3(RED_T), 0, src->stream, P, src->V, src->N, src->nz,
+                                   src->d_r, prog, pd, dst->d_np1);
+            };
+            if (src->N % 2 == 0) launch(std::integral_constant<int, 2>());
+            else launch(std::integral_constant<int, 1>());
+        });
+    }
     HIPCHK(hipEventRecord(st->done, src->stream));
     HIPCHK(hipStreamWaitEvent(dst->stream, st->done, 0));
     if (error_status()) return 1;

@@ -230,25 +230,25 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
     if (!st->d_part.grow((size_t)sg->n_items * n_out * h->nz, "sx_reduce") || !st->d_out.grow(n_res, "sx_reduce")) return 1;
     st->last_bytes = red_bytes(h, source, planes, n_planes);
 
-    timer_begin(h, timer_id(h, "k_reduce"));
-    scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
-        constexpr bool RINGS = decltype(rings)::value;
-        hipLaunchKernelGGL((k_reduce<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
-                           h->V, h->N, h->nz, sg->d_items, h->d_pstart, h->d_r, prog, st->d_part);
-    });
-    HIPCHK(hipGetLastError());
-    timer_end(h);
-    timer_begin(h, timer_id(h, "k_reduce_final"));
-    if (kind == SX_REDUCE_AZIMUTH)
-        hipLaunchKernelGGL(k_reduce_mean, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_part, sg->d_first, h->d_L, h->nrings, h->nz,
-                           n_out, st->d_out);
-    else {
-        hipLaunchKernelGGL(k_reduce_domain, dim3((unsigned)n_out, (unsigned)st->blocks2), dim3(RED_TF), 0, h->stream, st->d_part, sg->d_items,
-                           sg->d_wrl, sg->d_wz, sg->n_items, h->nz, n_out, st->d_part2);
-        hipLaunchKernelGGL(k_reduce_domain_sum, dim3(1), dim3(64), 0, h->stream, st->d_part2, st->blocks2, n_out, st->d_out);
+    {
+        TimedLaunch scope(h, "k_reduce");
+        scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
+            constexpr bool RINGS = decltype(rings)::value;
+            hipLaunchKernelGGL((k_reduce<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
+                               h->V, h->N, h->nz, sg->d_items, h->d_pstart, h->d_r, prog, st->d_part);
+        });
     }
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_reduce_final");
+        if (kind == SX_REDUCE_AZIMUTH)
+            hipLaunchKernelGGL(k_reduce_mean, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_part, sg->d_first, h->d_L, h->nrings, h->nz,
+                               n_out, st->d_out);
+        else {
+            hipLaunchKernelGGL(k_reduce_domain, dim3((unsigned)n_out, (unsigned)st->blocks2), dim3(RED_TF), 0, h->stream, st->d_part, sg->d_items,
+                               sg->d_wrl, sg->d_wz, sg->n_items, h->nz, n_out, st->d_part2);
+            hipLaunchKernelGGL(k_reduce_domain_sum, dim3(1), dim3(64), 0, h->stream, st->d_part2, st->blocks2, n_out, st->d_out);
+        }
+    }
     std::vector<double> res(n_res);      // held back until the call has succeeded: a failed call writes nothing to out
     HIPCHK(hipMemcpyAsync(res.data(), st->d_out, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));

@@ -360,13 +360,13 @@ int sx_regrid(sx_handle *src, sx_handle *dst, const double *centre, const int32_
         ra.P = st->d_P; ra.ET = tab->d_ET; ra.pidx = st->d_pidx; ra.rv = st->d_rv + g_first[g]; ra.out = dst->d_np1;
         ra.N = dst->N; ra.n_cols = (int)n_cols; ra.nprof = np; ra.Zb = Zb; ra.Kp = tab->Kp; ra.Mp = tab->Mp; ra.nz = dst->nz;
         ra.nrv = g_first[g + 1] - g_first[g];
-        timer_begin(src, timer_id(src, "k_regrid_levels"));
-        if (mfma)
-            hipLaunchKernelGGL(k_regrid_levels, dim3((unsigned)((n_cols + 15) / 16), (unsigned)ra.nrv), dim3(64), sizeof(double) * tab->Kp * RG_CS, src->stream, ra);
-        else
-            hipLaunchKernelGGL(k_regrid_levels_lane, grid1(n_cols * dst->nz * ra.nrv, 256), dim3(256), 0, src->stream, ra);
-        HIPCHK(hipGetLastError());
-        timer_end(src);
+        {
+            TimedLaunch scope(src, "k_regrid_levels");
+            if (mfma)
+                hipLaunchKernelGGL(k_regrid_levels, dim3((unsigned)((n_cols + 15) / 16), (unsigned)ra.nrv), dim3(64), sizeof(double) * tab->Kp * RG_CS, src->stream, ra);
+            else
+                hipLaunchKernelGGL(k_regrid_levels_lane, grid1(n_cols * dst->nz * ra.nrv, 256), dim3(256), 0, src->stream, ra);
+        }
     }
     HIPCHK(hipEventRecord(st->done, src->stream));
     HIPCHK(hipStreamWaitEvent(dst->stream, st->done, 0));

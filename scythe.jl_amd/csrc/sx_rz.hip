@@ -413,8 +413,7 @@ void launch_semi_mfma(sx_handle *h, const SemiArgs &a) {
 bool rz_fused(const sx_handle *h) { return h->sw.rz_fused && h->geom == SX_GEOM_RZ && !h->sp32; }
 
 void launch_rz_inverse(sx_handle *h, const int *d_mask) {
-    const int id = timer_id(h, "k_rz_inverse");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_rz_inverse");
     const RzInvPlan p = plan_rz_inverse(h->nz, h->Zb, h->ncells, h->V, h->f32, h->sw);      // SX_RZ_INV=0 (A/B): the ring-tile form
     const dim3 g(p.gx, p.gy, p.gz);
     const size_t lds = (size_t)p.lds;
@@ -424,8 +423,6 @@ void launch_rz_inverse(sx_handle *h, const int *d_mask) {
                                        d_mask, h->V, h->nz, h->Zb, h->ncells, h->nbt, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
         if (h->f32) RZ_INVN(float); else RZ_INVN(double);
 #undef RZ_INVN
-        HIPCHK(hipGetLastError());
-        timer_end(h);
         return;
     }
     if (p.attr) {
@@ -436,18 +433,13 @@ void launch_rz_inverse(sx_handle *h, const int *d_mask) {
                                       d_mask, h->V, h->nz, h->Zb, h->nrings, h->N, h->C, h->slot[0], h->slot[1], h->slot[2], h->slot[5], h->slot[6])
     if (h->f32) RZ_INV(float); else RZ_INV(double);
 #undef RZ_INV
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 void launch_rz_forward(sx_handle *h) {
-    const int id = timer_id(h, "k_rz_forward");
-    timer_begin(h, id);
+    TimedLaunch scope(h, "k_rz_forward");
     const RzFwdPlan p = plan_rz_forward(h->nz, h->Zb, h->ncells, h->v_cnt);
     hipLaunchKernelGGL(k_rz_forward, dim3(p.gx, p.gy, p.gz), dim3(256), (size_t)p.lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
                        h->d_Btile + (int64_t)h->v_lo * h->Zb, h->d_phi, h->d_wq, h->d_CBT, h->ncells, h->nbt, h->V, h->nz, h->Zb, h->N, h->C, p.mt_per_wg);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
 }
 
 }  // namespace sx

@@ -281,18 +281,18 @@ int sx_spectrum(sx_handle *h, int32_t kind, int32_t n_pairs, const int32_t *pair
     st->last_bytes = 0;
     for (int i = 0; i < h->nrings; i++) st->last_bytes += n_planes * 8.0 * 4.0 * a.Zb * (h->has_l ? 2 * st->kcap[i] + 1 : 1);
 
-    timer_begin(h, timer_id(h, "k_spectrum"));
-    if (a.Zb <= 16) spec_launch_ks<4>(h, st, a, domain);
-    else if (a.Zb <= 48) spec_launch_ks<12>(h, st, a, domain);
-    else spec_launch_ks<32>(h, st, a, domain);
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_spectrum");
+        if (a.Zb <= 16) spec_launch_ks<4>(h, st, a, domain);
+        else if (a.Zb <= 48) spec_launch_ks<12>(h, st, a, domain);
+        else spec_launch_ks<32>(h, st, a, domain);
+    }
     if (domain) {
-        timer_begin(h, timer_id(h, "k_spectrum_final"));
-        hipLaunchKernelGGL(k_spectrum_final, dim3((unsigned)((K + 15) / 16), (unsigned)n_pairs), dim3(SPEC_T), 0, h->stream, st->d_part,
-                           st->d_wring, h->nrings, K, st->d_out);
-        HIPCHK(hipGetLastError());
-        timer_end(h);
+        {
+            TimedLaunch scope(h, "k_spectrum_final");
+            hipLaunchKernelGGL(k_spectrum_final, dim3((unsigned)((K + 15) / 16), (unsigned)n_pairs), dim3(SPEC_T), 0, h->stream, st->d_part,
+                               st->d_wring, h->nrings, K, st->d_out);
+        }
     }
     std::vector<double> res(n_res);      // held back until the call has succeeded: a failed call writes nothing to out
     HIPCHK(hipMemcpyAsync(res.data(), st->d_out, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));

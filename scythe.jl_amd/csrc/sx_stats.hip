@@ -241,20 +241,20 @@ int sx_stats_accumulate(sx_handle *h, double time, double weight) {
     const ScanGrid *sg = scan_grid(h, "sx_stats", false);      // there since the set was installed
     if (!sg) return 1;
     st->last_bytes = red_bytes(h, st->source, st->planes, st->n_planes) + 32.0 * st->n_out * (double)h->N;
-    timer_begin(h, timer_id(h, "k_stats"));
-    scan_dispatch(h, st->source, [&](auto st_t, auto rings, auto P) {
-        constexpr bool RINGS = decltype(rings)::value;
-        auto launch = [&](auto width) {
-            constexpr int W = decltype(width)::value;
-            const dim3 grid = RINGS ? dim3((unsigned)sg->n_items, (unsigned)st->parts) : dim3(scan_flat_blocks(h, W));
-            hipLaunchKernelGGL((k_stats<decltype(st_t), RINGS, W>), grid, dim3(RED_T), 0, h->stream, P, h->V, h->N, h->nz, sg->d_items, h->d_pstart,
-                               h->d_r, st->prog, st->d_acc, time, weight, st->samples == 0 ? 1 : 0);
-        };
-        if (stat_width(h) == 2) launch(std::integral_constant<int, 2>());
-        else launch(std::integral_constant<int, 1>());
-    });
-    HIPCHK(hipGetLastError());
-    timer_end(h);
+    {
+        TimedLaunch scope(h, "k_stats");
+        scan_dispatch(h, st->source, [&](auto st_t, auto rings, auto P) {
+            constexpr bool RINGS = decltype(rings)::value;
+            auto launch = [&](auto width) {
+                constexpr int W = decltype(width)::value;
+                const dim3 grid = RINGS ? dim3((unsigned)sg->n_items, (unsigned)st->parts) : dim3(scan_flat_blocks(h, W));
+                hipLaunchKernelGGL((k_stats<decltype(st_t), RINGS, W>), grid, dim3(RED_T), 0, h->stream, P, h->V, h->N, h->nz, sg->d_items, h->d_pstart,
+                                   h->d_r, st->prog, st->d_acc, time, weight, st->samples == 0 ? 1 : 0);
+            };
+            if (stat_width(h) == 2) launch(std::integral_constant<int, 2>());
+            else launch(std::integral_constant<int, 1>());
+        });
+    }
     if (error_status()) return 1;
     if (st->samples == 0) st->t_first = time;
     st->t_last = time;

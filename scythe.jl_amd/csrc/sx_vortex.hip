@@ -394,14 +394,14 @@ int sx_vortex_harmonics(sx_handle *h, const double centre[2], const double *moti
         for (size_t c0 = 0; c0 < live.size(); c0 += batch) {
             const unsigned nb = (unsigned)std::min<size_t>(batch, live.size() - c0);
             ra.circ = fa.circ = st->d_circ + c0;
-            timer_begin(h, timer_id(h, "k_vortex_rings"));
-            hipLaunchKernelGGL(k_vortex_rings, dim3((unsigned)nchunks, nb), dim3(VORTEX_T), lds_r, h->stream, ra);
-            HIPCHK(hipGetLastError());
-            timer_end(h);
-            timer_begin(h, timer_id(h, "k_vortex_finish"));
-            hipLaunchKernelGGL(k_vortex_finish, dim3(nb, (unsigned)plan.nout), dim3(VORTEX_T), lds_f, h->stream, fa);
-            HIPCHK(hipGetLastError());
-            timer_end(h);
+            {
+                TimedLaunch scope(h, "k_vortex_rings");
+                hipLaunchKernelGGL(k_vortex_rings, dim3((unsigned)nchunks, nb), dim3(VORTEX_T), lds_r, h->stream, ra);
+            }
+            {
+                TimedLaunch scope(h, "k_vortex_finish");
+                hipLaunchKernelGGL(k_vortex_finish, dim3(nb, (unsigned)plan.nout), dim3(VORTEX_T), lds_f, h->stream, fa);
+            }
         }
         std::vector<double> dev(n_res);
         HIPCHK(hipMemcpyAsync(dev.data(), st->d_res, sizeof(double) * n_res, hipMemcpyDeviceToHost, h->stream));
