@@ -968,6 +968,67 @@ int sx_project_check(const sx_grid_desc *src, const sx_grid_desc *dst, int32_t s
 int sx_project_point(int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_out, int32_t n_planes,
                      const int32_t *planes /*[n_planes][2]*/, const double *val /*[n_planes]*/, double r, double *out /*[n_out]*/);
 
+/* --- function programs: nonlinear derived fields as variables (speed, potential vorticity, T, p, theta_e) ---------------
+ * A field program is polynomial.  A FUNCTION program is a field program, whose n_mid <= 16 outputs are now called the mids, followed by
+ * a list of n_ops <= 32 operations on a register file per gridpoint:
+ *     registers 0 .. n_mid - 1   the mids at the point (q_o exactly as sx_project forms it)
+ *     register  n_mid + i        the result of operation i, ops[i][4] = fn, a, b, c
+ * An operand >= 0 is a register and must be lower than the operation's own register - the list is in evaluation order -; an operand
+ * k < 0 is the constant consts[-1 - k], n_consts <= 16.  Operands an operation does not take are ignored.
+ * Exactly rounded operations, one IEEE operation each (the library is built without contraction, so the host reproduces them bit
+ * for bit):
+ *     ADD a + b   SUB a - b   MUL a * b   DIV a / b   NEG -a   ABS |a|   SQRT sqrt(a)
+ *     MIN, MAX    the smaller / larger of a and b; if a is NaN the result is a, else if b is NaN it is b (a NaN operand is
+ *                 returned, never dropped); of two equal operands (-0.0 and +0.0 among them) the result is a
+ *     SELECT      a >= 0 ? b : c; a NaN a takes c
+ * Math-library operations (within the library's error of the rounded argument; host and device libraries differ in the last bits):
+ *     EXP exp(a)   LOG log(a)   POW pow(a, b)   ATAN2 atan2(a, b)
+ * Point data (no register operands):
+ *     R           the point's first coordinate (the double sx_get_gridpoints returns)
+ *     Z           the point's height; refused on R / RL grids
+ *     REF         a = profile (0 sbar, 1 xibar, 2 mubar), b = slot (0 value, 1 d/dz, 2 d2/dz2), both literal: the entry of the
+ *                 source handle's sx_model_desc.ref_state [3][3][zDim] at the point's level; refused when the source has none
+ * Composites, which call the functions the equation-set kernels call (csrc/sx_thermo.hpp): a diagnosed temperature is bit for bit
+ * the one Euler_test / rainfall_test step with
+ *     AHYP ahyp(a)   DRY_DENSITY dry_density(a)   TEMPERATURE temperature(s = a, rho_d = b, q_v = c)   PRESSURE pressure(Tk = a, rho_d = b,
+ *     q_v = c) [hPa]   VAPOR_PRESSURE vapor_pressure(p = a, q_v = b)   ESAT_BUCK sat_pressure_liquid_buck(Tk = a, p = b)   L_V L_v(Tk = a)
+ * An argument outside a function's domain (the root of a negative, the logarithm of zero, a division by zero) gives the IEEE NaN / Inf
+ * at that point and nowhere else; it is not refused.
+ *
+ * sx_derive evaluates the program at every gridpoint of src (k_derive: streaming, one lane per point, the planes the mids name loaded
+ * once, the register file a column of LDS per lane, the operation list uniform across the wave; no atomics, nothing across lanes),
+ * writes register reg_dst[v] as the var_np1 plane of variable v (0-based position) of the companion handle dst - a mid may be written
+ * directly, a register may serve several variables, and dst has at most 48 variables, the size of the register file - and runs dst's
+ * forward transform and banded solve.  Source, streams, the event between them, what is overwritten in dst and
+ * what stays bitwise in src are exactly sx_project's, and so are the refusals of the handles and of the two grids.  Two calls agree
+ * bitwise, and a register's value does not depend on what else the program computes.
+ * Refused, with a message and before anything is written: a null handle; a null pointer with a non-zero count; dst == src; a dst with
+ * an equation set; a src or dst that is not a one-tile patch, or grids that differ (sx_project); whatever sx_reduce_planes refuses of
+ * the mids (n_mid in place of n_out); a mid with no term; n_ops > 32; n_consts > 16; an unknown fn; an operand that names the
+ * operation's own or a later register, or a constant beyond n_consts; Z on a grid without a vertical; REF on a source without a
+ * reference state, or with a profile or slot outside 0 .. 2; n_reg_dst other than dst's number of variables, or more than 48; a reg_dst outside
+ * 0 .. n_mid + n_ops - 1.
+ * sx_kernel_bytes("k_derive") gives the planes named x N x their element size (8, 4 for an fp32-stored plane) + dst n_vars x N x 8.
+ *
+ * sx_derive_check is that validation for two descriptors on the host (all but the null handles, dst == src and the equation set);
+ * has_ref_state says whether the source carries a reference state, which a descriptor does not.  sx_derive_point states every
+ * register at ONE point on the host, packed and formed by the code the kernel runs: val[j] is the value of plane (planes[j][0],
+ * planes[j][1]) there, r and z the point's coordinates, ref[profile][slot] the reference state at its level (NULL: REF is refused;
+ * Z is always allowed).  Pure host helpers (no handle, no device). */
+enum { SX_FN_ADD = 0, SX_FN_SUB, SX_FN_MUL, SX_FN_DIV, SX_FN_NEG, SX_FN_ABS, SX_FN_MIN, SX_FN_MAX, SX_FN_SQRT, SX_FN_SELECT,
+       SX_FN_EXP, SX_FN_LOG, SX_FN_POW, SX_FN_ATAN2, SX_FN_R, SX_FN_Z, SX_FN_REF, SX_FN_AHYP, SX_FN_TEMPERATURE, SX_FN_ESAT_BUCK,
+       SX_FN_DRY_DENSITY, SX_FN_PRESSURE, SX_FN_VAPOR_PRESSURE, SX_FN_L_V, SX_FN_COUNT };
+int sx_derive(sx_handle *src, int32_t source, int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_mid,
+              int32_t n_ops, const int32_t *ops /*[n_ops][4] = fn, a, b, c*/, int32_t n_consts, const double *consts,
+              sx_handle *dst, const int32_t *reg_dst /*[dst n_vars]: the register each destination variable receives*/);
+int sx_derive_check(const sx_grid_desc *src, int32_t has_ref_state, const sx_grid_desc *dst, int32_t source, int32_t n_terms,
+                    const int32_t *terms, int32_t n_mid, int32_t n_ops, const int32_t *ops, int32_t n_consts, int32_t n_reg_dst,
+                    const int32_t *reg_dst);
+int sx_derive_point(int32_t n_terms, const double *coef, const int32_t *terms, int32_t n_mid, int32_t n_ops, const int32_t *ops,
+                    int32_t n_consts, const double *consts, int32_t n_planes, const int32_t *planes /*[n_planes][2]*/,
+                    const double *val /*[n_planes]*/, double r, double z, const double *ref /*[3][3] or NULL*/,
+                    double *regs /*[n_mid + n_ops]*/);
+
 /* --- onto another grid: resize, re-level, re-centre -------------------------------------------------------------------
  * The restart-at-new-resolution and vortex-following primitive: sx_regrid lays the state of src down on the grid of dst.  It adds no
  * numerics of its own: the values are the continuous function sx_evaluate defines, the coefficients the projection

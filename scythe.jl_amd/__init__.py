@@ -8,7 +8,8 @@ from .model import (CubicBSpline, Chebyshev, GridParameters, ModelParameters, Gr
                     spectrum_check, pack_spectrum_pairs, companion_grid, elliptic_check, antiderivative_check, Refined, free_mask, newton_step,
                     Crossings, bracket_step, Isosurface, isosurface_check, column_series, columns_of, Distribution, distribution_slot, distribution_check,
                     pack_vortex_fields, default_vortex_n_az, vortex_check, Statistics, pack_statistics, companion_params, project_check,
-                    project_point, program_of_outputs, field_programs, regrid_check, regrid_columns)
+                    project_point, program_of_outputs, field_programs, regrid_check, regrid_columns, FunctionProgram,
+                    pack_function_program, derive_check, derive_point, function_programs, thermo_programs)
 from .driver import (PatchLayout, LocalExchange, DistExchange, A2ALayout, LocalA2AExchange, DistA2AExchange, LibExchange, LocalLibExchange, ModelRun,
                      integrate_model, Located, WindRadii, Cfad, Exceedance, Quantile, VortexProfile, Swath)
 from .io import read_physical_grid, write_output, write_gridded_output, write_parcels, write_statistics, statistics_header

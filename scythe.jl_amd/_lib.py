@@ -21,6 +21,13 @@ REDUCE_SOURCE = {"physical": 0, "state": 1}      # SX_REDUCE_PHYSICAL / SX_REDUC
 DIST_KIND = {"domain": 0, "level": 1}              # SX_DIST_DOMAIN / SX_DIST_LEVEL
 VORTEX_SCALAR, VORTEX_WIND = 0, 1                # SX_VORTEX_*
 REGRID_OUTSIDE = {"refuse": 0, "fill": 1}        # SX_REGRID_REFUSE / SX_REGRID_FILL
+# SX_FN_*: the operations of a function program (sx_derive), by the names the expressions of pack_function_program use
+FN = {n: i for i, n in enumerate(["add", "sub", "mul", "div", "neg", "abs", "min", "max", "sqrt", "select", "exp", "log", "pow", "atan2", "r", "z",
+                                  "ref", "ahyp", "temperature", "esat_buck", "dry_density", "pressure", "vapor_pressure", "l_v"])}
+FN_ARITY = {"r": 0, "z": 0, "ref": 0, "neg": 1, "abs": 1, "sqrt": 1, "exp": 1, "log": 1, "ahyp": 1, "dry_density": 1, "l_v": 1, "select": 3,
+            "temperature": 3, "pressure": 3}      # every other operation takes two
+REF_PROFILE = {"sbar": 0, "xibar": 1, "mubar": 2}
+REF_SLOT = {"": 0, "z": 1, "zz": 2}
 STAT_OP = {"sum": 0, "max": 1, "min": 2, "duration": 3}     # SX_STAT_SUM / SX_STAT_MAX / SX_STAT_MIN / SX_STAT_DURATION
 EXT_KIND = {"domain": 0, "azimuth": 1}           # SX_EXT_DOMAIN / SX_EXT_AZIMUTH
 EXT_WANT = {"min": -1, "any": 0, "max": 1}       # SX_EXT_MIN / SX_EXT_ANY / SX_EXT_MAX
@@ -170,6 +177,11 @@ SYMBOLS = {
     "sx_project": (C.c_int, [_H, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, _H, P_I32]),
     "sx_project_check": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, P_I32]),
     "sx_project_point": (C.c_int, [C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_I32, P_D, C.c_double, P_D]),
+    "sx_derive": (C.c_int, [_H, C.c_int32, C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_I32, C.c_int32, P_D, _H, P_I32]),
+    "sx_derive_check": (C.c_int, [C.POINTER(GridDesc), C.c_int32, C.POINTER(GridDesc), C.c_int32, C.c_int32, P_I32, C.c_int32, C.c_int32, P_I32,
+                                  C.c_int32, C.c_int32, P_I32]),
+    "sx_derive_point": (C.c_int, [C.c_int32, P_D, P_I32, C.c_int32, C.c_int32, P_I32, C.c_int32, P_D, C.c_int32, P_I32, P_D, C.c_double,
+                                  C.c_double, P_D, P_D]),
     "sx_regrid": (C.c_int, [_H, _H, P_D, P_I32, C.c_int32, P_D, P_I64]),
     "sx_regrid_check": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), P_D, P_I32, C.c_int32]),
     "sx_regrid_columns": (C.c_int, [C.POINTER(GridDesc), C.POINTER(GridDesc), P_D, P_D, P_I32, P_I64]),

@@ -757,7 +757,7 @@ int sx_destroy(sx_handle *h) {
     comm_release(h);
     iface_release(h);
     pcr_release(h);
-    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives, isosurfaces, project, regrid, then the scan table the field-program scans share: their device memory goes with them
+    for (auto &st : h->diag) st.reset();      // evaluate, harmonics, reduce, spectrum, parcels, elliptic, extrema, crossings, distribution, vortex harmonics, statistics, antiderivatives, isosurfaces, project, regrid, derive, then the scan table the field-program scans share: their device memory goes with them
     for (auto &p : h->pending) { hipEventDestroy(p.a); hipEventDestroy(p.b); }
     for (auto e : h->event_pool) hipEventDestroy(e);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
@@ -1547,6 +1547,7 @@ int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     else if (k == "k_stats") b = diag_bytes(DIAG_STATS);                    // the last sample's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 32
     else if (k == "k_project") b = diag_bytes(DIAG_PROJECT);                // the last call's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 8
     else if (k == "k_regrid_levels") b = diag_bytes(DIAG_REGRID);              // the last call's profiles in + E + the column table + the destination's var_np1 planes out
+    else if (k == "k_derive") b = diag_bytes(DIAG_DERIVE);                  // the last call's planes x N x 8 (4 for an fp32-stored plane) + destination variables x N x 8
     *bytes = b;
     return 0;
 }

@@ -170,7 +170,7 @@ void antiderivative_r_host(const AntiTables &t, const SplineClass &sc, const dou
 bool build_antiderivative_z(double zmin, double zmax, int nz, int Zb, int bcb, int bct, int origin, std::vector<double> &ZT, int &Kp, int &Mp,
                             std::string &err);
 
-// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics, sx_stats_*, sx_antiderivative, sx_isosurface, sx_project, sx_regrid) ----
+// ---- device memory and per-handle state of the diagnostics entry points (sx_evaluate, sx_harmonics, sx_reduce, sx_spectrum, sx_parcels_*, sx_elliptic_solve, sx_extrema, sx_crossings, sx_distribution, sx_vortex_harmonics, sx_stats_*, sx_antiderivative, sx_isosurface, sx_project, sx_regrid, sx_derive) ----
 template <class T>
 struct DevBuf {         // owns one device array; reads as the pointer
     T *p = nullptr;
@@ -207,7 +207,7 @@ struct DiagState {      // what one of these entry points keeps with the handle:
     double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
     virtual ~DiagState() = default;
 };
-enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_ANTIDERIVATIVE, DIAG_ISOSURFACE, DIAG_PROJECT, DIAG_REGRID, DIAG_SCAN, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them (DIAG_SCAN, the table the field-program scans share, after all of them: sx_redprog.hpp)
+enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_ANTIDERIVATIVE, DIAG_ISOSURFACE, DIAG_PROJECT, DIAG_REGRID, DIAG_DERIVE, DIAG_SCAN, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them (DIAG_SCAN, the table the field-program scans share, after all of them: sx_redprog.hpp)
 struct EvalClasses {    // the vertical boundary-condition classes of a handle's variables (eval_classes)
     std::vector<EvalVert> vert;       // empty without a vertical
     std::vector<int> vcls;            // [V] class of each variable

@@ -40,17 +40,7 @@ __global__ __launch_bounds__(RED_T) void k_project(Planes<ST> P, int V, int64_t 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct ProjectState : DiagState {     // last_bytes: k_project's
-    hipEvent_t done = nullptr;        // recorded on the source's stream behind k_project; the destination's stream waits on it
-    ~ProjectState() override { if (done) hipEventDestroy(done); }
-};
-
-// the handle's grid with what sx_project_check compares beyond desc_of
-static sx_grid_desc proj_desc(const sx_handle *h) {
-    sx_grid_desc gd = desc_of(h);
-    gd.ring_uniform_L = h->uniform_L; gd.zmin = h->zmin; gd.zmax = h->zmax;
-    return gd;
-}
+using ProjectState = CompanionWrite;      // last_bytes: k_project's
 
 // what sx_project and sx_project_check refuse of the pointers
 static bool proj_pointers_ok(const char *who, int n_terms, const double *coef, bool need_coef, const int32_t *terms, int n_out, const int32_t *var_dst) {
@@ -72,15 +62,7 @@ int sx_project_check(const sx_grid_desc *src, const sx_grid_desc *dst, int32_t s
     const char *who = "sx_project";
     if (!desc_ok(src, "sx_project_check") || !desc_ok(dst, "sx_project_check")) return 1;
     if (!proj_pointers_ok(who, n_terms, nullptr, false, terms, n_out, var_dst)) return 1;
-    if (src->tile_cell0 != 0 || src->tile_num_cells != src->num_cells || dst->tile_cell0 != 0 || dst->tile_num_cells != dst->num_cells) {
-        set_error("sx_project: source and destination must be one-tile patches");
-        return 1;
-    }
-    const EvalGeom gs = desc_geom(src), gd = desc_geom(dst);
-    const char *differs = src->geometry != dst->geometry ? "geometry" : src->xmin != dst->xmin ? "xmin" : src->xmax != dst->xmax ? "xmax" :
-                          src->num_cells != dst->num_cells ? "num_cells" : gs.uniform_L != gd.uniform_L ? "ring table" :
-                          gs.has_z && gs.nz != gd.nz ? "zDim" : gs.has_z && gs.zmin != gd.zmin ? "zmin" : gs.has_z && gs.zmax != gd.zmax ? "zmax" : nullptr;
-    if (differs) { set_error(std::string("sx_project: the destination's grid differs from the source's in ") + differs); return 1; }
+    if (!companion_pair_ok(who, src, dst)) return 1;
     if (n_out != dst->nvars) {
         set_error("sx_project: n_out = " + std::to_string(n_out) + " is not the destination's number of variables (" + std::to_string(dst->nvars) + "): every variable of the destination is written");
         return 1;
@@ -144,15 +126,13 @@ int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *co
     if (!proj_pointers_ok(who, n_terms, coef, true, terms, n_out, var_dst)) return 1;
     if (dst == src) { set_error("sx_project: the destination is the source (the forward transform reads var_np1, which is the model's state): project into a companion handle"); return 1; }
     if (dst->eq != SX_EQ_NONE) { set_error("sx_project: the destination handle has an equation set (only SX_EQ_NONE handles are overwritten)"); return 1; }
-    const sx_grid_desc gs = proj_desc(src), gd = proj_desc(dst);
+    const sx_grid_desc gs = companion_desc(src), gd = companion_desc(dst);
     if (sx_project_check(&gs, &gd, source, n_terms, terms, n_out, var_dst)) return 1;
     int32_t planes[RED_PLANES][2] = {}, n_planes = 0;
     RedProg prog;
     if (!red_program(who, &gs, source, n_terms, coef, terms, n_out, planes, &n_planes, prog)) return 1;
-    if (!src->diag[DIAG_PROJECT]) src->diag[DIAG_PROJECT].reset(new ProjectState());
-    ProjectState *st = diag_state<ProjectState>(src, DIAG_PROJECT);
-    if (!st->done) HIPCHK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
-    if (error_status()) return 1;
+    ProjectState *st = companion_write_state(src, DIAG_PROJECT);
+    if (!st) return 1;
 
     ProjDst pd = {};
     for (int o = 0; o < n_out; o++) pd.var[o] = (uint8_t)(var_dst[o] - 1);
@@ -173,16 +153,7 @@ int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *co
             else launch(std::integral_constant<int, 1>());
         });
     }
-    HIPCHK(hipEventRecord(st->done, src->stream));
-    HIPCHK(hipStreamWaitEvent(dst->stream, st->done, 0));
-    if (error_status()) return 1;
-    // the destination's own forward chain, every variable: what sx_spectral_transform + sx_spline_transform launch
-    dst->diag_dirty = false;
-    launch_fl_forward(dst);
-    launch_sb(dst);
-    launch_solve(dst);
-    HIPCHK(hipStreamSynchronize(dst->stream));
-    return error_status();
+    return companion_transform(src, dst, st);
 }
 
 }  // extern "C"

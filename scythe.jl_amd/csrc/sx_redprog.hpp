@@ -1,6 +1,5 @@
-// What the five entry points that evaluate a field program at every gridpoint of a tile share - sx_reduce, sx_extrema,
-// sx_distribution, sx_stats_* and sx_project (sx_<name>.hip): the program as the kernels read it and its acceptance, the loads of the
-// planes it names and its outputs at one point, the scan table of a handle (work list and weights) and the choice of the kernel
+// What the entry points that evaluate a field program at every gridpoint of a tile share - sx_reduce, sx_extrema, sx_distribution,
+// sx_stats_*, sx_project and sx_derive (sx_<name>.hip): the program as the kernels read it and its acceptance, the loads of the planes it names and its outputs at one point, the scan table of a handle (work list and weights) and the choice of the kernel
 // instantiation.  The walk of a ring piece stays written out in each kernel: as a helper that takes the body as a lambda, the
 // program and the accumulators the body captures went to scratch.
 #pragma once
@@ -233,5 +232,51 @@ inline void scan_dispatch(const sx_handle *h, int source, F &&f) {
 }
 // workgroups of a flat launch: RED_T lanes, W points each
 inline unsigned scan_flat_blocks(const sx_handle *h, int W = 1) { return (unsigned)((h->N + (int64_t)RED_T * W - 1) / ((int64_t)RED_T * W)); }
+
+// ---- what sx_project and sx_derive share: a kernel on the source's stream writes the var_np1 planes of a companion handle, whose own
+// forward chain then runs on its stream
+struct CompanionWrite : DiagState {   // last_bytes: the writing kernel's
+    hipEvent_t done = nullptr;        // recorded on the source's stream behind the kernel; the destination's stream waits on it
+    ~CompanionWrite() override { if (done) hipEventDestroy(done); }
+};
+// the state of entry point `which` of src with its event, made on first use; null with the error set
+inline CompanionWrite *companion_write_state(sx_handle *src, int which) {
+    if (!src->diag[which]) src->diag[which].reset(new CompanionWrite());
+    CompanionWrite *st = diag_state<CompanionWrite>(src, which);
+    if (!st->done) HIPCHK(hipEventCreateWithFlags(&st->done, hipEventDisableTiming));
+    return error_status() ? nullptr : st;
+}
+// the handle's grid with what companion_pair_ok compares beyond desc_of
+inline sx_grid_desc companion_desc(const sx_handle *h) {
+    sx_grid_desc gd = desc_of(h);
+    gd.ring_uniform_L = h->uniform_L; gd.zmin = h->zmin; gd.zmax = h->zmax;
+    return gd;
+}
+// both one-tile patches on the same grid (b_zDim may differ: the destination truncates as it says), or the refusal in who's name
+inline bool companion_pair_ok(const char *who, const sx_grid_desc *src, const sx_grid_desc *dst) {
+    if (src->tile_cell0 != 0 || src->tile_num_cells != src->num_cells || dst->tile_cell0 != 0 || dst->tile_num_cells != dst->num_cells) {
+        set_error(std::string(who) + ": source and destination must be one-tile patches");
+        return false;
+    }
+    const EvalGeom gs = desc_geom(src), gd = desc_geom(dst);
+    const char *differs = src->geometry != dst->geometry ? "geometry" : src->xmin != dst->xmin ? "xmin" : src->xmax != dst->xmax ? "xmax" :
+                          src->num_cells != dst->num_cells ? "num_cells" : gs.uniform_L != gd.uniform_L ? "ring table" :
+                          gs.has_z && gs.nz != gd.nz ? "zDim" : gs.has_z && gs.zmin != gd.zmin ? "zmin" : gs.has_z && gs.zmax != gd.zmax ? "zmax" : nullptr;
+    if (differs) set_error(std::string(who) + ": the destination's grid differs from the source's in " + differs);
+    return !differs;
+}
+// behind the kernel: the event hand-over, then the destination's own forward chain, every variable - what sx_spectral_transform +
+// sx_spline_transform launch; returns after completion
+inline int companion_transform(sx_handle *src, sx_handle *dst, CompanionWrite *st) {
+    HIPCHK(hipEventRecord(st->done, src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, st->done, 0));
+    if (error_status()) return 1;
+    dst->diag_dirty = false;
+    launch_fl_forward(dst);
+    launch_sb(dst);
+    launch_solve(dst);
+    HIPCHK(hipStreamSynchronize(dst->stream));
+    return error_status();
+}
 
 }  // namespace sx

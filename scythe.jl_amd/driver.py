@@ -14,7 +14,7 @@ import time
 import numpy as np
 
 from .model import (Distribution, Grid, GridParameters, ModelParameters, Statistics, calcTileSizes, checkCFL, comm_unique_id, getGridpoints,
-                    program_of_outputs)
+                    program_of_outputs, thermo_programs)
 
 Located = collections.namedtuple("Located", "pos value status")
 WindRadii = collections.namedtuple("WindRadii", "thresholds azimuths radii quadrants")
@@ -635,6 +635,34 @@ class ModelRun:
             into.tileTransform_()
         return into
 
+    def derive(self, outputs, names=None, source="physical", bcs=None):
+        """Nonlinear derived fields as spectral variables (Grid.derive): every output - a term list or an expression as
+        pack_function_program reads them; a list of them, or a dict name -> output such as function_programs(model) or
+        thermo_programs(model) give - becomes one variable of a companion Grid, which is returned, to be sampled, scanned and
+        inverted like any state: the speed, a potential vorticity, temperature, pressure, theta_e.  Companion, bcs and source as
+        for project.  One-tile patches."""
+        self._one_tile("derive")
+        if not isinstance(outputs, dict):
+            outputs = dict(zip(["f%d" % (o + 1) for o in range(len(outputs))] if names is None else list(names), outputs))
+        elif names is not None:
+            outputs = {n: outputs[n] for n in names}
+        self._check_stream()
+        tile = self.tiles[0]
+        if source == "physical":
+            tile.tileTransform_()
+        return tile.derive(outputs, tile.project_companion(list(outputs), **(bcs or {})), source)
+
+    def freezing_level(self, columns):
+        """The lowest height at which the temperature crosses 273.15 K in every column r[, lambda] (Euler_test / rainfall_test):
+        derive of thermo_programs' T, then height_where on the companion.  ndarray [n_cols], NaN where a column has no crossing."""
+        return self.height_where([(0, 1.0, 0, [("T", "")])], 273.15, columns, grid=self.derive({"T": thermo_programs(self.model)["T"]}))
+
+    def minimum_pressure(self):
+        """(p [hPa], gridpoint [n_coord]) of the lowest pressure on the grid (Euler_test / rainfall_test): derive of thermo_programs'
+        p, then Grid.extrema on the companion's state."""
+        val, idx = self.derive({"p": thermo_programs(self.model)["p"]}).extrema([(0, 1.0, 0, [("p", "")])], "domain", "state")
+        return float(val[0, 0]), self.gridpoints()[int(idx[0, 0])].copy()
+
     def column_integral(self, var):
         """int_{zmin}^{zmax} f dz of variable `var` in every column of the grid: (points [columns, n_coord - 1] - r[, lambda] of the
         columns in gridpoint order -, values [columns]); the vertical antiderivative sampled at zmax with the wavenumber cut of each
@@ -999,15 +1027,15 @@ class ModelRun:
         last = ok.shape[0] - 1 - np.argmax(ok[::-1], axis=0)
         return np.where(ok.any(axis=0), first if which == "lowest" else last, -1)
 
-    def height_where(self, terms, level, columns, which="lowest", rising=None):
+    def height_where(self, terms, level, columns, which="lowest", rising=None, grid=None):
         """The height at which the one-output program `terms` (as for Grid.reduce) crosses `level` in every column r[, lambda]
         (Grid.isosurface, up to 16 crossings per column kept): the vertical radius_where.  which="lowest" / "highest"; rising=True
         keeps the crossings where the program rises upward through the level, False those where it falls, None all.  Returns
         ndarray [n_cols], NaN where a column has no such crossing (or, highest, more than 16 crossings).  Reads the A coefficients
-        as they stand; one-tile patches."""
+        as they stand; one-tile patches.  grid: a companion Grid (project, derive) whose variables the program names instead."""
         if which not in ("lowest", "highest"):
             raise ValueError("which must be 'lowest' or 'highest'")
-        g = self._one_tile("height_where")
+        g = grid if grid is not None else self._one_tile("height_where")
         res = g.isosurface(terms, [level], columns, max_cross=16)
         k = self._pick_height(res, which, rising)
         out = np.where(k >= 0, res.height[np.maximum(k, 0), 0, np.arange(len(k))], np.nan)

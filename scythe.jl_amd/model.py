@@ -504,6 +504,21 @@ class Grid:
             cache[key] = companion_grid(self.patch_params, names=list(names), **bcs)
         return cache[key]
 
+    # -- function programs as variables (sx_derive)
+    def derive(self, program, into, source="physical"):
+        """Evaluate a function program at this tile's gridpoints on the device and make its outputs the variables of the companion
+        Grid `into` (sx_derive): a field program's polynomial outputs followed by square roots, quotients, exp / log / pow / atan2 and
+        the moist thermodynamics the model itself steps with.  program: outputs as pack_function_program reads them (a dict name ->
+        expression or a list, one per variable of `into`, in its order), or what pack_function_program returned for THIS grid.  source
+        and everything about `into` are Grid.project's.  Nothing of this Grid changes.  Returns `into`.  One-tile patches only."""
+        fp = program if isinstance(program, FunctionProgram) else pack_function_program(self.patch_params, program)
+        if source not in L.REDUCE_SOURCE:
+            raise ValueError("source must be 'physical' or 'state'")
+        if len(fp.reg_dst) != into.V:          # sx_derive reads one entry per variable of `into`
+            raise ValueError("derive: %d outputs for the %d variables of the destination" % (len(fp.reg_dst), into.V))
+        L.check(self._lib.sx_derive(self._h, L.REDUCE_SOURCE[source], *fp.args(), into._h, fp.reg_dst.ctypes.data_as(L.P_I32) if len(fp.reg_dst) else None))
+        return into
+
     # -- onto another grid (sx_regrid)
     def regrid(self, dst_grid, centre=None, variables=None, outside="refuse", fill=None):
         """Lay this tile's state down on the Grid `dst_grid` (sx_regrid): every variable of dst_grid receives, at dst_grid's gridpoints,
@@ -1145,6 +1160,127 @@ def project_point(terms, planes, values, r):
     return out
 
 
+# ----------------------------------------------------------------------------- function programs (sx_derive)
+class FunctionProgram:
+    """A packed function program (pack_function_program): the mids as pack_reduce_program packs them (coef, terms, n_mid), ops int32
+    [n_ops, 4] = fn, a, b, c, consts float64, reg_dst int32 [n_outputs] - the register of each output - and the outputs' names"""
+
+    def __init__(self, coef, terms, n_mid, ops, consts, reg_dst, names):
+        self.coef, self.terms, self.n_mid = np.ascontiguousarray(coef, dtype=np.float64), np.ascontiguousarray(terms, dtype=np.int32), int(n_mid)
+        self.ops = np.ascontiguousarray(ops, dtype=np.int32).reshape(-1, 4)
+        self.consts = np.ascontiguousarray(consts, dtype=np.float64)
+        self.reg_dst = np.ascontiguousarray(reg_dst, dtype=np.int32)
+        self.names = list(names)
+
+    def args(self, with_coef=True, with_consts=True):
+        """the program as sx_derive / sx_derive_check / sx_derive_point take it, up to and including the constants"""
+        P = lambda a, t: a.ctypes.data_as(t) if a.size else None
+        return ((len(self.coef),) + ((P(self.coef, L.P_D),) if with_coef else ()) + (P(self.terms, L.P_I32), self.n_mid, len(self.ops), P(self.ops, L.P_I32),
+                len(self.consts)) + ((P(self.consts, L.P_D),) if with_consts else ()))
+
+
+def _is_terms(x):
+    return isinstance(x, (list, tuple)) and (len(x) == 0 or isinstance(x[0], (list, tuple))) and not (len(x) and isinstance(x[0], str))
+
+
+def pack_function_program(patch: GridParameters, outputs):
+    """Outputs -> FunctionProgram.  outputs: a dict name -> output, or a list of outputs.  An output is a term list [(coef, r_power,
+    [(var, slot), ...]), ...] as for Grid.project, or a nested expression
+        ("sqrt", X)  ("div", X, Y)  ("atan2", X, Y)  ("select", A, X, Y)  ("temperature", S, RHO, QV)  ("ref", "sbar", "z")  "r"  "z"  a number
+    (the operations: _lib.FN) whose leaves are term lists, names of other outputs of the dict, or numbers.  Term lists become the mids,
+    numbers the constants, every other node one operation; identical sub-expressions become ONE register (structural sharing: a
+    term list is compared term by term, a number bit by bit), and operands come before the operation that reads them.  Raises
+    ValueError beyond the library's limits (16 mids, 32 operations, 16 constants), for an unknown operation or name, for a cycle of
+    names, and for an output that is a bare number (it would need no kernel)."""
+    named = dict(outputs) if isinstance(outputs, dict) else {}
+    outs = list(outputs.values()) if isinstance(outputs, dict) else list(outputs)
+    names = list(outputs) if isinstance(outputs, dict) else ["f%d" % (o + 1) for o in range(len(outs))]
+    mids, mid_of, consts, const_of, ops, op_of, visiting = [], {}, [], {}, [], {}, []
+
+    def operand(x):
+        """register (>= 0) or constant (< 0) of a node"""
+        if isinstance(x, (int, float, np.floating, np.integer)) and not isinstance(x, bool):
+            key = np.float64(x).tobytes()
+            if key not in const_of:
+                consts.append(float(x))
+                const_of[key] = -len(consts)
+            return const_of[key]
+        if isinstance(x, str) and x not in ("r", "z"):
+            if x not in named:
+                raise ValueError("pack_function_program: %r is neither an output nor 'r' / 'z'" % (x,))
+            if x in visiting:
+                raise ValueError("pack_function_program: the outputs name one another in a cycle (%s)" % " -> ".join(visiting + [x]))
+            visiting.append(x)
+            reg = operand(named[x])
+            visiting.pop()
+            return reg
+        if _is_terms(x):
+            key = tuple((float(t[-3]), int(t[-2]), tuple((v, s) for v, s in t[-1])) for t in x)
+            if key not in mid_of:
+                mid_of[key] = len(mids)
+                mids.append(key)
+            return ("mid", mid_of[key])
+        node = (x,) if isinstance(x, str) else tuple(x)
+        fn = node[0]
+        if fn not in L.FN:
+            raise ValueError("pack_function_program: unknown operation %r" % (fn,))
+        if fn == "ref":
+            if len(node) != 3 or node[1] not in L.REF_PROFILE or node[2] not in L.REF_SLOT:
+                raise ValueError("pack_function_program: ('ref', profile, slot) with profile in %s and slot in %s" % (sorted(L.REF_PROFILE), sorted(L.REF_SLOT)))
+            key = (fn, L.REF_PROFILE[node[1]], L.REF_SLOT[node[2]])
+        else:
+            if len(node) - 1 != L.FN_ARITY.get(fn, 2):
+                raise ValueError("pack_function_program: %r takes %d operand(s)" % (fn, L.FN_ARITY.get(fn, 2)))
+            key = (fn,) + tuple(operand(a) for a in node[1:])
+        if key not in op_of:
+            op_of[key] = len(ops)
+            ops.append(key)
+        return ("op", op_of[key])
+
+    tops = []
+    for name, out in zip(names, outs):
+        visiting[:] = [name] if isinstance(outputs, dict) else []
+        reg = operand(out)
+        if isinstance(reg, int):
+            raise ValueError("pack_function_program: output %r is a bare number" % (name,))
+        tops.append(reg)
+    if len(mids) > 16 or len(ops) > 32 or len(consts) > 16:
+        raise ValueError("pack_function_program: %d mids, %d operations, %d constants; the limits are 16, 32 and 16" % (len(mids), len(ops), len(consts)))
+    n_mid = len(mids)
+    reg = lambda x: x if isinstance(x, int) else x[1] + (n_mid if x[0] == "op" else 0)
+    coef, terms, _ = pack_reduce_program(patch, [(o, c, p, list(f)) for o, key in enumerate(mids) for c, p, f in key])
+    packed = np.zeros((len(ops), 4), dtype=np.int32)
+    for i, key in enumerate(ops):
+        packed[i, 0] = L.FN[key[0]]
+        packed[i, 1:len(key)] = [reg(a) for a in key[1:]] if key[0] != "ref" else key[1:]
+    return FunctionProgram(coef, terms, n_mid, packed, np.array(consts, dtype=np.float64), [reg(t) for t in tops], names)
+
+
+def derive_check(patch: GridParameters, dst_patch: GridParameters, program, source="physical", has_ref_state=False):
+    """What Grid.derive refuses of the two patches and the program, on the host (sx_derive_check: no handle, no device); raises
+    ScytheHipError with the library's message.  has_ref_state: whether the source's model carries a reference state."""
+    ds, k1 = grid_desc(patch)
+    dd, k2 = grid_desc(dst_patch)
+    fp = program if isinstance(program, FunctionProgram) else pack_function_program(patch, program)
+    L.check(L.load().sx_derive_check(C.byref(ds), int(bool(has_ref_state)), C.byref(dd), L.REDUCE_SOURCE[source], *fp.args(False, False),
+                                     len(fp.reg_dst), fp.reg_dst.ctypes.data_as(L.P_I32) if len(fp.reg_dst) else None))
+
+
+def derive_point(program, planes, values, r, z=0.0, ref=None):
+    """Every register of a function program at ONE point, on the host by the code k_derive runs (sx_derive_point): float64
+    [n_mid + n_ops].  program: a FunctionProgram; planes [(var, slot), ...] (1-based variable, slot index) lists every plane the
+    mids name, values their values at the point; r, z its coordinates; ref [3, 3] the reference state (profile, slot) at its level."""
+    pl = np.ascontiguousarray(np.asarray(planes, dtype=np.int32).reshape(-1, 2))
+    val = np.ascontiguousarray(values, dtype=np.float64)
+    if val.shape != (len(pl),):
+        raise ValueError("values must have one entry per plane")
+    rf = None if ref is None else np.ascontiguousarray(ref, dtype=np.float64).reshape(3, 3)
+    regs = np.zeros(program.n_mid + len(program.ops))
+    L.check(L.load().sx_derive_point(*program.args(), len(pl), pl.ctypes.data_as(L.P_I32) if len(pl) else None, val.ctypes.data_as(L.P_D) if len(pl) else None,
+                                     float(r), float(z), rf.ctypes.data_as(L.P_D) if rf is not None else None, regs.ctypes.data_as(L.P_D)))
+    return regs
+
+
 # ----------------------------------------------------------------------------- onto another grid (sx_regrid)
 def _regrid_var_src(patch: GridParameters, dst_patch: GridParameters, variables):
     """var_src as sx_regrid reads it: int32 [dst V], 1-based variables of the source; default: the destination's names in the source"""
@@ -1480,6 +1616,68 @@ def field_programs(model: ModelParameters, u="u", v="v"):
     out["kinetic_energy"] = _speed2(wind, 0.5)
     out["speed2"] = _speed2(wind, 1.0)
     return out
+
+
+def function_programs(model: ModelParameters, u="u", v="v", h="h"):
+    """The nonlinear derived fields of the wind (u, v) and the depth h as outputs for ModelRun.derive: a dict name -> expression with
+        speed                sqrt(u^2 + v^2)
+        inflow_angle         atan2(u, v): the angle of the wind off the tangential direction, positive outward
+        potential_vorticity  (vorticity + f) / (D + h), for the sets with a depth parameter D: Hfree, the depth the continuity
+                             equation of the slab and height-resolved shallow-water sets multiplies the divergence with
+                             (-(Hfree + h) div), or H of the linear shallow-water sets (-H div); f = 0 where the set has none
+        rossby_number        vorticity / f, where the set has a non-zero f
+    and the grid's field_programs entries they are made of.  Outputs are left out where the grid lacks their variables."""
+    gp = model.grid_params
+    fp = field_programs(model, u, v)
+    pp = {(k if isinstance(k, str) else str(k)).lstrip(":"): val for k, val in (model.physical_params or {}).items()}
+    out = {"speed": ("sqrt", fp["speed2"])}
+    if v in gp.vars:
+        out["inflow_angle"] = ("atan2", [(1.0, 0, [(u, "")])], [(1.0, 0, [(v, "")])])
+        f = float(pp.get("f", 0.0))
+        depth = pp.get("Hfree", pp.get("H"))
+        if depth is not None and h in gp.vars:
+            out["potential_vorticity"] = ("div", fp["vorticity"] + [(f, 0, [])], [(float(depth), 0, []), (1.0, 0, [(h, "")])])
+        if f != 0.0:
+            out["rossby_number"] = ("div", fp["vorticity"], f)
+    return out
+
+
+def thermo_programs(model: ModelParameters, liquid=None):
+    """The moist thermodynamic fields of Euler_test / rainfall_test as outputs for ModelRun.derive: a dict name -> expression with
+        q_v  rho_d  T [K]  p [hPa]  rho  theta  theta_e  theta_rho  rh  q_sat
+    on the totals s + sbar, xi + xibar, mu + mubar, each written expression by expression as the reference has it:
+    thermodynamic_tuple, potential_temperature, reversible_theta_e and theta_rho (src/thermodynamics.jl:260-297), q_sat_liquid
+    (:163-170), rh = e / e_s of reversible_theta_e's H_term, rho = rho_d (1 + q_v) for Euler_test (src/testModels.jl:166) and
+    rho_d (1 + q_t) for rainfall_test (:476).  ahyp, dry_density, temperature, the pressure of thermodynamic_tuple, vapor_pressure,
+    sat_pressure_liquid_buck and L_v are the library's own functions (the composites of sx_derive), so T and p are the model's.
+    liquid: the liquid mixing ratio q_l as an expression; None is the reference's default argument mu_l = 0, q_l = ahyp(0) = 0, for
+    Euler_test, and for rainfall_test q_l = ahyp(mu_c) + ahyp(mu_r) as the set forms it (src/testModels.jl:472-474).
+    All ten need 42 operations and a program holds 32: derive nine in one call and theta_e (30) in another.  rainfall_test's theta_e
+    with the set's own q_l needs 34 and does not pack; liquid=0.0 gives the reference's default there."""
+    eq = model.equation_set
+    if eq not in ("Euler_test", "rainfall_test"):
+        raise ValueError("thermo_programs: equation set %r carries no (s, xi, mu)" % (eq,))
+    from . import thermodynamics as TH
+    var = lambda n: [(1.0, 0, [(n, "")])]
+    S, XI, MU = (("add", var(n), ("ref", n + "bar", "")) for n in ("s", "xi", "mu"))
+    q_v = ("ahyp", MU)
+    rho_d = ("dry_density", XI)
+    T = ("temperature", S, rho_d, q_v)
+    p = ("pressure", T, rho_d, q_v)
+    if liquid is None and eq == "rainfall_test":
+        liquid = ("add", ("ahyp", var("mu_c")), ("ahyp", var("mu_r")))
+    q_t = q_v if liquid is None else ("add", q_v, liquid)
+    theta = ("mul", T, ("pow", ("div", TH.p_0, p), TH.Rd / TH.Cpd))
+    e, es = ("vapor_pressure", p, q_v), ("esat_buck", T, p)
+    cp = ("add", TH.Cpd, ("mul", TH.Cl, q_t))
+    theta_term = ("mul", T, ("pow", ("div", TH.p_0, ("sub", p, e)), ("div", TH.Rd, cp)))
+    rh = ("div", e, es)
+    H_term = ("pow", rh, ("div", ("mul", -TH.Rv, q_v), cp))
+    exp_term = ("exp", ("div", ("mul", ("l_v", T), q_v), ("mul", cp, T)))
+    return {"q_v": q_v, "rho_d": rho_d, "T": T, "p": p, "rho": ("mul", rho_d, ("add", 1.0, q_v if eq == "Euler_test" else q_t)), "theta": theta,
+            "theta_e": ("mul", ("mul", theta_term, H_term), exp_term),
+            "theta_rho": ("div", ("mul", theta, ("add", 1.0, ("div", q_v, TH.Eps))), ("add", 1.0, q_t)), "rh": rh,
+            "q_sat": ("div", ("mul", TH.Eps, es), ("sub", p, es))}
 
 
 def regular_gridpoints(gp: GridParameters, nr, nl=None, nz=None):

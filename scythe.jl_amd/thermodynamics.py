@@ -105,3 +105,38 @@ def thermodynamic_tuple(s, xi, mu):               # :260-269
 def P_xi_from_s(s, xi, mu):                       # :226-230
     q_v, rho_d, Tk, _ = thermodynamic_tuple(s, xi, mu)
     return P_xi(Tk, rho_d, q_v)
+
+
+def sat_pressure_liquid_buck(Tk, phPa):           # :101-118
+    Tc = np.asarray(Tk, dtype=float) - 273.15
+    A, B, C = 7.2e-4, 3.20e-6, 5.9e-10
+    fw4 = 1.0 + A + (phPa * (B + (C * (Tc * Tc))))
+    a, b, c, d = 6.1121, 18.729, 257.87, 227.3
+    return fw4 * (a * np.exp((b - (Tc / d)) * Tc / (Tc + c)))
+
+
+def q_sat_liquid(Tk, phPa):                       # :163-170
+    ew = sat_pressure_liquid_buck(Tk, phPa)
+    return Eps * ew / (phPa - ew)
+
+
+def potential_temperature(s, xi, mu):             # :271-275
+    q_v, rho_d, Tk, p = thermodynamic_tuple(s, xi, mu)
+    return Tk * (p_0 / p) ** (Rd / Cpd)
+
+
+def reversible_theta_e(s, xi, mu, mu_l=0.0):      # :277-288
+    q_v, rho_d, Tk, p = thermodynamic_tuple(s, xi, mu)
+    q_t = q_v + ahyp(mu_l)
+    e = vapor_pressure(p, q_v)
+    es = sat_pressure_liquid_buck(Tk, p)
+    theta_term = Tk * (p_0 / (p - e)) ** (Rd / (Cpd + (Cl * q_t)))
+    H_term = (e / es) ** ((-Rv * q_v) / (Cpd + (Cl * q_t)))
+    exp_term = np.exp(L_v(Tk) * q_v / ((Cpd + (Cl * q_t)) * Tk))
+    return theta_term * H_term * exp_term
+
+
+def theta_rho(s, xi, mu, mu_l=0.0):               # :290-297
+    q_v, rho_d, Tk, p = thermodynamic_tuple(s, xi, mu)
+    q_t = q_v + ahyp(mu_l)
+    return potential_temperature(s, xi, mu) * (1.0 + (q_v / Eps)) / (1.0 + q_t)
