@@ -1182,7 +1182,9 @@ int sx_reset_timers(sx_handle *h);
 int sx_timer_only(sx_handle *h, const char *name);
 /* names[i] borrowed static strings; ms[i] accumulated milliseconds; calls[i] launches. Returns count via n. */
 int sx_get_timers(sx_handle *h, int32_t max, const char **names, double *ms, int64_t *calls, int32_t *n);
-/* algorithmic bytes of one launch of the named kernel (SURVEY.md 8(d) accounting), 0 if unknown.  Three names report the handle's
+/* algorithmic bytes of the last launch under that timer name (SURVEY.md 8(d) accounting; a diagnostics entry point that launches
+ * several times per call: of the last call); 0 before the first, and for a name without a byte model or unknown.  The count is kept
+ * whether timers are on or not and whatever sx_timer_only names.  Three names report the handle's
  * device allocations instead: "alloc.d_Fl" (ring spectra; 0 where k_fl_forward_cells + k_nodes_z are taken and they are never
  * allocated), "alloc.d_Fn" (node spectra and edge partials of that pair; 0 otherwise), "alloc.total" (everything sx_create allocated) */
 int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes);

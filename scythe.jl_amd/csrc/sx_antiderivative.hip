@@ -240,7 +240,6 @@ struct AntiState : DiagState {
     // vertical operator and its key
     int z_origin = -1, bcb = -1, bct = -1, Kp = 0, Mp = 0;
     DevBuf<double> d_ZT;
-    double bytes_r = 0, bytes_z = 0;
 };
 
 static bool anti_same_grid(const sx_handle *s, const sx_handle *d) {
@@ -260,11 +259,6 @@ static void anti_cls_dev(const SplineClass &sc, AntiClsDev &o) {
     o.n = sc.nfree; o.rl = sc.rl; o.rr = sc.rr; o.pad = 0;
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 2; j++) { o.gl[i * 2 + j] = sc.gl[i][j]; o.gr[i * 2 + j] = sc.gr[i][j]; }
-}
-
-double antiderivative_bytes(const sx_handle *h, bool vertical) {
-    const AntiState *st = diag_state<AntiState>(h, DIAG_ANTIDERIVATIVE);
-    return !st ? 0.0 : vertical ? st->bytes_z : st->bytes_r;
 }
 
 }  // namespace sx
@@ -348,30 +342,24 @@ int sx_antiderivative(sx_handle *src, int32_t var_src, int32_t axis, int32_t ori
         a.P = st->d_P; a.c = st->d_c; a.m = st->d_m; a.F = st->d_F; a.cls = st->d_cls;
         a.Cs = src->C; a.Cd = dst->C; a.col_s = (int64_t)vs * ncol; a.col_d = (int64_t)vd * ncol;
         a.nb = nb; a.K2 = src->K2; a.ncol = ncol; a.high = origin == SX_INT_FROM_HIGH;
-        {
-            TimedLaunch scope(src, "k_antiderivative_r");
-            hipLaunchKernelGGL(k_antiderivative_r, grid1(ncol, ANT_T), dim3(ANT_T), 0, src->stream, a);
-        }
         // the live source columns in, the destination columns out, and honestly: b and y each go out to the destination column and come
         // back (2 stores + 2 loads of the live columns); the tables [nb][7 + 1 + 1] and the factor rows [2][nb][4]
-        st->bytes_r = 8.0 * nb * (live + ncol + 4.0 * live) + 8.0 * nb * (9.0 + 8.0);
+        TimedLaunch scope(src, "k_antiderivative_r", 8.0 * nb * (live + ncol + 4.0 * live) + 8.0 * nb * (9.0 + 8.0));
+        hipLaunchKernelGGL(k_antiderivative_r, grid1(ncol, ANT_T), dim3(ANT_T), 0, src->stream, a);
     } else {
         AntiZArgs a;
         a.A = src->d_A; a.D = dst->d_A; a.ZT = st->d_ZT;
         a.Cs = src->C; a.Cd = dst->C; a.col_s = (int64_t)vs * ncol; a.col_d = (int64_t)vd * ncol;
         a.nb = nb; a.Zb = src->Zb; a.K2 = src->K2; a.Mp = st->Mp;
-        {
-            TimedLaunch scope(src, "k_antiderivative_z");
-            if (src->K2 >= 16 && src->Zb <= 64) {
-                const dim3 g((src->K2 + 15) / 16, nb);
-                if (src->Zb <= 16) hipLaunchKernelGGL(k_antiderivative_z<4>, g, dim3(64), 0, src->stream, a);
-                else if (src->Zb <= 32) hipLaunchKernelGGL(k_antiderivative_z<8>, g, dim3(64), 0, src->stream, a);
-                else hipLaunchKernelGGL(k_antiderivative_z<16>, g, dim3(64), 0, src->stream, a);
-            } else {
-                hipLaunchKernelGGL(k_antiderivative_z_lane, grid1((int64_t)nb * ncol, 256), dim3(256), 0, src->stream, a);
-            }
+        TimedLaunch scope(src, "k_antiderivative_z", 2.0 * 8.0 * nb * ncol + 8.0 * src->Zb * src->Zb);      // the columns in and out, the operator
+        if (src->K2 >= 16 && src->Zb <= 64) {
+            const dim3 g((src->K2 + 15) / 16, nb);
+            if (src->Zb <= 16) hipLaunchKernelGGL(k_antiderivative_z<4>, g, dim3(64), 0, src->stream, a);
+            else if (src->Zb <= 32) hipLaunchKernelGGL(k_antiderivative_z<8>, g, dim3(64), 0, src->stream, a);
+            else hipLaunchKernelGGL(k_antiderivative_z<16>, g, dim3(64), 0, src->stream, a);
+        } else {
+            hipLaunchKernelGGL(k_antiderivative_z_lane, grid1((int64_t)nb * ncol, 256), dim3(256), 0, src->stream, a);
         }
-        st->bytes_z = 2.0 * 8.0 * nb * ncol + 8.0 * src->Zb * src->Zb;
     }
     HIPCHK(hipStreamSynchronize(src->stream));
     return error_status();

@@ -105,8 +105,9 @@ static hipEvent_t get_event(sx_handle *h) {
     return e;
 }
 
-TimedLaunch::TimedLaunch(sx_handle *h, const char *name) : name(name) {
+TimedLaunch::TimedLaunch(sx_handle *h, const char *name, double bytes) : name(name) {
     const int id = timer_id(h, name);
+    h->timers[id].bytes = bytes;
     if (!h->timers_on) return;
     if (!h->timer_only.empty() && h->timer_only != h->timers[id].name) return;
     if (h->pending.size() >= 8192) timers_flush(h);
@@ -124,6 +125,11 @@ TimedLaunch::~TimedLaunch() {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) set_error(std::string(name) + ": " + hipGetErrorString(e));
     if (end) hipEventRecord(end, stream);
+}
+
+void set_kernel_bytes(sx_handle *h, const char *name, double bytes) {
+    for (auto &t : h->timers)
+        if (!std::strcmp(t.name, name)) t.bytes = bytes;
 }
 
 void timers_flush(sx_handle *h) {
@@ -153,7 +159,7 @@ enum { KU = 1, KR = 2, KRR = 4, KL = 8, KLL = 16, KZ = 32, KZZ = 64 };
 enum { KRZ = KU | KR | KRR | KZ | KZZ, KRL = KU | KR | KRR | KL | KLL };     // every kind of an RZ / an RL grid
 enum { KURZ = KU | KR | KZ, KURL = KU | KR | KL };                            // value and first derivatives
 
-// What sx_create and sx_kernel_bytes need to know about an equation set: one row per SX_EQ_* id.
+// What sx_create needs to know about an equation set: one row per SX_EQ_* id.
 struct EqSet {
     int id;
     const char *name;       // the reference's name (src/semiimplicit.jl:359-361)
@@ -161,30 +167,29 @@ struct EqSet {
     bool reads_H;           // reads params[SX_P_H] (include/scythe_hip.h, sx_model_desc.params)
     bool needs_ref;         // needs sx_model_desc.ref_state
     int semi_xi, semi_w;    // 1-based xi / w positions it requires when semi-implicit, 0 = any
-    bool diag_w;            // variable 6 is a diagnostic w: no tendency history (DESIGN.md "Slot masks")
     int kinds[8];           // derivative kinds read by each of the first min_vars variables; the others read the value only
 };
 
 static const EqSet EQ_SETS[] = {
-    // id, name, geom, min_vars, reads_H, needs_ref, semi_xi, semi_w, diag_w, kinds per variable
-    {SX_EQ_LINEAR_ADVECTION_1D,  "LinearAdvection1D",                    SX_GEOM_R,   1, 0, 0, 0, 0, 0, {KU | KR | KRR}},
-    {SX_EQ_LINEAR_ADVECTION_RZ,  "LinearAdvectionRZ",                    SX_GEOM_RZ,  4, 0, 0, 0, 0, 0, {KRZ, KU, KU, KU}},
-    {SX_EQ_LINEAR_ADVECTION_RL,  "LinearAdvectionRL",                    SX_GEOM_RL,  3, 0, 0, 0, 0, 0, {KRL, KU, KU}},
-    {SX_EQ_LINEAR_ADVECTION_RLZ, "LinearAdvectionRLZ",                   SX_GEOM_RLZ, 3, 0, 0, 0, 0, 0, {KRL, KU, KU}},
-    {SX_EQ_ONEWAY_SW_SLAB,       "Oneway_ShallowWater_Slab",             SX_GEOM_RL,  6, 0, 0, 0, 0, 1, {KURL, KURL, KURL, KRL, KRL, 0}},
-    {SX_EQ_TWOWAY_SW_SLAB,       "Twoway_ShallowWater_Slab",             SX_GEOM_RL,  6, 0, 0, 0, 0, 1, {KURL, KURL, KURL, KRL, KRL, 0}},
-    {SX_EQ_ONEWAY_SW_HRBL,       "Oneway_ShallowWater_HeightResolvedBL", SX_GEOM_RLZ, 6, 0, 0, 0, 0, 1,
+    // id, name, geom, min_vars, reads_H, needs_ref, semi_xi, semi_w, kinds per variable
+    {SX_EQ_LINEAR_ADVECTION_1D,  "LinearAdvection1D",                    SX_GEOM_R,   1, 0, 0, 0, 0, {KU | KR | KRR}},
+    {SX_EQ_LINEAR_ADVECTION_RZ,  "LinearAdvectionRZ",                    SX_GEOM_RZ,  4, 0, 0, 0, 0, {KRZ, KU, KU, KU}},
+    {SX_EQ_LINEAR_ADVECTION_RL,  "LinearAdvectionRL",                    SX_GEOM_RL,  3, 0, 0, 0, 0, {KRL, KU, KU}},
+    {SX_EQ_LINEAR_ADVECTION_RLZ, "LinearAdvectionRLZ",                   SX_GEOM_RLZ, 3, 0, 0, 0, 0, {KRL, KU, KU}},
+    {SX_EQ_ONEWAY_SW_SLAB,       "Oneway_ShallowWater_Slab",             SX_GEOM_RL,  6, 0, 0, 0, 0, {KURL, KURL, KURL, KRL, KRL, 0}},
+    {SX_EQ_TWOWAY_SW_SLAB,       "Twoway_ShallowWater_Slab",             SX_GEOM_RL,  6, 0, 0, 0, 0, {KURL, KURL, KURL, KRL, KRL, 0}},
+    {SX_EQ_ONEWAY_SW_HRBL,       "Oneway_ShallowWater_HeightResolvedBL", SX_GEOM_RLZ, 6, 0, 0, 0, 0,
      {KURL, KURL, KURL, KRL | KZ, KRL | KZ, 0}},
-    {SX_EQ_LINEAR_ACOUSTIC_RZ,   "LinearAcousticRZ",                     SX_GEOM_RZ,  5, 0, 0, 0, 0, 0, {KRZ, KURZ, KRZ, KRZ, KRZ}},
-    {SX_EQ_EULER_TEST,           "Euler_test",                           SX_GEOM_RZ,  5, 0, 1, 0, 0, 0, {KRZ, KURZ, KRZ, KRZ, KRZ}},
+    {SX_EQ_LINEAR_ACOUSTIC_RZ,   "LinearAcousticRZ",                     SX_GEOM_RZ,  5, 0, 0, 0, 0, {KRZ, KURZ, KRZ, KRZ, KRZ}},
+    {SX_EQ_EULER_TEST,           "Euler_test",                           SX_GEOM_RZ,  5, 0, 1, 0, 0, {KRZ, KURZ, KRZ, KRZ, KRZ}},
     // src/shallowWaterModels.jl:253-254 and 291-293
-    {SX_EQ_LINEAR_SW_1D,         "LinearShallowWater1D",                 SX_GEOM_R,   2, 1, 0, 0, 0, 0, {KU | KR, KU | KR | KRR}},
-    {SX_EQ_LINEAR_SW_RL,         "LinearShallowWaterRL",                 SX_GEOM_RL,  3, 1, 0, 0, 0, 0, {KURL, KU | KR | KRR | KLL, KRL}},
+    {SX_EQ_LINEAR_SW_1D,         "LinearShallowWater1D",                 SX_GEOM_R,   2, 1, 0, 0, 0, {KU | KR, KU | KR | KRR}},
+    {SX_EQ_LINEAR_SW_RL,         "LinearShallowWaterRL",                 SX_GEOM_RL,  3, 1, 0, 0, 0, {KURL, KU | KR | KRR | KLL, KRL}},
     // src/testModels.jl:404-455: xi and qss have no K diffusion.  Semi-implicit, the tendency writes the implicit terms by
     // position (src/testModels.jl:545-566) while the adjustment finds xi and w by name: hence the fixed xi / w
-    {SX_EQ_RAINFALL_TEST,        "rainfall_test",                        SX_GEOM_RZ,  8, 0, 1, 2, 5, 0,
+    {SX_EQ_RAINFALL_TEST,        "rainfall_test",                        SX_GEOM_RZ,  8, 0, 1, 2, 5,
      {KRZ, KURZ, KRZ, KRZ, KRZ, KRZ, KRZ, KURZ}},
-    {SX_EQ_NONE,                 "None",                                 -1,          1, 0, 0, 0, 0, 0, {KU}},
+    {SX_EQ_NONE,                 "None",                                 -1,          1, 0, 0, 0, 0, {KU}},
 };
 
 static const EqSet *eq_set(int id) {
@@ -1484,70 +1489,15 @@ int sx_get_timers(sx_handle *h, int32_t max, const char **names, double *ms, int
 int sx_kernel_bytes(sx_handle *h, const char *name, double *bytes) {
     clear_error();
     if (!h || !name || !bytes) { set_error("null argument"); return 1; }
-    // Algorithmic bytes per launch (fp64), counting each array once (DESIGN.md "Kernels and rooflines").
-    // w = fp64; ws = width of the derivative slots of `physical` / G (4 bytes in the fp32-storage mode; value slots stay fp64)
-    const double w = 8.0, ws = h->f32 ? 4.0 : 8.0, wi = h->sp32 ? 4.0 : 8.0, N = (double)h->N, V = h->V;     // wi: Az / Fl entries
-    const double S_tile = (double)h->nbt * h->C, S_patch = (double)h->b_rDim * h->C;
-    const bool fusedz = h->node_mode && h->node_active && fft_fused_zinv(h);       // node-space units invert vertically inside their FFT kernel
-    const int zrows = h->last_zinv_rows > 0 || fusedz ? h->last_zinv_rows : h->nbt;
-    const double az = h->has_z ? (double)zrows * h->last_zinv_jobs * h->nz * h->K2 : S_tile;
-    // ring spectra, or with the forward pair that sums them into the nodes: node spectra + the segments' edge partials
-    const double fl = h->cells.on ? (double)(h->nbt + 3 * (h->cells.segs - 1)) * h->V * h->nz * h->K2 : (double)h->nrings * h->V * h->nz * h->K2, bz = (double)h->nbt * h->V * h->nz * h->K2;
-    std::string k(name);
+    // the launchers state the algorithmic bytes of each launch where they open its TimedLaunch scope (DESIGN.md "Kernels and rooflines")
+    const std::string k(name);
     double b = 0;
-    auto planes = [&](int bits, int val) { return w * val + ws * (bits - val); };        // bytes per point of a plane set
-    const double out_planes = h->last_mask_full ? planes(h->mask_full_bits, h->mask_full_val) : planes(h->mask_eq_bits, h->mask_eq_val);
-    const double eq_planes = planes(h->mask_eq_bits, h->mask_eq_val), node_planes = planes(h->mask_node_bits, h->mask_node_val);
-    const bool node = h->node_mode && h->node_active;
-    auto diag_bytes = [&](int which) { return h->diag[which] ? h->diag[which]->last_bytes : 0.0; };
-    const double fin = node ? (double)h->R_in / h->nrings : 1.0;   // fraction of rings on the ring-wise path
-    // node-space units actually transformed and read: cell c of the outer rings combines nodes c .. c + 3 and the first such cell is
-    // R_in / 3, so nodes [R_in / 3, nbt) - 132 of 174 at the bench grid; the nodes below feed the ring-wise inner rings only
-    const double n_units = node ? (double)(h->nbt - h->R_in / MUBAR) : 0.0;
-    const double NGu = n_units * (double)h->uniform_L * h->nz;
-    if (k == "k_rl_inverse") b = (N * out_planes + wi * az) * fin;   // write the requested physical planes, read Az
-    else if (k == "k_node_fft") b = NGu * node_planes + (fusedz ? w * n_units * h->C : wi * n_units * h->last_zinv_jobs * h->nz * h->K2);
-    else if (k == "k_phys_hrbl_inner") b = N * fin * (eq_planes + w * (4.0 * V - 3.0));
-    else if (k == "k_phys_hrbl" && node)                            // node transforms (read once) + history + outputs
-        b = NGu * node_planes + N * (1.0 - fin) * w * (4.0 * V - 3.0);
-    else if (k == "k_zinv") b = w * S_tile * zrows / h->nbt + wi * az;
-    else if (k == "k_phys_pointwise" || k == "k_phys_hrbl") {
-        // read the requested slots, E_nm1, E_nm2; write E_n, var_np1; the SW sets also write the diagnostic w plane and
-        // keep no tendency history for it
-        const bool sw = eq_set(h->eq)->diag_w;
-        b = N * (eq_planes + w * (4.0 * V + (sw ? -3.0 : 0.0)));        // inside sx_advance the diagnostic w plane is not stored
-    }
-    else if (k == "k_fl_forward") b = w * N * V + wi * fl;
-    else if (k == "k_sb") b = w * (fl + bz);
-    else if (k == "k_sbz") b = wi * fl + w * S_tile;
-    else if (k == "k_solve") b = w * (h->last_solve_part ? 2.0 : 4.0) * S_patch;   // read B, write y, read y, write A; k_solve_part: B in, A out
-    else if (k == "k_semiimplicit") b = w * N * 2.0 * 5.0;
-    else if (k == "k_phys_rain") b = N * (eq_planes + w * (4.0 * V + (h->semi ? V : 0.0)));   // as k_phys_pointwise, + impdot
-    else if (k == "k_condensation") b = w * N * (6.0 + 3.0);       // read s, xi, mu, mu_c, mu_r, qss of var_np1; write s, mu, mu_c
-    else if (k == "k_rz_inverse") b = w * S_tile + N * out_planes;       // read the tile's A rows, write the requested physical planes
-    else if (k == "k_rz_forward") b = w * N * V + w * S_tile;            // read var_np1, write the tile's B rows
-    else if (k == "k_evaluate") b = diag_bytes(DIAG_EVAL);                  // the last call's batches x 4 rows x live columns of A
-    else if (k == "k_harmonics") b = diag_bytes(DIAG_HARM);                // the last call's radii x 4 rows x b_zDim x (2 kcap + 1) of A
-    else if (k == "k_spectrum") b = diag_bytes(DIAG_SPEC);                  // the last call's rings x distinct planes x 4 rows x b_zDim x (2 kmax + 1) of A
-    else if (k == "k_parcels") b = diag_bytes(DIAG_PARCELS);                // the last advance's parcels x velocity variables x 4 rows x b_zDim x (2 kDim + 1) of A
-    else if (k == "k_elliptic") b = diag_bytes(DIAG_ELLIPTIC);              // the last solve's source columns in + destination columns out + factors
-    else if (k == "k_antiderivative_r" || k == "k_antiderivative_z") b = antiderivative_bytes(h, k == "k_antiderivative_z");   // the last radial / vertical call (sx_antiderivative.hip)
-    else if (k == "k_reduce") b = diag_bytes(DIAG_REDUCE);                  // the last call's planes x N x 8 (4 for an fp32-stored plane)
-    else if (k == "k_extrema") b = extrema_bytes(h, false);                 // the last scan's planes x N x 8 (4 for an fp32-stored plane)
-    else if (k == "alloc.d_Fl") b = (double)h->fl_bytes;                     // device bytes of the ring spectra (0: not allocated)
-    else if (k == "alloc.d_Fn") b = (double)h->fn_bytes;                     // ... of the node spectra and edge partials
-    else if (k == "alloc.total") b = (double)h->dev_bytes;                   // ... of everything sx_create allocated
-    else if (k == "k_refine") b = extrema_bytes(h, true);                   // the last refinement's evaluations x 4 rows x b_zDim x (2 kDim + 1) of A
-    else if (k == "k_ray_profiles") b = crossings_bytes(h, false);          // the last call's A columns of the variables named + ray coordinates in, profiles out
-    else if (k == "k_crossings") b = crossings_bytes(h, true);              // ... profiles in, radii, directions, counts and status out
-    else if (k == "k_column_profiles") b = isosurface_bytes(h, false);      // the last call's live A elements of the 4 node rows per batch and variable + column coordinates in, profiles out
-    else if (k == "k_isosurface") b = isosurface_bytes(h, true);            // ... profiles in, heights, directions, carried outputs, counts, status and station values out
-    else if (k == "k_distribution") b = diag_bytes(DIAG_DISTRIBUTION);      // the last call's planes x N x 8 (4 for an fp32-stored plane)
-    else if (k == "k_vortex_rings") b = diag_bytes(DIAG_VORTEX);            // the last call's live circles x n_az x distinct source variables x 4 rows x b_zDim x (2 kDim + 1) of A
-    else if (k == "k_stats") b = diag_bytes(DIAG_STATS);                    // the last sample's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 32
-    else if (k == "k_project") b = diag_bytes(DIAG_PROJECT);                // the last call's planes x N x 8 (4 for an fp32-stored plane) + n_out x N x 8
-    else if (k == "k_regrid_levels") b = diag_bytes(DIAG_REGRID);              // the last call's profiles in + E + the column table + the destination's var_np1 planes out
-    else if (k == "k_derive") b = diag_bytes(DIAG_DERIVE);                  // the last call's planes x N x 8 (4 for an fp32-stored plane) + destination variables x N x 8
+    if (k == "alloc.d_Fl") b = (double)h->fl_bytes;                     // device bytes of the ring spectra (0: not allocated)
+    else if (k == "alloc.d_Fn") b = (double)h->fn_bytes;                // ... of the node spectra and edge partials
+    else if (k == "alloc.total") b = (double)h->dev_bytes;              // ... of everything sx_create allocated
+    else
+        for (const auto &t : h->timers)
+            if (k == t.name) b = t.bytes;
     *bytes = b;
     return 0;
 }

@@ -40,7 +40,7 @@ void colprof_batches(const sx_handle *h, const double *r, int64_t n, std::vector
 // the grid's fields of the record (A, C, Zb, K2, kDim, the cells, xmin, DX); the caller fills the columns, the profiles and the plan
 void colprof_grid_args(const sx_handle *h, ColProfArgs &pa);
 // k_column_profiles over n_batches batches and nv variables (grids with an azimuth) or k_column_profiles_rz over pa.n_cols x pa.nprof
-// x pa.Zb outputs, on the handle's stream and under the timer "k_column_profiles"
-void launch_column_profiles(sx_handle *h, const ColProfArgs &pa, int n_batches, int nv);
+// x pa.Zb outputs, on the handle's stream and under the timer "k_column_profiles" with the launch's algorithmic bytes (0: no model)
+void launch_column_profiles(sx_handle *h, const ColProfArgs &pa, int n_batches, int nv, double bytes);
 
 }  // namespace sx

@@ -200,16 +200,10 @@ __global__ __launch_bounds__(64) void k_crossings(CrossArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct CrossState : DiagState {          // last_bytes: k_ray_profiles'
-    double cross_bytes = 0;             // k_crossings'
+struct CrossState : DiagState {
     DevBuf<double> d_rays, d_P, d_rad;
     DevBuf<int> d_i;                    // dir | count | status
 };
-
-double crossings_bytes(const sx_handle *h, bool scan) {
-    const CrossState *st = diag_state<CrossState>(h, DIAG_CROSSINGS);
-    return !st ? 0.0 : scan ? st->cross_bytes : st->last_bytes;
-}
 
 bool scan_args_ok(const sx_handle *h, const char *who, const char *count, const char *noun, int n_terms, const double *coef, int n_levels,
                   int max_cross, const double *levels, int64_t n, double tol) {
@@ -312,13 +306,12 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     pa.Zb = Zb; pa.nz = nz; pa.K2 = h->K2; pa.kDim = h->kDim; pa.has_l = h->has_l; pa.has_z = h->has_z;
     pa.zmin = h->zmin; pa.zmax = h->zmax;
     // A columns of the variables named (the padding block left out) and the ray coordinates in, the profiles out
-    st->last_bytes = nv == 0 ? 0.0 : 8.0 * ((double)rows * Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv + (double)nrc * n_rays + (double)rows * nprof * n_rays);
     if (nv > 0) {
-        {
-            TimedLaunch scope(h, "k_ray_profiles");
-            hipLaunchKernelGGL(k_ray_profiles, dim3((unsigned)((rows + 15) / 16), (unsigned)((n_rays + 15) / 16), (unsigned)nv), dim3(64), prof_lds(h),
-                               h->stream, pa);
-        }
+        TimedLaunch scope(h, "k_ray_profiles", 8.0 * ((double)rows * Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv + (double)nrc * n_rays + (double)rows * nprof * n_rays));
+        hipLaunchKernelGGL(k_ray_profiles, dim3((unsigned)((rows + 15) / 16), (unsigned)((n_rays + 15) / 16), (unsigned)nv), dim3(64), prof_lds(h),
+                           h->stream, pa);
+    } else {
+        set_kernel_bytes(h, "k_ray_profiles", 0.0);
     }
 
     ca.P = st->d_P; ca.radius = st->d_rad; ca.dir = st->d_i; ca.count = st->d_i + n_rad; ca.status = st->d_i + n_rad + (size_t)n_levels * n_rays;
@@ -329,9 +322,8 @@ int sx_crossings(sx_handle *h, int32_t n_terms, const double *coef, const int32_
     ca.n_rays = (int)n_rays; ca.rows = rows; ca.nprof = nprof; ca.n_levels = n_levels;
     ca.max_iter = max_iter <= 0 ? 60 : max_iter; ca.max_cross = max_cross;
     // the profiles in; radii, directions, counts and status out
-    st->cross_bytes = 8.0 * (double)rows * nprof * n_rays + 12.0 * (double)n_rad + 4.0 * ((double)n_levels + 1.0) * n_rays;
     {
-        TimedLaunch scope(h, "k_crossings");
+        TimedLaunch scope(h, "k_crossings", 8.0 * (double)rows * nprof * n_rays + 12.0 * (double)n_rad + 4.0 * ((double)n_levels + 1.0) * n_rays);
         hipLaunchKernelGGL(k_crossings, dim3((unsigned)n_rays), dim3(64), 0, h->stream, ca);
     }
 

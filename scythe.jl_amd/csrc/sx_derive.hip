@@ -201,10 +201,9 @@ int sx_derive(sx_handle *src, int32_t source, int32_t n_terms, const double *coe
     if (source == SX_REDUCE_PHYSICAL) flush_diag(src);
     HIPCHK(hipStreamSynchronize(dst->stream));      // the destination's own work on var_np1, B and A is complete before another stream writes them
     if (error_status()) return 1;
-    st->last_bytes = red_bytes(src, source, planes, n_planes) + 8.0 * dst->V * (double)src->N;
     const size_t lds = (size_t)std::max(n_mid + n_ops, 1) * RED_T * sizeof(double);      // <= 96 KB of the 160 KB
     {
-        TimedLaunch scope(src, "k_derive");
+        TimedLaunch scope(src, "k_derive", red_bytes(src, source, planes, n_planes) + 8.0 * dst->V * (double)src->N);
         scan_dispatch(src, source, [&](auto st_t, auto, auto P) {      // flat, no RINGS form
             auto kernel = k_derive<decltype(st_t)>;
             if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(FN_REGS * RED_T * sizeof(double))));

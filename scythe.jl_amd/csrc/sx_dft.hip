@@ -1599,7 +1599,8 @@ static void rlz_inverse(sx_handle *h, const int *d_mask) {
 }
 
 void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
-    TimedLaunch scope(h, "k_rl_inverse");
+    const bool full = d_mask == h->d_mask_full;       // write the requested physical planes, read Az
+    TimedLaunch scope(h, "k_rl_inverse", (double)h->N * out_plane_bytes(h, full) + (h->sp32 ? 4.0 : 8.0) * az_count(h, full));
 #ifdef SX_PHASES
     if (!g_dft_buf && !dft_planes(h)) {
         g_dft_n = (int64_t)level_chunks(h) * h->V * h->nrings;
@@ -1608,13 +1609,13 @@ void launch_rl_inverse_dft(sx_handle *h, const int *d_mask) {
         hipMemcpyToSymbol(HIP_SYMBOL(g_dft_dbg), &g_dft_buf, sizeof(g_dft_buf));
     }
 #endif
-    if (dft_planes(h)) launch_rl_inverse_dft_planes(h, d_mask == h->d_mask_full);
+    if (dft_planes(h)) launch_rl_inverse_dft_planes(h, full);
     else if (h->f32) rlz_inverse<float>(h, d_mask);
     else rlz_inverse<double>(h, d_mask);
 }
 
 void launch_fl_forward_dft(sx_handle *h) {
-    TimedLaunch scope(h, "k_fl_forward");
+    TimedLaunch scope(h, "k_fl_forward", 8.0 * (double)h->N * h->V + (h->sp32 ? 4.0 : 8.0) * fl_count(h));      // read var_np1, write the ring spectra
     const int planes = dft_planes(h) ? 1 : 0;
     const bool half = h->sw.dft_half != 0;      // A/B: the half-ring kernel
     auto go = [&](auto kern, dim3 grid, size_t lds, auto... tail) {

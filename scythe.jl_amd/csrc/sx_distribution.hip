@@ -318,7 +318,6 @@ int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms,
     if (!st->d_part.grow((size_t)nwg * E, "sx_distribution") || !st->d_pcnt.grow((size_t)nwg * EC, "sx_distribution") ||
         !st->d_sums.grow(E, "sx_distribution") || !st->d_count.grow(EC, "sx_distribution"))
         return 1;
-    st->last_bytes = red_bytes(h, source, planes, n_planes);
     HIPCHK(hipMemcpyAsync(st->d_edges, edges, sizeof(double) * (n_bins + 1), hipMemcpyHostToDevice, h->stream));
     if (error_status()) return 1;
 
@@ -328,7 +327,7 @@ int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms,
     a.N = h->N; a.n_work = n_work; a.V = h->V; a.nz = h->nz; a.n_bins = n_bins; a.level = level;
     const size_t lds = dist_lds_bytes(groups, level ? 1 : RED_T / 64, n_bins, n_out);
     {
-        TimedLaunch scope(h, "k_distribution");
+        TimedLaunch scope(h, "k_distribution", red_bytes(h, source, planes, n_planes));
         scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
             const auto kern = k_distribution<decltype(st_t), decltype(rings)::value>;
             if (lds > 65536) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -336,7 +335,7 @@ int sx_distribution(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms,
         });
     }
     {
-        TimedLaunch scope(h, "k_distribution_final");
+        TimedLaunch scope(h, "k_distribution_final", 0.0);
         hipLaunchKernelGGL(k_distribution_final, grid1((int64_t)E, DIST_FE), dim3(DIST_FE * DIST_PARTS), 0, h->stream, st->d_part, st->d_pcnt, nwg,
                            groups, S, n_out, st->d_sums, st->d_count);
     }

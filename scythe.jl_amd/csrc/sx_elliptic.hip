@@ -253,14 +253,13 @@ int sx_elliptic_solve(sx_handle *src, int32_t rhs_kind, int32_t var_a, int32_t v
     a.Cs = src->C; a.Cd = dst->C;
     a.nb = nb; a.K2 = src->K2; a.ncol = src->Zb * src->K2; a.kind = rhs_kind;
     a.col_p = (int64_t)vp * a.ncol; a.col_q = (int64_t)vq * a.ncol; a.col_d = (int64_t)vd * a.ncol;
+    // algorithmic bytes: the live source columns in (block 1 never; the partner block not for k = 0), the destination columns out, the factors
+    const double live = (double)src->Zb * (src->has_l ? src->K2 - 1 : 1), partner = two ? (double)src->Zb * (src->K2 - 2) : 0.0;
     {
-        TimedLaunch scope(src, "k_elliptic");
+        TimedLaunch scope(src, "k_elliptic", 8.0 * nb * (live + partner + a.ncol) + 8.0 * 4.0 * nb * (src->kDim + 1));
         hipLaunchKernelGGL(k_elliptic, grid1(a.ncol, ELL_T), dim3(ELL_T), 0, src->stream, a);
     }
     HIPCHK(hipStreamSynchronize(src->stream));
-    // algorithmic bytes: the live source columns in (block 1 never; the partner block not for k = 0), the destination columns out, the factors
-    const double live = (double)src->Zb * (src->has_l ? src->K2 - 1 : 1), partner = two ? (double)src->Zb * (src->K2 - 2) : 0.0;
-    st->last_bytes = 8.0 * nb * (live + partner + a.ncol) + 8.0 * 4.0 * nb * (src->kDim + 1);
     return error_status();
 }
 

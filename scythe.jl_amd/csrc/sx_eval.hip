@@ -247,8 +247,9 @@ static size_t eval_lds_bytes(int P, int csw, int Zb) {
 }
 
 // one launch: the points [p0, p0 + n) of the call
+// bytes: the A traffic of the call so far, this launch's added (its batches x 4 rows x live columns)
 static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const double *points, int64_t n_all, int64_t p0, int n, int flags,
-                       int kmin, int kband, double *out) {
+                       int kmin, int kband, double *out, double &bytes) {
     const std::vector<EvalVert> &vert = st->cls.vert;
     const int ncls = std::max<int>(1, (int)vert.size()), Zb = h->has_z ? h->Zb : 1;
     const long double two_pi = 8.0L * atanl(1.0L);
@@ -299,7 +300,7 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
         cols += (double)Zb * (h->has_l ? (kmin > 0 ? std::max(0, 2 * (khi - kmin + 1)) : 2 * khi + 1) : 1);
         i = j;
     }
-    st->last_bytes += 8.0 * 4.0 * cols * h->V;
+    bytes += 8.0 * 4.0 * cols * h->V;
     const size_t nres = (size_t)n * h->V * h->D;
     const char *who = "sx_evaluate";
     if (!st->d_pts.grow(pts.size(), who) || !st->d_batch.grow(batches.size(), who) || !st->d_wz.grow(wz.size(), who) || !st->d_res.grow(nres, who))
@@ -311,7 +312,7 @@ static bool eval_chunk(sx_handle *h, EvalState *st, const EvalGeom &g, const dou
     EvalSlots sl;
     for (int m = 0; m < 7; m++) sl.s[m] = h->slot[m];
     {
-        TimedLaunch scope(h, "k_evaluate");
+        TimedLaunch scope(h, "k_evaluate", bytes);
         hipLaunchKernelGGL(k_evaluate, dim3((unsigned)batches.size(), (unsigned)h->V), dim3(EVAL_T), eval_lds_bytes(P, csw, Zb), h->stream, h->d_A,
                            h->C, st->d_pts, st->d_batch, st->d_wz, st->cls.d_vcls, ncls, Zb, h->K2, h->has_l, csw, P, kmin, kband, sl, st->d_res, (int64_t)n, h->V);
     }
@@ -341,9 +342,9 @@ static int evaluate_band(sx_handle *h, const double *points, int64_t n_points, i
     flush_diag(h);
     // the results of every launch are held back until all of them have succeeded: a failed call writes nothing to out
     std::vector<double> tmp((size_t)n_points * h->V * h->D);
-    st->last_bytes = 0;
+    double bytes = 0;
     for (int64_t p0 = 0; p0 < n_points; p0 += EVAL_CHUNK)
-        if (!eval_chunk(h, st, g, points, n_points, p0, (int)std::min<int64_t>(EVAL_CHUNK, n_points - p0), flags, kmin, kband, tmp.data())) return 1;
+        if (!eval_chunk(h, st, g, points, n_points, p0, (int)std::min<int64_t>(EVAL_CHUNK, n_points - p0), flags, kmin, kband, tmp.data(), bytes)) return 1;
     std::memcpy(out, tmp.data(), sizeof(double) * tmp.size());
     return error_status();
 }

@@ -375,11 +375,10 @@ __global__ __launch_bounds__(PARCEL_T) void k_refine(RefineArgs a) {
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct ExtremaState : DiagState {      // last_bytes: k_extrema's.  The work list: the handle's scan table (sx_redprog.hpp)
+struct ExtremaState : DiagState {      // The work list: the handle's scan table (sx_redprog.hpp)
     DevBuf<double> d_pv, d_val;     // [2][piece][output][level]; the results
     DevBuf<long long> d_pi, d_idx;
     // refinement
-    double refine_bytes = 0;        // A bytes of the last sx_extremum_refine
     DevBuf<double> d_f;             // start | pos | grad [n_coord][n] each, value [n]
     DevBuf<int> d_i;                // status | iters
 };
@@ -387,11 +386,6 @@ struct ExtremaState : DiagState {      // last_bytes: k_extrema's.  The work lis
 static ExtremaState *extrema_state(sx_handle *h) {
     if (!h->diag[DIAG_EXTREMA]) h->diag[DIAG_EXTREMA].reset(new ExtremaState());
     return diag_state<ExtremaState>(h, DIAG_EXTREMA);
-}
-
-double extrema_bytes(const sx_handle *h, bool refine) {
-    const ExtremaState *st = diag_state<ExtremaState>(h, DIAG_EXTREMA);
-    return !st ? 0.0 : refine ? st->refine_bytes : st->last_bytes;
 }
 
 static size_t refine_lds(const sx_handle *h) {
@@ -441,10 +435,8 @@ int sx_extrema(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, cons
     if (!st->d_pv.grow(n_part, "sx_extrema") || !st->d_pi.grow(n_part, "sx_extrema") || !st->d_val.grow(n_res, "sx_extrema") ||
         !st->d_idx.grow(n_res, "sx_extrema"))
         return 1;
-    st->last_bytes = red_bytes(h, source, planes, n_planes);
-
     {
-        TimedLaunch scope(h, "k_extrema");
+        TimedLaunch scope(h, "k_extrema", red_bytes(h, source, planes, n_planes));
         scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
             constexpr bool RINGS = decltype(rings)::value;
             hipLaunchKernelGGL((k_extrema<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
@@ -452,7 +444,7 @@ int sx_extrema(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, cons
         });
     }
     {
-        TimedLaunch scope(h, "k_extrema_final");
+        TimedLaunch scope(h, "k_extrema_final", 0.0);
         if (kind == SX_EXT_AZIMUTH)
             hipLaunchKernelGGL(k_extrema_rings, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_pv, st->d_pi, sg->d_first, sg->n_items,
                                h->nrings, h->nz, n_out, st->d_val, st->d_idx);
@@ -516,7 +508,7 @@ int sx_extremum_refine(sx_handle *h, int32_t var, int32_t want, int32_t free_mas
     a.xmin = h->xmin; a.tol = tol <= 0.0 ? 1e-9 : tol;
     a.G = newton_geom(g);
     {
-        TimedLaunch scope(h, "k_refine");
+        TimedLaunch scope(h, "k_refine", 0.0);      // its bytes follow from the iteration counts: below
         hipLaunchKernelGGL(k_refine, dim3((unsigned)n), dim3(parcel_threads(h)), refine_lds(h), h->stream, a);
     }
     std::vector<double> rf(2 * blk + n);          // held back until the call has succeeded: a failed call writes nothing
@@ -531,7 +523,7 @@ int sx_extremum_refine(sx_handle *h, int32_t var, int32_t want, int32_t free_mas
     double evals = 0;
     for (int64_t i = 0; i < n; i++) { status[i] = ric[i]; iters[i] = ric[n + i]; evals += 1.0 + ric[n + i]; }
     // 4 node rows x every column of the variable but the padding block, once per evaluation (one more than the steps taken)
-    st->refine_bytes = 8.0 * 4.0 * (double)Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * evals;
+    set_kernel_bytes(h, "k_refine", 8.0 * 4.0 * (double)Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * evals);
     return 0;
 }
 

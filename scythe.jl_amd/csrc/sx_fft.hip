@@ -969,7 +969,10 @@ static void launch_fwd(sx_handle *h, dim3 g) {
 
 // ring-wise inverse of the first n_rings rings of the tile (all of them by default)
 void launch_rl_inverse_fft(sx_handle *h, const int *d_mask, int n_rings) {
-    TimedLaunch scope(h, "k_rl_inverse");
+    // write the requested physical planes, read Az: of the rings taken (n_rings = R_in: the ring-wise share of a node-space launch)
+    const bool full = d_mask == h->d_mask_full;
+    const double fin = n_rings < 0 ? 1.0 : (double)h->R_in / h->nrings;
+    TimedLaunch scope(h, "k_rl_inverse", ((double)h->N * out_plane_bytes(h, full) + (h->sp32 ? 4.0 : 8.0) * az_count(h, full)) * fin);
     InvTarget tg{h->d_phys, h->d_phi, h->d_kmax, h->d_pstart, h->d_phoff, n_rings < 0 ? h->nrings : n_rings, h->nrings, h->N, 0};
     launch_inv_any(h, d_mask, tg);
 }
@@ -994,7 +997,10 @@ void fft_phases_dump() {
 #endif
 
 void launch_node_fft(sx_handle *h) {
-    TimedLaunch scope(h, "k_node_fft");
+    // write the node-space transforms of the units taken; read their A rows (the vertical inverse in-kernel) or their share of Az
+    const double units = node_units(h), spec = h->sp32 ? 4.0 : 8.0;
+    TimedLaunch scope(h, "k_node_fft", node_points(h) * plane_bytes(h, h->mask_node_bits, h->mask_node_val) +
+                                       (fft_fused_zinv(h) ? 8.0 * units * h->C : spec * units * h->njobs_zinv_eq * h->nz * h->K2));
 #ifdef SX_PHASES
     if (!g_fft_buf) {
         g_fft_n = (int64_t)((h->nz + FFT_FZC - 1) / FFT_FZC) * h->V * 8 * ((h->nbt + 7) / 8);      // the fused grid: whole groups of 8 nodes
@@ -1039,7 +1045,7 @@ static void launch_fwd_cells(sx_handle *h, const CellsPlan &p) {
 }
 
 void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {
-    TimedLaunch scope(h, "k_fl_forward");
+    TimedLaunch scope(h, "k_fl_forward", 8.0 * (double)h->N * h->V + (h->sp32 ? 4.0 : 8.0) * fl_count(h));      // read var_np1, write the node spectra
     switch (p.logL) {
         case 4: launch_fwd_cells<4>(h, p); break;
         case 5: launch_fwd_cells<5>(h, p); break;
@@ -1050,7 +1056,7 @@ void launch_fl_forward_cells(sx_handle *h, const CellsPlan &p) {
 }
 
 void launch_fl_forward_fft(sx_handle *h) {
-    TimedLaunch scope(h, "k_fl_forward");
+    TimedLaunch scope(h, "k_fl_forward", 8.0 * (double)h->N * h->V + (h->sp32 ? 4.0 : 8.0) * fl_count(h));      // read var_np1, write the ring spectra
     dim3 g((h->nz + FFT_FZC - 1) / FFT_FZC, h->v_cnt, h->nrings);
     switch (ilog2(h->uniform_L)) {
         case 4: launch_fwd<4>(h, g); break;

@@ -117,22 +117,23 @@ static void harm_launch_ks(sx_handle *h, HarmState *st, const HarmLaunch &a, int
 }
 
 // one launch: the radii [r0, r0 + n) of the call; tmp [KO, nz, n_r, V, nslots] column-major
+// bytes: the A traffic of the call so far, this launch's added (4 rows x b_zDim x (2 kcap + 1) per radius and variable)
 static bool harm_chunk(sx_handle *h, HarmState *st, const EvalGeom &g, const double *radii, int n_all, int r0, int n, int flags,
-                       const HarmLaunch &a, double *tmp) {
+                       const HarmLaunch &a, double *tmp, double &bytes) {
     std::vector<RadialPt> pts(n);
     for (int i = 0; i < n; i++) {
         RadialPt &e = pts[i];
         eval_radial_pt(g, radii[r0 + i], flags, e.wr, e.cell, e.kcap);
         e.orig = i;
         e.pad = 0;
-        st->last_bytes += 8.0 * 4.0 * a.Zb * (h->has_l ? 2 * e.kcap + 1 : 1) * h->V;
+        bytes += 8.0 * 4.0 * a.Zb * (h->has_l ? 2 * e.kcap + 1 : 1) * h->V;
     }
     // by cell (neighbouring workgroups then read the same 4 rows); within a cell the caller's order
     std::stable_sort(pts.begin(), pts.end(), [](const RadialPt &x, const RadialPt &y) { return x.cell < y.cell; });
     HIPCHK(hipMemcpyAsync(st->d_pts, pts.data(), sizeof(RadialPt) * n, hipMemcpyHostToDevice, h->stream));
     if (error_status()) return false;
     {
-        TimedLaunch scope(h, "k_harmonics");
+        TimedLaunch scope(h, "k_harmonics", bytes);
         if (a.Zb <= 16) harm_launch_ks<4>(h, st, a, n);
         else if (a.Zb <= 48) harm_launch_ks<12>(h, st, a, n);
         else harm_launch_ks<32>(h, st, a, n);
@@ -203,9 +204,9 @@ int sx_harmonics(sx_handle *h, const double *radii, int32_t n_r, const double *h
     a.vcls = cls->d_vcls;
     // the results of every launch are held back until all of them have succeeded: a failed call writes nothing to out
     std::vector<double> tmp(per_r * n_r);
-    st->last_bytes = 0;
+    double bytes = 0;
     for (int r0 = 0; r0 < n_r; r0 += chunk)
-        if (!harm_chunk(h, st, g, radii, n_r, r0, std::min(chunk, n_r - r0), flags, a, tmp.data())) return 1;
+        if (!harm_chunk(h, st, g, radii, n_r, r0, std::min(chunk, n_r - r0), flags, a, tmp.data(), bytes)) return 1;
     std::memcpy(out, tmp.data(), sizeof(double) * tmp.size());
     return error_status();
 }

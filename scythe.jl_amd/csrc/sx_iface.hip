@@ -980,7 +980,7 @@ int sx_iface_local(sx_handle *h, void *dev_send) {
     IfaceState *st = h ? (IfaceState *)h->iface_state : nullptr;
     if (!st || !dev_send) { set_error("sx_iface_local: invalid argument / not configured"); return 1; }
     {
-        TimedLaunch scope(h, "k_iface_local");
+        TimedLaunch scope(h, "k_iface_local", 0.0);
         dim3 g((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb);
 #define IFL_ARGS h->d_Btile, st->d_Y, (double *)dev_send, st->d_owner, st->d_soff, st->d_cw, st->d_cs, h->d_cls, st->d_meta, h->d_gl, h->d_gr, \
                  st->d_Lf, h->nbt, h->Zb, h->K2, h->C
@@ -996,7 +996,7 @@ int sx_iface_reduce(sx_handle *h, const void *dev_recv, void *dev_send) {
     IfaceState *st = h ? (IfaceState *)h->iface_state : nullptr;
     if (!st || !dev_recv || !dev_send) { set_error("sx_iface_reduce: invalid argument / not configured"); return 1; }
     {
-        TimedLaunch scope(h, "k_iface_reduce");
+        TimedLaunch scope(h, "k_iface_reduce", 0.0);
         const int ng = st->g1 - st->g0, RN = IF_R * st->n, RNp = (RN + 15) / 16 * 16;
         if (ng > 0) {
             const int nchunk = (h->K2 + 63) / 64;        // a block = 4 waves x 16 columns
@@ -1015,7 +1015,7 @@ int sx_iface_apply(sx_handle *h, const void *dev_recv) {
     IfaceState *st = h ? (IfaceState *)h->iface_state : nullptr;
     if (!st || !dev_recv) { set_error("sx_iface_apply: invalid argument / not configured"); return 1; }
     {
-        TimedLaunch scope(h, "k_iface_apply");
+        TimedLaunch scope(h, "k_iface_apply", 0.0);
         hipLaunchKernelGGL(k_iface_apply, dim3((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb), dim3(64), sizeof(double) * IF_E * h->nbt, h->stream, st->d_Y, (const double *)dev_recv,
                            h->d_A + (int64_t)h->cell0 * h->C, st->d_owner, st->d_soff, st->d_cw, st->d_cs, h->d_cls, st->d_meta, h->d_gl, h->d_gr,
                            st->d_Z, h->nbt, h->Zb, h->K2, h->C);

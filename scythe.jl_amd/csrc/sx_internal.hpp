@@ -204,7 +204,6 @@ struct DevBuf {         // owns one device array; reads as the pointer
     bool upload(const std::vector<T> &v, const char *err) { return upload(v.data(), v.size(), err); }
 };
 struct DiagState {      // what one of these entry points keeps with the handle: made on first use, deleted by sx_destroy
-    double last_bytes = 0;            // bytes the last call's kernel read (sx_kernel_bytes)
     virtual ~DiagState() = default;
 };
 enum { DIAG_EVAL, DIAG_HARM, DIAG_REDUCE, DIAG_SPEC, DIAG_PARCELS, DIAG_ELLIPTIC, DIAG_EXTREMA, DIAG_CROSSINGS, DIAG_DISTRIBUTION, DIAG_VORTEX, DIAG_STATS, DIAG_ANTIDERIVATIVE, DIAG_ISOSURFACE, DIAG_PROJECT, DIAG_REGRID, DIAG_DERIVE, DIAG_SCAN, DIAG_COUNT };   // sx_handle::diag, in the order sx_destroy deletes them (DIAG_SCAN, the table the field-program scans share, after all of them: sx_redprog.hpp)
@@ -373,6 +372,7 @@ struct Timer {
     const char *name;
     double ms = 0.0;
     int64_t calls = 0;
+    double bytes = 0;       // algorithmic bytes of the last launch (or entry-point call) under this name: sx_kernel_bytes
 };
 
 struct PendingEvent {
@@ -465,7 +465,6 @@ struct sx_handle {
     int part_P = 0;                           // 0: no tables
     int *d_part_meta = nullptr;
     double *d_part_tab = nullptr;
-    bool last_solve_part = false;             // the last launch_solve took k_solve_part (sx_kernel_bytes)
     std::unique_ptr<sx::DiagState> diag[sx::DIAG_COUNT];   // states of the diagnostics entry points, made on first use (sx_eval.hip ... sx_parcels.hip)
     double *d_CBT = nullptr;                  // CB transposed [nz][Zb] (sx_rz.hip)
     std::vector<sx::SplineClass> classes;     // host copies of the spline classes (d_cls indexes them)
@@ -473,7 +472,6 @@ struct sx_handle {
     int *d_mask_full = nullptr, *d_mask_eq = nullptr;   // per-variable bit masks of derivative slots to produce
     int mask_eq_bits = 0, mask_full_bits = 0;            // total number of (variable, slot) planes in each mask
     int mask_eq_val = 0, mask_full_val = 0, mask_node_val = 0;   // of which value-slot planes (always fp64)
-    bool last_mask_full = true;
     // node-space ("radial last") inverse for uniform rings: rings [0, R_in) keep the ring-wise path (their wavenumber
     // truncation depends on the ring), rings [R_in, nrings) are evaluated from node-space transforms inside the equation set
     int node_mode = 0, node_active = 0, R_in = 0, mask_node_bits = 0;
@@ -482,7 +480,7 @@ struct sx_handle {
     int *d_nkmax = nullptr, *d_mask_node = nullptr;
     int64_t *d_npstart = nullptr, *d_nphoff = nullptr;
     sx::ColJob *d_jobs_zinv_full = nullptr, *d_jobs_zinv_eq = nullptr, *d_jobs_zf = nullptr;
-    int njobs_zinv_full = 0, njobs_zinv_eq = 0, last_zinv_jobs = 0, last_zinv_rows = 0;
+    int njobs_zinv_full = 0, njobs_zinv_eq = 0;
     int ncls = 0;
     size_t dev_bytes = 0;
     std::vector<void *> allocs;
@@ -544,15 +542,18 @@ void launch_a2a_pack(sx_handle *h, double *buf, int unpack);
 void launch_halo_add(sx_handle *h, const double *recv);
 void launch_nan_check(sx_handle *h);
 void launch_max_abs(sx_handle *h, unsigned long long *d_out);
-// The bracket of one timed kernel launch (or of the launches one timer name covers): a launcher opens `TimedLaunch scope(h, "k_name");`
-// where its timed region starts and lets the scope end where the region ends, early returns included.  Construction looks the name up
-// (first use appends it: sx_get_timers lists names in that order) and, with timers on and the name not excluded by sx_timer_only,
-// records the begin event on h->stream as it is then.  Destruction checks the launch - a failed one goes to set_error as
+// The bracket of one timed kernel launch (or of the launches one timer name covers): a launcher opens
+// `TimedLaunch scope(h, "k_name", bytes);` where its timed region starts and lets the scope end where the region ends, early returns
+// included.  bytes: the algorithmic bytes of this launch, every array it touches counted once (DESIGN.md "Kernels and rooflines"),
+// stated by the launcher from the quantities it launches with; 0.0 where the kernel has no byte model.  Construction looks the name up
+// (first use appends it: sx_get_timers lists names in that order), stores the bytes under it - timers on or off, the name excluded by
+// sx_timer_only or not: sx_kernel_bytes answers from there - and, with timers on and the name not excluded, records the begin event
+// on h->stream as it is then.  Destruction checks the launch - a failed one goes to set_error as
 // "k_name: <hip error text>" - and records the scope's own end event on the stream the begin event went to.
 // Scopes do not nest: a launcher called inside its caller's scope (launch_solve_part, launch_solve_pcr, launch_semi_mfma) opens none.
 class TimedLaunch {
 public:
-    TimedLaunch(sx_handle *h, const char *name);
+    TimedLaunch(sx_handle *h, const char *name, double bytes);
     ~TimedLaunch();
     TimedLaunch(const TimedLaunch &) = delete;
     TimedLaunch &operator=(const TimedLaunch &) = delete;
@@ -562,7 +563,28 @@ private:
     hipStream_t stream = nullptr;
     hipEvent_t end = nullptr;      // null: this launch is not timed
 };
+// for an entry point whose call launches nothing (no variables, an empty set): the name, if it has a timer, reads `bytes` from now on
+void set_kernel_bytes(sx_handle *h, const char *name, double bytes);
 void timers_flush(sx_handle *h);
+// ---- the byte models' shared terms (w = 8: fp64) ----
+// bytes per point of a set of `bits` (variable, slot) planes of `physical` / G, `val` of them value planes: those are always fp64,
+// the derivative slots 4 bytes wide in the fp32-storage mode
+inline double plane_bytes(const sx_handle *h, int bits, int val) { return 8.0 * val + (h->f32 ? 4.0 : 8.0) * (bits - val); }
+// ... of the planes an inverse transform writes: every slot (tileTransform!) or the equation set's
+inline double out_plane_bytes(const sx_handle *h, bool full) {
+    return full ? plane_bytes(h, h->mask_full_bits, h->mask_full_val) : plane_bytes(h, h->mask_eq_bits, h->mask_eq_val);
+}
+int zinv_rows(const sx_handle *h, bool full);       // rows of Az that launch_zinv(h, full) fills (sx_kernels.hip)
+double az_count(const sx_handle *h, bool full);     // entries the azimuthal inverse that follows it reads: those rows of Az, or the tile's A rows
+// entries of what the forward azimuthal transform writes: the ring spectra, or with the forward pair that sums them into the nodes
+// the node spectra + the segments' edge partials
+inline double fl_count(const sx_handle *h) {
+    return h->cells.on ? (double)(h->nbt + 3 * (h->cells.segs - 1)) * h->V * h->nz * h->K2 : (double)h->nrings * h->V * h->nz * h->K2;
+}
+// node-space units actually transformed and read: cell c of the outer rings combines nodes c .. c + 3 and the first such cell is
+// R_in / 3, so nodes [R_in / 3, nbt) - 132 of 174 at the bench grid; the nodes below feed the ring-wise inner rings only
+inline double node_units(const sx_handle *h) { return (double)(h->nbt - h->R_in / MUBAR); }
+inline double node_points(const sx_handle *h) { return node_units(h) * (double)h->uniform_L * h->nz; }       // points of their transforms (NGu)
 void clear_error();
 int error_status();   // 1 if set_error has been called since the last clear_error
 void comm_release(sx_handle *h);
@@ -586,10 +608,6 @@ double wrap_lambda(double lam);
 // (count: its argument's name), in the order the header lists (sx_crossings.hip)
 bool scan_args_ok(const sx_handle *h, const char *who, const char *count, const char *noun, int n_terms, const double *coef, int n_levels,
                   int max_cross, const double *levels, int64_t n, double tol);
-double extrema_bytes(const sx_handle *h, bool refine);   // bytes of the last sx_extrema (k_extrema) / sx_extremum_refine (k_refine)
-double crossings_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_crossings: k_ray_profiles / k_crossings (sx_crossings.hip)
-double antiderivative_bytes(const sx_handle *h, bool vertical);   // bytes of the last sx_antiderivative along r (k_antiderivative_r) / z (k_antiderivative_z)
-double isosurface_bytes(const sx_handle *h, bool scan);   // bytes of the last sx_isosurface: k_column_profiles / k_isosurface (sx_isosurface.hip)
 int default_bzdim(int zDim);                   // b_zDim of a descriptor that leaves it 0 (sx_api.cpp)
 bool rz_fused(const sx_handle *h);
 void launch_rz_inverse(sx_handle *h, const int *d_mask);

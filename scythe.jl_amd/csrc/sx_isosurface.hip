@@ -232,30 +232,22 @@ void colprof_grid_args(const sx_handle *h, ColProfArgs &pa) {
     pa.cell_lo = h->cell0; pa.cell_hi = h->cell0 + h->ncells - 1; pa.xmin = h->xmin; pa.DX = h->DX;
 }
 
-void launch_column_profiles(sx_handle *h, const ColProfArgs &pa, int n_batches, int nv) {
-    {
-        TimedLaunch scope(h, "k_column_profiles");
-        if (h->has_l)
-            hipLaunchKernelGGL(k_column_profiles, dim3((unsigned)((pa.Zb + 15) / 16), (unsigned)n_batches, (unsigned)nv), dim3(64), colprof_lds(h->kDim),
-                               h->stream, pa);
-        else
-            hipLaunchKernelGGL(k_column_profiles_rz, grid1((int64_t)pa.n_cols * pa.nprof * pa.Zb, 256), dim3(256), 0, h->stream, pa);
-    }
+void launch_column_profiles(sx_handle *h, const ColProfArgs &pa, int n_batches, int nv, double bytes) {
+    TimedLaunch scope(h, "k_column_profiles", bytes);
+    if (h->has_l)
+        hipLaunchKernelGGL(k_column_profiles, dim3((unsigned)((pa.Zb + 15) / 16), (unsigned)n_batches, (unsigned)nv), dim3(64), colprof_lds(h->kDim),
+                           h->stream, pa);
+    else
+        hipLaunchKernelGGL(k_column_profiles_rz, grid1((int64_t)pa.n_cols * pa.nprof * pa.Zb, 256), dim3(256), 0, h->stream, pa);
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct IsoState : DiagState {            // last_bytes: k_column_profiles'
-    double scan_bytes = 0;              // k_isosurface's
+struct IsoState : DiagState {
     DevBuf<double> d_tab;               // CA^T of the classes | Dc^T | the stations, uploaded once per handle
     bool tab_ready = false;
     DevBuf<double> d_cols, d_P, d_out;  // d_out: height | carry | values
     DevBuf<int> d_idx, d_ri;            // order | batches;  dir | count | status
 };
-
-double isosurface_bytes(const sx_handle *h, bool scan) {
-    const IsoState *st = diag_state<IsoState>(h, DIAG_ISOSURFACE);
-    return !st ? 0.0 : scan ? st->scan_bytes : st->last_bytes;
-}
 
 // What the program asks of the two kernels, from the grid and the program alone
 struct IsoPlan {
@@ -423,10 +415,12 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     std::memcpy(pa.psr, pl.psr, sizeof(pa.psr));
     // the live A elements of the 4 node rows once per batch and variable (RZ: once per column and profile), the coordinates in, the profiles out
     const double live = h->has_l ? 2.0 * h->kDim + 1.0 : 1.0;
-    st->last_bytes = nprof == 0 ? 0.0
-                                : 8.0 * (4.0 * Zb * live * (h->has_l ? (double)batches.size() * pl.nv : (double)n_cols * nprof) + (double)ncc * n_cols +
-                                         (double)Zb * nprof * n_cols);
-    if (nprof > 0) launch_column_profiles(h, pa, (int)batches.size(), pl.nv);
+    if (nprof > 0)
+        launch_column_profiles(h, pa, (int)batches.size(), pl.nv,
+                               8.0 * (4.0 * Zb * live * (h->has_l ? (double)batches.size() * pl.nv : (double)n_cols * nprof) + (double)ncc * n_cols +
+                                      (double)Zb * nprof * n_cols));
+    else
+        set_kernel_bytes(h, "k_column_profiles", 0.0);
 
     IsoArgs ia;
     std::memset(&ia, 0, sizeof(ia));
@@ -443,9 +437,8 @@ int sx_isosurface(sx_handle *h, int32_t n_terms, const double *coef, const int32
     ia.n_cols = (int)n_cols; ia.nprof = nprof; ia.Zb = Zb; ia.nz = nz; ia.ncls = ncls; ia.n_ser = pl.n_ser; ia.n_levels = n_levels;
     ia.max_iter = max_iter <= 0 ? 60 : max_iter; ia.max_cross = max_cross; ia.n_carry = n_carry;
     // the profiles in; heights, directions, carried outputs, counts, status and the station values out
-    st->scan_bytes = 8.0 * (double)Zb * nprof * n_cols + (12.0 + 8.0 * n_carry) * (double)n_hgt + 4.0 * ((double)n_levels + 1.0) * n_cols + 8.0 * (double)n_val;
     {
-        TimedLaunch scope(h, "k_isosurface");
+        TimedLaunch scope(h, "k_isosurface", 8.0 * (double)Zb * nprof * n_cols + (12.0 + 8.0 * n_carry) * (double)n_hgt + 4.0 * ((double)n_levels + 1.0) * n_cols + 8.0 * (double)n_val);
         hipLaunchKernelGGL(k_isosurface, dim3((unsigned)n_cols), dim3(64), iso_lds(pl.n_ser, nz), h->stream, ia);
     }
 

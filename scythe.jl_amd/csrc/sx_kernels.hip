@@ -969,17 +969,24 @@ void sbw_phases_dump() {
 }
 #endif
 
+// Rows of Az the vertical inverse fills.  Inside sx_advance (the equation-set mask) on uniform rings the node-space units invert
+// vertically inside their FFT kernel (sx_fft.hip, FUSE): Az is then needed only for the nodes the ring-wise inner rings read (cells
+// [0, R_in / 3) -> nodes 0 .. R_in / 3 + 2)
+int zinv_rows(const sx_handle *h, bool full) {
+    return (!full && h->node_mode && fft_fused_zinv(h)) ? (h->R_in > 0 ? std::min(h->nbt, h->R_in / MUBAR + 3) : 0) : h->nbt;
+}
+
+// entries of Az the azimuthal inverse reads after launch_zinv(h, full); without a vertical it reads the tile's A rows
+double az_count(const sx_handle *h, bool full) {
+    return h->has_z ? (double)zinv_rows(h, full) * (full ? h->njobs_zinv_full : h->njobs_zinv_eq) * h->nz * h->K2 : (double)h->nbt * h->C;
+}
+
 void launch_zinv(sx_handle *h, bool full) {
     if (!h->has_z || rz_fused(h)) return;          // RZ: the vertical inverse is part of k_rz_inverse (sx_rz.hip)
-    TimedLaunch scope(h, "k_zinv");
     const int njobs = full ? h->njobs_zinv_full : h->njobs_zinv_eq;
-    h->last_zinv_jobs = njobs;
-    if (njobs > 0) {
-        // inside sx_advance on uniform rings the node-space units invert vertically inside their FFT kernel (sx_fft.hip, FUSE):
-        // Az is then needed only for the nodes the ring-wise inner rings read (cells [0, R_in / 3) -> nodes 0 .. R_in / 3 + 2)
-        const int rows = (!full && h->node_mode && fft_fused_zinv(h)) ? (h->R_in > 0 ? std::min(h->nbt, h->R_in / MUBAR + 3) : 0) : h->nbt;
-        h->last_zinv_rows = rows;
-        if (rows == 0) return;
+    const int rows = zinv_rows(h, full);
+    TimedLaunch scope(h, "k_zinv", 8.0 * ((double)h->nbt * h->C) * rows / h->nbt + (h->sp32 ? 4.0 : 8.0) * az_count(h, full));   // read the rows' A, write Az
+    if (njobs > 0 && rows > 0) {
         const ZinvPlan p = plan_zinv(h->geom, h->nz, h->K2, h->sp32, h->sw);
         dim3 g(p.grid_x, njobs, rows);
         const ColJob *jobs = full ? h->d_jobs_zinv_full : h->d_jobs_zinv_eq;
@@ -1006,7 +1013,6 @@ void launch_zinv(sx_handle *h, bool full) {
 
 void launch_rl_inverse(sx_handle *h, bool full) {
     const int *mask = full ? h->d_mask_full : h->d_mask_eq;
-    h->last_mask_full = full;
     h->node_active = (!full && h->node_mode);
     if (rz_fused(h)) { launch_rz_inverse(h, mask); return; }
     if (h->node_active) {            // sx_advance on uniform rings: node-space transforms + ring-wise inner rings only
@@ -1016,7 +1022,8 @@ void launch_rl_inverse(sx_handle *h, bool full) {
     }
     if (fft_path_ok(h)) { launch_rl_inverse_fft(h, mask); return; }
     if (dft_mfma_ok(h)) { launch_rl_inverse_dft(h, mask); return; }
-    TimedLaunch scope(h, "k_rl_inverse");
+    // write the requested physical planes, read Az
+    TimedLaunch scope(h, "k_rl_inverse", (double)h->N * out_plane_bytes(h, full) + (h->sp32 ? 4.0 : 8.0) * az_count(h, full));
     const int cstride = (h->kmax_max + 1) | 1;
     const size_t lds = sizeof(double) * 2 * ZC * cstride;
     if (lds > 64 * 1024) {
@@ -1045,7 +1052,7 @@ void launch_fl_forward(sx_handle *h) {
     if (const CellsPlan cp = cells_plan(h); cp.on) { launch_fl_forward_cells(h, cp); return; }
     if (fft_path_ok(h)) { launch_fl_forward_fft(h); return; }
     if (dft_mfma_ok(h)) { launch_fl_forward_dft(h); return; }
-    TimedLaunch scope(h, "k_fl_forward");
+    TimedLaunch scope(h, "k_fl_forward", 8.0 * (double)h->N * h->V + (h->sp32 ? 4.0 : 8.0) * fl_count(h));      // read var_np1, write the spectra
     const int xstride = h->L_max | 1;
     const size_t lds = sizeof(double) * ZC * xstride;
     if (lds > 64 * 1024) {       // the scalar kernel stages a whole ring; longer rings need the matrix-core DFT (lengths that are multiples of 4)
@@ -1058,7 +1065,7 @@ void launch_fl_forward(sx_handle *h) {
 }
 
 static void launch_nodes_z(sx_handle *h, const CellsPlan &p) {
-    TimedLaunch scope(h, "k_sbz");
+    TimedLaunch scope(h, "k_sbz", (h->sp32 ? 4.0 : 8.0) * fl_count(h) + 8.0 * ((double)h->nbt * h->C));      // read the spectra, write the tile's B rows
     dim3 g((h->K2 + p.bw - 1) / p.bw, h->v_cnt, p.zsegs);
     const int64_t plane = (int64_t)h->V * h->nz * h->K2, flo = (int64_t)h->v_lo * h->nz * h->K2, blo = (int64_t)h->v_lo * h->Zb * h->K2;
 #define NODES_Z(...) hipLaunchKernelGGL((__VA_ARGS__), g, dim3(p.zthreads), 0, h->stream, h->d_Fn + flo, h->d_Fn + (int64_t)h->nbt * plane + flo, \
@@ -1077,7 +1084,9 @@ void launch_sb(sx_handle *h) {
     const SbPlan p = plan_sb(h->geom, h->nz, h->Zb, h->K2, h->v_cnt, h->ncells, h->sp32, h->sw);
     if (p.kernel == SbKernel::rz_forward) { launch_rz_forward(h); return; }
     if (p.kernel == SbKernel::refused) { set_error("launch_sb: fp32 ring spectra (storage_f32 = 2) need the matrix-core sliding-window kernel"); return; }
-    TimedLaunch scope(h, h->has_z ? "k_sbz" : "k_sb");       // k_sbz: fused with the vertical forward transform
+    // k_sbz (fused with the vertical forward transform): read the spectra, write the tile's B rows; k_sb: the same without a vertical
+    const double fl = fl_count(h), bz = (double)h->nbt * h->V * h->nz * h->K2;
+    TimedLaunch scope(h, h->has_z ? "k_sbz" : "k_sb", h->has_z ? (h->sp32 ? 4.0 : 8.0) * fl + 8.0 * ((double)h->nbt * h->C) : 8.0 * (fl + bz));
     if (p.kernel == SbKernel::sb) {
         const int64_t plane = (int64_t)h->V * h->nz * h->K2;
         dim3 g((unsigned)((plane + 255) / 256), h->nbt);
@@ -1122,7 +1131,6 @@ void launch_sb(sx_handle *h) {
 
 
 void launch_solve(sx_handle *h) {
-    TimedLaunch scope(h, "k_solve");
     dim3 g((h->K2 > 1 ? (h->K2 / 2 - 1 + 63) / 64 : 0) + 1, h->V * h->Zb);
     // few right-hand sides (the R grid's one column, RZ grids, small RL patches): LDS-staged parallel cyclic reduction (sx_pcr.hip)
     // instead of one wave's serial recurrence per 64 columns
@@ -1130,8 +1138,9 @@ void launch_solve(sx_handle *h) {
     const int ngroups = contiguous ? h->v_cnt * h->Zb : h->V * h->Zb;
     const int64_t ncols = (int64_t)ngroups * (h->K2 > 1 ? h->K2 - 1 : 1);
     // contiguous, non-periodic, enough columns to fill the chip: row partitions in one workgroup, y on chip (k_solve_part, sx_iface.hip)
-    h->last_solve_part = h->part_P && plan_solve_part(h->b_rDim, 0, contiguous, ncols, h->sw) == h->part_P;
-    if (h->last_solve_part) {
+    const bool part = h->part_P && plan_solve_part(h->b_rDim, 0, contiguous, ncols, h->sw) == h->part_P;
+    TimedLaunch scope(h, "k_solve", 8.0 * (part ? 2.0 : 4.0) * ((double)h->b_rDim * h->C));      // read B, write y, read y, write A; k_solve_part: B in, A out
+    if (part) {
         const int64_t clo = (int64_t)h->v_lo * h->Zb * h->K2;
         launch_solve_part(h, h->d_Bsrc + clo, h->d_A + clo, h->v_lo * h->Zb, ngroups);
         return;
@@ -1158,7 +1167,7 @@ void launch_solve(sx_handle *h) {
 // transposed solve: my column groups [g0, g1), right-hand sides from the all-to-all receive buffer, solution rows into
 // the all-to-all send buffer (both [tile][row][my columns]; a row shared by two tiles is summed on input, duplicated on output)
 void launch_solve_a2a(sx_handle *h, const double *recv, double *send) {
-    TimedLaunch scope(h, "k_solve");
+    TimedLaunch scope(h, "k_solve", 8.0 * 4.0 * ((double)h->b_rDim * h->C));      // read B, write y, read y, write A
     const int ng = h->a2a_g1 - h->a2a_g0;
     if (ng > 0 && pcr_wanted(h, (int64_t)ng * (h->K2 > 1 ? h->K2 - 1 : 1))) {
         launch_solve_pcr(h, false, recv, h->d_a2a_offA, h->d_a2a_offB, send, h->d_a2a_offA, h->d_a2a_offB, h->a2a_g0, ng, 0);
@@ -1176,7 +1185,7 @@ void launch_solve_a2a(sx_handle *h, const double *recv, double *send) {
 }
 
 void launch_a2a_pack(sx_handle *h, double *buf, int unpack) {
-    TimedLaunch scope(h, unpack ? "k_a2a_unpack" : "k_a2a_pack");
+    TimedLaunch scope(h, unpack ? "k_a2a_unpack" : "k_a2a_pack", 0.0);
     dim3 g((unsigned)((h->C + 255) / 256), h->nbt);
     const double *arr = unpack ? h->d_A : h->d_Btile;
     hipLaunchKernelGGL(k_a2a_pack, g, dim3(256), 0, h->stream, arr, buf, h->d_a2a_owner, h->d_a2a_soff, h->d_a2a_cw, h->d_a2a_cs,
@@ -1184,7 +1193,7 @@ void launch_a2a_pack(sx_handle *h, double *buf, int unpack) {
 }
 
 void launch_halo_add(sx_handle *h, const double *recv) {
-    TimedLaunch scope(h, "k_halo_add");
+    TimedLaunch scope(h, "k_halo_add", 0.0);
     const int64_t n = 3 * h->C;
     hipLaunchKernelGGL(k_halo_add, grid1(n, 256), dim3(256), 0, h->stream, h->d_Btile, recv, n);
 }

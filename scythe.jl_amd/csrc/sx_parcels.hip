@@ -193,7 +193,7 @@ static bool parcel_install(sx_handle *h, ParcelState *st, int64_t n, const int v
     HIPCHK(hipStreamSynchronize(h->stream));      // a step of the set that goes may still be in flight
     st->d_f.swap(d_f); st->d_i.swap(d_i); st->n = n;      // the set that goes is freed on return
     for (int m = 0; m < 3; m++) { st->var[m] = var[m]; st->cls[m] = cls[m]; }
-    st->last_bytes = 0;
+    set_kernel_bytes(h, "k_parcels", 0.0);      // the new set has not moved yet
     return true;
 }
 
@@ -263,9 +263,8 @@ int sx_parcels_advance(sx_handle *h, double dt) {
     a.wlo = h->xmin; a.wlen = h->xmax - h->xmin;
     a.wrap = !h->has_l && st->var[0] != 0 && h->bcl[st->var[0] - 1] == SX_BC_PERIODIC && h->bcr[st->var[0] - 1] == SX_BC_PERIODIC;
     // 4 node rows x every column but the padding block, once per velocity variable and parcel (frozen parcels read nothing: an upper bound)
-    st->last_bytes = 8.0 * 4.0 * (double)a.Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv * (double)st->n;
     {
-        TimedLaunch scope(h, "k_parcels");
+        TimedLaunch scope(h, "k_parcels", 8.0 * 4.0 * (double)a.Zb * (h->has_l ? 2 * h->kDim + 1 : 1) * nv * (double)st->n);
         hipLaunchKernelGGL(k_parcels, dim3((unsigned)st->n), dim3(parcel_threads(h)), parcel_lds(h), h->stream, a);
     }
     return error_status();

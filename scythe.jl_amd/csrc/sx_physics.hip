@@ -996,13 +996,20 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
     // launch_inverse_and_physics; the history rotation happens once, in part 1 before and in part 2 after)
     if (h->eq != SX_EQ_NONE && t == 1 && part != 2) h->rot = 0;
     PhysArgsT<ST> a = phys_args<ST>(h, t);
+    // Algorithmic bytes: read the requested slots, E_nm1, E_nm2; write E_n, var_np1.  The shallow-water sets keep no tendency history
+    // for their diagnostic w (-3 planes; inside sx_advance its plane is not stored either)
+    const double N = (double)h->N, V = h->V, eq_planes = plane_bytes(h, h->mask_eq_bits, h->mask_eq_val);
+    const bool diag_w = h->eq == SX_EQ_ONEWAY_SW_SLAB || h->eq == SX_EQ_TWOWAY_SW_SLAB || h->eq == SX_EQ_ONEWAY_SW_HRBL;
+    const double pointwise_bytes = N * (eq_planes + 8.0 * (4.0 * V + (diag_w ? -3.0 : 0.0)));
     if (h->eq == SX_EQ_ONEWAY_SW_HRBL && mfma_levels(h->nz)) {      // any ring table: the ring-wise kernel reads physical slots
         // rings [0, R_in): ring-wise physical slots; rings [R_in, nrings): node-space transforms (node_mode only)
         const int64_t split = (h->node_mode && h->node_active) ? (int64_t)h->R_in * h->uniform_L : h->Nh;
         if (h->d_G) a.G = planes_of<ST>(h->d_G, h->V, h->NG);
         a.phi = h->d_phi; a.NG = h->NG; a.L = h->uniform_L; a.nrings = h->nrings;
+        const double fin = (double)h->R_in / h->nrings;        // split < Nh: the fraction of rings on the ring-wise path
         if (split > 0 && part != 2) {
-            TimedLaunch scope(h, split < h->Nh ? "k_phys_hrbl_inner" : "k_phys_hrbl");
+            TimedLaunch scope(h, split < h->Nh ? "k_phys_hrbl_inner" : "k_phys_hrbl",
+                              split < h->Nh ? N * fin * (eq_planes + 8.0 * (4.0 * V - 3.0)) : pointwise_bytes);
             a.col0 = 0; a.col1 = split;
 #define RING_LAUNCH(NZ_, CPB_)                                                                                                     \
             do {                                                                                                                      \
@@ -1015,7 +1022,8 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
 #undef RING_LAUNCH
         }
         if (split < h->Nh && part != 1) {
-            TimedLaunch scope(h, "k_phys_hrbl");
+            // node transforms (read once) + history + outputs
+            TimedLaunch scope(h, "k_phys_hrbl", node_points(h) * plane_bytes(h, h->mask_node_bits, h->mask_node_val) + N * (1.0 - fin) * 8.0 * (4.0 * V - 3.0));
             a.col0 = split; a.col1 = h->Nh;
             const int ncell = (h->nrings - h->R_in) / MUBAR;         // R_in is a multiple of 3 (sx_create)
 #ifdef SX_PHASES
@@ -1032,20 +1040,20 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
 #undef CELL_LAUNCH
         }
     } else if (h->eq == SX_EQ_ONEWAY_SW_HRBL) {
-        TimedLaunch scope(h, "k_phys_hrbl");
+        TimedLaunch scope(h, "k_phys_hrbl", pointwise_bytes);
         const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
         const int bs = cpb * h->nz;
         const size_t lds = sizeof(double) * 5 * cpb * h->nz;
         hipLaunchKernelGGL(k_phys_hrbl<ST>, grid1(h->Nh, cpb), dim3(bs), lds, h->stream, a, cpb);
     } else if (h->eq == SX_EQ_RAINFALL_TEST) {
-        TimedLaunch scope(h, "k_phys_rain");
+        TimedLaunch scope(h, "k_phys_rain", N * (eq_planes + 8.0 * (4.0 * V + (h->semi ? V : 0.0))));      // as k_phys_pointwise, + impdot
         hipLaunchKernelGGL(k_phys_rain<ST>, grid1(h->N, 256), dim3(256), 0, h->stream, a);
     } else {
-        TimedLaunch scope(h, "k_phys_pointwise");
+        TimedLaunch scope(h, "k_phys_pointwise", pointwise_bytes);
         hipLaunchKernelGGL(k_phys_pointwise<ST>, grid1(h->N, 256), dim3(256), 0, h->stream, a);
     }
     if (h->semi && h->eq != SX_EQ_NONE) {
-        TimedLaunch scope(h, "k_semiimplicit");
+        TimedLaunch scope(h, "k_semiimplicit", 8.0 * N * 2.0 * 5.0);
         SemiArgs s;
         s.np1 = h->d_np1;
         s.In = h->d_I[h->rot % 3]; s.I1 = h->d_I[(h->rot + 1) % 3]; s.I2 = h->d_I[(h->rot + 2) % 3];
@@ -1058,7 +1066,7 @@ static void launch_physics_t(sx_handle *h, int t, int part) {
         else hipLaunchKernelGGL(k_semiimplicit, dim3((unsigned)sp.wgs), dim3(sp.threads), (size_t)sp.lds, h->stream, s, sp.cpb);
     }
     if (h->eq == SX_EQ_RAINFALL_TEST) {        // after the explicit and the semi-implicit step (src/testModels.jl:572-580)
-        TimedLaunch scope(h, "k_condensation");
+        TimedLaunch scope(h, "k_condensation", 8.0 * N * (6.0 + 3.0));      // read s, xi, mu, mu_c, mu_r, qss of var_np1; write s, mu, mu_c
         const int cpb = h->nz >= 256 ? 1 : 256 / h->nz;
         const size_t lds = sizeof(int) * 2 * cpb * (1 + h->nz);
         hipLaunchKernelGGL(k_condensation, grid1(h->Nh, cpb), dim3(cpb * h->nz), lds, h->stream, h->d_np1, h->d_ref, h->N, h->nz, cpb);
@@ -1085,7 +1093,6 @@ void launch_inverse_and_physics(sx_handle *h, int t) {
         launch_physics(h, t);
         return;
     }
-    h->last_mask_full = false;
     h->node_active = 1;
     if (!h->stream2) {
         HIPCHK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(RED_T) void k_project(Planes<ST> P, int V, int64_t 
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-using ProjectState = CompanionWrite;      // last_bytes: k_project's
+using ProjectState = CompanionWrite;
 
 // what sx_project and sx_project_check refuse of the pointers
 static bool proj_pointers_ok(const char *who, int n_terms, const double *coef, bool need_coef, const int32_t *terms, int n_out, const int32_t *var_dst) {
@@ -140,9 +140,8 @@ int sx_project(sx_handle *src, int32_t source, int32_t n_terms, const double *co
     if (source == SX_REDUCE_PHYSICAL) flush_diag(src);
     HIPCHK(hipStreamSynchronize(dst->stream));      // the destination's own work on var_np1, B and A is complete before another stream writes them
     if (error_status()) return 1;
-    st->last_bytes = red_bytes(src, source, planes, n_planes) + 8.0 * n_out * (double)src->N;
     {
-        TimedLaunch scope(src, "k_project");
+        TimedLaunch scope(src, "k_project", red_bytes(src, source, planes, n_planes) + 8.0 * n_out * (double)src->N);
         scan_dispatch(src, source, [&](auto st_t, auto, auto P) {      // W = 2 where N is even (above); no RINGS form
             auto launch = [&](auto width) {
                 constexpr int W = decltype(width)::value;

@@ -235,7 +235,7 @@ inline unsigned scan_flat_blocks(const sx_handle *h, int W = 1) { return (unsign
 
 // ---- what sx_project and sx_derive share: a kernel on the source's stream writes the var_np1 planes of a companion handle, whose own
 // forward chain then runs on its stream
-struct CompanionWrite : DiagState {   // last_bytes: the writing kernel's
+struct CompanionWrite : DiagState {
     hipEvent_t done = nullptr;        // recorded on the source's stream behind the kernel; the destination's stream waits on it
     ~CompanionWrite() override { if (done) hipEventDestroy(done); }
 };

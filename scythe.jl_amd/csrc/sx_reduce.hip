@@ -228,10 +228,8 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
 
     const size_t n_res = kind == SX_REDUCE_AZIMUTH ? (size_t)h->nrings * h->nz * n_out : (size_t)n_out;
     if (!st->d_part.grow((size_t)sg->n_items * n_out * h->nz, "sx_reduce") || !st->d_out.grow(n_res, "sx_reduce")) return 1;
-    st->last_bytes = red_bytes(h, source, planes, n_planes);
-
     {
-        TimedLaunch scope(h, "k_reduce");
+        TimedLaunch scope(h, "k_reduce", red_bytes(h, source, planes, n_planes));
         scan_dispatch(h, source, [&](auto st_t, auto rings, auto P) {
             constexpr bool RINGS = decltype(rings)::value;
             hipLaunchKernelGGL((k_reduce<decltype(st_t), RINGS>), dim3(RINGS ? (unsigned)sg->n_items : scan_flat_blocks(h)), dim3(RED_T), 0, h->stream, P,
@@ -239,7 +237,7 @@ int sx_reduce(sx_handle *h, int32_t kind, int32_t source, int32_t n_terms, const
         });
     }
     {
-        TimedLaunch scope(h, "k_reduce_final");
+        TimedLaunch scope(h, "k_reduce_final", 0.0);
         if (kind == SX_REDUCE_AZIMUTH)
             hipLaunchKernelGGL(k_reduce_mean, grid1((int64_t)n_res, 256), dim3(256), 0, h->stream, st->d_part, sg->d_first, h->d_L, h->nrings, h->nz,
                                n_out, st->d_out);

@@ -116,7 +116,7 @@ struct RegridTable {                      // E^T of every class of the source at
     int nz = 0, Kp = 0, Mp = 0;
     DevBuf<double> d_ET;
 };
-struct RegridState : DiagState {          // kept with the SOURCE handle; last_bytes: k_regrid_levels'
+struct RegridState : DiagState {          // kept with the SOURCE handle
     hipEvent_t done = nullptr;            // recorded on the source's stream behind stage 2; the destination's stream waits on it
     std::vector<std::unique_ptr<RegridTable>> tables;
     DevBuf<double> d_cols, d_P;
@@ -338,7 +338,7 @@ int sx_regrid(sx_handle *src, sx_handle *dst, const double *centre, const int32_
 
     const int ncls_used = src->has_z ? (int)k->vert.size() : 1;
     // the profiles in (once per destination variable), E of the classes, the column table, the var_np1 planes out
-    st->last_bytes = 8.0 * ((double)Vd * Zb * n_in + (double)ncls_used * Zb * dst->nz + (double)Vd * dst->N) + 4.0 * n_cols;
+    const double levels_bytes = 8.0 * ((double)Vd * Zb * n_in + (double)ncls_used * Zb * dst->nz + (double)Vd * dst->N) + 4.0 * n_cols;
     const bool mfma = dst->has_l && dst->has_z;
     for (int g = 0; g < ngroups; g++) {
         const int p0 = g * RED_PLANES, np = std::min<int>((int)distinct.size() - p0, RED_PLANES);
@@ -353,7 +353,7 @@ int sx_regrid(sx_handle *src, sx_handle *dst, const double *centre, const int32_
                 for (int kd = 0; kd < ISO_KINDS; kd++) pa.v[p].prof[kd] = kd == 0 ? p : -1;
                 pa.pvar[p] = (uint8_t)distinct[p0 + p]; pa.psr[p] = 0;
             }
-            launch_column_profiles(src, pa, (int)batches.size(), np);
+            launch_column_profiles(src, pa, (int)batches.size(), np, 0.0);
         }
         RegridArgs ra;
         std::memset(&ra, 0, sizeof(ra));
@@ -361,7 +361,7 @@ int sx_regrid(sx_handle *src, sx_handle *dst, const double *centre, const int32_
         ra.N = dst->N; ra.n_cols = (int)n_cols; ra.nprof = np; ra.Zb = Zb; ra.Kp = tab->Kp; ra.Mp = tab->Mp; ra.nz = dst->nz;
         ra.nrv = g_first[g + 1] - g_first[g];
         {
-            TimedLaunch scope(src, "k_regrid_levels");
+            TimedLaunch scope(src, "k_regrid_levels", levels_bytes);
             if (mfma)
                 hipLaunchKernelGGL(k_regrid_levels, dim3((unsigned)((n_cols + 15) / 16), (unsigned)ra.nrv), dim3(64), sizeof(double) * tab->Kp * RG_CS, src->stream, ra);
             else

@@ -413,7 +413,8 @@ void launch_semi_mfma(sx_handle *h, const SemiArgs &a) {
 bool rz_fused(const sx_handle *h) { return h->sw.rz_fused && h->geom == SX_GEOM_RZ && !h->sp32; }
 
 void launch_rz_inverse(sx_handle *h, const int *d_mask) {
-    TimedLaunch scope(h, "k_rz_inverse");
+    // read the tile's A rows, write the requested physical planes
+    TimedLaunch scope(h, "k_rz_inverse", 8.0 * ((double)h->nbt * h->C) + (double)h->N * out_plane_bytes(h, d_mask == h->d_mask_full));
     const RzInvPlan p = plan_rz_inverse(h->nz, h->Zb, h->ncells, h->V, h->f32, h->sw);      // SX_RZ_INV=0 (A/B): the ring-tile form
     const dim3 g(p.gx, p.gy, p.gz);
     const size_t lds = (size_t)p.lds;
@@ -436,7 +437,7 @@ void launch_rz_inverse(sx_handle *h, const int *d_mask) {
 }
 
 void launch_rz_forward(sx_handle *h) {
-    TimedLaunch scope(h, "k_rz_forward");
+    TimedLaunch scope(h, "k_rz_forward", 8.0 * (double)h->N * h->V + 8.0 * ((double)h->nbt * h->C));      // read var_np1, write the tile's B rows
     const RzFwdPlan p = plan_rz_forward(h->nz, h->Zb, h->ncells, h->v_cnt);
     hipLaunchKernelGGL(k_rz_forward, dim3(p.gx, p.gy, p.gz), dim3(256), (size_t)p.lds, h->stream, h->d_np1 + (int64_t)h->v_lo * h->N,
                        h->d_Btile + (int64_t)h->v_lo * h->Zb, h->d_phi, h->d_wq, h->d_CBT, h->ncells, h->nbt, h->V, h->nz, h->Zb, h->N, h->C, p.mt_per_wg);

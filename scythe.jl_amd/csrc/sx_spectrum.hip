@@ -278,18 +278,18 @@ int sx_spectrum(sx_handle *h, int32_t kind, int32_t n_pairs, const int32_t *pair
     if (!st->d_out.grow(n_res, "sx_spectrum") || (domain && !st->d_part.grow(n_ring, "sx_spectrum"))) return 1;
     // the A traffic: every distinct (var, slot) plane reads 4 rows x b_zDim x (2 kmax + 1) doubles per ring
     const double n_planes = (double)std::count(plane.begin(), plane.end(), true);
-    st->last_bytes = 0;
-    for (int i = 0; i < h->nrings; i++) st->last_bytes += n_planes * 8.0 * 4.0 * a.Zb * (h->has_l ? 2 * st->kcap[i] + 1 : 1);
+    double a_bytes = 0;
+    for (int i = 0; i < h->nrings; i++) a_bytes += n_planes * 8.0 * 4.0 * a.Zb * (h->has_l ? 2 * st->kcap[i] + 1 : 1);
 
     {
-        TimedLaunch scope(h, "k_spectrum");
+        TimedLaunch scope(h, "k_spectrum", a_bytes);
         if (a.Zb <= 16) spec_launch_ks<4>(h, st, a, domain);
         else if (a.Zb <= 48) spec_launch_ks<12>(h, st, a, domain);
         else spec_launch_ks<32>(h, st, a, domain);
     }
     if (domain) {
         {
-            TimedLaunch scope(h, "k_spectrum_final");
+            TimedLaunch scope(h, "k_spectrum_final", 0.0);
             hipLaunchKernelGGL(k_spectrum_final, dim3((unsigned)((K + 15) / 16), (unsigned)n_pairs), dim3(SPEC_T), 0, h->stream, st->d_part,
                                st->d_wring, h->nrings, K, st->d_out);
         }

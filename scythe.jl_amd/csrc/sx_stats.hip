@@ -98,7 +98,7 @@ __global__ void k_stats_fill(double *__restrict__ acc, int64_t N, int n_out, Sta
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------
-struct StatsState : DiagState {     // last_bytes: k_stats'.  The work list: the handle's scan table (sx_redprog.hpp)
+struct StatsState : DiagState {     // The work list: the handle's scan table (sx_redprog.hpp)
     int parts = 1;                  // workgroups per piece (stat_install)
     // the set
     DevBuf<double> d_acc;           // [n_out][2][N]
@@ -181,7 +181,7 @@ static bool stat_install(sx_handle *h, const char *who, int source, int n_terms,
         st->prog.op[o] = (int8_t)st->op[o]; st->prog.thr[o] = st->thr[o];
     }
     st->clear_counters();
-    st->last_bytes = 0;
+    set_kernel_bytes(h, "k_stats", 0.0);      // the new set has taken no sample
     if (raw) {
         HIPCHK(hipMemcpyAsync(st->d_acc, raw, sizeof(double) * n_acc, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));      // raw is borrowed for the call only
@@ -199,7 +199,7 @@ static void stat_drop(sx_handle *h) {
     st->n_out = st->n_terms = st->n_planes = 0;
     st->coef.clear(); st->terms.clear();
     st->clear_counters();
-    st->last_bytes = 0;
+    set_kernel_bytes(h, "k_stats", 0.0);
 }
 
 }  // namespace sx
@@ -240,9 +240,8 @@ int sx_stats_accumulate(sx_handle *h, double time, double weight) {
     if (!st || st->n_out == 0) return 0;
     const ScanGrid *sg = scan_grid(h, "sx_stats", false);      // there since the set was installed
     if (!sg) return 1;
-    st->last_bytes = red_bytes(h, st->source, st->planes, st->n_planes) + 32.0 * st->n_out * (double)h->N;
     {
-        TimedLaunch scope(h, "k_stats");
+        TimedLaunch scope(h, "k_stats", red_bytes(h, st->source, st->planes, st->n_planes) + 32.0 * st->n_out * (double)h->N);
         scan_dispatch(h, st->source, [&](auto st_t, auto rings, auto P) {
             constexpr bool RINGS = decltype(rings)::value;
             auto launch = [&](auto width) {

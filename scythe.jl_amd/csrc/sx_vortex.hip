@@ -358,7 +358,9 @@ int sx_vortex_harmonics(sx_handle *h, const double centre[2], const double *moti
         if (stat[i] == 0) live.push_back(VortexCircle{radii[i], i, 0});
     const size_t n_res = (size_t)plan.nout * n_rho * nz * 2 * K;
     std::vector<double> res(n_res, std::nan(""));      // held back until the call has succeeded: a failed call writes nothing to out
-    st->last_bytes = 8.0 * 4.0 * (double)Zb * (2 * h->kDim + 1) * plan.nsrc * (double)n_az * (double)live.size();
+    // every live circle of the call: n_az points x distinct source variables x 4 rows x b_zDim x (2 kDim + 1) of A
+    const double rings_bytes = 8.0 * 4.0 * (double)Zb * (2 * h->kDim + 1) * plan.nsrc * (double)n_az * (double)live.size();
+    if (live.empty()) set_kernel_bytes(h, "k_vortex_rings", 0.0);
     if (!live.empty()) {
         const size_t per_circle = (size_t)nchunks * nent;
         const int batch = (int)std::max<size_t>(1, std::min<size_t>({live.size(), VORTEX_SCRATCH / (per_circle * sizeof(double2)), (size_t)32768}));
@@ -395,11 +397,11 @@ int sx_vortex_harmonics(sx_handle *h, const double centre[2], const double *moti
             const unsigned nb = (unsigned)std::min<size_t>(batch, live.size() - c0);
             ra.circ = fa.circ = st->d_circ + c0;
             {
-                TimedLaunch scope(h, "k_vortex_rings");
+                TimedLaunch scope(h, "k_vortex_rings", rings_bytes);
                 hipLaunchKernelGGL(k_vortex_rings, dim3((unsigned)nchunks, nb), dim3(VORTEX_T), lds_r, h->stream, ra);
             }
             {
-                TimedLaunch scope(h, "k_vortex_finish");
+                TimedLaunch scope(h, "k_vortex_finish", 0.0);
                 hipLaunchKernelGGL(k_vortex_finish, dim3(nb, (unsigned)plan.nout), dim3(VORTEX_T), lds_f, h->stream, fa);
             }
         }
